@@ -13,7 +13,11 @@ process is one rank; started plainly (`python bench.py --gpus N`, no WORLD_SIZE)
 child processes, before this process imports torch or touches a GPU -- and relays rank 0's line and the exit code
 (launch_ranks).  `--rehearse-launch` runs the same launch + band exchange on the CPU over gloo (no render, `value` null).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with "roofline" and "cpu_baseline".
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline fields (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration); `--dump-outputs DIR` also writes the last
+timed step's framebuffer as .npy.  Everything else -- the timed frame's parity against the oracle, the step taken apart, the
+per-kernel one-stream pass and "roofline", the host-API timing, "cpu_baseline" and the other BASELINE configurations
+(`workloads`) -- is measured only with `--full`.
 
 Roofline.  The dominant kernel is k_trace on queued (bounce >= 1) rays.  On the headline scene the
 whole tree lives in LDS, so the kernel is bound by vector-instruction issue, not by HBM: `bound` names that pipe,
@@ -186,6 +190,9 @@ EXTRA_WORKLOADS = {
 }
 SCALING_WORKLOAD = "shirley_4k_spp256_d8"  # BASELINE.json configs[4]: what the >= 6x target at 8 GPUs is quoted on
 METRIC = "Msamples/s (WxHxspp) + achieved HBM GB/s vs roofline; per-pixel Linf vs CPU ref"
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20  # a framebuffer larger than the limit: this many whole pixels of it, chosen with DUMP_SAMPLE_SEED
+DUMP_SAMPLE_SEED = 20
 
 
 class Mods:
@@ -618,15 +625,41 @@ def roofline_block(args, job, world, counts, kernel_ms, launches, trace_ms_total
     return roofline
 
 
+def dump_outputs(job, out_dir):
+    """`--dump-outputs DIR`, rank 0, after the timed steps: what the timed path hands its caller -- the post-gamma framebuffer of
+    the last timed step, (H, W, 3) binary64 -- as DIR/rgb.npy.  A framebuffer larger than DUMP_LIMIT_BYTES is written as a fixed
+    sample instead: DUMP_SAMPLE_PIXELS whole pixels chosen with DUMP_SAMPLE_SEED (rgb_sample.npy, N x 3) and their flat indices
+    y * W + x (rgb_sample_pixel.npy).  Returns {name: shape}."""
+    import numpy as np
+    job.sync()
+    rgb = job.rgb.cpu().numpy()
+    if rgb.nbytes <= DUMP_LIMIT_BYTES:
+        arrays = {"rgb": rgb}
+    else:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        pix = np.sort(rng.choice(job.h * job.w, min(DUMP_SAMPLE_PIXELS, job.h * job.w), replace=False))
+        arrays = {"rgb_sample": rgb.reshape(-1, 3)[pix], "rgb_sample_pixel": pix.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="shirley_1080p_spp64_d8", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the timed frame's parity, the step taken apart, the one-stream per-kernel pass and the roofline, "
+                         "the host-API timing, the CPU baseline and its parity, and the `workloads` block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's framebuffer to DIR/<name>.npy (binary64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the `workloads` block (N = 1: the other single-GPU BASELINE configurations in a child process; N > 1: config 5 across the ranks)")
+                    help="--full: skip the `workloads` block (N = 1: the other single-GPU BASELINE configurations in a child process; N > 1: config 5 across the ranks)")
     ap.add_argument("--workloads-timeout", type=float, default=240.0, help="N = 1: seconds the child process that times the other configurations may take")
     ap.add_argument("--extras-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=None)
@@ -638,6 +671,8 @@ def main():
                          "synthetic bands, breakdown, CPU baseline, config-5 block, the JSON line) with value null -- checks that "
                          "`bench.py --gpus N` can start its own ranks and what its line will carry")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.extras_child:
         return extras_child(args)
@@ -682,12 +717,37 @@ def main():
     job = Job(m, args.workload, rank, world, dev, local_dev, backend, passes_per_batch=args.passes_per_batch, rehearse=rehearse)
     scene_name, w, h, spp, depth = job.scene_name, job.w, job.h, job.spp, job.depth
     elapsed = job.timed(args.steps, args.warmup)
-    timed_parity = job.frame_parity()       # rank 0: whole pixels of the timed, gathered frame against the oracle
+    dumped = None
+    if args.dump_outputs and rank == 0 and not rehearse:
+        dumped = dump_outputs(job, args.dump_outputs)
     rehearsal_ok = None
     if rehearse and rank == 0:
         import numpy as np
         img = D.ungather(job.bg.gathered.numpy(), h, world)
         rehearsal_ok = bool((img[:, 0, 0] == np.arange(h) + 0.25 * (job.n_frames - 1)).all())
+
+    out = None
+    if rank == 0:
+        samples = w * h * spp
+        ms_per_step = elapsed / args.steps * 1e3
+        value = samples * args.steps / elapsed * 1e-6
+        out = {
+            "metric": METRIC, "value": None if rehearse else value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": None if rehearse else ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64", "data": "none (launch rehearsal over gloo: no GPU used, nothing rendered, nothing measured)" if rehearse else "synthetic",
+            "config": {"workload": args.workload, "scene": scene_name, "width": w, "height": h, "spp": spp,
+                       "max_bounces": depth, "samples_per_step": samples,
+                       "sharding": f"{world} rank(s), interleaved {D.BAND_ROWS}-row bands, 1 gather/step" if world > 1 else "1 rank"},
+        }
+        if args.dump_outputs:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                              "note": "launch rehearsal: nothing was rendered" if rehearse else "framebuffer of the last timed step, binary64"}
+        if rehearse:
+            out["rehearsal"] = {"bands_arrived_in_place": rehearsal_ok}
+    if not args.full:
+        return finish(out, rank, world, dist, rehearse and rehearsal_ok is False)
+
+    timed_parity = job.frame_parity()       # rank 0: whole pixels of the timed, gathered frame against the oracle
     bd = job.breakdown()
 
     counts = kernel_ms = launches = None
@@ -713,22 +773,9 @@ def main():
         counts = dict(zip(keys, [int(v) for v in cvec[:5].tolist()]))
         trace_ms_total, trace_launches = float(cvec[5]), float(cvec[6])  # one step, one stream
 
-    out = None
     if rank == 0:
-        samples = w * h * spp
-        ms_per_step = elapsed / args.steps * 1e3
-        value = samples * args.steps / elapsed * 1e-6
-        out = {
-            "metric": METRIC, "value": None if rehearse else value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": None if rehearse else ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "none (launch rehearsal over gloo: no GPU used, nothing rendered, nothing measured)" if rehearse else "synthetic",
-            "config": {"workload": args.workload, "scene": scene_name, "width": w, "height": h, "spp": spp,
-                       "max_bounces": depth, "samples_per_step": samples,
-                       "sharding": f"{world} rank(s), interleaved {D.BAND_ROWS}-row bands, 1 gather/step" if world > 1 else "1 rank"},
-            "collective": collective_block(m, job, backend, bd),
-        }
+        out["collective"] = collective_block(m, job, backend, bd)
         if rehearse:
-            out["rehearsal"] = {"bands_arrived_in_place": rehearsal_ok}
             out["roofline"] = None
         else:
             sstats = job.sstats
@@ -815,9 +862,14 @@ def main():
         torch.cuda.empty_cache()
         P.lib().ptx_release_workspaces()
         out["workloads"] = run_extras_in_child(args.workloads_timeout)
+    finish(out, rank, world, dist, rehearse and rehearsal_ok is False)
+
+
+def finish(out, rank, world, dist, rehearsal_failed):
+    """Rank 0 prints the one JSON line; every rank leaves the process group."""
     if rank == 0:
         print(json.dumps(out), flush=True)
-    if rehearse and rank == 0 and rehearsal_ok is False:
+    if rehearsal_failed:
         raise SystemExit("band exchange rehearsal failed")
     if world > 1:
         dist.barrier()

@@ -72,7 +72,7 @@ def test_bench_starts_its_own_ranks(world, workload):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--rehearse-launch",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--rehearse-launch", "--full",
                         "--steps", "2", "--warmup", "1", "--workload", workload],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -108,4 +108,32 @@ def test_self_launched_ranks_refuse_to_run_without_a_gpu():
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
     assert "no CPU fallback" in (r.stderr + r.stdout)
+    assert _json_lines(r.stdout) == []
+
+
+def test_plain_run_prints_the_headline_only():
+    """Without --full the line carries the headline fields and nothing that takes runs of its own: no CPU leg, no parity, no
+    step taken apart, no `workloads`.  Walked over the self-launched ranks of a rehearsal, so it runs without a GPU."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rehearse-launch",
+                        "--steps", "3", "--warmup", "1", "--workload", "shirley_600x300_spp32_d8"],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["config"]["samples_per_step"] == 600 * 300 * 32
+    assert line["rehearsal"]["bands_arrived_in_place"] is True
+    assert not set(line) & {"cpu_baseline", "parity", "collective", "roofline", "workloads", "host_api", "kernel_ms_per_step"}
+
+
+@pytest.mark.parametrize("flags", [["--steps", "0"], ["--warmup", "-1"]])
+def test_bench_refuses_a_step_count_it_cannot_time(flags):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
     assert _json_lines(r.stdout) == []

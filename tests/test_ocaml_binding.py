@@ -104,24 +104,67 @@ def test_files_and_symbols_agree():
         assert text.startswith("--- a/") and "+++ b/" in text, p
 
 
+def _preimages(patch_text):
+    """{path: text} of the files a unified diff applies to, rebuilt from the diff alone: every hunk's context and removed lines
+    at the line its header names, filler lines (which match nothing) in between, the file ending where the last hunk ends."""
+    files, lines, path, i = {}, patch_text.splitlines(), None, 0
+    while i < len(lines):
+        if lines[i].startswith("--- a/"):
+            path = lines[i][len("--- a/"):].split("\t")[0]
+            files[path] = []
+            i += 2
+            continue
+        hdr = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,(\d+))? @@", lines[i])
+        if hdr:
+            start, count, new_count = int(hdr.group(1)), int(hdr.group(2) or 1), int(hdr.group(3) or 1)
+            old = files[path]
+            while len(old) < start - 1:
+                old.append(f"(* line {len(old) + 1} of {path}, not in the patch *)")
+            i += 1
+            body, added = [], 0
+            while (len(body) < count or added < new_count) and i < len(lines):
+                assert lines[i][:1] in (" ", "-", "+", ""), f"{path}: hunk at line {start} ends early: {lines[i]!r}"
+                if lines[i][:1] != "-":
+                    added += 1
+                if lines[i][:1] != "+":
+                    body.append(lines[i][1:])
+                i += 1
+            assert (len(body), added) == (count, new_count), f"{path}: hunk at line {start} is shorter than its header says"
+            assert len(old) == start - 1, f"{path}: hunk at line {start} overlaps the one before it"
+            old.extend(body)
+            continue
+        i += 1
+    return {p: "\n".join(v) + "\n" for p, v in files.items()}
+
+
 def test_patches_apply_to_the_reference(tmp_path):
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("no reference checkout on this machine (the GPU box has none)")
-    for p in sorted(os.listdir(os.path.join(B, "patches"))):
-        text = open(os.path.join(B, "patches", p)).read()
-        for rel in re.findall(r"^--- a/(\S+)", text, flags=re.M):
-            dst = tmp_path / rel
-            dst.parent.mkdir(parents=True, exist_ok=True)
-            if not dst.exists():
-                dst.write_bytes(open(os.path.join(ref, rel), "rb").read())
-        subprocess.check_call(["patch", "-p1", "-s", "-i", os.path.join(B, "patches", p)], cwd=tmp_path)
-    assert "Make_gpu" in (tmp_path / "render_command/src/render_command.ml").read_text()
-    assert "Make_gpu" in (tmp_path / "progressive-photon-map/src/progressive_photon_map.ml").read_text()
+    """Each patch applies exactly (no fuzz, no offset) to the preimage its own hunks record, and what it adds is there
+    afterwards.  PT_REFERENCE_DIR naming a checkout of the reference applies them to its files as well."""
+    ref = os.environ.get("PT_REFERENCE_DIR")
+    trees = [tmp_path / "from_patches"] + ([tmp_path / "reference"] if ref else [])
+    for tree in trees:
+        for p in sorted(os.listdir(os.path.join(B, "patches"))):
+            text = open(os.path.join(B, "patches", p)).read()
+            pre = _preimages(text)
+            assert pre, p
+            for rel, body in pre.items():
+                dst = tree / rel
+                dst.parent.mkdir(parents=True, exist_ok=True)
+                if not dst.exists():
+                    dst.write_bytes(open(os.path.join(ref, rel), "rb").read() if tree.name == "reference" else body.encode())
+            r = subprocess.run(["patch", "-p1", "--fuzz=0", "-i", os.path.join(B, "patches", p)], cwd=tree, capture_output=True, text=True)
+            assert r.returncode == 0, r.stdout + r.stderr
+            assert tree.name == "reference" or "offset" not in r.stdout, r.stdout
+        _check_patched_tree(tree)
+
+
+def _check_patched_tree(tree):
+    assert "Make_gpu" in (tree / "render_command/src/render_command.ml").read_text()
+    assert "Make_gpu" in (tree / "progressive-photon-map/src/progressive_photon_map.ml").read_text()
     for exe in ("cornell-box", "ganesha", "shirley_spheres"):
-        text = (tmp_path / exe / "bin" / "main.ml").read_text()
+        text = (tree / exe / "bin" / "main.ml").read_text()
         assert "gpus" in text and "Ptx.scene_create" in text, exe
-        assert " ptx" in (tmp_path / exe / "bin" / "dune").read_text(), exe
+        assert " ptx" in (tree / exe / "bin" / "dune").read_text(), exe
     # only what the reference's interfaces export is used: Material.dielectric is not in material.mli
     for p in sorted(os.listdir(os.path.join(B, "patches"))):
         added = [l for l in open(os.path.join(B, "patches", p)).read().splitlines() if l.startswith("+")]

@@ -14,7 +14,7 @@ set -e
 export TMPDIR=/tmp
 wl=$1; out=$2
 mkdir -p $out
-cmd="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-workloads --workload $wl"
+cmd="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-workloads --workload $wl"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ktrace -- $cmd > $out/bench_ktrace.log 2>&1
 export PTX_STREAMS=1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ktrace1 -- $cmd > $out/bench_ktrace1.log 2>&1
