@@ -73,8 +73,11 @@ HIT, MISS, UNSURE = 1, 0, -1
 
 
 # ---------------------------------------------------------------- scene descriptions
-def make_desc(abi, spheres=(), tris=(), leaf_kind=1, cutoff=4, mats=None, num_bins=32):
-    """spheres: (x, y, z, r, mat); tris: (a, b, c, mat) with 3-vectors.  Returns (desc, keepalive)."""
+def make_desc(abi, spheres=(), tris=(), leaf_kind=1, cutoff=4, mats=None, num_bins=32, tri_uv=None, materials=None,
+              textures=None, background=None):
+    """spheres: (x, y, z, r, mat); tris: (a, b, c, mat) with 3-vectors.  Returns (desc, keepalive).
+    Optional (the defaults build the same description as before): tri_uv, 6 numbers per triangle (ta, tb, tc); materials,
+    (kind, texture, index, emit3) each; textures, (kind, width, height, even3, odd3) each; background, "sky" or "black"."""
     keep = []
     d = abi.SceneDesc()
     sp = np.array([s[:4] for s in spheres], dtype=np.float64).reshape(-1, 4)
@@ -89,7 +92,8 @@ def make_desc(abi, spheres=(), tris=(), leaf_kind=1, cutoff=4, mats=None, num_bi
         v = np.array([p for t in tris for p in t[:3]], dtype=np.float64).reshape(-1, 3)
         vc = [np.ascontiguousarray(v[:, k]) for k in range(3)]
         idx = np.arange(3 * len(tris), dtype=np.int32)
-        uv = np.tile(np.array([0.0, 0.0, 1.0, 0.0, 1.0, 1.0]), len(tris))
+        uv = np.tile(np.array([0.0, 0.0, 1.0, 0.0, 1.0, 1.0]), len(tris)) if tri_uv is None else \
+            np.ascontiguousarray(tri_uv, dtype=np.float64).reshape(6 * len(tris))
         tm = np.array([t[3] for t in tris], dtype=np.int32)
         keep += vc + [idx, uv, tm]
         d.n_vertices, d.n_triangles = len(v), len(tris)
@@ -108,10 +112,20 @@ def make_desc(abi, spheres=(), tris=(), leaf_kind=1, cutoff=4, mats=None, num_bi
     M[0].kind, M[0].texture = abi.PTX_MAT_LAMBERTIAN, 1
     M[1].kind, M[1].texture = abi.PTX_MAT_METAL, 0
     M[2].kind, M[2].index = abi.PTX_MAT_DIELECTRIC, 1.5
+    if materials is not None:
+        M = (abi.Material * len(materials))()
+        for m, (kind, tex, index, emit) in zip(M, materials):
+            m.kind, m.texture, m.index = kind, tex, index
+            m.emit[:] = list(emit)
+    if textures is not None:
+        T = (abi.Texture * len(textures))()
+        for t, (kind, w, h, even, odd) in zip(T, textures):
+            t.kind, t.width, t.height = kind, w, h
+            t.even[:], t.odd[:] = list(even), list(odd)
     keep += [M, T]
-    d.n_materials, d.materials, d.n_textures, d.textures = 3, M, 2, T
+    d.n_materials, d.materials, d.n_textures, d.textures = len(M), M, len(T), T
     d.camera.lower_left_x, d.camera.lower_left_y, d.camera.view_x, d.camera.view_y = -1.0, -0.5, 2.0, 1.0
-    d.background.kind = abi.PTX_BG_SKY
+    d.background.kind = abi.PTX_BG_BLACK if background == "black" else abi.PTX_BG_SKY
     d.background.horizon[:] = [1.0, 1.0, 1.0]
     d.background.zenith[:] = [0.5, 0.7, 1.0]
     d.leaf_kind, d.length_cutoff, d.num_bins = leaf_kind, cutoff, num_bins
