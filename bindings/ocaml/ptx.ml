@@ -170,6 +170,15 @@ external ppm_render_flat
   -> unit
   = "ptx_ml_ppm_render_stub"
 
+external render_progressive_flat
+  :  scene
+  -> floatarray (* width, height, samples_per_pixel, max_bounces, passes_per_update, target_rel_err *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* image, W*H*3 *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* per-pixel error, W*H*3, or empty *)
+  -> (int -> float -> bool -> bool) (* passes done, rel_err, last update; true stops the render *)
+  -> int
+  = "ptx_ml_render_progressive_stub"
+
 module FA = Stdlib.Float.Array
 
 (* the tables are interned structurally: a 150 k-triangle mesh with one material gets one row, not 150 k *)
@@ -329,6 +338,38 @@ let mesh_bbox (mesh : mesh) =
 (* Integrator.create ... |> Integrator.render ~update_progress, on [gpus] GPUs of this node *)
 let render ?(gpus = 1) scene ~width ~height ~samples_per_pixel ~max_bounces ~image ~update_progress =
   render_flat scene width height samples_per_pixel max_bounces gpus image update_progress
+;;
+
+(* [render] as a sequence of updates: after every [passes_per_update] passes and after the last, [image] holds the frame filmed
+   from the passes done so far, [err] (if given) its per-pixel standard error, and [on_update] runs on the calling thread;
+   it returns true to stop, and the render also stops at the first update whose [rel_err] is at most [target_rel_err] > 0.
+   The result is the number of passes in [image]; run to [samples_per_pixel] passes, [image] is what [render] gives.  An
+   exception raised by [on_update] stops the render and is raised again once the library has returned. *)
+let render_progressive
+  ?(target_rel_err = 0.)
+  ?err
+  scene
+  ~width
+  ~height
+  ~samples_per_pixel
+  ~max_bounces
+  ~passes_per_update
+  ~image
+  ~on_update
+  =
+  let err = Option.value err ~default:(Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0) in
+  let params =
+    FA.of_list
+      [ Float.of_int width
+      ; Float.of_int height
+      ; Float.of_int samples_per_pixel
+      ; Float.of_int max_bounces
+      ; Float.of_int passes_per_update
+      ; target_rel_err
+      ]
+  in
+  render_progressive_flat scene params image err (fun passes_done rel_err last ->
+    on_update ~passes_done ~rel_err ~last)
 ;;
 
 (* [f ()] with [image] pinned; a host that renders many frames into one Bimage (an animation loop around Render_command's run)

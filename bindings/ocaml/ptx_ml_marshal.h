@@ -174,4 +174,24 @@ static int32_t ptx_ml_ppm_render(ptx_scene* s, const double* params6, const doub
   return ptx_ppm_render(s, &p, lights, n_lights, img_sum, NULL, iteration_cb, user);
 }
 
+/* Integrator.render as a sequence of updates (ptx_render_progressive, want_error on): params6 = width, height,
+ * samples_per_pixel, max_bounces, passes_per_update, target_rel_err.  image (W*H*3) holds the image of the last update, err
+ * (nullable) its per-pixel standard error, *passes_done its passes; on_update runs after every update. */
+static __attribute__((unused)) int32_t ptx_ml_render_progressive(ptx_scene* s, const double* params6, double* image, double* err, int32_t* passes_done,
+                                                                 ptx_update_fn on_update, void* user) {
+  if (!params6) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params6[0];
+  p.height = (int32_t)params6[1];
+  p.samples_per_pixel = (int32_t)params6[2];
+  p.max_bounces = (int32_t)params6[3];
+  ptx_progressive_params pp;
+  memset(&pp, 0, sizeof pp);
+  pp.passes_per_update = (int32_t)params6[4];
+  pp.want_error = 1;
+  pp.target_rel_err = params6[5];
+  return ptx_render_progressive(s, &p, &pp, image, err, passes_done, NULL, on_update, user);
+}
+
 #endif /* PTX_ML_MARSHAL_H */

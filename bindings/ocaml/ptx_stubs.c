@@ -367,3 +367,70 @@ CAMLprim value ptx_ml_ppm_render_stub(value handle, value params, value lights, 
   if (rc != 0) caml_failwith(ptx_last_error());
   CAMLreturn(Val_unit);
 }
+
+/* the update callback: the library has already filled the caller's Bigarrays (image, err) when it calls */
+typedef struct ptx_ml_update_cb {
+  ptx_ml_cb cb;
+  int32_t samples_per_pixel; /* N: the update of N passes is the last */
+  int stop;                  /* what the closure returned */
+} ptx_ml_update_cb;
+
+/* runs with the runtime lock held */
+static void ptx_ml_call_on_update(ptx_ml_update_cb* u, int32_t passes_done, double rel_err) {
+  CAMLparam0();
+  CAMLlocal2(boxed_rel_err, r);
+  boxed_rel_err = caml_copy_double(rel_err);
+  r = caml_callback3_exn(*u->cb.closure, Val_long(passes_done), boxed_rel_err, Val_int(passes_done >= u->samples_per_pixel));
+  if (Is_exception_result(r)) {
+    *u->cb.exn = Extract_exception(r);
+    u->cb.raised = 1;
+  } else {
+    u->stop = Int_val(r) != 0;
+  }
+  CAMLreturn0;
+}
+
+static int32_t ptx_ml_on_update(void* user, int32_t passes_done, double rel_err, const double* rgb, const double* err) {
+  ptx_ml_update_cb* u = (ptx_ml_update_cb*)user;
+  (void)rgb;
+  (void)err;
+  if (u->cb.raised) return 1;
+  caml_acquire_runtime_system(); /* the render runs with the lock released */
+  ptx_ml_call_on_update(u, passes_done, rel_err);
+  caml_release_runtime_system();
+  return (u->cb.raised || u->stop) ? 1 : 0; /* a raise stops the render: no callbacks after it */
+}
+
+/* external render_progressive_flat : scene -> floatarray -> image -> err -> (int -> float -> bool -> bool) -> int
+ *   = "ptx_ml_render_progressive_stub"
+ * (scene, [width; height; samples_per_pixel; max_bounces; passes_per_update; target_rel_err], image (W*H*3), err (W*H*3 or
+ * empty), on_update passes_done rel_err last -> stop) -> passes done.  The exception of a callback that raised is raised here,
+ * after the library has returned (and has drained everything it queued). */
+CAMLprim value ptx_ml_render_progressive_stub(value handle, value params, value image, value err, value on_update) {
+  CAMLparam5(handle, params, image, err, on_update);
+  CAMLlocal1(exn);
+  if (floatarray_length(params) != 6) caml_invalid_argument("Ptx.render_progressive: params needs 6 floats");
+  double p6[6];
+  memcpy(p6, floatarray_data(params), sizeof p6);
+  const intnat w = (intnat)p6[0], h = (intnat)p6[1];
+  if (w <= 0 || h <= 0 || Caml_ba_array_val(image)->dim[0] != w * h * 3)
+    caml_invalid_argument("Ptx.render_progressive: image must hold width * height * 3 floats");
+  const intnat n_err = Caml_ba_array_val(err)->dim[0];
+  if (n_err != 0 && n_err != w * h * 3) caml_invalid_argument("Ptx.render_progressive: err must be empty or hold width * height * 3 floats");
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_progressive: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_progressive: scene already destroyed");
+  double* out = (double*)Caml_ba_data_val(image); /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  double* err_out = n_err ? (double*)Caml_ba_data_val(err) : NULL;
+  exn = Val_unit;
+  ptx_ml_update_cb cb = {{&on_update, &exn, 0}, (int32_t)p6[2], 0};
+  int32_t passes_done = 0;
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_progressive(s, p6, out, err_out, &passes_done, ptx_ml_on_update, &cb);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (cb.cb.raised) caml_raise(exn);
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_long(passes_done));
+}

@@ -308,6 +308,49 @@ int32_t ptx_film_resolve_banded_queue(int32_t device, int32_t width, int32_t hei
                                       const double* d_gathered, int32_t n_ranks, int32_t band_rows, int32_t pad_rows,
                                       double* d_rgb_out, void* stream);
 
+/* ---- progressive rendering ----
+ * The sampler offset of a sample depends only on (x, y, pass, N) (integrator.ml:98), and the raw sums add the passes in order,
+ * so a frame rendered as consecutive pass slices into the same sums is bit for bit the frame rendered at once. */
+
+/* Passes [pass_first, pass_first + pass_count) of the frame `params` describes -- params->samples_per_pixel is the frame's
+ * TOTAL N, which fixes the sampler offsets -- ADDED to this rank's raw sums at d_raw_inout (never zeroed: the caller zeroes
+ * them before the first slice).  d_sq_inout (DEVICE, nullable, same layout) receives the sums of the squared per-sample
+ * contributions in the same pass order (s = s + c * c), for ptx_pixel_error_device.  Bands, `stream` and PTX_RENDER_ASYNC as
+ * in ptx_render_raw_device; ptx_render_raw_device is the range [0, N) with zeroing.  PTX_ERR_ARG for a range outside
+ * [0, N) or pass_count < 1. */
+int32_t ptx_render_passes_device(ptx_scene* scene, const ptx_render_params* params, int32_t pass_first, int32_t pass_count,
+                                 double* d_raw_inout, double* d_sq_inout, void* stream, ptx_stats* stats);
+
+/* Per-pixel, per-channel standard error of the pixel's sample mean after k = passes_done passes, from the DEVICE sums S1
+ * (d_raw) and S2 (d_sq) of `rows` x `width` pixels: se = sqrt(max(0, S2 - S1 * S1 / k) / (k (k - 1))) for k >= 2, +inf for
+ * k < 2 -- linear radiance, before the film and the gamma.  d_err_out (DEVICE, nullable) receives se, 3 per pixel;
+ * *rel_err_out (HOST, nullable) the frame summary sqrt(sum se^2) / sqrt(sum (S1 / k)^2), 0 when both sums are 0, +inf for
+ * k < 2, reduced in a fixed order (the same sums give the same bits on every run).  se is the estimate for INDEPENDENT samples;
+ * the sampler is a low-discrepancy sequence, so it usually OVERESTIMATES the error of the rendered mean.  Waits for `stream`. */
+int32_t ptx_pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t passes_done, const double* d_raw,
+                               const double* d_sq, double* d_err_out, double* rel_err_out, void* stream);
+
+typedef struct ptx_progressive_params {
+  int32_t passes_per_update; /* K >= 1: an update after every K passes, and after the last */
+  int32_t want_error;        /* 1: keep the square sums and compute rel_err (and err_out) at every update */
+  double target_rel_err;     /* > 0 (needs want_error): stop at the first update with rel_err <= this; 0 = never */
+} ptx_progressive_params;
+
+/* Called on the CALLING thread after every update with the passes done so far (k), the frame's rel_err (NaN without
+ * want_error), the image filmed from k passes (rgb_out) and its per-pixel error (err_out, or NULL).  Non-zero stops the render. */
+typedef int32_t (*ptx_update_fn)(void* user, int32_t passes_done, double rel_err, const double* rgb, const double* err);
+
+/* ptx_render as a sequence of updates, on ONE GPU (params->n_gpus > 1: PTX_ERR_ARG).  After every passes_per_update passes and
+ * after the last, the running sums are filmed with spp = k (ptx_film_resolve_device), the image is copied into rgb_out (HOST,
+ * W*H*3; a pinned image takes one DMA), err into err_out (HOST, nullable, needs want_error), and on_update (nullable) is
+ * called.  It stops when the callback returns non-zero, when rel_err <= target_rel_err > 0, or after N passes.  On return
+ * rgb_out holds the image handed to the last callback, *passes_done_out (nullable) its k, stats->samples = W*H*k, and nothing
+ * the call queued is still running (also on every error).  Run to N passes, rgb_out is ptx_render's image bit for bit.  The
+ * film and the copy of update j overlap the bounces of the next slice, so an early stop discards at most one slice of work. */
+int32_t ptx_render_progressive(ptx_scene* scene, const ptx_render_params* params, const ptx_progressive_params* progressive,
+                               double* rgb_out, double* err_out, int32_t* passes_done_out, ptx_stats* stats,
+                               ptx_update_fn on_update, void* user);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

@@ -34,10 +34,12 @@ EXPORTS = (
     "ptx_film_resolve_device", "ptx_trace_samples", "ptx_intersect_rays", "ptx_scene_tree", "ptx_lds_sample",
     "ptx_math_eval", "ptx_ppm_render", "ptx_debug_first_scatter", "ptx_render_multi", "ptx_scene_replicate",
     "ptx_film_resolve_banded_device", "ptx_film_resolve_banded_queue", "ptx_release_workspaces",
-    "ptx_image_pin", "ptx_image_unpin",
+    "ptx_image_pin", "ptx_image_unpin", "ptx_render_passes_device", "ptx_pixel_error_device", "ptx_render_progressive",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
+# ptx_update_fn: (user, passes_done, rel_err, rgb, err) -> non-zero stops the render
+UPDATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p)
 
 
 def lib():
@@ -80,6 +82,12 @@ def lib():
     L.ptx_release_workspaces.restype = None
     L.ptx_image_pin.argtypes = [C.c_void_p, dp, C.c_int64]
     L.ptx_image_unpin.argtypes = [C.c_void_p]
+    L.ptx_render_passes_device.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
+    L.ptx_pixel_error_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         dp, C.c_void_p]
+    L.ptx_render_progressive.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.ProgressiveParams), dp, dp,
+                                         ip, C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
     L.ptx_trace_samples.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int64, ip, ip, ip, dp,
                                     C.POINTER(abi.Stats)]
     L.ptx_intersect_rays.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp, ip, C.POINTER(abi.Stats)]
@@ -206,6 +214,57 @@ class Scene:
                                            C.c_void_p(stream) if stream else None, C.byref(st)))
         return stats_dict(st)
 
+    def render_passes_device(self, params, pass_first, pass_count, d_raw_ptr, d_sq_ptr=None, stream=None):
+        """ptx_render_passes_device: passes [pass_first, pass_first + pass_count) of the frame of params.samples_per_pixel
+        passes ADDED to this rank's raw sums in DEVICE memory (never zeroed), and their squares to d_sq_ptr if given."""
+        st = abi.Stats()
+        _check(lib().ptx_render_passes_device(self._h, C.byref(params), int(pass_first), int(pass_count), C.c_void_p(d_raw_ptr),
+                                              C.c_void_p(d_sq_ptr) if d_sq_ptr else None,
+                                              C.c_void_p(stream) if stream else None, C.byref(st)))
+        return stats_dict(st)
+
+    def render_progressive(self, width, height, samples_per_pixel, max_bounces, passes_per_update, on_update=None,
+                           target_rel_err=0.0, want_error=True, out=None, err_out=None, **kw):
+        """ptx_render_progressive: the frame as a sequence of updates, one after every `passes_per_update` passes and one after
+        the last.  on_update(passes_done, rel_err, rgb, err) is called after each with the (H, W, 3) image filmed from the
+        passes done so far and its per-pixel standard error (None without want_error); a truthy return stops the render, and
+        so does rel_err <= target_rel_err when the target is > 0.  An exception raised by on_update stops the render and is
+        raised again here.  Returns (rgb, err, passes_done, stats); rgb is the image of the last update."""
+        if int(passes_per_update) < 1:
+            raise ValueError("passes_per_update must be >= 1")
+        if not float(target_rel_err) >= 0.0:
+            raise ValueError("target_rel_err must be >= 0")
+        if (float(target_rel_err) > 0.0 or err_out is not None) and not want_error:
+            raise ValueError("target_rel_err and err_out need want_error")
+        if kw.get("n_gpus", 0) > 1:
+            raise ValueError("progressive rendering runs on one GPU")
+        out = _image_arg(out, width, height, "out")
+        err_out = _image_arg(err_out, width, height, "err_out") if want_error else None
+        p = render_params(width, height, samples_per_pixel, max_bounces, **kw)
+        pp = abi.ProgressiveParams()
+        pp.passes_per_update, pp.want_error, pp.target_rel_err = int(passes_per_update), int(bool(want_error)), float(target_rel_err)
+        raised = []
+
+        def trampoline(user, passes_done, rel_err, rgb, err):
+            if raised:
+                return 1
+            try:
+                return 1 if on_update(passes_done, rel_err, out, err_out) else 0
+            except BaseException as e:  # noqa: BLE001 -- carried across the C frames, raised again below
+                raised.append(e)
+                return 1
+
+        cb = UPDATE_FN(trampoline) if on_update is not None else None
+        done = C.c_int32(0)
+        st = abi.Stats()
+        rc = lib().ptx_render_progressive(self._h, C.byref(p), C.byref(pp), _dp(out),
+                                          _dp(err_out) if err_out is not None else None, C.byref(done), C.byref(st),
+                                          C.cast(cb, C.c_void_p) if cb else None, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return out, err_out, done.value, stats_dict(st)
+
     def trace_samples(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes, count_work=False):
         xs = np.ascontiguousarray(xs, dtype=np.int32)
         ys = np.ascontiguousarray(ys, dtype=np.int32)
@@ -244,6 +303,24 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def _image_arg(a, width, height, name):
+    if a is None:
+        return np.zeros((height, width, 3))
+    if a.shape != (height, width, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{name} must be a C-contiguous float64 array of shape (height, width, 3)")
+    return a
+
+
+def pixel_error_device(device, width, rows, passes_done, d_raw_ptr, d_sq_ptr, d_err_ptr=None, stream=None):
+    """ptx_pixel_error_device: per-pixel standard error of the sample mean after `passes_done` passes from the DEVICE sums
+    (raw, squares) into d_err_ptr (if given); returns the frame's rel_err = sqrt(sum se^2) / sqrt(sum mean^2)."""
+    rel = C.c_double(0.0)
+    _check(lib().ptx_pixel_error_device(device, width, rows, passes_done, C.c_void_p(d_raw_ptr), C.c_void_p(d_sq_ptr),
+                                        C.c_void_p(d_err_ptr) if d_err_ptr else None, C.byref(rel),
+                                        C.c_void_p(stream) if stream else None))
+    return rel.value
 
 
 def render_multi(scenes, width, height, samples_per_pixel, max_bounces, progress=None, **kw):

@@ -73,6 +73,10 @@ class Stats(C.Structure):
     ]
 
 
+class ProgressiveParams(C.Structure):
+    _fields_ = [("passes_per_update", C.c_int32), ("want_error", C.c_int32), ("target_rel_err", C.c_double)]
+
+
 PTX_LIGHT_POINT, PTX_LIGHT_SPOT = 0, 1
 
 

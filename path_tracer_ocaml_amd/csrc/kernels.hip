@@ -3144,6 +3144,101 @@ __global__ __launch_bounds__(256) void k_film(const double* __restrict__ raw, in
   out[3 * p + 2] = pt_sqrt(b * spp_inv);
 }
 
+/* ------------------------------------------------------------------ progressive rendering: second moments + per-pixel error */
+/* k_accum that also sums each channel's squared contribution into sq, in the same pass order: s = s + c * c (the build has
+ * -ffp-contract=off, so the product is rounded before the add, as numpy's s + c * c does) */
+__global__ __launch_bounds__(256) void k_accum_sq(PtContrib contrib, long long npix, int n_pass, double* __restrict__ raw,
+                                                  double* __restrict__ sq, long long p0, long long p1) {
+  const long long p = p0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= p1) return;
+  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
+  double sr = sq[3 * p], sg = sq[3 * p + 1], sb = sq[3 * p + 2];
+  for (int k = 0; k < n_pass; ++k) {
+    const long long j = (long long)k * npix + p;
+    const double4 c = contrib.rgbx[j];
+    r = r + c.x;
+    g = g + c.y;
+    b = b + c.z;
+    sr = sr + c.x * c.x;
+    sg = sg + c.y * c.y;
+    sb = sb + c.z * c.z;
+  }
+  raw[3 * p] = r;
+  raw[3 * p + 1] = g;
+  raw[3 * p + 2] = b;
+  sq[3 * p] = sr;
+  sq[3 * p + 1] = sg;
+  sq[3 * p + 2] = sb;
+}
+
+/* Standard error of a pixel channel's sample mean after k passes, from S1 = sum c and S2 = sum c^2:
+ * se = sqrt(max(0, S2 - S1 * S1 / k) / (k (k - 1))) for k >= 2, +inf below.  This is the estimate for INDEPENDENT samples; the
+ * sampler is a low-discrepancy sequence, so it usually overestimates the error of the rendered mean. */
+__device__ __forceinline__ double pt_pixel_se(double s1, double s2, double kd) {
+  if (!(kd >= 2.0)) return __builtin_inf();
+  const double v = s2 - s1 * s1 / kd;
+  return pt_sqrt((v > 0.0 ? v : 0.0) / (kd * (kd - 1.0)));
+}
+
+constexpr int PT_ERR_THREADS = 256;
+/* One pixel per thread: err (optional, 3 per pixel) and, per workgroup, partials[2 block] = sum of se^2 and partials[2 block + 1]
+ * = sum of (S1 / k)^2 over its pixels and channels, both summed in a fixed tree order (no atomics: the same sums give the same
+ * bits on every run) */
+__global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error(const double* __restrict__ raw, const double* __restrict__ sq,
+                                                                long long npix, int k, double* __restrict__ err,
+                                                                double* __restrict__ partials) {
+  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
+  const long long p = (long long)blockIdx.x * PT_ERR_THREADS + threadIdx.x;
+  double se2 = 0.0, mean2 = 0.0;
+  if (p < npix) {
+    const double kd = (double)k;
+    for (int c = 0; c < 3; ++c) {
+      const double s1 = raw[3 * p + c], se = pt_pixel_se(s1, sq[3 * p + c], kd), m = s1 / kd;
+      if (err) err[3 * p + c] = se;
+      se2 = se2 + se * se;
+      mean2 = mean2 + m * m;
+    }
+  }
+  lds_se[threadIdx.x] = se2;
+  lds_mean[threadIdx.x] = mean2;
+  for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < off) {
+      lds_se[threadIdx.x] = lds_se[threadIdx.x] + lds_se[threadIdx.x + off];
+      lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
+    }
+  }
+  if (threadIdx.x == 0) {
+    partials[2 * (long long)blockIdx.x] = lds_se[0];
+    partials[2 * (long long)blockIdx.x + 1] = lds_mean[0];
+  }
+}
+
+/* One workgroup: the frame summary rel_err = sqrt(sum se^2) / sqrt(sum mean^2) from k_pixel_error's n_blocks partial pairs, in a
+ * fixed order (thread t sums blocks t, t + 256, ... in turn, then a tree); 0 when both sums are 0, +inf for k < 2 */
+__global__ __launch_bounds__(PT_ERR_THREADS) void k_error_summary(const double* __restrict__ partials, long long n_blocks, int k,
+                                                                  double* __restrict__ rel_err) {
+  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
+  double se2 = 0.0, mean2 = 0.0;
+  for (long long b = threadIdx.x; b < n_blocks; b += PT_ERR_THREADS) {
+    se2 = se2 + partials[2 * b];
+    mean2 = mean2 + partials[2 * b + 1];
+  }
+  lds_se[threadIdx.x] = se2;
+  lds_mean[threadIdx.x] = mean2;
+  for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < off) {
+      lds_se[threadIdx.x] = lds_se[threadIdx.x] + lds_se[threadIdx.x + off];
+      lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double a = lds_se[0], m = lds_mean[0];
+    *rel_err = k < 2 ? __builtin_inf() : (a == 0.0 && m == 0.0) ? 0.0 : pt_sqrt(a) / pt_sqrt(m);
+  }
+}
+
 /* ------------------------------------------------------------------ unit entry points */
 __global__ void k_lds_sample(const double* __restrict__ alpha, long long n, const int32_t* __restrict__ offsets,
                              const int32_t* __restrict__ dims, double* __restrict__ out) {

@@ -257,6 +257,8 @@ struct ptx_scene {
   struct AlphaRef { double* p = nullptr; } alpha;      /* the current render's table (a view into alpha_tables) */
   std::vector<std::pair<int, double*>> alpha_tables;   /* (dimension, device copy) */
   DevBuf<double> raw, rgb;
+  DevBuf<double> sq, err, err_partials;     /* ptx_render_progressive: square sums, per-pixel error, k_pixel_error partials + rel_err */
+  hipEvent_t ev_update = nullptr;           /* ptx_render_progressive: update j filmed (its copy waits for this) */
   DevBuf<PtCounters> counters;
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> event_pool;
@@ -269,6 +271,9 @@ struct ptx_scene {
   int cur_bounce = 0;
   uint4* cur_susp = nullptr;                         /* the launching workspace set's parked-walk buffer */
   int sets_in_flight = 1;                            /* batches sharing the chip during the current render */
+  /* the last render_raw ran its batch(es) on the caller's stream with workspace set 0 (one set): the lanes of the next one must not
+   * start before that stream (slices of different lengths, ptx_render_passes_device, can alternate between one set and two) */
+  bool single_set_last = false;
   int trace_block = env_int("PTX_TRACE_BLOCK", 0); /* 0 = by schedule (trace_block_lds) */
   int fused = env_int("PTX_FUSED", 2);             /* LDS-resident scenes: one kernel per bounce (k_bounce: walk + shade in the same wave) -- 2: every bounce, 1: all but the camera rays', 0: k_trace + k_shade_pool */
   int bounce_fence_wg = env_int("PTX_BOUNCE_FENCE_WG", 0); /* k_bounce: 1 = workgroup-scope fences around a wave's own records (the safety net; tests run both) */
@@ -719,8 +724,8 @@ void fill_tree_stats(const ptx_scene* s, ptx_stats* st) {
  * per-launch tail and the per-workgroup LDS scene load: on the headline frame 2 batches of 32 passes (66M paths,
  * ~13 GB of queues per batch) render 9 % faster than 8 batches of 8.  The count is made even so the two streams
  * get the same number of batches, and a job that would fit one batch is still split in two for them. */
-int choose_passes_per_batch(const ptx_render_params* p, long long npix, long long padded) {
-  const long long spp = p->samples_per_pixel;
+int choose_passes_per_batch(const ptx_render_params* p, long long npix, long long padded, int n_passes) {
+  const long long spp = n_passes; /* the passes this call renders: the whole frame, or a slice of it */
   long long k = std::min<long long>(p->passes_per_batch, spp);
   if (k <= 0) {
   long long target = 80ll << 20; /* paths in flight per batch */
@@ -743,6 +748,14 @@ int choose_passes_per_batch(const ptx_render_params* p, long long npix, long lon
 }
 
 /* the whole integrator for this rank's rows -> raw per-pixel sums at d_raw (rows*W*3) */
+/* A slice of the frame (ptx_render_passes_device, ptx_render_progressive): passes [pass_first, pass_first + pass_count) of the
+ * frame of p->samples_per_pixel passes (the sampler offsets depend on that total), ADDED to d_raw when zero is false; d_sq, if
+ * given, receives the sums of the squared contributions in the same order (k_accum_sq) */
+struct PassRange {
+  int first = 0, count = -1; /* count < 0: the whole frame [0, samples_per_pixel) */
+  bool zero = true;
+  double* d_sq = nullptr;
+};
 /* ptx_render's tail (below): row slabs of the frame's last accumulate, an event recorded behind each */
 constexpr int kMaxFinalSlabs = 8;
 struct FinalSlabs {
@@ -752,8 +765,11 @@ struct FinalSlabs {
   bool used = false;                  /* out: the last batch was accumulated in slabs and the events were recorded */
 };
 int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStream_t st, ptx_stats* stats,
-               ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr) {
+               ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr, const PassRange& range = PassRange()) {
   const int rows = local_rows(p);
+  const int pass_first = range.count < 0 ? 0 : range.first;
+  const int pass_count = range.count < 0 ? p->samples_per_pixel : range.count;
+  const int pass_end = pass_first + pass_count;
   const long long npix = (long long)rows * p->width;
   s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
   s->timed.clear();
@@ -765,13 +781,13 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   if (npix >= 0xffffffffll) return fail(PTX_ERR_ARG, "too many pixels for one rank");
   /* bounce-0 hit records are indexed by the VIRTUAL primary index (8x8 tiles, ragged edges padded) */
   const size_t padded = (size_t)((p->width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
-  int ppb = choose_passes_per_batch(p, npix, (long long)padded);
+  int ppb = choose_passes_per_batch(p, npix, (long long)padded, pass_count);
   /* the blocked output queue of k_shade_pool numbers its blocks in 20 bits: 268 M entries per batch */
   while (ppb > 1 && (size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries) --ppb;
   if ((size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries)
     return fail(PTX_ERR_ARG, "one pass over %lld pixels exceeds the %zu entries a path queue can number (block numbers are 20 bits): render the image in bands", npix, kPoolMaxEntries);
   const size_t cap = (size_t)ppb * padded;
-  const int n_batches = (p->samples_per_pixel + ppb - 1) / ppb;
+  const int n_batches = (pass_count + ppb - 1) / ppb;
   /* Two batches in flight on two streams: trace is f64-VALU-bound, shade streams ~170 B per segment through
    * HBM; run side by side, one batch's shade fills the memory pipes while the other's trace fills the SIMDs. */
   int n_sets = (n_batches >= 2 && p->max_bounces > 0) ? 2 : 1;
@@ -787,7 +803,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
    * flight on two PAIRS of lanes, so that a frame's whole tail overlaps the next frame's head: 3.64 ms, and the full
    * frame 22.9 -> 23.5 ms -- four kernels sharing the CUs cost more than the idle tail they fill; measured, dropped.) */
   const bool overlap_frames = (p->flags & PTX_RENDER_ASYNC) && !count && !timed && !progress && !PT_SHADE_TIMING && n_sets >= 2 &&
-                              env_int("PTX_OVERLAP_FRAMES", 1);
+                              !s->single_set_last && env_int("PTX_OVERLAP_FRAMES", 1);
   const int base = 0;
   Workspace ws[kMaxSets];
   int rc = 0;
@@ -795,7 +811,11 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     rc = ensure_workspace(s, cap, p->max_bounces, &ws[k], base + k);
     if (rc) return rc;
   }
-  HIP_TRY(hipMemsetAsync(d_raw, 0, sizeof(double) * (size_t)npix * 3, st));
+  s->single_set_last = n_sets < 2;
+  if (range.zero) {
+    HIP_TRY(hipMemsetAsync(d_raw, 0, sizeof(double) * (size_t)npix * 3, st));
+    if (range.d_sq) HIP_TRY(hipMemsetAsync(range.d_sq, 0, sizeof(double) * (size_t)npix * 3, st));
+  }
   if (count) HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(PtCounters), st));
   hipStream_t lanes[kMaxSets];
   hipEvent_t* ev_accum = s->ev_accum + base;
@@ -831,11 +851,11 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
 
   long long done_pixels_reported = 0;
   int batch = 0;
-  for (int first = 0; first < p->samples_per_pixel; first += ppb, ++batch) {
+  for (int first = pass_first; first < pass_end; first += ppb, ++batch) {
     const int set = batch % n_sets;
     Workspace& w = ws[set];
     hipStream_t ls = lanes[set];
-    const int n_pass = std::min(ppb, p->samples_per_pixel - first);
+    const int n_pass = std::min(ppb, pass_end - first);
     g.first_pass = first; g.n_pass = n_pass;
     const size_t n_paths = (size_t)n_pass * (size_t)npix;
     HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * kCountsWords, ls));
@@ -854,8 +874,10 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     if (n_sets >= 2 && overlap_frames && batch < n_sets) HIP_TRY(hipStreamWaitEvent(ls, ev_fork, 0)); /* the caller's buffer: see the fork */
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_ACCUM);
-      const bool last_batch = first + ppb >= p->samples_per_pixel;
-      if (slabs && slabs->n > 1 && last_batch && !timed) {
+      const bool last_batch = first + ppb >= pass_end;
+      if (range.d_sq) {
+        hipLaunchKernelGGL(k_accum_sq, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ls, w.contrib, npix, n_pass, d_raw, range.d_sq, 0ll, npix);
+      } else if (slabs && slabs->n > 1 && last_batch && !timed) {
         /* the frame's last accumulate in row slabs, an event behind each: the caller films and copies slab k while k + 1 is summed */
         for (int k = 0; k < slabs->n; ++k) {
           const long long q0 = (long long)slabs->row[k] * p->width, q1 = (long long)slabs->row[k + 1] * p->width;
@@ -879,10 +901,10 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     /* update_progress gets pixel areas summing to W*H (integrator.ml:150, render_command.ml:87-103).  The batches keep
      * running on both streams; the host only waits for their accumulate steps in order, on the calling thread. */
     int b = 0;
-    for (int first = 0; first < p->samples_per_pixel; first += ppb, ++b) {
+    for (int first = pass_first; first < pass_end; first += ppb, ++b) {
       HIP_TRY(hipEventSynchronize(batch_done[(size_t)b]));
-      const int n_pass = std::min(ppb, p->samples_per_pixel - first);
-      const long long upto = (long long)((double)(first + n_pass) / p->samples_per_pixel * (double)npix);
+      const int n_pass = std::min(ppb, pass_end - first);
+      const long long upto = (long long)((double)(first - pass_first + n_pass) / pass_count * (double)npix);
       progress(user, upto - done_pixels_reported);
       done_pixels_reported = upto;
     }
@@ -910,7 +932,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   }
 #endif
   if (stats) {
-    stats->samples = (int64_t)npix * p->samples_per_pixel;
+    stats->samples = (int64_t)npix * pass_count;
     if (count) {
       rc = collect_counters(s, stats);
       if (rc) return rc;
@@ -1137,6 +1159,18 @@ int film_resolve_rows(int width, int height, int spp, const double* d_raw, doubl
   const long long n = (long long)width * (row1 - row0);
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, 1.0 / (double)spp, k, PtBandMap{1, 1, 0}, d_out, row0, row1);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+/* k_pixel_error + k_error_summary queued on st: d_partials holds pixel_error_partials(npix) doubles, the last of them rel_err */
+size_t pixel_error_blocks(long long npix) { return (size_t)((npix + PT_ERR_THREADS - 1) / PT_ERR_THREADS); }
+size_t pixel_error_partials(long long npix) { return 2 * pixel_error_blocks(npix) + 1; }
+int pixel_error_queue(long long npix, int k, const double* d_raw, const double* d_sq, double* d_err, double* d_partials, hipStream_t st) {
+  const size_t n_blocks = pixel_error_blocks(npix);
+  hipLaunchKernelGGL(k_pixel_error, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, npix, k, d_err, d_partials);
+  hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, k,
+                     d_partials + 2 * n_blocks);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1700,6 +1734,7 @@ void ptx_scene_destroy(ptx_scene* s) {
     if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]);
   }
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
+  if (s->ev_update) (void)hipEventDestroy(s->ev_update);
   if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
   for (hipEvent_t ev : s->ev_slab)
     if (ev) (void)hipEventDestroy(ev);
@@ -1845,15 +1880,23 @@ int timed_film(const ptx_render_params& p, const double* d_raw, double* d_rgb, P
 /* The post-gamma framebuffer back to the caller's (pageable) memory.  A plain hipMemcpy of 50 MB into pageable memory
  * runs at ~7 GB/s (6.8 ms at 1080p, a fifth of the render).  Here the device copies 4 MB chunks into a pinned staging
  * buffer with asynchronous DMA while a few host threads move finished chunks on to the caller's buffer: ~2 ms. */
-int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n_doubles) {
-  if (env_int("PTX_PLAIN_D2H", 0) || n_doubles < (1u << 20)) {
+/* cs: the stream the copies are ordered on (NULL: the null stream, and the call waits for the whole device at the end);
+ * ptx_render_progressive copies update j on its copy stream while the next slice is already queued on the others */
+int copy_to_host_on(hipStream_t cs, const double* d_src, double* dst, size_t n_doubles) {
+  if (!cs) {
     HIP_TRY(hipMemcpy(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost));
     return 0;
   }
+  HIP_TRY(hipMemcpyAsync(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost, cs));
+  HIP_TRY(hipStreamSynchronize(cs));
+  return 0;
+}
+int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n_doubles, hipStream_t cs = nullptr) {
+  if (env_int("PTX_PLAIN_D2H", 0) || n_doubles < (1u << 20)) return copy_to_host_on(cs, d_src, dst, n_doubles);
   /* an image the caller has pinned (ptx_image_pin): one DMA straight into it */
   if (s->reg_ptr && dst >= s->reg_ptr && dst + n_doubles <= s->reg_ptr + s->reg_n) {
-    HIP_TRY(hipMemcpyAsync(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpyAsync(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipStreamSynchronize(cs));
     return 0;
   }
   if (s->pinned_n < n_doubles) {
@@ -1862,8 +1905,7 @@ int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n
     s->pinned_n = 0;
     if (hipHostMalloc((void**)&s->pinned, sizeof(double) * n_doubles, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
-      HIP_TRY(hipMemcpy(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost)); /* no pinned memory to be had */
-      return 0;
+      return copy_to_host_on(cs, d_src, dst, n_doubles); /* no pinned memory to be had */
     }
     s->pinned_n = n_doubles;
   }
@@ -1874,8 +1916,8 @@ int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n
   for (size_t k = 0; k < n_chunks && rc == 0; ++k) {
     const size_t off = k * chunk, len = std::min(chunk, n_doubles - off);
     if (hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess ||
-        hipMemcpyAsync(s->pinned + off, d_src + off, sizeof(double) * len, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
-        hipEventRecord(done[k], nullptr) != hipSuccess)
+        hipMemcpyAsync(s->pinned + off, d_src + off, sizeof(double) * len, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipEventRecord(done[k], cs) != hipSuccess)
       rc = fail(PTX_ERR_HIP, "framebuffer copy failed: %s", hipGetErrorString(hipGetLastError()));
   }
   if (rc == 0) {
@@ -1896,7 +1938,8 @@ int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n
     for (std::thread& t : th) t.join();
     if (bad) rc = fail(PTX_ERR_HIP, "framebuffer copy failed: %s", hipGetErrorString(hipGetLastError()));
   }
-  (void)hipDeviceSynchronize();
+  if (cs) (void)hipStreamSynchronize(cs);
+  else (void)hipDeviceSynchronize();
   for (hipEvent_t e : done)
     if (e) (void)hipEventDestroy(e);
   return rc;
@@ -2110,6 +2153,189 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
   rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n);
   if (rc) return rc;
   if (stats) stats->render_ms = wall_ms() - t0;
+  return 0;
+}
+
+/* ---- progressive rendering: a frame rendered as consecutive pass slices into the same raw sums ---- */
+namespace {
+int check_pass_range(const ptx_render_params* p, int32_t pass_first, int32_t pass_count) {
+  if (pass_count < 1) return fail(PTX_ERR_ARG, "pass_count must be >= 1 (got %d)", pass_count);
+  if (pass_first < 0 || (long long)pass_first + pass_count > p->samples_per_pixel)
+    return fail(PTX_ERR_ARG, "pass range [%d, %lld) is outside the frame's passes [0, %d)", pass_first,
+                (long long)pass_first + pass_count, p->samples_per_pixel);
+  return 0;
+}
+
+void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
+  acc->segments += o.segments; acc->nodes_tested += o.nodes_tested; acc->prims_tested += o.prims_tested;
+  acc->floor_tested += o.floor_tested; acc->filter_undecided += o.filter_undecided;
+  acc->filter_fallback_steps += o.filter_fallback_steps; acc->solo_launches += o.solo_launches;
+  for (int i = 0; i < PTX_N_KERNELS; ++i) {
+    acc->kernel_ms[i] += o.kernel_ms[i];
+    acc->kernel_launches[i] += o.kernel_launches[i];
+  }
+}
+
+/* every exit of ptx_render_progressive: nothing the call queued is still running when it returns (an error half-way may leave
+ * lanes that were never joined, hence the whole device) */
+struct DrainOnExit {
+  bool armed = true;
+  ~DrainOnExit() {
+    if (armed) (void)hipDeviceSynchronize();
+  }
+};
+}  // namespace
+
+int32_t ptx_render_passes_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
+                                 double* d_raw_inout, double* d_sq_inout, void* stream, ptx_stats* stats) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (!d_raw_inout) return fail(PTX_ERR_ARG, "d_raw_inout is NULL");
+  int rc = check_params(p);
+  if (rc) return rc;
+  rc = check_pass_range(p, pass_first, pass_count);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  PassRange range;
+  range.first = pass_first;
+  range.count = pass_count;
+  range.zero = false;
+  range.d_sq = d_sq_inout;
+  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, range);
+  if (rc) return rc;
+  if (stats) stats->render_ms = wall_ms() - t0;
+  return 0;
+}
+
+int32_t ptx_pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t passes_done, const double* d_raw,
+                               const double* d_sq, double* d_err_out, double* rel_err_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
+  if (!d_raw || !d_sq) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || rows <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, rows);
+  if (passes_done < 1) return fail(PTX_ERR_ARG, "passes_done must be >= 1 (got %d)", passes_done);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    (void)hipGetLastError();
+    return fail(PTX_ERR_ARG, "device %d out of range (have %d HIP devices): this library has no CPU fallback", device, ndev);
+  }
+  HIP_TRY(hipSetDevice(device));
+  const long long npix = (long long)width * rows;
+  LocalBuf<double> part;
+  HIP_TRY(part.ensure(pixel_error_partials(npix)));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = pixel_error_queue(npix, passes_done, d_raw, d_sq, d_err_out, part.p, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  double rel = 0.0;
+  HIP_TRY(hipMemcpyAsync(&rel, part.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (rel_err_out) *rel_err_out = rel;
+  return 0;
+}
+
+int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
+                               double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update, void* user) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (!pp || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+  int rc = check_params(p_in);
+  if (rc) return rc;
+  if (p_in->n_gpus > 1) return fail(PTX_ERR_ARG, "progressive rendering runs on one GPU (n_gpus %d)", p_in->n_gpus);
+  if (pp->passes_per_update < 1) return fail(PTX_ERR_ARG, "passes_per_update must be >= 1 (got %d)", pp->passes_per_update);
+  if (!(pp->target_rel_err >= 0.0)) return fail(PTX_ERR_ARG, "target_rel_err must be >= 0 (got %g)", pp->target_rel_err);
+  if (!pp->want_error && (pp->target_rel_err > 0.0 || err_out))
+    return fail(PTX_ERR_ARG, "target_rel_err and err_out need want_error");
+  if (passes_done_out) *passes_done_out = 0;
+  ptx_render_params p = *p_in;
+  p.band_step = 0; /* whole image on this GPU */
+  p.n_gpus = 0;
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  const int N = p.samples_per_pixel, K = pp->passes_per_update;
+  const long long npix = (long long)p.width * p.height;
+  const size_t n = (size_t)npix * 3;
+  const bool want_err = pp->want_error != 0;
+  HIP_TRY(s->raw.ensure(n));
+  HIP_TRY(s->rgb.ensure(n));
+  if (want_err) {
+    HIP_TRY(s->sq.ensure(n));
+    HIP_TRY(s->err_partials.ensure(pixel_error_partials(npix)));
+    if (err_out) HIP_TRY(s->err.ensure(n));
+  }
+  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+  if (!s->ev_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_update, hipEventDisableTiming));
+  DrainOnExit drain;
+  ptx_stats acc, slice;
+  std::memset(&acc, 0, sizeof acc);
+  fill_tree_stats(s, &acc);
+  /* Slices are queued on the null stream (PTX_RENDER_ASYNC: render_raw returns once they are queued).  Update j is filmed there
+   * behind slice j's accumulate; slice j + 1 is queued next, so its bounces run while update j is copied out on copy_stream and
+   * handed to the callback -- its accumulate waits for the film (render_raw's fork event, recorded behind it).  The copy of update
+   * j + 1 is queued only after callback j has returned.  A render that counts work or times kernels waits for every slice and
+   * queues the next one only after the callback. */
+  const bool ahead = !p.count_work && !p.time_kernels;
+  auto queue_slice = [&](int first, int count) -> int {
+    PassRange r;
+    r.first = first;
+    r.count = count;
+    r.zero = first == 0;
+    r.d_sq = want_err ? s->sq.p : nullptr;
+    ptx_render_params pq = p;
+    pq.flags = PTX_RENDER_ASYNC;
+    const int r2 = render_raw(s, &pq, s->raw.p, nullptr, &slice, nullptr, nullptr, nullptr, r);
+    if (r2 == 0) add_slice_stats(&acc, slice);
+    return r2;
+  };
+  int k = std::min(K, N);
+  rc = queue_slice(0, k);
+  if (rc) return rc;
+  double rel = std::nan("");
+  for (;;) {
+    rc = film_resolve(p.width, p.height, k, s->raw.p, s->rgb.p, nullptr);
+    if (rc) return rc;
+    if (want_err) {
+      rc = pixel_error_queue(npix, k, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipEventRecord(s->ev_update, nullptr));
+    const int next = std::min(K, N - k);
+    if (next > 0 && ahead) {
+      rc = queue_slice(k, next);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_update, 0));
+    rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n, s->copy_stream);
+    if (rc) return rc;
+    if (err_out) {
+      rc = framebuffer_to_host(s, s->err.p, err_out, n, s->copy_stream);
+      if (rc) return rc;
+    }
+    if (want_err) {
+      HIP_TRY(hipMemcpyAsync(&rel, s->err_partials.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, s->copy_stream));
+      HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    }
+    if (passes_done_out) *passes_done_out = k;
+    bool stop = on_update && on_update(user, k, rel, rgb_out, err_out) != 0;
+    if (want_err && pp->target_rel_err > 0.0 && rel <= pp->target_rel_err) stop = true;
+    if (stop || next == 0) break;
+    if (!ahead) {
+      rc = queue_slice(k, next);
+      if (rc) return rc;
+    }
+    k += next;
+  }
+  /* (after an early stop the slice queued ahead finishes here; its passes are in the raw sums only, never in rgb_out) */
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipStreamSynchronize(s->copy_stream));
+  drain.armed = false;
+  if (stats) {
+    *stats = acc;
+    stats->samples = (int64_t)npix * k;
+    stats->render_ms = wall_ms() - t0;
+  }
   return 0;
 }
 

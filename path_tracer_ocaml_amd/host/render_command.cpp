@@ -6,7 +6,9 @@
 //   --max-ray-bounces=INT (default 8)
 // plus shirley_spheres' own --no-simd (shirley_spheres/bin/main.ml:12-23), and the prints of
 // shirley_spheres/bin/main.ml:254-267 / render_command.ml:108.  Additions: --scene, --device, --gpus (SURVEY section 5
-// "config / flags": the image spread over N GPUs of the node inside this process, ptx_render_params.n_gpus).
+// "config / flags": the image spread over N GPUs of the node inside this process, ptx_render_params.n_gpus), and
+// --progressive=K / --target-error=E: -o rewritten after every K passes (ptx_render_progressive), as the photon-map binaries
+// rewrite it after every iteration, stopping early once the frame's relative standard error is at most E.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +34,8 @@ struct Args {
   int ganesha_triangles = 150000;
   double ceiling_emit = 12.0;
   std::string ganesha_ply; // -ganesha-ply <file> (ganesha/bin/main.ml:19-24); empty = synthetic stand-in mesh
+  int progressive = 0;       // passes per update; 0 = one ptx_render
+  double target_error = 0.0; // stop at the first update whose rel_err is <= this (0 = never)
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -39,7 +43,8 @@ struct Args {
   std::fprintf(stderr,
                "Usage: %s -d WIDTH,HEIGHT [--samples-per-pixel=INT] [-o PATH] [--no-progress]\n"
                "          [--max-ray-bounces=INT] [--no-simd] [--scene=shirley|cornell|ganesha] [--device=INT] [--gpus=INT]\n"
-               "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n",
+               "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
+               "          [--progressive=K] [--target-error=FLOAT]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -80,6 +85,13 @@ Args parse(int argc, char** argv) {
     else if (take_value(argc, argv, i, "triangles", nullptr, &v)) a.ganesha_triangles = std::atoi(v.c_str());
     else if (take_value(argc, argv, i, "ceiling-emit", nullptr, &v)) a.ceiling_emit = std::atof(v.c_str());
     else if (take_value(argc, argv, i, "ganesha-ply", nullptr, &v)) a.ganesha_ply = v;
+    else if (take_value(argc, argv, i, "progressive", nullptr, &v)) {
+      a.progressive = std::atoi(v.c_str());
+      if (a.progressive < 1) usage(argv[0], "invalid value for --progressive, must be >= 1");
+    } else if (take_value(argc, argv, i, "target-error", nullptr, &v)) {
+      a.target_error = std::atof(v.c_str());
+      if (!(a.target_error > 0.0)) usage(argv[0], "invalid value for --target-error, must be > 0");
+    }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
     else if (!std::strcmp(argv[i], "--no-simd")) a.no_simd = true;
@@ -93,6 +105,8 @@ Args parse(int argc, char** argv) {
   if (a.samples_per_pixel < 1) usage(argv[0], "invalid value for --samples-per-pixel, must be >= 1");
   if (a.max_bounces < 0) usage(argv[0], "invalid value for --max-ray-bounces, must be >= 0");
   if (a.gpus < 1) usage(argv[0], "invalid value for --gpus, must be >= 1");
+  if (a.target_error > 0.0 && !a.progressive) usage(argv[0], "--target-error requires --progressive");
+  if (a.progressive && a.gpus > 1) usage(argv[0], "--progressive renders on one GPU (--gpus=1)");
   return a;
 }
 
@@ -116,6 +130,22 @@ void on_progress(void* user, int64_t pixels) { // the ASCII bar of render_comman
   for (int i = 0; i < width; ++i) std::fputc(i < fill ? '#' : '-', stderr);
   std::fprintf(stderr, "] %3.0f%%    ", 100.0 * (double)p->done / (double)p->total);
   if (p->done >= p->total) std::fputc('\n', stderr);
+}
+
+struct Updates { // --progressive: the PNG rewritten after every update, one line per update on stdout
+  const char* output;
+  int width, height;
+  bool write_failed = false;
+};
+int32_t on_update(void* user, int32_t passes_done, double rel_err, const double* rgb, const double*) {
+  Updates* u = (Updates*)user;
+  std::printf("#passes = %d, error = %.6g\n", passes_done, rel_err);
+  std::fflush(stdout);
+  if (pth_write_png(u->output, u->width, u->height, rgb) != 0) {
+    u->write_failed = true;
+    return 1;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -172,14 +202,26 @@ int main(int argc, char** argv) {
   /* the image lives until the PNG is written, like the reference's Bimage (render_command.ml:64-70): pin it, so the frame comes
    * back with one DMA (optional: a failure only means the staged copy) */
   (void)ptx_image_pin(scene, rgb.data(), (int64_t)rgb.size());
-  const int rc = ptx_render(scene, &p, rgb.data(), &st, a.no_progress ? nullptr : on_progress, &prog);
+  Updates upd{a.output.c_str(), a.width, a.height};
+  int rc;
+  if (a.progressive) {
+    ptx_progressive_params pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.passes_per_update = a.progressive;
+    pp.want_error = 1;
+    pp.target_rel_err = a.target_error;
+    int32_t passes_done = 0;
+    rc = ptx_render_progressive(scene, &p, &pp, rgb.data(), nullptr, &passes_done, &st, on_update, &upd);
+  } else {
+    rc = ptx_render(scene, &p, rgb.data(), &st, a.no_progress ? nullptr : on_progress, &prog);
+  }
   (void)ptx_image_unpin(scene);
   const double elapsed = now_ms() - t0;
   if (rc != 0) {
-    std::fprintf(stderr, "ptx_render: %s\n", ptx_last_error());
+    std::fprintf(stderr, "%s: %s\n", a.progressive ? "ptx_render_progressive" : "ptx_render", ptx_last_error());
     return 1;
   }
-  if (pth_write_png(a.output.c_str(), a.width, a.height, rgb.data()) != 0) {
+  if (upd.write_failed || pth_write_png(a.output.c_str(), a.width, a.height, rgb.data()) != 0) {
     std::fprintf(stderr, "cannot write %s\n", a.output.c_str());
     return 1;
   }

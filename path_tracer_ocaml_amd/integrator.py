@@ -61,6 +61,7 @@ class Integrator:
         self.samples_per_pixel, self.max_bounces = samples_per_pixel, max_bounces
         self._scene = scene if isinstance(scene, Scene) else Scene(scene.ptr, device, keepalive=scene)
         self.stats = None
+        self.error = self.passes_done = None  # render_progressive
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0):
@@ -72,6 +73,18 @@ class Integrator:
                                      progress=update_progress)
         self.image[...] = rgb
         self.stats = st
+        return self.image
+
+    def render_progressive(self, passes_per_update, on_update=None, target_rel_err=0.0, want_error=True):
+        """``render`` as a sequence of updates (Scene.render_progressive): ``image`` holds the image of the last update,
+        ``error`` its per-pixel standard error (None without want_error), ``passes_done`` how many passes it holds."""
+        out = self.image if self.image.flags["C_CONTIGUOUS"] else None
+        rgb, err, done, st = self._scene.render_progressive(self.width, self.height, self.samples_per_pixel, self.max_bounces,
+                                                            passes_per_update, on_update=on_update,
+                                                            target_rel_err=target_rel_err, want_error=want_error, out=out)
+        if out is None:
+            self.image[...] = rgb
+        self.error, self.passes_done, self.stats = err, done, st
         return self.image
 
 
