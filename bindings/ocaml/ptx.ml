@@ -179,6 +179,18 @@ external render_progressive_flat
   -> int
   = "ptx_ml_render_progressive_stub"
 
+external render_adaptive_flat
+  :  scene
+  -> floatarray
+     (* width, height, samples_per_pixel, max_bounces, min_passes, passes_per_round, target_rel_err, radiance_floor *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* image, W*H*3 *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* per-pixel error, W*H*3, or empty *)
+  -> (int32, Bigarray.int32_elt, Bigarray.c_layout) Bigarray.Array1.t (* per-pixel pass count, W*H, or empty *)
+  -> (int -> int -> int * int * float -> bool)
+     (* round, passes done, (pixels of the next round, samples so far, rel_err); true stops the render *)
+  -> int
+  = "ptx_ml_render_adaptive_stub_bytecode" "ptx_ml_render_adaptive_stub"
+
 module FA = Stdlib.Float.Array
 
 (* the tables are interned structurally: a 150 k-triangle mesh with one material gets one row, not 150 k *)
@@ -370,6 +382,46 @@ let render_progressive
   in
   render_progressive_flat scene params image err (fun passes_done rel_err last ->
     on_update ~passes_done ~rel_err ~last)
+;;
+
+(* [render] with per-pixel pass counts: round 1 gives every pixel [min_passes] passes, every later round gives the pixels whose
+   standard error is still above [target_rel_err] times their mean radiance (at least [radiance_floor])
+   [passes_per_round] more, up to [samples_per_pixel].  After every round [image] holds the frame filmed from each pixel's
+   own passes, [err] (if given) its per-pixel standard error, [passes] (if given) the count map, and [on_round] runs on the
+   calling thread; it returns true to stop.  The result is the number of samples in [image].  With [target_rel_err] = 0
+   every pixel gets [samples_per_pixel] passes and [image] is what [render] gives.  An exception raised by [on_round] stops
+   the render and is raised again once the library has returned. *)
+let render_adaptive
+  ?(min_passes = 8)
+  ?(passes_per_round = 8)
+  ?(radiance_floor = 1e-3)
+  ?err
+  ?passes
+  scene
+  ~width
+  ~height
+  ~samples_per_pixel
+  ~max_bounces
+  ~target_rel_err
+  ~image
+  ~on_round
+  =
+  let err = Option.value err ~default:(Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0) in
+  let passes = Option.value passes ~default:(Bigarray.Array1.create Bigarray.int32 Bigarray.c_layout 0) in
+  let params =
+    FA.of_list
+      [ Float.of_int width
+      ; Float.of_int height
+      ; Float.of_int samples_per_pixel
+      ; Float.of_int max_bounces
+      ; Float.of_int min_passes
+      ; Float.of_int passes_per_round
+      ; target_rel_err
+      ; radiance_floor
+      ]
+  in
+  render_adaptive_flat scene params image err passes (fun round passes_done (active_next, samples, rel_err) ->
+    on_round ~round ~passes_done ~active_next ~samples ~rel_err)
 ;;
 
 (* [f ()] with [image] pinned; a host that renders many frames into one Bimage (an animation loop around Render_command's run)

@@ -194,4 +194,30 @@ static __attribute__((unused)) int32_t ptx_ml_render_progressive(ptx_scene* s, c
   return ptx_render_progressive(s, &p, &pp, image, err, passes_done, NULL, on_update, user);
 }
 
+/* Integrator.render with per-pixel pass counts (ptx_render_adaptive): params8 = width, height, samples_per_pixel, max_bounces,
+ * min_passes, passes_per_round, target_rel_err, radiance_floor.  image (W*H*3) holds the image of the last round, err (nullable)
+ * its per-pixel standard error, passes (nullable, W*H) the count map, *samples the sum of the map; on_round runs after every
+ * round. */
+static __attribute__((unused)) int32_t ptx_ml_render_adaptive(ptx_scene* s, const double* params8, double* image, double* err, int32_t* passes,
+                                                              int64_t* samples, ptx_round_fn on_round, void* user) {
+  if (!params8) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params8[0];
+  p.height = (int32_t)params8[1];
+  p.samples_per_pixel = (int32_t)params8[2];
+  p.max_bounces = (int32_t)params8[3];
+  ptx_adaptive_params ap;
+  memset(&ap, 0, sizeof ap);
+  ap.min_passes = (int32_t)params8[4];
+  ap.passes_per_round = (int32_t)params8[5];
+  ap.target_rel_err = params8[6];
+  ap.radiance_floor = params8[7];
+  ptx_stats st;
+  memset(&st, 0, sizeof st);
+  const int32_t rc = ptx_render_adaptive(s, &p, &ap, image, err, passes, &st, on_round, user);
+  if (samples) *samples = st.samples;
+  return rc;
+}
+
 #endif /* PTX_ML_MARSHAL_H */

@@ -434,3 +434,87 @@ CAMLprim value ptx_ml_render_progressive_stub(value handle, value params, value 
   if (rc != 0) caml_failwith(ptx_last_error());
   CAMLreturn(Val_long(passes_done));
 }
+
+/* the round callback: the library has already filled the caller's Bigarrays (image, err, passes) when it calls */
+typedef struct ptx_ml_round_cb {
+  ptx_ml_cb cb;
+  int stop; /* what the closure returned */
+} ptx_ml_round_cb;
+
+/* runs with the runtime lock held: on_round round passes_done (active_next, samples, rel_err) */
+static void ptx_ml_call_on_round(ptx_ml_round_cb* u, int32_t round, int32_t passes_done, int64_t active_next, int64_t samples,
+                                 double rel_err) {
+  CAMLparam0();
+  CAMLlocal3(boxed_rel_err, info, r);
+  boxed_rel_err = caml_copy_double(rel_err);
+  info = caml_alloc_tuple(3);
+  Store_field(info, 0, Val_long(active_next));
+  Store_field(info, 1, Val_long(samples));
+  Store_field(info, 2, boxed_rel_err);
+  r = caml_callback3_exn(*u->cb.closure, Val_long(round), Val_long(passes_done), info);
+  if (Is_exception_result(r)) {
+    *u->cb.exn = Extract_exception(r);
+    u->cb.raised = 1;
+  } else {
+    u->stop = Int_val(r) != 0;
+  }
+  CAMLreturn0;
+}
+
+static int32_t ptx_ml_on_round(void* user, int32_t round, int32_t passes_done, int64_t active_next, int64_t samples, double rel_err,
+                               const double* rgb, const double* err, const int32_t* passes) {
+  ptx_ml_round_cb* u = (ptx_ml_round_cb*)user;
+  (void)rgb;
+  (void)err;
+  (void)passes;
+  if (u->cb.raised) return 1;
+  caml_acquire_runtime_system(); /* the render runs with the lock released */
+  ptx_ml_call_on_round(u, round, passes_done, active_next, samples, rel_err);
+  caml_release_runtime_system();
+  return (u->cb.raised || u->stop) ? 1 : 0; /* a raise stops the render: no callbacks after it */
+}
+
+/* external render_adaptive_flat : scene -> floatarray -> image -> err -> passes -> (int -> int -> int * int * float -> bool) -> int
+ *   = "ptx_ml_render_adaptive_stub"
+ * (scene, [width; height; samples_per_pixel; max_bounces; min_passes; passes_per_round; target_rel_err; radiance_floor], image
+ * (W*H*3), err (W*H*3 or empty), passes (int32, W*H or empty), on_round round passes_done (active_next, samples, rel_err) -> stop)
+ * -> samples (the sum of the count map).  The exception of a callback that raised is raised here, after the library has returned
+ * (and has drained everything it queued). */
+CAMLprim value ptx_ml_render_adaptive_stub(value handle, value params, value image, value err, value passes, value on_round) {
+  CAMLparam5(handle, params, image, err, passes);
+  CAMLxparam1(on_round);
+  CAMLlocal1(exn);
+  if (floatarray_length(params) != 8) caml_invalid_argument("Ptx.render_adaptive: params needs 8 floats");
+  double p8[8];
+  memcpy(p8, floatarray_data(params), sizeof p8);
+  const intnat w = (intnat)p8[0], h = (intnat)p8[1];
+  if (w <= 0 || h <= 0 || Caml_ba_array_val(image)->dim[0] != w * h * 3)
+    caml_invalid_argument("Ptx.render_adaptive: image must hold width * height * 3 floats");
+  const intnat n_err = Caml_ba_array_val(err)->dim[0];
+  if (n_err != 0 && n_err != w * h * 3) caml_invalid_argument("Ptx.render_adaptive: err must be empty or hold width * height * 3 floats");
+  const intnat n_passes = Caml_ba_array_val(passes)->dim[0];
+  if (n_passes != 0 && n_passes != w * h) caml_invalid_argument("Ptx.render_adaptive: passes must be empty or hold width * height int32s");
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_adaptive: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_adaptive: scene already destroyed");
+  double* out = (double*)Caml_ba_data_val(image); /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  double* err_out = n_err ? (double*)Caml_ba_data_val(err) : NULL;
+  int32_t* passes_out = n_passes ? (int32_t*)Caml_ba_data_val(passes) : NULL;
+  exn = Val_unit;
+  ptx_ml_round_cb cb = {{&on_round, &exn, 0}, 0};
+  int64_t samples = 0;
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_adaptive(s, p8, out, err_out, passes_out, &samples, ptx_ml_on_round, &cb);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (cb.cb.raised) caml_raise(exn);
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_long(samples));
+}
+
+/* bytecode entry of the 6-argument external */
+CAMLprim value ptx_ml_render_adaptive_stub_bytecode(value* argv, int argn) {
+  (void)argn;
+  return ptx_ml_render_adaptive_stub(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5]);
+}

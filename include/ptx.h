@@ -351,6 +351,60 @@ int32_t ptx_render_progressive(ptx_scene* scene, const ptx_render_params* params
                                double* rgb_out, double* err_out, int32_t* passes_done_out, ptx_stats* stats,
                                ptx_update_fn on_update, void* user);
 
+/* ---- adaptive sampling ----
+ * A pixel that stops after n passes holds the pass-order prefix of its own N-pass sums (the sampler offset depends only on
+ * (x, y, pass, N)), so every pixel's sums are bit for bit ptx_render_passes_device's over [0, n).  All of these run on ONE GPU over
+ * the whole image (n_gpus > 1 or band_step > 1: PTX_ERR_ARG). */
+
+/* Passes [pass_first, pass_first + pass_count) of the N-pass frame for the DEVICE list d_pixels of n_pixels DISTINCT indices
+ * y * W + x, ADDED to the whole-image sums d_raw_inout (and the squares to d_sq_inout, DEVICE, nullable), in pass order as
+ * ptx_render_passes_device adds them; unlisted pixels are untouched.  PTX_ERR_ARG for a bad pass range, n_pixels outside
+ * [0, W*H], or an index outside [0, W*H) -- checked on the device before anything is queued, the sums left untouched (the check
+ * waits for `stream`).  stats->samples = n_pixels * pass_count.  `stream` and PTX_RENDER_ASYNC as in ptx_render_raw_device. */
+int32_t ptx_render_pixels_device(ptx_scene* scene, const ptx_render_params* params, int32_t pass_first, int32_t pass_count,
+                                 const int32_t* d_pixels, int64_t n_pixels, double* d_raw_inout, double* d_sq_inout, void* stream,
+                                 ptx_stats* stats);
+
+/* ptx_film_resolve_device with a per-pixel pass count d_passes (DEVICE, W*H, every count >= 1).  Where all in-image taps of the
+ * 3x3 film have the same count n, the pixel is ptx_film_resolve_device's with spp = n, bit for bit; elsewhere it is
+ * sqrt(sum w * (S(q) * (1 / n(q)))), the film of each tap's own mean.  Waits for `stream`. */
+int32_t ptx_film_resolve_counts_device(int32_t device, int32_t width, int32_t height, const double* d_raw, const int32_t* d_passes,
+                                       double* d_rgb_out, void* stream);
+
+/* ptx_pixel_error_device with the pixel's own pass count k = d_passes[p] (DEVICE, rows * W): se per pixel and channel into
+ * d_err_out (nullable), *rel_err_out = sqrt(sum se^2) / sqrt(sum (S1 / k)^2) in the same fixed order (0 when both sums are 0;
+ * +inf when some pixel has k < 2).  A uniform map gives ptx_pixel_error_device's bits.  Waits for `stream`. */
+int32_t ptx_pixel_error_counts_device(int32_t device, int32_t width, int32_t rows, const int32_t* d_passes, const double* d_raw,
+                                      const double* d_sq, double* d_err_out, double* rel_err_out, void* stream);
+
+typedef struct ptx_adaptive_params {
+  int32_t min_passes;       /* M >= 2: round 1 gives every pixel passes [0, min(M, N)) */
+  int32_t passes_per_round; /* K >= 1: every later round gives the pixels still active K more passes (the last one fewer) */
+  double target_rel_err;    /* T >= 0: a pixel stops once e <= T * d (below); 0 = no pixel stops before N */
+  double radiance_floor;    /* F >= 0: d is at least this, so dark pixels stop on an absolute error */
+} ptx_adaptive_params;
+
+/* Called on the CALLING thread after every round: its number (1, 2, ...), the passes the round ended at (b), how many pixels the
+ * next round renders (0: none, the render ends), the samples so far (the sum of the count map), the frame's rel_err, the image,
+ * its per-pixel error (or NULL) and the count map (or NULL).  Non-zero stops the render. */
+typedef int32_t (*ptx_round_fn)(void* user, int32_t round, int32_t passes_done, int64_t active_next, int64_t samples,
+                                double rel_err, const double* rgb, const double* err, const int32_t* passes);
+
+/* ptx_render with per-pixel pass counts.  Round 1 gives every pixel passes [0, min(M, N)).  After a round that ended at b < N,
+ * the next round gives the pixels of that round that have NOT converged passes [b, min(b + K, N)); the render ends at N, when no
+ * pixel is left, or when on_round (nullable) returns non-zero.  The rule, for a pixel with k passes and sums S1_c, S2_c:
+ *   se_c = sqrt(max(0, S2_c - S1_c * S1_c / k) / (k (k - 1))),  m_c = S1_c / k,  e = sqrt((se_r^2 + se_g^2) + se_b^2),
+ *   d = max(sqrt((m_r^2 + m_g^2) + m_b^2), F),  converged <=> T > 0 and e <= T * d.
+ * After every round the sums are filmed with the count map (ptx_film_resolve_counts_device) into rgb_out (HOST, W*H*3), the
+ * per-pixel error goes to err_out (HOST, nullable; ptx_pixel_error_counts_device), the map to passes_out (HOST, W*H, nullable),
+ * and on_round is called.  On return they hold what the last callback saw, stats->samples is the sum of the map, and nothing the
+ * call queued is still running (also on every error).  A round over the whole image is a plain slice; the next list is selected
+ * on the device in a fixed order (8x8-tile order, no atomics), so a frame gives the same map on every run.  With T = 0 every
+ * pixel gets N passes and rgb_out is ptx_render's image bit for bit.  PTX_ERR_ARG for M < 2, K < 1, T or F negative or NaN. */
+int32_t ptx_render_adaptive(ptx_scene* scene, const ptx_render_params* params, const ptx_adaptive_params* adaptive,
+                            double* rgb_out, double* err_out, int32_t* passes_out, ptx_stats* stats, ptx_round_fn on_round,
+                            void* user);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

@@ -35,11 +35,13 @@ EXPORTS = (
     "ptx_math_eval", "ptx_ppm_render", "ptx_debug_first_scatter", "ptx_render_multi", "ptx_scene_replicate",
     "ptx_film_resolve_banded_device", "ptx_film_resolve_banded_queue", "ptx_release_workspaces",
     "ptx_image_pin", "ptx_image_unpin", "ptx_render_passes_device", "ptx_pixel_error_device", "ptx_render_progressive",
+    "ptx_render_pixels_device", "ptx_film_resolve_counts_device", "ptx_pixel_error_counts_device", "ptx_render_adaptive",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
 # ptx_update_fn: (user, passes_done, rel_err, rgb, err) -> non-zero stops the render
 UPDATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p)
+ROUND_FN = abi.ROUND_FN
 
 
 def lib():
@@ -88,6 +90,14 @@ def lib():
                                          dp, C.c_void_p]
     L.ptx_render_progressive.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.ProgressiveParams), dp, dp,
                                          ip, C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
+    L.ptx_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
+    L.ptx_film_resolve_counts_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+    L.ptx_pixel_error_counts_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, dp, C.c_void_p]
+    L.ptx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.AdaptiveParams), dp, dp, ip,
+                                      C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
     L.ptx_trace_samples.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int64, ip, ip, ip, dp,
                                     C.POINTER(abi.Stats)]
     L.ptx_intersect_rays.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp, ip, C.POINTER(abi.Stats)]
@@ -265,6 +275,67 @@ class Scene:
         _check(rc)
         return out, err_out, done.value, stats_dict(st)
 
+    def render_pixels_device(self, params, pass_first, pass_count, d_pixels_ptr, n_pixels, d_raw_ptr, d_sq_ptr=None,
+                             stream=None):
+        """ptx_render_pixels_device: passes [pass_first, pass_first + pass_count) of the frame of params.samples_per_pixel passes
+        for the n_pixels DISTINCT indices y * W + x of the DEVICE list d_pixels_ptr (int32), ADDED to the whole-image raw sums
+        (and their squares to d_sq_ptr if given); unlisted pixels are untouched."""
+        if int(n_pixels) < 0:
+            raise ValueError("n_pixels must be >= 0")
+        st = abi.Stats()
+        _check(lib().ptx_render_pixels_device(self._h, C.byref(params), int(pass_first), int(pass_count),
+                                              C.c_void_p(d_pixels_ptr) if d_pixels_ptr else None, int(n_pixels),
+                                              C.c_void_p(d_raw_ptr), C.c_void_p(d_sq_ptr) if d_sq_ptr else None,
+                                              C.c_void_p(stream) if stream else None, C.byref(st)))
+        return stats_dict(st)
+
+    def render_adaptive(self, width, height, spp, depth, target_rel_err, min_passes=8, passes_per_round=8,
+                        radiance_floor=1e-3, on_round=None, out=None, err_out=None, passes_out=None, **kw):
+        """ptx_render_adaptive: round 1 gives every pixel min(min_passes, spp) passes, every later round gives the pixels that have
+        not converged (per-pixel standard error e <= target_rel_err * max(|mean|, radiance_floor)) passes_per_round more, up to
+        spp.  on_round(round, passes_done, active_next, samples, rel_err, rgb, err, passes) is called after each with the (H, W, 3)
+        image, its per-pixel error and the (H, W) int32 pass counts; a truthy return stops the render.  An exception raised by
+        on_round stops the render and is raised again here.  Returns (rgb, err, passes, stats) of the last round."""
+        if int(min_passes) < 2:
+            raise ValueError("min_passes must be >= 2")
+        if int(passes_per_round) < 1:
+            raise ValueError("passes_per_round must be >= 1")
+        if not float(target_rel_err) >= 0.0:
+            raise ValueError("target_rel_err must be >= 0")
+        if not float(radiance_floor) >= 0.0:
+            raise ValueError("radiance_floor must be >= 0")
+        if kw.get("n_gpus", 0) > 1 or kw.get("band_step", 0) > 1:
+            raise ValueError("adaptive rendering runs on one GPU over the whole image")
+        out = _image_arg(out, width, height, "out")
+        err_out = _image_arg(err_out, width, height, "err_out")
+        if passes_out is None:
+            passes_out = np.zeros((height, width), dtype=np.int32)
+        elif passes_out.shape != (height, width) or passes_out.dtype != np.int32 or not passes_out.flags["C_CONTIGUOUS"]:
+            raise ValueError("passes_out must be a C-contiguous int32 array of shape (height, width)")
+        p = render_params(width, height, spp, depth, **kw)
+        ap = abi.AdaptiveParams()
+        ap.min_passes, ap.passes_per_round = int(min_passes), int(passes_per_round)
+        ap.target_rel_err, ap.radiance_floor = float(target_rel_err), float(radiance_floor)
+        raised = []
+
+        def trampoline(user, rnd, passes_done, active_next, samples, rel_err, rgb, err, passes):
+            if raised:
+                return 1
+            try:
+                return 1 if on_round(rnd, passes_done, active_next, samples, rel_err, out, err_out, passes_out) else 0
+            except BaseException as e:  # noqa: BLE001 -- carried across the C frames, raised again below
+                raised.append(e)
+                return 1
+
+        cb = ROUND_FN(trampoline) if on_round is not None else None
+        st = abi.Stats()
+        rc = lib().ptx_render_adaptive(self._h, C.byref(p), C.byref(ap), _dp(out), _dp(err_out), _ip(passes_out), C.byref(st),
+                                       C.cast(cb, C.c_void_p) if cb else None, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return out, err_out, passes_out, stats_dict(st)
+
     def trace_samples(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes, count_work=False):
         xs = np.ascontiguousarray(xs, dtype=np.int32)
         ys = np.ascontiguousarray(ys, dtype=np.int32)
@@ -320,6 +391,21 @@ def pixel_error_device(device, width, rows, passes_done, d_raw_ptr, d_sq_ptr, d_
     _check(lib().ptx_pixel_error_device(device, width, rows, passes_done, C.c_void_p(d_raw_ptr), C.c_void_p(d_sq_ptr),
                                         C.c_void_p(d_err_ptr) if d_err_ptr else None, C.byref(rel),
                                         C.c_void_p(stream) if stream else None))
+    return rel.value
+
+
+def film_resolve_counts_device(device, width, height, d_raw_ptr, d_passes_ptr, d_rgb_ptr, stream=None):
+    """ptx_film_resolve_counts_device: the film of DEVICE raw sums with a per-pixel pass count (int32, H x W)"""
+    _check(lib().ptx_film_resolve_counts_device(device, width, height, C.c_void_p(d_raw_ptr), C.c_void_p(d_passes_ptr),
+                                                C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
+
+
+def pixel_error_counts_device(device, width, rows, d_passes_ptr, d_raw_ptr, d_sq_ptr, d_err_ptr=None, stream=None):
+    """ptx_pixel_error_counts_device: pixel_error_device with each pixel's own pass count (int32, rows x W); returns rel_err"""
+    rel = C.c_double(0.0)
+    _check(lib().ptx_pixel_error_counts_device(device, width, rows, C.c_void_p(d_passes_ptr), C.c_void_p(d_raw_ptr),
+                                               C.c_void_p(d_sq_ptr), C.c_void_p(d_err_ptr) if d_err_ptr else None,
+                                               C.byref(rel), C.c_void_p(stream) if stream else None))
     return rel.value
 
 

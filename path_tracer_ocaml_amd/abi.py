@@ -77,6 +77,16 @@ class ProgressiveParams(C.Structure):
     _fields_ = [("passes_per_update", C.c_int32), ("want_error", C.c_int32), ("target_rel_err", C.c_double)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_passes", C.c_int32), ("passes_per_round", C.c_int32), ("target_rel_err", C.c_double),
+                ("radiance_floor", C.c_double)]
+
+
+# ptx_round_fn: (user, round, passes_done, active_next, samples, rel_err, rgb, err, passes) -> non-zero stops the render
+ROUND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                       C.c_void_p)
+
+
 PTX_LIGHT_POINT, PTX_LIGHT_SPOT = 0, 1
 
 

@@ -3239,6 +3239,246 @@ __global__ __launch_bounds__(PT_ERR_THREADS) void k_error_summary(const double* 
   }
 }
 
+/* ------------------------------------------------------------------ adaptive sampling: pixel lists and per-pixel pass counts */
+/* Every listed index lies in [0, npix): *bad (zeroed by the caller) is set to 1 otherwise.  Runs before anything else is queued. */
+__global__ __launch_bounds__(256) void k_list_check(const int32_t* __restrict__ pix, long long n, long long npix, int32_t* __restrict__ bad) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int32_t p = pix[j];
+  if (p < 0 || (long long)p >= npix) *bad = 1;
+}
+
+/* Camera rays of passes [first_pass, first_pass + n_pass) for the listed pixels (pix[j] = y * width + x, whole image), pass-major
+ * then list order: entry i = pass_in_batch * n_list + j, and its contribution id is i.  k_generate_list's arithmetic, but every entry
+ * owns its slot (no append), so the queue is dense and keeps the list's order; *q.count is set to the entry count. */
+__global__ __launch_bounds__(256) void k_generate_pixels(PtSceneDev sc, int width, int height, int spp, int first_pass, int n_pass,
+                                                         const int32_t* __restrict__ pix, long long n_list,
+                                                         const double* __restrict__ alpha, PtQueue q) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n = (long long)n_pass * n_list;
+  if (i == 0) *q.count = (uint32_t)n;
+  if (i >= n) return;
+  const long long pass_in_batch = i / n_list, j = i - pass_in_batch * n_list;
+  const int p = pix[j];
+  const int gy = p / width, x = p - gy * width;
+  const int offset = (gy * width) + x + ((first_pass + (int)pass_in_batch) * spp);
+  const double widthf = 1.0 / (double)width, heightf = 1.0 / (double)height;
+  const double dxs = pt_lds_get(alpha, offset, 0), dys = pt_lds_get(alpha, offset, 1);
+  const double cx = ((double)x + dxs) * widthf;
+  const double cy = 1.0 - (((double)gy + dys) * heightf);
+  const V3 dir = pt_camera_dir(sc, cx, cy);
+  if (sc.has_emit) pt_q_store<true>(q, (uint32_t)i, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
+  else pt_q_store<false>(q, (uint32_t)i, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
+}
+
+/* k_accum / k_accum_sq over a pixel list: raw[pix[j]] += contributions pass_in_batch * n_list + j in pass order, sq (nullable) the
+ * squares, as those kernels add them; passes (nullable: the count map) [pix[j]] = pass_end */
+__global__ __launch_bounds__(256) void k_accum_list(PtContrib contrib, long long n_list, int n_pass, const int32_t* __restrict__ pix,
+                                                    double* __restrict__ raw, double* __restrict__ sq, int32_t* __restrict__ passes,
+                                                    int pass_end) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_list) return;
+  const long long p = pix[j];
+  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
+  if (sq) {
+    double sr = sq[3 * p], sg = sq[3 * p + 1], sb = sq[3 * p + 2];
+    for (int k = 0; k < n_pass; ++k) {
+      const double4 c = contrib.rgbx[(long long)k * n_list + j];
+      r = r + c.x;
+      g = g + c.y;
+      b = b + c.z;
+      sr = sr + c.x * c.x;
+      sg = sg + c.y * c.y;
+      sb = sb + c.z * c.z;
+    }
+    sq[3 * p] = sr;
+    sq[3 * p + 1] = sg;
+    sq[3 * p + 2] = sb;
+  } else {
+    for (int k = 0; k < n_pass; ++k) {
+      const double4 c = contrib.rgbx[(long long)k * n_list + j];
+      r = r + c.x;
+      g = g + c.y;
+      b = b + c.z;
+    }
+  }
+  raw[3 * p] = r;
+  raw[3 * p + 1] = g;
+  raw[3 * p + 2] = b;
+  if (passes) passes[p] = pass_end;
+}
+
+/* The stopping rule for a pixel after k passes, evaluated as written (the build has -ffp-contract=off):
+ * se_c = pt_pixel_se(S1_c, S2_c, k), m_c = S1_c / k, e = sqrt((se_r^2 + se_g^2) + se_b^2), d = max(sqrt((m_r^2 + m_g^2) + m_b^2), F);
+ * converged <=> T > 0 and e <= T * d */
+__device__ __forceinline__ bool pt_adaptive_converged(const double* __restrict__ raw, const double* __restrict__ sq, long long p, double kd,
+                                                      double target, double floor_) {
+  const double s1r = raw[3 * p], s1g = raw[3 * p + 1], s1b = raw[3 * p + 2];
+  const double ser = pt_pixel_se(s1r, sq[3 * p], kd), seg = pt_pixel_se(s1g, sq[3 * p + 1], kd), seb = pt_pixel_se(s1b, sq[3 * p + 2], kd);
+  const double mr = s1r / kd, mg = s1g / kd, mb = s1b / kd;
+  const double e = pt_sqrt((ser * ser + seg * seg) + seb * seb);
+  const double m = pt_sqrt((mr * mr + mg * mg) + mb * mb);
+  const double d = m > floor_ ? m : floor_;
+  return target > 0.0 && e <= target * d;
+}
+
+constexpr int PT_SEL_THREADS = 256;
+/* Entry j of the last round's list: pix[j], or with pix == nullptr the whole image in pt_primary_decode's 8x8-tile order (entry j is
+ * tile j / 64, lane j % 64; lanes off the image are never kept) */
+__device__ __forceinline__ long long pt_select_pixel(const int32_t* __restrict__ pix, long long j, int width, int height, int tiles_x) {
+  if (pix) return pix[j];
+  const int tile = (int)(j >> 6), lane = (int)(j & 63);
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+  return (x < width && y < height) ? (long long)y * width + x : -1;
+}
+/* rank of this lane among the workgroup's kept lanes, and the workgroup's kept count (waves in order: no atomics) */
+__device__ __forceinline__ uint32_t pt_select_rank(bool keep, uint32_t* lds_wave, uint32_t* total) {
+  const unsigned long long m = __ballot(keep);
+  const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6);
+  if (lane == 0) lds_wave[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+  for (int w = 0; w < PT_SEL_THREADS / 64; ++w) {
+    if (w < wave) before += lds_wave[w];
+    all += lds_wave[w];
+  }
+  *total = all;
+  return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+/* select, step 1: keep[j] = the pixel has not converged after k passes; block_counts[block] = kept entries of the workgroup */
+__global__ __launch_bounds__(PT_SEL_THREADS) void k_select_count(const int32_t* __restrict__ pix, long long n, int width, int height,
+                                                                 int tiles_x, const double* __restrict__ raw, const double* __restrict__ sq,
+                                                                 int k, double target, double floor_, uint8_t* __restrict__ keep,
+                                                                 uint32_t* __restrict__ block_counts) {
+  __shared__ uint32_t lds_wave[PT_SEL_THREADS / 64];
+  const long long j = (long long)blockIdx.x * PT_SEL_THREADS + threadIdx.x;
+  bool kp = false;
+  if (j < n) {
+    const long long p = pt_select_pixel(pix, j, width, height, tiles_x);
+    kp = p >= 0 && !pt_adaptive_converged(raw, sq, p, (double)k, target, floor_);
+    keep[j] = kp ? 1 : 0;
+  }
+  uint32_t total = 0;
+  (void)pt_select_rank(kp, lds_wave, &total);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+/* select, step 2 (one workgroup): block_offsets = the exclusive prefix sums of block_counts in block order, *n_next their total.
+ * Thread t scans the blocks [t c, (t + 1) c) of a contiguous chunk, the chunks' totals are scanned in LDS. */
+__global__ __launch_bounds__(PT_SEL_THREADS) void k_select_scan(const uint32_t* __restrict__ block_counts, long long n_blocks,
+                                                                uint32_t* __restrict__ block_offsets, int32_t* __restrict__ n_next) {
+  __shared__ uint32_t lds[PT_SEL_THREADS];
+  const long long chunk = (n_blocks + PT_SEL_THREADS - 1) / PT_SEL_THREADS;
+  const long long b0 = (long long)threadIdx.x * chunk, b1 = b0 + chunk < n_blocks ? b0 + chunk : n_blocks;
+  uint32_t s = 0;
+  for (long long b = b0; b < b1; ++b) s += block_counts[b];
+  lds[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 1; off < PT_SEL_THREADS; off <<= 1) { /* inclusive Hillis-Steele scan of the chunk totals */
+    const uint32_t v = (int)threadIdx.x >= off ? lds[threadIdx.x - off] : 0u;
+    __syncthreads();
+    lds[threadIdx.x] += v;
+    __syncthreads();
+  }
+  uint32_t run = threadIdx.x > 0 ? lds[threadIdx.x - 1] : 0u;
+  for (long long b = b0; b < b1; ++b) {
+    block_offsets[b] = run;
+    run += block_counts[b];
+  }
+  if (threadIdx.x == PT_SEL_THREADS - 1) *n_next = (int32_t)lds[PT_SEL_THREADS - 1];
+}
+/* select, step 3: the kept entries' pixels written to out in entry order (the next round's list) */
+__global__ __launch_bounds__(PT_SEL_THREADS) void k_select_scatter(const int32_t* __restrict__ pix, long long n, int width, int height,
+                                                                   int tiles_x, const uint8_t* __restrict__ keep,
+                                                                   const uint32_t* __restrict__ block_offsets, int32_t* __restrict__ out) {
+  __shared__ uint32_t lds_wave[PT_SEL_THREADS / 64];
+  const long long j = (long long)blockIdx.x * PT_SEL_THREADS + threadIdx.x;
+  const bool kp = j < n && keep[j] != 0;
+  uint32_t total = 0;
+  const uint32_t rank = pt_select_rank(kp, lds_wave, &total);
+  if (kp) out[block_offsets[blockIdx.x] + rank] = (int32_t)pt_select_pixel(pix, j, width, height, tiles_x);
+}
+
+/* k_film with a per-pixel pass count n(q) (the count map).  Where every in-image tap has the same count n it is k_film with
+ * spp_inv = 1.0 / n, bit for bit; elsewhere each tap contributes its own mean: sqrt(fma-sum(w * (S(q) * (1.0 / n(q))))). */
+__global__ __launch_bounds__(256) void k_film_counts(const double* __restrict__ raw, const int32_t* __restrict__ passes, int width,
+                                                     int height, PtFilm3 kern, double* __restrict__ out) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (long long)width * height) return;
+  const int x = (int)(p % width), y = (int)(p / width);
+  const int n0 = passes[p];
+  bool same = true;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int sx = x - dx, sy = y - dy;
+      if (sx < 0 || sx >= width || sy < 0 || sy >= height) continue;
+      if (passes[(long long)sy * width + sx] != n0) same = false;
+    }
+  double r = 0.0, g = 0.0, b = 0.0;
+  int k = 0;
+  for (int dy = -1; dy <= 1; ++dy) {
+    const int sy = y - dy;
+    for (int dx = -1; dx <= 1; ++dx, ++k) {
+      const int sx = x - dx;
+      if (sx < 0 || sx >= width || sy < 0 || sy >= height) continue;
+      const long long q = (long long)sy * width + sx;
+      const double* s = raw + q * 3;
+      const double wgt = kern.w[k];
+      if (same) {
+        r = pt_fma(wgt, s[0], r);
+        g = pt_fma(wgt, s[1], g);
+        b = pt_fma(wgt, s[2], b);
+      } else {
+        const double inv = 1.0 / (double)passes[q];
+        r = pt_fma(wgt, s[0] * inv, r);
+        g = pt_fma(wgt, s[1] * inv, g);
+        b = pt_fma(wgt, s[2] * inv, b);
+      }
+    }
+  }
+  if (same) {
+    const double spp_inv = 1.0 / (double)n0;
+    r = r * spp_inv;
+    g = g * spp_inv;
+    b = b * spp_inv;
+  }
+  out[3 * p] = pt_sqrt(r);
+  out[3 * p + 1] = pt_sqrt(g);
+  out[3 * p + 2] = pt_sqrt(b);
+}
+
+/* k_pixel_error with the pixel's own pass count k = passes[p]; the partials are k_error_summary's (called with k = 2: a pixel with
+ * fewer than 2 passes has se = +inf, which the sums carry) */
+__global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error_counts(const double* __restrict__ raw, const double* __restrict__ sq,
+                                                                       const int32_t* __restrict__ passes, long long npix,
+                                                                       double* __restrict__ err, double* __restrict__ partials) {
+  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
+  const long long p = (long long)blockIdx.x * PT_ERR_THREADS + threadIdx.x;
+  double se2 = 0.0, mean2 = 0.0;
+  if (p < npix) {
+    const double kd = (double)passes[p];
+    for (int c = 0; c < 3; ++c) {
+      const double s1 = raw[3 * p + c], se = pt_pixel_se(s1, sq[3 * p + c], kd), m = s1 / kd;
+      if (err) err[3 * p + c] = se;
+      se2 = se2 + se * se;
+      mean2 = mean2 + m * m;
+    }
+  }
+  lds_se[threadIdx.x] = se2;
+  lds_mean[threadIdx.x] = mean2;
+  for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < off) {
+      lds_se[threadIdx.x] = lds_se[threadIdx.x] + lds_se[threadIdx.x + off];
+      lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
+    }
+  }
+  if (threadIdx.x == 0) {
+    partials[2 * (long long)blockIdx.x] = lds_se[0];
+    partials[2 * (long long)blockIdx.x + 1] = lds_mean[0];
+  }
+}
+
 /* ------------------------------------------------------------------ unit entry points */
 __global__ void k_lds_sample(const double* __restrict__ alpha, long long n, const int32_t* __restrict__ offsets,
                              const int32_t* __restrict__ dims, double* __restrict__ out) {

@@ -259,6 +259,12 @@ struct ptx_scene {
   DevBuf<double> raw, rgb;
   DevBuf<double> sq, err, err_partials;     /* ptx_render_progressive: square sums, per-pixel error, k_pixel_error partials + rel_err */
   hipEvent_t ev_update = nullptr;           /* ptx_render_progressive: update j filmed (its copy waits for this) */
+  /* ptx_render_adaptive: the count map and its copy for round j's callback, the two pixel lists (this round's, the next one's), the
+   * select scratch (keep flags, per-workgroup counts and offsets, the next list's length) and the event behind the select */
+  DevBuf<int32_t> passes, passes_img, list[2], sel_n;
+  DevBuf<uint8_t> sel_keep;
+  DevBuf<uint32_t> sel_blocks, sel_offsets;
+  hipEvent_t ev_select = nullptr;
   DevBuf<PtCounters> counters;
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> event_pool;
@@ -755,6 +761,12 @@ struct PassRange {
   int first = 0, count = -1; /* count < 0: the whole frame [0, samples_per_pixel) */
   bool zero = true;
   double* d_sq = nullptr;
+  /* list mode (ptx_render_pixels_device, ptx_render_adaptive): only the n_list pixels of the DEVICE list d_list (whole image,
+   * y * W + x), their camera rays written by k_generate_pixels and bounced from a queue; d_passes (nullable), the count map, gets
+   * the range's end for every listed pixel */
+  const int32_t* d_list = nullptr;
+  long long n_list = 0;
+  int32_t* d_passes = nullptr;
 };
 /* ptx_render's tail (below): row slabs of the frame's last accumulate, an event recorded behind each */
 constexpr int kMaxFinalSlabs = 8;
@@ -771,21 +783,23 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   const int pass_count = range.count < 0 ? p->samples_per_pixel : range.count;
   const int pass_end = pass_first + pass_count;
   const long long npix = (long long)rows * p->width;
+  const bool list = range.d_list != nullptr;
   s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
   s->timed.clear();
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
     fill_tree_stats(s, stats);
   }
-  if (npix == 0) return 0;
+  if (npix == 0 || (list && range.n_list == 0)) return 0;
   if (npix >= 0xffffffffll) return fail(PTX_ERR_ARG, "too many pixels for one rank");
-  /* bounce-0 hit records are indexed by the VIRTUAL primary index (8x8 tiles, ragged edges padded) */
-  const size_t padded = (size_t)((p->width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
-  int ppb = choose_passes_per_batch(p, npix, (long long)padded, pass_count);
+  /* bounce-0 hit records are indexed by the VIRTUAL primary index (8x8 tiles, ragged edges padded); a list's queue is dense */
+  const size_t padded = list ? (size_t)range.n_list : (size_t)((p->width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
+  const long long per_pass = list ? range.n_list : npix; /* samples of one pass */
+  int ppb = choose_passes_per_batch(p, per_pass, (long long)padded, pass_count);
   /* the blocked output queue of k_shade_pool numbers its blocks in 20 bits: 268 M entries per batch */
   while (ppb > 1 && (size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries) --ppb;
   if ((size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries)
-    return fail(PTX_ERR_ARG, "one pass over %lld pixels exceeds the %zu entries a path queue can number (block numbers are 20 bits): render the image in bands", npix, kPoolMaxEntries);
+    return fail(PTX_ERR_ARG, "one pass over %lld pixels exceeds the %zu entries a path queue can number (block numbers are 20 bits): render the image in bands", per_pass, kPoolMaxEntries);
   const size_t cap = (size_t)ppb * padded;
   const int n_batches = (pass_count + ppb - 1) / ppb;
   /* Two batches in flight on two streams: trace is f64-VALU-bound, shade streams ~170 B per segment through
@@ -802,8 +816,9 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
    * caller's buffer, waits for the fork event.  One rank's share of an 8-rank job: 3.53 -> 3.44 ms per step.  (Two frames in
    * flight on two PAIRS of lanes, so that a frame's whole tail overlaps the next frame's head: 3.64 ms, and the full
    * frame 22.9 -> 23.5 ms -- four kernels sharing the CUs cost more than the idle tail they fill; measured, dropped.) */
+  /* (a list is the caller's buffer, read by the first kernel of every batch: list mode always waits for the fork) */
   const bool overlap_frames = (p->flags & PTX_RENDER_ASYNC) && !count && !timed && !progress && !PT_SHADE_TIMING && n_sets >= 2 &&
-                              !s->single_set_last && env_int("PTX_OVERLAP_FRAMES", 1);
+                              !s->single_set_last && !list && env_int("PTX_OVERLAP_FRAMES", 1);
   const int base = 0;
   Workspace ws[kMaxSets];
   int rc = 0;
@@ -857,11 +872,20 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     hipStream_t ls = lanes[set];
     const int n_pass = std::min(ppb, pass_end - first);
     g.first_pass = first; g.n_pass = n_pass;
-    const size_t n_paths = (size_t)n_pass * (size_t)npix;
+    const size_t n_paths = (size_t)n_pass * (size_t)per_pass;
     HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * kCountsWords, ls));
     if (p->max_bounces <= 0) {
       /* loop returns add_mul emit0 attn0 black = 0 for every sample (integrator.ml:31-32) */
       HIP_TRY(hipMemsetAsync(w.contrib_all, 0, sizeof(double) * w.contrib_n, ls));
+    } else if (list) {
+      PtQueue q0 = w.q[0];
+      q0.count = w.counts;
+      {
+        LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
+        hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
+      }
+      run_bounces(s, ls, w, n_paths, p->max_bounces, count, timed, PrimaryLaunch());
     } else {
       PrimaryLaunch pl;
       pl.on = true;
@@ -875,7 +899,10 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_ACCUM);
       const bool last_batch = first + ppb >= pass_end;
-      if (range.d_sq) {
+      if (list) {
+        hipLaunchKernelGGL(k_accum_list, dim3((unsigned)((range.n_list + 255) / 256)), dim3(256), 0, ls, w.contrib, range.n_list, n_pass,
+                           range.d_list, d_raw, range.d_sq, range.d_passes, first + n_pass);
+      } else if (range.d_sq) {
         hipLaunchKernelGGL(k_accum_sq, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ls, w.contrib, npix, n_pass, d_raw, range.d_sq, 0ll, npix);
       } else if (slabs && slabs->n > 1 && last_batch && !timed) {
         /* the frame's last accumulate in row slabs, an event behind each: the caller films and copies slab k while k + 1 is summed */
@@ -932,7 +959,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   }
 #endif
   if (stats) {
-    stats->samples = (int64_t)npix * pass_count;
+    stats->samples = (int64_t)per_pass * pass_count;
     if (count) {
       rc = collect_counters(s, stats);
       if (rc) return rc;
@@ -1170,6 +1197,25 @@ int pixel_error_queue(long long npix, int k, const double* d_raw, const double* 
   const size_t n_blocks = pixel_error_blocks(npix);
   hipLaunchKernelGGL(k_pixel_error, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, npix, k, d_err, d_partials);
   hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, k,
+                     d_partials + 2 * n_blocks);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+/* adaptive sampling: k_film_counts, and k_pixel_error_counts + k_error_summary (d_partials as in pixel_error_queue), queued on st */
+int film_counts_queue(int width, int height, const double* d_raw, const int32_t* d_passes, double* d_out, hipStream_t st) {
+  PtFilm3 k;
+  binomial_3x3(k.w);
+  const long long n = (long long)width * height;
+  hipLaunchKernelGGL(k_film_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, d_passes, width, height, k, d_out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int pixel_error_counts_queue(long long npix, const int32_t* d_passes, const double* d_raw, const double* d_sq, double* d_err,
+                             double* d_partials, hipStream_t st) {
+  const size_t n_blocks = pixel_error_blocks(npix);
+  hipLaunchKernelGGL(k_pixel_error_counts, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, d_passes, npix, d_err, d_partials);
+  hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, 2,
                      d_partials + 2 * n_blocks);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1735,6 +1781,7 @@ void ptx_scene_destroy(ptx_scene* s) {
   }
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_update) (void)hipEventDestroy(s->ev_update);
+  if (s->ev_select) (void)hipEventDestroy(s->ev_select);
   if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
   for (hipEvent_t ev : s->ev_slab)
     if (ev) (void)hipEventDestroy(ev);
@@ -2334,6 +2381,268 @@ int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, cons
   if (stats) {
     *stats = acc;
     stats->samples = (int64_t)npix * k;
+    stats->render_ms = wall_ms() - t0;
+  }
+  return 0;
+}
+
+/* ---- adaptive sampling: rounds of passes for the pixels that have not converged yet ---- */
+namespace {
+int check_one_gpu(const ptx_render_params* p, const char* what) {
+  if (p->n_gpus > 1 || p->band_step > 1)
+    return fail(PTX_ERR_ARG, "%s runs on one GPU over the whole image (n_gpus %d, band_step %d)", what, p->n_gpus, p->band_step);
+  return 0;
+}
+
+int check_device(int32_t device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    (void)hipGetLastError();
+    return fail(PTX_ERR_ARG, "device %d out of range (have %d HIP devices): this library has no CPU fallback", device, ndev);
+  }
+  return 0;
+}
+
+/* every index of the DEVICE list in [0, npix), checked on the device before anything else is queued (waits for st) */
+int check_list_device(ptx_scene* s, const int32_t* d_list, long long n, long long npix, hipStream_t st) {
+  HIP_TRY(s->sel_n.ensure(2)); /* [1]: the flag */
+  HIP_TRY(hipMemsetAsync(s->sel_n.p + 1, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(k_list_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_list, n, npix, s->sel_n.p + 1);
+  HIP_TRY(hipGetLastError());
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, s->sel_n.p + 1, sizeof bad, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (bad) return fail(PTX_ERR_ARG, "the pixel list holds an index outside [0, %lld)", npix);
+  return 0;
+}
+}  // namespace
+
+int32_t ptx_render_pixels_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
+                                 const int32_t* d_pixels, int64_t n_pixels, double* d_raw_inout, double* d_sq_inout, void* stream,
+                                 ptx_stats* stats) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (!d_raw_inout) return fail(PTX_ERR_ARG, "d_raw_inout is NULL");
+  int rc = check_params(p);
+  if (rc) return rc;
+  rc = check_one_gpu(p, "a pixel list");
+  if (rc) return rc;
+  rc = check_pass_range(p, pass_first, pass_count);
+  if (rc) return rc;
+  const long long npix = (long long)p->width * p->height;
+  if (n_pixels < 0 || n_pixels > npix) return fail(PTX_ERR_ARG, "n_pixels %lld is outside [0, %lld]", (long long)n_pixels, npix);
+  if (n_pixels > 0 && !d_pixels) return fail(PTX_ERR_ARG, "d_pixels is NULL");
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  if (n_pixels == 0) {
+    if (stats) {
+      std::memset(stats, 0, sizeof *stats);
+      fill_tree_stats(s, stats);
+    }
+    return 0;
+  }
+  rc = check_list_device(s, d_pixels, n_pixels, npix, (hipStream_t)stream);
+  if (rc) return rc;
+  PassRange range;
+  range.first = pass_first;
+  range.count = pass_count;
+  range.zero = false;
+  range.d_sq = d_sq_inout;
+  range.d_list = d_pixels;
+  range.n_list = n_pixels;
+  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, range);
+  if (rc) return rc;
+  if (stats) stats->render_ms = wall_ms() - t0;
+  return 0;
+}
+
+int32_t ptx_film_resolve_counts_device(int32_t device, int32_t width, int32_t height, const double* d_raw, const int32_t* d_passes,
+                                       double* d_rgb_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the film runs on a HIP device only, no CPU fallback exists", device);
+  if (!d_raw || !d_passes || !d_rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || height <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, height);
+  int rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  rc = film_counts_queue(width, height, d_raw, d_passes, d_rgb_out, (hipStream_t)stream);
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  return rc;
+}
+
+int32_t ptx_pixel_error_counts_device(int32_t device, int32_t width, int32_t rows, const int32_t* d_passes, const double* d_raw,
+                                      const double* d_sq, double* d_err_out, double* rel_err_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
+  if (!d_passes || !d_raw || !d_sq) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || rows <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, rows);
+  int rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const long long npix = (long long)width * rows;
+  LocalBuf<double> part;
+  HIP_TRY(part.ensure(pixel_error_partials(npix)));
+  hipStream_t st = (hipStream_t)stream;
+  rc = pixel_error_counts_queue(npix, d_passes, d_raw, d_sq, d_err_out, part.p, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  double rel = 0.0;
+  HIP_TRY(hipMemcpyAsync(&rel, part.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (rel_err_out) *rel_err_out = rel;
+  return 0;
+}
+
+int32_t ptx_render_adaptive(ptx_scene* s, const ptx_render_params* p_in, const ptx_adaptive_params* ap, double* rgb_out,
+                            double* err_out, int32_t* passes_out, ptx_stats* stats, ptx_round_fn on_round, void* user) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (!ap || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+  int rc = check_params(p_in);
+  if (rc) return rc;
+  rc = check_one_gpu(p_in, "adaptive rendering");
+  if (rc) return rc;
+  if (ap->min_passes < 2) return fail(PTX_ERR_ARG, "min_passes must be >= 2 (got %d)", ap->min_passes);
+  if (ap->passes_per_round < 1) return fail(PTX_ERR_ARG, "passes_per_round must be >= 1 (got %d)", ap->passes_per_round);
+  if (!(ap->target_rel_err >= 0.0)) return fail(PTX_ERR_ARG, "target_rel_err must be >= 0 (got %g)", ap->target_rel_err);
+  if (!(ap->radiance_floor >= 0.0)) return fail(PTX_ERR_ARG, "radiance_floor must be >= 0 (got %g)", ap->radiance_floor);
+  ptx_render_params p = *p_in;
+  p.band_step = 0;
+  p.n_gpus = 0;
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  const int N = p.samples_per_pixel, M = ap->min_passes, K = ap->passes_per_round, W = p.width, H = p.height;
+  const double T = ap->target_rel_err, F = ap->radiance_floor;
+  const long long npix = (long long)W * H;
+  const size_t n = (size_t)npix * 3;
+  const int tiles_x = (W + 7) / 8;
+  const long long padded = (long long)tiles_x * ((H + 7) / 8) * 64; /* the whole image in 8x8-tile order */
+  const size_t max_blocks = (size_t)((padded + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
+  HIP_TRY(s->raw.ensure(n));
+  HIP_TRY(s->sq.ensure(n));
+  HIP_TRY(s->rgb.ensure(n));
+  if (err_out) HIP_TRY(s->err.ensure(n));
+  HIP_TRY(s->err_partials.ensure(pixel_error_partials(npix)));
+  HIP_TRY(s->passes.ensure((size_t)npix));
+  HIP_TRY(s->passes_img.ensure((size_t)npix));
+  HIP_TRY(s->list[0].ensure((size_t)npix));
+  HIP_TRY(s->list[1].ensure((size_t)npix));
+  HIP_TRY(s->sel_n.ensure(2));
+  HIP_TRY(s->sel_keep.ensure((size_t)padded));
+  HIP_TRY(s->sel_blocks.ensure(max_blocks));
+  HIP_TRY(s->sel_offsets.ensure(max_blocks));
+  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+  if (!s->ev_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_update, hipEventDisableTiming));
+  if (!s->ev_select) HIP_TRY(hipEventCreateWithFlags(&s->ev_select, hipEventDisableTiming));
+  DrainOnExit drain;
+  ptx_stats acc, part;
+  std::memset(&acc, 0, sizeof acc);
+  fill_tree_stats(s, &acc);
+  int64_t samples = 0;
+  /* Rounds are queued on the null stream as ptx_render_progressive queues its slices; a round over the whole image is a plain slice
+   * (camera rays decoded in k_bounce), a partial one runs in list mode.  After round j: the film, the error and a copy of the count
+   * map, then the select of round j + 1's list.  The host waits for the select only (it needs the list's length to size the next
+   * round), queues round j + 1, and copies update j out on copy_stream and calls back while round j + 1's bounces run.  A render
+   * that counts work or times kernels queues the next round only after the callback. */
+  const bool ahead = !p.count_work && !p.time_kernels;
+  auto queue_round = [&](int first, int count, const int32_t* lst, long long n_lst) -> int {
+    PassRange r;
+    r.first = first;
+    r.count = count;
+    r.zero = first == 0;
+    r.d_sq = s->sq.p;
+    r.d_list = lst;
+    r.n_list = lst ? n_lst : 0;
+    r.d_passes = s->passes.p;
+    ptx_render_params pq = p;
+    pq.flags = PTX_RENDER_ASYNC;
+    const int r2 = render_raw(s, &pq, s->raw.p, nullptr, &part, nullptr, nullptr, nullptr, r);
+    if (r2) return r2;
+    add_slice_stats(&acc, part);
+    samples += part.samples;
+    if (!lst) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->passes.p, first + count, (size_t)npix, nullptr));
+    return 0;
+  };
+  int b = std::min(M, N);
+  rc = queue_round(0, b, nullptr, npix);
+  if (rc) return rc;
+  const int32_t* cur = nullptr; /* this round's list (nullptr: the whole image) */
+  long long n_cur = npix;
+  int which = 0;                /* the list buffer the next list is written to */
+  int64_t samples_done = 0;
+  for (int round = 1;; ++round) {
+    rc = film_counts_queue(W, H, s->raw.p, s->passes.p, s->rgb.p, nullptr);
+    if (rc) return rc;
+    rc = pixel_error_counts_queue(npix, s->passes.p, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->passes_img.p, s->passes.p, sizeof(int32_t) * (size_t)npix, hipMemcpyDeviceToDevice, nullptr));
+    const int next = std::min(K, N - b);
+    long long n_next = 0;
+    int32_t* next_list = nullptr;
+    if (next > 0 && !(T > 0.0)) {
+      n_next = n_cur; /* T = 0: no pixel converges */
+    } else if (next > 0) {
+      next_list = s->list[which].p;
+      const long long n_sel = cur ? n_cur : padded;
+      const unsigned nb = (unsigned)((n_sel + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
+      hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur, n_sel, W, H, tiles_x, (const double*)s->raw.p,
+                         (const double*)s->sq.p, b, T, F, s->sel_keep.p, s->sel_blocks.p);
+      hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(PT_SEL_THREADS), 0, nullptr, (const uint32_t*)s->sel_blocks.p, (long long)nb,
+                         s->sel_offsets.p, s->sel_n.p);
+      hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur, n_sel, W, H, tiles_x,
+                         (const uint8_t*)s->sel_keep.p, (const uint32_t*)s->sel_offsets.p, next_list);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(s->ev_select, nullptr));
+    }
+    HIP_TRY(hipEventRecord(s->ev_update, nullptr));
+    if (next_list) {
+      int32_t got = 0;
+      HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_select, 0));
+      HIP_TRY(hipMemcpyAsync(&got, s->sel_n.p, sizeof got, hipMemcpyDeviceToHost, s->copy_stream));
+      HIP_TRY(hipStreamSynchronize(s->copy_stream));
+      n_next = got;
+    }
+    /* a list that holds the whole image runs as a plain slice */
+    const int32_t* lst_next = n_next == npix ? nullptr : next_list;
+    samples_done = samples;
+    if (n_next > 0 && ahead) {
+      rc = queue_round(b, next, lst_next, n_next);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_update, 0));
+    rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n, s->copy_stream);
+    if (rc) return rc;
+    if (err_out) {
+      rc = framebuffer_to_host(s, s->err.p, err_out, n, s->copy_stream);
+      if (rc) return rc;
+    }
+    if (passes_out)
+      HIP_TRY(hipMemcpyAsync(passes_out, s->passes_img.p, sizeof(int32_t) * (size_t)npix, hipMemcpyDeviceToHost, s->copy_stream));
+    double rel = 0.0;
+    HIP_TRY(hipMemcpyAsync(&rel, s->err_partials.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, s->copy_stream));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    const bool stop = on_round && on_round(user, round, b, n_next, samples_done, rel, rgb_out, err_out, passes_out) != 0;
+    if (stop || n_next == 0) break;
+    if (!ahead) {
+      rc = queue_round(b, next, lst_next, n_next);
+      if (rc) return rc;
+    }
+    if (lst_next) {
+      cur = lst_next;
+      which ^= 1;
+    } else {
+      cur = nullptr;
+    }
+    n_cur = n_next;
+    b += next;
+  }
+  /* (after an early stop the round queued ahead finishes here; its passes are in the sums only, never in rgb_out) */
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipStreamSynchronize(s->copy_stream));
+  drain.armed = false;
+  if (stats) {
+    *stats = acc;
+    stats->samples = samples_done; /* the sum of the returned count map */
     stats->render_ms = wall_ms() - t0;
   }
   return 0;

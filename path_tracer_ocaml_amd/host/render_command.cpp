@@ -8,7 +8,8 @@
 // shirley_spheres/bin/main.ml:254-267 / render_command.ml:108.  Additions: --scene, --device, --gpus (SURVEY section 5
 // "config / flags": the image spread over N GPUs of the node inside this process, ptx_render_params.n_gpus), and
 // --progressive=K / --target-error=E: -o rewritten after every K passes (ptx_render_progressive), as the photon-map binaries
-// rewrite it after every iteration, stopping early once the frame's relative standard error is at most E.
+// rewrite it after every iteration, stopping early once the frame's relative standard error is at most E; and --adaptive=T
+// (with --progressive=K passes per round and --min-passes=M): per-pixel pass counts, ptx_render_adaptive.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +37,8 @@ struct Args {
   std::string ganesha_ply; // -ganesha-ply <file> (ganesha/bin/main.ml:19-24); empty = synthetic stand-in mesh
   int progressive = 0;       // passes per update; 0 = one ptx_render
   double target_error = 0.0; // stop at the first update whose rel_err is <= this (0 = never)
+  double adaptive = -1.0;    // per-pixel target T of ptx_render_adaptive (< 0: not adaptive)
+  int min_passes = 0;        // --min-passes (0: not given; 8 with --adaptive)
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -44,7 +47,7 @@ struct Args {
                "Usage: %s -d WIDTH,HEIGHT [--samples-per-pixel=INT] [-o PATH] [--no-progress]\n"
                "          [--max-ray-bounces=INT] [--no-simd] [--scene=shirley|cornell|ganesha] [--device=INT] [--gpus=INT]\n"
                "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
-               "          [--progressive=K] [--target-error=FLOAT]\n",
+               "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -91,6 +94,12 @@ Args parse(int argc, char** argv) {
     } else if (take_value(argc, argv, i, "target-error", nullptr, &v)) {
       a.target_error = std::atof(v.c_str());
       if (!(a.target_error > 0.0)) usage(argv[0], "invalid value for --target-error, must be > 0");
+    } else if (take_value(argc, argv, i, "adaptive", nullptr, &v)) {
+      a.adaptive = std::atof(v.c_str());
+      if (!(a.adaptive >= 0.0)) usage(argv[0], "invalid value for --adaptive, must be >= 0");
+    } else if (take_value(argc, argv, i, "min-passes", nullptr, &v)) {
+      a.min_passes = std::atoi(v.c_str());
+      if (a.min_passes < 2) usage(argv[0], "invalid value for --min-passes, must be >= 2");
     }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
@@ -105,6 +114,10 @@ Args parse(int argc, char** argv) {
   if (a.samples_per_pixel < 1) usage(argv[0], "invalid value for --samples-per-pixel, must be >= 1");
   if (a.max_bounces < 0) usage(argv[0], "invalid value for --max-ray-bounces, must be >= 0");
   if (a.gpus < 1) usage(argv[0], "invalid value for --gpus, must be >= 1");
+  const bool adaptive = a.adaptive >= 0.0;
+  if (adaptive && a.target_error > 0.0) usage(argv[0], "--adaptive cannot be combined with --target-error");
+  if (adaptive && a.gpus > 1) usage(argv[0], "--adaptive renders on one GPU (--gpus=1)");
+  if (a.min_passes && !adaptive) usage(argv[0], "--min-passes requires --adaptive");
   if (a.target_error > 0.0 && !a.progressive) usage(argv[0], "--target-error requires --progressive");
   if (a.progressive && a.gpus > 1) usage(argv[0], "--progressive renders on one GPU (--gpus=1)");
   return a;
@@ -140,6 +153,20 @@ struct Updates { // --progressive: the PNG rewritten after every update, one lin
 int32_t on_update(void* user, int32_t passes_done, double rel_err, const double* rgb, const double*) {
   Updates* u = (Updates*)user;
   std::printf("#passes = %d, error = %.6g\n", passes_done, rel_err);
+  std::fflush(stdout);
+  if (pth_write_png(u->output, u->width, u->height, rgb) != 0) {
+    u->write_failed = true;
+    return 1;
+  }
+  return 0;
+}
+
+// --adaptive: the PNG rewritten after every round, one line per round on stdout
+int32_t on_round(void* user, int32_t round, int32_t passes_done, int64_t active_next, int64_t samples, double rel_err,
+                 const double* rgb, const double*, const int32_t*) {
+  Updates* u = (Updates*)user;
+  std::printf("#round = %d, passes = %d, active = %lld, samples = %lld, error = %.6g\n", round, passes_done, (long long)active_next,
+              (long long)samples, rel_err);
   std::fflush(stdout);
   if (pth_write_png(u->output, u->width, u->height, rgb) != 0) {
     u->write_failed = true;
@@ -204,7 +231,16 @@ int main(int argc, char** argv) {
   (void)ptx_image_pin(scene, rgb.data(), (int64_t)rgb.size());
   Updates upd{a.output.c_str(), a.width, a.height};
   int rc;
-  if (a.progressive) {
+  const bool adaptive = a.adaptive >= 0.0;
+  if (adaptive) {
+    ptx_adaptive_params ap;
+    std::memset(&ap, 0, sizeof ap);
+    ap.min_passes = a.min_passes ? a.min_passes : 8;
+    ap.passes_per_round = a.progressive ? a.progressive : 8;
+    ap.target_rel_err = a.adaptive;
+    ap.radiance_floor = 1e-3;
+    rc = ptx_render_adaptive(scene, &p, &ap, rgb.data(), nullptr, nullptr, &st, on_round, &upd);
+  } else if (a.progressive) {
     ptx_progressive_params pp;
     std::memset(&pp, 0, sizeof pp);
     pp.passes_per_update = a.progressive;
@@ -218,7 +254,8 @@ int main(int argc, char** argv) {
   (void)ptx_image_unpin(scene);
   const double elapsed = now_ms() - t0;
   if (rc != 0) {
-    std::fprintf(stderr, "%s: %s\n", a.progressive ? "ptx_render_progressive" : "ptx_render", ptx_last_error());
+    std::fprintf(stderr, "%s: %s\n", adaptive ? "ptx_render_adaptive" : a.progressive ? "ptx_render_progressive" : "ptx_render",
+                 ptx_last_error());
     return 1;
   }
   if (upd.write_failed || pth_write_png(a.output.c_str(), a.width, a.height, rgb.data()) != 0) {

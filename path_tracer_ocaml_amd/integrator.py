@@ -62,6 +62,7 @@ class Integrator:
         self._scene = scene if isinstance(scene, Scene) else Scene(scene.ptr, device, keepalive=scene)
         self.stats = None
         self.error = self.passes_done = None  # render_progressive
+        self.passes = None  # render_adaptive
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0):
@@ -85,6 +86,19 @@ class Integrator:
         if out is None:
             self.image[...] = rgb
         self.error, self.passes_done, self.stats = err, done, st
+        return self.image
+
+    def render_adaptive(self, target_rel_err, min_passes=8, passes_per_round=8, radiance_floor=1e-3, on_round=None):
+        """``render`` with per-pixel pass counts (Scene.render_adaptive): ``image`` holds the image of the last round, ``error``
+        its per-pixel standard error and ``passes`` each pixel's pass count (int32, H x W)."""
+        out = self.image if self.image.flags["C_CONTIGUOUS"] else None
+        rgb, err, passes, st = self._scene.render_adaptive(self.width, self.height, self.samples_per_pixel, self.max_bounces,
+                                                           target_rel_err, min_passes=min_passes,
+                                                           passes_per_round=passes_per_round, radiance_floor=radiance_floor,
+                                                           on_round=on_round, out=out)
+        if out is None:
+            self.image[...] = rgb
+        self.error, self.passes, self.stats = err, passes, st
         return self.image
 
 
