@@ -3081,22 +3081,45 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
 /* ------------------------------------------------------------------ accumulate + film */
 /* raw[pix] += contributions of this batch's passes, in pass order (the order render_tile's pass loop
  * feeds the film, integrator.ml:96) */
+/* The sample-sum core of k_accum, k_accum_sq and k_accum_list: pixel p's sums += contributions j, j + stride, ... of n_pass passes.
+ * SQ: sq also gets each channel's squared contribution in the same pass order, s = s + c * c (the build has -ffp-contract=off, so
+ * the product is rounded before the add, as numpy's s + c * c does) */
+template <bool SQ>
+__device__ __forceinline__ void pt_accum_pixel(const PtContrib& contrib, long long j, long long stride, int n_pass, long long p,
+                                               double* __restrict__ raw, double* __restrict__ sq) {
+  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
+  double sr = 0.0, sg = 0.0, sb = 0.0;
+  if (SQ) {
+    sr = sq[3 * p];
+    sg = sq[3 * p + 1];
+    sb = sq[3 * p + 2];
+  }
+  for (int k = 0; k < n_pass; ++k) {
+    const double4 c = contrib.rgbx[(long long)k * stride + j];
+    r = r + c.x;
+    g = g + c.y;
+    b = b + c.z;
+    if (SQ) {
+      sr = sr + c.x * c.x;
+      sg = sg + c.y * c.y;
+      sb = sb + c.z * c.z;
+    }
+  }
+  raw[3 * p] = r;
+  raw[3 * p + 1] = g;
+  raw[3 * p + 2] = b;
+  if (SQ) {
+    sq[3 * p] = sr;
+    sq[3 * p + 1] = sg;
+    sq[3 * p + 2] = sb;
+  }
+}
 /* [p0, p1): the pixels of this launch -- the whole image, or one row slab of the frame's last batch (ptx_render: the film and the
  * copy of slab k to the host run while slab k + 1 is still being summed) */
 __global__ __launch_bounds__(256) void k_accum(PtContrib contrib, long long npix, int n_pass, double* __restrict__ raw, long long p0, long long p1) {
   const long long p = p0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= p1) return;
-  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
-  for (int k = 0; k < n_pass; ++k) {
-    const long long j = (long long)k * npix + p;
-    const double4 c = contrib.rgbx[j];
-    r = r + c.x;
-    g = g + c.y;
-    b = b + c.z;
-  }
-  raw[3 * p] = r;
-  raw[3 * p + 1] = g;
-  raw[3 * p + 2] = b;
+  pt_accum_pixel<false>(contrib, p, npix, n_pass, p, raw, nullptr);
 }
 
 struct PtFilm3 {
@@ -3145,30 +3168,12 @@ __global__ __launch_bounds__(256) void k_film(const double* __restrict__ raw, in
 }
 
 /* ------------------------------------------------------------------ progressive rendering: second moments + per-pixel error */
-/* k_accum that also sums each channel's squared contribution into sq, in the same pass order: s = s + c * c (the build has
- * -ffp-contract=off, so the product is rounded before the add, as numpy's s + c * c does) */
+/* k_accum that also sums each channel's squared contribution into sq (pt_accum_pixel<true>) */
 __global__ __launch_bounds__(256) void k_accum_sq(PtContrib contrib, long long npix, int n_pass, double* __restrict__ raw,
                                                   double* __restrict__ sq, long long p0, long long p1) {
   const long long p = p0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= p1) return;
-  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
-  double sr = sq[3 * p], sg = sq[3 * p + 1], sb = sq[3 * p + 2];
-  for (int k = 0; k < n_pass; ++k) {
-    const long long j = (long long)k * npix + p;
-    const double4 c = contrib.rgbx[j];
-    r = r + c.x;
-    g = g + c.y;
-    b = b + c.z;
-    sr = sr + c.x * c.x;
-    sg = sg + c.y * c.y;
-    sb = sb + c.z * c.z;
-  }
-  raw[3 * p] = r;
-  raw[3 * p + 1] = g;
-  raw[3 * p + 2] = b;
-  sq[3 * p] = sr;
-  sq[3 * p + 1] = sg;
-  sq[3 * p + 2] = sb;
+  pt_accum_pixel<true>(contrib, p, npix, n_pass, p, raw, sq);
 }
 
 /* Standard error of a pixel channel's sample mean after k passes, from S1 = sum c and S2 = sum c^2:
@@ -3181,24 +3186,9 @@ __device__ __forceinline__ double pt_pixel_se(double s1, double s2, double kd) {
 }
 
 constexpr int PT_ERR_THREADS = 256;
-/* One pixel per thread: err (optional, 3 per pixel) and, per workgroup, partials[2 block] = sum of se^2 and partials[2 block + 1]
- * = sum of (S1 / k)^2 over its pixels and channels, both summed in a fixed tree order (no atomics: the same sums give the same
- * bits on every run) */
-__global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error(const double* __restrict__ raw, const double* __restrict__ sq,
-                                                                long long npix, int k, double* __restrict__ err,
-                                                                double* __restrict__ partials) {
-  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
-  const long long p = (long long)blockIdx.x * PT_ERR_THREADS + threadIdx.x;
-  double se2 = 0.0, mean2 = 0.0;
-  if (p < npix) {
-    const double kd = (double)k;
-    for (int c = 0; c < 3; ++c) {
-      const double s1 = raw[3 * p + c], se = pt_pixel_se(s1, sq[3 * p + c], kd), m = s1 / kd;
-      if (err) err[3 * p + c] = se;
-      se2 = se2 + se * se;
-      mean2 = mean2 + m * m;
-    }
-  }
+/* The workgroup's (se^2, mean^2) pairs summed in a fixed tree order (no atomics: the same sums give the same bits on every run);
+ * thread 0 finds the totals in lds_se[0] and lds_mean[0] */
+__device__ __forceinline__ void pt_error_block_sum(double se2, double mean2, double* lds_se, double* lds_mean) {
   lds_se[threadIdx.x] = se2;
   lds_mean[threadIdx.x] = mean2;
   for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
@@ -3208,10 +3198,36 @@ __global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error(const double* __
       lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
     }
   }
+}
+/* The body of k_pixel_error and k_pixel_error_counts.  One pixel per thread, after k passes (COUNTS: the pixel's own passes[p]):
+ * err (optional, 3 per pixel) and, per workgroup, partials[2 block] = sum of se^2 and partials[2 block + 1] = sum of
+ * (S1 / k)^2 over its pixels and channels (pt_error_block_sum) */
+template <bool COUNTS>
+__device__ __forceinline__ void pt_pixel_error_block(const double* __restrict__ raw, const double* __restrict__ sq,
+                                                     const int32_t* __restrict__ passes, int k, long long npix, double* __restrict__ err,
+                                                     double* __restrict__ partials) {
+  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
+  const long long p = (long long)blockIdx.x * PT_ERR_THREADS + threadIdx.x;
+  double se2 = 0.0, mean2 = 0.0;
+  if (p < npix) {
+    const double kd = (double)(COUNTS ? passes[p] : k);
+    for (int c = 0; c < 3; ++c) {
+      const double s1 = raw[3 * p + c], se = pt_pixel_se(s1, sq[3 * p + c], kd), m = s1 / kd;
+      if (err) err[3 * p + c] = se;
+      se2 = se2 + se * se;
+      mean2 = mean2 + m * m;
+    }
+  }
+  pt_error_block_sum(se2, mean2, lds_se, lds_mean);
   if (threadIdx.x == 0) {
     partials[2 * (long long)blockIdx.x] = lds_se[0];
     partials[2 * (long long)blockIdx.x + 1] = lds_mean[0];
   }
+}
+__global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error(const double* __restrict__ raw, const double* __restrict__ sq,
+                                                                long long npix, int k, double* __restrict__ err,
+                                                                double* __restrict__ partials) {
+  pt_pixel_error_block<false>(raw, sq, nullptr, k, npix, err, partials);
 }
 
 /* One workgroup: the frame summary rel_err = sqrt(sum se^2) / sqrt(sum mean^2) from k_pixel_error's n_blocks partial pairs, in a
@@ -3224,15 +3240,7 @@ __global__ __launch_bounds__(PT_ERR_THREADS) void k_error_summary(const double* 
     se2 = se2 + partials[2 * b];
     mean2 = mean2 + partials[2 * b + 1];
   }
-  lds_se[threadIdx.x] = se2;
-  lds_mean[threadIdx.x] = mean2;
-  for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < off) {
-      lds_se[threadIdx.x] = lds_se[threadIdx.x] + lds_se[threadIdx.x + off];
-      lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
-    }
-  }
+  pt_error_block_sum(se2, mean2, lds_se, lds_mean);
   if (threadIdx.x == 0) {
     const double a = lds_se[0], m = lds_mean[0];
     *rel_err = k < 2 ? __builtin_inf() : (a == 0.0 && m == 0.0) ? 0.0 : pt_sqrt(a) / pt_sqrt(m);
@@ -3279,32 +3287,8 @@ __global__ __launch_bounds__(256) void k_accum_list(PtContrib contrib, long long
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n_list) return;
   const long long p = pix[j];
-  double r = raw[3 * p], g = raw[3 * p + 1], b = raw[3 * p + 2];
-  if (sq) {
-    double sr = sq[3 * p], sg = sq[3 * p + 1], sb = sq[3 * p + 2];
-    for (int k = 0; k < n_pass; ++k) {
-      const double4 c = contrib.rgbx[(long long)k * n_list + j];
-      r = r + c.x;
-      g = g + c.y;
-      b = b + c.z;
-      sr = sr + c.x * c.x;
-      sg = sg + c.y * c.y;
-      sb = sb + c.z * c.z;
-    }
-    sq[3 * p] = sr;
-    sq[3 * p + 1] = sg;
-    sq[3 * p + 2] = sb;
-  } else {
-    for (int k = 0; k < n_pass; ++k) {
-      const double4 c = contrib.rgbx[(long long)k * n_list + j];
-      r = r + c.x;
-      g = g + c.y;
-      b = b + c.z;
-    }
-  }
-  raw[3 * p] = r;
-  raw[3 * p + 1] = g;
-  raw[3 * p + 2] = b;
+  if (sq) pt_accum_pixel<true>(contrib, j, n_list, n_pass, p, raw, sq);
+  else pt_accum_pixel<false>(contrib, j, n_list, n_pass, p, raw, nullptr);
   if (passes) passes[p] = pass_end;
 }
 
@@ -3452,31 +3436,7 @@ __global__ __launch_bounds__(256) void k_film_counts(const double* __restrict__ 
 __global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error_counts(const double* __restrict__ raw, const double* __restrict__ sq,
                                                                        const int32_t* __restrict__ passes, long long npix,
                                                                        double* __restrict__ err, double* __restrict__ partials) {
-  __shared__ double lds_se[PT_ERR_THREADS], lds_mean[PT_ERR_THREADS];
-  const long long p = (long long)blockIdx.x * PT_ERR_THREADS + threadIdx.x;
-  double se2 = 0.0, mean2 = 0.0;
-  if (p < npix) {
-    const double kd = (double)passes[p];
-    for (int c = 0; c < 3; ++c) {
-      const double s1 = raw[3 * p + c], se = pt_pixel_se(s1, sq[3 * p + c], kd), m = s1 / kd;
-      if (err) err[3 * p + c] = se;
-      se2 = se2 + se * se;
-      mean2 = mean2 + m * m;
-    }
-  }
-  lds_se[threadIdx.x] = se2;
-  lds_mean[threadIdx.x] = mean2;
-  for (int off = PT_ERR_THREADS / 2; off > 0; off >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < off) {
-      lds_se[threadIdx.x] = lds_se[threadIdx.x] + lds_se[threadIdx.x + off];
-      lds_mean[threadIdx.x] = lds_mean[threadIdx.x] + lds_mean[threadIdx.x + off];
-    }
-  }
-  if (threadIdx.x == 0) {
-    partials[2 * (long long)blockIdx.x] = lds_se[0];
-    partials[2 * (long long)blockIdx.x + 1] = lds_mean[0];
-  }
+  pt_pixel_error_block<true>(raw, sq, passes, 0, npix, err, partials);
 }
 
 /* ------------------------------------------------------------------ unit entry points */

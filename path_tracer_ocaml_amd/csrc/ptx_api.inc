@@ -754,7 +754,7 @@ int choose_passes_per_batch(const ptx_render_params* p, long long npix, long lon
 }
 
 /* the whole integrator for this rank's rows -> raw per-pixel sums at d_raw (rows*W*3) */
-/* A slice of the frame (ptx_render_passes_device, ptx_render_progressive): passes [pass_first, pass_first + pass_count) of the
+/* A slice of the frame (ptx_render_passes_device, render_updates): passes [pass_first, pass_first + pass_count) of the
  * frame of p->samples_per_pixel passes (the sampler offsets depend on that total), ADDED to d_raw when zero is false; d_sq, if
  * given, receives the sums of the squared contributions in the same order (k_accum_sq) */
 struct PassRange {
@@ -767,6 +767,15 @@ struct PassRange {
   const int32_t* d_list = nullptr;
   long long n_list = 0;
   int32_t* d_passes = nullptr;
+  PassRange() = default;
+  PassRange(int first_, int count_, bool zero_, double* d_sq_) : first(first_), count(count_), zero(zero_), d_sq(d_sq_) {}
+  PassRange listed(const int32_t* list, long long n, int32_t* passes) const { /* list == nullptr: the whole image */
+    PassRange r = *this;
+    r.d_list = list;
+    r.n_list = list ? n : 0;
+    r.d_passes = passes;
+    return r;
+  }
 };
 /* ptx_render's tail (below): row slabs of the frame's last accumulate, an event recorded behind each */
 constexpr int kMaxFinalSlabs = 8;
@@ -776,39 +785,51 @@ struct FinalSlabs {
   hipEvent_t done[kMaxFinalSlabs] = {};
   bool used = false;                  /* out: the last batch was accumulated in slabs and the events were recorded */
 };
-int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStream_t st, ptx_stats* stats,
-               ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr, const PassRange& range = PassRange()) {
-  const int rows = local_rows(p);
-  const int pass_first = range.count < 0 ? 0 : range.first;
-  const int pass_count = range.count < 0 ? p->samples_per_pixel : range.count;
-  const int pass_end = pass_first + pass_count;
-  const long long npix = (long long)rows * p->width;
-  const bool list = range.d_list != nullptr;
-  s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
-  s->timed.clear();
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    fill_tree_stats(s, stats);
-  }
-  if (npix == 0 || (list && range.n_list == 0)) return 0;
-  if (npix >= 0xffffffffll) return fail(PTX_ERR_ARG, "too many pixels for one rank");
+
+/* render_raw, piece 1: how the range's passes are cut into batches and how many of them are in flight */
+struct BatchPlan {
+  int rows = 0, pass_first = 0, pass_count = 0, pass_end = 0;
+  long long npix = 0, per_pass = 0; /* pixels of this rank; samples of one pass (the list's length in list mode) */
+  bool list = false;
+  size_t padded = 0, cap = 0;       /* entries of one pass in a queue; of one batch */
+  int ppb = 0, n_batches = 0, n_sets = 0;
+};
+int plan_batches(ptx_scene* s, const ptx_render_params* p, const PassRange& range, BatchPlan* out) {
+  BatchPlan& b = *out = BatchPlan();
+  b.rows = local_rows(p);
+  b.pass_first = range.count < 0 ? 0 : range.first;
+  b.pass_count = range.count < 0 ? p->samples_per_pixel : range.count;
+  b.pass_end = b.pass_first + b.pass_count;
+  b.npix = (long long)b.rows * p->width;
+  b.list = range.d_list != nullptr;
+  if (b.npix == 0 || (b.list && range.n_list == 0)) return 0; /* n_batches stays 0: nothing to render */
+  if (b.npix >= 0xffffffffll) return fail(PTX_ERR_ARG, "too many pixels for one rank");
   /* bounce-0 hit records are indexed by the VIRTUAL primary index (8x8 tiles, ragged edges padded); a list's queue is dense */
-  const size_t padded = list ? (size_t)range.n_list : (size_t)((p->width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
-  const long long per_pass = list ? range.n_list : npix; /* samples of one pass */
-  int ppb = choose_passes_per_batch(p, per_pass, (long long)padded, pass_count);
+  b.padded = b.list ? (size_t)range.n_list : (size_t)((p->width + 7) / 8) * (size_t)((b.rows + 7) / 8) * 64;
+  b.per_pass = b.list ? range.n_list : b.npix;
+  b.ppb = choose_passes_per_batch(p, b.per_pass, (long long)b.padded, b.pass_count);
   /* the blocked output queue of k_shade_pool numbers its blocks in 20 bits: 268 M entries per batch */
-  while (ppb > 1 && (size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries) --ppb;
-  if ((size_t)ppb * padded + shade_pool_slack(s) >= kPoolMaxEntries)
-    return fail(PTX_ERR_ARG, "one pass over %lld pixels exceeds the %zu entries a path queue can number (block numbers are 20 bits): render the image in bands", per_pass, kPoolMaxEntries);
-  const size_t cap = (size_t)ppb * padded;
-  const int n_batches = (pass_count + ppb - 1) / ppb;
+  while (b.ppb > 1 && (size_t)b.ppb * b.padded + shade_pool_slack(s) >= kPoolMaxEntries) --b.ppb;
+  if ((size_t)b.ppb * b.padded + shade_pool_slack(s) >= kPoolMaxEntries)
+    return fail(PTX_ERR_ARG, "one pass over %lld pixels exceeds the %zu entries a path queue can number (block numbers are 20 bits): render the image in bands", b.per_pass, kPoolMaxEntries);
+  b.cap = (size_t)b.ppb * b.padded;
+  b.n_batches = (b.pass_count + b.ppb - 1) / b.ppb;
   /* Two batches in flight on two streams: trace is f64-VALU-bound, shade streams ~170 B per segment through
    * HBM; run side by side, one batch's shade fills the memory pipes while the other's trace fills the SIMDs. */
-  int n_sets = (n_batches >= 2 && p->max_bounces > 0) ? 2 : 1;
-  if (const char* e = getenv("PTX_STREAMS")) n_sets = std::max(1, std::min(kMaxSets, atoi(e)));
-  n_sets = std::min(n_sets, n_batches);
-  s->sets_in_flight = n_sets;
-  const bool count = p->count_work != 0, timed = p->time_kernels != 0;
+  b.n_sets = (b.n_batches >= 2 && p->max_bounces > 0) ? 2 : 1;
+  if (const char* e = getenv("PTX_STREAMS")) b.n_sets = std::max(1, std::min(kMaxSets, atoi(e)));
+  b.n_sets = std::min(b.n_sets, b.n_batches);
+  s->sets_in_flight = b.n_sets;
+  return 0;
+}
+
+/* render_raw, piece 2: the lanes the batches run on (batch k on lane k % n_sets; one set: the caller's stream itself) */
+struct Lanes {
+  hipStream_t lane[kMaxSets] = {};
+  bool overlap_frames = false;
+};
+/* fork: the lanes start after everything already queued on the caller's stream (a queued frame: only its k_accum does) */
+int fork_lanes(ptx_scene* s, const ptx_render_params* p, const BatchPlan& b, hipStream_t st, bool has_progress, Lanes* l) {
   /* A QUEUED frame's bounces (PTX_RENDER_ASYNC) read the scene and this handle's workspace only, both ordered by the lanes
    * themselves, so they do not wait for what the caller's stream still carries -- the previous frame's join, band exchange and
    * film: a lane that has finished its batch of frame k starts frame k + 1 while the other lane still runs frame k's last
@@ -817,106 +838,151 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
    * flight on two PAIRS of lanes, so that a frame's whole tail overlaps the next frame's head: 3.64 ms, and the full
    * frame 22.9 -> 23.5 ms -- four kernels sharing the CUs cost more than the idle tail they fill; measured, dropped.) */
   /* (a list is the caller's buffer, read by the first kernel of every batch: list mode always waits for the fork) */
-  const bool overlap_frames = (p->flags & PTX_RENDER_ASYNC) && !count && !timed && !progress && !PT_SHADE_TIMING && n_sets >= 2 &&
-                              !s->single_set_last && !list && env_int("PTX_OVERLAP_FRAMES", 1);
-  const int base = 0;
-  Workspace ws[kMaxSets];
-  int rc = 0;
-  for (int k = 0; k < n_sets; ++k) {
-    rc = ensure_workspace(s, cap, p->max_bounces, &ws[k], base + k);
-    if (rc) return rc;
+  l->overlap_frames = (p->flags & PTX_RENDER_ASYNC) && !p->count_work && !p->time_kernels && !has_progress && !PT_SHADE_TIMING &&
+                      b.n_sets >= 2 && !s->single_set_last && !b.list && env_int("PTX_OVERLAP_FRAMES", 1);
+  s->single_set_last = b.n_sets < 2; /* (crosses calls: the next frame's overlap rule reads it) */
+  for (int k = 0; k < kMaxSets; ++k) l->lane[k] = st;
+  if (b.n_sets < 2) return 0;
+  for (int k = 0; k < b.n_sets; ++k) {
+    if (!s->streams[k]) HIP_TRY(hipStreamCreateWithFlags(&s->streams[k], hipStreamNonBlocking));
+    if (!s->ev_accum[k]) HIP_TRY(hipEventCreateWithFlags(&s->ev_accum[k], hipEventDisableTiming));
+    if (!s->ev_join[k]) HIP_TRY(hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming));
+    l->lane[k] = s->streams[k];
   }
-  s->single_set_last = n_sets < 2;
-  if (range.zero) {
-    HIP_TRY(hipMemsetAsync(d_raw, 0, sizeof(double) * (size_t)npix * 3, st));
-    if (range.d_sq) HIP_TRY(hipMemsetAsync(range.d_sq, 0, sizeof(double) * (size_t)npix * 3, st));
+  if (!s->ev_fork) HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(s->ev_fork, st));
+  if (!l->overlap_frames)
+    for (int k = 0; k < b.n_sets; ++k) HIP_TRY(hipStreamWaitEvent(l->lane[k], s->ev_fork, 0));
+  return 0;
+}
+/* join: the caller's stream continues after every lane */
+int join_lanes(ptx_scene* s, const BatchPlan& b, const Lanes& l, hipStream_t st) {
+  for (int k = 0; k < b.n_sets && b.n_sets >= 2; ++k) {
+    HIP_TRY(hipEventRecord(s->ev_join[k], l.lane[k]));
+    HIP_TRY(hipStreamWaitEvent(st, s->ev_join[k], 0));
   }
-  if (count) HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(PtCounters), st));
-  hipStream_t lanes[kMaxSets];
-  hipEvent_t* ev_accum = s->ev_accum + base;
-  hipEvent_t* ev_join = s->ev_join + base;
-  hipEvent_t& ev_fork = s->ev_fork;
-  for (int k = 0; k < kMaxSets; ++k) lanes[k] = st;
-  if (n_sets >= 2) {
-    for (int k = 0; k < n_sets; ++k) {
-      if (!s->streams[base + k]) HIP_TRY(hipStreamCreateWithFlags(&s->streams[base + k], hipStreamNonBlocking));
-      if (!ev_accum[k]) HIP_TRY(hipEventCreateWithFlags(&ev_accum[k], hipEventDisableTiming));
-      if (!ev_join[k]) HIP_TRY(hipEventCreateWithFlags(&ev_join[k], hipEventDisableTiming));
-      lanes[k] = s->streams[base + k];
+  return 0;
+}
+
+/* render_raw, piece 3: one batch's camera rays and bounces on its lane -> the batch's contributions in w.contrib */
+int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan& b, const PassRange& range, Workspace& w, hipStream_t ls,
+                      int first, int n_pass) {
+  const bool count = p->count_work != 0, timed = p->time_kernels != 0;
+  const size_t n_paths = (size_t)n_pass * (size_t)b.per_pass;
+  HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * kCountsWords, ls));
+  if (p->max_bounces <= 0) {
+    /* loop returns add_mul emit0 attn0 black = 0 for every sample (integrator.ml:31-32) */
+    HIP_TRY(hipMemsetAsync(w.contrib_all, 0, sizeof(double) * w.contrib_n, ls));
+  } else if (b.list) {
+    PtQueue q0 = w.q[0];
+    q0.count = w.counts;
+    {
+      LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
+      hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                         p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
     }
-    if (!ev_fork) HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    /* fork: the lanes start after everything already queued on the caller's stream (a queued frame: only its k_accum does) */
-    HIP_TRY(hipEventRecord(ev_fork, st));
-    if (!overlap_frames)
-      for (int k = 0; k < n_sets; ++k) HIP_TRY(hipStreamWaitEvent(lanes[k], ev_fork, 0));
+    run_bounces(s, ls, w, n_paths, p->max_bounces, count, timed, PrimaryLaunch());
+  } else {
+    PrimaryLaunch pl;
+    pl.on = true;
+    PtGenParams& g = pl.g;
+    g.width = p->width; g.height = p->height; g.spp = p->samples_per_pixel; g.local_rows = b.rows;
+    g.band_rows = p->band_rows > 0 ? p->band_rows : 32; g.band_first = p->band_first; g.band_step = p->band_step;
+    g.tiles_x = (p->width + 7) / 8; g.tiles_y = (b.rows + 7) / 8;
+    g.first_pass = first; g.n_pass = n_pass;
+    pl.n = (uint32_t)((size_t)n_pass * (size_t)g.tiles_x * (size_t)g.tiles_y * 64u);
+    run_bounces(s, ls, w, std::max<size_t>(n_paths, pl.n), p->max_bounces, count, timed, pl);
   }
-  /* Grids cover the whole chip for every batch in flight; how many workgroups a CU takes of each kernel is decided per launch
-   * (share_cus: half a CU each on Simd_leaf LDS scenes). */
-  s->grid_div = std::max(1, env_int("PTX_GRID_DIV", 1));
+  return 0;
+}
+
+/* render_raw, piece 4: one batch's contributions added to the caller's sums -- the only place that knows about squares, lists,
+ * count maps and row slabs */
+int queue_batch_accumulate(ptx_scene* s, const ptx_render_params* p, const BatchPlan& b, const PassRange& range, FinalSlabs* slabs,
+                           const Workspace& w, hipStream_t ls, double* d_raw, int first, int n_pass) {
+  const bool timed = p->time_kernels != 0, last_batch = first + b.ppb >= b.pass_end;
+  LaunchTimer t(s, ls, timed, PTX_KERNEL_ACCUM);
+  const dim3 grid((unsigned)((b.per_pass + 255) / 256)), block(256);
+  if (b.list) {
+    hipLaunchKernelGGL(k_accum_list, grid, block, 0, ls, w.contrib, range.n_list, n_pass, range.d_list, d_raw, range.d_sq, range.d_passes,
+                       first + n_pass);
+  } else if (range.d_sq) {
+    hipLaunchKernelGGL(k_accum_sq, grid, block, 0, ls, w.contrib, b.npix, n_pass, d_raw, range.d_sq, 0ll, b.npix);
+  } else if (slabs && slabs->n > 1 && last_batch && !timed) {
+    /* the frame's last accumulate in row slabs, an event behind each: the caller films and copies slab k while k + 1 is summed */
+    for (int k = 0; k < slabs->n; ++k) {
+      const long long q0 = (long long)slabs->row[k] * p->width, q1 = (long long)slabs->row[k + 1] * p->width;
+      if (q1 > q0) hipLaunchKernelGGL(k_accum, dim3((unsigned)((q1 - q0 + 255) / 256)), block, 0, ls, w.contrib, b.npix, n_pass, d_raw, q0, q1);
+      HIP_TRY(hipEventRecord(slabs->done[k], ls));
+    }
+    slabs->used = true;
+  } else {
+    hipLaunchKernelGGL(k_accum, grid, block, 0, ls, w.contrib, b.npix, n_pass, d_raw, 0ll, b.npix);
+  }
+  return 0;
+}
+
+/* render_raw, piece 5: update_progress gets pixel areas summing to W*H (integrator.ml:150, render_command.ml:87-103).  The batches
+ * keep running on both streams; the host only waits for their accumulate steps in order, on the calling thread. */
+int wait_progress(const BatchPlan& b, const std::vector<hipEvent_t>& batch_done, ptx_progress_fn progress, void* user) {
+  long long done_pixels_reported = 0;
+  int k = 0;
+  for (int first = b.pass_first; first < b.pass_end; first += b.ppb, ++k) {
+    HIP_TRY(hipEventSynchronize(batch_done[(size_t)k]));
+    const int n_pass = std::min(b.ppb, b.pass_end - first);
+    const long long upto = (long long)((double)(first - b.pass_first + n_pass) / b.pass_count * (double)b.npix);
+    progress(user, upto - done_pixels_reported);
+    done_pixels_reported = upto;
+  }
+  return 0;
+}
+
+int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStream_t st, ptx_stats* stats,
+               ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr, const PassRange& range = PassRange()) {
+  s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
+  s->timed.clear();
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    fill_tree_stats(s, stats);
+  }
   struct GridDivGuard { /* every exit path, also the HIP_TRY ones, leaves later launches on this scene with whole grids */
     ptx_scene* s;
     ~GridDivGuard() { s->grid_div = 1; s->sets_in_flight = 1; }
   } grid_div_guard{s};
+  BatchPlan b;
+  int rc = plan_batches(s, p, range, &b);
+  if (rc || b.n_batches == 0) return rc;
+  const bool count = p->count_work != 0, timed = p->time_kernels != 0;
+  Workspace ws[kMaxSets];
+  for (int k = 0; k < b.n_sets; ++k) {
+    rc = ensure_workspace(s, b.cap, p->max_bounces, &ws[k], k);
+    if (rc) return rc;
+  }
+  if (range.zero) {
+    HIP_TRY(hipMemsetAsync(d_raw, 0, sizeof(double) * (size_t)b.npix * 3, st));
+    if (range.d_sq) HIP_TRY(hipMemsetAsync(range.d_sq, 0, sizeof(double) * (size_t)b.npix * 3, st));
+  }
+  if (count) HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(PtCounters), st));
+  Lanes l;
+  rc = fork_lanes(s, p, b, st, progress != nullptr, &l);
+  if (rc) return rc;
+  /* Grids cover the whole chip for every batch in flight; how many workgroups a CU takes of each kernel is decided per launch
+   * (share_cus: half a CU each on Simd_leaf LDS scenes). */
+  s->grid_div = std::max(1, env_int("PTX_GRID_DIV", 1));
   std::vector<hipEvent_t> batch_done; /* progress: one event per batch, waited for in order after everything is queued */
-
-  PtGenParams g;
-  g.width = p->width; g.height = p->height; g.spp = p->samples_per_pixel; g.local_rows = rows;
-  g.band_rows = p->band_rows > 0 ? p->band_rows : 32; g.band_first = p->band_first; g.band_step = p->band_step;
-  g.tiles_x = (p->width + 7) / 8; g.tiles_y = (rows + 7) / 8;
-
-  long long done_pixels_reported = 0;
   int batch = 0;
-  for (int first = pass_first; first < pass_end; first += ppb, ++batch) {
-    const int set = batch % n_sets;
-    Workspace& w = ws[set];
-    hipStream_t ls = lanes[set];
-    const int n_pass = std::min(ppb, pass_end - first);
-    g.first_pass = first; g.n_pass = n_pass;
-    const size_t n_paths = (size_t)n_pass * (size_t)per_pass;
-    HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * kCountsWords, ls));
-    if (p->max_bounces <= 0) {
-      /* loop returns add_mul emit0 attn0 black = 0 for every sample (integrator.ml:31-32) */
-      HIP_TRY(hipMemsetAsync(w.contrib_all, 0, sizeof(double) * w.contrib_n, ls));
-    } else if (list) {
-      PtQueue q0 = w.q[0];
-      q0.count = w.counts;
-      {
-        LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-        hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
-      }
-      run_bounces(s, ls, w, n_paths, p->max_bounces, count, timed, PrimaryLaunch());
-    } else {
-      PrimaryLaunch pl;
-      pl.on = true;
-      pl.g = g;
-      pl.n = (uint32_t)((size_t)n_pass * (size_t)g.tiles_x * (size_t)g.tiles_y * 64u);
-      run_bounces(s, ls, w, std::max<size_t>(n_paths, pl.n), p->max_bounces, count, timed, pl);
-    }
+  for (int first = b.pass_first; first < b.pass_end; first += b.ppb, ++batch) {
+    const int set = batch % b.n_sets;
+    hipStream_t ls = l.lane[set];
+    const int n_pass = std::min(b.ppb, b.pass_end - first);
+    rc = queue_batch_paths(s, p, b, range, ws[set], ls, first, n_pass);
+    if (rc) return rc;
     /* raw sums are accumulated in PASS order: batch k's accumulate runs after batch k-1's */
-    if (n_sets >= 2 && batch > 0) HIP_TRY(hipStreamWaitEvent(ls, ev_accum[(batch - 1) % n_sets], 0));
-    if (n_sets >= 2 && overlap_frames && batch < n_sets) HIP_TRY(hipStreamWaitEvent(ls, ev_fork, 0)); /* the caller's buffer: see the fork */
-    {
-      LaunchTimer t(s, ls, timed, PTX_KERNEL_ACCUM);
-      const bool last_batch = first + ppb >= pass_end;
-      if (list) {
-        hipLaunchKernelGGL(k_accum_list, dim3((unsigned)((range.n_list + 255) / 256)), dim3(256), 0, ls, w.contrib, range.n_list, n_pass,
-                           range.d_list, d_raw, range.d_sq, range.d_passes, first + n_pass);
-      } else if (range.d_sq) {
-        hipLaunchKernelGGL(k_accum_sq, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ls, w.contrib, npix, n_pass, d_raw, range.d_sq, 0ll, npix);
-      } else if (slabs && slabs->n > 1 && last_batch && !timed) {
-        /* the frame's last accumulate in row slabs, an event behind each: the caller films and copies slab k while k + 1 is summed */
-        for (int k = 0; k < slabs->n; ++k) {
-          const long long q0 = (long long)slabs->row[k] * p->width, q1 = (long long)slabs->row[k + 1] * p->width;
-          if (q1 > q0) hipLaunchKernelGGL(k_accum, dim3((unsigned)((q1 - q0 + 255) / 256)), dim3(256), 0, ls, w.contrib, npix, n_pass, d_raw, q0, q1);
-          HIP_TRY(hipEventRecord(slabs->done[k], ls));
-        }
-        slabs->used = true;
-      } else {
-        hipLaunchKernelGGL(k_accum, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ls, w.contrib, npix, n_pass, d_raw, 0ll, npix);
-      }
-    }
-    if (n_sets >= 2) HIP_TRY(hipEventRecord(ev_accum[set], ls));
+    if (b.n_sets >= 2 && batch > 0) HIP_TRY(hipStreamWaitEvent(ls, s->ev_accum[(batch - 1) % b.n_sets], 0));
+    if (b.n_sets >= 2 && l.overlap_frames && batch < b.n_sets) HIP_TRY(hipStreamWaitEvent(ls, s->ev_fork, 0)); /* the caller's buffer: see the fork */
+    rc = queue_batch_accumulate(s, p, b, range, slabs, ws[set], ls, d_raw, first, n_pass);
+    if (rc) return rc;
+    if (b.n_sets >= 2) HIP_TRY(hipEventRecord(s->ev_accum[set], ls));
     HIP_TRY(hipGetLastError());
     if (progress) {
       const hipEvent_t ev = scene_event(s);
@@ -925,23 +991,11 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     }
   }
   if (progress) {
-    /* update_progress gets pixel areas summing to W*H (integrator.ml:150, render_command.ml:87-103).  The batches keep
-     * running on both streams; the host only waits for their accumulate steps in order, on the calling thread. */
-    int b = 0;
-    for (int first = pass_first; first < pass_end; first += ppb, ++b) {
-      HIP_TRY(hipEventSynchronize(batch_done[(size_t)b]));
-      const int n_pass = std::min(ppb, pass_end - first);
-      const long long upto = (long long)((double)(first - pass_first + n_pass) / pass_count * (double)npix);
-      progress(user, upto - done_pixels_reported);
-      done_pixels_reported = upto;
-    }
+    rc = wait_progress(b, batch_done, progress, user);
+    if (rc) return rc;
   }
-  if (n_sets >= 2) { /* join: the caller's stream continues after every lane */
-    for (int k = 0; k < n_sets; ++k) {
-      HIP_TRY(hipEventRecord(ev_join[k], lanes[k]));
-      HIP_TRY(hipStreamWaitEvent(st, ev_join[k], 0));
-    }
-  }
+  rc = join_lanes(s, b, l, st);
+  if (rc) return rc;
   /* PTX_RENDER_ASYNC: the frame is queued, the caller's stream carries the order (everything above is stream-ordered: the
    * lanes fork from `st` and join it, the workspace is reused in stream order, a reallocation synchronises by itself) */
   const bool wait = !(p->flags & PTX_RENDER_ASYNC) || count || timed || progress || PT_SHADE_TIMING;
@@ -949,17 +1003,17 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
 #if PT_SHADE_TIMING
   { /* diagnostic build: the last batch of each workspace set, per bounce (units of 256 shader clocks, summed over waves) */
     std::vector<uint32_t> h(kCountsWords);
-    for (int k = 0; k < n_sets; ++k) {
+    for (int k = 0; k < b.n_sets; ++k) {
       HIP_TRY(hipMemcpy(h.data(), ws[k].counts, sizeof(uint32_t) * kCountsWords, hipMemcpyDeviceToHost));
-      for (int b = 0; b < p->max_bounces; ++b) {
-        const uint32_t* t = h.data() + kWorkBase + (size_t)b * kWorkPerBounce + 8 + 16;
-        if (t[5]) fprintf(stderr, "shade_timing set %d bounce %d rays %u waves %u sort/refill %u entry %u append/push %u (first barrier/live lanes %u) store/steps %u life %u (longest wave %u, mean %u)\n", k, b, h[b], t[5], t[0], t[1], t[2], t[6], t[3], t[4], t[7], t[4] / t[5]);
+      for (int bo = 0; bo < p->max_bounces; ++bo) {
+        const uint32_t* t = h.data() + kWorkBase + (size_t)bo * kWorkPerBounce + 8 + 16;
+        if (t[5]) fprintf(stderr, "shade_timing set %d bounce %d rays %u waves %u sort/refill %u entry %u append/push %u (first barrier/live lanes %u) store/steps %u life %u (longest wave %u, mean %u)\n", k, bo, h[bo], t[5], t[0], t[1], t[2], t[6], t[3], t[4], t[7], t[4] / t[5]);
       }
     }
   }
 #endif
   if (stats) {
-    stats->samples = (int64_t)per_pass * pass_count;
+    stats->samples = (int64_t)b.per_pass * b.pass_count;
     if (count) {
       rc = collect_counters(s, stats);
       if (rc) return rc;
@@ -1169,40 +1223,37 @@ bool bvh_build_gpu(const std::vector<Box>& boxes, int num_bins, int length_cutof
   return true;
 }
 
+/* rows [row0, row1) of the image (reads raw rows row0 - 1 .. row1); row1 < 0: the whole image */
 int film_resolve(int width, int height, int spp, const double* d_raw, double* d_out, hipStream_t st,
-                 PtBandMap map = PtBandMap{1, 1, 0}) {
+                 PtBandMap map = PtBandMap{1, 1, 0}, int row0 = 0, int row1 = -1) {
   PtFilm3 k;
   binomial_3x3(k.w);
   const double spp_inv = 1.0 / (double)spp; /* 1 // samples_per_pixel */
-  const long long n = (long long)width * height;
-  hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, spp_inv, k, map, d_out, 0, height);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-/* rows [row0, row1) only (reads raw rows row0 - 1 .. row1) */
-int film_resolve_rows(int width, int height, int spp, const double* d_raw, double* d_out, hipStream_t st, int row0, int row1) {
-  PtFilm3 k;
-  binomial_3x3(k.w);
+  if (row1 < 0) row1 = height;
   const long long n = (long long)width * (row1 - row0);
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, 1.0 / (double)spp, k, PtBandMap{1, 1, 0}, d_out, row0, row1);
+  hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, spp_inv, k, map, d_out, row0, row1);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-/* k_pixel_error + k_error_summary queued on st: d_partials holds pixel_error_partials(npix) doubles, the last of them rel_err */
+/* k_pixel_error (d_passes == nullptr: k passes for every pixel) or k_pixel_error_counts (the pixel's own d_passes[p]), then
+ * k_error_summary, queued on st: d_partials holds pixel_error_partials(npix) doubles, the last of them rel_err */
 size_t pixel_error_blocks(long long npix) { return (size_t)((npix + PT_ERR_THREADS - 1) / PT_ERR_THREADS); }
 size_t pixel_error_partials(long long npix) { return 2 * pixel_error_blocks(npix) + 1; }
-int pixel_error_queue(long long npix, int k, const double* d_raw, const double* d_sq, double* d_err, double* d_partials, hipStream_t st) {
+int pixel_error_queue(long long npix, int k, const int32_t* d_passes, const double* d_raw, const double* d_sq, double* d_err,
+                      double* d_partials, hipStream_t st) {
   const size_t n_blocks = pixel_error_blocks(npix);
-  hipLaunchKernelGGL(k_pixel_error, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, npix, k, d_err, d_partials);
-  hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, k,
+  if (d_passes) hipLaunchKernelGGL(k_pixel_error_counts, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, d_passes, npix, d_err, d_partials);
+  else hipLaunchKernelGGL(k_pixel_error, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, npix, k, d_err, d_partials);
+  /* (a count map's summary is called with k = 2: a pixel with fewer than 2 passes has se = +inf, which the sums carry) */
+  hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, d_passes ? 2 : k,
                      d_partials + 2 * n_blocks);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-/* adaptive sampling: k_film_counts, and k_pixel_error_counts + k_error_summary (d_partials as in pixel_error_queue), queued on st */
+/* adaptive sampling: k_film_counts queued on st */
 int film_counts_queue(int width, int height, const double* d_raw, const int32_t* d_passes, double* d_out, hipStream_t st) {
   PtFilm3 k;
   binomial_3x3(k.w);
@@ -1211,15 +1262,43 @@ int film_counts_queue(int width, int height, const double* d_raw, const int32_t*
   HIP_TRY(hipGetLastError());
   return 0;
 }
-int pixel_error_counts_queue(long long npix, const int32_t* d_passes, const double* d_raw, const double* d_sq, double* d_err,
-                             double* d_partials, hipStream_t st) {
-  const size_t n_blocks = pixel_error_blocks(npix);
-  hipLaunchKernelGGL(k_pixel_error_counts, dim3((unsigned)n_blocks), dim3(PT_ERR_THREADS), 0, st, d_raw, d_sq, d_passes, npix, d_err, d_partials);
-  hipLaunchKernelGGL(k_error_summary, dim3(1), dim3(PT_ERR_THREADS), 0, st, (const double*)d_partials, (long long)n_blocks, 2,
-                     d_partials + 2 * n_blocks);
-  HIP_TRY(hipGetLastError());
+
+/* What the render entry points check first, in this order: the scene handle, a device behind it, the caller's other pointers
+ * (missing: the message when one of them is NULL, else nullptr), the params */
+int check_render_args(const ptx_scene* s, const ptx_render_params* p, const char* missing) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (missing) return fail(PTX_ERR_ARG, "%s", missing);
+  return check_params(p);
+}
+
+int check_device(int32_t device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    (void)hipGetLastError();
+    return fail(PTX_ERR_ARG, "device %d out of range (have %d HIP devices): this library has no CPU fallback", device, ndev);
+  }
   return 0;
 }
+
+/* the second stream and the events of the pipelines that film and copy out behind a queued frame, made once per scene */
+int ensure_event(hipEvent_t* ev) {
+  if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  return 0;
+}
+int ensure_copy_stream(ptx_scene* s) {
+  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+  return 0;
+}
+/* Every exit of a call that queues a frame and works behind it (render_updates, render_into_pinned): nothing the call queued is
+ * still running when it returns (an error half-way may leave lanes that were never joined, and a copy into the caller's image in
+ * flight, hence the whole device).  Disarmed once the null stream and copy_stream have been waited for. */
+struct DrainOnExit {
+  bool armed = true;
+  ~DrainOnExit() {
+    if (armed) (void)hipDeviceSynchronize();
+  }
+};
 
 }  // namespace
 
@@ -1798,8 +1877,7 @@ int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
 
 int32_t ptx_render_raw_device(ptx_scene* s, const ptx_render_params* p, double* d_raw_out, void* stream, ptx_stats* stats) {
   if (!s || !d_raw_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  int rc = check_params(p);
+  int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const double t0 = wall_ms();
@@ -2128,10 +2206,47 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
   return 0;
 }
 
+/* ptx_render's tail into an image the caller has pinned, as a pipeline: the last batch's accumulate runs in row slabs, and on a
+ * second stream slab k is filmed (once slab k + 1 has been summed: the 3 x 3 filter reads one row beyond) and copied into the
+ * image while the later slabs are still being summed.  49.8 MB at the 55.6 GB/s the PCIe link gives (tools/d2h_rate.py: 0.89 ms,
+ * whatever the number of pieces or streams) is the floor of this entry point over the device-resident one; what the
+ * pipeline hides is the last accumulate (0.37 ms at 1080p).
+ * *copied = false: the frame had no last batch to cut into slabs (one pass per batch); the raw sums are complete in s->raw and
+ * the caller films and copies them the plain way. */
+namespace {
+int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, double* rgb_out, ptx_stats* stats, bool* copied) {
+  FinalSlabs fs;
+  fs.n = std::min(n_slabs, kMaxFinalSlabs);
+  for (int k = 0; k <= fs.n; ++k) fs.row[k] = (int)((long long)p.height * k / fs.n);
+  int rc = ensure_copy_stream(s);
+  for (int k = 0; k < fs.n && !rc; ++k) {
+    rc = ensure_event(&s->ev_slab[k]);
+    fs.done[k] = s->ev_slab[k];
+  }
+  if (rc) return rc;
+  DrainOnExit drain; /* from the queued frame to the last wait, every return drains the lanes, the film and the copy into rgb_out */
+  ptx_render_params pq = p;
+  pq.flags = PTX_RENDER_ASYNC; /* queued: this thread goes on to queue the tail behind the slabs' events */
+  rc = render_raw(s, &pq, s->raw.p, nullptr, stats, nullptr, nullptr, &fs);
+  if (rc) return rc;
+  for (int k = 0; k < fs.n && fs.used; ++k) {
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, fs.done[std::min(k + 1, fs.n - 1)], 0));
+    rc = film_resolve(p.width, p.height, p.samples_per_pixel, s->raw.p, s->rgb.p, s->copy_stream, PtBandMap{1, 1, 0}, fs.row[k], fs.row[k + 1]);
+    if (rc) return rc;
+    const size_t off = (size_t)fs.row[k] * p.width * 3, len = (size_t)(fs.row[k + 1] - fs.row[k]) * p.width * 3;
+    if (len) HIP_TRY(hipMemcpyAsync(rgb_out + off, s->rgb.p + off, sizeof(double) * len, hipMemcpyDeviceToHost, s->copy_stream));
+  }
+  if (fs.used) HIP_TRY(hipStreamSynchronize(s->copy_stream));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  drain.armed = false;
+  *copied = fs.used;
+  return 0;
+}
+}  // namespace
+
 int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out, ptx_stats* stats, ptx_progress_fn progress, void* user) {
   if (!s || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  int rc = check_params(p_in);
+  int rc = check_render_args(s, p_in, nullptr);
   if (rc) return rc;
   if (p_in->n_gpus > 1) {
     /* replicas on the following device ordinals, made once and kept with the handle */
@@ -2157,43 +2272,16 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
   const size_t n = (size_t)p.width * p.height * 3;
   HIP_TRY(s->raw.ensure(n));
   HIP_TRY(s->rgb.ensure(n));
-  /* An image the caller has pinned takes the frame's tail as a pipeline: the last batch's accumulate runs in row slabs, and on a
-   * second stream slab k is filmed (once slab k + 1 has been summed: the 3 x 3 filter reads one row beyond) and copied into the
-   * image while the later slabs are still being summed.  49.8 MB at the 55.6 GB/s the PCIe link gives (tools/d2h_rate.py: 0.89 ms,
-   * whatever the number of pieces or streams) is the floor of this entry point over the device-resident one; what the
-   * pipeline hides is the last accumulate (0.37 ms at 1080p). */
+  /* an image the caller has pinned takes the frame's tail as a pipeline (render_into_pinned) */
   const bool pinned = s->reg_ptr && rgb_out >= s->reg_ptr && rgb_out + n <= s->reg_ptr + s->reg_n;
   const int n_slabs = (pinned && !p.count_work && !p.time_kernels && !progress && p.height >= 64 && p.max_bounces > 0) ? env_int("PTX_FINAL_SLABS", 4) : 1;
-  if (n_slabs > 1) {
-    FinalSlabs fs;
-    fs.n = std::min(n_slabs, kMaxFinalSlabs);
-    for (int k = 0; k <= fs.n; ++k) fs.row[k] = (int)((long long)p.height * k / fs.n);
-    for (int k = 0; k < fs.n; ++k) {
-      if (!s->ev_slab[k]) HIP_TRY(hipEventCreateWithFlags(&s->ev_slab[k], hipEventDisableTiming));
-      fs.done[k] = s->ev_slab[k];
-    }
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    ptx_render_params pq = p;
-    pq.flags = PTX_RENDER_ASYNC; /* queued: this thread goes on to queue the tail behind the slabs' events */
-    rc = render_raw(s, &pq, s->raw.p, nullptr, stats, nullptr, nullptr, &fs);
-    if (rc) return rc;
-    if (fs.used) {
-      for (int k = 0; k < fs.n; ++k) {
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, fs.done[std::min(k + 1, fs.n - 1)], 0));
-        rc = film_resolve_rows(p.width, p.height, p.samples_per_pixel, s->raw.p, s->rgb.p, s->copy_stream, fs.row[k], fs.row[k + 1]);
-        if (rc) return rc;
-        const size_t off = (size_t)fs.row[k] * p.width * 3, len = (size_t)(fs.row[k + 1] - fs.row[k]) * p.width * 3;
-        if (len) HIP_TRY(hipMemcpyAsync(rgb_out + off, s->rgb.p + off, sizeof(double) * len, hipMemcpyDeviceToHost, s->copy_stream));
-      }
-      HIP_TRY(hipStreamSynchronize(s->copy_stream));
-      HIP_TRY(hipStreamSynchronize(nullptr));
-      if (stats) stats->render_ms = wall_ms() - t0;
-      return 0;
-    }
-    HIP_TRY(hipStreamSynchronize(nullptr)); /* (a frame of one pass per batch and no last-batch slabs: the plain tail below) */
-  } else {
-    rc = render_raw(s, &p, s->raw.p, nullptr, stats, progress, user);
-    if (rc) return rc;
+  bool copied = false;
+  if (n_slabs > 1) rc = render_into_pinned(s, p, n_slabs, rgb_out, stats, &copied);
+  else rc = render_raw(s, &p, s->raw.p, nullptr, stats, progress, user);
+  if (rc) return rc;
+  if (copied) {
+    if (stats) stats->render_ms = wall_ms() - t0;
+    return 0;
   }
   rc = timed_film(p, s->raw.p, s->rgb.p, PtBandMap{1, 1, 0}, stats);
   if (rc) return rc;
@@ -2213,6 +2301,12 @@ int check_pass_range(const ptx_render_params* p, int32_t pass_first, int32_t pas
   return 0;
 }
 
+int check_one_gpu(const ptx_render_params* p, const char* what) {
+  if (p->n_gpus > 1 || p->band_step > 1)
+    return fail(PTX_ERR_ARG, "%s runs on one GPU over the whole image (n_gpus %d, band_step %d)", what, p->n_gpus, p->band_step);
+  return 0;
+}
+
 void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
   acc->segments += o.segments; acc->nodes_tested += o.nodes_tested; acc->prims_tested += o.prims_tested;
   acc->floor_tested += o.floor_tested; acc->filter_undecided += o.filter_undecided;
@@ -2223,88 +2317,23 @@ void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
   }
 }
 
-/* every exit of ptx_render_progressive: nothing the call queued is still running when it returns (an error half-way may leave
- * lanes that were never joined, hence the whole device) */
-struct DrainOnExit {
-  bool armed = true;
-  ~DrainOnExit() {
-    if (armed) (void)hipDeviceSynchronize();
-  }
-};
-}  // namespace
-
-int32_t ptx_render_passes_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
-                                 double* d_raw_inout, double* d_sq_inout, void* stream, ptx_stats* stats) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (!d_raw_inout) return fail(PTX_ERR_ARG, "d_raw_inout is NULL");
-  int rc = check_params(p);
-  if (rc) return rc;
-  rc = check_pass_range(p, pass_first, pass_count);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+/* The update loop of ptx_render_progressive and ptx_render_adaptive: a frame rendered as slices, an update (the image, its error,
+ * a callback) after each.
+ * Slices are queued on the null stream (PTX_RENDER_ASYNC: render_raw returns once they are queued).  Update j is filmed there
+ * behind slice j's accumulate; slice j + 1 is queued next, so its bounces run while update j is copied out on copy_stream and
+ * handed to the callback -- its accumulate waits for the film (render_raw's fork event, recorded behind it).  The copy of update
+ * j + 1 is queued only after callback j has returned.  A render that counts work or times kernels waits for every slice and
+ * queues the next one only after the callback.
+ * The policy says what a slice and an update are: prepare() makes its own buffers and events; first() is the frame's first slice;
+ * queue_update(cur) queues, on the null stream behind slice cur, the film into s->rgb, the error (s->err if asked for, rel_err at
+ * the end of s->err_partials) and whatever else follows an update; next_slice(cur, &next) gives the slice after cur, count 0 when
+ * the frame is complete (it may wait for what queue_update queued, and for nothing else); copy_extras(cs) queues further copies of
+ * the update to the host on cs; call_back(update, cur, next, samples, rel) is the caller's callback and the stopping rule. */
+extern "C++" template <class Policy>
+int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool want_err, double* rgb_out, double* err_out, ptx_stats* stats) {
   const double t0 = wall_ms();
-  PassRange range;
-  range.first = pass_first;
-  range.count = pass_count;
-  range.zero = false;
-  range.d_sq = d_sq_inout;
-  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, range);
-  if (rc) return rc;
-  if (stats) stats->render_ms = wall_ms() - t0;
-  return 0;
-}
-
-int32_t ptx_pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t passes_done, const double* d_raw,
-                               const double* d_sq, double* d_err_out, double* rel_err_out, void* stream) {
-  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
-  if (!d_raw || !d_sq) return fail(PTX_ERR_ARG, "NULL argument");
-  if (width <= 0 || rows <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, rows);
-  if (passes_done < 1) return fail(PTX_ERR_ARG, "passes_done must be >= 1 (got %d)", passes_done);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    return fail(PTX_ERR_ARG, "device %d out of range (have %d HIP devices): this library has no CPU fallback", device, ndev);
-  }
-  HIP_TRY(hipSetDevice(device));
-  const long long npix = (long long)width * rows;
-  LocalBuf<double> part;
-  HIP_TRY(part.ensure(pixel_error_partials(npix)));
-  hipStream_t st = (hipStream_t)stream;
-  int rc = pixel_error_queue(npix, passes_done, d_raw, d_sq, d_err_out, part.p, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  double rel = 0.0;
-  HIP_TRY(hipMemcpyAsync(&rel, part.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (rel_err_out) *rel_err_out = rel;
-  return 0;
-}
-
-int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
-                               double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update, void* user) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (!pp || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
-  int rc = check_params(p_in);
-  if (rc) return rc;
-  if (p_in->n_gpus > 1) return fail(PTX_ERR_ARG, "progressive rendering runs on one GPU (n_gpus %d)", p_in->n_gpus);
-  if (pp->passes_per_update < 1) return fail(PTX_ERR_ARG, "passes_per_update must be >= 1 (got %d)", pp->passes_per_update);
-  if (!(pp->target_rel_err >= 0.0)) return fail(PTX_ERR_ARG, "target_rel_err must be >= 0 (got %g)", pp->target_rel_err);
-  if (!pp->want_error && (pp->target_rel_err > 0.0 || err_out))
-    return fail(PTX_ERR_ARG, "target_rel_err and err_out need want_error");
-  if (passes_done_out) *passes_done_out = 0;
-  ptx_render_params p = *p_in;
-  p.band_step = 0; /* whole image on this GPU */
-  p.n_gpus = 0;
-  HIP_TRY(hipSetDevice(s->device));
-  const double t0 = wall_ms();
-  const int N = p.samples_per_pixel, K = pp->passes_per_update;
   const long long npix = (long long)p.width * p.height;
   const size_t n = (size_t)npix * 3;
-  const bool want_err = pp->want_error != 0;
   HIP_TRY(s->raw.ensure(n));
   HIP_TRY(s->rgb.ensure(n));
   if (want_err) {
@@ -2312,45 +2341,40 @@ int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, cons
     HIP_TRY(s->err_partials.ensure(pixel_error_partials(npix)));
     if (err_out) HIP_TRY(s->err.ensure(n));
   }
-  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-  if (!s->ev_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_update, hipEventDisableTiming));
+  int rc = pol.prepare();
+  if (!rc) rc = ensure_copy_stream(s);
+  if (!rc) rc = ensure_event(&s->ev_update);
+  if (rc) return rc;
   DrainOnExit drain;
-  ptx_stats acc, slice;
+  ptx_stats acc, one;
   std::memset(&acc, 0, sizeof acc);
   fill_tree_stats(s, &acc);
-  /* Slices are queued on the null stream (PTX_RENDER_ASYNC: render_raw returns once they are queued).  Update j is filmed there
-   * behind slice j's accumulate; slice j + 1 is queued next, so its bounces run while update j is copied out on copy_stream and
-   * handed to the callback -- its accumulate waits for the film (render_raw's fork event, recorded behind it).  The copy of update
-   * j + 1 is queued only after callback j has returned.  A render that counts work or times kernels waits for every slice and
-   * queues the next one only after the callback. */
+  int64_t samples = 0, samples_done = 0; /* queued so far; in the sums the last update was made from */
   const bool ahead = !p.count_work && !p.time_kernels;
-  auto queue_slice = [&](int first, int count) -> int {
-    PassRange r;
-    r.first = first;
-    r.count = count;
-    r.zero = first == 0;
-    r.d_sq = want_err ? s->sq.p : nullptr;
+  auto queue_slice = [&](const PassRange& r) -> int {
     ptx_render_params pq = p;
     pq.flags = PTX_RENDER_ASYNC;
-    const int r2 = render_raw(s, &pq, s->raw.p, nullptr, &slice, nullptr, nullptr, nullptr, r);
-    if (r2 == 0) add_slice_stats(&acc, slice);
-    return r2;
+    const int r2 = render_raw(s, &pq, s->raw.p, nullptr, &one, nullptr, nullptr, nullptr, r);
+    if (r2) return r2;
+    add_slice_stats(&acc, one);
+    samples += one.samples;
+    /* a slice over the whole image sets the whole count map */
+    if (r.d_passes && !r.d_list) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)r.d_passes, r.first + r.count, (size_t)npix, nullptr));
+    return 0;
   };
-  int k = std::min(K, N);
-  rc = queue_slice(0, k);
+  PassRange cur = pol.first(), next;
+  rc = queue_slice(cur);
   if (rc) return rc;
   double rel = std::nan("");
-  for (;;) {
-    rc = film_resolve(p.width, p.height, k, s->raw.p, s->rgb.p, nullptr);
+  for (int update = 1;; ++update) {
+    rc = pol.queue_update(cur);
     if (rc) return rc;
-    if (want_err) {
-      rc = pixel_error_queue(npix, k, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
-      if (rc) return rc;
-    }
     HIP_TRY(hipEventRecord(s->ev_update, nullptr));
-    const int next = std::min(K, N - k);
-    if (next > 0 && ahead) {
-      rc = queue_slice(k, next);
+    rc = pol.next_slice(cur, &next);
+    if (rc) return rc;
+    samples_done = samples;
+    if (next.count > 0 && ahead) {
+      rc = queue_slice(next);
       if (rc) return rc;
     }
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_update, 0));
@@ -2360,19 +2384,18 @@ int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, cons
       rc = framebuffer_to_host(s, s->err.p, err_out, n, s->copy_stream);
       if (rc) return rc;
     }
+    rc = pol.copy_extras(s->copy_stream);
+    if (rc) return rc;
     if (want_err) {
       HIP_TRY(hipMemcpyAsync(&rel, s->err_partials.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, s->copy_stream));
       HIP_TRY(hipStreamSynchronize(s->copy_stream));
     }
-    if (passes_done_out) *passes_done_out = k;
-    bool stop = on_update && on_update(user, k, rel, rgb_out, err_out) != 0;
-    if (want_err && pp->target_rel_err > 0.0 && rel <= pp->target_rel_err) stop = true;
-    if (stop || next == 0) break;
+    if (pol.call_back(update, cur, next, samples_done, rel) || next.count <= 0) break;
     if (!ahead) {
-      rc = queue_slice(k, next);
+      rc = queue_slice(next);
       if (rc) return rc;
     }
-    k += next;
+    cur = next;
   }
   /* (after an early stop the slice queued ahead finishes here; its passes are in the raw sums only, never in rgb_out) */
   HIP_TRY(hipStreamSynchronize(nullptr));
@@ -2380,25 +2403,8 @@ int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, cons
   drain.armed = false;
   if (stats) {
     *stats = acc;
-    stats->samples = (int64_t)npix * k;
+    stats->samples = samples_done; /* W*H*k; with a count map, its sum */
     stats->render_ms = wall_ms() - t0;
-  }
-  return 0;
-}
-
-/* ---- adaptive sampling: rounds of passes for the pixels that have not converged yet ---- */
-namespace {
-int check_one_gpu(const ptx_render_params* p, const char* what) {
-  if (p->n_gpus > 1 || p->band_step > 1)
-    return fail(PTX_ERR_ARG, "%s runs on one GPU over the whole image (n_gpus %d, band_step %d)", what, p->n_gpus, p->band_step);
-  return 0;
-}
-
-int check_device(int32_t device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    return fail(PTX_ERR_ARG, "device %d out of range (have %d HIP devices): this library has no CPU fallback", device, ndev);
   }
   return 0;
 }
@@ -2415,15 +2421,112 @@ int check_list_device(ptx_scene* s, const int32_t* d_list, long long n, long lon
   if (bad) return fail(PTX_ERR_ARG, "the pixel list holds an index outside [0, %lld)", npix);
   return 0;
 }
+
+/* ptx_pixel_error_device and ptx_pixel_error_counts_device (d_passes == nullptr: passes_done for every pixel); the caller has
+ * checked its own arguments */
+int pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t passes_done, const int32_t* d_passes, const double* d_raw,
+                       const double* d_sq, double* d_err_out, double* rel_err_out, hipStream_t st) {
+  int rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const long long npix = (long long)width * rows;
+  LocalBuf<double> part;
+  HIP_TRY(part.ensure(pixel_error_partials(npix)));
+  rc = pixel_error_queue(npix, passes_done, d_passes, d_raw, d_sq, d_err_out, part.p, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  double rel = 0.0;
+  HIP_TRY(hipMemcpyAsync(&rel, part.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (rel_err_out) *rel_err_out = rel;
+  return 0;
+}
 }  // namespace
 
+int32_t ptx_render_passes_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
+                                 double* d_raw_inout, double* d_sq_inout, void* stream, ptx_stats* stats) {
+  int rc = check_render_args(s, p, d_raw_inout ? nullptr : "d_raw_inout is NULL");
+  if (rc) return rc;
+  rc = check_pass_range(p, pass_first, pass_count);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, PassRange(pass_first, pass_count, false, d_sq_inout));
+  if (rc) return rc;
+  if (stats) stats->render_ms = wall_ms() - t0;
+  return 0;
+}
+
+int32_t ptx_pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t passes_done, const double* d_raw,
+                               const double* d_sq, double* d_err_out, double* rel_err_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
+  if (!d_raw || !d_sq) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || rows <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, rows);
+  if (passes_done < 1) return fail(PTX_ERR_ARG, "passes_done must be >= 1 (got %d)", passes_done);
+  return pixel_error_device(device, width, rows, passes_done, nullptr, d_raw, d_sq, d_err_out, rel_err_out, (hipStream_t)stream);
+}
+
+namespace {
+/* ptx_render_progressive as render_updates sees it: slices of K passes over the whole image, k_film with spp = the passes done */
+struct ProgressivePolicy {
+  ptx_scene* s;
+  const ptx_render_params& p;
+  const ptx_progressive_params& pp;
+  double *rgb_out, *err_out;
+  int32_t* passes_done_out;
+  ptx_update_fn on_update;
+  void* user;
+  bool want_err() const { return pp.want_error != 0; }
+  PassRange slice(int first) const {
+    return PassRange(first, std::min(pp.passes_per_update, p.samples_per_pixel - first), first == 0, want_err() ? s->sq.p : nullptr);
+  }
+  int prepare() { return 0; }
+  PassRange first() const { return slice(0); }
+  int queue_update(const PassRange& cur) {
+    const int k = cur.first + cur.count;
+    const int rc = film_resolve(p.width, p.height, k, s->raw.p, s->rgb.p, nullptr);
+    if (rc || !want_err()) return rc;
+    return pixel_error_queue((long long)p.width * p.height, k, nullptr, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
+  }
+  int next_slice(const PassRange& cur, PassRange* next) {
+    *next = slice(cur.first + cur.count);
+    return 0;
+  }
+  int copy_extras(hipStream_t) { return 0; }
+  bool call_back(int, const PassRange& cur, const PassRange&, int64_t, double rel) {
+    const int k = cur.first + cur.count;
+    if (passes_done_out) *passes_done_out = k;
+    const bool stop = on_update && on_update(user, k, rel, rgb_out, err_out) != 0;
+    return stop || (want_err() && pp.target_rel_err > 0.0 && rel <= pp.target_rel_err);
+  }
+};
+}  // namespace
+
+int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
+                               double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update, void* user) {
+  int rc = check_render_args(s, p_in, (pp && rgb_out) ? nullptr : "NULL argument");
+  if (rc) return rc;
+  if (p_in->n_gpus > 1) return fail(PTX_ERR_ARG, "progressive rendering runs on one GPU (n_gpus %d)", p_in->n_gpus);
+  if (pp->passes_per_update < 1) return fail(PTX_ERR_ARG, "passes_per_update must be >= 1 (got %d)", pp->passes_per_update);
+  if (!(pp->target_rel_err >= 0.0)) return fail(PTX_ERR_ARG, "target_rel_err must be >= 0 (got %g)", pp->target_rel_err);
+  if (!pp->want_error && (pp->target_rel_err > 0.0 || err_out))
+    return fail(PTX_ERR_ARG, "target_rel_err and err_out need want_error");
+  if (passes_done_out) *passes_done_out = 0;
+  ptx_render_params p = *p_in;
+  p.band_step = 0; /* whole image on this GPU */
+  p.n_gpus = 0;
+  HIP_TRY(hipSetDevice(s->device));
+  ProgressivePolicy pol{s, p, *pp, rgb_out, err_out, passes_done_out, on_update, user};
+  return render_updates(s, p, pol, pol.want_err(), rgb_out, err_out, stats);
+}
+
+/* ---- adaptive sampling: rounds of passes for the pixels that have not converged yet ---- */
 int32_t ptx_render_pixels_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
                                  const int32_t* d_pixels, int64_t n_pixels, double* d_raw_inout, double* d_sq_inout, void* stream,
                                  ptx_stats* stats) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (!d_raw_inout) return fail(PTX_ERR_ARG, "d_raw_inout is NULL");
-  int rc = check_params(p);
+  int rc = check_render_args(s, p, d_raw_inout ? nullptr : "d_raw_inout is NULL");
   if (rc) return rc;
   rc = check_one_gpu(p, "a pixel list");
   if (rc) return rc;
@@ -2443,14 +2546,8 @@ int32_t ptx_render_pixels_device(ptx_scene* s, const ptx_render_params* p, int32
   }
   rc = check_list_device(s, d_pixels, n_pixels, npix, (hipStream_t)stream);
   if (rc) return rc;
-  PassRange range;
-  range.first = pass_first;
-  range.count = pass_count;
-  range.zero = false;
-  range.d_sq = d_sq_inout;
-  range.d_list = d_pixels;
-  range.n_list = n_pixels;
-  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr, range);
+  rc = render_raw(s, p, d_raw_inout, (hipStream_t)stream, stats, nullptr, nullptr, nullptr,
+                  PassRange(pass_first, pass_count, false, d_sq_inout).listed(d_pixels, n_pixels, nullptr));
   if (rc) return rc;
   if (stats) stats->render_ms = wall_ms() - t0;
   return 0;
@@ -2474,31 +2571,94 @@ int32_t ptx_pixel_error_counts_device(int32_t device, int32_t width, int32_t row
   if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
   if (!d_passes || !d_raw || !d_sq) return fail(PTX_ERR_ARG, "NULL argument");
   if (width <= 0 || rows <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, rows);
-  int rc = check_device(device);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(device));
-  const long long npix = (long long)width * rows;
-  LocalBuf<double> part;
-  HIP_TRY(part.ensure(pixel_error_partials(npix)));
-  hipStream_t st = (hipStream_t)stream;
-  rc = pixel_error_counts_queue(npix, d_passes, d_raw, d_sq, d_err_out, part.p, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  double rel = 0.0;
-  HIP_TRY(hipMemcpyAsync(&rel, part.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (rel_err_out) *rel_err_out = rel;
-  return 0;
+  return pixel_error_device(device, width, rows, 0, d_passes, d_raw, d_sq, d_err_out, rel_err_out, (hipStream_t)stream);
 }
+
+namespace {
+/* ptx_render_adaptive as render_updates sees it.  A round over the whole image is a plain slice (camera rays decoded in k_bounce), a
+ * partial one runs in list mode.  After round j: the film, the error and a copy of the count map, then the select of round j + 1's
+ * list.  The host waits for the select only (it needs the list's length to size the next round); render_updates then queues round
+ * j + 1, and copies update j out on copy_stream and calls back while round j + 1's bounces run. */
+struct AdaptivePolicy {
+  ptx_scene* s;
+  const ptx_render_params& p;
+  const ptx_adaptive_params& ap;
+  double *rgb_out, *err_out;
+  int32_t* passes_out;
+  ptx_round_fn on_round;
+  void* user;
+  bool selecting = false; /* queue_update queued a select: next_slice waits for it */
+  long long npix() const { return (long long)p.width * p.height; }
+  int tiles_x() const { return (p.width + 7) / 8; }
+  long long padded() const { return (long long)tiles_x() * ((p.height + 7) / 8) * 64; } /* the whole image in 8x8-tile order */
+  PassRange round(int first, int count, const int32_t* list, long long n_list) const {
+    return PassRange(first, count, first == 0, s->sq.p).listed(list, n_list, s->passes.p);
+  }
+  /* the list the round after cur is selected into: the buffer that does not hold cur's */
+  int32_t* next_list(const PassRange& cur) const { return s->list[cur.d_list == s->list[0].p ? 1 : 0].p; }
+  int prepare() {
+    const size_t max_blocks = (size_t)((padded() + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
+    HIP_TRY(s->passes.ensure((size_t)npix()));
+    HIP_TRY(s->passes_img.ensure((size_t)npix()));
+    HIP_TRY(s->list[0].ensure((size_t)npix()));
+    HIP_TRY(s->list[1].ensure((size_t)npix()));
+    HIP_TRY(s->sel_n.ensure(2));
+    HIP_TRY(s->sel_keep.ensure((size_t)padded()));
+    HIP_TRY(s->sel_blocks.ensure(max_blocks));
+    HIP_TRY(s->sel_offsets.ensure(max_blocks));
+    return ensure_event(&s->ev_select);
+  }
+  PassRange first() const { return round(0, std::min(ap.min_passes, p.samples_per_pixel), nullptr, 0); }
+  int queue_update(const PassRange& cur) {
+    const int W = p.width, H = p.height, b = cur.first + cur.count;
+    int rc = film_counts_queue(W, H, s->raw.p, s->passes.p, s->rgb.p, nullptr);
+    if (rc) return rc;
+    rc = pixel_error_queue(npix(), 0, s->passes.p, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->passes_img.p, s->passes.p, sizeof(int32_t) * (size_t)npix(), hipMemcpyDeviceToDevice, nullptr));
+    selecting = b < p.samples_per_pixel && ap.target_rel_err > 0.0; /* T = 0: no pixel converges */
+    if (!selecting) return 0;
+    const long long n_sel = cur.d_list ? cur.n_list : padded();
+    const unsigned nb = (unsigned)((n_sel + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
+    hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur.d_list, n_sel, W, H, tiles_x(), (const double*)s->raw.p,
+                       (const double*)s->sq.p, b, ap.target_rel_err, ap.radiance_floor, s->sel_keep.p, s->sel_blocks.p);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(PT_SEL_THREADS), 0, nullptr, (const uint32_t*)s->sel_blocks.p, (long long)nb,
+                       s->sel_offsets.p, s->sel_n.p);
+    hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur.d_list, n_sel, W, H, tiles_x(),
+                       (const uint8_t*)s->sel_keep.p, (const uint32_t*)s->sel_offsets.p, next_list(cur));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->ev_select, nullptr));
+    return 0;
+  }
+  int next_slice(const PassRange& cur, PassRange* next) {
+    const int b = cur.first + cur.count, count = std::min(ap.passes_per_round, p.samples_per_pixel - b);
+    long long n_next = cur.d_list ? cur.n_list : npix();
+    if (selecting) {
+      int32_t got = 0;
+      HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_select, 0));
+      HIP_TRY(hipMemcpyAsync(&got, s->sel_n.p, sizeof got, hipMemcpyDeviceToHost, s->copy_stream));
+      HIP_TRY(hipStreamSynchronize(s->copy_stream));
+      n_next = got;
+    }
+    /* a list that holds the whole image runs as a plain slice; an empty one ends the render */
+    const bool whole = !selecting || n_next == npix();
+    *next = round(b, n_next > 0 ? count : 0, whole ? nullptr : next_list(cur), n_next);
+    return 0;
+  }
+  int copy_extras(hipStream_t cs) {
+    if (passes_out) HIP_TRY(hipMemcpyAsync(passes_out, s->passes_img.p, sizeof(int32_t) * (size_t)npix(), hipMemcpyDeviceToHost, cs));
+    return 0;
+  }
+  bool call_back(int update, const PassRange& cur, const PassRange& next, int64_t samples, double rel) {
+    const long long active_next = next.count <= 0 ? 0 : next.d_list ? next.n_list : npix();
+    return on_round && on_round(user, update, cur.first + cur.count, active_next, samples, rel, rgb_out, err_out, passes_out) != 0;
+  }
+};
+}  // namespace
 
 int32_t ptx_render_adaptive(ptx_scene* s, const ptx_render_params* p_in, const ptx_adaptive_params* ap, double* rgb_out,
                             double* err_out, int32_t* passes_out, ptx_stats* stats, ptx_round_fn on_round, void* user) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (!ap || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
-  int rc = check_params(p_in);
+  int rc = check_render_args(s, p_in, (ap && rgb_out) ? nullptr : "NULL argument");
   if (rc) return rc;
   rc = check_one_gpu(p_in, "adaptive rendering");
   if (rc) return rc;
@@ -2510,149 +2670,14 @@ int32_t ptx_render_adaptive(ptx_scene* s, const ptx_render_params* p_in, const p
   p.band_step = 0;
   p.n_gpus = 0;
   HIP_TRY(hipSetDevice(s->device));
-  const double t0 = wall_ms();
-  const int N = p.samples_per_pixel, M = ap->min_passes, K = ap->passes_per_round, W = p.width, H = p.height;
-  const double T = ap->target_rel_err, F = ap->radiance_floor;
-  const long long npix = (long long)W * H;
-  const size_t n = (size_t)npix * 3;
-  const int tiles_x = (W + 7) / 8;
-  const long long padded = (long long)tiles_x * ((H + 7) / 8) * 64; /* the whole image in 8x8-tile order */
-  const size_t max_blocks = (size_t)((padded + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
-  HIP_TRY(s->raw.ensure(n));
-  HIP_TRY(s->sq.ensure(n));
-  HIP_TRY(s->rgb.ensure(n));
-  if (err_out) HIP_TRY(s->err.ensure(n));
-  HIP_TRY(s->err_partials.ensure(pixel_error_partials(npix)));
-  HIP_TRY(s->passes.ensure((size_t)npix));
-  HIP_TRY(s->passes_img.ensure((size_t)npix));
-  HIP_TRY(s->list[0].ensure((size_t)npix));
-  HIP_TRY(s->list[1].ensure((size_t)npix));
-  HIP_TRY(s->sel_n.ensure(2));
-  HIP_TRY(s->sel_keep.ensure((size_t)padded));
-  HIP_TRY(s->sel_blocks.ensure(max_blocks));
-  HIP_TRY(s->sel_offsets.ensure(max_blocks));
-  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-  if (!s->ev_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_update, hipEventDisableTiming));
-  if (!s->ev_select) HIP_TRY(hipEventCreateWithFlags(&s->ev_select, hipEventDisableTiming));
-  DrainOnExit drain;
-  ptx_stats acc, part;
-  std::memset(&acc, 0, sizeof acc);
-  fill_tree_stats(s, &acc);
-  int64_t samples = 0;
-  /* Rounds are queued on the null stream as ptx_render_progressive queues its slices; a round over the whole image is a plain slice
-   * (camera rays decoded in k_bounce), a partial one runs in list mode.  After round j: the film, the error and a copy of the count
-   * map, then the select of round j + 1's list.  The host waits for the select only (it needs the list's length to size the next
-   * round), queues round j + 1, and copies update j out on copy_stream and calls back while round j + 1's bounces run.  A render
-   * that counts work or times kernels queues the next round only after the callback. */
-  const bool ahead = !p.count_work && !p.time_kernels;
-  auto queue_round = [&](int first, int count, const int32_t* lst, long long n_lst) -> int {
-    PassRange r;
-    r.first = first;
-    r.count = count;
-    r.zero = first == 0;
-    r.d_sq = s->sq.p;
-    r.d_list = lst;
-    r.n_list = lst ? n_lst : 0;
-    r.d_passes = s->passes.p;
-    ptx_render_params pq = p;
-    pq.flags = PTX_RENDER_ASYNC;
-    const int r2 = render_raw(s, &pq, s->raw.p, nullptr, &part, nullptr, nullptr, nullptr, r);
-    if (r2) return r2;
-    add_slice_stats(&acc, part);
-    samples += part.samples;
-    if (!lst) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->passes.p, first + count, (size_t)npix, nullptr));
-    return 0;
-  };
-  int b = std::min(M, N);
-  rc = queue_round(0, b, nullptr, npix);
-  if (rc) return rc;
-  const int32_t* cur = nullptr; /* this round's list (nullptr: the whole image) */
-  long long n_cur = npix;
-  int which = 0;                /* the list buffer the next list is written to */
-  int64_t samples_done = 0;
-  for (int round = 1;; ++round) {
-    rc = film_counts_queue(W, H, s->raw.p, s->passes.p, s->rgb.p, nullptr);
-    if (rc) return rc;
-    rc = pixel_error_counts_queue(npix, s->passes.p, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(s->passes_img.p, s->passes.p, sizeof(int32_t) * (size_t)npix, hipMemcpyDeviceToDevice, nullptr));
-    const int next = std::min(K, N - b);
-    long long n_next = 0;
-    int32_t* next_list = nullptr;
-    if (next > 0 && !(T > 0.0)) {
-      n_next = n_cur; /* T = 0: no pixel converges */
-    } else if (next > 0) {
-      next_list = s->list[which].p;
-      const long long n_sel = cur ? n_cur : padded;
-      const unsigned nb = (unsigned)((n_sel + PT_SEL_THREADS - 1) / PT_SEL_THREADS);
-      hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur, n_sel, W, H, tiles_x, (const double*)s->raw.p,
-                         (const double*)s->sq.p, b, T, F, s->sel_keep.p, s->sel_blocks.p);
-      hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(PT_SEL_THREADS), 0, nullptr, (const uint32_t*)s->sel_blocks.p, (long long)nb,
-                         s->sel_offsets.p, s->sel_n.p);
-      hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(PT_SEL_THREADS), 0, nullptr, cur, n_sel, W, H, tiles_x,
-                         (const uint8_t*)s->sel_keep.p, (const uint32_t*)s->sel_offsets.p, next_list);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(s->ev_select, nullptr));
-    }
-    HIP_TRY(hipEventRecord(s->ev_update, nullptr));
-    if (next_list) {
-      int32_t got = 0;
-      HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_select, 0));
-      HIP_TRY(hipMemcpyAsync(&got, s->sel_n.p, sizeof got, hipMemcpyDeviceToHost, s->copy_stream));
-      HIP_TRY(hipStreamSynchronize(s->copy_stream));
-      n_next = got;
-    }
-    /* a list that holds the whole image runs as a plain slice */
-    const int32_t* lst_next = n_next == npix ? nullptr : next_list;
-    samples_done = samples;
-    if (n_next > 0 && ahead) {
-      rc = queue_round(b, next, lst_next, n_next);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_update, 0));
-    rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n, s->copy_stream);
-    if (rc) return rc;
-    if (err_out) {
-      rc = framebuffer_to_host(s, s->err.p, err_out, n, s->copy_stream);
-      if (rc) return rc;
-    }
-    if (passes_out)
-      HIP_TRY(hipMemcpyAsync(passes_out, s->passes_img.p, sizeof(int32_t) * (size_t)npix, hipMemcpyDeviceToHost, s->copy_stream));
-    double rel = 0.0;
-    HIP_TRY(hipMemcpyAsync(&rel, s->err_partials.p + 2 * pixel_error_blocks(npix), sizeof rel, hipMemcpyDeviceToHost, s->copy_stream));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    const bool stop = on_round && on_round(user, round, b, n_next, samples_done, rel, rgb_out, err_out, passes_out) != 0;
-    if (stop || n_next == 0) break;
-    if (!ahead) {
-      rc = queue_round(b, next, lst_next, n_next);
-      if (rc) return rc;
-    }
-    if (lst_next) {
-      cur = lst_next;
-      which ^= 1;
-    } else {
-      cur = nullptr;
-    }
-    n_cur = n_next;
-    b += next;
-  }
-  /* (after an early stop the round queued ahead finishes here; its passes are in the sums only, never in rgb_out) */
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipStreamSynchronize(s->copy_stream));
-  drain.armed = false;
-  if (stats) {
-    *stats = acc;
-    stats->samples = samples_done; /* the sum of the returned count map */
-    stats->render_ms = wall_ms() - t0;
-  }
-  return 0;
+  AdaptivePolicy pol{s, p, *ap, rgb_out, err_out, passes_out, on_round, user};
+  return render_updates(s, p, pol, true, rgb_out, err_out, stats);
 }
 
 int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
                           const int32_t* passes, double* rgb_out, ptx_stats* stats) {
   if (!s || !xs || !ys || !passes || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  int rc = check_params(p);
+  int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad sample count");
   if (stats) {
@@ -2790,8 +2815,7 @@ int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, 
 int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
                                 const int32_t* passes, double* ray_out, double* attn_out, int32_t* alive_out) {
   if (!s || !xs || !ys || !passes || !ray_out || !attn_out || !alive_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  int rc = check_params(p);
+  int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
   HIP_TRY(hipSetDevice(s->device));
