@@ -188,7 +188,9 @@ typedef struct ptx_stats {
   /* if count_work: launches of the one-kernel-per-bounce path that found their input small enough (PTX_SOLO_ENTRIES) to run all
    * remaining bounces of their batch by themselves; the batch's later launches return at once (ABI 6) */
   int32_t solo_launches;
-  int32_t reserved_stats;
+  /* if count_work: launches of the one-kernel-per-bounce path in the shade-first order (k_bounce_carry; PTX_BOUNCE_ORDER=0 and the
+   * modes that keep the walk-first order give 0).  Took the place of a reserved word: the layout of ABI 6 is unchanged */
+  int32_t carry_launches;
 } ptx_stats;
 
 /* ---- progressive photon mapping (progressive-photon-map/src/progressive_photon_map.ml) ---- */

@@ -13,7 +13,8 @@
  * A render runs trace + shade of a bounce as ONE kernel (k_bounce: a wave walks 64 rays, files them in per-category pools, shades
  * a pool when it holds 64) -- around an LDS copy of the scene where tree and packets fit one, over the per-octant node image in
  * HBM / L2 otherwise; k_trace + k_shade_pool remain for what k_bounce does not cover (ptx_intersect_rays, scenes too large for
- * LDS beside the pools, PTX_FUSED = 0).
+ * LDS beside the pools, PTX_FUSED = 0).  LDS-resident scenes binned by elevation run its steps in the other order (k_bounce_carry:
+ * an entry carries its hit; a launch shades its input first and walks the new rays second, nothing is gathered or read twice).
  * Both walks are stackless and their links TAGGED: a visit ends with one select between "what a hit leads to" and "what a miss leads
  * to", and the walk's control state -- wants a node, holds a leaf, over -- lives in the link's spare bits (PT_SWZ_TAG_* on the LDS
  * image, the top two bits of a word on the per-octant record).  On Simd_leaf scenes in LDS the node loop itself is gfx950 assembly
@@ -126,6 +127,7 @@ struct PtCounters { /* device-side work counters (count_work) */
   unsigned long long segments, nodes, prims, floor;
   unsigned long long undecided, fallback_steps; /* binary32 filter: lane tests handed to the binary64 code, wave steps that ran it */
   unsigned long long solo;                      /* k_bounce launches that ran their batch's remaining bounces by themselves (PtSolo) */
+  unsigned long long carry;                     /* k_bounce_carry launches */
 };
 
 /* ------------------------------------------------------------------ small device helpers */
@@ -2419,18 +2421,16 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
 
 /* blk_list / blk_n (LDS, or null): every block this workgroup takes from the output queue is also noted there (PtSolo: the workgroup
  * reads its own survivors back in the next bounce of the same launch) */
-template <bool EMIT>
-__device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue& out, const PtShadeOut& so, uint32_t* lds_out,
-                                             uint32_t* blk_list = nullptr, uint32_t* blk_n = nullptr, bool one_bin = false) {
+/* The reservation: room for the wave's entries (`keep` lanes, each under its `bin`) in the workgroup's output blocks.  Returns the
+ * lane's entry of `out` (meaningful where `keep`); at least one lane must keep. */
+__device__ __forceinline__ uint32_t pt_pool_reserve(const PtQueue& out, bool keep, int bin, uint32_t* lds_out,
+                                                    uint32_t* blk_list = nullptr, uint32_t* blk_n = nullptr) {
   const int lane = pt_lane();
-  /* one_bin (wave-uniform): a workgroup whose rays would not fill a block does not spread them over eight (PtSolo) */
-  const int bin = one_bin ? 0 : pt_bin_key<PT_POOL_BINS>(sc, so.n_o, so.n_d);
-  if (__ballot(so.keep) == 0) return;
   /* all bins at once: lane b < 8 holds bin b's survivor count and makes its reservation -- one LDS atomic instruction */
   uint32_t rank = 0, kk = 0;
 #pragma unroll
   for (int b = 0; b < PT_POOL_BINS; ++b) {
-    const unsigned long long m = __ballot(so.keep && bin == b);
+    const unsigned long long m = __ballot(keep && bin == b);
     if (bin == b) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     if (lane == b) kk = (uint32_t)__popcll(m);
   }
@@ -2477,11 +2477,17 @@ __device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue
   const uint32_t my_st = (uint32_t)__shfl((int)st, bin, 64);
   const uint32_t my_head = (uint32_t)__shfl((int)head, bin, 64);
   const uint32_t my_blk2 = (uint32_t)__shfl((int)blk2, bin, 64);
-  if (so.keep) {
-    const uint32_t dst = rank < my_head ? (my_st >> 12) * (uint32_t)PT_POOL_BLOCK + (my_st & 0xfffu) + rank
-                                        : my_blk2 * (uint32_t)PT_POOL_BLOCK + (rank - my_head);
-    pt_q_store<EMIT>(out, dst, so.n_o, so.n_d, so.n_attn, so.n_emit, so.id, so.offset);
-  }
+  return rank < my_head ? (my_st >> 12) * (uint32_t)PT_POOL_BLOCK + (my_st & 0xfffu) + rank
+                        : my_blk2 * (uint32_t)PT_POOL_BLOCK + (rank - my_head);
+}
+template <bool EMIT>
+__device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue& out, const PtShadeOut& so, uint32_t* lds_out,
+                                             uint32_t* blk_list = nullptr, uint32_t* blk_n = nullptr, bool one_bin = false) {
+  /* one_bin (wave-uniform): a workgroup whose rays would not fill a block does not spread them over eight (PtSolo) */
+  const int bin = one_bin ? 0 : pt_bin_key<PT_POOL_BINS>(sc, so.n_o, so.n_d);
+  if (__ballot(so.keep) == 0) return;
+  const uint32_t dst = pt_pool_reserve(out, so.keep, bin, lds_out, blk_list, blk_n);
+  if (so.keep) pt_q_store<EMIT>(out, dst, so.n_o, so.n_d, so.n_attn, so.n_emit, so.id, so.offset);
 }
 
 template <bool EMIT, bool PRIMARY>
@@ -3075,6 +3081,273 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
     if (blk == PT_POOL_NO_BLOCK) continue;
     for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE)
       out.ray[(size_t)blk * PT_POOL_BLOCK + e].dx = __hiloint2double((int)PT_HOLE_HI, 0);
+  }
+}
+
+/* ------------------------------------------------------------------ a bounce launch that shades first and walks second
+ * k_bounce above is walk(b) -> pools -> shade(b) -> push: the shade step gathers by pool index, one to several chunks after the
+ * walk read them densely, the ray it walked, the path record and the hit distance -- and the L2 has let go of them by then: 190 B
+ * of fabric reads per segment against 88 B of records.  k_bounce_carry turns the loop round.  A queue ENTRY CARRIES ITS HIT: the
+ * ray, the path record, and in PtHits at the entry's own index the slot and the distance of the hit the ray has already found.
+ * Survivors are binned by the shading category of that hit, a block is single-bin, so a chunk of 64 entries is one category by
+ * construction, as a pool step is.  A wave's turn in launch b:
+ *     read a chunk densely, once -> pt_shade_entry<CAT> of bounce b on the lane's own entry -> the new ray is in registers ->
+ *     walk it at once (bounce b + 1) -> a miss ends the path on the spot (PT_CARRY_MISS_IN_PLACE), a hit is pushed as {new ray,
+ *     path record, slot, t} under its category.
+ * (The key of the next walk's length that pt_bin_key takes from the new direction is gone: that direction does not exist until the
+ * next launch has shaded.  Predicting it for the checker category from the sampler value the scatter will use, two and four levels,
+ * measured slower than no key: DESIGN.md Appendix A.)
+ * Nothing is gathered, nothing is read twice, no pools.  Launches per batch stay max_bounces:
+ *     launch 0 (PRIMARY)         camera rays as a packet walk -> shade 0 in place, category by category -> walk 1 -> push
+ *     launch b, 0 < b < last     shade b -> walk b + 1 -> push
+ *     the last launch            shade only: nothing survives it.
+ * A walk the tail cut stops has its ray nowhere in memory, so the parked record is the whole entry (ray, path record, node, slot,
+ * t [, emission] [, u, v]); the workgroup-level pool, its lock and "resume 64 at a time" are k_bounce's.  Holes are marked in the
+ * slot array (PT_SLOT_HOLE) and skipped before they are shaded.  Same arithmetic, same tests per ray in the same order; which wave
+ * does what when, and the order of a queue, change -- which no result depends on.  `hits` belongs to the input queue (launch 0:
+ * to the camera samples), `hout` to the output queue. */
+#ifndef PT_CARRY_MISS_IN_PLACE
+#define PT_CARRY_MISS_IN_PLACE 1 /* a walk that ends in a miss is shaded where it ends; 0: pushed under the miss category like any other */
+#endif
+/* 16-byte words of a parked entry: {node | slot << 16, offset, t}, 3 x ray, {attn.x, attn.y}, {attn.z, id} [, 2 x emission] [, {u, v}] */
+#define PT_CARRY_PARK_WORDS(EMIT_, UV_) (6 + ((EMIT_) ? 2 : 0) + ((UV_) ? 1 : 0))
+static_assert(PT_POOL_BINS >= PT_N_SHADE_CAT, "k_bounce_carry: one output bin per shading category");
+
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
+__global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_carry(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtHits hout, PtContrib contrib,
+                                                                 const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
+                                                                 uint32_t n_primary, int stack_depth, uint32_t pool_off,
+                                                                 PtCounters* counters, int fence_wg) {
+  extern __shared__ __attribute__((aligned(64))) unsigned char lds_raw[];
+  __shared__ uint32_t lds_out[PT_POOL_BINS];
+  __shared__ uint32_t lds_chunk_ctr, lds_done;
+  __shared__ uint32_t lds_park_n, lds_park_lock;
+  const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+  typedef uint16_t StackT;
+  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, StackT, stack_depth));
+  const uint32_t n = PRIMARY ? n_primary : *q.count;
+  const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
+  uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
+  n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg);
+  if (COUNT && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->carry, 1ull);
+  if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
+  if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; lds_park_n = 0u; lds_park_lock = 0u; }
+  if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
+  PtSceneView sv = pt_scene_view<MODE, true, StackT>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
+  PtSceneDev scl = sc; /* the shade steps read the slots' kinds and geometry where the walk reads them (k_bounce) */
+  if (PT_SHADE_LDS_GEOM) {
+    scl.slot_kind = sv.kind;
+    scl.sph = sv.sph;
+    scl.tri = sv.tri;
+  }
+  constexpr int CUT = PT_TAIL_CUT;
+  constexpr bool TAIL = CUT > 0;
+  constexpr bool TAIL_UV = TAIL && MODE == PT_MODE_ARRAY;
+  /* the workgroup's parked walks behind the scene image (there are no pools): one array of 16-byte words per field (PT_CARRY_PARK_WORDS) */
+  const uint32_t park_cap = (uint32_t)PT_PARK_CAP(nw, CUT);
+  uint4* const park0 = (uint4*)(lds_raw + pool_off);
+  uint4* const park_emit = park0 + 6u * park_cap;
+  uint4* const park_uv = park_emit + (EMIT ? 2u * park_cap : 0u);
+  bool more = true; /* wave-uniform: the workgroup's share of the input (launch 0: of the camera samples) is not exhausted */
+  unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0}; /* COUNT: as in k_trace */
+  for (;;) {
+    const uint32_t park_hint = TAIL ? __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u; /* (wave-uniform: one LDS word) */
+    /* what this turn walks: the lane's ray, and the rest of the entry it will push */
+    bool resume = false, valid = false;
+    V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0), attn = v3(0.0, 0.0, 0.0), emit = v3(0.0, 0.0, 0.0);
+    uint32_t id = 0u;
+    int offset = 0;
+    PtTailCtl tc;
+    tc.node = 0u;
+    tc.slot = -1;
+    tc.t = tc.u = tc.v = 0.0;
+    if (TAIL && (park_hint >= (uint32_t)PT_WAVE || (!more && park_hint > 0))) {
+      /* 64 parked walks (the most recently parked: a stack), or what is left once this wave's share of the input is exhausted */
+      pt_lds_lock(&lds_park_lock);
+      const uint32_t np = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const uint32_t take = (np >= (uint32_t)PT_WAVE || !more) ? (np < (uint32_t)PT_WAVE ? np : (uint32_t)PT_WAVE) : 0u;
+      const uint32_t base = np - take;
+      if ((uint32_t)lane < take) {
+        const uint4* p = park0 + base + lane;
+        const uint4 h = p[0], r0 = p[park_cap], r1 = p[2u * park_cap], r2 = p[3u * park_cap], a0 = p[4u * park_cap], a1 = p[5u * park_cap];
+        tc.node = h.x & 0xffffu;
+        tc.slot = (int)(h.x >> 16) == 0xffff ? -1 : (int)(h.x >> 16);
+        offset = (int)h.y;
+        tc.t = __hiloint2double((int)h.w, (int)h.z);
+        o = v3(__hiloint2double((int)r0.y, (int)r0.x), __hiloint2double((int)r0.w, (int)r0.z), __hiloint2double((int)r1.y, (int)r1.x));
+        d = v3(__hiloint2double((int)r1.w, (int)r1.z), __hiloint2double((int)r2.y, (int)r2.x), __hiloint2double((int)r2.w, (int)r2.z));
+        attn = v3(__hiloint2double((int)a0.y, (int)a0.x), __hiloint2double((int)a0.w, (int)a0.z), __hiloint2double((int)a1.y, (int)a1.x));
+        id = a1.z;
+        if (EMIT) {
+          const uint4 e0 = park_emit[base + lane], e1 = park_emit[park_cap + base + lane];
+          emit = v3(__hiloint2double((int)e0.y, (int)e0.x), __hiloint2double((int)e0.w, (int)e0.z), __hiloint2double((int)e1.y, (int)e1.x));
+        }
+        if (TAIL_UV) {
+          const uint4 w = park_uv[base + lane];
+          tc.u = __hiloint2double((int)w.y, (int)w.x);
+          tc.v = __hiloint2double((int)w.w, (int)w.z);
+        }
+      }
+      if (lane == 0 && take) __hip_atomic_store(&lds_park_n, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      pt_lds_unlock(&lds_park_lock);
+      if (take == 0u) continue; /* (another wave was faster) */
+      resume = true;
+      valid = (uint32_t)lane < take;
+    } else {
+      /* a shade step on the next chunk of the share: 64 entries of one category by construction (launch 0: 64 camera samples) */
+      int c = -1;
+      uint32_t i = 0u;
+      int sl = -1;
+      bool live = false;
+      int my_cat = PT_CAT_NONE; /* PRIMARY: the lane's own category (a chunk of camera samples may hold several) */
+      if (!more) {
+        if (park_hint > 0) continue;
+        break;
+      }
+      /* the next chunk of the workgroup's share (runs of PT_POOL_RUN consecutive chunks, dealt round-robin, as in k_bounce) */
+      uint32_t unit = 0u;
+      if (lane == 0) unit = __hip_atomic_fetch_add(&lds_chunk_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
+      unit = (unit / PT_POOL_RUN) * (n_wg * PT_POOL_RUN) + blockIdx.x * PT_POOL_RUN + (unit % PT_POOL_RUN);
+      more = unit < total_chunks;
+      if (!more) continue;
+      i = unit * PT_WAVE + (uint32_t)lane;
+      if (PRIMARY) {
+        /* camera samples: generate, walk as a packet (k_bounce's front half).  The hit goes straight to the shade steps below:
+         * a chunk is one 8 x 8 tile of one pass, mostly one category, so there are no pools -- each category present is shaded
+         * in turn, its lanes live */
+        live = i < n;
+        if (live) {
+          const PtPrimarySample ps = pt_primary_decode(g, i);
+          live = ps.valid;
+          if (live) d = pt_primary_dir(sc, g, ps, alpha);
+        }
+        if (COUNT && live) c_seg++;
+        const PtTraceResult r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, c_nodes, c_prims, c_floor, c_filter);
+        if (live) {
+          if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
+          sl = r.slot;
+          my_cat = r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot];
+        }
+        /* this wave's own stores (hit distances) before its own loads of them (k_bounce) */
+        if (PT_BOUNCE_FENCE_WG || fence_wg) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        } else {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        o = v3(0.0, 0.0, 0.0);
+        d = v3(0.0, 0.0, -1.0);
+      } else {
+        sl = i < n ? hits.slot[i] : PT_SLOT_HOLE;
+        live = sl != PT_SLOT_HOLE;
+        /* the chunk's category: its first entry's (a block holds one bin, a bin one category) */
+        const unsigned long long lm = __ballot(live);
+        if (lm == 0ull) continue; /* the unwritten part of a bin's last block */
+        my_cat = !live ? PT_CAT_NONE : (sl < 0 ? PT_CAT_MISS : (int)sv.cat[sl]);
+        c = __builtin_amdgcn_readlane(my_cat, __ffsll((long long)lm) - 1);
+      }
+      /* (PRIMARY: every category some lane holds, in turn; else the chunk's one) */
+#define PT_CARRY_STEP(K, ...)                                                                                          \
+  if (PRIMARY ? __ballot(my_cat == K) != 0ull : c == K) {                                                              \
+    PtShadeOut so;                                                                                                     \
+    pt_shade_entry<EMIT, PRIMARY, K>(PT_SHADE_LDS_GEOM ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, ##__VA_ARGS__); \
+    if (so.keep) {                                                                                                     \
+      valid = true;                                                                                                    \
+      o = so.n_o;                                                                                                      \
+      d = so.n_d;                                                                                                      \
+      attn = so.n_attn;                                                                                                \
+      emit = so.n_emit;                                                                                                \
+      id = so.id;                                                                                                      \
+      offset = so.offset;                                                                                              \
+    }                                                                                                                  \
+  }
+      PT_CARRY_STEP(PT_CAT_MISS)
+      PT_CARRY_STEP(PT_CAT_LAMBERT_SOLID, sl)
+      PT_CARRY_STEP(PT_CAT_LAMBERT_CHECKER, sl)
+      PT_CARRY_STEP(PT_CAT_METAL, sl)
+      PT_CARRY_STEP(PT_CAT_DIELECTRIC, sl)
+#undef PT_CARRY_STEP
+      if (last_bounce || __ballot(valid) == 0ull) continue; /* nothing survives the step */
+      if (COUNT && valid) c_seg++;
+    }
+    /* walk the new rays (or go on with the parked ones); the last chunks of a wave run to completion */
+    tc.min_active = (TAIL && more) ? CUT : 0;
+    tc.resume = resume && valid;
+    tc.unfinished = false;
+    const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid, TAIL ? &tc : nullptr, c_filter);
+    const bool park = TAIL && tc.unfinished;
+    const bool done = valid && !park;
+    const int cat = !done ? PT_CAT_NONE : (r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot]);
+    /* a ray that left the scene ends its path here: pt_shade_entry<PT_CAT_MISS>'s one line on the registers that hold its operands
+     * (None -> add_mul emit0 attn0 background, integrator.ml:36), instead of an entry for the next launch to read back */
+    if (PT_CARRY_MISS_IN_PLACE && cat == PT_CAT_MISS) {
+      const V3 result = v3_fma(attn, pt_background(sc, d), EMIT ? emit : v3(0.0, 0.0, 0.0));
+      contrib.rgbx[id] = make_double4(result.x, result.y, result.z, 0.0);
+    }
+    const bool push = done && !(PT_CARRY_MISS_IN_PLACE && cat == PT_CAT_MISS);
+    if (__ballot(push) != 0ull) {
+      const uint32_t dst = pt_pool_reserve(out, push, push ? cat : 0, lds_out); /* the bin: the category, so that a chunk is one category */
+      if (push) {
+        pt_q_store<EMIT>(out, dst, o, d, attn, emit, id, offset);
+        hout.slot[dst] = r.slot;
+        if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hout.t[dst] = r.t; /* (else the shade step recomputes it: PtHits) */
+      }
+    }
+    if (TAIL) {
+      const unsigned long long pm = __ballot(park);
+      if (pm != 0) {
+        pt_lds_lock(&lds_park_lock);
+        const uint32_t base = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (park) {
+          uint4* p = park0 + base + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
+          p[0] = make_uint4(tc.node | ((uint32_t)(r.slot < 0 ? 0xffff : r.slot) << 16), (uint32_t)offset,
+                            (uint32_t)__double2loint(r.t), (uint32_t)__double2hiint(r.t));
+          p[park_cap] = make_uint4((uint32_t)__double2loint(o.x), (uint32_t)__double2hiint(o.x), (uint32_t)__double2loint(o.y), (uint32_t)__double2hiint(o.y));
+          p[2u * park_cap] = make_uint4((uint32_t)__double2loint(o.z), (uint32_t)__double2hiint(o.z), (uint32_t)__double2loint(d.x), (uint32_t)__double2hiint(d.x));
+          p[3u * park_cap] = make_uint4((uint32_t)__double2loint(d.y), (uint32_t)__double2hiint(d.y), (uint32_t)__double2loint(d.z), (uint32_t)__double2hiint(d.z));
+          p[4u * park_cap] = make_uint4((uint32_t)__double2loint(attn.x), (uint32_t)__double2hiint(attn.x), (uint32_t)__double2loint(attn.y), (uint32_t)__double2hiint(attn.y));
+          p[5u * park_cap] = make_uint4((uint32_t)__double2loint(attn.z), (uint32_t)__double2hiint(attn.z), id, 0u);
+          if (EMIT) {
+            p[6u * park_cap] = make_uint4((uint32_t)__double2loint(emit.x), (uint32_t)__double2hiint(emit.x), (uint32_t)__double2loint(emit.y), (uint32_t)__double2hiint(emit.y));
+            p[7u * park_cap] = make_uint4((uint32_t)__double2loint(emit.z), (uint32_t)__double2hiint(emit.z), 0u, 0u);
+          }
+          if (TAIL_UV)
+            p[(EMIT ? 8u : 6u) * park_cap] = make_uint4((uint32_t)__double2loint(r.u), (uint32_t)__double2hiint(r.u), (uint32_t)__double2loint(r.v), (uint32_t)__double2hiint(r.v));
+        }
+        if (lane == 0) __hip_atomic_store(&lds_park_n, base + (uint32_t)__popcll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        pt_lds_unlock(&lds_park_lock);
+      }
+    }
+  }
+  if (COUNT) {
+    c_nodes = pt_wave_sum(c_nodes);
+    c_prims = pt_wave_sum(c_prims);
+    c_floor = pt_wave_sum(c_floor);
+    c_seg = pt_wave_sum(c_seg);
+    c_filter[0] = pt_wave_sum(c_filter[0]);
+    c_filter[1] = pt_wave_sum(c_filter[1]);
+    if (lane == 0) {
+      atomicAdd(&counters->nodes, c_nodes);
+      atomicAdd(&counters->prims, c_prims);
+      atomicAdd(&counters->floor, c_floor);
+      atomicAdd(&counters->segments, c_seg);
+      atomicAdd(&counters->undecided, c_filter[0]);
+      atomicAdd(&counters->fallback_steps, c_filter[1]);
+    }
+  }
+  if (last_bounce) return;
+  /* the workgroup's last wave marks what is left of its blocks as holes */
+  uint32_t fin = 0u;
+  if (lane == 0) fin = __hip_atomic_fetch_add(&lds_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+  fin = (uint32_t)__builtin_amdgcn_readfirstlane((int)fin);
+  if (fin != (uint32_t)(nw - 1)) return;
+  for (int b = 0; b < PT_POOL_BINS; ++b) {
+    const uint32_t st = __hip_atomic_load(lds_out + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint32_t blk = st >> 12, pos = st & 0xfffu;
+    if (blk == PT_POOL_NO_BLOCK) continue;
+    for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE) hout.slot[(size_t)blk * PT_POOL_BLOCK + e] = PT_SLOT_HOLE;
   }
 }
 

@@ -285,6 +285,7 @@ struct ptx_scene {
   int bounce_fence_wg = env_int("PTX_BOUNCE_FENCE_WG", 0); /* k_bounce: 1 = workgroup-scope fences around a wave's own records (the safety net; tests run both) */
   int solo_entries = env_int("PTX_SOLO_ENTRIES", 0); /* k_bounce: a launch whose input queue holds at most this many entries runs the batch's remaining bounces by itself (0 = off) */
   int fused_global = env_int("PTX_FUSED_GLOBAL", 1); /* scenes walked from HBM / L2: 1 = k_bounce<..., LDS_SCENE = false> instead of k_trace + k_shade_pool */
+  int bounce_order = env_int("PTX_BOUNCE_ORDER", 2); /* LDS-resident scenes, PTX_FUSED=2: 1 = a bounce launch shades its input's carried hits first and walks the new rays second (k_bounce_carry), 0 = walk first (k_bounce), 2 = by scene (carry_possible) */
   int bounce_threads = env_int("PTX_BOUNCE_THREADS", 0); /* k_bounce workgroup size (0 = PT_BOUNCE_THREADS; tests: 64 .. 1024) */
   int bounce_wgs = env_int("PTX_BOUNCE_WGS", 0);         /* k_bounce workgroups per launch (0 = one per CU; tests: a few, so that every wave walks hundreds of chunks) */
   int trace_top = env_int("PTX_TRACE_TOP", 0);     /* scenes walked from HBM / L2: 1 = keep the tree's top in LDS (measured: no gain, the top of the tree is hot in L1 anyway; DESIGN.md section 4) */
@@ -502,12 +503,15 @@ int bounce_threads(const ptx_scene* s) {
   const int dflt = bounce_from_hbm(s) ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS;
   return s->bounce_threads > 0 ? std::min(PT_BOUNCE_THREADS, std::max(64, s->bounce_threads & ~63)) : dflt;
 }
-size_t bounce_lds_bytes(const ptx_scene* s, size_t* pool_off) {
+size_t bounce_lds_bytes(const ptx_scene* s, size_t* pool_off, bool carry = false) {
   const int stack_depth = std::max(1, s->tree_depth + 1), waves = bounce_threads(s) / 64;
   /* the workgroup's parked walks behind the shade pools (k_bounce): 16 bytes per entry, + 16 for a triangle hit's (u, v), + 16 for
    * the 32-bit node index and slot of a walk from HBM / L2 */
   const bool hbm = bounce_from_hbm(s);
-  const size_t park = (size_t)PT_PARK_CAP(waves, hbm ? PT_TAIL_CUT_GLOBAL : PT_TAIL_CUT) * 16 * (1 + (s->dev.mode == PT_MODE_ARRAY ? 1 : 0) + (hbm ? 1 : 0));
+  /* (k_bounce_carry: the parked record is the whole entry, PT_CARRY_PARK_WORDS) */
+  const size_t park = (size_t)PT_PARK_CAP(waves, hbm ? PT_TAIL_CUT_GLOBAL : PT_TAIL_CUT) * 16 *
+                      (carry ? (size_t)PT_CARRY_PARK_WORDS(s->dev.has_emit != 0, s->dev.mode == PT_MODE_ARRAY)
+                             : (size_t)(1 + (s->dev.mode == PT_MODE_ARRAY ? 1 : 0) + (hbm ? 1 : 0)));
   if (hbm) { /* no stacks, no scene image: the pools only */
     if (pool_off) *pool_off = 0;
     return (size_t)waves * PT_N_SHADE_CAT * 128 * PT_BOUNCE_POOL_ENTRY_BYTES(false) + park;
@@ -516,6 +520,7 @@ size_t bounce_lds_bytes(const ptx_scene* s, size_t* pool_off) {
   const size_t stacks = ((size_t)waves * PT_WAVE_STACK_BYTES(true, uint16_t, stack_depth) + 63) & ~(size_t)63;
   const size_t off = (stacks + trace_scene_lds_bytes(s) + 63) & ~(size_t)63;
   if (pool_off) *pool_off = off;
+  if (carry) return off + park; /* (no pools: its parked entries start where they would) */
   return off + (size_t)waves * PT_N_SHADE_CAT * 128 * PT_BOUNCE_POOL_ENTRY_BYTES(true) + park;
 }
 /* dynamic LDS a k_bounce launch may ask for: the 160 KB of a CU less the kernel's own static words -- bins, counters, the floor
@@ -526,6 +531,57 @@ constexpr size_t kBounceLdsLimit = (size_t)160 * 1024 - (2 * PT_SOLO_MAX_BLOCKS 
 bool use_fused(const ptx_scene* s, size_t cap_entries) {
   return s->fused && cap_entries < kPoolMaxEntries && (trace_scene_lds_bytes(s) > 0 || bounce_from_hbm(s)) &&
          bounce_lds_bytes(s, nullptr) <= kBounceLdsLimit;
+}
+/* the shade-first order (k_bounce_carry) is for LDS-resident scenes whose larger parked record still fits, with every bounce a
+ * k_bounce launch and no solo run configured.  By default (PTX_BOUNCE_ORDER=2) the scenes binned by elevation take it -- open
+ * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
+ * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
+ * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
+bool carry_possible(const ptx_scene* s) {
+  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && s->fused >= 2 && s->solo_entries <= 0 && trace_scene_lds_bytes(s) > 0 && !bounce_from_hbm(s) &&
+         bounce_lds_bytes(s, nullptr, true) <= kBounceLdsLimit;
+}
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
+void launch_carry_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
+                       const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
+  const int stack_depth = std::max(1, s->tree_depth + 1);
+  size_t pool_off = 0;
+  const size_t lds = bounce_lds_bytes(s, &pool_off, true);
+  auto kern = k_bounce_carry<MODE, COUNT, EMIT, PRIMARY>;
+  if (s->attr_done.insert((const void*)kern).second) {
+    raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void*)kern) == hipSuccess && (size_t)fa.sharedSizeBytes + kBounceLdsLimit > (size_t)160 * 1024) {
+      fprintf(stderr, "ptx: k_bounce_carry holds %zu bytes of static LDS, more than kBounceLdsLimit leaves room for\n", (size_t)fa.sharedSizeBytes);
+      abort(); /* a build error (a new __shared__ array), caught on the first launch of any test */
+    }
+  }
+  const int threads = bounce_threads(s);
+  int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
+  if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
+                     (uint32_t)pool_off, s->counters.p, s->bounce_fence_wg);
+}
+template <int MODE, bool COUNT>
+void launch_carry_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
+                       const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
+  if (s->dev.has_emit) {
+    if (pl.on) launch_carry_inst<MODE, COUNT, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else launch_carry_inst<MODE, COUNT, true, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+  } else {
+    if (pl.on) launch_carry_inst<MODE, COUNT, false, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else launch_carry_inst<MODE, COUNT, false, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+  }
+}
+void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
+                         const PtContrib& c, size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl) {
+  if (s->dev.mode == PT_MODE_SIMD) {
+    if (count) launch_carry_mode<PT_MODE_SIMD, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else launch_carry_mode<PT_MODE_SIMD, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+  } else {
+    if (count) launch_carry_mode<PT_MODE_ARRAY, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else launch_carry_mode<PT_MODE_ARRAY, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+  }
 }
 template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE>
 void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
@@ -588,6 +644,7 @@ struct Workspace {
   uint32_t* counts; /* counts[b] = live paths entering bounce b (b >= 1; counts[0] for list-mode generation) */
   uint4* susp = nullptr;
   size_t cap_entries = 0; /* queue / hit-record capacity */
+  size_t carry_stride = 0; /* k_bounce_carry: the hit arrays hold a second half of this many entries (0: they do not) */
   double* contrib_all = nullptr;
   size_t contrib_n = 0;
 };
@@ -611,8 +668,10 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
    * shade step recomputes them (PtHits, PT_RECOMPUTE_HIT) and the buffer is not even allocated */
   const bool hit_records = s->dev.has_triangles && (want_hit_records || !PT_RECOMPUTE_HIT);
   if (hit_records) HIP_TRY(b.hit_tuv.ensure(cap * 4));
-  else HIP_TRY(b.hit_t.ensure((s->solo_entries > 0 && !s->dev.has_triangles) ? 2 * cap : cap)); /* (PtHits.t_parity_stride: a solo launch keeps the distances of even and odd bounces apart) */
-  HIP_TRY(b.hit_slot.ensure(cap));
+  /* k_bounce_carry reads its input's hits while it writes its output's: entries of even and odd bounces in two halves */
+  const bool carry = carry_possible(s) && !hit_records;
+  if (!hit_records) HIP_TRY(b.hit_t.ensure(((s->solo_entries > 0 || carry) && !s->dev.has_triangles) ? 2 * cap : cap)); /* (PtHits.t_parity_stride: a solo launch keeps the distances of even and odd bounces apart) */
+  HIP_TRY(b.hit_slot.ensure(carry ? 2 * cap : cap));
   HIP_TRY(b.contrib.ensure(cap * 4));
   HIP_TRY(b.counts.ensure(kCountsWords));
   /* parked walks of k_trace: <= 4 workgroups of <= 16 waves per CU with 64 states (3 x 16 bytes) per wave (k_bounce keeps its own in LDS) */
@@ -641,6 +700,7 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
   w->counts = b.counts.p;
   w->susp = b.susp.p;
   w->cap_entries = cap;
+  w->carry_stride = carry ? cap : 0;
   w->q[0] = b.qa.view(nullptr);
   w->q[1] = b.qb.view(nullptr);
   w->hits.t = s->dev.has_triangles ? nullptr : b.hit_t.p;
@@ -659,6 +719,8 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
 void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int max_bounces, bool count, bool timed,
                  const PrimaryLaunch& pl, int run_only = -1) {
   const int n_run = run_only >= 0 ? run_only : max_bounces;
+  /* the shade-first order: a whole batch from its camera launch on (its launch b shades bounce b and walks bounce b + 1) */
+  const bool carry = pl.on && run_only < 0 && max_bounces >= 2 && w.carry_stride > 0 && carry_possible(s) && use_fused(s, w.cap_entries);
   for (int b = 0; b < n_run; ++b) {
     PtQueue in = w.q[b & 1], out = w.q[(b + 1) & 1];
     in.count = w.counts + b;
@@ -666,6 +728,18 @@ void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int
     const PrimaryLaunch here = (b == 0) ? pl : PrimaryLaunch();
     s->cur_bounce = here.on ? 0 : std::max(b, 1); /* list-mode bounce 0 (explicit samples) reads a queue like any bounce */
     s->cur_susp = w.susp;
+    if (carry) {
+      LaunchTimer t(s, st, timed, PTX_KERNEL_BOUNCE);
+      PtHits h_in = w.hits, h_out = w.hits;
+      h_in.slot += (size_t)(b & 1) * w.carry_stride;
+      h_out.slot += (size_t)((b + 1) & 1) * w.carry_stride;
+      if (w.hits.t) {
+        h_in.t += (size_t)(b & 1) * w.carry_stride;
+        h_out.t += (size_t)((b + 1) & 1) * w.carry_stride;
+      }
+      launch_bounce_carry(s, st, in, h_in, out, h_out, w.contrib, n_upper, b, b == max_bounces - 1 ? 1 : 0, count, here);
+      continue;
+    }
     if ((!here.on || s->fused >= 2) && use_fused(s, w.cap_entries)) { /* PTX_FUSED=2: the camera rays' bounce too */
       LaunchTimer t(s, st, timed, PTX_KERNEL_BOUNCE);
       /* PtSolo: the first launch whose input has shrunk to s->solo_entries runs the batch's remaining bounces by itself, the
@@ -713,6 +787,7 @@ int collect_counters(ptx_scene* s, ptx_stats* stats) {
   stats->filter_undecided = (int64_t)c.undecided;
   stats->filter_fallback_steps = (int64_t)c.fallback_steps;
   stats->solo_launches = (int32_t)c.solo;
+  stats->carry_launches = (int32_t)c.carry;
   return 0;
 }
 
@@ -2310,7 +2385,7 @@ int check_one_gpu(const ptx_render_params* p, const char* what) {
 void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
   acc->segments += o.segments; acc->nodes_tested += o.nodes_tested; acc->prims_tested += o.prims_tested;
   acc->floor_tested += o.floor_tested; acc->filter_undecided += o.filter_undecided;
-  acc->filter_fallback_steps += o.filter_fallback_steps; acc->solo_launches += o.solo_launches;
+  acc->filter_fallback_steps += o.filter_fallback_steps; acc->solo_launches += o.solo_launches; acc->carry_launches += o.carry_launches;
   for (int i = 0; i < PTX_N_KERNELS; ++i) {
     acc->kernel_ms[i] += o.kernel_ms[i];
     acc->kernel_launches[i] += o.kernel_launches[i];

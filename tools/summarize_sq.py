@@ -154,13 +154,13 @@ def targs_of(k):
 
 
 def is_timed_trace(k):
-    if not k.startswith(("k_trace<", "k_trace_stream<", "k_bounce<")):
+    if not k.startswith(("k_trace<", "k_trace_stream<", "k_bounce<", "k_bounce_carry<")):
         return False
     return targs_of(k)[1] == "false"
 
 
 def is_primary(k):
-    if k.startswith("k_bounce<"):
+    if k.startswith(("k_bounce<", "k_bounce_carry<")):
         return targs_of(k)[3] == "true"
     if k.startswith("k_trace<"):
         return targs_of(k)[2] == "true"
@@ -168,8 +168,8 @@ def is_primary(k):
 
 
 tr = {k: e for k, e in out["kernels"].items() if is_timed_trace(k) and e.get("launches")}
-if any(k.startswith("k_bounce<") for k in tr):
-    tr = {k: e for k, e in tr.items() if k.startswith("k_bounce<")}
+if any(k.startswith(("k_bounce<", "k_bounce_carry<")) for k in tr):
+    tr = {k: e for k, e in tr.items() if k.startswith(("k_bounce<", "k_bounce_carry<"))}
 sec = {k: e for k, e in tr.items() if not is_primary(k)}
 ri_path = os.path.join(prof, "roofline_inputs.json")
 ri = json.load(open(ri_path)) if os.path.exists(ri_path) else {}
@@ -186,7 +186,7 @@ if tr:
     entry["counters_of"] = [k for k, e in out["kernels"].items() if e is dom][0]
     # time-weighted share of SIMD time the vector pipe issues, per stage (timed instantiations only): what bench.py turns
     # into the frame's vector-issue time (sum over stages of one-stream kernel time x this share)
-    for stage, pref in (("trace", ("k_trace<", "k_trace_stream<")), ("shade", ("k_shade<", "k_shade_pool<", "k_shade_cat<")), ("bounce", ("k_bounce<",))):
+    for stage, pref in (("trace", ("k_trace<", "k_trace_stream<")), ("shade", ("k_shade<", "k_shade_pool<", "k_shade_cat<")), ("bounce", ("k_bounce<", "k_bounce_carry<"))):
         ks = [e for k, e in out["kernels"].items() if k.startswith(pref) and "one_stream" in e and e.get("valu_busy") is not None
               and (stage == "shade" or is_timed_trace(k))]
         tot = sum(e["one_stream"]["total_ms"] for e in ks)
@@ -205,7 +205,7 @@ if tr:
         walk_per_step = lps.get("bounce") or lps.get("trace")
         depth = (bl.get("config") or {}).get("max_bounces")
         def walk(k):
-            return k.startswith(("k_trace<", "k_trace_stream<", "k_bounce<"))
+            return k.startswith(("k_trace<", "k_trace_stream<", "k_bounce<", "k_bounce_carry<"))
         prim_timed = sum(e["launches"] for k, e in out["kernels"].items() if walk(k) and is_primary(k) and is_timed_trace(k) and e.get("launches"))
         prim_all = sum(e["launches"] for k, e in out["kernels"].items() if walk(k) and is_primary(k) and e.get("launches"))
         if walk_per_step and depth and prim_timed:
