@@ -149,6 +149,18 @@ external scene_tree_stats : scene -> int * int * int * int = "ptx_ml_scene_tree_
 external image_pin : scene -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t -> unit = "ptx_ml_image_pin_stub"
 external image_unpin : scene -> unit = "ptx_ml_image_unpin_stub"
 
+(* What Integrator.create's ~diffuse_plus_light slot becomes (ptx_scene_set_lighting): Reference = Pdf.diffuse and the reference's
+   emission formula emit0' = a * emit0 + emit (order-reversed once something emits); Path_order = Pdf.diffuse with every hit's emission
+   weighted by what came before it; Sampled = Path_order with diffuse_plus_light = 1/2 cosine + 1/2 the scene's emissive triangles.
+   Sticky: every later render of the scene reads it.  Failure when Sampled finds no emissive triangle (or more than 64), or while a
+   render runs on the scene. *)
+type lighting = Reference | Path_order | Sampled
+
+external set_lighting_int : scene -> int -> unit = "ptx_ml_set_lighting_stub"
+
+let set_lighting scene lighting =
+  set_lighting_int scene (match lighting with Reference -> 0 | Path_order -> 1 | Sampled -> 2)
+
 external render_flat
   :  scene
   -> int (* width *)

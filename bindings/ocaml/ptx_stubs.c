@@ -253,6 +253,22 @@ CAMLprim value ptx_ml_image_unpin_stub(value handle) {
   CAMLreturn(Val_unit);
 }
 
+/* external set_lighting_int : scene -> int -> unit = "ptx_ml_set_lighting_stub" (ptx_scene_set_lighting; Ptx.set_lighting maps the
+ * variant).  The mode changes what a running render launches next: like image_pin it takes the scene exclusively and raises Failure
+ * while a render runs on another thread or domain. */
+CAMLprim value ptx_ml_set_lighting_stub(value handle, value mode) {
+  CAMLparam2(handle, mode);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_lighting: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_lighting: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_scene_set_lighting(s, (int32_t)Long_val(mode));
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_lighting: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
 /* What a callback trampoline needs: the closure (a GC root registered by the stub that owns this struct) and the first
  * exception a callback raised.  While `raised` is set no further callbacks are made. */
 typedef struct ptx_ml_cb {

@@ -247,6 +247,30 @@ void ptx_scene_destroy(ptx_scene* scene);
 /* copies the build statistics (tree_* and build_ms fields) */
 int32_t ptx_scene_stats(const ptx_scene* scene, ptx_stats* out);
 
+/* The lighting mode of a scene: how a path sums emission and what a Diffuse scatter samples.  Sticky state of the handle (default
+ * PTX_LIGHTING_REFERENCE), read by every entry point that shades -- ptx_render, _multi, _raw_device, _passes_device, _pixels_device,
+ * _progressive, _adaptive, ptx_trace_samples, ptx_debug_first_scatter -- and not by ptx_ppm_render; ptx_scene_replicate copies it, and
+ * the replicas a scene owns (ptx_render with n_gpus > 1) follow it.
+ *   REFERENCE   the reference's text: Pdf.diffuse, emit0' = a * emit0 + emit (integrator.ml:46,65).  With real emitters that formula
+ *               is order-reversed: it scales the emission of EARLIER hits by the attenuation of LATER ones.
+ *   PATH_ORDER  Pdf.diffuse, emit0' = fma(attn0, emit, emit0): every hit's emission weighted by what came BEFORE it.  On a scene
+ *               without emitters this is REFERENCE (there is no emission to order).
+ *   SAMPLED     PATH_ORDER with diffuse_plus_light = 1/2 cosine + 1/2 the emissive triangles, sampled uniformly by area from the hit's
+ *               own two sampler dimensions (the sampler's dimension stays 2 + 2 * max_bounces).  The light list is built the first time
+ *               this mode is set: the tree triangles whose material has a non-zero emit, in build-list order.  Emissive spheres and
+ *               floor triangles are not sampled (they still emit when hit; the cosine half keeps the estimator unbiased).
+ *               PTX_ERR_ARG when the scene has no emissive tree triangle or more than PTX_MAX_LIGHT_TRIANGLES of them.
+ * A host-only scene accepts the call (the light list can be inspected without a GPU).  PTX_ERR_STATE while a render runs on the
+ * scene (from a progress or update callback); PTX_ERR_ARG for an unknown mode. */
+#define PTX_LIGHTING_REFERENCE 0
+#define PTX_LIGHTING_PATH_ORDER 1
+#define PTX_LIGHTING_SAMPLED 2
+#define PTX_MAX_LIGHT_TRIANGLES 64
+int32_t ptx_scene_set_lighting(ptx_scene* scene, int32_t mode);
+/* The mode last set and, once PTX_LIGHTING_SAMPLED has been set, the light list's length and total area (0 and 0.0 before).  Any
+ * out pointer may be NULL. */
+int32_t ptx_scene_lighting(const ptx_scene* scene, int32_t* mode_out, int32_t* n_light_triangles_out, double* light_area_out);
+
 /* Replaces Integrator.render (integrator.ml:130-156) for the whole image on one GPU:
  * rgb_out is HOST memory, width*height*3 doubles, index (y*W + x)*3 + c, y = 0 at the
  * top, post-gamma -- the contents of the reference's Bimage after render. */

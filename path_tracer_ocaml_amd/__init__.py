@@ -36,6 +36,7 @@ EXPORTS = (
     "ptx_film_resolve_banded_device", "ptx_film_resolve_banded_queue", "ptx_release_workspaces",
     "ptx_image_pin", "ptx_image_unpin", "ptx_render_passes_device", "ptx_pixel_error_device", "ptx_render_progressive",
     "ptx_render_pixels_device", "ptx_film_resolve_counts_device", "ptx_pixel_error_counts_device", "ptx_render_adaptive",
+    "ptx_scene_set_lighting", "ptx_scene_lighting",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -106,6 +107,8 @@ def lib():
     L.ptx_math_eval.argtypes = [C.c_int32, C.c_int32, C.c_int64, dp, dp, dp]
     L.ptx_ppm_render.argtypes = [C.c_void_p, C.POINTER(abi.PpmParams), C.POINTER(abi.Light), C.c_int32, dp,
                                  C.POINTER(abi.PpmStats), C.c_void_p, C.c_void_p]
+    L.ptx_scene_set_lighting.argtypes = [C.c_void_p, C.c_int32]
+    L.ptx_scene_lighting.argtypes = [C.c_void_p, ip, ip, dp]
     _LIB = L
     return L
 
@@ -177,6 +180,18 @@ class Scene:
         if not h:
             raise PtxError(f"ptx_scene_replicate failed: {last_error()}")
         return Scene._adopt(h, device, keepalive=self)
+
+    def set_lighting(self, mode):
+        """ptx_scene_set_lighting: abi.PTX_LIGHTING_REFERENCE / _PATH_ORDER / _SAMPLED or its name ("reference", "path-order",
+        "sampled").  Sticky; every later render of this scene reads it."""
+        _check(lib().ptx_scene_set_lighting(self._h, abi.lighting_mode(mode)))
+
+    def lighting(self):
+        """ptx_scene_lighting: (mode, light triangles, their total area); the last two are 0 until "sampled" has been set."""
+        mode, n = C.c_int32(0), C.c_int32(0)
+        area = C.c_double(0.0)
+        _check(lib().ptx_scene_lighting(self._h, C.byref(mode), C.byref(n), C.byref(area)))
+        return mode.value, n.value, area.value
 
     def stats(self):
         st = abi.Stats()

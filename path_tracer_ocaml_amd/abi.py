@@ -14,6 +14,21 @@ PTX_LEAF_SIMD, PTX_LEAF_ARRAY = 0, 1
 PTX_KERNEL_NAMES = ("generate", "trace", "shade", "accum", "film", "bounce")
 PTX_N_KERNELS = 6
 PTX_RENDER_ASYNC = 1
+PTX_LIGHTING_REFERENCE, PTX_LIGHTING_PATH_ORDER, PTX_LIGHTING_SAMPLED = 0, 1, 2
+PTX_LIGHTING_NAMES = ("reference", "path-order", "sampled")
+PTX_MAX_LIGHT_TRIANGLES = 64
+
+
+def lighting_mode(mode):
+    """A PTX_LIGHTING_* value from the value itself or from its name in PTX_LIGHTING_NAMES."""
+    if isinstance(mode, str):
+        if mode not in PTX_LIGHTING_NAMES:
+            raise ValueError(f"lighting must be one of {', '.join(PTX_LIGHTING_NAMES)} (got {mode!r})")
+        return PTX_LIGHTING_NAMES.index(mode)
+    mode = int(mode)
+    if not 0 <= mode < len(PTX_LIGHTING_NAMES):
+        raise ValueError(f"lighting must be 0, 1 or 2 (got {mode})")
+    return mode
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)

@@ -2230,9 +2230,48 @@ struct PtShadeOut {
   uint32_t id;
   int offset;
 };
+/* ------------------------------------------------------------------ light sampling (PTX_LIGHTING_SAMPLED)
+ * Pdf.sample of the light half of diffuse_plus_light: a point on the emissive triangles, uniform by area, from the hit's two sampler
+ * dimensions (u < 0.5 chose this half); returns the world-space unit direction from p towards it.  The scan of the running sums is
+ * wave-uniform (scalar loads); the chosen record is a per-lane gather from a table of at most 64 x 112 bytes. */
+/* (the table through the constant address space: it is never written while a kernel runs, and a load whose address is wave-uniform
+ * is then a scalar load whatever the kernel has stored before it -- from the global address space the compiler keeps vector loads) */
+typedef const double __attribute__((address_space(4))) PtConstDouble;
+__device__ __forceinline__ V3 pt_light_sample(const PtSceneDev& sc, V3 p, double u, double v) {
+  const double x = (2.0 * u) * sc.light_area;
+  const PtConstDouble* table = (const PtConstDouble*)sc.lights;
+  int k = sc.n_lights - 1;
+  for (int j = sc.n_lights - 2; j >= 0; --j)
+    if (x < table[j * PT_LIGHT_DOUBLES + PT_LIGHT_CUM]) k = j; /* ends at the FIRST k with x < cum_k (the last if none) */
+  const double* L = sc.lights + (size_t)k * PT_LIGHT_DOUBLES;
+  const double before = k > 0 ? L[PT_LIGHT_CUM - PT_LIGHT_DOUBLES] : 0.0;
+  const double u2 = pt_base_min((x - before) / L[PT_LIGHT_AREA], 1.0);
+  const double s = pt_sqrt_nonneg(u2);
+  const double b1 = 1.0 - s, b2 = v * s;
+  const double w = 1.0 - b1 - b2;
+  const V3 q = v3_add(v3_add(v3_scale(pt_load_v3(L), w), v3_scale(pt_load_v3(L + 3), b1)), v3_scale(pt_load_v3(L + 6), b2)); /* Triangle point */
+  return v3_normalize(v3_sub(q, p));
+}
+/* Pdf.eval of the light half for the world direction w at p: every light the ray (p, w) meets, by the walk's own element test,
+ * contributes its solid-angle density t^2 / (A_total |n . w|).  The table is indexed uniformly: scalar loads. */
+__device__ __forceinline__ double pt_light_pd(const PtSceneDev& sc, V3 p, V3 w) {
+  double pd = 0.0;
+  const PtConstDouble* table = (const PtConstDouble*)sc.lights;
+  for (int k = 0; k < sc.n_lights; ++k) {
+    const PtConstDouble* L = table + k * PT_LIGHT_DOUBLES;
+    double t = 0.0, bu, bv;
+    if (pt_triangle_intersect(v3(L[0], L[1], L[2]), v3(L[3], L[4], L[5]), v3(L[6], L[7], L[8]), p, w, 0.0, PT_MAX_FINITE, &t, &bu, &bv))
+      pd = pd + (t * t) / (sc.light_area * pt_fabs(v3_dot(v3(L[9], L[10], L[11]), w)));
+  }
+  return pd;
+}
+
 /* The body of `loop` in Integrator.path_tracer (integrator.ml:30-66) for entry i of the queue (PRIMARY: virtual
- * entry i = a camera sample).  CAT = the entry's shading category if the kernel is specialised for one. */
-template <bool EMIT, bool PRIMARY, int CAT>
+ * entry i = a camera sample).  CAT = the entry's shading category if the kernel is specialised for one.
+ * LIT (emissive scenes in lighting modes 1 and 2 only; mode 0 never launches it): emission is summed in path order,
+ * emit0' = fma(attn0, emit, emit0), and in mode 2 (a wave-uniform branch) a Diffuse scatter samples and divides by
+ * diffuse_plus_light = 1/2 cosine + 1/2 emissive triangles. */
+template <bool EMIT, bool PRIMARY, int CAT, bool LIT = false>
 __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQueue& q, const PtHits& hits, const PtContrib& contrib,
                                                const double* __restrict__ alpha, int bounce, int last_bounce,
                                                const PtGenParams& g, uint32_t i, bool live, PtShadeOut& so,
@@ -2321,16 +2360,25 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
           bool scatter_ok = true;
           if (sc_kind == 2) {
             /* Pdf.sample / Pdf.eval (pdf.ml:5-15, shader_space.ml:56-64) */
-            const double r = pt_sqrt_nonneg(su);
-            const double theta = sv * 2.0 * pi;
-            double sn, cs;
-            pt_sincos(theta, &sn, &cs);
-            wo = v3(r * cs, r * sn, pt_sqrt_nonneg(1.0 - su));
+            /* mode 2: Pdf.sample diffuse_plus_light -- u < 0.5 the light half, else the cosine half on (2u - 1, v) */
+            const bool sampled = LIT && sc.lighting == PT_LIGHTING_SAMPLED; /* (wave-uniform) */
+            const double hu = sampled ? 2.0 * su - 1.0 : su;
+            if (sampled && su < 0.5) {
+              wo = pt_quat_transform(sf.rot, pt_light_sample(sc, point, su, sv)); /* Pdf.sample returns a shader-space direction */
+            } else {
+              const double r = pt_sqrt_nonneg(hu);
+              const double theta = sv * 2.0 * pi;
+              double sn, cs;
+              pt_sincos(theta, &sn, &cs);
+              wo = v3(r * cs, r * sn, pt_sqrt_nonneg(1.0 - hu));
+            }
             const double diffuse_pd = (wo.z < 0.0) ? 0.0 : wo.z / pi;
             if (diffuse_pd == 0.0) {
               scatter_ok = false;
             } else {
-              const double pd = diffuse_pd / diffuse_pd; /* divisor = Pdf.eval diffuse_plus_light = the same */
+              double divisor = diffuse_pd; /* modes 0 and 1: divisor = Pdf.eval diffuse_plus_light = the same */
+              if (sampled) divisor = 0.5 * diffuse_pd + 0.5 * pt_light_pd(sc, point, pt_quat_transform(rot_inv, wo));
+              const double pd = diffuse_pd / divisor;
               if (!pt_isfinite(pd)) scatter_ok = false;
               else attenuation = v3_scale(attenuation, pd);
             }
@@ -2342,7 +2390,8 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
             const V3 dir = pt_quat_transform(rot_inv, wo);
             n_o = v3_add(point, v3_scale(dir, 1e-3));
             n_d = dir;
-            n_emit = v3_fma(attenuation, emit0, emit); /* add_mul emit attenuation emit0 */
+            if (LIT) n_emit = v3_fma(attn0, emit, emit0); /* path order: add_mul emit0 attn0 emit, the old attn0 */
+            else n_emit = v3_fma(attenuation, emit0, emit); /* add_mul emit attenuation emit0 */
             n_attn = v3_mul(attenuation, attn0);
             if (last_bounce) {
               /* the recursive call sees max_bounces <= 0: add_mul emit0 attn0 Color.black (integrator.ml:31-32) */
@@ -2490,7 +2539,7 @@ __device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue
   if (so.keep) pt_q_store<EMIT>(out, dst, so.n_o, so.n_d, so.n_attn, so.n_emit, so.id, so.offset);
 }
 
-template <bool EMIT, bool PRIMARY>
+template <bool EMIT, bool PRIMARY, bool LIT = false>
 __global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                 const double* __restrict__ alpha, int bounce, int last_bounce,
                                                 PtGenParams g, uint32_t n_primary, uint32_t* work) {
@@ -2573,7 +2622,7 @@ __global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(
       i = e.x;                                                                                                             \
       sl = (int)e.y;                                                                                                       \
     }                                                                                                                      \
-    pt_shade_entry<EMIT, PRIMARY, K>(sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__);    \
+    pt_shade_entry<EMIT, PRIMARY, K, LIT>(sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
   } break;
       switch (c) {
         PT_POOL_STEP(PT_CAT_MISS)
@@ -2724,7 +2773,7 @@ struct PtSolo {
 #ifndef PT_SOLO_MAX_BLOCKS
 #define PT_SOLO_MAX_BLOCKS 256 /* output blocks a workgroup can note per bounce; a launch whose shares could need more does not run solo */
 #endif
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false>
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
@@ -2853,7 +2902,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
       sl = (int)pool_s[K][start + lane];                                                                                   \
       if (LDS_SCENE && sl == 0xffff) sl = -1; /* (misses are filed with slot -1) */                                        \
     }                                                                                                                      \
-    pt_shade_entry<EMIT, PRIMARY, K>((PT_SHADE_LDS_GEOM && LDS_SCENE) ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
+    pt_shade_entry<EMIT, PRIMARY, K, LIT>((PT_SHADE_LDS_GEOM && LDS_SCENE) ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
   } break;
       switch (c) {
         PT_POOL_STEP(PT_CAT_MISS)

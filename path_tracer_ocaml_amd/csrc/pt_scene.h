@@ -151,6 +151,18 @@ struct PtSceneDev {
   int32_t pad0;
   double bg_horizon[3];
   double bg_zenith[3];
+  /* The lighting mode in effect (PTX_LIGHTING_*; ptx_scene_set_lighting) and, in mode 2, the light table: n_lights records of
+   * PT_LIGHT_DOUBLES doubles {a, b, c, unit normal, area, running sum of the areas}, the scene's emissive tree triangles in build-list
+   * order.  Read only by the instantiations flagged LIT (pt_shade_entry), which mode 0 never launches. */
+  const double* lights;
+  int32_t n_lights;
+  int32_t lighting;
+  double light_area; /* the sum of the areas = the last record's running sum */
 };
+
+#define PT_LIGHTING_SAMPLED 2 /* = PTX_LIGHTING_SAMPLED */
+#define PT_LIGHT_DOUBLES 14
+#define PT_LIGHT_AREA 12
+#define PT_LIGHT_CUM 13
 
 #endif /* PT_SCENE_H */

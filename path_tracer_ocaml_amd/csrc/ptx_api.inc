@@ -221,6 +221,16 @@ struct ptx_scene {
   hipEvent_t ev_slab[8] = {};
   double* reg_ptr = nullptr;                /* the caller's framebuffer while it is pinned (ptx_image_pin) */
   size_t reg_n = 0;
+  /* Lighting (ptx_scene_set_lighting): the mode asked for; the emissive tree triangles of the build list as scene_build found them (9
+   * doubles each, kept up to one past PTX_MAX_LIGHT_TRIANGLES; n_emissive_tris counts them all); the light table made of them when mode
+   * 2 is first set (PT_LIGHT_DOUBLES per record) and its device copy, which lives as long as the handle (queued frames keep reading it);
+   * the number of calls that are rendering with this handle right now */
+  int lighting = 0;
+  int n_emissive_tris = 0;
+  std::vector<double> emissive_tris;
+  std::vector<double> light_table;
+  DevBuf<double> d_lights;
+  std::atomic<int> busy{0};
   /* owned device memory */
   DevBuf<PtNode> nodes;
   DevBuf<double> sph, tri, tri_uv, tri_frame;
@@ -303,6 +313,16 @@ hipEvent_t scene_event(ptx_scene* s) {
   }
   return s->event_pool[s->event_next++];
 }
+
+/* Held by every call that shades with a handle, for as long as it does: ptx_scene_set_lighting refuses meanwhile (a progress or
+ * update callback that tries gets PTX_ERR_STATE).  Calls nest (ptx_render_progressive around its slices). */
+struct RenderBusy {
+  ptx_scene* s;
+  explicit RenderBusy(ptx_scene* s_) : s(s_) { s->busy.fetch_add(1); }
+  ~RenderBusy() { s->busy.fetch_sub(1); }
+  RenderBusy(const RenderBusy&) = delete;
+  RenderBusy& operator=(const RenderBusy&) = delete;
+};
 
 struct LaunchTimer {
   ptx_scene* s;
@@ -466,6 +486,10 @@ void launch_trace(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& 
   else launch_trace_mode<PT_MODE_ARRAY>(s, st, q, h, n_upper, count, pl, work);
 }
 
+/* An emissive scene in lighting mode 1 or 2 (PtSceneDev.lighting holds the mode in effect: mode 1 without emitters is mode 0): the
+ * instantiations flagged LIT.  Such a scene takes the walk-first kernel and never runs solo. */
+bool scene_lit(const ptx_scene* s) { return s->dev.lighting != 0 && s->dev.has_emit != 0; }
+
 /* k_shade_pool leaves holes in its output queue (part-filled blocks): at most one block per (workgroup, bin) */
 /* block numbers are 20 bits next to a 12-bit cursor (pt_pool_push); 0xfffff = "no block yet" */
 constexpr size_t kPoolMaxEntries = (size_t)(PT_POOL_NO_BLOCK - 1) * PT_POOL_BLOCK;
@@ -484,7 +508,10 @@ void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
   const int grid = strided_grid(s, n_upper, threads, per_cu);
   const dim3 gd(grid), bd(threads);
   const size_t lds = (size_t)(threads / 64) * PT_N_SHADE_CAT * 128 * sizeof(uint2);
-  if (s->dev.has_emit) {
+  if (scene_lit(s)) {
+    if (pl.on) hipLaunchKernelGGL((k_shade_pool<true, true, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
+    else hipLaunchKernelGGL((k_shade_pool<true, false, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
+  } else if (s->dev.has_emit) {
     if (pl.on) hipLaunchKernelGGL((k_shade_pool<true, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
     else hipLaunchKernelGGL((k_shade_pool<true, false>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
   } else {
@@ -538,7 +565,7 @@ bool use_fused(const ptx_scene* s, size_t cap_entries) {
  * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
  * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
 bool carry_possible(const ptx_scene* s) {
-  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && s->fused >= 2 && s->solo_entries <= 0 && trace_scene_lds_bytes(s) > 0 && !bounce_from_hbm(s) &&
+  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !scene_lit(s) && s->fused >= 2 && s->solo_entries <= 0 && trace_scene_lds_bytes(s) > 0 && !bounce_from_hbm(s) &&
          bounce_lds_bytes(s, nullptr, true) <= kBounceLdsLimit;
 }
 template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
@@ -583,14 +610,16 @@ void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
     else launch_carry_mode<PT_MODE_ARRAY, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
   }
 }
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE>
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE, bool LIT>
 void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                          size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
   const int stack_depth = std::max(1, s->tree_depth + 1);
   size_t pool_off = 0;
   const size_t lds = bounce_lds_bytes(s, &pool_off);
   /* the instantiation with the loop over a batch's remaining bounces (PtSolo) only where it can be taken */
-  auto kern = (solo.flag != nullptr && !PRIMARY) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, !PRIMARY> : k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false>;
+  /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
+  auto kern = LIT ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT>
+                  : ((solo.flag != nullptr && !PRIMARY) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, !PRIMARY && !LIT> : k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false>);
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
     hipFuncAttributes fa;
@@ -608,26 +637,28 @@ void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
                      (uint32_t)pool_off, s->counters.p, s->bounce_fence_wg, solo);
 }
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LIT>
 void launch_bounce_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                         size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (bounce_from_hbm(s)) launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  else launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+  if (bounce_from_hbm(s)) launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, false, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+  else launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, true, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
 }
-template <int MODE, bool COUNT, bool EMIT>
+template <int MODE, bool COUNT, bool EMIT, bool LIT = false>
 void launch_bounce_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                         size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (pl.on) launch_bounce_inst<MODE, COUNT, EMIT, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  else launch_bounce_inst<MODE, COUNT, EMIT, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+  if (pl.on) launch_bounce_inst<MODE, COUNT, EMIT, true, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+  else launch_bounce_inst<MODE, COUNT, EMIT, false, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
 }
 template <int MODE>
 void launch_bounce_count(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                          size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl, const PtSolo& solo) {
   if (count) {
-    if (s->dev.has_emit) launch_bounce_mode<MODE, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+    if (scene_lit(s)) launch_bounce_mode<MODE, true, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+    else if (s->dev.has_emit) launch_bounce_mode<MODE, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
     else launch_bounce_mode<MODE, true, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
   } else {
-    if (s->dev.has_emit) launch_bounce_mode<MODE, false, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+    if (scene_lit(s)) launch_bounce_mode<MODE, false, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
+    else if (s->dev.has_emit) launch_bounce_mode<MODE, false, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
     else launch_bounce_mode<MODE, false, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
   }
 }
@@ -746,7 +777,7 @@ void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int
        * later ones return at once (the flag: a word of the batch's counts, zeroed with them).  A partial run (run_only) and a
        * hit-distance array without its second half never run solo. */
       PtSolo solo;
-      solo.flag = (run_only < 0 && s->solo_entries > 0 && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
+      solo.flag = (run_only < 0 && s->solo_entries > 0 && !scene_lit(s) && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
       solo.max_entries = (uint32_t)std::max(0, s->solo_entries);
       solo.max_bounces = max_bounces;
       solo.cap_entries = (uint32_t)std::min<size_t>(w.cap_entries, 0xffffffffu);
@@ -1014,6 +1045,7 @@ int wait_progress(const BatchPlan& b, const std::vector<hipEvent_t>& batch_done,
 
 int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStream_t st, ptx_stats* stats,
                ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr, const PassRange& range = PassRange()) {
+  RenderBusy busy(s);
   s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
   s->timed.clear();
   if (stats) {
@@ -1499,6 +1531,18 @@ static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
     b.mx = v3(c.x + r, c.y + r, c.z + r);
     boxes[(size_t)(n_tri + i)] = b;
   }
+  /* the emissive tree triangles in build-list order (ptx_scene_set_lighting makes the light table of them) */
+  s->n_emissive_tris = 0;
+  s->emissive_tris.clear();
+  for (int i = 0; i < n_tri; ++i) {
+    const ptx_material& m = d->materials[d->tri_material[i]];
+    if (m.emit[0] == 0.0 && m.emit[1] == 0.0 && m.emit[2] == 0.0) continue;
+    if (s->n_emissive_tris++ > PTX_MAX_LIGHT_TRIANGLES) continue;
+    for (int v = 0; v < 3; ++v) {
+      const V3 pnt = vtx(d->tri_indices[3 * i + v]);
+      s->emissive_tris.insert(s->emissive_tris.end(), {pnt.x, pnt.y, pnt.z});
+    }
+  }
   const bool simd = d->leaf_kind == PTX_LEAF_SIMD;
   /* builder: desc->reserved 0 = auto (GPU for large scenes on a device, host otherwise), 1 = host, 2 = GPU */
   BvhResult tree;
@@ -1943,6 +1987,64 @@ void ptx_scene_destroy(ptx_scene* s) {
   delete s;
 }
 
+/* The light table of mode 2: per emissive tree triangle {a, b, c, n, A, cum} with n = normalize(cross(b - a, c - a)) (pt_tri_normal: the
+ * host's pt_hypot chain, like tri_frame) and A = 0.5 * sqrt(quadrance(cross(b - a, c - a))); contraction is off for this file. */
+static void light_table_build(ptx_scene* s) {
+  const int n = s->n_emissive_tris;
+  s->light_table.assign((size_t)n * PT_LIGHT_DOUBLES, 0.0);
+  double cum = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double* t = &s->emissive_tris[(size_t)k * 9];
+    const V3 a = v3(t[0], t[1], t[2]), b = v3(t[3], t[4], t[5]), c = v3(t[6], t[7], t[8]);
+    const V3 nrm = pt_tri_normal(a, b, c);
+    const double area = 0.5 * std::sqrt(v3_quadrance(v3_cross(v3_sub(b, a), v3_sub(c, a))));
+    cum = cum + area;
+    double* o = &s->light_table[(size_t)k * PT_LIGHT_DOUBLES];
+    std::memcpy(o, t, sizeof(double) * 9);
+    o[9] = nrm.x; o[10] = nrm.y; o[11] = nrm.z;
+    o[PT_LIGHT_AREA] = area;
+    o[PT_LIGHT_CUM] = cum;
+  }
+}
+
+int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (mode != PTX_LIGHTING_REFERENCE && mode != PTX_LIGHTING_PATH_ORDER && mode != PTX_LIGHTING_SAMPLED) return fail(PTX_ERR_ARG, "unknown lighting mode %d", mode);
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lighting mode cannot change while a render runs on the scene");
+  if (mode == PTX_LIGHTING_SAMPLED) {
+    if (s->n_emissive_tris == 0) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
+    if (s->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return fail(PTX_ERR_ARG, "%d emissive tree triangles, more than PTX_MAX_LIGHT_TRIANGLES = %d (no light hierarchy)", s->n_emissive_tris, PTX_MAX_LIGHT_TRIANGLES);
+    if (s->light_table.empty()) light_table_build(s);
+    if (s->device >= 0 && !s->d_lights.p) {
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(s->d_lights.ensure(s->light_table.size()));
+      HIP_TRY(hipMemcpy(s->d_lights.p, s->light_table.data(), sizeof(double) * s->light_table.size(), hipMemcpyHostToDevice));
+    }
+  }
+  s->lighting = mode;
+  if (s->device >= 0) {
+    /* the mode in effect: without emitters there is no emission to order, and mode 1 is mode 0 */
+    s->dev.lighting = s->dev.has_emit ? mode : PTX_LIGHTING_REFERENCE;
+    s->dev.lights = mode == PTX_LIGHTING_SAMPLED ? s->d_lights.p : nullptr;
+    s->dev.n_lights = mode == PTX_LIGHTING_SAMPLED ? s->n_emissive_tris : 0;
+    s->dev.light_area = mode == PTX_LIGHTING_SAMPLED ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
+  }
+  for (ptx_scene* r : s->replicas) {
+    const int rc = ptx_scene_set_lighting(r, mode);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_lighting(const ptx_scene* s, int32_t* mode_out, int32_t* n_light_triangles_out, double* light_area_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (mode_out) *mode_out = s->lighting;
+  /* the light list exists once mode 2 has been set */
+  if (n_light_triangles_out) *n_light_triangles_out = (int32_t)(s->light_table.size() / PT_LIGHT_DOUBLES);
+  if (light_area_out) *light_area_out = s->light_table.empty() ? 0.0 : s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM];
+  return 0;
+}
+
 int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
   if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
   std::memset(out, 0, sizeof *out);
@@ -2037,7 +2139,9 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->n_prims = src->n_prims;
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;
-  if (scene_upload(s) != 0) {
+  s->n_emissive_tris = src->n_emissive_tris;
+  s->emissive_tris = src->emissive_tris;
+  if (scene_upload(s) != 0 || (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
     ptx_scene_destroy(s);
     return nullptr;
   }
@@ -2406,6 +2510,7 @@ void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
  * the update to the host on cs; call_back(update, cur, next, samples, rel) is the caller's callback and the stopping rule. */
 extern "C++" template <class Policy>
 int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool want_err, double* rgb_out, double* err_out, ptx_stats* stats) {
+  RenderBusy busy(s);
   const double t0 = wall_ms();
   const long long npix = (long long)p.width * p.height;
   const size_t n = (size_t)npix * 3;
@@ -2764,6 +2869,7 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
     if (xs[i] < 0 || xs[i] >= p->width || ys[i] < 0 || ys[i] >= p->height || passes[i] < 0 || passes[i] >= p->samples_per_pixel)
       return fail(PTX_ERR_ARG, "sample %lld out of range", (long long)i);
   HIP_TRY(hipSetDevice(s->device));
+  RenderBusy busy(s);
   Workspace w;
   s->sets_in_flight = 1;
   rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
@@ -2894,6 +3000,7 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
   if (rc) return rc;
   if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
   HIP_TRY(hipSetDevice(s->device));
+  RenderBusy busy(s);
   Workspace w;
   s->sets_in_flight = 1;
   rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
-EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_camera_create", "pth_scene_shirley", "pth_scene_cornell",
+EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_camera_create", "pth_scene_shirley", "pth_scene_cornell", "pth_scene_cornell_lamp",
            "pth_scene_ganesha_like", "pth_write_png", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
@@ -31,6 +31,8 @@ def lib():
         L.pth_scene_shirley.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
         L.pth_scene_cornell.restype = C.c_void_p
         L.pth_scene_cornell.argtypes = [C.c_int32, C.c_int32, C.c_double]
+        L.pth_scene_cornell_lamp.restype = C.c_void_p
+        L.pth_scene_cornell_lamp.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]
         L.pth_scene_ganesha_like.restype = C.c_void_p
         L.pth_scene_ganesha_like.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64]
         L.pth_write_png.argtypes = [C.c_char_p, C.c_int32, C.c_int32, abi.c_double_p]
@@ -125,6 +127,12 @@ def shirley_spheres(width, height, no_simd=False, seed=42):
 def cornell_box(width, height, ceiling_emit=12.0):
     """cornell-box/bin/main.ml geometry + the documented ceiling emitter (path-integrator lighting)."""
     return HostScene(lib().pth_scene_cornell(width, height, ceiling_emit))
+
+
+def cornell_lamp(width, height, ceiling_emit=0.0, lamp_half_side=0.03, lamp_y=0.999, lamp_emit=400.0):
+    """cornell_box plus a square lamp (two triangles appended after all others) of that half side and emission, centred at
+    (0.5, lamp_y, 0.5): the scene Scene.set_lighting("sampled") is for."""
+    return HostScene(lib().pth_scene_cornell_lamp(width, height, ceiling_emit, lamp_half_side, lamp_y, lamp_emit))
 
 
 def ganesha_like(width, height, n_target=150000, seed=7):

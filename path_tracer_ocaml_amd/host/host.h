@@ -24,6 +24,12 @@ void pth_camera_create(const double eye[3], const double target[3], const double
 pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed);
 /* cornell-box/bin/main.ml geometry + documented ceiling emitter */
 pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit);
+/* pth_scene_cornell plus a lamp, two triangles appended after all others: a horizontal square of half side lamp_half_side centred at
+ * (0.5, lamp_y, 0.5), vertices a = (-, y, -), b = (+, y, -), c = (+, y, +), d = (-, y, +), triangles (a, b, c) and (a, c, d), through
+ * the camera like the rest; Lambertian, solid black, emit = lamp_emit (the reference lights this box from light_center =
+ * (0.5, 0.82, 0.5)).  What ptx_scene_set_lighting(PTX_LIGHTING_SAMPLED) is for. */
+pth_scene* pth_scene_cornell_lamp(int32_t width, int32_t height, double ceiling_emit, double lamp_half_side, double lamp_y,
+                                  double lamp_emit);
 /* ganesha/bin/main.ml camera / floor / material over a synthetic mesh of ~n_target triangles */
 pth_scene* pth_scene_ganesha_like(int32_t width, int32_t height, int32_t n_target, uint64_t seed);
 

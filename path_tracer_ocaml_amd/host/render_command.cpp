@@ -10,6 +10,8 @@
 // --progressive=K / --target-error=E: -o rewritten after every K passes (ptx_render_progressive), as the photon-map binaries
 // rewrite it after every iteration, stopping early once the frame's relative standard error is at most E; and --adaptive=T
 // (with --progressive=K passes per round and --min-passes=M): per-pixel pass counts, ptx_render_adaptive.
+// --lighting=reference|path-order|sampled: the scene's lighting mode (ptx_scene_set_lighting); --lamp=HALF_SIDE,Y,EMIT (with
+// --scene=cornell): a square lamp of that half side and emission at height Y (pth_scene_cornell_lamp).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +41,9 @@ struct Args {
   double target_error = 0.0; // stop at the first update whose rel_err is <= this (0 = never)
   double adaptive = -1.0;    // per-pixel target T of ptx_render_adaptive (< 0: not adaptive)
   int min_passes = 0;        // --min-passes (0: not given; 8 with --adaptive)
+  int lighting = PTX_LIGHTING_REFERENCE; // --lighting
+  bool have_lamp = false;                // --lamp=HALF_SIDE,Y,EMIT
+  double lamp_half_side = 0.0, lamp_y = 0.0, lamp_emit = 0.0;
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -47,7 +52,8 @@ struct Args {
                "Usage: %s -d WIDTH,HEIGHT [--samples-per-pixel=INT] [-o PATH] [--no-progress]\n"
                "          [--max-ray-bounces=INT] [--no-simd] [--scene=shirley|cornell|ganesha] [--device=INT] [--gpus=INT]\n"
                "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
-               "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n",
+               "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
+               "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -100,6 +106,17 @@ Args parse(int argc, char** argv) {
     } else if (take_value(argc, argv, i, "min-passes", nullptr, &v)) {
       a.min_passes = std::atoi(v.c_str());
       if (a.min_passes < 2) usage(argv[0], "invalid value for --min-passes, must be >= 2");
+    } else if (take_value(argc, argv, i, "lighting", nullptr, &v)) {
+      if (v == "reference") a.lighting = PTX_LIGHTING_REFERENCE;
+      else if (v == "path-order") a.lighting = PTX_LIGHTING_PATH_ORDER;
+      else if (v == "sampled") a.lighting = PTX_LIGHTING_SAMPLED;
+      else usage(argv[0], "invalid value for --lighting, expected reference, path-order or sampled");
+    } else if (take_value(argc, argv, i, "lamp", nullptr, &v)) {
+      char tail = 0;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &a.lamp_half_side, &a.lamp_y, &a.lamp_emit, &tail) != 3)
+        usage(argv[0], "invalid value for --lamp, expected HALF_SIDE,Y,EMIT");
+      if (!(a.lamp_half_side > 0.0) || !(a.lamp_emit > 0.0) || !(a.lamp_y == a.lamp_y)) usage(argv[0], "invalid value for --lamp, HALF_SIDE and EMIT must be > 0");
+      a.have_lamp = true;
     }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
@@ -120,6 +137,7 @@ Args parse(int argc, char** argv) {
   if (a.min_passes && !adaptive) usage(argv[0], "--min-passes requires --adaptive");
   if (a.target_error > 0.0 && !a.progressive) usage(argv[0], "--target-error requires --progressive");
   if (a.progressive && a.gpus > 1) usage(argv[0], "--progressive renders on one GPU (--gpus=1)");
+  if (a.have_lamp && a.scene != "cornell") usage(argv[0], "--lamp requires --scene=cornell");
   return a;
 }
 
@@ -181,7 +199,9 @@ int main(int argc, char** argv) {
   const Args a = parse(argc, argv);
   pth_scene* hs = nullptr;
   if (a.scene == "shirley") hs = pth_scene_shirley(a.width, a.height, a.no_simd ? 1 : 0, 42); // Random.init 42
-  else if (a.scene == "cornell") hs = pth_scene_cornell(a.width, a.height, a.ceiling_emit);
+  else if (a.scene == "cornell")
+    hs = a.have_lamp ? pth_scene_cornell_lamp(a.width, a.height, a.ceiling_emit, a.lamp_half_side, a.lamp_y, a.lamp_emit)
+                     : pth_scene_cornell(a.width, a.height, a.ceiling_emit);
   else if (a.scene == "ganesha")
     hs = a.ganesha_ply.empty() ? pth_scene_ganesha_like(a.width, a.height, a.ganesha_triangles, 7) : pth_scene_ganesha_ply(a.ganesha_ply.c_str(), a.width, a.height);
   else usage(argv[0], "unknown --scene");
@@ -196,6 +216,10 @@ int main(int argc, char** argv) {
   ptx_scene* scene = ptx_scene_create(d, a.device);
   if (!scene) {
     std::fprintf(stderr, "ptx_scene_create: %s\n", ptx_last_error());
+    return 1;
+  }
+  if (a.lighting != PTX_LIGHTING_REFERENCE && ptx_scene_set_lighting(scene, a.lighting) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_lighting: %s\n", ptx_last_error());
     return 1;
   }
   ptx_stats st;

@@ -322,7 +322,8 @@ pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int
 
 // cornell-box/bin/main.ml geometry for the path integrator; ceiling_emit is the documented emitter
 // extension (the reference lights this scene with a photon-map point light the path integrator ignores).
-pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit) {
+// lamp (pth_scene_cornell_lamp): null, or {half side, y, emit} of a square lamp appended after everything else
+static pth_scene* cornell_build(int32_t width, int32_t height, double ceiling_emit, const double* lamp) {
   pth_scene* s = new pth_scene();
   const double fov = (2.0 * std::atan(0.5)) * 180.0 / kPi;
   const Camera cam = camera_create(v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, fov);
@@ -362,6 +363,16 @@ pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit)
     const double big = 10.0;
     s->sphere(camera_transform(cam, v3(0.5, 0.5, -2.0 - big)), big, m_back);
   }
+  if (lamp) { // a = (-, y, -), b = (+, y, -), c = (+, y, +), d = (-, y, +): triangles (a, b, c), (a, c, d), the last of the list
+    const double h = lamp[0], y = lamp[1];
+    const int m_lamp = s->material(PTX_MAT_LAMBERTIAN, s->solid(0.0, 0.0, 0.0));
+    for (double& e : s->mats[(size_t)m_lamp].emit) e = lamp[2];
+    const V3 a = v3(0.5 - h, y, 0.5 - h), b = v3(0.5 + h, y, 0.5 - h), c = v3(0.5 + h, y, 0.5 + h), d = v3(0.5 - h, y, 0.5 + h);
+    Tri t1{a, b, c, {}, m_lamp}, t2{a, c, d, {}, m_lamp};
+    uv3(t1.uv, kT00, kT10, kT11);
+    uv3(t2.uv, kT00, kT11, kT01);
+    emit({t1, t2});
+  }
   s->d.camera = cam.view;
   s->d.background = ptx_background{};
   s->d.background.kind = PTX_BG_BLACK;
@@ -370,6 +381,13 @@ pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit)
   s->d.num_bins = 32;
   s->sync();
   return s;
+}
+
+pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit) { return cornell_build(width, height, ceiling_emit, nullptr); }
+pth_scene* pth_scene_cornell_lamp(int32_t width, int32_t height, double ceiling_emit, double lamp_half_side, double lamp_y,
+                                  double lamp_emit) {
+  const double lamp[3] = {lamp_half_side, lamp_y, lamp_emit};
+  return cornell_build(width, height, ceiling_emit, lamp);
 }
 
 // Synthetic "ganesha-like" mesh (the real ganesha.ply is not in the reference repository): a closed
