@@ -362,10 +362,7 @@ __device__ __forceinline__ bool pt_slab_hit_exact(const double* nb, V3 o, V3 inv
  *   bytes 44..59  skip[8] u16          bytes 60..75  near[8] u16          bytes 76..83  unused (see PT_SWZ_NODE_BYTES)
  * and every node reference (lhs, rhs, skip, near, the walk's `node`) is the node's ABSOLUTE LDS byte address, so a visit
  * starts reading at `node` itself (PT_SWZ_END / PT_SWZ_LEAF stay out of range: the image ends below 0xfffe). */
-#ifndef PT_SWZ_NODE_BYTES
-#define PT_SWZ_NODE_BYTES 92 /* 80 used + 12: 23 words, an ODD stride, so that node k starts in LDS bank 21 k mod 64 -- all 64 banks.
-                                With 80 bytes (20 words) the nodes start in 16 of the 64 banks only, with 64 bytes in 4 */
-#endif
+/* (PT_SWZ_NODE_BYTES of this layout: pt_scene.h) */
 #define PT_SWZ_OFF_LINKS 36
 #define PT_SWZ_OFF_SKIP 44
 #define PT_SWZ_OFF_NEAR 60
@@ -379,6 +376,7 @@ typedef unsigned int pt_u2 __attribute__((ext_vector_type(2), aligned(4)));
 /*   words 12..15 near[8], u16 each: for octant o the NEAR child of a branch (shape_tree.ml:209: lhs if bit `axis` of o is set,
  *               else rhs), PT_SWZ_LEAF for a leaf.  With it a visit needs no axis extraction, no bit test and no child select:
  *               next = hit an inner node ? near[o] : skip[o]. */
+#undef PT_SWZ_NODE_BYTES
 #define PT_SWZ_NODE_BYTES 64
 #define PT_SWZ_OFF_LINKS 24
 #define PT_SWZ_OFF_SKIP 32
@@ -386,6 +384,7 @@ typedef unsigned int pt_u2 __attribute__((ext_vector_type(2), aligned(4)));
 #undef PT_SWZ_SIGNSEL
 #define PT_SWZ_SIGNSEL 0
 #else
+#undef PT_SWZ_NODE_BYTES
 #define PT_SWZ_NODE_BYTES 48
 #define PT_SWZ_OFF_LINKS 24
 #define PT_SWZ_OFF_SKIP 32
@@ -433,8 +432,6 @@ struct PtThreadTag {};
  * instead of 6 MB of image + table).  A pre-order tree needs no lhs link (the lhs child of node k is k + 1), which is what
  * frees the word: inner nodes keep `rhs | axis << 30`, leaves pack `tag << 30 | real slots << 22 | first slot`. */
 struct PtThreadOctTag {};
-#define PT_OCT_LEAF_FIRST_BITS 22
-#define PT_OCT_LEAF_REAL_MAX 255u
 /* Round 5, second layout of the per-octant record: what the tagged links did for the LDS image, for the walk from
  * HBM / L2 -- where four fifths of the visits are answered by the L1 in ~120 clocks and the ~45 vector + ~40 scalar instructions
  * the old record cost per visit were as long a chain as the load.  An octant fixes the sign of every direction component, so
@@ -465,8 +462,7 @@ struct PtThreadOctTag {};
                                    the binary64 test TOGETHER after the loop (resolve_pending), before the leaf phase.  Same tests per ray, same order */
 #endif
 #define PT_OCT_PENDING 0xc0000000u /* top bits 11: "the test of node (low 30 bits) awaits its binary64 evaluation"; oct_link / oct_skip hold its links */
-#define PT_OCT_END 0x80000000u
-#define PT_OCT_LEAF_TAG 0x40000000u
+/* (PT_OCT_LEAF_FIRST_BITS, PT_OCT_LEAF_REAL_MAX, PT_OCT_END, PT_OCT_LEAF_TAG: pt_scene.h, the host builds the image) */
 
 struct PtSceneView {
   const PtNode* nodes;
@@ -1948,10 +1944,7 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
 }
 
 /* ------------------------------------------------------------------ shade */
-struct Quat {
-  double r;
-  V3 v;
-};
+/* (Quat, pt_shader_rotation and pt_tri_normal: pt_vec.h -- the host computes tri_frame and the light table with them) */
 /* Quaternion.mul (quaternion.ml:25-32) */
 __device__ __forceinline__ Quat pt_quat_mul(Quat a, Quat b) {
   Quat o;
@@ -1969,28 +1962,6 @@ __device__ __forceinline__ V3 pt_quat_transform(Quat t, V3 v) {
   c.v = v3_neg(t.v);
   return pt_quat_mul(pt_quat_mul(t, p), c).v;
 }
-/* Shader_space.create (shader_space.ml:11-23) + Quaternion.normalize (quaternion.ml:11-15) */
-__host__ __device__ __forceinline__ Quat pt_shader_rotation(V3 normal) {
-  const double epsilon = 1e-9;
-  Quat q;
-  if (normal.z > 1.0 - epsilon) {
-    q.r = 1.0;
-    q.v = v3(0.0, 0.0, 0.0);
-  } else if (normal.z < epsilon - 1.0) {
-    q.r = 0.0;
-    q.v = v3(0.0, 1.0, 0.0);
-  } else {
-    const double r = 1.0 + normal.z;
-    const V3 v = v3(normal.y, -normal.x, 0.0);
-    const double s = pt_rnorm_frame(r, v.x, v.y); /* v.z = 0 */
-    q.r = r * s;
-    q.v = v3_scale(v, s);
-  }
-  return q;
-}
-/* Triangle.Hit.to_hit's geometric normal (triangle.ml:43-64) */
-#define PT_TRI_FRAME_DOUBLES 12
-__host__ __device__ __forceinline__ V3 pt_tri_normal(V3 a, V3 b, V3 c) { return v3_normalize(v3_cross(v3_sub(b, a), v3_sub(c, a))); }
 __device__ __forceinline__ Quat pt_quat_conj(Quat q) {
   Quat c;
   c.r = q.r;

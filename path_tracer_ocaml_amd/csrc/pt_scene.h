@@ -1,5 +1,5 @@
 /* pt_scene.h -- the flattened scene as it lives in HBM, shared by the host builder
- * (bvh_build.cpp) and the HIP kernels (kernels.hip).
+ * (bvh_build.cpp for the tree, scene_host.cpp for everything made of it) and the HIP kernels (kernels.hip).
  *
  * Layout decisions:
  *  - BVH node = one 64-byte record (bbox 6 x f64 + two u32 links), 64-byte aligned: a lane
@@ -20,6 +20,22 @@
 #define PT_TOP_FLAG 0x20000000u /* a node reference into the LDS-resident top image (PtSceneDev.top_nodes): flag | byte offset */
 #define PT_TOP_NODE_BYTES 64
 #define PT_MAX_FINITE 1.7976931348623157e308
+
+/* Layout constants of the images the host builds (scene_host.cpp) and the kernels walk (kernels.hip describes the walks). */
+/* bytes per node of the LDS-resident filter image; the host's "fits LDS" threshold: a tree of n_nodes * PT_SWZ_NODE_BYTES >= 65535
+ * bytes is walked from HBM / L2 and gets the per-octant and the top image */
+#ifndef PT_SWZ_NODE_BYTES
+#define PT_SWZ_NODE_BYTES 92 /* 80 used + 12: 23 words, an ODD stride, so that node k starts in LDS bank 21 k mod 64 -- all 64 banks.
+                                With 80 bytes (20 words) the nodes start in 16 of the 64 banks only, with 64 bytes in 4 */
+#endif
+/* the per-octant record (PtSceneDev.nodes32o): word 6 of a leaf = PT_OCT_LEAF_TAG | real slots << PT_OCT_LEAF_FIRST_BITS | first slot,
+ * word 7 = the octant's skip link or PT_OCT_END */
+#define PT_OCT_LEAF_FIRST_BITS 22
+#define PT_OCT_LEAF_REAL_MAX 255u
+#define PT_OCT_END 0x80000000u
+#define PT_OCT_LEAF_TAG 0x40000000u
+#define PT_TRI_FRAME_DOUBLES 12 /* PtSceneDev.tri_frame: doubles per slot */
+constexpr int kTriFrameMaxSlots = 1024; /* PtSceneDev.tri_frame: <= 96 KB, resident in L1 / L2 */
 
 /* One BVH node, 64 bytes.  Tree.t = Bbox.t * (Leaf | Branch {axis; lhs; rhs}), shape_tree.ml:153-161 */
 struct __attribute__((aligned(64))) PtNode {
@@ -89,8 +105,8 @@ struct PtSceneDev {
   const double* tri_uv;/* n_slots x 6 */
   /* Small scenes with triangles: what Triangle.Hit.to_hit + Shader_space.create derive from the triangle ALONE, per slot, 12 doubles:
    * {g_normal xyz, -, rotation of +g_normal (r, x, y, z), rotation of -g_normal}.  Computed once on the host with the functions
-   * the shade step itself uses (pt_surface_hit), so a load replaces ~130 vector instructions per triangle hit with the same
-   * bits.  NULL: the shade step computes them (large meshes: the table would be one more gathered line per segment). */
+   * the shade step itself uses (pt_tri_normal / pt_shader_rotation of pt_vec.h; scene_host.cpp), so a load replaces ~130 vector
+   * instructions per triangle hit with the same bits.  NULL: the shade step computes them (large meshes: the table would be one more gathered line per segment). */
   const double* tri_frame;
   const uint8_t* slot_kind;
   const uint8_t* slot_cat;  /* shading category of the slot's material, PT_CAT_* (wave-coherent shading) */
@@ -104,7 +120,8 @@ struct PtSceneDev {
   int32_t has_checker;
   /* LDS-resident scenes: 1 = the LDS image also carries every node's six binary64 bounds (48 bytes per node) for the tests the
    * binary32 filter leaves undecided -- 2 % (Shirley) to 5.5 % (cornell) of a walk's wave steps, each of which otherwise waits for a
-   * global load.  Set by the host when the scene still fits LDS with them (scene_upload). */
+   * global load.  Set per upload (scene_upload in ptx_api.inc: it depends on the device's LDS, unlike the
+   * scalars scene_host.cpp fills) when the scene still fits LDS with them. */
   int32_t lds_nodes64;
   const PtMaterial* materials;
   const PtTexture* textures;

@@ -47,6 +47,33 @@ PT_HD V3 v3_cross(V3 p, V3 q) {
 }
 PT_HD double v3_axis(V3 v, int axis) { return axis == 0 ? v.x : (axis == 1 ? v.y : v.z); }
 
+/* Quaternion.t (quaternion.ml) and the two functions of the shade step that the host evaluates too (tri_frame, the light table) */
+struct Quat {
+  double r;
+  V3 v;
+};
+/* Shader_space.create (shader_space.ml:11-23) + Quaternion.normalize (quaternion.ml:11-15) */
+PT_HD Quat pt_shader_rotation(V3 normal) {
+  const double epsilon = 1e-9;
+  Quat q;
+  if (normal.z > 1.0 - epsilon) {
+    q.r = 1.0;
+    q.v = v3(0.0, 0.0, 0.0);
+  } else if (normal.z < epsilon - 1.0) {
+    q.r = 0.0;
+    q.v = v3(0.0, 1.0, 0.0);
+  } else {
+    const double r = 1.0 + normal.z;
+    const V3 v = v3(normal.y, -normal.x, 0.0);
+    const double s = pt_rnorm_frame(r, v.x, v.y); /* v.z = 0 */
+    q.r = r * s;
+    q.v = v3_scale(v, s);
+  }
+  return q;
+}
+/* Triangle.Hit.to_hit's geometric normal (triangle.ml:43-64) */
+PT_HD V3 pt_tri_normal(V3 a, V3 b, V3 c) { return v3_normalize(v3_cross(v3_sub(b, a), v3_sub(c, a))); }
+
 /* Bbox.t (bbox.ml:3-6) */
 struct Box {
   V3 mn, mx;

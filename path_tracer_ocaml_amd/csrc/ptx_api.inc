@@ -17,6 +17,7 @@
 
 #include "../../include/ptx.h"
 #include "bvh_build.h"
+#include "scene_host.h"
 
 namespace {
 
@@ -34,10 +35,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define PTX_ERR_ARG (-1)
-#define PTX_ERR_HIP (-2)
-#define PTX_ERR_STATE (-3)
-
+/* (PTX_ERR_ARG / PTX_ERR_HIP / PTX_ERR_STATE: scene_host.h) */
 #define HIP_TRY(expr)                                                                              \
   do {                                                                                             \
     hipError_t e_ = (expr);                                                                        \
@@ -184,32 +182,13 @@ constexpr int kMaxSets = 4; /* batches in flight (one HIP stream and one workspa
 /* the per-batch control words, zeroed together: counts[b] = live paths entering bounce b (130 words), then per
  * bounce kWorkPerBounce work-distribution words (PtChunkFeed counters, per-category list lengths) */
 /* per bounce kWorkPerBounce words: [0..7] trace feed, [16 + 8 c ..] shade feed of category c (5), [56..60] category list lengths */
-constexpr int kTriFrameMaxSlots = 1024; /* PtSceneDev.tri_frame: <= 96 KB, resident in L1 / L2 */
 constexpr size_t kSoloFlagWord = 130; /* (counts[0 .. 127] are the bounces' queue counts) k_bounce's PtSolo.flag */
 constexpr size_t kWorkBase = 136, kWorkPerBounce = 64, kCountsWords = kWorkBase + 128 * kWorkPerBounce;
-
-/* Everything ptx_scene_create uploads, kept on the host (<= 20 MB even for 150 k triangles) so that a REPLICA of the
- * scene on another device is one more upload, not another BVH build (ptx_scene_replicate, ptx_render n_gpus > 1). */
-struct PtHostArrays {
-  std::vector<PtNode> nodes;
-  std::vector<double> sph, tri, tri_uv, tri_frame;
-  std::vector<uint8_t> kind, cat;
-  std::vector<int32_t> slot_mat, slot_prim;
-  std::vector<PtMaterial> mats;
-  std::vector<PtTexture> texs;
-  std::vector<PtShadeRec> shade;
-  std::vector<uint16_t> skip; /* node_skip: n_nodes x 8, empty for trees of >= 65535 nodes */
-  std::vector<uint32_t> skip32; /* node_skip32: n_nodes x 8 */
-  std::vector<uint32_t> nodes32; /* 8 words per node: the binary32 filter image for the walk from HBM / L2 */
-  std::vector<uint32_t> nodes32o; /* PtSceneDev.nodes32o: 8 octants x 8 words per node; empty = not built */
-  std::vector<uint32_t> top_nodes, skip32_top; /* PtSceneDev.top_nodes (16 words per top node) / node_skip32_top; empty = none */
-  PtSceneDev dev{}; /* the scalar fields; device pointers are filled per upload */
-};
 
 struct ptx_scene {
   int device = 0;
   PtSceneDev dev{};
-  std::shared_ptr<const PtHostArrays> host; /* shared by a scene and its replicas */
+  std::shared_ptr<const PtHostArrays> host; /* scene_host.h; shared by a scene and its replicas; a host-only scene's holds the tree only */
   std::vector<ptx_scene*> replicas;         /* ptx_render with n_gpus > 1: owned, destroyed with the scene */
   std::set<const void*> attr_done;          /* kernels whose dynamic-LDS limit was raised on THIS scene's device */
   int peer_root = -1;                       /* ptx_render_multi: the root device peer access was last set up with ... */
@@ -221,13 +200,10 @@ struct ptx_scene {
   hipEvent_t ev_slab[8] = {};
   double* reg_ptr = nullptr;                /* the caller's framebuffer while it is pinned (ptx_image_pin) */
   size_t reg_n = 0;
-  /* Lighting (ptx_scene_set_lighting): the mode asked for; the emissive tree triangles of the build list as scene_build found them (9
-   * doubles each, kept up to one past PTX_MAX_LIGHT_TRIANGLES; n_emissive_tris counts them all); the light table made of them when mode
-   * 2 is first set (PT_LIGHT_DOUBLES per record) and its device copy, which lives as long as the handle (queued frames keep reading it);
+  /* Lighting (ptx_scene_set_lighting): the mode asked for; the light table made of host->emissive_tris when mode 2 is first set
+   * (PT_LIGHT_DOUBLES per record) and its device copy, which lives as long as the handle (queued frames keep reading it);
    * the number of calls that are rendering with this handle right now */
   int lighting = 0;
-  int n_emissive_tris = 0;
-  std::vector<double> emissive_tris;
   std::vector<double> light_table;
   DevBuf<double> d_lights;
   std::atomic<int> busy{0};
@@ -241,9 +217,6 @@ struct ptx_scene {
   DevBuf<PtShadeRec> slot_shade;
   DevBuf<uint16_t> node_skip;
   DevBuf<uint32_t> node_skip32, nodes32, nodes32o, top_nodes, node_skip32_top;
-  /* host copies for inspection */
-  std::vector<PtNode> h_nodes;
-  std::vector<int32_t> h_slot_prim;
   int n_prims = 0;
   int tree_depth = 0, tree_leaves = 0;
   double build_ms = 0.0;
@@ -823,7 +796,7 @@ int collect_counters(ptx_scene* s, ptx_stats* stats) {
 }
 
 void fill_tree_stats(const ptx_scene* s, ptx_stats* st) {
-  st->tree_nodes = (int32_t)s->h_nodes.size();
+  st->tree_nodes = (int32_t)s->host->nodes.size();
   st->tree_depth = s->tree_depth;
   st->tree_leaves = s->tree_leaves;
   st->leaf_slots = s->dev.n_slots;
@@ -1478,71 +1451,13 @@ static int scene_upload(ptx_scene* s) {
   return 0;
 }
 
+/* descriptor -> boxes -> tree -> host arrays (scene_host.cpp) -> upload; a host-only scene stops after the tree */
 static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
   const double t0 = wall_ms();
-  const int n_tri = d->n_triangles, n_sph = d->n_spheres, n = n_tri + n_sph;
-  if (n_tri < 0 || n_sph < 0 || d->n_floor_triangles < 0) return fail(PTX_ERR_ARG, "negative primitive count");
-  if (n == 0) return fail(PTX_ERR_ARG, "Shape_tree.create: expected non-empty list of shapes");
-  if (d->leaf_kind != PTX_LEAF_SIMD && d->leaf_kind != PTX_LEAF_ARRAY) return fail(PTX_ERR_ARG, "unknown leaf_kind %d", d->leaf_kind);
-  if (d->leaf_kind == PTX_LEAF_SIMD && (n_tri > 0 || d->n_floor_triangles > 0)) return fail(PTX_ERR_ARG, "Simd_leaf holds spheres only");
-  if (d->leaf_kind == PTX_LEAF_SIMD && d->length_cutoff > 16) return fail(PTX_ERR_ARG, "Simd_leaf length_cutoff must be <= leaf_size () = 16");
-  if (d->length_cutoff < 1) return fail(PTX_ERR_ARG, "length_cutoff must be >= 1");
-  const int num_bins = d->num_bins > 0 ? d->num_bins : 32;
-  if (num_bins < 4) return fail(PTX_ERR_ARG, "num_bins must be >= 4 (shape_tree.ml:253)");
-  if (d->n_materials <= 0 || !d->materials) return fail(PTX_ERR_ARG, "no materials");
-  if (n_sph > 0 && !(d->sphere_x && d->sphere_y && d->sphere_z && d->sphere_r && d->sphere_material)) return fail(PTX_ERR_ARG, "sphere arrays missing");
-  if (n_tri > 0 && !(d->vertex_x && d->vertex_y && d->vertex_z && d->tri_indices && d->tri_uv && d->tri_material)) return fail(PTX_ERR_ARG, "triangle arrays missing");
-  if (d->n_floor_triangles > 0 && !(d->floor_vertices && d->floor_uv && d->floor_material)) return fail(PTX_ERR_ARG, "floor arrays missing");
-  bool has_emit = false, has_checker = false;
-  for (int i = 0; i < d->n_materials; ++i) {
-    const ptx_material& m = d->materials[i];
-    if (m.kind < 0 || m.kind > 2) return fail(PTX_ERR_ARG, "material %d: unknown kind %d", i, m.kind);
-    if (m.kind != PTX_MAT_DIELECTRIC && (m.texture < 0 || m.texture >= d->n_textures)) return fail(PTX_ERR_ARG, "material %d: texture %d out of range", i, m.texture);
-    if (m.emit[0] != 0.0 || m.emit[1] != 0.0 || m.emit[2] != 0.0) has_emit = true;
-  }
-  for (int i = 0; i < d->n_textures; ++i) {
-    if (d->textures[i].kind == PTX_TEX_CHECKER) has_checker = true;
-    else if (d->textures[i].kind != PTX_TEX_SOLID) return fail(PTX_ERR_ARG, "texture %d: unknown kind", i);
-  }
-  auto mat_ok = [&](int m) { return m >= 0 && m < d->n_materials; };
-
-  /* Leaf.elt_bbox of every element, build list = [triangles] @ [spheres] */
-  std::vector<Box> boxes((size_t)n);
-  auto vtx = [&](int i) { return v3(d->vertex_x[i], d->vertex_y[i], d->vertex_z[i]); };
-  for (int i = 0; i < n_tri; ++i) {
-    const int ia = d->tri_indices[3 * i], ib = d->tri_indices[3 * i + 1], ic = d->tri_indices[3 * i + 2];
-    if (ia < 0 || ib < 0 || ic < 0 || ia >= d->n_vertices || ib >= d->n_vertices || ic >= d->n_vertices) return fail(PTX_ERR_ARG, "triangle %d: vertex index out of range", i);
-    if (!mat_ok(d->tri_material[i])) return fail(PTX_ERR_ARG, "triangle %d: material out of range", i);
-    /* Triangle.bbox (triangle.ml:67-72): lo (lo a b) c */
-    Box ab, c;
-    ab.mn = ab.mx = vtx(ia);
-    Box bb;
-    bb.mn = bb.mx = vtx(ib);
-    c.mn = c.mx = vtx(ic);
-    boxes[(size_t)i] = box_union(box_union(ab, bb), c);
-  }
-  for (int i = 0; i < n_sph; ++i) {
-    if (!mat_ok(d->sphere_material[i])) return fail(PTX_ERR_ARG, "sphere %d: material out of range", i);
-    /* Sphere.bbox (sphere.ml:16-19): centre + (-r), centre + r */
-    const V3 c = v3(d->sphere_x[i], d->sphere_y[i], d->sphere_z[i]);
-    const double r = d->sphere_r[i];
-    Box b;
-    b.mn = v3(c.x + (-r), c.y + (-r), c.z + (-r));
-    b.mx = v3(c.x + r, c.y + r, c.z + r);
-    boxes[(size_t)(n_tri + i)] = b;
-  }
-  /* the emissive tree triangles in build-list order (ptx_scene_set_lighting makes the light table of them) */
-  s->n_emissive_tris = 0;
-  s->emissive_tris.clear();
-  for (int i = 0; i < n_tri; ++i) {
-    const ptx_material& m = d->materials[d->tri_material[i]];
-    if (m.emit[0] == 0.0 && m.emit[1] == 0.0 && m.emit[2] == 0.0) continue;
-    if (s->n_emissive_tris++ > PTX_MAX_LIGHT_TRIANGLES) continue;
-    for (int v = 0; v < 3; ++v) {
-      const V3 pnt = vtx(d->tri_indices[3 * i + v]);
-      s->emissive_tris.insert(s->emissive_tris.end(), {pnt.x, pnt.y, pnt.z});
-    }
-  }
+  std::string msg;
+  if (const int rc = scene_check_desc(d, &msg)) return fail(rc, "%s", msg.c_str());
+  const std::vector<Box> boxes = scene_boxes(d);
+  const int n = (int)boxes.size(), num_bins = scene_num_bins(d);
   const bool simd = d->leaf_kind == PTX_LEAF_SIMD;
   /* builder: desc->reserved 0 = auto (GPU for large scenes on a device, host otherwise), 1 = host, 2 = GPU */
   BvhResult tree;
@@ -1555,338 +1470,20 @@ static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
   }
   if (!built) tree = bvh_build(boxes, num_bins, d->length_cutoff, simd);
   s->built_on_gpu = built;
-  const int n_slots = (int)tree.slot_prim.size();
-  for (const PtNode& nd : tree.nodes)
-    if ((nd.b >> 30) == PT_NODE_LEAF_AXIS && (nd.b & 0x3fffffffu) > 0x7fffu) return fail(PTX_ERR_ARG, "a leaf holds more than 32767 slots (coincident centroids?)");
-  if (simd) {
-    for (const PtNode& nd : tree.nodes)
-      if ((nd.b >> 30) == PT_NODE_LEAF_AXIS && (nd.b & 0x3fffffffu) > 16u) return fail(PTX_ERR_ARG, "a Simd_leaf packet would exceed 16 lanes (coincident centroids?)");
-  }
-  const int n_floor = d->n_floor_triangles;
-  const int total_slots = n_slots + n_floor;
-  const bool any_tri = n_tri > 0 || n_floor > 0;
-  std::vector<double> sph((size_t)total_slots * 4, 0.0), tri, tri_uv;
-  if (any_tri) {
-    tri.assign((size_t)total_slots * 10, 0.0);
-    tri_uv.assign((size_t)total_slots * 6, 0.0);
-  }
-  std::vector<uint8_t> kind((size_t)total_slots, PT_SLOT_PAD);
-  std::vector<int32_t> slot_mat((size_t)total_slots, 0), slot_prim((size_t)total_slots, -1);
-  std::vector<uint8_t> slot_cat((size_t)total_slots, PT_CAT_NONE);
-  const double qnan = pt_nan();
-  for (int sl = 0; sl < n_slots; ++sl) {
-    const int e = tree.slot_prim[(size_t)sl];
-    slot_prim[(size_t)sl] = e;
-    if (e < 0) { /* Float.nan padding, main.ml:185 */
-      for (int k = 0; k < 4; ++k) sph[(size_t)sl * 4 + k] = qnan;
-      continue;
-    }
-    if (e < n_tri) {
-      kind[(size_t)sl] = PT_SLOT_TRIANGLE;
-      slot_mat[(size_t)sl] = d->tri_material[e];
-      for (int v = 0; v < 3; ++v) {
-        const int vi = d->tri_indices[3 * e + v];
-        tri[(size_t)sl * 10 + 3 * v] = d->vertex_x[vi];
-        tri[(size_t)sl * 10 + 3 * v + 1] = d->vertex_y[vi];
-        tri[(size_t)sl * 10 + 3 * v + 2] = d->vertex_z[vi];
-      }
-      std::memcpy(&tri_uv[(size_t)sl * 6], &d->tri_uv[6 * e], sizeof(double) * 6);
-    } else {
-      const int si = e - n_tri;
-      kind[(size_t)sl] = PT_SLOT_SPHERE;
-      slot_mat[(size_t)sl] = d->sphere_material[si];
-      sph[(size_t)sl * 4] = d->sphere_x[si];
-      sph[(size_t)sl * 4 + 1] = d->sphere_y[si];
-      sph[(size_t)sl * 4 + 2] = d->sphere_z[si];
-      sph[(size_t)sl * 4 + 3] = d->sphere_r[si];
-    }
-  }
-  for (int f = 0; f < n_floor; ++f) {
-    const int sl = n_slots + f;
-    if (!mat_ok(d->floor_material[f])) return fail(PTX_ERR_ARG, "floor triangle %d: material out of range", f);
-    kind[(size_t)sl] = PT_SLOT_TRIANGLE;
-    slot_mat[(size_t)sl] = d->floor_material[f];
-    slot_prim[(size_t)sl] = n + f;
-    std::memcpy(&tri[(size_t)sl * 10], &d->floor_vertices[9 * f], sizeof(double) * 9);
-    std::memcpy(&tri_uv[(size_t)sl * 6], &d->floor_uv[6 * f], sizeof(double) * 6);
-  }
-  /* PtSceneDev.tri_frame: small scenes only (the table of a large mesh would be one more gathered line per segment) */
-  std::vector<double> tri_frame;
-  if (any_tri && total_slots <= kTriFrameMaxSlots && env_int("PTX_TRI_FRAME", 1)) {
-    tri_frame.assign((size_t)total_slots * PT_TRI_FRAME_DOUBLES, 0.0);
-    for (int sl = 0; sl < total_slots; ++sl) {
-      if (kind[(size_t)sl] != PT_SLOT_TRIANGLE) continue;
-      const double* t = &tri[(size_t)sl * 10];
-      const V3 g = pt_tri_normal(v3(t[0], t[1], t[2]), v3(t[3], t[4], t[5]), v3(t[6], t[7], t[8]));
-      const Quat qf = pt_shader_rotation(g), qb = pt_shader_rotation(v3_neg(g));
-      double* o = &tri_frame[(size_t)sl * PT_TRI_FRAME_DOUBLES];
-      o[0] = g.x; o[1] = g.y; o[2] = g.z;
-      o[4] = qf.r; o[5] = qf.v.x; o[6] = qf.v.y; o[7] = qf.v.z;
-      o[8] = qb.r; o[9] = qb.v.x; o[10] = qb.v.y; o[11] = qb.v.z;
-    }
-  }
-  for (int sl = 0; sl < total_slots; ++sl) {
-    if (kind[(size_t)sl] == PT_SLOT_PAD) continue;
-    const ptx_material& m = d->materials[slot_mat[(size_t)sl]];
-    const bool checker = m.kind != PTX_MAT_DIELECTRIC && d->textures[m.texture].kind == PTX_TEX_CHECKER;
-    slot_cat[(size_t)sl] = m.kind == PTX_MAT_DIELECTRIC ? PT_CAT_DIELECTRIC : (m.kind == PTX_MAT_METAL ? PT_CAT_METAL : (checker ? PT_CAT_LAMBERT_CHECKER : PT_CAT_LAMBERT_SOLID));
-  }
-  std::vector<PtMaterial> mats((size_t)d->n_materials);
-  for (int i = 0; i < d->n_materials; ++i) {
-    PtMaterial& m = mats[(size_t)i];
-    std::memset(&m, 0, sizeof m);
-    m.kind = d->materials[i].kind;
-    m.texture = d->materials[i].kind == PTX_MAT_DIELECTRIC ? 0 : d->materials[i].texture;
-    m.index = d->materials[i].index;
-    std::memcpy(m.emit, d->materials[i].emit, sizeof m.emit);
-  }
-  std::vector<PtTexture> texs((size_t)std::max(d->n_textures, 1));
-  std::memset(texs.data(), 0, sizeof(PtTexture) * texs.size());
-  for (int i = 0; i < d->n_textures; ++i) {
-    PtTexture& t = texs[(size_t)i];
-    t.kind = d->textures[i].kind;
-    t.width = d->textures[i].width;
-    t.height = d->textures[i].height;
-    std::memcpy(t.even, d->textures[i].even, sizeof t.even);
-    std::memcpy(t.odd, d->textures[i].odd, sizeof t.odd);
-  }
-
   s->n_prims = n;
   s->tree_depth = tree.depth;
   s->tree_leaves = tree.leaves;
-  s->h_nodes = tree.nodes;
-  s->h_slot_prim = slot_prim;
-  if (s->device < 0) {
-    s->dev.n_slots = n_slots;
-    s->dev.n_nodes = (int)tree.nodes.size();
-    s->build_ms = wall_ms() - t0;
-    return 0;
-  }
   auto ha = std::make_shared<PtHostArrays>();
-  PtSceneDev& dv = ha->dev;
-  std::memset(&dv, 0, sizeof dv);
-  dv.n_nodes = (int)tree.nodes.size(); dv.depth = tree.depth;
-  dv.mode = simd ? PT_MODE_SIMD : PT_MODE_ARRAY;
-  dv.n_slots = n_slots;
-  dv.all_triangles = (n_tri > 0 && n_sph == 0) ? 1 : 0;
-  dv.n_floor = n_floor; dv.has_triangles = any_tri ? 1 : 0; dv.has_emit = has_emit ? 1 : 0; dv.has_checker = has_checker ? 1 : 0;
-  dv.cam_llx = d->camera.lower_left_x; dv.cam_lly = d->camera.lower_left_y; dv.cam_vx = d->camera.view_x; dv.cam_vy = d->camera.view_y;
-  dv.bg_kind = d->background.kind;
-  std::memcpy(dv.bg_horizon, d->background.horizon, sizeof dv.bg_horizon);
-  std::memcpy(dv.bg_zenith, d->background.zenith, sizeof dv.bg_zenith);
-  /* thread the tree per direction octant (shape_tree.ml:201,209: bit `axis` of the octant set = lhs first) */
-  {
-    const std::vector<PtNode>& nd = tree.nodes;
-    ha->skip32.assign(nd.size() * 8, 0xffffffffu);
-    std::vector<std::pair<uint32_t, uint32_t>> todo; /* (node, what follows its subtree) */
-    for (uint32_t o = 0; o < 8; ++o) {
-      todo.clear();
-      todo.emplace_back(0u, 0xffffffffu);
-      while (!todo.empty()) {
-        const auto [k, next] = todo.back();
-        todo.pop_back();
-        ha->skip32[(size_t)k * 8 + o] = next;
-        const uint32_t axis = nd[k].b >> 30;
-        if (axis == PT_NODE_LEAF_AXIS) continue;
-        const uint32_t lhs = nd[k].a, rhs = nd[k].b & 0x3fffffffu;
-        const bool lhs_first = (o >> axis) & 1u;
-        const uint32_t near_c = lhs_first ? lhs : rhs, far_c = lhs_first ? rhs : lhs;
-        todo.emplace_back(near_c, far_c);
-        todo.emplace_back(far_c, next);
-      }
-    }
-    ha->nodes32.resize(nd.size() * 8);
-    for (size_t k = 0; k < nd.size(); ++k) {
-      uint32_t* w = &ha->nodes32[k * 8];
-      for (int a = 0; a < 3; ++a) {
-        const float lo = (float)nd[k].mn[a], hi = (float)nd[k].mx[a];
-        std::memcpy(&w[a], &lo, 4);
-        std::memcpy(&w[3 + a], &hi, 4);
-      }
-      w[6] = nd[k].a;
-      const bool leaf = (nd[k].b >> 30) == PT_NODE_LEAF_AXIS;
-      w[7] = leaf ? ((nd[k].b & 0x7fffu) | ((nd[k].pad[0] & 0x7fffu) << 15) | (PT_NODE_LEAF_AXIS << 30)) : nd[k].b;
-    }
-    /* the per-octant image (PtSceneDev.nodes32o) for trees that will be walked from HBM / L2 (too large for the LDS image).
-     * PTX_OCT_IMAGE=0 keeps the shared image + skip table. */
-    if (env_int("PTX_OCT_IMAGE", 1) && nd.size() * PT_SWZ_NODE_BYTES >= 65535 && nd.size() * 8 < 0xffffffffull / 32u) {
-      bool ok = true;
-      for (size_t k = 0; k < nd.size() && ok; ++k) {
-        const bool leaf = (nd[k].b >> 30) == PT_NODE_LEAF_AXIS;
-        if (leaf) ok = nd[k].a < (1u << PT_OCT_LEAF_FIRST_BITS) && nd[k].pad[0] <= PT_OCT_LEAF_REAL_MAX;
-        else ok = nd[k].a == (uint32_t)k + 1u; /* pre-order: the lhs child follows its parent */
-      }
-      if (ok) {
-        ha->nodes32o.resize(nd.size() * 64);
-        for (uint32_t o = 0; o < 8; ++o)
-          for (size_t k = 0; k < nd.size(); ++k) {
-            uint32_t* w = &ha->nodes32o[((size_t)o * nd.size() + k) * 8];
-            const bool leaf = (nd[k].b >> 30) == PT_NODE_LEAF_AXIS;
-            /* the tagged record (kernels.hip, "second layout of the per-octant record"): near xyz, far xyz for this octant's direction signs (bit a set = component
-             * a >= 0: near = mn), what a hit leads to, what a miss leads to */
-            const uint32_t* b32 = &ha->nodes32[k * 8]; /* mn.xyz, mx.xyz as binary32 */
-            for (int a = 0; a < 3; ++a) {
-              const bool pos = (o >> a) & 1u;
-              w[a] = pos ? b32[a] : b32[3 + a];
-              w[3 + a] = pos ? b32[3 + a] : b32[a];
-            }
-            const uint32_t axis = nd[k].b >> 30;
-            /* links are record numbers in the whole image (this octant's base added), as the walk's `node` is */
-            const uint32_t obase = o * (uint32_t)nd.size();
-            w[6] = leaf ? (PT_OCT_LEAF_TAG | (nd[k].pad[0] << PT_OCT_LEAF_FIRST_BITS) | nd[k].a)
-                        : obase + (((o >> axis) & 1u) ? nd[k].a : (nd[k].b & 0x3fffffffu)); /* shape_tree.ml:209: lhs first where the component is >= 0 */
-            const uint32_t sk = ha->skip32[k * 8 + o];
-            w[7] = sk == 0xffffffffu ? PT_OCT_END : obase + sk;
-          }
-      }
-    }
-    /* the top of a tree that is too large for LDS as a whole (PtSceneDev.top_nodes): breadth-first prefix */
-    const size_t want_top = (size_t)std::max(0, std::min(1023, env_int("PTX_TOP_NODES", 512)));
-    if (want_top > 0 && nd.size() * PT_SWZ_NODE_BYTES >= 65535 && nd.size() < (size_t)PT_TOP_FLAG) {
-      std::vector<uint32_t> bfs; /* top slot -> node */
-      std::vector<int32_t> slot_of(nd.size(), -1);
-      bfs.push_back(0u);
-      for (size_t h = 0; h < bfs.size() && bfs.size() < want_top; ++h) {
-        const uint32_t k = bfs[h];
-        if ((nd[k].b >> 30) == PT_NODE_LEAF_AXIS) continue;
-        /* both children or neither: a top node's skip targets are siblings of its ancestors, so siblings travel together */
-        if (bfs.size() + 2 > want_top) break;
-        bfs.push_back(nd[k].a);
-        bfs.push_back(nd[k].b & 0x3fffffffu);
-      }
-      for (size_t t = 0; t < bfs.size(); ++t) slot_of[bfs[t]] = (int32_t)t;
-      auto enc = [&](uint32_t node) { return slot_of[node] >= 0 ? (PT_TOP_FLAG | (uint32_t)slot_of[node] * PT_TOP_NODE_BYTES) : node; };
-      ha->top_nodes.assign(bfs.size() * 16, 0u);
-      bool ok = true;
-      for (size_t t = 0; t < bfs.size(); ++t) {
-        const uint32_t k = bfs[t];
-        uint32_t* w = &ha->top_nodes[t * 16];
-        std::memcpy(w, &ha->nodes32[(size_t)k * 8], 6 * sizeof(uint32_t)); /* the same binary32 bounds */
-        const bool leaf = (nd[k].b >> 30) == PT_NODE_LEAF_AXIS;
-        w[6] = leaf ? nd[k].a : enc(nd[k].a);
-        w[7] = leaf ? ha->nodes32[(size_t)k * 8 + 7] : ((nd[k].b & 0xc0000000u) | enc(nd[k].b & 0x3fffffffu));
-        uint16_t* sk = (uint16_t*)(w + 8);
-        for (int o = 0; o < 8; ++o) {
-          const uint32_t nx = ha->skip32[(size_t)k * 8 + o];
-          if (nx == 0xffffffffu) sk[o] = 0xffffu;
-          else if (slot_of[nx] < 0) ok = false; /* cannot happen: see above */
-          else sk[o] = (uint16_t)((uint32_t)slot_of[nx] * PT_TOP_NODE_BYTES);
-        }
-        w[12] = k;
-      }
-      if (ok && bfs.size() >= 3) {
-        ha->skip32_top = ha->skip32;
-        for (uint32_t& v : ha->skip32_top)
-          if (v != 0xffffffffu) v = enc(v);
-      } else {
-        ha->top_nodes.clear();
-      }
-    }
-    if (nd.size() < 65535) { /* the LDS image's 16-bit copy */
-      ha->skip.resize(ha->skip32.size());
-      for (size_t i = 0; i < ha->skip32.size(); ++i) ha->skip[i] = (uint16_t)(ha->skip32[i] == 0xffffffffu ? 0xffffu : ha->skip32[i]);
-    }
-  }
-  { /* sort_axis: smallest-variance direction of the primitive centres, the 5 % largest primitives left out (a ground
-     * sphere of radius 1000 is not part of the "slab" the small ones lie in); oriented away from those large ones */
-    std::vector<std::pair<double, int>> by_size((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      const Box& b = boxes[(size_t)i];
-      by_size[(size_t)i] = {(b.mx.x - b.mn.x) + (b.mx.y - b.mn.y) + (b.mx.z - b.mn.z), i};
-    }
-    std::sort(by_size.begin(), by_size.end());
-    const int keep = std::max(1, n - n / 20);
-    double mean[3] = {0, 0, 0}, big[3] = {0, 0, 0};
-    auto centre = [&](int i, double c[3]) {
-      const Box& b = boxes[(size_t)i];
-      c[0] = 0.5 * (b.mn.x + b.mx.x); c[1] = 0.5 * (b.mn.y + b.mx.y); c[2] = 0.5 * (b.mn.z + b.mx.z);
-    };
-    for (int k = 0; k < keep; ++k) {
-      double c[3];
-      centre(by_size[(size_t)k].second, c);
-      for (int a = 0; a < 3; ++a) mean[a] += c[a] / keep;
-    }
-    double cov[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int k = 0; k < keep; ++k) {
-      double c[3];
-      centre(by_size[(size_t)k].second, c);
-      for (int a = 0; a < 3; ++a)
-        for (int b2 = 0; b2 < 3; ++b2) cov[a][b2] += (c[a] - mean[a]) * (c[b2] - mean[b2]);
-    }
-    for (int k = keep; k < n; ++k) {
-      double c[3];
-      centre(by_size[(size_t)k].second, c);
-      for (int a = 0; a < 3; ++a) big[a] += c[a] - mean[a];
-    }
-    /* cyclic Jacobi on the symmetric 3x3: columns of v become the eigenvectors */
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep)
-      for (int p2 = 0; p2 < 3; ++p2)
-        for (int q2 = p2 + 1; q2 < 3; ++q2) {
-          if (std::fabs(cov[p2][q2]) < 1e-300) continue;
-          const double th = 0.5 * std::atan2(2.0 * cov[p2][q2], cov[q2][q2] - cov[p2][p2]);
-          const double cs = std::cos(th), sn = std::sin(th);
-          for (int k = 0; k < 3; ++k) { /* rotate columns p2, q2 of cov and v */
-            const double a1 = cov[k][p2], a2 = cov[k][q2];
-            cov[k][p2] = cs * a1 - sn * a2; cov[k][q2] = sn * a1 + cs * a2;
-            const double v1 = v[k][p2], v2 = v[k][q2];
-            v[k][p2] = cs * v1 - sn * v2; v[k][q2] = sn * v1 + cs * v2;
-          }
-          for (int k = 0; k < 3; ++k) { /* and rows */
-            const double a1 = cov[p2][k], a2 = cov[q2][k];
-            cov[p2][k] = cs * a1 - sn * a2; cov[q2][k] = sn * a1 + cs * a2;
-          }
-        }
-    int best = 0;
-    for (int a = 1; a < 3; ++a)
-      if (cov[a][a] < cov[best][best]) best = a;
-    double ax[3] = {v[0][best], v[1][best], v[2][best]};
-    const double len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    int worst = 0;
-    for (int a = 1; a < 3; ++a)
-      if (cov[a][a] > cov[worst][worst]) worst = a;
-    dv.sort_by_elevation = (keep >= 16 && cov[best][best] < 0.02 * cov[worst][worst]) ? 1 : 0;
-    /* a floor tested before the tree (ganesha's checker floor): most bounce rays start on it, outside the tree's box */
-    dv.sort_by_root = (!dv.sort_by_elevation && dv.n_floor > 0 && !tree.nodes.empty()) ? 1 : 0;
-    if (const char* e = getenv("PTX_BIN_KEY")) { /* 0 octant, 1 elevation, 2 reaches-the-root-box */
-      dv.sort_by_elevation = atoi(e) == 1;
-      dv.sort_by_root = (atoi(e) == 2 && !tree.nodes.empty()) ? 1 : 0;
-    }
-    double root_mag = 0.0;
-    for (int a = 0; a < 3 && !tree.nodes.empty(); ++a) {
-      dv.root_mn[a] = (float)tree.nodes[0].mn[a];
-      dv.root_mx[a] = (float)tree.nodes[0].mx[a];
-      root_mag = std::fmax(root_mag, std::fmax(std::fabs(tree.nodes[0].mn[a]), std::fabs(tree.nodes[0].mx[a])));
-    }
-    /* rounded up; a NaN or a value beyond binary32 becomes +inf, which sends every ray of the scene to the binary64 test */
-    dv.root_mag = (root_mag < 3.0e38) ? (float)(root_mag * 1.0000002) : INFINITY;
-    dv.pad_f = 0.0f;
-    const double toward_big = ax[0] * big[0] + ax[1] * big[1] + ax[2] * big[2];
-    for (int a = 0; a < 3; ++a) dv.sort_axis[a] = (len > 0 && std::isfinite(len)) ? (toward_big > 0 ? -ax[a] : ax[a]) / len : (a == 1 ? 1.0 : 0.0);
-  }
-  ha->nodes = std::move(tree.nodes);
-  ha->sph = std::move(sph); ha->tri = std::move(tri); ha->tri_uv = std::move(tri_uv); ha->tri_frame = std::move(tri_frame);
-  ha->kind = std::move(kind); ha->cat = std::move(slot_cat);
-  ha->slot_mat = std::move(slot_mat); ha->slot_prim = std::move(slot_prim);
-  /* the per-slot shading records: material + its texture, flattened */
-  ha->shade.assign((size_t)total_slots, PtShadeRec{});
-  for (int sl = 0; sl < total_slots; ++sl) {
-    if (ha->kind[(size_t)sl] == PT_SLOT_PAD) continue;
-    const PtMaterial& m = mats[(size_t)ha->slot_mat[(size_t)sl]];
-    PtShadeRec& r = ha->shade[(size_t)sl];
-    r.kind = m.kind;
-    r.index = m.index;
-    std::memcpy(r.emit, m.emit, sizeof r.emit);
-    if (m.kind != PTX_MAT_DIELECTRIC) {
-      const PtTexture& t = texs[(size_t)m.texture];
-      r.tex_kind = t.kind; r.tex_w = t.width; r.tex_h = t.height;
-      std::memcpy(r.even, t.even, sizeof r.even);
-      std::memcpy(r.odd, t.odd, sizeof r.odd);
-    }
-  }
-  ha->mats = std::move(mats); ha->texs = std::move(texs);
+  if (const int rc = scene_set_tree(d, std::move(tree), ha.get(), &msg)) return fail(rc, "%s", msg.c_str());
   s->host = ha;
-  const int rc = scene_upload(s);
+  int rc = 0;
+  if (s->device < 0) {
+    s->dev.n_slots = ha->dev.n_slots;
+    s->dev.n_nodes = ha->dev.n_nodes;
+  } else {
+    scene_assemble(d, boxes, scene_options_from_env(), ha.get());
+    rc = scene_upload(s);
+  }
   s->build_ms = wall_ms() - t0;
   return rc;
 }
@@ -1987,34 +1584,14 @@ void ptx_scene_destroy(ptx_scene* s) {
   delete s;
 }
 
-/* The light table of mode 2: per emissive tree triangle {a, b, c, n, A, cum} with n = normalize(cross(b - a, c - a)) (pt_tri_normal: the
- * host's pt_hypot chain, like tri_frame) and A = 0.5 * sqrt(quadrance(cross(b - a, c - a))); contraction is off for this file. */
-static void light_table_build(ptx_scene* s) {
-  const int n = s->n_emissive_tris;
-  s->light_table.assign((size_t)n * PT_LIGHT_DOUBLES, 0.0);
-  double cum = 0.0;
-  for (int k = 0; k < n; ++k) {
-    const double* t = &s->emissive_tris[(size_t)k * 9];
-    const V3 a = v3(t[0], t[1], t[2]), b = v3(t[3], t[4], t[5]), c = v3(t[6], t[7], t[8]);
-    const V3 nrm = pt_tri_normal(a, b, c);
-    const double area = 0.5 * std::sqrt(v3_quadrance(v3_cross(v3_sub(b, a), v3_sub(c, a))));
-    cum = cum + area;
-    double* o = &s->light_table[(size_t)k * PT_LIGHT_DOUBLES];
-    std::memcpy(o, t, sizeof(double) * 9);
-    o[9] = nrm.x; o[10] = nrm.y; o[11] = nrm.z;
-    o[PT_LIGHT_AREA] = area;
-    o[PT_LIGHT_CUM] = cum;
-  }
-}
-
 int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");
   if (mode != PTX_LIGHTING_REFERENCE && mode != PTX_LIGHTING_PATH_ORDER && mode != PTX_LIGHTING_SAMPLED) return fail(PTX_ERR_ARG, "unknown lighting mode %d", mode);
   if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lighting mode cannot change while a render runs on the scene");
   if (mode == PTX_LIGHTING_SAMPLED) {
-    if (s->n_emissive_tris == 0) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
-    if (s->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return fail(PTX_ERR_ARG, "%d emissive tree triangles, more than PTX_MAX_LIGHT_TRIANGLES = %d (no light hierarchy)", s->n_emissive_tris, PTX_MAX_LIGHT_TRIANGLES);
-    if (s->light_table.empty()) light_table_build(s);
+    if (s->host->n_emissive_tris == 0) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
+    if (s->host->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return fail(PTX_ERR_ARG, "%d emissive tree triangles, more than PTX_MAX_LIGHT_TRIANGLES = %d (no light hierarchy)", s->host->n_emissive_tris, PTX_MAX_LIGHT_TRIANGLES);
+    if (s->light_table.empty()) s->light_table = light_table_build(*s->host);
     if (s->device >= 0 && !s->d_lights.p) {
       HIP_TRY(hipSetDevice(s->device));
       HIP_TRY(s->d_lights.ensure(s->light_table.size()));
@@ -2026,7 +1603,7 @@ int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
     /* the mode in effect: without emitters there is no emission to order, and mode 1 is mode 0 */
     s->dev.lighting = s->dev.has_emit ? mode : PTX_LIGHTING_REFERENCE;
     s->dev.lights = mode == PTX_LIGHTING_SAMPLED ? s->d_lights.p : nullptr;
-    s->dev.n_lights = mode == PTX_LIGHTING_SAMPLED ? s->n_emissive_tris : 0;
+    s->dev.n_lights = mode == PTX_LIGHTING_SAMPLED ? s->host->n_emissive_tris : 0;
     s->dev.light_area = mode == PTX_LIGHTING_SAMPLED ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
   }
   for (ptx_scene* r : s->replicas) {
@@ -2134,13 +1711,9 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
   s->host = src->host;
-  s->h_nodes = src->h_nodes;
-  s->h_slot_prim = src->h_slot_prim;
   s->n_prims = src->n_prims;
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;
-  s->n_emissive_tris = src->n_emissive_tris;
-  s->emissive_tris = src->emissive_tris;
   if (scene_upload(s) != 0 || (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
     ptx_scene_destroy(s);
     return nullptr;
@@ -2954,7 +2527,7 @@ int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const
       prim_out[i] = -1;
       t_out[i] = 0.0;
     } else {
-      prim_out[i] = s->h_slot_prim[(size_t)sl];
+      prim_out[i] = s->host->slot_prim[(size_t)sl];
     }
   }
   if (stats) {
@@ -2967,9 +2540,9 @@ int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const
 int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, int32_t node_capacity,
                        int32_t* prim_order_out, int32_t slot_capacity) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  const int n = (int)s->h_nodes.size();
+  const int n = (int)s->host->nodes.size();
   for (int i = 0; i < n && i < node_capacity; ++i) {
-    const PtNode& nd = s->h_nodes[(size_t)i];
+    const PtNode& nd = s->host->nodes[(size_t)i];
     if (bbox_out) {
       for (int k = 0; k < 3; ++k) {
         bbox_out[6 * i + k] = nd.mn[k];
@@ -2986,7 +2559,7 @@ int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, 
     }
   }
   if (prim_order_out)
-    for (int i = 0; i < s->dev.n_slots && i < slot_capacity; ++i) prim_order_out[i] = s->h_slot_prim[(size_t)i];
+    for (int i = 0; i < s->dev.n_slots && i < slot_capacity; ++i) prim_order_out[i] = s->host->slot_prim[(size_t)i];
   return n;
 }
 
@@ -3054,7 +2627,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
     return fail(PTX_ERR_ARG, "bad photon-mapping parameters");
   if ((long long)p->iterations * ((long long)p->width * p->height > p->photon_count ? (long long)p->width * p->height : p->photon_count) >= 2147483647LL)
     return fail(PTX_ERR_ARG, "sampler offset does not fit 32 bits");
-  if (s->h_nodes.empty()) return fail(PTX_ERR_STATE, "scene has no tree (Scene.bbox undefined)");
+  if (s->host->nodes.empty()) return fail(PTX_ERR_STATE, "scene has no tree (Scene.bbox undefined)");
   HIP_TRY(hipSetDevice(s->device));
   const double t_total0 = wall_ms();
   ptx_ppm_stats st;
@@ -3093,7 +2666,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   /* samplers: p_sampler dimension 2 + 2 max_bounces, e_sampler 2 + max_bounces (:426-431) */
   const std::vector<double> p_alpha = lds_alpha(2 + 2 * mb), e_alpha = lds_alpha(2 + mb);
   /* init_radius2 (:292-297) from Scene.bbox = the tree's bbox */
-  const PtNode& root = s->h_nodes[0];
+  const PtNode& root = s->host->nodes[0];
   const double ext_x = root.mx[0] - root.mn[0], ext_y = root.mx[1] - root.mn[1], ext_z = root.mx[2] - root.mn[2];
   const double a = (ext_x + ext_y + ext_z) / 3.0;
   const double b = (double)(W + H) / (double)2;

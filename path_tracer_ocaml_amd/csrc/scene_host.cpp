@@ -1,0 +1,509 @@
+/* scene_host.cpp -- see scene_host.h.  One function per array (or family of arrays) of PtHostArrays; scene_assemble at the end
+ * calls them in the order their inputs become available.  Contraction is off for this file like for the kernels: tri_frame and
+ * the light table must carry the bits the shade step itself would compute. */
+#include "scene_host.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+
+namespace {
+
+const uint32_t kNone = 0xffffffffu; /* skip32: nothing follows */
+
+int reject(std::string* msg, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  *msg = buf;
+  return PTX_ERR_ARG;
+}
+
+bool is_leaf(const PtNode& nd) { return (nd.b >> 30) == PT_NODE_LEAF_AXIS; }
+bool any_triangles(const ptx_scene_desc* d) { return d->n_triangles > 0 || d->n_floor_triangles > 0; }
+V3 vertex(const ptx_scene_desc* d, int i) { return v3(d->vertex_x[i], d->vertex_y[i], d->vertex_z[i]); }
+bool emits(const ptx_material& m) { return m.emit[0] != 0.0 || m.emit[1] != 0.0 || m.emit[2] != 0.0; }
+/* trees that will be walked from HBM / L2: too large for the LDS image */
+bool beyond_lds(const std::vector<PtNode>& nd) { return nd.size() * PT_SWZ_NODE_BYTES >= 65535; }
+
+/* the emissive tree triangles in build-list order */
+void emissive_list(const ptx_scene_desc* d, PtHostArrays* h) {
+  h->n_emissive_tris = 0;
+  h->emissive_tris.clear();
+  for (int i = 0; i < d->n_triangles; ++i) {
+    if (!emits(d->materials[d->tri_material[i]])) continue;
+    if (h->n_emissive_tris++ > PTX_MAX_LIGHT_TRIANGLES) continue;
+    for (int v = 0; v < 3; ++v) {
+      const V3 pnt = vertex(d, d->tri_indices[3 * i + v]);
+      h->emissive_tris.insert(h->emissive_tris.end(), {pnt.x, pnt.y, pnt.z});
+    }
+  }
+}
+
+/* sph / tri / tri_uv / kind / slot_mat in the order of h->slot_prim: leaf order, then the floor */
+void slot_arrays(const ptx_scene_desc* d, PtHostArrays* h) {
+  const int n_tri = d->n_triangles, n_slots = h->dev.n_slots, total_slots = (int)h->slot_prim.size();
+  h->sph.assign((size_t)total_slots * 4, 0.0);
+  if (any_triangles(d)) {
+    h->tri.assign((size_t)total_slots * 10, 0.0);
+    h->tri_uv.assign((size_t)total_slots * 6, 0.0);
+  }
+  h->kind.assign((size_t)total_slots, PT_SLOT_PAD);
+  h->slot_mat.assign((size_t)total_slots, 0);
+  const double qnan = pt_nan();
+  for (int sl = 0; sl < n_slots; ++sl) {
+    const int e = h->slot_prim[(size_t)sl];
+    if (e < 0) { /* Float.nan padding, main.ml:185 */
+      for (int k = 0; k < 4; ++k) h->sph[(size_t)sl * 4 + k] = qnan;
+      continue;
+    }
+    if (e < n_tri) {
+      h->kind[(size_t)sl] = PT_SLOT_TRIANGLE;
+      h->slot_mat[(size_t)sl] = d->tri_material[e];
+      for (int v = 0; v < 3; ++v) {
+        const int vi = d->tri_indices[3 * e + v];
+        h->tri[(size_t)sl * 10 + 3 * v] = d->vertex_x[vi];
+        h->tri[(size_t)sl * 10 + 3 * v + 1] = d->vertex_y[vi];
+        h->tri[(size_t)sl * 10 + 3 * v + 2] = d->vertex_z[vi];
+      }
+      std::memcpy(&h->tri_uv[(size_t)sl * 6], &d->tri_uv[6 * e], sizeof(double) * 6);
+    } else {
+      const int si = e - n_tri;
+      h->kind[(size_t)sl] = PT_SLOT_SPHERE;
+      h->slot_mat[(size_t)sl] = d->sphere_material[si];
+      h->sph[(size_t)sl * 4] = d->sphere_x[si];
+      h->sph[(size_t)sl * 4 + 1] = d->sphere_y[si];
+      h->sph[(size_t)sl * 4 + 2] = d->sphere_z[si];
+      h->sph[(size_t)sl * 4 + 3] = d->sphere_r[si];
+    }
+  }
+  for (int f = 0; f < d->n_floor_triangles; ++f) {
+    const int sl = n_slots + f;
+    h->kind[(size_t)sl] = PT_SLOT_TRIANGLE;
+    h->slot_mat[(size_t)sl] = d->floor_material[f];
+    std::memcpy(&h->tri[(size_t)sl * 10], &d->floor_vertices[9 * f], sizeof(double) * 9);
+    std::memcpy(&h->tri_uv[(size_t)sl * 6], &d->floor_uv[6 * f], sizeof(double) * 6);
+  }
+}
+
+/* PtSceneDev.tri_frame: small scenes only (the table of a large mesh would be one more gathered line per segment) */
+void tri_frame_table(const SceneOptions& opt, PtHostArrays* h) {
+  const int total_slots = (int)h->kind.size();
+  if (h->tri.empty() || total_slots > kTriFrameMaxSlots || !opt.tri_frame) return;
+  h->tri_frame.assign((size_t)total_slots * PT_TRI_FRAME_DOUBLES, 0.0);
+  for (int sl = 0; sl < total_slots; ++sl) {
+    if (h->kind[(size_t)sl] != PT_SLOT_TRIANGLE) continue;
+    const double* t = &h->tri[(size_t)sl * 10];
+    const V3 g = pt_tri_normal(v3(t[0], t[1], t[2]), v3(t[3], t[4], t[5]), v3(t[6], t[7], t[8]));
+    const Quat qf = pt_shader_rotation(g), qb = pt_shader_rotation(v3_neg(g));
+    double* o = &h->tri_frame[(size_t)sl * PT_TRI_FRAME_DOUBLES];
+    o[0] = g.x; o[1] = g.y; o[2] = g.z;
+    o[4] = qf.r; o[5] = qf.v.x; o[6] = qf.v.y; o[7] = qf.v.z;
+    o[8] = qb.r; o[9] = qb.v.x; o[10] = qb.v.y; o[11] = qb.v.z;
+  }
+}
+
+/* the shading category of every slot, the material and texture tables, and the per-slot shading records (material + its
+ * texture, flattened) */
+void shading_records(const ptx_scene_desc* d, PtHostArrays* h) {
+  const int total_slots = (int)h->kind.size();
+  h->cat.assign((size_t)total_slots, PT_CAT_NONE);
+  for (int sl = 0; sl < total_slots; ++sl) {
+    if (h->kind[(size_t)sl] == PT_SLOT_PAD) continue;
+    const ptx_material& m = d->materials[h->slot_mat[(size_t)sl]];
+    const bool checker = m.kind != PTX_MAT_DIELECTRIC && d->textures[m.texture].kind == PTX_TEX_CHECKER;
+    h->cat[(size_t)sl] = m.kind == PTX_MAT_DIELECTRIC ? PT_CAT_DIELECTRIC : (m.kind == PTX_MAT_METAL ? PT_CAT_METAL : (checker ? PT_CAT_LAMBERT_CHECKER : PT_CAT_LAMBERT_SOLID));
+  }
+  h->mats.resize((size_t)d->n_materials);
+  for (int i = 0; i < d->n_materials; ++i) {
+    PtMaterial& m = h->mats[(size_t)i];
+    std::memset(&m, 0, sizeof m);
+    m.kind = d->materials[i].kind;
+    m.texture = d->materials[i].kind == PTX_MAT_DIELECTRIC ? 0 : d->materials[i].texture;
+    m.index = d->materials[i].index;
+    std::memcpy(m.emit, d->materials[i].emit, sizeof m.emit);
+  }
+  h->texs.resize((size_t)std::max(d->n_textures, 1));
+  std::memset(h->texs.data(), 0, sizeof(PtTexture) * h->texs.size());
+  for (int i = 0; i < d->n_textures; ++i) {
+    PtTexture& t = h->texs[(size_t)i];
+    t.kind = d->textures[i].kind;
+    t.width = d->textures[i].width;
+    t.height = d->textures[i].height;
+    std::memcpy(t.even, d->textures[i].even, sizeof t.even);
+    std::memcpy(t.odd, d->textures[i].odd, sizeof t.odd);
+  }
+  h->shade.assign((size_t)total_slots, PtShadeRec{});
+  for (int sl = 0; sl < total_slots; ++sl) {
+    if (h->kind[(size_t)sl] == PT_SLOT_PAD) continue;
+    const PtMaterial& m = h->mats[(size_t)h->slot_mat[(size_t)sl]];
+    PtShadeRec& r = h->shade[(size_t)sl];
+    r.kind = m.kind;
+    r.index = m.index;
+    std::memcpy(r.emit, m.emit, sizeof r.emit);
+    if (m.kind != PTX_MAT_DIELECTRIC) {
+      const PtTexture& t = h->texs[(size_t)m.texture];
+      r.tex_kind = t.kind; r.tex_w = t.width; r.tex_h = t.height;
+      std::memcpy(r.even, t.even, sizeof r.even);
+      std::memcpy(r.odd, t.odd, sizeof r.odd);
+    }
+  }
+}
+
+/* the scalars of PtSceneDev that come straight from the descriptor (scene_set_tree has set n_nodes, n_slots, depth) */
+void dev_scalars(const ptx_scene_desc* d, PtSceneDev* dv) {
+  dv->mode = d->leaf_kind == PTX_LEAF_SIMD ? PT_MODE_SIMD : PT_MODE_ARRAY;
+  dv->all_triangles = (d->n_triangles > 0 && d->n_spheres == 0) ? 1 : 0;
+  dv->n_floor = d->n_floor_triangles;
+  dv->has_triangles = any_triangles(d) ? 1 : 0;
+  for (int i = 0; i < d->n_materials; ++i)
+    if (emits(d->materials[i])) dv->has_emit = 1;
+  for (int i = 0; i < d->n_textures; ++i)
+    if (d->textures[i].kind == PTX_TEX_CHECKER) dv->has_checker = 1;
+  dv->cam_llx = d->camera.lower_left_x; dv->cam_lly = d->camera.lower_left_y; dv->cam_vx = d->camera.view_x; dv->cam_vy = d->camera.view_y;
+  dv->bg_kind = d->background.kind;
+  std::memcpy(dv->bg_horizon, d->background.horizon, sizeof dv->bg_horizon);
+  std::memcpy(dv->bg_zenith, d->background.zenith, sizeof dv->bg_zenith);
+}
+
+/* skip32: the tree threaded per direction octant (shape_tree.ml:201,209: bit `axis` of the octant set = lhs first) */
+void thread_octants(PtHostArrays* h) {
+  const std::vector<PtNode>& nd = h->nodes;
+  h->skip32.assign(nd.size() * 8, kNone);
+  std::vector<std::pair<uint32_t, uint32_t>> todo; /* (node, what follows its subtree) */
+  for (uint32_t o = 0; o < 8; ++o) {
+    todo.clear();
+    todo.emplace_back(0u, kNone);
+    while (!todo.empty()) {
+      const auto [k, next] = todo.back();
+      todo.pop_back();
+      h->skip32[(size_t)k * 8 + o] = next;
+      const uint32_t axis = nd[k].b >> 30;
+      if (axis == PT_NODE_LEAF_AXIS) continue;
+      const uint32_t lhs = nd[k].a, rhs = nd[k].b & 0x3fffffffu;
+      const bool lhs_first = (o >> axis) & 1u;
+      const uint32_t near_c = lhs_first ? lhs : rhs, far_c = lhs_first ? rhs : lhs;
+      todo.emplace_back(near_c, far_c);
+      todo.emplace_back(far_c, next);
+    }
+  }
+}
+
+/* nodes32: mn.xyz, mx.xyz rounded to binary32, a, b (leaf b: padded count | real count << 15 | tag) */
+void binary32_image(PtHostArrays* h) {
+  const std::vector<PtNode>& nd = h->nodes;
+  h->nodes32.resize(nd.size() * 8);
+  for (size_t k = 0; k < nd.size(); ++k) {
+    uint32_t* w = &h->nodes32[k * 8];
+    for (int a = 0; a < 3; ++a) {
+      const float lo = (float)nd[k].mn[a], hi = (float)nd[k].mx[a];
+      std::memcpy(&w[a], &lo, 4);
+      std::memcpy(&w[3 + a], &hi, 4);
+    }
+    w[6] = nd[k].a;
+    w[7] = is_leaf(nd[k]) ? ((nd[k].b & 0x7fffu) | ((nd[k].pad[0] & 0x7fffu) << 15) | (PT_NODE_LEAF_AXIS << 30)) : nd[k].b;
+  }
+}
+
+/* nodes32o: the per-octant tagged image for trees that will be walked from HBM / L2, from nodes32 and skip32 */
+void octant_image(const SceneOptions& opt, PtHostArrays* h) {
+  const std::vector<PtNode>& nd = h->nodes;
+  if (!opt.oct_image || !beyond_lds(nd) || nd.size() * 8 >= 0xffffffffull / 32u) return;
+  for (size_t k = 0; k < nd.size(); ++k) {
+    const bool ok = is_leaf(nd[k]) ? nd[k].a < (1u << PT_OCT_LEAF_FIRST_BITS) && nd[k].pad[0] <= PT_OCT_LEAF_REAL_MAX
+                                   : nd[k].a == (uint32_t)k + 1u; /* pre-order: the lhs child follows its parent */
+    if (!ok) return;
+  }
+  h->nodes32o.resize(nd.size() * 64);
+  for (uint32_t o = 0; o < 8; ++o)
+    for (size_t k = 0; k < nd.size(); ++k) {
+      uint32_t* w = &h->nodes32o[((size_t)o * nd.size() + k) * 8];
+      /* the tagged record (pt_scene.h, PT_OCT_*): near xyz, far xyz for this octant's direction signs (bit a set = component
+       * a >= 0: near = mn), what a hit leads to, what a miss leads to */
+      const uint32_t* b32 = &h->nodes32[k * 8]; /* mn.xyz, mx.xyz as binary32 */
+      for (int a = 0; a < 3; ++a) {
+        const bool pos = (o >> a) & 1u;
+        w[a] = pos ? b32[a] : b32[3 + a];
+        w[3 + a] = pos ? b32[3 + a] : b32[a];
+      }
+      const uint32_t axis = nd[k].b >> 30;
+      /* links are record numbers in the whole image (this octant's base added), as the walk's `node` is */
+      const uint32_t obase = o * (uint32_t)nd.size();
+      w[6] = is_leaf(nd[k]) ? (PT_OCT_LEAF_TAG | (nd[k].pad[0] << PT_OCT_LEAF_FIRST_BITS) | nd[k].a)
+                            : obase + (((o >> axis) & 1u) ? nd[k].a : (nd[k].b & 0x3fffffffu)); /* shape_tree.ml:209: lhs first where the component is >= 0 */
+      const uint32_t sk = h->skip32[k * 8 + o];
+      w[7] = sk == kNone ? PT_OCT_END : obase + sk;
+    }
+}
+
+/* top_nodes / skip32_top: the top of a tree that is too large for LDS as a whole, a breadth-first prefix */
+void top_image(const SceneOptions& opt, PtHostArrays* h) {
+  const std::vector<PtNode>& nd = h->nodes;
+  const size_t want_top = (size_t)std::max(0, std::min(1023, opt.top_nodes));
+  if (want_top == 0 || !beyond_lds(nd) || nd.size() >= (size_t)PT_TOP_FLAG) return;
+  std::vector<uint32_t> bfs; /* top slot -> node */
+  std::vector<int32_t> slot_of(nd.size(), -1);
+  bfs.push_back(0u);
+  for (size_t t = 0; t < bfs.size() && bfs.size() < want_top; ++t) {
+    const uint32_t k = bfs[t];
+    if (is_leaf(nd[k])) continue;
+    /* both children or neither: a top node's skip targets are siblings of its ancestors, so siblings travel together */
+    if (bfs.size() + 2 > want_top) break;
+    bfs.push_back(nd[k].a);
+    bfs.push_back(nd[k].b & 0x3fffffffu);
+  }
+  for (size_t t = 0; t < bfs.size(); ++t) slot_of[bfs[t]] = (int32_t)t;
+  auto enc = [&](uint32_t node) { return slot_of[node] >= 0 ? (PT_TOP_FLAG | (uint32_t)slot_of[node] * PT_TOP_NODE_BYTES) : node; };
+  h->top_nodes.assign(bfs.size() * 16, 0u);
+  bool ok = true;
+  for (size_t t = 0; t < bfs.size(); ++t) {
+    const uint32_t k = bfs[t];
+    uint32_t* w = &h->top_nodes[t * 16];
+    std::memcpy(w, &h->nodes32[(size_t)k * 8], 6 * sizeof(uint32_t)); /* the same binary32 bounds */
+    w[6] = is_leaf(nd[k]) ? nd[k].a : enc(nd[k].a);
+    w[7] = is_leaf(nd[k]) ? h->nodes32[(size_t)k * 8 + 7] : ((nd[k].b & 0xc0000000u) | enc(nd[k].b & 0x3fffffffu));
+    for (int o = 0; o < 8; ++o) { /* words 8 .. 11: eight 16-bit skip links, byte offsets into this image */
+      const uint32_t nx = h->skip32[(size_t)k * 8 + o];
+      uint16_t sk = 0xffffu;
+      if (nx != kNone && slot_of[nx] < 0) ok = false; /* cannot happen: see above */
+      else if (nx != kNone) sk = (uint16_t)((uint32_t)slot_of[nx] * PT_TOP_NODE_BYTES);
+      std::memcpy((unsigned char*)(w + 8) + 2 * o, &sk, 2);
+    }
+    w[12] = k;
+  }
+  if (ok && bfs.size() >= 3) {
+    h->skip32_top = h->skip32;
+    for (uint32_t& v : h->skip32_top)
+      if (v != kNone) v = enc(v);
+  } else {
+    h->top_nodes.clear();
+  }
+}
+
+/* skip: the LDS image's 16-bit copy of skip32 */
+void skip16_copy(PtHostArrays* h) {
+  if (h->nodes.size() >= 65535) return;
+  h->skip.resize(h->skip32.size());
+  for (size_t i = 0; i < h->skip32.size(); ++i) h->skip[i] = (uint16_t)(h->skip32[i] == kNone ? 0xffffu : h->skip32[i]);
+}
+
+/* cyclic Jacobi on the symmetric 3x3 `cov`: it becomes (nearly) diagonal, the columns of v the eigenvectors */
+void jacobi3(double cov[3][3], double v[3][3]) {
+  for (int sweep = 0; sweep < 12; ++sweep)
+    for (int p2 = 0; p2 < 3; ++p2)
+      for (int q2 = p2 + 1; q2 < 3; ++q2) {
+        if (std::fabs(cov[p2][q2]) < 1e-300) continue;
+        const double th = 0.5 * std::atan2(2.0 * cov[p2][q2], cov[q2][q2] - cov[p2][p2]);
+        const double cs = std::cos(th), sn = std::sin(th);
+        for (int k = 0; k < 3; ++k) { /* rotate columns p2, q2 of cov and v */
+          const double a1 = cov[k][p2], a2 = cov[k][q2];
+          cov[k][p2] = cs * a1 - sn * a2; cov[k][q2] = sn * a1 + cs * a2;
+          const double v1 = v[k][p2], v2 = v[k][q2];
+          v[k][p2] = cs * v1 - sn * v2; v[k][q2] = sn * v1 + cs * v2;
+        }
+        for (int k = 0; k < 3; ++k) { /* and rows */
+          const double a1 = cov[p2][k], a2 = cov[q2][k];
+          cov[p2][k] = cs * a1 - sn * a2; cov[q2][k] = sn * a1 + cs * a2;
+        }
+      }
+}
+
+/* The bin key of the shade step (sort_axis / sort_by_* / root_*).  sort_axis: smallest-variance direction of the primitive
+ * centres, the 5 % largest primitives left out (a ground sphere of radius 1000 is not part of the "slab" the small ones lie
+ * in); oriented away from those large ones */
+void bin_key(const std::vector<Box>& boxes, const SceneOptions& opt, PtHostArrays* h) {
+  PtSceneDev& dv = h->dev;
+  const std::vector<PtNode>& nodes = h->nodes;
+  const int n = (int)boxes.size();
+  std::vector<std::pair<double, int>> by_size((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const Box& b = boxes[(size_t)i];
+    by_size[(size_t)i] = {(b.mx.x - b.mn.x) + (b.mx.y - b.mn.y) + (b.mx.z - b.mn.z), i};
+  }
+  std::sort(by_size.begin(), by_size.end());
+  const int keep = std::max(1, n - n / 20);
+  double mean[3] = {0, 0, 0}, big[3] = {0, 0, 0};
+  auto centre = [&](int i, double c[3]) {
+    const Box& b = boxes[(size_t)i];
+    c[0] = 0.5 * (b.mn.x + b.mx.x); c[1] = 0.5 * (b.mn.y + b.mx.y); c[2] = 0.5 * (b.mn.z + b.mx.z);
+  };
+  for (int k = 0; k < keep; ++k) {
+    double c[3];
+    centre(by_size[(size_t)k].second, c);
+    for (int a = 0; a < 3; ++a) mean[a] += c[a] / keep;
+  }
+  double cov[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  for (int k = 0; k < keep; ++k) {
+    double c[3];
+    centre(by_size[(size_t)k].second, c);
+    for (int a = 0; a < 3; ++a)
+      for (int b2 = 0; b2 < 3; ++b2) cov[a][b2] += (c[a] - mean[a]) * (c[b2] - mean[b2]);
+  }
+  for (int k = keep; k < n; ++k) {
+    double c[3];
+    centre(by_size[(size_t)k].second, c);
+    for (int a = 0; a < 3; ++a) big[a] += c[a] - mean[a];
+  }
+  double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  jacobi3(cov, v);
+  int best = 0;
+  for (int a = 1; a < 3; ++a)
+    if (cov[a][a] < cov[best][best]) best = a;
+  double ax[3] = {v[0][best], v[1][best], v[2][best]};
+  const double len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+  int worst = 0;
+  for (int a = 1; a < 3; ++a)
+    if (cov[a][a] > cov[worst][worst]) worst = a;
+  dv.sort_by_elevation = (keep >= 16 && cov[best][best] < 0.02 * cov[worst][worst]) ? 1 : 0;
+  /* a floor tested before the tree (ganesha's checker floor): most bounce rays start on it, outside the tree's box */
+  dv.sort_by_root = (!dv.sort_by_elevation && dv.n_floor > 0 && !nodes.empty()) ? 1 : 0;
+  if (opt.bin_key >= 0) {
+    dv.sort_by_elevation = opt.bin_key == 1;
+    dv.sort_by_root = (opt.bin_key == 2 && !nodes.empty()) ? 1 : 0;
+  }
+  double root_mag = 0.0;
+  for (int a = 0; a < 3 && !nodes.empty(); ++a) {
+    dv.root_mn[a] = (float)nodes[0].mn[a];
+    dv.root_mx[a] = (float)nodes[0].mx[a];
+    root_mag = std::fmax(root_mag, std::fmax(std::fabs(nodes[0].mn[a]), std::fabs(nodes[0].mx[a])));
+  }
+  /* rounded up; a NaN or a value beyond binary32 becomes +inf, which sends every ray of the scene to the binary64 test */
+  dv.root_mag = (root_mag < 3.0e38) ? (float)(root_mag * 1.0000002) : INFINITY;
+  dv.pad_f = 0.0f;
+  const double toward_big = ax[0] * big[0] + ax[1] * big[1] + ax[2] * big[2];
+  for (int a = 0; a < 3; ++a) dv.sort_axis[a] = (len > 0 && std::isfinite(len)) ? (toward_big > 0 ? -ax[a] : ax[a]) / len : (a == 1 ? 1.0 : 0.0);
+}
+
+}  // namespace
+
+SceneOptions scene_options_from_env() {
+  auto env_int = [](const char* name, int dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+  };
+  SceneOptions o;
+  o.tri_frame = env_int("PTX_TRI_FRAME", 1);
+  o.oct_image = env_int("PTX_OCT_IMAGE", 1);
+  o.top_nodes = std::max(0, std::min(1023, env_int("PTX_TOP_NODES", 512)));
+  if (std::getenv("PTX_BIN_KEY")) { /* any other value: by octant */
+    const int k = env_int("PTX_BIN_KEY", 0);
+    o.bin_key = (k == 1 || k == 2) ? k : 0;
+  }
+  return o;
+}
+
+int scene_check_desc(const ptx_scene_desc* d, std::string* msg) {
+  const int n_tri = d->n_triangles, n_sph = d->n_spheres;
+  if (n_tri < 0 || n_sph < 0 || d->n_floor_triangles < 0) return reject(msg, "negative primitive count");
+  if (n_tri + n_sph == 0) return reject(msg, "Shape_tree.create: expected non-empty list of shapes");
+  if (d->leaf_kind != PTX_LEAF_SIMD && d->leaf_kind != PTX_LEAF_ARRAY) return reject(msg, "unknown leaf_kind %d", d->leaf_kind);
+  if (d->leaf_kind == PTX_LEAF_SIMD && (n_tri > 0 || d->n_floor_triangles > 0)) return reject(msg, "Simd_leaf holds spheres only");
+  if (d->leaf_kind == PTX_LEAF_SIMD && d->length_cutoff > 16) return reject(msg, "Simd_leaf length_cutoff must be <= leaf_size () = 16");
+  if (d->length_cutoff < 1) return reject(msg, "length_cutoff must be >= 1");
+  if (scene_num_bins(d) < 4) return reject(msg, "num_bins must be >= 4 (shape_tree.ml:253)");
+  if (d->n_materials <= 0 || !d->materials) return reject(msg, "no materials");
+  if (n_sph > 0 && !(d->sphere_x && d->sphere_y && d->sphere_z && d->sphere_r && d->sphere_material)) return reject(msg, "sphere arrays missing");
+  if (n_tri > 0 && !(d->vertex_x && d->vertex_y && d->vertex_z && d->tri_indices && d->tri_uv && d->tri_material)) return reject(msg, "triangle arrays missing");
+  if (d->n_floor_triangles > 0 && !(d->floor_vertices && d->floor_uv && d->floor_material)) return reject(msg, "floor arrays missing");
+  for (int i = 0; i < d->n_materials; ++i) {
+    const ptx_material& m = d->materials[i];
+    if (m.kind < 0 || m.kind > 2) return reject(msg, "material %d: unknown kind %d", i, m.kind);
+    if (m.kind != PTX_MAT_DIELECTRIC && (m.texture < 0 || m.texture >= d->n_textures)) return reject(msg, "material %d: texture %d out of range", i, m.texture);
+  }
+  if (d->n_textures > 0 && !d->textures) return reject(msg, "texture array missing");
+  for (int i = 0; i < d->n_textures; ++i)
+    if (d->textures[i].kind != PTX_TEX_CHECKER && d->textures[i].kind != PTX_TEX_SOLID) return reject(msg, "texture %d: unknown kind", i);
+  auto mat_ok = [&](int m) { return m >= 0 && m < d->n_materials; };
+  for (int i = 0; i < n_tri; ++i) {
+    const int ia = d->tri_indices[3 * i], ib = d->tri_indices[3 * i + 1], ic = d->tri_indices[3 * i + 2];
+    if (ia < 0 || ib < 0 || ic < 0 || ia >= d->n_vertices || ib >= d->n_vertices || ic >= d->n_vertices) return reject(msg, "triangle %d: vertex index out of range", i);
+    if (!mat_ok(d->tri_material[i])) return reject(msg, "triangle %d: material out of range", i);
+  }
+  for (int i = 0; i < n_sph; ++i)
+    if (!mat_ok(d->sphere_material[i])) return reject(msg, "sphere %d: material out of range", i);
+  for (int f = 0; f < d->n_floor_triangles; ++f)
+    if (!mat_ok(d->floor_material[f])) return reject(msg, "floor triangle %d: material out of range", f);
+  return 0;
+}
+
+std::vector<Box> scene_boxes(const ptx_scene_desc* d) {
+  const int n_tri = d->n_triangles, n_sph = d->n_spheres;
+  std::vector<Box> boxes((size_t)(n_tri + n_sph));
+  for (int i = 0; i < n_tri; ++i) {
+    /* Triangle.bbox (triangle.ml:67-72): lo (lo a b) c */
+    Box ab, c;
+    ab.mn = ab.mx = vertex(d, d->tri_indices[3 * i]);
+    Box bb;
+    bb.mn = bb.mx = vertex(d, d->tri_indices[3 * i + 1]);
+    c.mn = c.mx = vertex(d, d->tri_indices[3 * i + 2]);
+    boxes[(size_t)i] = box_union(box_union(ab, bb), c);
+  }
+  for (int i = 0; i < n_sph; ++i) {
+    /* Sphere.bbox (sphere.ml:16-19): centre + (-r), centre + r */
+    const V3 c = v3(d->sphere_x[i], d->sphere_y[i], d->sphere_z[i]);
+    const double r = d->sphere_r[i];
+    Box b;
+    b.mn = v3(c.x + (-r), c.y + (-r), c.z + (-r));
+    b.mx = v3(c.x + r, c.y + r, c.z + r);
+    boxes[(size_t)(n_tri + i)] = b;
+  }
+  return boxes;
+}
+
+int scene_set_tree(const ptx_scene_desc* d, BvhResult&& tree, PtHostArrays* h, std::string* msg) {
+  for (const PtNode& nd : tree.nodes)
+    if (is_leaf(nd) && (nd.b & 0x3fffffffu) > 0x7fffu) return reject(msg, "a leaf holds more than 32767 slots (coincident centroids?)");
+  if (d->leaf_kind == PTX_LEAF_SIMD) {
+    for (const PtNode& nd : tree.nodes)
+      if (is_leaf(nd) && (nd.b & 0x3fffffffu) > 16u) return reject(msg, "a Simd_leaf packet would exceed 16 lanes (coincident centroids?)");
+  }
+  h->nodes = std::move(tree.nodes);
+  h->slot_prim = std::move(tree.slot_prim);
+  std::memset(&h->dev, 0, sizeof h->dev);
+  h->dev.n_nodes = (int)h->nodes.size();
+  h->dev.n_slots = (int)h->slot_prim.size();
+  h->dev.depth = tree.depth;
+  for (int f = 0; f < d->n_floor_triangles; ++f) h->slot_prim.push_back(d->n_triangles + d->n_spheres + f);
+  emissive_list(d, h);
+  return 0;
+}
+
+void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, const SceneOptions& opt, PtHostArrays* h) {
+  slot_arrays(d, h);
+  tri_frame_table(opt, h);
+  shading_records(d, h);
+  dev_scalars(d, &h->dev);
+  thread_octants(h);
+  binary32_image(h);
+  octant_image(opt, h);
+  top_image(opt, h);
+  skip16_copy(h);
+  bin_key(boxes, opt, h);
+}
+
+/* n = normalize(cross(b - a, c - a)) (pt_tri_normal: the host's pt_hypot chain, like tri_frame) and
+ * A = 0.5 * sqrt(quadrance(cross(b - a, c - a))); cum = the running sum of the areas */
+std::vector<double> light_table_build(const PtHostArrays& h) {
+  const int n = h.n_emissive_tris;
+  std::vector<double> table((size_t)n * PT_LIGHT_DOUBLES, 0.0);
+  double cum = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double* t = &h.emissive_tris[(size_t)k * 9];
+    const V3 a = v3(t[0], t[1], t[2]), b = v3(t[3], t[4], t[5]), c = v3(t[6], t[7], t[8]);
+    const V3 nrm = pt_tri_normal(a, b, c);
+    const double area = 0.5 * std::sqrt(v3_quadrance(v3_cross(v3_sub(b, a), v3_sub(c, a))));
+    cum = cum + area;
+    double* o = &table[(size_t)k * PT_LIGHT_DOUBLES];
+    std::memcpy(o, t, sizeof(double) * 9);
+    o[9] = nrm.x; o[10] = nrm.y; o[11] = nrm.z;
+    o[PT_LIGHT_AREA] = area;
+    o[PT_LIGHT_CUM] = cum;
+  }
+  return table;
+}

@@ -1,0 +1,72 @@
+/* scene_host.h -- from a caller's ptx_scene_desc to the arrays the kernels walk (PtHostArrays), in plain C++: no HIP call, so the
+ * sanitizer build (host/Makefile `asan`, tests/c/asan_host_driver.cpp) compiles and runs exactly what the library ships.
+ * ptx_api.inc drives it: scene_check_desc, scene_boxes, a tree (bvh_build or the GPU builder), scene_set_tree, and for a scene
+ * with a device scene_assemble, then the upload. */
+#ifndef SCENE_HOST_H
+#define SCENE_HOST_H
+
+#include <string>
+#include <vector>
+
+#include "../../include/ptx.h"
+#include "bvh_build.h"
+
+/* the codes the C ABI returns (include/ptx.h); everything this unit rejects is an argument error */
+#define PTX_ERR_ARG (-1)
+#define PTX_ERR_HIP (-2)
+#define PTX_ERR_STATE (-3)
+
+/* Everything ptx_scene_create uploads, kept on the host (<= 20 MB even for 150 k triangles) so that a REPLICA of the
+ * scene on another device is one more upload, not another BVH build (ptx_scene_replicate, ptx_render n_gpus > 1).
+ * A host-only scene (device -1) holds nodes, slot_prim, the emissive list and dev.n_nodes / n_slots / depth only. */
+struct PtHostArrays {
+  std::vector<PtNode> nodes;
+  std::vector<double> sph, tri, tri_uv, tri_frame;
+  std::vector<uint8_t> kind, cat;
+  std::vector<int32_t> slot_mat, slot_prim;
+  std::vector<PtMaterial> mats;
+  std::vector<PtTexture> texs;
+  std::vector<PtShadeRec> shade;
+  std::vector<uint16_t> skip; /* node_skip: n_nodes x 8, empty for trees of >= 65535 nodes */
+  std::vector<uint32_t> skip32; /* node_skip32: n_nodes x 8 */
+  std::vector<uint32_t> nodes32; /* 8 words per node: the binary32 filter image for the walk from HBM / L2 */
+  std::vector<uint32_t> nodes32o; /* PtSceneDev.nodes32o: 8 octants x 8 words per node; empty = not built */
+  std::vector<uint32_t> top_nodes, skip32_top; /* PtSceneDev.top_nodes (16 words per top node) / node_skip32_top; empty = none */
+  /* the emissive tree triangles of the build list, in its order: 9 doubles each, kept up to one past PTX_MAX_LIGHT_TRIANGLES;
+   * n_emissive_tris counts them all (ptx_scene_set_lighting makes the light table of them) */
+  std::vector<double> emissive_tris;
+  int n_emissive_tris = 0;
+  PtSceneDev dev{}; /* the scalar fields; device pointers are filled per upload */
+};
+
+/* the tuning switches of scene construction (documented in DESIGN.md), read once per ptx_scene_create */
+struct SceneOptions {
+  int tri_frame = 1;   /* PTX_TRI_FRAME: 0 = no tri_frame table */
+  int oct_image = 1;   /* PTX_OCT_IMAGE: 0 = keep the shared image + skip table */
+  int top_nodes = 512; /* PTX_TOP_NODES: size of the breadth-first top image, clamped to 0 .. 1023 */
+  int bin_key = -1;    /* PTX_BIN_KEY: -1 = by scene, 0 octant, 1 elevation, 2 reaches-the-root-box */
+};
+SceneOptions scene_options_from_env();
+
+/* ?num_bins of Shape_tree.create: 32 unless the descriptor says otherwise */
+inline int scene_num_bins(const ptx_scene_desc* d) { return d->num_bins > 0 ? d->num_bins : 32; }
+
+/* Every check of an untrusted descriptor: counts, NULL arrays, material and texture kinds, then per element its vertex and
+ * material indices.  0, or PTX_ERR_ARG with *msg set; nothing below is called with a descriptor this rejected. */
+int scene_check_desc(const ptx_scene_desc* d, std::string* msg);
+
+/* Leaf.elt_bbox of every element, build list = [triangles] @ [spheres] */
+std::vector<Box> scene_boxes(const ptx_scene_desc* d);
+
+/* Takes the tree: rejects leaves the kernels cannot hold (0, or PTX_ERR_ARG with *msg set), then fills h->nodes, h->slot_prim (leaf
+ * order, then the floor triangles), the emissive list and dev.n_nodes / n_slots / depth.  Host-only scenes stop here. */
+int scene_set_tree(const ptx_scene_desc* d, BvhResult&& tree, PtHostArrays* h, std::string* msg);
+
+/* Everything else a device needs, from h->nodes and h->slot_prim: slot arrays, tri_frame, shading records, the threading and the
+ * node images, the bin key, the remaining scalars of h->dev.  boxes = scene_boxes(d). */
+void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, const SceneOptions& opt, PtHostArrays* h);
+
+/* The light table of PTX_LIGHTING_SAMPLED: per emissive tree triangle PT_LIGHT_DOUBLES doubles {a, b, c, n, A, cum} */
+std::vector<double> light_table_build(const PtHostArrays& h);
+
+#endif /* SCENE_HOST_H */

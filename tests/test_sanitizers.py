@@ -125,6 +125,54 @@ def test_scene_builders_and_host_bvh(built, scene):
     assert "nodes" in out and "depth" in out
 
 
+HOSTILE = """n_triangles -1: negative primitive count
+n_spheres -1: negative primitive count
+n_floor_triangles -1: negative primitive count
+no primitives: Shape_tree.create: expected non-empty list of shapes
+materials NULL: no materials
+n_materials 0: no materials
+textures NULL: texture array missing
+sphere_x NULL: sphere arrays missing
+sphere_y NULL: sphere arrays missing
+sphere_z NULL: sphere arrays missing
+sphere_r NULL: sphere arrays missing
+sphere_material NULL: sphere arrays missing
+vertex_x NULL: triangle arrays missing
+vertex_y NULL: triangle arrays missing
+vertex_z NULL: triangle arrays missing
+tri_indices NULL: triangle arrays missing
+tri_uv NULL: triangle arrays missing
+tri_material NULL: triangle arrays missing
+floor_vertices NULL: floor arrays missing
+floor_uv NULL: floor arrays missing
+floor_material NULL: floor arrays missing
+vertex index n_vertices: triangle 17: vertex index out of range
+vertex index -1: triangle 1: vertex index out of range
+triangle material n_materials: triangle 17: material out of range
+triangle material -1: triangle 0: material out of range
+sphere material n_materials: sphere 2: material out of range
+sphere material -1: sphere 0: material out of range
+floor material n_materials: floor triangle 1: material out of range
+floor material -1: floor triangle 0: material out of range
+texture index n_textures: material 0: texture 8 out of range
+texture index -1: material 0: texture -1 out of range
+material kind 3: material 0: unknown kind 3
+material kind -1: material 0: unknown kind -1
+texture kind 7: texture 7: unknown kind
+leaf_kind 5: unknown leaf_kind 5
+Simd leaves over triangles: Simd_leaf holds spheres only
+Simd length_cutoff 0: length_cutoff must be >= 1
+Simd length_cutoff 17: Simd_leaf length_cutoff must be <= leaf_size () = 16
+num_bins 3: num_bins must be >= 4 (shape_tree.ml:253)"""
+
+
+def test_scene_construction_on_hostile_descriptors(built):
+    """The descriptor check and the assembly of csrc/scene_host.cpp (what ptx_scene_create runs) on broken descriptors derived
+    from valid ones: every one comes back rejected, with the message the library reports."""
+    out = run_clean([os.path.join(built, "host_asan_driver"), "hostile"])
+    assert out.splitlines() == ["rejected " + line for line in HOSTILE.splitlines()]
+
+
 def test_png_writer(built, tmp_path):
     p = str(tmp_path / "a.png")
     run_clean([os.path.join(built, "host_asan_driver"), "png", p])
