@@ -223,6 +223,8 @@ typedef struct ptx_ppm_stats {
   int64_t neighbors;       /* photons accepted by the radiance estimates */
   double photon_ms, build_ms, gather_ms, total_ms;
   double last_radius;
+  int64_t device_trees;    /* iterations whose photon list and tree were made on the device and never left it */
+  int64_t gpu_built_trees; /* iterations whose tree the GPU builder made (those, and host-side lists of >= 4096 photons) */
 } ptx_ppm_stats;
 
 typedef struct ptx_scene ptx_scene; /* opaque */
@@ -451,7 +453,11 @@ int32_t ptx_intersect_rays(ptx_scene* scene, int64_t n, const double* origins,
  * gamma + PNG write: img_sum_out (HOST, width*height*3, row 0 = top as Bimage stores it) receives the
  * reference's img_sum after `iterations` iterations, i.e. the sum over iterations of estimate / photon_count.
  * Scene.bbox is the bounding box of the scene's tree; the eye pass and the photon pass use the scene's camera.
- * iteration_cb (optional) is called on the calling thread after every iteration with the running img_sum. */
+ * iteration_cb (optional) is called on the calling thread after every iteration with the running img_sum.
+ * The light table is checked before anything is allocated or launched: PTX_ERR_ARG for a light whose power, colour or position
+ * is not finite, whose power x colour has a negative component, for a spot direction of zero length, and for lights whose total
+ * power is not positive, and ("BUG: no photons") when every light's share of photon_count truncates to no path at all.
+ * PTX_ERR_STATE ("BUG: no photons") when paths were traced and an iteration stored no photon. */
 typedef void (*ptx_ppm_iteration_fn)(void* user, int32_t iteration, double radius, int64_t photon_map_length,
                                      const double* img_sum);
 int32_t ptx_ppm_render(ptx_scene* scene, const ptx_ppm_params* params, const ptx_light* lights, int32_t n_lights,

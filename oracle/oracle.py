@@ -100,6 +100,9 @@ def lib():
     L.orc_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int64), dp]
     L.orc_set_math.argtypes = [C.c_int]
     L.orc_ppm_render.argtypes = [C.c_void_p, C.POINTER(abi.PpmParams), C.POINTER(abi.Light), C.c_int, dp, C.POINTER(C.c_int64), dp]
+    L.orc_ppm_dump.restype = C.c_int64
+    L.orc_ppm_dump.argtypes = [C.c_void_p, C.POINTER(abi.PpmParams), C.POINTER(abi.Light), C.c_int, C.c_int, C.c_int64, dp, ip, ip,
+                               dp, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64)]
     L.orc_lights_cornell.argtypes = [C.c_int, C.c_int, C.POINTER(abi.Light)]
     L.orc_lights_ganesha.argtypes = [C.c_void_p, C.POINTER(abi.Light)]
     _LIB = L
@@ -264,6 +267,33 @@ class Scene:
             raise RuntimeError(f"orc_ppm_render failed: {rc}")
         return img, {"photons_stored": int(st[0]), "photon_rays": int(st[1]), "eye_rays": int(st[2]), "neighbors": int(st[3]),
                      "last_radius": radius.value}
+
+    def ppm_dump(self, params, lights, iteration):
+        """Read-only taps on iteration `iteration` (0-based) of the run ppm_render(params, lights) makes: the photon list in list
+        order (centre, normal, flux: (n, 3) each; path: the sampler offset of the path that stored it), the radius, and per pixel
+        y * W + x (y before the image's flip) the eye record: diffuse (a diffuse hit was reached), hit_point, hit_normal, beta,
+        neighbors (accepted count) and estimate (before inv_photon_count).  img and stats are ppm_render's own."""
+        arr = (abi.Light * len(lights))(*lights)
+        w, h = params.width, params.height
+        cap = max(1, params.photon_count * params.max_bounces)
+        ph = np.zeros((cap, 9))
+        paths = np.zeros(cap, dtype=np.int32)
+        diffuse = np.zeros(w * h, dtype=np.int32)
+        eye = np.zeros((w * h, 12))
+        nb = np.zeros(w * h, dtype=np.int64)
+        info = np.zeros(2)
+        img = np.zeros((h, w, 3))
+        st = (C.c_int64 * 4)()
+        n = lib().orc_ppm_dump(self._h, C.byref(params), arr, len(lights), iteration, cap, _dp(ph), _ip(paths), _ip(diffuse), _dp(eye),
+                               nb.ctypes.data_as(C.POINTER(C.c_int64)), _dp(info), _dp(img), st)
+        if n < 0:
+            raise RuntimeError(f"orc_ppm_dump failed: {n}")
+        assert n <= cap
+        return {"center": ph[:n, 0:3].copy(), "normal": ph[:n, 3:6].copy(), "flux": ph[:n, 6:9].copy(), "path": paths[:n].copy(),
+                "radius": float(info[0]), "init_radius2": float(info[1]), "diffuse": diffuse.astype(bool),
+                "hit_point": eye[:, 0:3].copy(), "hit_normal": eye[:, 3:6].copy(), "beta": eye[:, 6:9].copy(),
+                "estimate": eye[:, 9:12].copy(), "neighbors": nb, "img": img,
+                "stats": {"photons_stored": int(st[0]), "photon_rays": int(st[1]), "eye_rays": int(st[2]), "neighbors": int(st[3])}}
 
     def lights_ganesha(self):
         out = (abi.Light * 2)()

@@ -1793,9 +1793,12 @@ ORC_API void orc_debug_first_scatter(const orc_scene* sc, int width, int height,
 
 /* ================================================================== progressive photon mapping
  * progressive-photon-map/src/progressive_photon_map.ml -- the integrator the reference uses for cornell-box and
- * ganesha.  No fixture of the reference pins this part: PARITY UNPINNED for PPM
- * (the restatement is checked only for internal consistency and against the GPU). */
-typedef struct { sspace_t shader_space; v3 wi, flux; double radius; } photon_t; /* Photon.t, :112-130 */
+ * ganesha.  No fixture of the reference pins this part: PARITY UNPINNED for PPM.
+ * Pinned instead, by tests/test_ppm_oracle.py through orc_ppm_dump below: the gather (fold_neighbors, the radius and normal
+ * tests, the cone weight, the normaliser, the flip) against a brute-force gather in extended precision, the radius schedule
+ * against exact rationals, and the rays the lights send out.  Still unpinned: the photon pass past the light's ray rests on
+ * the trace / scatter code shared with the path integrator, which the golden image and the interval tests pin. */
+typedef struct { sspace_t shader_space; v3 wi, flux; double radius; int path; /* sampler offset of its path: orc_ppm_dump only */ } photon_t; /* Photon.t, :112-130 */
 
 typedef struct {
   int kind;
@@ -1865,6 +1868,7 @@ static void trace_photon(const orc_scene* sc, const light_t* light, const double
     ph.wi = v3_normalize(v3_neg(ray.direction));
     ph.flux = flux;
     ph.radius = radius;
+    ph.path = offset;
     pv_push(out, ph);
     double color_max = v3_max_coord(color);
     if (u <= color_max) {
@@ -1937,9 +1941,12 @@ static void fold_neighbors_rec(const photon_map_t* pm, const node_t* t, v3 point
   fold_neighbors_rec(pm, t->rhs, point, hit_normal, acc);
 }
 
+/* what orc_ppm_dump reports of one pixel's eye path (written only when asked for; no arithmetic depends on it) */
+typedef struct { int diffuse; v3 hit_point, hit_normal, beta; int64_t n_neighbors; } eye_rec_t;
+
 /* estimate_color :316-372 */
 static v3 ppm_estimate(const orc_scene* sc, const photon_map_t* pm, const double* alpha, int offset, int x, int y, int width, int height,
-                       int max_bounces, int_vec* scratch, int64_t* rays, int64_t* n_neighbors) {
+                       int max_bounces, int_vec* scratch, int64_t* rays, int64_t* n_neighbors, eye_rec_t* rec) {
   sampler_t smp; smp.alpha = alpha; smp.offset = offset;
   double inv_widthf = 1.0 / (double)width, inv_heightf = 1.0 / (double)height;
   double dx = sample_dim(&smp, 0), dy = sample_dim(&smp, 1);
@@ -1962,6 +1969,7 @@ static v3 ppm_estimate(const orc_scene* sc, const photon_map_t* pm, const double
     v3 hit_point = h.shader_space.origin, hit_normal = h.shader_space.normal;
     scratch->n = 0;
     if (pm->root) fold_neighbors_rec(pm, pm->root, hit_point, hit_normal, scratch);
+    if (rec) { rec->diffuse = 1; rec->hit_point = hit_point; rec->hit_normal = hit_normal; rec->beta = beta; rec->n_neighbors = (int64_t)scratch->n; }
     if (scratch->n == 0) return black;
     *n_neighbors += (int64_t)scratch->n;
     const double k = 1.0;
@@ -1986,9 +1994,21 @@ static double ppm_radius2(int i, double alpha, double init_radius2) {
   return product * init_radius2 / (double)i;
 }
 
+/* orc_ppm_dump's request: the photon list and the eye records of ONE iteration of the run (read-only taps) */
+typedef struct {
+  int iteration;
+  int64_t photon_cap, n_photons;
+  double* photons;   /* photon_cap * 9: centre, world normal, flux, in list order */
+  int32_t* paths;    /* photon_cap: the sampler offset of the path that stored it */
+  double radius, init_radius2;
+  int32_t* diffuse;  /* W*H, pixel = y * W + x with y as render_image counts it (before write_pixel's flip) */
+  double* eye;       /* W*H * 12: hit point, hit normal, beta, estimate before inv_photon_count */
+  int64_t* neighbors; /* W*H */
+} ppm_dump_t;
+
 /* Make(Scene).go :420-451 without the gamma / PNG step; img_sum_out W*H*3 (row 0 = top) */
-ORC_API int orc_ppm_render(const orc_scene* sc, const ptx_ppm_params* p, const ptx_light* lights_in, int n_lights, double* img_sum_out,
-                           int64_t* stats_out /* photons_stored, photon_rays, eye_rays, neighbors */, double* radius_out) {
+static int ppm_go(const orc_scene* sc, const ptx_ppm_params* p, const ptx_light* lights_in, int n_lights, double* img_sum_out,
+                  int64_t* stats_out, double* radius_out, ppm_dump_t* dump) {
   int width = p->width, height = p->height, max_bounces = p->max_bounces;
   if (!sc->root || n_lights <= 0) return -1;
   light_t* lights = (light_t*)malloc(sizeof(light_t) * (size_t)n_lights);
@@ -2014,10 +2034,29 @@ ORC_API int orc_ppm_render(const orc_scene* sc, const ptx_ppm_params* p, const p
     photon_map_t pm = photon_map_create(sc, p_alpha, it * p->photon_count, radius, p->photon_count, max_bounces, lights, n_lights, &st[1]);
     if (pm.n == 0) { photon_map_free(&pm); free(lights); free(p_alpha); free(e_alpha); free(scratch.idx); return -2; }
     st[0] += (int64_t)pm.n;
+    const int tap = dump && dump->iteration == it;
+    if (tap) {
+      dump->radius = radius; dump->init_radius2 = init_radius2; dump->n_photons = (int64_t)pm.n;
+      for (size_t i = 0; i < pm.n && (int64_t)i < dump->photon_cap; ++i) {
+        const photon_t* ph = &pm.photons[i];
+        const v3 c = ph->shader_space.origin, n = ph->shader_space.normal;
+        double* o = dump->photons + 9 * i;
+        o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = n.x; o[4] = n.y; o[5] = n.z; o[6] = ph->flux.x; o[7] = ph->flux.y; o[8] = ph->flux.z;
+        dump->paths[i] = ph->path;
+      }
+    }
     int eye_sample_base = it * width * height;
     for (int pixel = 0; pixel < width * height; ++pixel) { /* render_image :374-381 */
       int x = pixel % width, y = pixel / width;
-      v3 c = ppm_estimate(sc, &pm, e_alpha, pixel + eye_sample_base, x, y, width, height, max_bounces, &scratch, &st[2], &st[3]);
+      eye_rec_t rec; memset(&rec, 0, sizeof rec);
+      v3 c = ppm_estimate(sc, &pm, e_alpha, pixel + eye_sample_base, x, y, width, height, max_bounces, &scratch, &st[2], &st[3], tap ? &rec : NULL);
+      if (tap) {
+        double* e = dump->eye + 12 * (size_t)pixel;
+        dump->diffuse[pixel] = rec.diffuse; dump->neighbors[pixel] = rec.n_neighbors;
+        e[0] = rec.hit_point.x; e[1] = rec.hit_point.y; e[2] = rec.hit_point.z;
+        e[3] = rec.hit_normal.x; e[4] = rec.hit_normal.y; e[5] = rec.hit_normal.z;
+        e[6] = rec.beta.x; e[7] = rec.beta.y; e[8] = rec.beta.z; e[9] = c.x; e[10] = c.y; e[11] = c.z;
+      }
       v3 color = v3_scale(c, inv_photon_count);
       int yy = height - 1 - y; /* write_pixel :305-313 */
       double* px = &img_sum_out[((size_t)yy * width + x) * 3];
@@ -2029,6 +2068,32 @@ ORC_API int orc_ppm_render(const orc_scene* sc, const ptx_ppm_params* p, const p
   if (radius_out) *radius_out = radius;
   free(lights); free(p_alpha); free(e_alpha); free(scratch.idx);
   return 0;
+}
+ORC_API int orc_ppm_render(const orc_scene* sc, const ptx_ppm_params* p, const ptx_light* lights_in, int n_lights, double* img_sum_out,
+                           int64_t* stats_out /* photons_stored, photon_rays, eye_rays, neighbors */, double* radius_out) {
+  return ppm_go(sc, p, lights_in, n_lights, img_sum_out, stats_out, radius_out, NULL);
+}
+
+/* Two read-only exports for tests/ppm_reference.py: iteration `iteration` (0-based, < p->iterations) of the run orc_ppm_render
+ * makes of the same arguments.  (1) the photon list in list order: 9 doubles a photon (centre, world normal, flux) and the
+ * sampler offset of its path, at most photon_cap of them; (2) per pixel y * W + x (y before write_pixel's flip): whether the eye
+ * path reached a diffuse hit, and then its hit point, hit normal, beta (12 doubles with the estimate before inv_photon_count,
+ * which is there for every pixel) and the number of accepted neighbours.  info_out: radius, init_radius2.  Returns the length of
+ * the list (which may exceed photon_cap: nothing past the cap is written), or orc_ppm_render's negative code. */
+ORC_API int64_t orc_ppm_dump(const orc_scene* sc, const ptx_ppm_params* p, const ptx_light* lights_in, int n_lights, int iteration,
+                             int64_t photon_cap, double* photons_out, int32_t* paths_out, int32_t* diffuse_out, double* eye_out,
+                             int64_t* neighbors_out, double* info_out, double* img_sum_out, int64_t* stats_out) {
+  if (!p || iteration < 0 || iteration >= p->iterations || photon_cap < 0 || !photons_out || !paths_out || !diffuse_out || !eye_out ||
+      !neighbors_out || !img_sum_out)
+    return -1;
+  ppm_dump_t d; memset(&d, 0, sizeof d);
+  d.iteration = iteration; d.photon_cap = photon_cap; d.photons = photons_out; d.paths = paths_out;
+  d.diffuse = diffuse_out; d.eye = eye_out; d.neighbors = neighbors_out;
+  double radius = 0.0;
+  const int rc = ppm_go(sc, p, lights_in, n_lights, img_sum_out, stats_out, &radius, &d);
+  if (rc != 0) return rc;
+  if (info_out) { info_out[0] = d.radius; info_out[1] = d.init_radius2; }
+  return d.n_photons;
 }
 
 /* lights of the two reference scenes, in camera space */

@@ -43,6 +43,8 @@ PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
 # ptx_update_fn: (user, passes_done, rel_err, rgb, err) -> non-zero stops the render
 UPDATE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p)
 ROUND_FN = abi.ROUND_FN
+# ptx_ppm_iteration_fn: (user, iteration, radius, photon_map_length, img_sum)
+PPM_ITERATION_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_double, C.c_int64, dp)
 
 
 def lib():
@@ -372,12 +374,31 @@ class Scene:
         _check(lib().ptx_intersect_rays(self._h, n, _dp(o), _dp(d), _dp(t), _ip(prim), C.byref(st)))
         return t, prim, stats_dict(st)
 
-    def ppm_render(self, params, lights):
-        """ptx_ppm_render: Progressive_photon_map.Make(Scene).go without the gamma / PNG step -> img_sum (H, W, 3)."""
+    def ppm_render(self, params, lights, callback=None):
+        """ptx_ppm_render: Progressive_photon_map.Make(Scene).go without the gamma / PNG step -> img_sum (H, W, 3).
+        callback(iteration, radius, length, image) is called after every iteration (0-based) with that iteration's radius, the
+        length of its photon list and a copy of the running img_sum.  An exception it raises is raised again here, after the
+        render has finished (the C entry point has no way to stop early); the later iterations are not reported."""
         arr = (abi.Light * len(lights))(*lights)
-        img = np.zeros((params.height, params.width, 3))
+        h, w = params.height, params.width
+        img = np.zeros((h, w, 3))
         st = abi.PpmStats()
-        _check(lib().ptx_ppm_render(self._h, C.byref(params), arr, len(lights), _dp(img), C.byref(st), None, None))
+        raised = []
+
+        def trampoline(user, iteration, radius, length, img_sum):
+            if raised:
+                return
+            try:
+                callback(iteration, radius, length, np.ctypeslib.as_array(img_sum, shape=(h, w, 3)).copy())
+            except BaseException as e:  # noqa: BLE001 -- carried across the C frames, raised again below
+                raised.append(e)
+
+        cb = PPM_ITERATION_FN(trampoline) if callback is not None else None
+        rc = lib().ptx_ppm_render(self._h, C.byref(params), arr, len(lights), _dp(img), C.byref(st),
+                                  C.cast(cb, C.c_void_p) if cb else None, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
         return img, {f: getattr(st, f) for f, _ in abi.PpmStats._fields_}
 
     def close(self):

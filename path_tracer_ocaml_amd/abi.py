@@ -118,7 +118,7 @@ class PpmParams(C.Structure):
 class PpmStats(C.Structure):
     _fields_ = [("photons_stored", C.c_int64), ("photon_rays", C.c_int64), ("eye_rays", C.c_int64), ("neighbors", C.c_int64),
                 ("photon_ms", C.c_double), ("build_ms", C.c_double), ("gather_ms", C.c_double), ("total_ms", C.c_double),
-                ("last_radius", C.c_double)]
+                ("last_radius", C.c_double), ("device_trees", C.c_int64), ("gpu_built_trees", C.c_int64)]
 
 
 def ppm_params(width=600, height=None, iterations=10, max_bounces=4, photon_count=75000, alpha=2.0 / 3.0):

@@ -2641,6 +2641,16 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   for (int i = 0; i < n_lights; ++i) {
     const ptx_light& L = lights[i];
     if (L.kind != PTX_LIGHT_POINT && L.kind != PTX_LIGHT_SPOT) return fail(PTX_ERR_ARG, "light %d: unknown kind", i);
+    /* the light table is checked here, on the host: none of these values may reach the photon split below or a kernel */
+    if (!std::isfinite(L.power)) return fail(PTX_ERR_ARG, "light %d: power is not finite", i);
+    for (int k = 0; k < 3; ++k) {
+      if (!std::isfinite(L.color[k]) || !std::isfinite(L.position[k])) return fail(PTX_ERR_ARG, "light %d: colour or position is not finite", i);
+      if (!std::isfinite(L.power * L.color[k]) || L.power * L.color[k] < 0.0) return fail(PTX_ERR_ARG, "light %d: power x colour must be finite and >= 0", i);
+    }
+    if (L.kind == PTX_LIGHT_SPOT) {
+      const double len2 = L.direction[0] * L.direction[0] + L.direction[1] * L.direction[1] + L.direction[2] * L.direction[2];
+      if (!std::isfinite(len2) || !(len2 > 0.0)) return fail(PTX_ERR_ARG, "light %d: spot direction must be finite and of non-zero length", i);
+    }
     PtLightDev& d = hl[(size_t)i];
     std::memset(&d, 0, sizeof d);
     d.kind = L.kind;
@@ -2657,6 +2667,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
     power[(size_t)i] = d.color[0] + d.color[1] + d.color[2]; /* Light.power */
     total_power = total_power + power[(size_t)i];
   }
+  if (!std::isfinite(total_power) || !(total_power > 0.0)) return fail(PTX_ERR_ARG, "the lights' total power must be finite and positive");
   for (int i = 0; i < n_lights; ++i) {
     const double f = power[(size_t)i] / total_power;
     first[(size_t)i + 1] = first[(size_t)i] + (int)((double)p->photon_count * f); /* Int.of_float */
@@ -2761,6 +2772,8 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
           tree_nodes = dt.n_nodes;
           tree_nodes_dev = dt.nodes;
           on_device = true;
+          ++st.device_trees;
+          ++st.gpu_built_trees;
         }
       }
     }
@@ -2785,7 +2798,8 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
       BvhResult tree;
       bool built = false;
       if (n_ph >= 4096) built = bvh_build_gpu(boxes, 8, 8, false, &tree);
-      if (!built) tree = bvh_build(boxes, 8, 8, false);
+      if (built) ++st.gpu_built_trees;
+      else tree = bvh_build(boxes, 8, 8, false);
       n_slots = tree.slot_prim.size();
       std::vector<double> pm_host(n_slots * 9);
       for (size_t sl = 0; sl < n_slots; ++sl) {

@@ -32,6 +32,24 @@ static int run(orc_desc* od, int w, int h, int spp, int depth, int ppm) {
     double radius;
     memset(raw, 0, sizeof(double) * (size_t)w * h * 3);
     if (orc_ppm_render(sc, &p, lights, nl, raw, st, &radius) != 0) return 3;
+    { /* the two read-only exports (photon list, eye records) of the last iteration: same run, same image */
+      const int64_t cap = (int64_t)p.photon_count * p.max_bounces;
+      double* ph = (double*)calloc((size_t)cap * 9, sizeof(double));
+      int32_t* paths = (int32_t*)calloc((size_t)cap, sizeof(int32_t));
+      int32_t* diffuse = (int32_t*)calloc((size_t)w * h, sizeof(int32_t));
+      double* eye = (double*)calloc((size_t)w * h * 12, sizeof(double));
+      int64_t* nb = (int64_t*)calloc((size_t)w * h, sizeof(int64_t));
+      double* img2 = (double*)calloc((size_t)w * h * 3, sizeof(double));
+      double dump_info[2];
+      int64_t st2[4];
+      const int64_t n = orc_ppm_dump(sc, &p, lights, nl, 1, cap, ph, paths, diffuse, eye, nb, dump_info, img2, st2);
+      const int same = n > 0 && n <= cap && memcmp(img2, raw, sizeof(double) * (size_t)w * h * 3) == 0 && memcmp(st, st2, sizeof st) == 0 &&
+                       dump_info[0] == radius;
+      /* a cap smaller than the list: nothing past it may be written */
+      const int64_t n_small = orc_ppm_dump(sc, &p, lights, nl, 0, 1, ph, paths, diffuse, eye, nb, dump_info, img2, st2);
+      free(img2); free(ph); free(paths); free(diffuse); free(eye); free(nb);
+      if (!same || n_small <= 0) return 4;
+    }
   }
   printf("nodes %d depth %d segments %lld first %.6f\n", info[0], info[2], (long long)ct[1], rgb[0]);
   free(rgb);
