@@ -191,6 +191,11 @@ typedef struct ptx_stats {
   /* if count_work: launches of the one-kernel-per-bounce path in the shade-first order (k_bounce_carry; PTX_BOUNCE_ORDER=0 and the
    * modes that keep the walk-first order give 0).  Took the place of a reserved word: the layout of ABI 6 is unchanged */
   int32_t carry_launches;
+  /* if count_work: camera launches (k_bounce / k_bounce_carry, LDS-resident scenes) whose rays walked the tree one per lane
+   * (pt_trace_ray) instead of as a wave packet (pt_trace_packet): PTX_PRIMARY_WALK.  APPENDED: every offset of ABI 6 is unchanged but
+   * sizeof(ptx_stats) grows by 8 bytes (the word and its padding), and the library writes the whole struct: a caller must be
+   * compiled against this header (the Python, OCaml and host callers of this repository are).  ptx_version() stays 6 */
+  int32_t primary_lane_walks;
 } ptx_stats;
 
 /* ---- progressive photon mapping (progressive-photon-map/src/progressive_photon_map.ml) ---- */

@@ -128,6 +128,7 @@ struct PtCounters { /* device-side work counters (count_work) */
   unsigned long long undecided, fallback_steps; /* binary32 filter: lane tests handed to the binary64 code, wave steps that ran it */
   unsigned long long solo;                      /* k_bounce launches that ran their batch's remaining bounces by themselves (PtSolo) */
   unsigned long long carry;                     /* k_bounce_carry launches */
+  unsigned long long lane_walks;                /* camera launches of k_bounce / k_bounce_carry that walked one ray per lane (LANE_WALK) */
 };
 
 /* ------------------------------------------------------------------ small device helpers */
@@ -2744,7 +2745,7 @@ struct PtSolo {
 #ifndef PT_SOLO_MAX_BLOCKS
 #define PT_SOLO_MAX_BLOCKS 256 /* output blocks a workgroup can note per bounce; a launch whose shares could need more does not run solo */
 #endif
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false>
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false, bool LANE_WALK = false /* (PRIMARY && LDS_SCENE: k_bounce_carry) */>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
@@ -2783,6 +2784,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
       if (COUNT) atomicAdd(&counters->solo, 1ull);
     }
   }
+  if (COUNT && PRIMARY && LDS_SCENE && LANE_WALK && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->lane_walks, 1ull);
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
 #if PT_DIAG_FLOOR == 2
   if (gridDim.x > 0) return; /* diagnostic build (tools/README.md): what a launch costs before it does anything */
@@ -2819,7 +2821,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
 #pragma unroll
   for (int k = 0; k < PT_N_SHADE_CAT; ++k) cnt[k] = 0u;
   constexpr int CUT = LDS_SCENE ? PT_TAIL_CUT : PT_TAIL_CUT_GLOBAL;
-  constexpr bool TAIL = CUT > 0 && !(PRIMARY && LDS_SCENE); /* LDS scenes: camera rays walk as a packet (pt_trace_packet) and finish together */
+  constexpr bool TAIL = CUT > 0 && !(PRIMARY && LDS_SCENE); /* LDS scenes: camera rays walk as a packet (pt_trace_packet), or one per lane without a cut (LANE_WALK), and finish together */
   constexpr bool TAIL_UV = TAIL && MODE == PT_MODE_ARRAY;
   constexpr bool TAIL_W = TAIL && !LDS_SCENE; /* 32-bit node index and slot: a third 16 bytes (as in k_trace) */
   /* Parked walks (PtTailCtl) are pooled per WORKGROUP in LDS, behind the shade pools: whichever wave next looks for work and finds
@@ -2970,9 +2972,9 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
     tc.unfinished = false;
     PtTraceResult r;
     PT_TM5(c_floor);
-    unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the packet walk's own counters go nowhere) */
-    if constexpr (PRIMARY && LDS_SCENE) r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, valid, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
-    else r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, LDS_SCENE ? PT_BOUNCE_DIV_LOOP(MODE) : PT_TRACE_DIV_LOOP(false), LDS_SCENE && !COUNT && MODE == PT_MODE_SIMD /* (Array_leaf kernels have no registers to pin: cornell +0.5 %; the walk from HBM / L2 in assembly: +1.9 %, profiles/r05_ab_oct_asm.txt) */>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
+    unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the walk's own counters go nowhere) */
+    if constexpr (PRIMARY && LDS_SCENE && !LANE_WALK) r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, valid, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
+    else r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, LDS_SCENE ? PT_BOUNCE_DIV_LOOP(MODE) : PT_TRACE_DIV_LOOP(false), LDS_SCENE && !COUNT && MODE == PT_MODE_SIMD /* (Array_leaf kernels have no registers to pin: cornell +0.5 %; the walk from HBM / L2 in assembly: +1.9 %, profiles/r05_ab_oct_asm.txt) */>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
     PT_TM5(c_nodes);
     if (DIAG_T) c_filter[1] += (lane == 0);
     const bool park = TAIL && tc.unfinished;
@@ -3133,7 +3135,9 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
 #define PT_CARRY_PARK_WORDS(EMIT_, UV_) (6 + ((EMIT_) ? 2 : 0) + ((UV_) ? 1 : 0))
 static_assert(PT_POOL_BINS >= PT_N_SHADE_CAT, "k_bounce_carry: one output bin per shading category");
 
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
+/* LANE_WALK (PRIMARY launches, PTX_PRIMARY_WALK): the camera rays walk one per lane through pt_trace_ray -- on Simd_leaf scenes the
+ * assembly node loop the queued rays use -- instead of as a wave packet.  A ray's tests and their order are the same in both. */
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_carry(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtHits hout, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
@@ -3150,6 +3154,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
   n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg);
   if (COUNT && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->carry, 1ull);
+  if (COUNT && PRIMARY && LANE_WALK && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->lane_walks, 1ull);
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
   if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; lds_park_n = 0u; lds_park_lock = 0u; }
   if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
@@ -3170,7 +3175,17 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   uint4* const park_uv = park_emit + (EMIT ? 2u * park_cap : 0u);
   bool more = true; /* wave-uniform: the workgroup's share of the input (launch 0: of the camera samples) is not exhausted */
   unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0}; /* COUNT: as in k_trace */
+  /* PT_DIAG == 8 (tools/diag_phases.py; counting renders of diagnostic builds, the camera launch): where a wave's life goes, in ticks
+   * of the 100 MHz clock summed over waves -- nodes = chunk hand-out + ray set-up + the camera walk, prims = shade 0, floor = bounce 1's
+   * walk (resumed walks included), undecided = pushes + parking, segments = the whole loop; fallback_steps = the number of tile turns.
+   * The queued rays' launches add nothing */
+  constexpr bool DIAG_T = COUNT && PT_DIAG == 8 && PRIMARY;
+  unsigned long long tm_last = DIAG_T ? __builtin_readcyclecounter() : 0ull;
+  const unsigned long long tm_begin = tm_last;
+  unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the walks' own counters go nowhere) */
+#define PT_TM8(var) do { if (DIAG_T) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); (var) += now_ - tm_last; tm_last = now_; __builtin_amdgcn_sched_barrier(0); } } while (0)
   for (;;) {
+    PT_TM8(c_filter[0]);
     const uint32_t park_hint = TAIL ? __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u; /* (wave-uniform: one LDS word) */
     /* what this turn walks: the lane's ray, and the rest of the entry it will push */
     bool resume = false, valid = false;
@@ -3233,7 +3248,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
       if (!more) continue;
       i = unit * PT_WAVE + (uint32_t)lane;
       if (PRIMARY) {
-        /* camera samples: generate, walk as a packet (k_bounce's front half).  The hit goes straight to the shade steps below:
+        /* camera samples: generate, walk as a packet or one ray per lane (LANE_WALK; k_bounce's front half).  The hit goes straight to the shade steps below:
          * a chunk is one 8 x 8 tile of one pass, mostly one category, so there are no pools -- each category present is shaded
          * in turn, its lanes live */
         live = i < n;
@@ -3242,8 +3257,11 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
           live = ps.valid;
           if (live) d = pt_primary_dir(sc, g, ps, alpha);
         }
-        if (COUNT && live) c_seg++;
-        const PtTraceResult r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, c_nodes, c_prims, c_floor, c_filter);
+        if (COUNT && !DIAG_T && live) c_seg++;
+        PtTraceResult r;
+        if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
+          r = pt_trace_ray<MODE, COUNT, true, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
+        else r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
         if (live) {
           if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
           sl = r.slot;
@@ -3259,6 +3277,8 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         }
         o = v3(0.0, 0.0, 0.0);
         d = v3(0.0, 0.0, -1.0);
+        PT_TM8(c_nodes);
+        if (DIAG_T) c_filter[1] += (lane == 0);
       } else {
         sl = i < n ? hits.slot[i] : PT_SLOT_HOLE;
         live = sl != PT_SLOT_HOLE;
@@ -3289,14 +3309,16 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
       PT_CARRY_STEP(PT_CAT_METAL, sl)
       PT_CARRY_STEP(PT_CAT_DIELECTRIC, sl)
 #undef PT_CARRY_STEP
+      PT_TM8(c_prims);
       if (last_bounce || __ballot(valid) == 0ull) continue; /* nothing survives the step */
-      if (COUNT && valid) c_seg++;
+      if (COUNT && !DIAG_T && valid) c_seg++;
     }
     /* walk the new rays (or go on with the parked ones); the last chunks of a wave run to completion */
     tc.min_active = (TAIL && more) ? CUT : 0;
     tc.resume = resume && valid;
     tc.unfinished = false;
-    const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid, TAIL ? &tc : nullptr, c_filter);
+    const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
+    PT_TM8(c_floor);
     const bool park = TAIL && tc.unfinished;
     const bool done = valid && !park;
     const int cat = !done ? PT_CAT_NONE : (r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot]);
@@ -3341,7 +3363,13 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
       }
     }
   }
-  if (COUNT) {
+  if (DIAG_T) {
+    PT_TM8(c_filter[0]);
+    c_seg = (lane == 0) ? tm_last - tm_begin : 0ull;
+    if (lane != 0) c_nodes = c_prims = c_floor = c_filter[0] = 0ull; /* wave-uniform quantities: one lane's copy */
+  }
+#undef PT_TM8
+  if (COUNT && !(PT_DIAG == 8 && !PRIMARY)) { /* (that diagnostic build measures the camera launch only) */
     c_nodes = pt_wave_sum(c_nodes);
     c_prims = pt_wave_sum(c_prims);
     c_floor = pt_wave_sum(c_floor);

@@ -269,6 +269,7 @@ struct ptx_scene {
   int solo_entries = env_int("PTX_SOLO_ENTRIES", 0); /* k_bounce: a launch whose input queue holds at most this many entries runs the batch's remaining bounces by itself (0 = off) */
   int fused_global = env_int("PTX_FUSED_GLOBAL", 1); /* scenes walked from HBM / L2: 1 = k_bounce<..., LDS_SCENE = false> instead of k_trace + k_shade_pool */
   int bounce_order = env_int("PTX_BOUNCE_ORDER", 2); /* LDS-resident scenes, PTX_FUSED=2: 1 = a bounce launch shades its input's carried hits first and walks the new rays second (k_bounce_carry), 0 = walk first (k_bounce), 2 = by scene (carry_possible) */
+  int primary_walk = env_int("PTX_PRIMARY_WALK", 2); /* LDS-resident scenes, the camera launch of k_bounce / k_bounce_carry: 0 = the tile walks as a wave packet (pt_trace_packet), 1 = one ray per lane (pt_trace_ray), 2 = by scene (primary_lane_walk) */
   int bounce_threads = env_int("PTX_BOUNCE_THREADS", 0); /* k_bounce workgroup size (0 = PT_BOUNCE_THREADS; tests: 64 .. 1024) */
   int bounce_wgs = env_int("PTX_BOUNCE_WGS", 0);         /* k_bounce workgroups per launch (0 = one per CU; tests: a few, so that every wave walks hundreds of chunks) */
   int trace_top = env_int("PTX_TRACE_TOP", 0);     /* scenes walked from HBM / L2: 1 = keep the tree's top in LDS (measured: no gain, the top of the tree is hot in L1 anyway; DESIGN.md section 4) */
@@ -541,13 +542,19 @@ bool carry_possible(const ptx_scene* s) {
   return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !scene_lit(s) && s->fused >= 2 && s->solo_entries <= 0 && trace_scene_lds_bytes(s) > 0 && !bounce_from_hbm(s) &&
          bounce_lds_bytes(s, nullptr, true) <= kBounceLdsLimit;
 }
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY>
+/* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
+ * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
+ * scenes, which have no such loop, keep the wave packet (DESIGN.md Appendix A).  1 = per lane everywhere, 0 = the packet everywhere */
+bool primary_lane_walk(const ptx_scene* s) {
+  return s->primary_walk == 1 || (s->primary_walk >= 2 && s->dev.mode == PT_MODE_SIMD);
+}
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false>
 void launch_carry_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
                        const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
   const int stack_depth = std::max(1, s->tree_depth + 1);
   size_t pool_off = 0;
   const size_t lds = bounce_lds_bytes(s, &pool_off, true);
-  auto kern = k_bounce_carry<MODE, COUNT, EMIT, PRIMARY>;
+  auto kern = k_bounce_carry<MODE, COUNT, EMIT, PRIMARY, LANE_WALK>;
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
     hipFuncAttributes fa;
@@ -566,10 +573,12 @@ template <int MODE, bool COUNT>
 void launch_carry_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
                        const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
   if (s->dev.has_emit) {
-    if (pl.on) launch_carry_inst<MODE, COUNT, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    if (pl.on && primary_lane_walk(s)) launch_carry_inst<MODE, COUNT, true, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else if (pl.on) launch_carry_inst<MODE, COUNT, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
     else launch_carry_inst<MODE, COUNT, true, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
   } else {
-    if (pl.on) launch_carry_inst<MODE, COUNT, false, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    if (pl.on && primary_lane_walk(s)) launch_carry_inst<MODE, COUNT, false, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
+    else if (pl.on) launch_carry_inst<MODE, COUNT, false, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
     else launch_carry_inst<MODE, COUNT, false, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
   }
 }
@@ -591,7 +600,9 @@ void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
   const size_t lds = bounce_lds_bytes(s, &pool_off);
   /* the instantiation with the loop over a batch's remaining bounces (PtSolo) only where it can be taken */
   /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
-  auto kern = LIT ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT>
+  /* (camera rays of an LDS-resident scene: the packet walk or one ray per lane, primary_lane_walk) */
+  auto kern = (PRIMARY && LDS_SCENE && primary_lane_walk(s)) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT, PRIMARY && LDS_SCENE>
+            : LIT ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT>
                   : ((solo.flag != nullptr && !PRIMARY) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, !PRIMARY && !LIT> : k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false>);
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
@@ -792,6 +803,7 @@ int collect_counters(ptx_scene* s, ptx_stats* stats) {
   stats->filter_fallback_steps = (int64_t)c.fallback_steps;
   stats->solo_launches = (int32_t)c.solo;
   stats->carry_launches = (int32_t)c.carry;
+  stats->primary_lane_walks = (int32_t)c.lane_walks;
   return 0;
 }
 
@@ -2063,6 +2075,7 @@ void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
   acc->segments += o.segments; acc->nodes_tested += o.nodes_tested; acc->prims_tested += o.prims_tested;
   acc->floor_tested += o.floor_tested; acc->filter_undecided += o.filter_undecided;
   acc->filter_fallback_steps += o.filter_fallback_steps; acc->solo_launches += o.solo_launches; acc->carry_launches += o.carry_launches;
+  acc->primary_lane_walks += o.primary_lane_walks;
   for (int i = 0; i < PTX_N_KERNELS; ++i) {
     acc->kernel_ms[i] += o.kernel_ms[i];
     acc->kernel_launches[i] += o.kernel_launches[i];
