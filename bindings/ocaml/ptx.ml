@@ -203,6 +203,18 @@ external render_adaptive_flat
   -> int
   = "ptx_ml_render_adaptive_stub_bytecode" "ptx_ml_render_adaptive_stub"
 
+external render_denoised_flat
+  :  scene
+  -> floatarray
+     (* width, height, samples_per_pixel, max_bounces, passes_per_update, target_rel_err, levels, normal_power_log2,
+        feature_passes, flags, sigma_luminance, sigma_depth, sigma_albedo *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* image, W*H*3 *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* per-pixel error, W*H*3, or empty *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* first-hit feature means, W*H*8, or empty *)
+  -> (int -> float -> bool -> bool) (* passes done, rel_err, last update; true stops the render *)
+  -> int
+  = "ptx_ml_render_denoised_stub_bytecode" "ptx_ml_render_denoised_stub"
+
 module FA = Stdlib.Float.Array
 
 (* the tables are interned structurally: a 150 k-triangle mesh with one material gets one row, not 150 k *)
@@ -393,6 +405,55 @@ let render_progressive
       ]
   in
   render_progressive_flat scene params image err (fun passes_done rel_err last ->
+    on_update ~passes_done ~rel_err ~last)
+;;
+
+(* [render_progressive] whose updates show the image filtered by the variance-guided a-trous denoiser (ptx_render_denoised):
+   [levels] iterations (0 = no filter), the normal weight raised to 2^[normal_power_log2], the first-hit features taken from the
+   first [feature_passes] passes (0 = all), [demodulate] dividing the radiance by the first-hit albedo before filtering.  The
+   defaults are ptx_denoise_defaults'.  [passes_per_update] is at least 2.  [err] (if given) receives the UN-denoised per-pixel
+   standard error and [features] (if given, W*H*8: albedo, normal, depth, hits) the feature means. *)
+let render_denoised
+  ?(target_rel_err = 0.)
+  ?(levels = 5)
+  ?(normal_power_log2 = 5)
+  ?(feature_passes = 8)
+  ?(demodulate = true)
+  ?(sigma_luminance = 4.)
+  ?(sigma_depth = 0.05)
+  ?(sigma_albedo = 0.2)
+  ?err
+  ?features
+  scene
+  ~width
+  ~height
+  ~samples_per_pixel
+  ~max_bounces
+  ~passes_per_update
+  ~image
+  ~on_update
+  =
+  let empty () = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0 in
+  let err = Option.value err ~default:(empty ()) in
+  let features = Option.value features ~default:(empty ()) in
+  let params =
+    FA.of_list
+      [ Float.of_int width
+      ; Float.of_int height
+      ; Float.of_int samples_per_pixel
+      ; Float.of_int max_bounces
+      ; Float.of_int passes_per_update
+      ; target_rel_err
+      ; Float.of_int levels
+      ; Float.of_int normal_power_log2
+      ; Float.of_int feature_passes
+      ; (if demodulate then 1. else 0.)
+      ; sigma_luminance
+      ; sigma_depth
+      ; sigma_albedo
+      ]
+  in
+  render_denoised_flat scene params image err features (fun passes_done rel_err last ->
     on_update ~passes_done ~rel_err ~last)
 ;;
 

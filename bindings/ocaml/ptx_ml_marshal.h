@@ -220,4 +220,34 @@ static __attribute__((unused)) int32_t ptx_ml_render_adaptive(ptx_scene* s, cons
   return rc;
 }
 
+/* Integrator.render as a sequence of DENOISED updates (ptx_render_denoised): params13 = width, height, samples_per_pixel,
+ * max_bounces, passes_per_update, target_rel_err, then the denoiser's levels, normal_power_log2, feature_passes, flags,
+ * sigma_luminance, sigma_depth, sigma_albedo.  image (W*H*3) holds the filtered image of the last update, err (nullable) the
+ * un-denoised per-pixel standard error, feat (nullable, W*H*8) the first-hit feature means, *passes_done its passes. */
+static __attribute__((unused)) int32_t ptx_ml_render_denoised(ptx_scene* s, const double* params13, double* image, double* err, double* feat,
+                                                              int32_t* passes_done, ptx_update_fn on_update, void* user) {
+  if (!params13) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params13[0];
+  p.height = (int32_t)params13[1];
+  p.samples_per_pixel = (int32_t)params13[2];
+  p.max_bounces = (int32_t)params13[3];
+  ptx_progressive_params pp;
+  memset(&pp, 0, sizeof pp);
+  pp.passes_per_update = (int32_t)params13[4];
+  pp.want_error = 1;
+  pp.target_rel_err = params13[5];
+  ptx_denoise_params dn;
+  memset(&dn, 0, sizeof dn);
+  dn.levels = (int32_t)params13[6];
+  dn.normal_power_log2 = (int32_t)params13[7];
+  dn.feature_passes = (int32_t)params13[8];
+  dn.flags = (int32_t)params13[9];
+  dn.sigma_luminance = params13[10];
+  dn.sigma_depth = params13[11];
+  dn.sigma_albedo = params13[12];
+  return ptx_render_denoised(s, &p, &pp, &dn, image, err, feat, passes_done, NULL, on_update, user);
+}
+
 #endif /* PTX_ML_MARSHAL_H */

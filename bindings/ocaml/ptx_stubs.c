@@ -534,3 +534,48 @@ CAMLprim value ptx_ml_render_adaptive_stub_bytecode(value* argv, int argn) {
   (void)argn;
   return ptx_ml_render_adaptive_stub(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5]);
 }
+
+/* external render_denoised_flat : scene -> floatarray -> image -> err -> feat -> (int -> float -> bool -> bool) -> int
+ *   = "ptx_ml_render_denoised_stub"
+ * (scene, the 13 floats of ptx_ml_render_denoised, image (W*H*3), err (W*H*3 or empty), feat (W*H*8 or empty), on_update passes_done
+ * rel_err last -> stop) -> passes done.  The exception of a callback that raised is raised here, after the library has returned
+ * (and has drained everything it queued). */
+CAMLprim value ptx_ml_render_denoised_stub(value handle, value params, value image, value err, value feat, value on_update) {
+  CAMLparam5(handle, params, image, err, feat);
+  CAMLxparam1(on_update);
+  CAMLlocal1(exn);
+  if (floatarray_length(params) != 13) caml_invalid_argument("Ptx.render_denoised: params needs 13 floats");
+  double p13[13];
+  memcpy(p13, floatarray_data(params), sizeof p13);
+  const intnat w = (intnat)p13[0], h = (intnat)p13[1];
+  if (w <= 0 || h <= 0 || Caml_ba_array_val(image)->dim[0] != w * h * 3)
+    caml_invalid_argument("Ptx.render_denoised: image must hold width * height * 3 floats");
+  const intnat n_err = Caml_ba_array_val(err)->dim[0];
+  if (n_err != 0 && n_err != w * h * 3) caml_invalid_argument("Ptx.render_denoised: err must be empty or hold width * height * 3 floats");
+  const intnat n_feat = Caml_ba_array_val(feat)->dim[0];
+  if (n_feat != 0 && n_feat != w * h * PTX_FEATURE_DOUBLES)
+    caml_invalid_argument("Ptx.render_denoised: feat must be empty or hold width * height * 8 floats");
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_denoised: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_denoised: scene already destroyed");
+  double* out = (double*)Caml_ba_data_val(image); /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  double* err_out = n_err ? (double*)Caml_ba_data_val(err) : NULL;
+  double* feat_out = n_feat ? (double*)Caml_ba_data_val(feat) : NULL;
+  exn = Val_unit;
+  ptx_ml_update_cb cb = {{&on_update, &exn, 0}, (int32_t)p13[2], 0};
+  int32_t passes_done = 0;
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_denoised(s, p13, out, err_out, feat_out, &passes_done, ptx_ml_on_update, &cb);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (cb.cb.raised) caml_raise(exn);
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_long(passes_done));
+}
+
+/* bytecode entry of the 6-argument external */
+CAMLprim value ptx_ml_render_denoised_stub_bytecode(value* argv, int argn) {
+  (void)argn;
+  return ptx_ml_render_denoised_stub(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5]);
+}

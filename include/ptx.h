@@ -438,6 +438,92 @@ int32_t ptx_render_adaptive(ptx_scene* scene, const ptx_render_params* params, c
                             double* rgb_out, double* err_out, int32_t* passes_out, ptx_stats* stats, ptx_round_fn on_round,
                             void* user);
 
+/* ---- first-hit feature buffers and the variance-guided a-trous denoiser ----
+ * Image-space passes beside the integrator: no render entry point above changes, and the ABI version stays 6 (only entry points and
+ * structs were added).  Everything here runs on ONE GPU over the whole image. */
+
+/* The feature record of one sample = what the FIRST hit of its camera ray shows (the first hit, not the first non-specular one: a
+ * mirror or a glass ball shows its own surface).  8 doubles per pixel, index (y * W + x) * 8:
+ *   [0..2] albedo  at a hit: Texture.eval of the hit material's texture at the hit's texture coordinates for Lambertian and Metal
+ *                  (the texture colour, not the Schlick-tinted attenuation), (1, 1, 1) for Dielectric; at a miss: Scene.background
+ *                  of the ray
+ *   [3..5] normal  the facing shading normal (Sphere.hit / Triangle.Hit.to_hit, negated when hit_front is false; floor triangles
+ *                  included); 0 at a miss
+ *   [6]    depth   t_hit; 0 at a miss
+ *   [7]    hits    1 at a hit, 0 at a miss */
+#define PTX_FEATURE_DOUBLES 8 /* albedo r g b, normal x y z, depth, hits */
+
+/* The records of the camera rays of every sample (x, y, pass), pass in [pass_first, pass_first + pass_count), of the frame `params`
+ * describes -- the ray the render traces: sampler offset y * W + x + pass * N, dimensions 0 and 1, Camera.ray -- ADDED to
+ * d_feat_inout (DEVICE, W * H * 8 doubles, never zeroed: the caller zeroes it before the first slice) per pixel in pass order, so
+ * slices of a range give the range's sums bit for bit, and no float atomics are used: the same inputs give the same bits on every
+ * run.  Every value comes from the functions the render's own first segment uses (same bits).  max_bounces fixes the sampler's
+ * dimension as in a render.  PTX_ERR_ARG for band_step > 1 or n_gpus > 1 and for a range outside [0, N) or pass_count < 1.
+ * stats->samples = W * H * pass_count.  `stream` and PTX_RENDER_ASYNC as in ptx_render_passes_device; queued calls on one handle
+ * share its feature workspace and must be ordered on ONE stream.  d_feat_inout must be 16-byte aligned (the records move as
+ * 16-byte accesses; any hipMalloc'ed buffer is). */
+int32_t ptx_render_features_device(ptx_scene* scene, const ptx_render_params* params, int32_t pass_first, int32_t pass_count,
+                                   double* d_feat_inout, void* stream, ptx_stats* stats);
+
+#define PTX_DENOISE_DEMODULATE 1
+typedef struct ptx_denoise_params {      /* 40 bytes */
+  int32_t levels;             /* L, 0..8: a-trous iterations, step 2^l */
+  int32_t normal_power_log2;  /* m, 0..8: w_n = max(0, n_p . n_q)^(2^m) by m squarings */
+  int32_t feature_passes;     /* ptx_render_denoised only: features from passes [0, min(F, k)); 0 = all */
+  int32_t flags;              /* PTX_DENOISE_DEMODULATE */
+  double sigma_luminance, sigma_depth, sigma_albedo;   /* each > 0 and finite */
+} ptx_denoise_params;
+/* levels 5, normal_power_log2 5, feature_passes 8, flags PTX_DENOISE_DEMODULATE, sigmas 4.0, 0.05, 0.2 */
+int32_t ptx_denoise_defaults(ptx_denoise_params* out);
+
+/* The edge-avoiding a-trous wavelet filter, guided by the feature sums and the per-pixel standard error.  DEVICE inputs: the raw
+ * sums S1 (d_raw, W*H*3), se per channel exactly as ptx_pixel_error_device / ptx_pixel_error_counts_device write it (d_err, W*H*3),
+ * the feature sums of kf = feature_passes_done >= 1 passes (d_feat, W*H*8); k = passes_done, or the pixel's own d_passes[p]
+ * (DEVICE, nullable, every count >= 2: what ptx_render_adaptive leaves).  k < 2 is PTX_ERR_ARG (se would be infinite, and an
+ * infinite variance times a zero weight is NaN); a count map is not checked.  Output d_raw_out (DEVICE, W*H*3, not d_raw): the
+ * denoised SUMS, mean * k(p), so ptx_film_resolve_device / ptx_film_resolve_counts_device apply unchanged.  levels = 0 copies
+ * d_raw bit for bit.  Waits for `stream`.  PTX_ERR_ARG for levels or normal_power_log2 outside 0..8, unknown flags, a sigma that is
+ * not > 0 and finite.  d_feat must be 16-byte aligned (as ptx_render_features_device's buffer is).
+ *
+ * The rule, operation for operation (binary64, no contraction; every sum over taps starts at 0 and runs in row-major tap order,
+ * j outer, i inner; a tap outside the image is skipped):
+ *   prepare   kd = (double)k, kfd = (double)kf;  m_c = S1_c / kd;  var_c = se_c * se_c;
+ *             a_c = A_c / kfd, n = N / kfd, z = Z / kfd (A, N, Z: the albedo, normal and depth sums), h = the hits sum;
+ *             D_c = (DEMODULATE and a_c > 2^-7) ? a_c : 1;  c_c = m_c / D_c;
+ *             V = (var_r / (D_r * D_r) + var_g / (D_g * D_g)) + var_b / (D_b * D_b)
+ *   level l = 0 .. L-1, step s = 2^l, for every pixel p from the level's input (c, V):
+ *             lambda(q) = (c_r(q) + c_g(q)) + c_b(q)
+ *             Vbar = sum over q = p + (i, j), i, j in -1..1, of (b_j * b_i) * V(q), b = (1/4, 1/2, 1/4) (not renormalised)
+ *             den = (sigma_l * sigma_l) * Vbar + 1e-12
+ *             for q = p + s * (i, j), i, j in -2..2, with h5 = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *               w_n = 1 when h(p) = 0 and h(q) = 0; else d = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z,
+ *                     w_n = d > 0 ? d : 0, then w_n = w_n * w_n, m times
+ *               r = (z_p - z_q) / (sigma_z * (|z_p| + |z_q|) + 1e-300);  w_z = 1 / (1 + r * r)
+ *               e = a_p - a_q;  w_a = 1 / (1 + ((e_r * e_r + e_g * e_g) + e_b * e_b) / (sigma_a * sigma_a))
+ *               t = lambda(p) - lambda(q);  w_l = 1 / (1 + (t * t) / den)
+ *               w = (h5_j * h5_i) * (((w_n * w_z) * w_a) * w_l)
+ *               sw = sw + w;  sc_c = sc_c + w * c_c(q);  sv = sv + (w * w) * V(q)
+ *             c'_c = sc_c / sw;  V' = sv / (sw * sw)       (the centre tap has w = (3/8)^2, so sw > 0)
+ *   finish    out_c = (c_c * D_c) * kd */
+int32_t ptx_denoise_device(int32_t device, int32_t width, int32_t height, const ptx_denoise_params* denoise,
+                           int32_t passes_done, const int32_t* d_passes /* nullable, W*H, each >= 2 */,
+                           int32_t feature_passes_done /* kf >= 1 */,
+                           const double* d_raw, const double* d_err, const double* d_feat,
+                           double* d_raw_out, void* stream);
+
+/* ptx_render_progressive whose updates show the DENOISED image.  The square sums are always kept (progressive->want_error is
+ * implied; target_rel_err works as there, on the un-denoised sums); passes_per_update >= 2 is required.  Beside every slice
+ * [first, first + count) the feature slice [first, min(first + count, F)) is rendered while first < F (F = denoise->feature_passes,
+ * 0 = N).  An update after k passes is: ptx_pixel_error_device, ptx_denoise_device with kf = min(F, k) into a buffer the scene
+ * owns, ptx_film_resolve_device of the denoised sums with spp = k.  rgb_out: the denoised image; err_out (HOST, nullable): the
+ * un-denoised se; feat_out (HOST, nullable, W*H*8): the feature MEANS, sums / kf.  The callback sees the denoised image and the
+ * un-denoised se.  Early stop, the drain on every exit, PTX_ERR_STATE for ptx_scene_set_lighting from a callback, and the refusal
+ * of a host-only scene are ptx_render_progressive's.  With levels = 0, run to N passes, rgb_out is ptx_render's image bit for bit. */
+int32_t ptx_render_denoised(ptx_scene* scene, const ptx_render_params* params, const ptx_progressive_params* progressive,
+                            const ptx_denoise_params* denoise, double* rgb_out, double* err_out /* nullable */,
+                            double* feat_out /* nullable, HOST, W*H*8 means */, int32_t* passes_done_out, ptx_stats* stats,
+                            ptx_update_fn on_update, void* user);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

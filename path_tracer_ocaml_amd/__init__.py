@@ -37,6 +37,7 @@ EXPORTS = (
     "ptx_image_pin", "ptx_image_unpin", "ptx_render_passes_device", "ptx_pixel_error_device", "ptx_render_progressive",
     "ptx_render_pixels_device", "ptx_film_resolve_counts_device", "ptx_pixel_error_counts_device", "ptx_render_adaptive",
     "ptx_scene_set_lighting", "ptx_scene_lighting",
+    "ptx_render_features_device", "ptx_denoise_defaults", "ptx_denoise_device", "ptx_render_denoised",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -111,6 +112,13 @@ def lib():
                                  C.POINTER(abi.PpmStats), C.c_void_p, C.c_void_p]
     L.ptx_scene_set_lighting.argtypes = [C.c_void_p, C.c_int32]
     L.ptx_scene_lighting.argtypes = [C.c_void_p, ip, ip, dp]
+    L.ptx_render_features_device.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.POINTER(abi.Stats)]
+    L.ptx_denoise_defaults.argtypes = [C.POINTER(abi.DenoiseParams)]
+    L.ptx_denoise_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(abi.DenoiseParams), C.c_int32, C.c_void_p,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptx_render_denoised.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.ProgressiveParams),
+                                      C.POINTER(abi.DenoiseParams), dp, dp, dp, ip, C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 
@@ -354,6 +362,65 @@ class Scene:
         _check(rc)
         return out, err_out, passes_out, stats_dict(st)
 
+    def render_features_device(self, params, pass_first, pass_count, d_feat_ptr, stream=None):
+        """ptx_render_features_device: the first-hit feature records (albedo, normal, depth, hits: 8 doubles per pixel) of passes
+        [pass_first, pass_first + pass_count) of the frame of params.samples_per_pixel passes ADDED to the whole-image feature
+        sums in DEVICE memory (never zeroed), in pass order."""
+        if getattr(params, "n_gpus", 0) > 1 or getattr(params, "band_step", 0) > 1:
+            raise ValueError("a feature pass runs on one GPU over the whole image")
+        st = abi.Stats()
+        _check(lib().ptx_render_features_device(self._h, C.byref(params), int(pass_first), int(pass_count), C.c_void_p(d_feat_ptr),
+                                                C.c_void_p(stream) if stream else None, C.byref(st)))
+        return stats_dict(st)
+
+    def render_denoised(self, width, height, samples_per_pixel, max_bounces, passes_per_update, denoise=None, on_update=None,
+                        target_rel_err=0.0, out=None, err_out=None, feat_out=None, **kw):
+        """ptx_render_denoised: render_progressive whose updates show the image filtered by the variance-guided a-trous denoiser
+        (`denoise`: an abi.DenoiseParams, a dict of its fields over the defaults, or None for denoise_defaults()).  The error is
+        always kept; on_update(passes_done, rel_err, rgb, err) sees the denoised image and the un-denoised per-pixel standard
+        error.  feat_out ((H, W, 8) float64, or True to have one made) receives the first-hit feature means.  Returns
+        (rgb, err, feat or None, passes_done, stats)."""
+        if int(passes_per_update) < 2:
+            raise ValueError("passes_per_update must be >= 2")
+        if int(samples_per_pixel) < 2:
+            raise ValueError("samples_per_pixel must be >= 2")
+        if not float(target_rel_err) >= 0.0:
+            raise ValueError("target_rel_err must be >= 0")
+        if kw.get("n_gpus", 0) > 1 or kw.get("band_step", 0) > 1:
+            raise ValueError("denoised rendering runs on one GPU over the whole image")
+        dn = denoise_params(denoise)
+        out = _image_arg(out, width, height, "out")
+        err_out = _image_arg(err_out, width, height, "err_out")
+        if feat_out is True:
+            feat_out = np.zeros((height, width, abi.PTX_FEATURE_DOUBLES))
+        elif feat_out is not None and (getattr(feat_out, "shape", None) != (height, width, abi.PTX_FEATURE_DOUBLES)
+                                       or feat_out.dtype != np.float64 or not feat_out.flags["C_CONTIGUOUS"]):
+            raise ValueError("feat_out must be a C-contiguous float64 array of shape (height, width, 8)")
+        p = render_params(width, height, samples_per_pixel, max_bounces, **kw)
+        pp = abi.ProgressiveParams()
+        pp.passes_per_update, pp.want_error, pp.target_rel_err = int(passes_per_update), 1, float(target_rel_err)
+        raised = []
+
+        def trampoline(user, passes_done, rel_err, rgb, err):
+            if raised:
+                return 1
+            try:
+                return 1 if on_update(passes_done, rel_err, out, err_out) else 0
+            except BaseException as e:  # noqa: BLE001 -- carried across the C frames, raised again below
+                raised.append(e)
+                return 1
+
+        cb = UPDATE_FN(trampoline) if on_update is not None else None
+        done = C.c_int32(0)
+        st = abi.Stats()
+        rc = lib().ptx_render_denoised(self._h, C.byref(p), C.byref(pp), C.byref(dn), _dp(out), _dp(err_out),
+                                       _dp(feat_out) if feat_out is not None else None, C.byref(done), C.byref(st),
+                                       C.cast(cb, C.c_void_p) if cb else None, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return out, err_out, feat_out, done.value, stats_dict(st)
+
     def trace_samples(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes, count_work=False):
         xs = np.ascontiguousarray(xs, dtype=np.int32)
         ys = np.ascontiguousarray(ys, dtype=np.int32)
@@ -429,6 +496,61 @@ def pixel_error_device(device, width, rows, passes_done, d_raw_ptr, d_sq_ptr, d_
                                         C.c_void_p(d_err_ptr) if d_err_ptr else None, C.byref(rel),
                                         C.c_void_p(stream) if stream else None))
     return rel.value
+
+
+def denoise_defaults():
+    """ptx_denoise_defaults: levels 5, normal_power_log2 5, feature_passes 8, demodulation on, sigmas 4.0, 0.05, 0.2"""
+    d = abi.DenoiseParams()
+    _check(lib().ptx_denoise_defaults(C.byref(d)))
+    return d
+
+
+def denoise_params(denoise=None):
+    """An abi.DenoiseParams from None (the defaults), a dict of fields over the defaults (`demodulate` sets the flag), or a
+    DenoiseParams; checked as the library checks it (ValueError)."""
+    if isinstance(denoise, abi.DenoiseParams):
+        d = denoise
+    else:
+        d = denoise_defaults()
+        fields = {f for f, _ in abi.DenoiseParams._fields_}
+        for k, v in (denoise or {}).items():
+            if k == "demodulate":
+                d.flags = (d.flags | abi.PTX_DENOISE_DEMODULATE) if v else (d.flags & ~abi.PTX_DENOISE_DEMODULATE)
+            elif k in fields:
+                setattr(d, k, v)
+            else:
+                raise ValueError(f"unknown denoiser setting {k!r}")
+    if not 0 <= d.levels <= 8:
+        raise ValueError("levels must be in [0, 8]")
+    if not 0 <= d.normal_power_log2 <= 8:
+        raise ValueError("normal_power_log2 must be in [0, 8]")
+    if d.feature_passes < 0:
+        raise ValueError("feature_passes must be >= 0")
+    if d.flags & ~abi.PTX_DENOISE_DEMODULATE:
+        raise ValueError("unknown bits in flags")
+    for name in ("sigma_luminance", "sigma_depth", "sigma_albedo"):
+        v = getattr(d, name)
+        if not (v > 0.0 and v < float("inf")):
+            raise ValueError(f"{name} must be > 0 and finite")
+    return d
+
+
+def denoise_device(device, width, height, denoise, passes_done, feature_passes_done, d_raw_ptr, d_err_ptr, d_feat_ptr, d_out_ptr,
+                   d_passes_ptr=None, stream=None):
+    """ptx_denoise_device: the a-trous filter over DEVICE raw sums (W*H*3), their per-pixel standard error (W*H*3) and the
+    feature sums of `feature_passes_done` passes (W*H*8) into d_out_ptr: denoised sums on the input's scale.  k = passes_done, or
+    each pixel's own count from d_passes_ptr (int32, every count >= 2)."""
+    dn = denoise_params(denoise)
+    if not d_passes_ptr and int(passes_done) < 2:
+        raise ValueError("passes_done must be >= 2")
+    if int(feature_passes_done) < 1:
+        raise ValueError("feature_passes_done must be >= 1")
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError("bad dimensions")
+    _check(lib().ptx_denoise_device(device, int(width), int(height), C.byref(dn), int(passes_done),
+                                    C.c_void_p(d_passes_ptr) if d_passes_ptr else None, int(feature_passes_done),
+                                    C.c_void_p(d_raw_ptr), C.c_void_p(d_err_ptr), C.c_void_p(d_feat_ptr), C.c_void_p(d_out_ptr),
+                                    C.c_void_p(stream) if stream else None))
 
 
 def film_resolve_counts_device(device, width, height, d_raw_ptr, d_passes_ptr, d_rgb_ptr, stream=None):

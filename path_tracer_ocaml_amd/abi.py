@@ -98,6 +98,15 @@ class AdaptiveParams(C.Structure):
                 ("radiance_floor", C.c_double)]
 
 
+PTX_FEATURE_DOUBLES = 8  # albedo r g b, normal x y z, depth, hits
+PTX_DENOISE_DEMODULATE = 1
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("normal_power_log2", C.c_int32), ("feature_passes", C.c_int32), ("flags", C.c_int32),
+                ("sigma_luminance", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
+
+
 # ptx_round_fn: (user, round, passes_done, active_next, samples, rel_err, rgb, err, passes) -> non-zero stops the render
 ROUND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                        C.c_void_p)

@@ -3845,5 +3845,6 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #ifndef PT_KERNELS_ONLY /* (tools/quick_kernel.sh instantiates single kernels of this file for register / ISA studies) */
 #include "bvh_build_gpu.inc"
 #include "ppm.inc"
+#include "denoise.inc"
 #include "ptx_api.inc"
 #endif

@@ -248,6 +248,14 @@ struct ptx_scene {
   DevBuf<uint8_t> sel_keep;
   DevBuf<uint32_t> sel_blocks, sel_offsets;
   hipEvent_t ev_select = nullptr;
+  /* ptx_render_features_device: the hit records of one batch of camera rays (slot; t on scenes without triangles), k_trace's
+   * hand-out words and parked walks -- its own, because a queued slice of a render may be running on the workspace sets meanwhile;
+   * ptx_render_denoised: the feature sums, their means for the host, the filter's guide and {c, V} pair, the denoised sums */
+  DevBuf<int32_t> feat_slot;
+  DevBuf<double> feat_t;
+  DevBuf<uint32_t> feat_work;
+  DevBuf<uint4> feat_susp;
+  DevBuf<double> feat, feat_mean, den_raw, den_guide, den_cv[2];
   DevBuf<PtCounters> counters;
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> event_pool;
@@ -664,6 +672,27 @@ struct Workspace {
   size_t contrib_n = 0;
 };
 
+/* The sampler's alpha table for renders of this depth becomes the scene's current one (ptx_scene.alpha): looked up, or made and
+ * uploaded the first time the dimension is asked for */
+int use_alpha_table(ptx_scene* s, int max_bounces) {
+  const int dim = 2 + 2 * std::max(max_bounces, 0);
+  double* table = nullptr;
+  for (const auto& t : s->alpha_tables)
+    if (t.first == dim) table = t.second;
+  if (!table) {
+    const std::vector<double> alpha = lds_alpha(dim); /* create_sampler, integrator.ml:89 */
+    HIP_TRY(hipMalloc((void**)&table, sizeof(double) * (size_t)dim));
+    /* uploaded first, cached on success only: a table whose upload failed must not be found by the next render of this depth */
+    if (hipMemcpy(table, alpha.data(), sizeof(double) * (size_t)dim, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(table);
+      return fail(PTX_ERR_HIP, "uploading the sampler's alpha table (%d dimensions) failed", dim);
+    }
+    s->alpha_tables.emplace_back(dim, table); /* owned from here on (freed by ptx_scene_destroy) */
+  }
+  s->alpha.p = table;
+  return 0;
+}
+
 int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, int set = 0, bool want_hit_records = false) {
   ptx_scene::WorkBufs& b = s->wb[set];
   const size_t cap_paths = cap;
@@ -693,21 +722,8 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
   HIP_TRY(b.susp.ensure((size_t)s->n_cu * 4 * 16 * PT_WAVE * 3));
   HIP_TRY(s->counters.ensure(1));
   { /* (every set: a cached lookup) */
-    const int dim = 2 + 2 * std::max(max_bounces, 0);
-    double* table = nullptr;
-    for (const auto& t : s->alpha_tables)
-      if (t.first == dim) table = t.second;
-    if (!table) {
-      const std::vector<double> alpha = lds_alpha(dim); /* create_sampler, integrator.ml:89 */
-      HIP_TRY(hipMalloc((void**)&table, sizeof(double) * (size_t)dim));
-      /* uploaded first, cached on success only: a table whose upload failed must not be found by the next render of this depth */
-      if (hipMemcpy(table, alpha.data(), sizeof(double) * (size_t)dim, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(table);
-        return fail(PTX_ERR_HIP, "uploading the sampler's alpha table (%d dimensions) failed", dim);
-      }
-      s->alpha_tables.emplace_back(dim, table); /* owned from here on (freed by ptx_scene_destroy) */
-    }
-    s->alpha.p = table;
+    const int rc = use_alpha_table(s, max_bounces);
+    if (rc) return rc;
   }
   /* views must use the capacity the buffers were SIZED with */
   b.qa.cap = b.qa.ray.n;
@@ -2437,6 +2453,246 @@ int32_t ptx_render_adaptive(ptx_scene* s, const ptx_render_params* p_in, const p
   p.n_gpus = 0;
   HIP_TRY(hipSetDevice(s->device));
   AdaptivePolicy pol{s, p, *ap, rgb_out, err_out, passes_out, on_round, user};
+  return render_updates(s, p, pol, true, rgb_out, err_out, stats);
+}
+
+/* ---- first-hit feature sums and the a-trous denoiser (kernels: denoise.inc; the rule: include/ptx.h) ---- */
+namespace {
+/* Passes [pass_first, pass_first + pass_count) of the frame's camera rays -> d_feat, queued on st.  A batch of passes is one PRIMARY
+ * launch of the unchanged k_trace (launch_trace: LDS-resident scenes and scenes walked from HBM / L2 alike; the camera rays are
+ * never written anywhere) that keeps slot and distance per entry, then k_features, which computes every ray again and adds the
+ * batch's records per pixel in pass order.  12 bytes per sample in flight; the batches of a call run one after the other. */
+int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int pass_count, double* d_feat, hipStream_t st) {
+  const int tiles_x = (p->width + 7) / 8, tiles_y = (p->height + 7) / 8;
+  const unsigned long long padded = (unsigned long long)tiles_x * (unsigned long long)tiles_y * 64ull; /* entries of one pass */
+  if (padded >= 0xffffffffull) return fail(PTX_ERR_ARG, "too many pixels for one feature pass");
+  long long ppb = p->passes_per_batch > 0 ? p->passes_per_batch : std::max<long long>(1, (16ll << 20) / (long long)padded);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) /* 12 bytes of hit record per entry: below a quarter of what is free */
+    ppb = std::min<long long>(ppb, std::max<long long>(1, (long long)(free_b / 4 / 12 / padded)));
+  ppb = std::max<long long>(1, std::min<long long>(ppb, pass_count));
+  while (ppb > 1 && (unsigned long long)ppb * padded >= 0xffffffffull) --ppb; /* entry indices are 32-bit */
+  const size_t cap = (size_t)ppb * (size_t)padded;
+  HIP_TRY(s->feat_slot.ensure(cap));
+  if (!s->dev.has_triangles) HIP_TRY(s->feat_t.ensure(cap));
+  HIP_TRY(s->feat_work.ensure(8));
+  HIP_TRY(s->feat_susp.ensure((size_t)s->n_cu * 4 * 16 * PT_WAVE * 3)); /* as a workspace set's (ensure_workspace) */
+  HIP_TRY(s->counters.ensure(1));
+  int rc = use_alpha_table(s, p->max_bounces);
+  if (rc) return rc;
+  const double* alpha = s->alpha.p;
+  PtHits h{};
+  h.t = s->dev.has_triangles ? nullptr : s->feat_t.p; /* with triangles k_features recomputes (t, u, v), as a render's shade step does */
+  h.slot = s->feat_slot.p;
+  for (int first = pass_first; first < pass_first + pass_count; first += (int)ppb) {
+    const int n_pass = std::min<int>((int)ppb, pass_first + pass_count - first);
+    PrimaryLaunch pl;
+    pl.on = true;
+    PtGenParams& g = pl.g;
+    g.width = p->width; g.height = p->height; g.spp = p->samples_per_pixel; g.local_rows = p->height;
+    g.band_rows = 32; g.band_first = 0; g.band_step = 0;
+    g.tiles_x = tiles_x; g.tiles_y = tiles_y;
+    g.first_pass = first; g.n_pass = n_pass;
+    pl.n = (uint32_t)((unsigned long long)n_pass * padded);
+    HIP_TRY(hipMemsetAsync(s->feat_work.p, 0, sizeof(uint32_t) * 8, st));
+    s->cur_bounce = 0;
+    s->cur_susp = s->feat_susp.p;
+    launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, pl);
+    hipLaunchKernelGGL(k_features, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+int check_denoise_params(const ptx_denoise_params* d) {
+  if (d->levels < 0 || d->levels > 8) return fail(PTX_ERR_ARG, "levels must be in [0, 8] (got %d)", d->levels);
+  if (d->normal_power_log2 < 0 || d->normal_power_log2 > 8)
+    return fail(PTX_ERR_ARG, "normal_power_log2 must be in [0, 8] (got %d)", d->normal_power_log2);
+  if (d->feature_passes < 0) return fail(PTX_ERR_ARG, "feature_passes must be >= 0 (got %d)", d->feature_passes);
+  if (d->flags & ~PTX_DENOISE_DEMODULATE) return fail(PTX_ERR_ARG, "unknown bits in the denoiser's flags (0x%x)", (unsigned)d->flags);
+  const double sg[3] = {d->sigma_luminance, d->sigma_depth, d->sigma_albedo};
+  for (double v : sg)
+    if (!(v > 0.0) || !std::isfinite(v)) return fail(PTX_ERR_ARG, "sigma_luminance, sigma_depth and sigma_albedo must be > 0 and finite (got %g)", v);
+  return 0;
+}
+
+/* prepare, one k_atrous per level, finish, queued on st; guide holds W*H*8 doubles, cv0 and cv1 W*H*4 each (the levels' ping-pong) */
+int denoise_queue(int width, int height, const ptx_denoise_params& d, int k, const int32_t* d_passes, int kf, const double* d_raw,
+                  const double* d_err, const double* d_feat, double* guide, double* cv0, double* cv1, double* d_out, hipStream_t st) {
+  const long long npix = (long long)width * height;
+  if (d.levels == 0) {
+    HIP_TRY(hipMemcpyAsync(d_out, d_raw, sizeof(double) * (size_t)npix * 3, hipMemcpyDeviceToDevice, st));
+    return 0;
+  }
+  PtDenoise dn;
+  dn.width = width; dn.height = height; dn.m = d.normal_power_log2; dn.demodulate = (d.flags & PTX_DENOISE_DEMODULATE) ? 1 : 0;
+  dn.sl2 = d.sigma_luminance * d.sigma_luminance; dn.sz = d.sigma_depth; dn.sa2 = d.sigma_albedo * d.sigma_albedo;
+  const dim3 lin((unsigned)((npix + 255) / 256)), tiles((unsigned)((width + PT_ATROUS_TX - 1) / PT_ATROUS_TX), (unsigned)((height + PT_ATROUS_TY - 1) / PT_ATROUS_TY));
+  double4* cv[2] = {(double4*)cv0, (double4*)cv1};
+  hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, st, dn, k, d_passes, (double)kf, d_raw, d_err, d_feat, (PtGuide*)guide, cv[0]);
+  /* how a level fetches its taps: the tile and its halo through LDS at steps <= PTX_ATROUS_LDS (0 .. PT_ATROUS_LDS_STEP), gathers
+   * through L1 / L2 above -- the same bits either way.  Default 1: measured, the LDS copy wins at step 1 and ties at step 2
+   * (DESIGN.md section 8, tools/denoise_cost.py) */
+  const int lds_steps = std::max(0, std::min(PT_ATROUS_LDS_STEP, env_int("PTX_ATROUS_LDS", 1)));
+  for (int l = 0; l < d.levels; ++l) {
+    const int step = 1 << l;
+    auto kern = step <= lds_steps ? k_atrous<true> : k_atrous<false>;
+    hipLaunchKernelGGL(kern, tiles, dim3(PT_ATROUS_TX * PT_ATROUS_TY), 0, st, dn, step, (const PtGuide*)guide, (const double4*)cv[l & 1], cv[(l + 1) & 1]);
+  }
+  hipLaunchKernelGGL(k_denoise_finish, lin, dim3(256), 0, st, dn, k, d_passes, (const PtGuide*)guide, (const double4*)cv[d.levels & 1], d_out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int32_t ptx_render_features_device(ptx_scene* s, const ptx_render_params* p, int32_t pass_first, int32_t pass_count,
+                                   double* d_feat_inout, void* stream, ptx_stats* stats) {
+  int rc = check_render_args(s, p, d_feat_inout ? nullptr : "d_feat_inout is NULL");
+  if (rc) return rc;
+  rc = check_one_gpu(p, "a feature pass");
+  if (rc) return rc;
+  rc = check_pass_range(p, pass_first, pass_count);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  RenderBusy busy(s);
+  const double t0 = wall_ms();
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    fill_tree_stats(s, stats);
+  }
+  rc = features_queue(s, p, pass_first, pass_count, d_feat_inout, (hipStream_t)stream);
+  if (rc) {
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    return rc;
+  }
+  if (!(p->flags & PTX_RENDER_ASYNC)) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (stats) {
+    stats->samples = (int64_t)p->width * p->height * pass_count;
+    stats->render_ms = wall_ms() - t0;
+  }
+  return 0;
+}
+
+int32_t ptx_denoise_defaults(ptx_denoise_params* out) {
+  if (!out) return fail(PTX_ERR_ARG, "NULL argument");
+  out->levels = 5;
+  out->normal_power_log2 = 5;
+  out->feature_passes = 8;
+  out->flags = PTX_DENOISE_DEMODULATE;
+  out->sigma_luminance = 4.0;
+  out->sigma_depth = 0.05;
+  out->sigma_albedo = 0.2;
+  return 0;
+}
+
+int32_t ptx_denoise_device(int32_t device, int32_t width, int32_t height, const ptx_denoise_params* d, int32_t passes_done,
+                           const int32_t* d_passes, int32_t feature_passes_done, const double* d_raw, const double* d_err,
+                           const double* d_feat, double* d_raw_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the denoiser runs on a HIP device only, no CPU fallback exists", device);
+  if (!d || !d_raw || !d_err || !d_feat || !d_raw_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (d_raw_out == d_raw) return fail(PTX_ERR_ARG, "d_raw_out must not be d_raw");
+  if (width <= 0 || height <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, height);
+  int rc = check_denoise_params(d);
+  if (rc) return rc;
+  if (!d_passes && passes_done < 2) return fail(PTX_ERR_ARG, "passes_done must be >= 2 (got %d): the error of fewer passes is infinite", passes_done);
+  if (feature_passes_done < 1) return fail(PTX_ERR_ARG, "feature_passes_done must be >= 1 (got %d)", feature_passes_done);
+  rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  const size_t npix = (size_t)width * (size_t)height;
+  LocalBuf<double> guide, cv0, cv1;
+  if (d->levels > 0) {
+    HIP_TRY(guide.ensure(npix * 8));
+    HIP_TRY(cv0.ensure(npix * 4));
+    HIP_TRY(cv1.ensure(npix * 4));
+  }
+  rc = denoise_queue(width, height, *d, passes_done, d_passes, feature_passes_done, d_raw, d_err, d_feat, guide.p, cv0.p, cv1.p, d_raw_out,
+                     (hipStream_t)stream);
+  const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* (also on an error: the scratch buffers go with this frame) */
+  if (rc) return rc;
+  HIP_TRY(e);
+  return 0;
+}
+
+namespace {
+/* ptx_render_denoised as render_updates sees it: ProgressivePolicy with the squares always kept, a feature slice beside every slice
+ * while it starts below F, and an update that films the DENOISED sums */
+struct DenoisePolicy {
+  ptx_scene* s;
+  const ptx_render_params& p;
+  const ptx_progressive_params& pp;
+  const ptx_denoise_params& dp;
+  double *rgb_out, *err_out, *feat_out;
+  int32_t* passes_done_out;
+  ptx_update_fn on_update;
+  void* user;
+  long long npix() const { return (long long)p.width * p.height; }
+  int feature_end() const { return dp.feature_passes > 0 ? std::min(dp.feature_passes, p.samples_per_pixel) : p.samples_per_pixel; }
+  PassRange slice(int first) const {
+    return PassRange(first, std::min(pp.passes_per_update, p.samples_per_pixel - first), first == 0, s->sq.p);
+  }
+  int prepare() {
+    const size_t n = (size_t)npix();
+    HIP_TRY(s->err.ensure(n * 3)); /* the filter's input, whether the caller wants it or not */
+    HIP_TRY(s->feat.ensure(n * 8));
+    if (feat_out) HIP_TRY(s->feat_mean.ensure(n * 8));
+    HIP_TRY(s->den_raw.ensure(n * 3));
+    HIP_TRY(s->den_guide.ensure(n * 8));
+    HIP_TRY(s->den_cv[0].ensure(n * 4));
+    HIP_TRY(s->den_cv[1].ensure(n * 4));
+    HIP_TRY(hipMemsetAsync(s->feat.p, 0, sizeof(double) * n * 8, nullptr));
+    return 0;
+  }
+  PassRange first() const { return slice(0); }
+  int queue_update(const PassRange& cur) {
+    const int k = cur.first + cur.count, F = feature_end(), kf = std::min(F, k);
+    int rc = 0;
+    if (cur.first < F) rc = features_queue(s, &p, cur.first, kf - cur.first, s->feat.p, nullptr);
+    if (!rc) rc = pixel_error_queue(npix(), k, nullptr, s->raw.p, s->sq.p, s->err.p, s->err_partials.p, nullptr);
+    if (!rc) rc = denoise_queue(p.width, p.height, dp, k, nullptr, kf, s->raw.p, s->err.p, s->feat.p, s->den_guide.p, s->den_cv[0].p, s->den_cv[1].p,
+                                s->den_raw.p, nullptr);
+    if (!rc) rc = film_resolve(p.width, p.height, k, s->den_raw.p, s->rgb.p, nullptr);
+    if (rc || !feat_out) return rc;
+    const long long n = npix() * 8;
+    hipLaunchKernelGGL(k_feature_means, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)s->feat.p, n, (double)kf, s->feat_mean.p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  int next_slice(const PassRange& cur, PassRange* next) {
+    *next = slice(cur.first + cur.count);
+    return 0;
+  }
+  int copy_extras(hipStream_t cs) {
+    if (feat_out) HIP_TRY(hipMemcpyAsync(feat_out, s->feat_mean.p, sizeof(double) * (size_t)npix() * 8, hipMemcpyDeviceToHost, cs));
+    return 0;
+  }
+  bool call_back(int, const PassRange& cur, const PassRange&, int64_t, double rel) {
+    const int k = cur.first + cur.count;
+    if (passes_done_out) *passes_done_out = k;
+    const bool stop = on_update && on_update(user, k, rel, rgb_out, err_out) != 0;
+    return stop || (pp.target_rel_err > 0.0 && rel <= pp.target_rel_err);
+  }
+};
+}  // namespace
+
+int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, const ptx_denoise_params* dp,
+                            double* rgb_out, double* err_out, double* feat_out, int32_t* passes_done_out, ptx_stats* stats,
+                            ptx_update_fn on_update, void* user) {
+  int rc = check_render_args(s, p_in, (pp && dp && rgb_out) ? nullptr : "NULL argument");
+  if (rc) return rc;
+  rc = check_one_gpu(p_in, "denoised rendering");
+  if (rc) return rc;
+  if (pp->passes_per_update < 2) return fail(PTX_ERR_ARG, "passes_per_update must be >= 2 (got %d): the filter needs the error of every update", pp->passes_per_update);
+  if (p_in->samples_per_pixel < 2) return fail(PTX_ERR_ARG, "samples_per_pixel must be >= 2 (got %d): the error of one pass is infinite", p_in->samples_per_pixel);
+  if (!(pp->target_rel_err >= 0.0)) return fail(PTX_ERR_ARG, "target_rel_err must be >= 0 (got %g)", pp->target_rel_err);
+  rc = check_denoise_params(dp);
+  if (rc) return rc;
+  if (passes_done_out) *passes_done_out = 0;
+  ptx_render_params p = *p_in;
+  p.band_step = 0; /* whole image on this GPU */
+  p.n_gpus = 0;
+  HIP_TRY(hipSetDevice(s->device));
+  DenoisePolicy pol{s, p, *pp, *dp, rgb_out, err_out, feat_out, passes_done_out, on_update, user};
   return render_updates(s, p, pol, true, rgb_out, err_out, stats);
 }
 

@@ -12,6 +12,9 @@
 // (with --progressive=K passes per round and --min-passes=M): per-pixel pass counts, ptx_render_adaptive.
 // --lighting=reference|path-order|sampled: the scene's lighting mode (ptx_scene_set_lighting); --lamp=HALF_SIDE,Y,EMIT (with
 // --scene=cornell): a square lamp of that half side and emission at height Y (pth_scene_cornell_lamp).
+// --denoise[=LEVELS]: the image of every update filtered by the variance-guided a-trous denoiser (ptx_render_denoised; with
+// --progressive=K an update every K passes, without it one update after the last pass); --aov=PREFIX (with --denoise) also writes the
+// first-hit feature means as PREFIX-albedo.png, PREFIX-normal.png (n / 2 + 1 / 2) and PREFIX-depth.png (z / max z).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +47,8 @@ struct Args {
   int lighting = PTX_LIGHTING_REFERENCE; // --lighting
   bool have_lamp = false;                // --lamp=HALF_SIDE,Y,EMIT
   double lamp_half_side = 0.0, lamp_y = 0.0, lamp_emit = 0.0;
+  int denoise = -1;                      // --denoise[=LEVELS]: a-trous levels (< 0: no denoiser)
+  std::string aov;                       // --aov=PREFIX
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -53,7 +58,8 @@ struct Args {
                "          [--max-ray-bounces=INT] [--no-simd] [--scene=shirley|cornell|ganesha] [--device=INT] [--gpus=INT]\n"
                "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
                "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
-               "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n",
+               "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
+               "          [--denoise[=LEVELS]] [--aov=PREFIX]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -118,6 +124,16 @@ Args parse(int argc, char** argv) {
       if (!(a.lamp_half_side > 0.0) || !(a.lamp_emit > 0.0) || !(a.lamp_y == a.lamp_y)) usage(argv[0], "invalid value for --lamp, HALF_SIDE and EMIT must be > 0");
       a.have_lamp = true;
     }
+    else if (!std::strcmp(argv[i], "--denoise")) a.denoise = 5; // ptx_denoise_defaults' levels
+    else if (!std::strncmp(argv[i], "--denoise=", 10)) {
+      char* end = nullptr;
+      const long l = std::strtol(argv[i] + 10, &end, 10);
+      if (end == argv[i] + 10 || *end || l < 0 || l > 8) usage(argv[0], "invalid value for --denoise, LEVELS must be in 0..8");
+      a.denoise = (int)l;
+    } else if (take_value(argc, argv, i, "aov", nullptr, &v)) {
+      if (v.empty()) usage(argv[0], "invalid value for --aov, expected a file name prefix");
+      a.aov = v;
+    }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
     else if (!std::strcmp(argv[i], "--no-simd")) a.no_simd = true;
@@ -138,6 +154,11 @@ Args parse(int argc, char** argv) {
   if (a.target_error > 0.0 && !a.progressive) usage(argv[0], "--target-error requires --progressive");
   if (a.progressive && a.gpus > 1) usage(argv[0], "--progressive renders on one GPU (--gpus=1)");
   if (a.have_lamp && a.scene != "cornell") usage(argv[0], "--lamp requires --scene=cornell");
+  if (!a.aov.empty() && a.denoise < 0) usage(argv[0], "--aov requires --denoise");
+  if (a.denoise >= 0 && adaptive) usage(argv[0], "--denoise cannot be combined with --adaptive");
+  if (a.denoise >= 0 && a.gpus > 1) usage(argv[0], "--denoise renders on one GPU (--gpus=1)");
+  if (a.denoise >= 0 && a.samples_per_pixel < 2) usage(argv[0], "--denoise requires --samples-per-pixel >= 2");
+  if (a.denoise >= 0 && a.progressive == 1) usage(argv[0], "--denoise requires --progressive >= 2");
   return a;
 }
 
@@ -191,6 +212,23 @@ int32_t on_round(void* user, int32_t round, int32_t passes_done, int64_t active_
     return 1;
   }
   return 0;
+}
+
+// --aov: the feature means (8 doubles per pixel: albedo, normal, depth, hits) as three PNGs
+int write_aovs(const std::string& prefix, int width, int height, const std::vector<double>& feat) {
+  const size_t npix = (size_t)width * height;
+  std::vector<double> img(npix * 3);
+  for (size_t p = 0; p < npix; ++p)
+    for (int c = 0; c < 3; ++c) img[3 * p + c] = feat[8 * p + c];
+  if (pth_write_png((prefix + "-albedo.png").c_str(), width, height, img.data()) != 0) return -1;
+  for (size_t p = 0; p < npix; ++p)
+    for (int c = 0; c < 3; ++c) img[3 * p + c] = feat[8 * p + 3 + c] * 0.5 + 0.5;
+  if (pth_write_png((prefix + "-normal.png").c_str(), width, height, img.data()) != 0) return -1;
+  double zmax = 0.0;
+  for (size_t p = 0; p < npix; ++p) zmax = feat[8 * p + 6] > zmax ? feat[8 * p + 6] : zmax;
+  for (size_t p = 0; p < npix; ++p)
+    for (int c = 0; c < 3; ++c) img[3 * p + c] = zmax > 0.0 ? feat[8 * p + 6] / zmax : 0.0;
+  return pth_write_png((prefix + "-depth.png").c_str(), width, height, img.data()) != 0 ? -1 : 0;
 }
 
 }  // namespace
@@ -264,6 +302,23 @@ int main(int argc, char** argv) {
     ap.target_rel_err = a.adaptive;
     ap.radiance_floor = 1e-3;
     rc = ptx_render_adaptive(scene, &p, &ap, rgb.data(), nullptr, nullptr, &st, on_round, &upd);
+  } else if (a.denoise >= 0) {
+    ptx_progressive_params pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.passes_per_update = a.progressive ? a.progressive : a.samples_per_pixel; // without --progressive: one update, after the last pass
+    pp.want_error = 1;
+    pp.target_rel_err = a.target_error;
+    ptx_denoise_params dn;
+    ptx_denoise_defaults(&dn);
+    dn.levels = a.denoise;
+    std::vector<double> feat(a.aov.empty() ? 0 : (size_t)a.width * a.height * PTX_FEATURE_DOUBLES);
+    int32_t passes_done = 0;
+    rc = ptx_render_denoised(scene, &p, &pp, &dn, rgb.data(), nullptr, feat.empty() ? nullptr : feat.data(), &passes_done, &st, on_update,
+                             &upd);
+    if (rc == 0 && !feat.empty() && write_aovs(a.aov, a.width, a.height, feat) != 0) {
+      std::fprintf(stderr, "cannot write %s-*.png\n", a.aov.c_str());
+      return 1;
+    }
   } else if (a.progressive) {
     ptx_progressive_params pp;
     std::memset(&pp, 0, sizeof pp);
@@ -278,7 +333,7 @@ int main(int argc, char** argv) {
   (void)ptx_image_unpin(scene);
   const double elapsed = now_ms() - t0;
   if (rc != 0) {
-    std::fprintf(stderr, "%s: %s\n", adaptive ? "ptx_render_adaptive" : a.progressive ? "ptx_render_progressive" : "ptx_render",
+    std::fprintf(stderr, "%s: %s\n", adaptive ? "ptx_render_adaptive" : a.denoise >= 0 ? "ptx_render_denoised" : a.progressive ? "ptx_render_progressive" : "ptx_render",
                  ptx_last_error());
     return 1;
   }

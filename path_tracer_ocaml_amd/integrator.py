@@ -67,6 +67,7 @@ class Integrator:
         self.stats = None
         self.error = self.passes_done = None  # render_progressive
         self.passes = None  # render_adaptive
+        self.features = None  # render_denoised
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None):
@@ -103,6 +104,20 @@ class Integrator:
         if out is None:
             self.image[...] = rgb
         self.error, self.passes, self.stats = err, passes, st
+        return self.image
+
+    def render_denoised(self, passes_per_update, denoise=None, on_update=None, target_rel_err=0.0, want_features=False):
+        """``render`` as a sequence of DENOISED updates (Scene.render_denoised): ``image`` holds the filtered image of the last
+        update, ``error`` the un-denoised per-pixel standard error, ``passes_done`` its passes and ``features`` the first-hit
+        feature means ((H, W, 8): albedo, normal, depth, hits) when want_features is set."""
+        out = self.image if self.image.flags["C_CONTIGUOUS"] else None
+        rgb, err, feat, done, st = self._scene.render_denoised(self.width, self.height, self.samples_per_pixel, self.max_bounces,
+                                                               passes_per_update, denoise=denoise, on_update=on_update,
+                                                               target_rel_err=target_rel_err, out=out,
+                                                               feat_out=True if want_features else None)
+        if out is None:
+            self.image[...] = rgb
+        self.error, self.passes_done, self.features, self.stats = err, done, feat, st
         return self.image
 
 
