@@ -18,7 +18,8 @@
  * Both walks are stackless and their links TAGGED: a visit ends with one select between "what a hit leads to" and "what a miss leads
  * to", and the walk's control state -- wants a node, holds a leaf, over -- lives in the link's spare bits (PT_SWZ_TAG_* on the LDS
  * image, the top two bits of a word on the per-octant record).  On Simd_leaf scenes in LDS the node loop itself is gfx950 assembly
- * (PtTraverser::walk_asm); everything else is HIP C++.
+ * (PtTraverser::walk_asm); everything else is HIP C++.  What lies where in a kernel's dynamic LDS buffer -- stacks, the scene image,
+ * pools, parked walks -- and which scenes get an LDS copy at all is stated once, in pt_lds_layout.h, for these kernels and the host.
  *
  * Compiled with -ffp-contract=off; every fused multiply-add below is written out exactly where the
  * reference writes Float.fma / _mm256_fmadd_pd.  No MFMA: there is no dense contraction on this path.
@@ -27,6 +28,7 @@
 
 #include <type_traits>
 
+#include "pt_lds_layout.h"
 #include "pt_scene.h"
 #include "pt_vec.h"
 
@@ -68,13 +70,10 @@ struct PtHits {
    * t + (b & 1) * t_parity_stride there (0: `t` holds one array only and no launch runs solo). */
   size_t t_parity_stride;
 };
-#ifndef PT_RECOMPUTE_HIT
-#define PT_RECOMPUTE_HIT 1
-#endif
 __device__ __forceinline__ void pt_hit_store(const PtHits& hits, uint32_t i, double t, int slot, double u, double v, bool with_uv) {
   hits.slot[i] = slot;
   if (with_uv) {
-    if (!PT_RECOMPUTE_HIT || hits.tuv) hits.tuv[i] = make_double4(t, u, v, 0.0);
+    if (hits.tuv) hits.tuv[i] = make_double4(t, u, v, 0.0);
   } else hits.t[i] = t;
 }
 
@@ -337,22 +336,15 @@ __device__ __forceinline__ bool pt_slab_hit_exact(const double* nb, V3 o, V3 inv
  * max|1/d| > 2^-60 (else: always binary64):
  *   t~ = fma32(bound32, inv32, -(o * inv)32) differs from the reference's fl64((bound - o) * inv) by at most
  *        3.2 * 2^-24 * (|bound| + |o|) * |inv|  <=  M := 3.2 * 2^-24 * (mag + max|o|) * max|inv|
- *   (three binary32 roundings of the inputs, one of the fma, the reference's own two binary64 roundings; with PT_F32_INV,
- *   where inv32 and (o inv)32 are computed in binary32 from the start: 6 instead of 3.2, see PtTraverser::begin);
+ *   (three binary32 roundings of the inputs, one of the fma, the reference's own two binary64 roundings; as built,
+ *   with inv32 and (o inv)32 computed in binary32 from the start: 6 instead of 3.2, see PtTraverser::begin);
  *   max / min are 1-Lipschitz, so lo~ = max(0, a~) and hi~ = min(b~, t32) are within M (+ 2^-24 t for the rounded
  *   closest-hit distance) of the reference's lo, hi, and u = hi~ - lo~ (one more rounding) within 8.4 * 2^-24 * (..)
  *   + 2^-24 t of hi - lo.  With m2 = 2^-19 * (mag + max|o|) * max|inv| + 2^-21 * t32  (twice that bound):
  *        u >= m2  =>  lo <= hi (hit)        u <= -m2  =>  lo > hi (miss)        otherwise (|u| < m2 or unordered): binary64.
  * The undecided share is ~4 m2 / (hi - lo spread) ~ 1e-5 per test, scale-free because mag is the node's own. */
-#ifndef PT_SWZ_NEAR
-#define PT_SWZ_NEAR 1 /* 1: the LDS image also carries, per direction octant, the child the walk descends into (64-byte nodes) */
-#endif
-#ifndef PT_SWZ_SIGNSEL
-#define PT_SWZ_SIGNSEL 1 /* needs PT_SWZ_NEAR.  1: 80-byte nodes whose bounds are stored as (mn, mx, mn) per axis, node references are
-                            absolute LDS addresses */
-#endif
-#if PT_SWZ_NEAR && PT_SWZ_SIGNSEL
-/* Layout 3 (this one).  The vector pipe is what the walk is bound by, so the image is arranged to take instructions out of a
+/* Layout 3 (layouts 1 and 2 -- 48-byte nodes, 64-byte nodes with the near-child table -- were its A/B partners and are gone from
+ * the source).  The vector pipe is what the walk is bound by, so the image is arranged to take instructions out of a
  * visit:
  *   bytes  0..35  per axis a: mn_a, mx_a, mn_a (binary32).  A ray reads the PAIR at 12 a + (d_a >= 0 ? 0 : 4): (near, far)
  *                 bound of that axis for its direction sign, so t_near = fma(near, inv, n), t_far = fma(far, inv, n) need no
@@ -373,25 +365,6 @@ typedef const __attribute__((address_space(3))) unsigned char* PtLdsPtr;
 typedef float pt_f2 __attribute__((ext_vector_type(2), aligned(4)));
 typedef unsigned int pt_u2 __attribute__((ext_vector_type(2), aligned(4)));
 #define PT_LDS_AT(addr) ((PtLdsPtr)(uintptr_t)(uint32_t)(addr))
-#elif PT_SWZ_NEAR
-/*   words 12..15 near[8], u16 each: for octant o the NEAR child of a branch (shape_tree.ml:209: lhs if bit `axis` of o is set,
- *               else rhs), PT_SWZ_LEAF for a leaf.  With it a visit needs no axis extraction, no bit test and no child select:
- *               next = hit an inner node ? near[o] : skip[o]. */
-#undef PT_SWZ_NODE_BYTES
-#define PT_SWZ_NODE_BYTES 64
-#define PT_SWZ_OFF_LINKS 24
-#define PT_SWZ_OFF_SKIP 32
-#define PT_SWZ_OFF_NEAR 48
-#undef PT_SWZ_SIGNSEL
-#define PT_SWZ_SIGNSEL 0
-#else
-#undef PT_SWZ_NODE_BYTES
-#define PT_SWZ_NODE_BYTES 48
-#define PT_SWZ_OFF_LINKS 24
-#define PT_SWZ_OFF_SKIP 32
-#undef PT_SWZ_SIGNSEL
-#define PT_SWZ_SIGNSEL 0
-#endif
 #define PT_SWZ_LEAF 0xfffeu
 /* Layout 3: TAGGED links (round 5).  Node addresses are multiples of 4, so the two low bits of a 16-bit link are free:
  *   tag 0  a node to visit                       tag 1  "this lane holds a leaf; afterwards continue at link & ~3"
@@ -401,25 +374,12 @@ typedef unsigned int pt_u2 __attribute__((ext_vector_type(2), aligned(4)));
  * finished <=> node == PT_SWZ_END.  The leaf's (first slot, real count) word stays in the register the visit loaded it into
  * (`lkx`) until the leaf phase decodes it.  Before: a leaf compare, two conditional updates of (leaf_first, leaf_n), the END
  * compare, the conditional update of `node` and the (walking > leaf_n) compare -- 9 of a visit's 27 vector instructions. */
-#ifndef PT_SWZ_TAGGED
-#define PT_SWZ_TAGGED 1 /* (0: the untagged links of round 4, for the A/B) */
-#endif
 #define PT_SWZ_TAG_LEAF 1u
 #define PT_SWZ_TAG_END 2u
-/* doubles per sphere slot in the LDS copy: 4 used ({x, y, z, r}) + padding.  With 4 (8 words) a slot starts in 8 of the 64 banks
- * only; with 6 (12 words) in 16.  Global memory keeps 4. */
-#ifndef PT_LDS_SPH_DOUBLES
-#define PT_LDS_SPH_DOUBLES 4
-#endif
-#define PT_SPH_STRIDE(SWZ_) ((SWZ_) ? PT_LDS_SPH_DOUBLES : 4)
-#if PT_SWZ_SIGNSEL && PT_SWZ_TAGGED
 #define PT_SWZ_END 0xfffeu /* tag 2 (see PT_SWZ_TAG_*) */
-#else
-#define PT_SWZ_END 0xffffu
-#endif
-/* bytes of LDS a wave keeps for traversal stacks: LDS-resident scenes walk the threaded image (no per-lane stack) and
- * only the camera-ray packet walk keeps its shared (node, mask) stack there: 12 bytes per level, rounded to 16 */
-#define PT_WAVE_STACK_BYTES(LDS_SCENE, StackT, depth) ((LDS_SCENE) ? (size_t)(depth) * 16u : ((std::is_same<StackT, PtThreadTag>::value || std::is_same<StackT, PtThreadOctTag>::value) ? (size_t)0 : (size_t)(depth) * PT_WAVE * sizeof(StackT)))
+/* (A sphere slot is 4 doubles, {x, y, z, r}, in the LDS copy as in global memory: padding it to 6 -- a slot then starts in 16 of the
+ * 64 banks instead of 8 -- was measured, no gain: profiles/r05_ab_sphere_stride.txt.) */
+/* (what lies where in the dynamic LDS buffer -- the per-wave stacks, the scene image, pools, parked walks: pt_lds_layout.h) */
 
 /* where the traversal data of this launch lives: HBM/L2 (large scenes) or an LDS copy (small scenes) */
 /* StackT of a walk that needs no stack: scenes traversed from HBM / L2 follow per-octant skip links like the LDS image
@@ -472,8 +432,8 @@ struct PtSceneView {
   const unsigned char* nodes32o; /* ... per direction octant (PtThreadOctTag), 8 x n_nodes x 32 bytes, or null */
   uint32_t n_nodes;
   const unsigned char* swz_nodes; /* LDS-resident scenes: the binary32 filter image, PT_SWZ_NODE_BYTES per node */
-  uint32_t swz_root;              /* what the walk's `node` is for node 0: 0 (byte offsets into the image) or, with PT_SWZ_SIGNSEL, the
-                                     image's absolute LDS address */
+  uint32_t swz_root;              /* what the walk's `node` is for node 0: the image's absolute LDS address (node references are
+                                     absolute LDS addresses) */
   const unsigned char* top;       /* scenes walked from HBM / L2: the LDS copy of PtSceneDev.top_nodes if has_top (else never dereferenced:
                                      no node reference carries PT_TOP_FLAG) */
   bool has_top;
@@ -517,19 +477,9 @@ __device__ __forceinline__ uint32_t pt_stack_pop(const PtThreadOctTag*, int) { r
 #define PT_WALK_MIN_GLOBAL 16 /* the same threshold for the walk from HBM / L2, where a node step is a round trip to the L2 and the leaf phase's
                                  first loads are the longest waits of the walk: leaves are taken up sooner (ganesha-like frame 4: 28.1, 8: 26.4, 16: 25.8 ms) */
 #endif
-#ifndef PT_LEAF_PREFETCH
-#define PT_LEAF_PREFETCH 1 /* triangle-only scenes walked from HBM / L2: request triangle k + 1 before testing triangle k */
-#endif
 #ifndef PT_MARGIN_K2
 #define PT_MARGIN_K2 0x1.000002p-19f /* the filter's margin m2 = PT_MARGIN_K2 (mag + max|o|) max|1/d| + PT_MARGIN_T t (header comment) */
 #define PT_MARGIN_T 0x1p-21f
-#endif
-#ifndef PT_F32_INV
-#define PT_F32_INV 1 /* the filter's reciprocals by v_rcp_f32 instead of Ray.create's three binary64 divisions (PtTraverser::begin) */
-#endif
-#ifndef PT_WALK_LOOP
-#define PT_WALK_LOOP 0 /* 0: wave-level loop with a `want` ballot per turn; 1: the node walk as one divergent loop (fewer scalar
-                          instructions per turn, but the kernel is bound by VECTOR issue: measured 3 % slower) */
 #endif
 /* PT_DIAG (diagnostic builds only, tools/diag_utilisation.sh): re-purposes the COUNT counters of SECONDARY launches
  * to measure lane utilisation per traversal phase: nodes = useful lane steps, floor = lane slots the wave spent.
@@ -555,12 +505,6 @@ __device__ __forceinline__ uint32_t pt_stack_pop(const PtThreadOctTag*, int) { r
 #ifndef PT_WALK_ASM
 #define PT_WALK_ASM 1 /* k_bounce on LDS scenes: the node loop in assembly (PtTraverser::walk_asm); 0: the compiler's loop */
 #endif
-#ifndef PT_SCAN_ADDC
-#define PT_SCAN_ADDC 1
-#endif
-#ifndef PT_PACKET_DEFER
-#define PT_PACKET_DEFER 1
-#endif
 #define PT_DIAG_WAVE_SLOTS(c) do { if (pt_lane() == __ffsll((long long)__ballot(1)) - 1) (c) += 64; } while (0)
 
 /* One ray's traversal state.  begin() = Ray.create + the per-ray constants; node_step() = one visit of
@@ -584,14 +528,14 @@ struct PtTraverser {
 #if PT_FILTER_DEBUG
   mutable float dbg_u, dbg_m2; /* the binary32 filter's u = hi~ - lo~ and margin m2 of the last box test (OTAG branch) */
 #endif
-  uint32_t sel_x, sel_y, sel_z; /* PT_SWZ_SIGNSEL: byte offsets of the ray's (near, far) bound pairs */
+  uint32_t sel_x, sel_y, sel_z; /* SWZ: byte offsets of the ray's (near, far) bound pairs */
   mutable unsigned long long n_undecided = 0, n_wave_fallbacks = 0; /* COUNT only (ptx_stats.filter_*) */
   double qa, one_over_a;
   PtTraceResult r;
   int sp;
   /* TAGGED (the LDS image, layout 3): `node` carries the walk's control state in its two low bits (PT_SWZ_TAG_*), `walking` and
    * `leaf_n` are not used between the leaf phases; `lkx` = word 6 of the node visited last (a leaf's first slot | real count << 16) */
-  static constexpr bool TAGGED = SWZ && (PT_SWZ_SIGNSEL != 0) && (PT_SWZ_TAGGED != 0);
+  static constexpr bool TAGGED = SWZ;
   static constexpr bool OTAG = OCT; /* the per-octant record: tagged, pre-offset links */
   static constexpr bool TAGS = TAGGED || OTAG;
   uint32_t node;
@@ -620,7 +564,7 @@ struct PtTraverser {
     d = d_;
     /* dirs, shape_tree.ml:201 */
     dirs = (d.x >= 0.0 ? 1u : 0u) | (d.y >= 0.0 ? 2u : 0u) | (d.z >= 0.0 ? 4u : 0u);
-    if (!FILT || !PT_F32_INV) {
+    if (!FILT) {
       inv = v3(1.0 / d.x, 1.0 / d.y, 1.0 / d.z); /* Ray.create, ray.ml:7-10 */
       exact_slab = !(pt_isfinite(inv.x) && pt_isfinite(inv.y) && pt_isfinite(inv.z));
     } else {
@@ -628,18 +572,13 @@ struct PtTraverser {
       exact_slab = false;
     }
     if (FILT) {
-#if PT_SWZ_SIGNSEL
       skip_off = 2u * dirs;
       if (SWZ) { /* where this ray's (near, far) pair of each axis starts inside a node */
         sel_x = (dirs & 1u) ? 0u : 4u;
         sel_y = 12u + ((dirs & 2u) ? 0u : 4u);
         sel_z = 24u + ((dirs & 4u) ? 0u : 4u);
       }
-#else
-      skip_off = PT_SWZ_OFF_SKIP + 2u * dirs;
-#endif
       const double omax = __builtin_fmax(pt_fabs(o.x), __builtin_fmax(pt_fabs(o.y), pt_fabs(o.z)));
-#if PT_F32_INV
       /* The filter's constants straight in binary32: inv32 = v_rcp_f32(fl32(d)) (1 ulp) is within 3 * 2^-24 of 1 / d and
        * (o inv)32 = fl32(fl32(o) inv32) within 5 * 2^-24 of o / d, instead of one rounding each from Ray.create's binary64
        * quotients -- three binary64 divisions per ray (~40 vector instructions of a walk's ~1000) that only the filter used.
@@ -651,10 +590,6 @@ struct PtTraverser {
       fiz = __builtin_amdgcn_rcpf((float)d.z);
       const float fimax = __builtin_fmaxf(__builtin_fabsf(fix), __builtin_fmaxf(__builtin_fabsf(fiy), __builtin_fabsf(fiz)));
       const float fisum = __builtin_fabsf(fix) + __builtin_fabsf(fiy) + __builtin_fabsf(fiz); /* (fmax drops a NaN, a sum keeps it) */
-#else
-      const double ax = pt_fabs(inv.x), ay = pt_fabs(inv.y), az = pt_fabs(inv.z);
-      const double imax = __builtin_fmax(ax, __builtin_fmax(ay, az));
-#endif
       /* every binary32 intermediate stays far inside the format: (mag + |o|) |inv| < 2^100 for every node, because every
        * node lies inside the root box (root_mag = its largest |coordinate|, +inf when that exceeds binary32: such a scene
        * is walked in binary64 throughout), so no product, sum or margin of the filter can overflow, whatever the scene's
@@ -662,19 +597,10 @@ struct PtTraverser {
        * are subnormal -- or flushed to zero, whatever the f32 denormal mode of the code object -- are then wrong by
        * < 2^-126 (mag + |o|) absolute, which m2 >= 2^-19 (mag + |o|) 2^-60 + 1e-30 covers with room to spare. */
       const float fomax = (float)omax; /* (a magnitude beyond binary32 becomes +inf and fails the guard) */
-#if PT_F32_INV
       if (!((sc.root_mag + fomax) * fisum < 0x1p100f) || !(fimax > 0x1p-60f)) exact_slab = true;
       fnx = ORIGIN_ZERO ? 0.0f : -((float)o.x * fix);
       fny = ORIGIN_ZERO ? 0.0f : -((float)o.y * fiy);
       fnz = ORIGIN_ZERO ? 0.0f : -((float)o.z * fiz);
-#else
-      const float fimax = (float)imax;
-      if (!((sc.root_mag + fomax) * fimax < 0x1p100f) || !(fimax > 0x1p-60f)) exact_slab = true;
-      fix = (float)inv.x; fiy = (float)inv.y; fiz = (float)inv.z;
-      fnx = ORIGIN_ZERO ? 0.0f : -(float)(o.x * inv.x);
-      fny = ORIGIN_ZERO ? 0.0f : -(float)(o.y * inv.y);
-      fnz = ORIGIN_ZERO ? 0.0f : -(float)(o.z * inv.z);
-#endif
       k2 = fimax * PT_MARGIN_K2;
       if (OTAG) k2 *= 1.000002f; /* (the node's magnitude is taken from its bounds as they are: test_box) */
       c2base = __builtin_fmaf(fomax * 1.000001f, k2, 1e-30f);
@@ -905,7 +831,6 @@ struct PtTraverser {
         }
         return hit;
       }
-#if PT_SWZ_SIGNSEL
       if (SWZ) { /* nd is the node's absolute LDS address; the ray's sign-selected (near, far) bounds: see the layout */
         const pt_f2 bx = *(const __attribute__((address_space(3))) pt_f2*)PT_LDS_AT(nd + sel_x);
         const pt_f2 by = *(const __attribute__((address_space(3))) pt_f2*)PT_LDS_AT(nd + sel_y);
@@ -937,15 +862,7 @@ struct PtTraverser {
         }
         return hit;
       }
-#endif
-      if (SWZ) { /* nd is the node's BYTE offset in the LDS image */
-        w0 = *(const uint4*)(sv.swz_nodes + nd);
-        w1 = *(const uint4*)(sv.swz_nodes + nd + 16);
-        na = w1.z & 0xffffu;
-        nb = (w1.z >> 16) | ((w1.w & 3u) << 30);
-        n_real = w1.z >> 16; /* meaningful for leaves only */
-        mag = __uint_as_float(w1.w);
-      } else { /* nd is the node's index; 32-byte global image: six binary32 bounds, a, b (leaf b: count | real << 15 | tag) */
+      { /* nd is the node's index; 32-byte global image: six binary32 bounds, a, b (leaf b: count | real << 15 | tag) */
         if (nd & PT_TOP_FLAG) { /* ... or PT_TOP_FLAG | byte offset into the LDS copy of the tree's top: same words */
           const uint4* p = (const uint4*)(sv.top + (nd & (PT_TOP_FLAG - 1u)));
           w0 = p[0];
@@ -983,8 +900,7 @@ struct PtTraverser {
           if (pt_lane() == __ffsll((long long)__ballot(1)) - 1) n_wave_fallbacks++;
         }
         /* the reference's arithmetic, on the binary64 node (global memory: L2-resident, rarely read) */
-        hit = slab64(sv.nodes + (SWZ ? nd / PT_SWZ_NODE_BYTES
-                                     : ((nd & PT_TOP_FLAG) ? *(const uint32_t*)(sv.top + (nd & (PT_TOP_FLAG - 1u)) + 48) : nd)));
+        hit = slab64(sv.nodes + ((nd & PT_TOP_FLAG) ? *(const uint32_t*)(sv.top + (nd & (PT_TOP_FLAG - 1u)) + 48) : nd));
       }
     } else {
       const PtNode* np = sv.nodes + nd;
@@ -1017,53 +933,30 @@ struct PtTraverser {
     /* threaded image: where to go once this subtree is done (issued beside the node's own reads) */
     constexpr bool THREAD32 = G32;
     uint32_t skip;
-#if PT_SWZ_SIGNSEL
     if (SWZ) {
       skip = (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)PT_LDS_AT(node + skip_off + PT_SWZ_OFF_SKIP);
-      if (TAGGED) asm("" : "+v"(skip)); /* (a zero-extended 16-bit load the select below need not mask again) */
+      asm("" : "+v"(skip)); /* (a zero-extended 16-bit load the select below need not mask again) */
     }
-#else
-    if (SWZ) skip = (uint32_t)*(const uint16_t*)(sv.swz_nodes + node + skip_off);
-#endif
     else if (!THREAD32) skip = 0u;
     else if (node & PT_TOP_FLAG) { /* top image: 16-bit byte offsets, a top node's successor is a top node */
       const uint32_t s16 = (uint32_t)*(const uint16_t*)(sv.top + (node & (PT_TOP_FLAG - 1u)) + 32u + 2u * dirs);
       skip = s16 == 0xffffu ? 0xffffffffu : (PT_TOP_FLAG | s16);
     } else skip = sv.skip32[(size_t)node * 8u + dirs];
-#if PT_SWZ_NEAR
-    if (SWZ) {
-#if PT_SWZ_SIGNSEL
+    if (SWZ) { /* (TAGGED) */
       uint32_t near_c = (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)PT_LDS_AT(node + skip_off + PT_SWZ_OFF_NEAR);
-      if (TAGGED) asm("" : "+v"(near_c));
-#else
-      const uint32_t near_c = (uint32_t)*(const uint16_t*)(sv.swz_nodes + node + skip_off + 16u);
-#endif
+      asm("" : "+v"(near_c));
       const bool hit = test_box(sv, node, na, nb, n_real);
-      if (TAGGED) {
 #if PT_DIAG_VISIT_VALU || PT_DIAG_VISIT_LDS || PT_DIAG_VISIT_SALU
-        for (int k_ = 0; k_ < PT_DIAG_VISIT_VALU; ++k_) asm volatile("v_add_u32 %0, 1, %0" : "+v"(lkx_diag));
-        for (int k_ = 0; k_ < PT_DIAG_VISIT_LDS; ++k_) lkx_diag += (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)PT_LDS_AT(node + skip_off + PT_SWZ_OFF_SKIP + 2u * (uint32_t)(k_ + 1));
-        for (int k_ = 0; k_ < PT_DIAG_VISIT_SALU; ++k_) { uint32_t t_; asm volatile("s_mov_b32 %0, 1" : "=s"(t_)); }
+      for (int k_ = 0; k_ < PT_DIAG_VISIT_VALU; ++k_) asm volatile("v_add_u32 %0, 1, %0" : "+v"(lkx_diag));
+      for (int k_ = 0; k_ < PT_DIAG_VISIT_LDS; ++k_) lkx_diag += (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)PT_LDS_AT(node + skip_off + PT_SWZ_OFF_SKIP + 2u * (uint32_t)(k_ + 1));
+      for (int k_ = 0; k_ < PT_DIAG_VISIT_SALU; ++k_) { uint32_t t_; asm volatile("s_mov_b32 %0, 1" : "=s"(t_)); }
 #endif
-        /* an inner node that was hit: its near child; a leaf that was hit: what follows it, tagged "holds a leaf"; a miss: what
-         * follows this subtree (PT_SWZ_END: nothing) */
-        if (COUNT && PT_DIAG == 0 && hit && (near_c & PT_SWZ_TAG_LEAF)) c_prims += (unsigned long long)(MODE == PT_MODE_SIMD ? ((n_real + 3u) & ~3u) : n_real);
-        node = hit ? near_c : skip;
-        return;
-      }
-      const bool leaf_hit = hit && near_c == PT_SWZ_LEAF;
-      if (leaf_hit) {
-        leaf_first = (int)na;
-        leaf_n = (int)n_real; /* real slots; the NaN padding (main.ml:185) can never be selected */
-        if (COUNT && PT_DIAG == 0) c_prims += (unsigned long long)(MODE == PT_MODE_SIMD ? ((n_real + 3u) & ~3u) : n_real);
-      }
-      /* an inner node that was hit: its near child; else (miss, or a leaf taken) what follows this subtree */
-      const uint32_t nx = (hit && !leaf_hit) ? near_c : skip;
-      if (nx == PT_SWZ_END) walking = false;
-      else node = nx;
+      /* an inner node that was hit: its near child; a leaf that was hit: what follows it, tagged "holds a leaf"; a miss: what
+       * follows this subtree (PT_SWZ_END: nothing) */
+      if (COUNT && PT_DIAG == 0 && hit && (near_c & PT_SWZ_TAG_LEAF)) c_prims += (unsigned long long)(MODE == PT_MODE_SIMD ? ((n_real + 3u) & ~3u) : n_real);
+      node = hit ? near_c : skip;
       return;
     }
-#endif
     const bool hit = test_box(sv, node, na, nb, n_real);
     if (hit) {
       const uint32_t axis = nb >> 30;
@@ -1071,12 +964,12 @@ struct PtTraverser {
         leaf_first = (int)na;
         leaf_n = (int)n_real; /* real slots; the NaN padding (main.ml:185) can never be selected */
         /* Leaf.length incl. padding: Simd_leaf pads to a multiple of 4 (main.ml:179-186); the filter image keeps the real count */
-        if (COUNT && PT_DIAG == 0) c_prims += (unsigned long long)(SWZ ? (MODE == PT_MODE_SIMD ? ((n_real + 3u) & ~3u) : n_real) : (nb & 0x3fffffffu));
+        if (COUNT && PT_DIAG == 0) c_prims += (unsigned long long)(nb & 0x3fffffffu);
       } else {
         /* Branch: near child first (shape_tree.ml:209), far child deferred */
         const uint32_t lhs = na, rhs = nb & 0x3fffffffu;
         const bool lhs_first = (dirs >> axis) & 1u;
-        if (!SWZ && !THREAD32) {
+        if (!THREAD32) {
           PT_STACK_PUSH(stack, sp, lhs_first ? rhs : lhs);
           ++sp;
         }
@@ -1087,10 +980,7 @@ struct PtTraverser {
     if (!descend) {
       /* the next node's bbox is tested on the NEXT visit, i.e. after this leaf's packet has been
        * intersected and r.t shrunk -- the t_max the reference passes to the far child */
-      if (SWZ) {
-        if (skip == PT_SWZ_END) walking = false;
-        else node = skip;
-      } else if (THREAD32) {
+      if (THREAD32) {
         if (skip == 0xffffffffu) walking = false;
         else node = skip;
       } else if (sp == 0) walking = false;
@@ -1134,7 +1024,6 @@ struct PtTraverser {
        * discriminant is >= +0; only then do the lanes that found one run the HEAVY part (sqrt, divide)
        * together.  Testing slot after slot in lockstep would execute ~50 sqrt/div instructions per slot with
        * one lane in eight active.  Slots are still visited in order, so `t <= t_found` ties resolve alike. */
-#if PT_PACKET_DEFER
       /* pass 1, lockstep over the slots: only the discriminant's sign; pass 2: the roots of the candidates, in slot
        * order.  The discriminant does not depend on the closest hit so far, so deferring the roots changes nothing. */
       for (int base = 0; base < leaf_n; base += 32) {
@@ -1145,7 +1034,7 @@ struct PtTraverser {
             c_nodes++;
             PT_DIAG_WAVE_SLOTS(c_floor);
           }
-          const double* s = sv.sph + (size_t)(leaf_first + base + k) * PT_SPH_STRIDE(SWZ);
+          const double* s = sv.sph + (size_t)(leaf_first + base + k) * 4;
           const double fx = ORIGIN_ZERO ? s[0] : s[0] - o.x, fy = ORIGIN_ZERO ? s[1] : s[1] - o.y,
                        fz = ORIGIN_ZERO ? s[2] : s[2] - o.z;
           const double bp_over_a = pt_fma(fx, d.x, pt_fma(fy, d.y, fz * d.z)) * one_over_a;
@@ -1153,7 +1042,6 @@ struct PtTraverser {
           const double wy = pt_fma(d.y, bp_over_a, -fy);
           const double wz = pt_fma(d.z, bp_over_a, -fz);
           const double disc = (s[3] * s[3]) - pt_fma(wx, wx, pt_fma(wy, wy, wz * wz));
-#if PT_SCAN_ADDC
           /* "neither NaN nor sign bit set" (lib.rs:162-166) is ONE unsigned comparison of the bit pattern (+0 ... +inf), and the
            * candidate mask takes the outcome as the carry of cand + cand: two vector instructions instead of five; the mask
            * comes out in reverse order and is turned round once per leaf */
@@ -1162,13 +1050,8 @@ struct PtTraverser {
             unsigned long long co_;
             asm("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(cand), "=s"(co_) : "s"(fm));
           }
-#else
-          if ((disc == disc) && !pt_signbit(disc)) cand |= 1u << k;
-#endif
         }
-#if PT_SCAN_ADDC
         cand = __brev(cand) >> (32 - m); /* slot k -> bit k (m >= 1) */
-#endif
         while (cand != 0) {
           if (COUNT && PT_DIAG == 4 && !ORIGIN_ZERO) {
             c_nodes++;
@@ -1176,7 +1059,7 @@ struct PtTraverser {
           }
           const int k = __ffs((int)cand) - 1;
           cand &= cand - 1u;
-          const double* s = sv.sph + (size_t)(leaf_first + base + k) * PT_SPH_STRIDE(SWZ);
+          const double* s = sv.sph + (size_t)(leaf_first + base + k) * 4;
           const double fx = ORIGIN_ZERO ? s[0] : s[0] - o.x, fy = ORIGIN_ZERO ? s[1] : s[1] - o.y,
                        fz = ORIGIN_ZERO ? s[2] : s[2] - o.z;
           const double r2 = s[3] * s[3];
@@ -1196,51 +1079,8 @@ struct PtTraverser {
           }
         }
       }
-#else
-      int k = 0;
-      while (k < leaf_n) {
-        double c = 0.0, bp = 0.0, disc = 0.0;
-        bool found = false;
-        while (k < leaf_n && !found) {
-          if (COUNT && PT_DIAG == 3 && !ORIGIN_ZERO) {
-            c_nodes++;
-            PT_DIAG_WAVE_SLOTS(c_floor);
-          }
-          const double* s = sv.sph + (size_t)(leaf_first + k) * PT_SPH_STRIDE(SWZ);
-          const double fx = ORIGIN_ZERO ? s[0] : s[0] - o.x, fy = ORIGIN_ZERO ? s[1] : s[1] - o.y,
-                       fz = ORIGIN_ZERO ? s[2] : s[2] - o.z; /* f = center - origin */
-          const double r2 = s[3] * s[3];
-          c = pt_fma(fx, fx, pt_fma(fy, fy, fz * fz)) - r2;
-          bp = pt_fma(fx, d.x, pt_fma(fy, d.y, fz * d.z));
-          const double bp_over_a = bp * one_over_a;
-          const double wx = pt_fma(d.x, bp_over_a, -fx);
-          const double wy = pt_fma(d.y, bp_over_a, -fy);
-          const double wz = pt_fma(d.z, bp_over_a, -fz);
-          const double wq = pt_fma(wx, wx, pt_fma(wy, wy, wz * wz));
-          disc = r2 - wq;
-          /* lanes whose discriminant has its sign bit set (or is NaN) end up NaN (lib.rs:162-166) */
-          found = (disc == disc) && !pt_signbit(disc);
-          ++k;
-        }
-        if (COUNT && PT_DIAG == 4 && !ORIGIN_ZERO) {
-          if (found) c_nodes++;
-          if (__ballot(found)) PT_DIAG_WAVE_SLOTS(c_floor);
-        }
-        if (found) {
-          const double q_rhs = pt_sqrt(qa * disc);
-          const double qq = pt_signbit(bp) ? (bp - q_rhs) : (bp + q_rhs);
-          const double t = pt_signbit(c) ? (qq * one_over_a) : (c / qq);
-          /* not (t < t_min), not (t > t_max), then `t <= t_found` (last index wins ties, lib.rs:169-177) */
-          if (!(t < t_min) && t <= r.t) {
-            r.t = t;
-            r.slot = leaf_first + k - 1;
-          }
-        }
-      }
-#endif
     } else {
       /* Array_leaf.intersect, shape_tree.ml:299-311: shrinking t_max, later element wins ties */
-#if PT_LEAF_PREFETCH
       if (!SWZ && sv.kind == nullptr) {
         /* a triangle-only scene walked from HBM / L2 (a mesh): the leaf's triangles are 80-byte records that mostly miss
          * every cache level above L2, and testing them one after the other made a leaf visit a chain of up to
@@ -1264,7 +1104,6 @@ struct PtTraverser {
         if (FILT) update_t32();
         return;
       }
-#endif
       for (int k = 0; k < leaf_n; ++k) {
         if (COUNT && PT_DIAG == 3 && !ORIGIN_ZERO) {
           c_nodes++;
@@ -1272,7 +1111,7 @@ struct PtTraverser {
         }
         const int slot = leaf_first + k;
         if (sv.kind[slot] == PT_SLOT_SPHERE) {
-          const double* s = sv.sph + (size_t)slot * PT_SPH_STRIDE(SWZ);
+          const double* s = sv.sph + (size_t)slot * 4;
           double t;
           if (pt_sphere_intersect_scalar(v3(s[0], s[1], s[2]), s[3], o, d, t_min, r.t, &t)) {
             r.t = t;
@@ -1315,7 +1154,7 @@ struct PtTailCtl {
   int slot;
   bool unfinished;  /* out: the ray is still walking */
 };
-template <int MODE, bool COUNT, bool ORIGIN_ZERO, typename StackT, bool SWZ = false, bool DIV_LOOP = (PT_WALK_LOOP != 0), bool ASM_WALK = false>
+template <int MODE, bool COUNT, bool ORIGIN_ZERO, typename StackT, bool SWZ = false, bool DIV_LOOP = false, bool ASM_WALK = false>
 __device__ __forceinline__ PtTraceResult pt_trace_ray(const PtSceneDev& sc, const PtSceneView& sv, StackT* stack,
                                                       V3 o, V3 d, unsigned long long& c_nodes,
                                                       unsigned long long& c_prims, unsigned long long& c_floor,
@@ -1414,9 +1253,6 @@ __device__ __forceinline__ PtTraceResult pt_trace_ray(const PtSceneDev& sc, cons
  * and a far child is tested when popped, against each ray's own closest hit.  What changes is the cost: node and
  * packet addresses are wave-uniform (LDS broadcasts, scalar control flow), no per-lane stack traffic, and the
  * packet loop runs in lockstep.  wstack: 3 words per level, shared by the wave. */
-#ifndef PT_PRIMARY_PACKET
-#define PT_PRIMARY_PACKET 1
-#endif
 template <int MODE, bool COUNT, bool ORIGIN_ZERO, bool SWZ>
 __device__ __forceinline__ PtTraceResult pt_trace_packet(const PtSceneDev& sc, const PtSceneView& sv, uint32_t* wstack,
                                                          bool valid, V3 o, V3 d, unsigned long long& c_nodes,
@@ -1438,16 +1274,10 @@ __device__ __forceinline__ PtTraceResult pt_trace_packet(const PtSceneDev& sc, c
     for (;;) {
       /* the node's links: one address for the whole wave */
       uint32_t ua, ub, n_real;
-      if (SWZ) { /* node = byte offset in the binary32 image */
-#if PT_SWZ_SIGNSEL
+      if (SWZ) { /* node = the node's absolute LDS address */
         const pt_u2 lk = *(const __attribute__((address_space(3))) pt_u2*)PT_LDS_AT(node + PT_SWZ_OFF_LINKS);
         const uint32_t w6 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lk.x);
         const uint32_t w7 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lk.y);
-#else
-        const unsigned char* nbase = sv.swz_nodes + node;
-        const uint32_t w6 = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const uint32_t*)(nbase + PT_SWZ_OFF_LINKS));
-        const uint32_t w7 = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const uint32_t*)(nbase + PT_SWZ_OFF_LINKS + 4));
-#endif
         ua = w6 & 0xffffu;
         ub = (w6 >> 16) | ((w7 & 3u) << 30);
         n_real = w6 >> 16;
@@ -1474,7 +1304,7 @@ __device__ __forceinline__ PtTraceResult pt_trace_packet(const PtSceneDev& sc, c
              * leaf's box; the roots only where a ray's discriminant is >= +0 (same order per ray as packet()) */
             const double t_min = 0.0;
             for (uint32_t k = 0; k < n_real; ++k) {
-              const double* sp4 = sv.sph + (size_t)(ua + k) * PT_SPH_STRIDE(SWZ);
+              const double* sp4 = sv.sph + (size_t)(ua + k) * 4;
               /* f = center - origin; for camera rays the origin is (+0, +0, +0) and x - (+0) == x bit for bit */
               const double fx = ORIGIN_ZERO ? sp4[0] : sp4[0] - tr.o.x, fy = ORIGIN_ZERO ? sp4[1] : sp4[1] - tr.o.y,
                            fz = ORIGIN_ZERO ? sp4[2] : sp4[2] - tr.o.z;
@@ -1541,7 +1371,7 @@ __device__ __forceinline__ PtTraceResult pt_trace_packet(const PtSceneDev& sc, c
 
 /* Where this workgroup traverses from.  LDS_SCENE: the whole tree and every leaf packet are first copied into LDS
  * behind the traversal stacks (nodes expanded to the swizzled image on the way); ends with a __syncthreads(). */
-template <int MODE, bool LDS_SCENE, typename StackT>
+template <int MODE, bool LDS_SCENE>
 __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsigned char* lds_raw, int stack_depth, bool want_top = false) {
   const uint32_t waves_per_block = blockDim.x >> 6;
   PtSceneView sv;
@@ -1568,44 +1398,26 @@ __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsig
   sv.kind = sc.slot_kind;
   sv.cat = sc.slot_cat;
   sv.nodes64 = nullptr;
-#if PT_LEAF_PREFETCH
   if (!LDS_SCENE && sc.all_triangles) sv.kind = nullptr; /* PtTraverser::packet: the pipelined triangle loop */
-#endif
   if (LDS_SCENE) {
-    size_t off = ((size_t)waves_per_block * PT_WAVE_STACK_BYTES(LDS_SCENE, StackT, stack_depth) + 63) & ~(size_t)63;
-    unsigned char* l_nodes = lds_raw + off;
-    off += ((size_t)sc.n_nodes * PT_SWZ_NODE_BYTES + 63) & ~(size_t)63; /* (the packets behind it are read 16 bytes at a time) */
+    unsigned char *l_nodes, *l_sph, *l_tri, *l_kind, *l_cat, *l_nodes64, *l_end; /* the regions of the image: pt_lds_layout.h */
+#define PT_VIEW_AT(region, off_) l_##region = lds_raw + (off_)
+    PT_LDS_IMAGE_REGIONS(PT_VIEW_AT, MODE, waves_per_block, stack_depth, sc.n_nodes, sc.n_slots + sc.n_floor, sc.has_triangles, sc.lds_nodes64);
+#undef PT_VIEW_AT
+    (void)l_end;
     const int total_slots = sc.n_slots + sc.n_floor;
-    double* l_sph = (double*)(lds_raw + off);
-    off += (size_t)total_slots * PT_LDS_SPH_DOUBLES * sizeof(double);
-    double* l_tri = (double*)(lds_raw + off);
-    if (MODE == PT_MODE_ARRAY && sc.has_triangles) off += (size_t)total_slots * 10 * sizeof(double);
-    uint8_t* l_kind = (uint8_t*)(lds_raw + off);
-    if (MODE == PT_MODE_ARRAY) off += ((size_t)total_slots + 15) & ~(size_t)15;
-    uint8_t* l_cat = (uint8_t*)(lds_raw + off);
-    off += ((size_t)total_slots + 15) & ~(size_t)15;
-    double* l_n64 = (double*)(lds_raw + off);
-    /* nodes: the binary32 filter image (PT_SWZ_NODE_BYTES each); links become byte offsets into it -- with PT_SWZ_SIGNSEL,
-     * absolute LDS addresses (layout 3 above) */
-#if PT_SWZ_SIGNSEL
+    /* nodes: the binary32 filter image (PT_SWZ_NODE_BYTES each); links become absolute LDS
+     * addresses (layout 3 above) */
     const uint32_t nbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)l_nodes;
-#else
-    const uint32_t nbase = 0u;
-#endif
     for (int k = threadIdx.x; k < sc.n_nodes; k += blockDim.x) {
       const PtNode* src = sc.nodes + k;
       uint32_t* w = (uint32_t*)(l_nodes + (size_t)k * PT_SWZ_NODE_BYTES);
       float mag = 0.0f;
       for (int ax = 0; ax < 3; ++ax) {
         const float lo = (float)src->mn[ax], hi = (float)src->mx[ax];
-#if PT_SWZ_SIGNSEL
         w[3 * ax] = __float_as_uint(lo);
         w[3 * ax + 1] = __float_as_uint(hi);
         w[3 * ax + 2] = __float_as_uint(lo);
-#else
-        w[ax] = __float_as_uint(lo);
-        w[3 + ax] = __float_as_uint(hi);
-#endif
         mag = __builtin_fmaxf(mag, __builtin_fmaxf(__builtin_fabsf(lo), __builtin_fabsf(hi)));
       }
       const uint32_t axis = src->b >> 30;
@@ -1619,21 +1431,15 @@ __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsig
       for (int o = 0; o < 8; ++o) {
         const uint32_t nx = sc.node_skip[(size_t)k * 8 + o];
         sk[o] = nx == 0xffffu ? (uint16_t)PT_SWZ_END : (uint16_t)(nbase + nx * PT_SWZ_NODE_BYTES);
-#if PT_SWZ_NEAR
         uint16_t* nr = (uint16_t*)((unsigned char*)w + PT_SWZ_OFF_NEAR);
-#if PT_SWZ_SIGNSEL && PT_SWZ_TAGGED
         /* tagged links (PT_SWZ_TAG_*): a leaf's entry is what follows it, with "holds a leaf" set */
         nr[o] = leaf ? (uint16_t)(sk[o] | PT_SWZ_TAG_LEAF) : (uint16_t)(nbase + (((o >> axis) & 1) ? src->a : (src->b & 0x3fffffffu)) * PT_SWZ_NODE_BYTES);
-#else
-        nr[o] = leaf ? (uint16_t)PT_SWZ_LEAF : (uint16_t)(nbase + (((o >> axis) & 1) ? src->a : (src->b & 0x3fffffffu)) * PT_SWZ_NODE_BYTES);
-#endif
-#endif
       }
     }
     {
       const uint4* src = (const uint4*)sc.sph;
       uint4* dst = (uint4*)l_sph;
-      for (int k = threadIdx.x; k < total_slots * 2; k += blockDim.x) dst[(k >> 1) * (PT_LDS_SPH_DOUBLES / 2) + (k & 1)] = src[k];
+      for (int k = threadIdx.x; k < total_slots * 2; k += blockDim.x) dst[k] = src[k];
     }
     if (MODE == PT_MODE_ARRAY) {
       if (sc.has_triangles) {
@@ -1646,15 +1452,15 @@ __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsig
     for (int k = threadIdx.x; k < total_slots; k += blockDim.x) l_cat[k] = sc.slot_cat[k];
     if (sc.lds_nodes64) /* (workgroup-uniform) mn.xyz, mx.xyz: the first 48 bytes of a PtNode */
       for (int k = threadIdx.x; k < sc.n_nodes * 3; k += blockDim.x)
-        ((double2*)l_n64)[k] = ((const double2*)(sc.nodes + k / 3))[k % 3];
+        ((double2*)l_nodes64)[k] = ((const double2*)(sc.nodes + k / 3))[k % 3];
     __syncthreads();
     sv.swz_nodes = l_nodes;
     sv.swz_root = nbase;
-    sv.sph = l_sph;
-    sv.tri = l_tri;
+    sv.sph = (const double*)l_sph;
+    sv.tri = (const double*)l_tri;
     sv.kind = l_kind;
     sv.cat = l_cat;
-    if (sc.lds_nodes64) sv.nodes64 = l_n64;
+    if (sc.lds_nodes64) sv.nodes64 = (const double*)l_nodes64;
   }
   return sv;
 }
@@ -1663,58 +1469,25 @@ __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsig
  * stride (unit = wave + k * n_waves) gave every wave ~28 units per launch whose costs differ several-fold (sky
  * against ground rows, 1 against 8 live bounces): the slowest wave ran ~1.7x the mean and a resident wave was alive
  * for only 62 % (trace) / 47 % (shade) of its kernel's duration (rocprofv3 SQ_WAVE_CYCLES against the kernel time,
- * profiles/r02a_sq.json).  Units are dealt from up to 8 counters (workgroups b and b + 8 share an XCD, so a counter's
- * line stays in one L2: MI355X_MICROARCH.md "dequeue": one word saturates at ~88 atomics / us, 8 sharded heads do
- * not), PT_CHUNK_FETCH units per atomic.  The counters must be zero at launch.  Wave-uniform. */
-#ifndef PT_CHUNK_FETCH
-#define PT_CHUNK_FETCH 2
-#endif
-#ifndef PT_DYNAMIC_CHUNKS
-#define PT_DYNAMIC_CHUNKS 2
-#endif
-/* PT_DYNAMIC_CHUNKS: 0 = static stride per wave; 1 = global counters (above); 2 = the workgroup keeps its static
- * share (chunks blockIdx, blockIdx + gridDim, ...) and its waves take them from a counter in LDS: no global atomic,
- * and a workgroup's total is the sum of ~450 chunk costs instead of a wave's ~28, so the spread between workgroups is
- * a quarter of the spread between waves. */
+ * profiles/r02a_sq.json).  The workgroup keeps its static share (chunks blockIdx, blockIdx + gridDim, ...) and its waves
+ * take them from a counter in LDS: no global atomic (units dealt from up to 8 sharded global counters were this scheme's A/B
+ * partner), and a workgroup's total is the sum of ~450 chunk costs instead of a wave's ~28, so the spread between
+ * workgroups is a quarter of the spread between waves.  Wave-uniform. */
 struct PtChunkFeed {
   uint32_t* ctr;
   uint32_t nc, c, limit, next, end;
-  __device__ __forceinline__ void init(uint32_t* work, uint32_t total_units, uint32_t* lds_ctr) {
-#if PT_DYNAMIC_CHUNKS == 0
-    /* static stride: unit = wave + k * n_waves */
-    nc = gridDim.x * (blockDim.x >> 6);
-    c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    limit = c < total_units ? (total_units - c + nc - 1u) / nc : 0u;
-    next = 0u;
-    end = limit;
-    ctr = work;
-#elif PT_DYNAMIC_CHUNKS == 2
+  __device__ __forceinline__ void init(uint32_t total_units, uint32_t* lds_ctr) {
     nc = gridDim.x;
     c = blockIdx.x;
     limit = c < total_units ? (total_units - c + nc - 1u) / nc : 0u;
     next = end = 0u;
     ctr = lds_ctr; /* zeroed by the caller before a workgroup barrier */
-#else
-    nc = gridDim.x < 8u ? gridDim.x : 8u;
-    c = blockIdx.x % nc;
-    ctr = work + c;
-    limit = c < total_units ? (total_units - c + nc - 1u) / nc : 0u; /* units c, c + nc, c + 2 nc, ... */
-    next = end = 0u;
-#endif
   }
   __device__ __forceinline__ bool take(uint32_t& unit) {
-#if PT_DYNAMIC_CHUNKS == 0
-    if (next >= end) return false;
-#else
     if (next >= end) {
       uint32_t k = 0u;
-#if PT_DYNAMIC_CHUNKS == 2
       if (pt_lane() == 0) k = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const uint32_t got = 1u;
-#else
-      if (pt_lane() == 0) k = atomicAdd(ctr, (uint32_t)PT_CHUNK_FETCH);
-      const uint32_t got = PT_CHUNK_FETCH;
-#endif
       k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
       if (k >= limit) {
         next = end = limit;
@@ -1723,7 +1496,6 @@ struct PtChunkFeed {
       next = k;
       end = (k + got < limit) ? k + got : limit;
     }
-#endif
     unit = next * nc + c;
     ++next;
     return true;
@@ -1737,24 +1509,7 @@ struct PtChunkFeed {
 #ifndef PT_TRACE_GLOBAL_WAVES
 #define PT_TRACE_GLOBAL_WAVES 4
 #endif
-#ifndef PT_TRACE_PRIO
-#define PT_TRACE_PRIO 0 /* s_setprio of the trace / pooled shade waves (0..3): matters only where both share a SIMD (two batches) */
-#endif
-#ifndef PT_SHADE_PRIO
-#define PT_SHADE_PRIO 0
-#endif
-#ifndef PT_TAIL_CUT
-#define PT_TAIL_CUT 16 /* 0 = off */
-#endif
-#ifndef PT_TAIL_CUT_GLOBAL
-/* scenes walked from HBM / L2 (k_trace): a step of the walk is a round trip to the L2, so lanes that idle while a chunk's long
- * rays finish cost more there, and a chunk is cut earlier.  Ganesha-like, per-octant node image: trace 23.7 (cut at 16) ->
- * 22.8 ms (24, 32); round 3 measured 24 / 32 within noise on the three-load walk. */
-#define PT_TAIL_CUT_GLOBAL 32
-#endif
-#ifndef PT_TRACE_DIV_LOOP
-#define PT_TRACE_DIV_LOOP(LDS_SCENE) (PT_WALK_LOOP != 0 || !(LDS_SCENE))
-#endif
+/* (PT_TAIL_CUT, PT_TAIL_CUT_GLOBAL: pt_lds_layout.h -- the parked walks' room depends on them) */
 #ifndef PT_TRACE_BLOCK_LDS
 #define PT_TRACE_BLOCK_LDS 1024 /* workgroup size when the scene is copied to LDS (one copy per workgroup) */
 #endif
@@ -1777,19 +1532,16 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
                                                PtCounters* counters, PtGenParams g, const double* __restrict__ alpha,
                                                uint32_t n_primary, uint32_t* work, uint4* susp, int top_in_lds) {
   extern __shared__ __attribute__((aligned(64))) unsigned char lds_raw[];
-#if PT_TRACE_PRIO
-  __builtin_amdgcn_s_setprio(PT_TRACE_PRIO);
-#endif
   const int lane = pt_lane();
   const int wave_in_block = (int)(threadIdx.x >> 6);
   /* LDS-resident scenes have < 65536 nodes: 16-bit stack entries halve the stack footprint */
   /* no per-lane stack anywhere: both walks are threaded.  PACKET on a scene walked from HBM / L2 (where wave packets do not
    * pay) selects the per-octant node image instead (PtThreadOctTag; the host launches it when PtSceneDev.nodes32o exists) */
   typedef typename std::conditional<LDS_SCENE, uint16_t, typename std::conditional<PACKET, PtThreadOctTag, PtThreadTag>::type>::type StackT;
-  StackT* stack = (StackT*)(lds_raw + (size_t)wave_in_block * PT_WAVE_STACK_BYTES(LDS_SCENE, StackT, stack_depth));
+  StackT* stack = (StackT*)(lds_raw + (size_t)wave_in_block * PT_WAVE_STACK_BYTES(LDS_SCENE, stack_depth));
   __shared__ uint32_t lds_chunk_ctr;
   if (threadIdx.x == 0) lds_chunk_ctr = 0u;
-  PtSceneView sv = pt_scene_view<MODE, LDS_SCENE, StackT>(sc, lds_raw, stack_depth, top_in_lds != 0);
+  PtSceneView sv = pt_scene_view<MODE, LDS_SCENE>(sc, lds_raw, stack_depth, top_in_lds != 0);
   if (!LDS_SCENE) {
     __shared__ double lds_floor[PT_FLOOR_LDS * 10];
     if (MODE == PT_MODE_ARRAY && sc.n_floor > 0) { /* the pre-tested floor triangles: see PtSceneView.floor_lds */
@@ -1801,13 +1553,13 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
   }
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   PtChunkFeed feed;
-  feed.init(work, (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE), &lds_chunk_ctr);
+  feed.init((uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE), &lds_chunk_ctr);
   uint32_t chunk;
   unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0};
 
   if (PACKET && LDS_SCENE) { /* the 64 rays of the wave walk the tree together (pt_trace_packet) */
     /* the wave's private stack area (stack_depth x 64 entries) holds the shared (node, mask) stack: 12 B per level */
-    uint32_t* wstack = (uint32_t*)(lds_raw + (size_t)wave_in_block * PT_WAVE_STACK_BYTES(LDS_SCENE, StackT, stack_depth));
+    uint32_t* wstack = (uint32_t*)(lds_raw + (size_t)wave_in_block * PT_WAVE_STACK_BYTES(LDS_SCENE, stack_depth));
     while (feed.take(chunk)) {
       const uint32_t i = chunk * PT_WAVE + lane;
       bool valid = i < n;
@@ -1834,7 +1586,9 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
       }
     }
   } else {
-    /* One ray per lane.  TAIL: see PtTailCtl -- a chunk ends when fewer than PT_TAIL_CUT of its rays are still walking;
+    /* One ray per lane; on LDS scenes the wave-level node loop with a `want` ballot per turn (the divergent loop has fewer scalar
+     * instructions per turn, but k_trace is bound by VECTOR issue there: measured 3 % slower).
+     * TAIL: see PtTailCtl -- a chunk ends when fewer than PT_TAIL_CUT of its rays are still walking;
      * their states (16 bytes each) go to this wave's list in `susp` and once 64 - PT_TAIL_CUT have gathered the wave walks
      * them as a chunk of their own.  tools/sim_coherence.py: 0.527 -> 0.435 wave steps per ray at 16. */
     constexpr int CUT = LDS_SCENE ? PT_TAIL_CUT : PT_TAIL_CUT_GLOBAL;
@@ -1895,7 +1649,7 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
       /* every lane goes in (wave-level ballots inside); lanes without a ray commit nothing */
       /* (the node loop as one divergent loop where the kernel runs at 4 waves per SIMD: the walk from HBM / L2 -- ganesha-like
        * frame 35.4 -> 33.6 ms; the LDS walk at 8 waves per SIMD loses 3 % with it) */
-      const PtTraceResult r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, PT_TRACE_DIV_LOOP(LDS_SCENE)>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid, TAIL ? &tc : nullptr, c_filter);
+      const PtTraceResult r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, /* DIV_LOOP */ !LDS_SCENE>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid, TAIL ? &tc : nullptr, c_filter);
       if (COUNT && PT_DIAG == 2 && !PRIMARY && valid) {
         unsigned long long m = c_nodes - diag_n0;
         for (int off = 32; off > 0; off >>= 1) {
@@ -2285,7 +2039,6 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
         geom.kind = PT_SLOT_SPHERE;
         if (sc.has_triangles) {
           geom.kind = (int)sc.slot_kind[slot];
-#if PT_RECOMPUTE_HIT
           /* (t, u, v) of the hit again, from the ray and the primitive the walk settled on: Array_leaf's own element tests
            * (PtTraverser::packet, begin's floor test) on the same operands.  Their acceptance range only ever decided WHICH
            * primitive won; the values do not depend on it. */
@@ -2297,13 +2050,6 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
             const double* tvx = sc.tri + (size_t)slot * 10;
             (void)pt_triangle_intersect(pt_load_v3(tvx), pt_load_v3(tvx + 3), pt_load_v3(tvx + 6), o, d, 0.0, PT_MAX_FINITE, &t_hit, &bu, &bv);
           }
-#else
-          const double2* hp = (const double2*)(hits.tuv + i); /* one 32-byte record (PtHits) */
-          const double2 h0 = hp[0], h1 = hp[1];
-          t_hit = h0.x;
-          bu = h0.y;
-          bv = h1.x;
-#endif
         } else {
           t_hit = hits.t[i];
           const double2* sp = (const double2*)(sc.sph + (size_t)slot * 4);
@@ -2415,7 +2161,6 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
  *    is then a number of ENTRIES (a multiple of the block), not of rays; the segment counters count rays.
  * Every ray still gets exactly pt_shade_entry's arithmetic; the order of the queue changes, which no result depends on
  * (contributions are stored per path id and summed in pass order). */
-#define PT_N_SHADE_CAT 5 /* PT_CAT_MISS .. PT_CAT_DIELECTRIC */
 #ifndef PT_POOL_BLOCK
 #define PT_POOL_BLOCK 256 /* < 4096 - 16 * 64: the cursor field must hold a full block plus one stray reservation per wave */
 #endif
@@ -2518,9 +2263,6 @@ __global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_pool_raw[]; /* [waves][PT_N_SHADE_CAT][128] x (queue index, hit slot) */
   __shared__ uint32_t lds_out[PT_POOL_BINS];
   __shared__ uint32_t lds_chunk_ctr, lds_done;
-#if PT_SHADE_PRIO
-  __builtin_amdgcn_s_setprio(PT_SHADE_PRIO);
-#endif
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
@@ -2680,21 +2422,14 @@ __global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(
 #ifndef PT_BOUNCE_WAVES
 #define PT_BOUNCE_WAVES 4 /* waves per SIMD asked of the register allocator (PT_BOUNCE_THREADS / 256); 768 threads / 3 waves: +16 % */
 #endif
-#ifndef PT_BOUNCE_DIV_LOOP
-#define PT_BOUNCE_DIV_LOOP(MODE) ((MODE) == PT_MODE_SIMD || (PT_SWZ_SIGNSEL && PT_SWZ_TAGGED)) /* the walk phase's node loop as one divergent
-                                                              loop (pt_trace_ray DIV_LOOP): headline -0.7 ... -1.1 %; cornell (Array_leaf) +1 % with
-                                                              the untagged links of round 4, -1.5 % with tagged ones (no ballot of "a lane holds a
-                                                              leaf" per turn any more: profiles/r05_ab_divloop_array_and_global_thresholds.txt) */
-#endif
+/* The walk phase's node loop on LDS scenes is one divergent loop (pt_trace_ray DIV_LOOP) in both leaf modes: headline -0.7 ... -1.1 %;
+ * cornell (Array_leaf) +1 % with the untagged links of round 4, -1.5 % with tagged ones (no ballot of "a lane holds a leaf" per turn
+ * any more: profiles/r05_ab_divloop_array_and_global_thresholds.txt) */
 #ifndef PT_BOUNCE_MIN_CHUNKS
 #define PT_BOUNCE_MIN_CHUNKS 2 /* chunks per wave below which fewer workgroups take part (k_shade_pool: 16 -- there a chunk is a few microseconds) */
 #endif
-#ifndef PT_SHADE_LDS_GEOM
-#define PT_SHADE_LDS_GEOM 1 /* k_bounce's shade steps read slot kinds / spheres / triangles from the LDS image instead of global memory */
-#endif
-#ifndef PT_LDS_CAT
-#define PT_LDS_CAT 1 /* k_bounce reads a finished ray's shading category from the LDS copy (PtSceneView.cat); 0: from global memory */
-#endif
+/* (k_bounce's shade steps read slot kinds / spheres / triangles, and a finished ray's shading category (PtSceneView.cat), from the LDS
+ * image instead of global memory.) */
 #ifndef PT_DIAG_FLOOR
 #define PT_DIAG_FLOOR 0 /* diagnostic builds only: 1 = k_bounce returns once the scene image is in LDS, 2 = at once (the launch floor) */
 #endif
@@ -2729,22 +2464,16 @@ __device__ __forceinline__ void pt_lds_unlock(uint32_t* l) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   if (pt_lane() == 0) __hip_atomic_store(l, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-/* entries the parked-walk pool of a k_bounce workgroup of nw waves must hold: a wave takes a fresh chunk only while fewer than 64
- * walks are parked and parks fewer than the cut when it ends; a resumed chunk takes 64 out before it can put any back */
-#define PT_PARK_CAP(nw, cut) (PT_WAVE + (nw) * (cut))
 struct PtSolo {
   uint32_t* flag;       /* per batch, zero at its start; null = never run solo */
   uint32_t max_entries; /* run solo when the input queue holds at most this many entries (0 = never) */
   int32_t max_bounces;
   uint32_t cap_entries; /* capacity of each of the two queues, in entries */
 };
-#define PT_BOUNCE_POOL_ENTRY_BYTES(LDS_SCENE_) ((LDS_SCENE_) ? 6u : 8u) /* k_bounce's pool entries: 32-bit queue index + 16- / 32-bit slot */
 #ifndef PT_SOLO_ONE_BIN_CHUNKS
 #define PT_SOLO_ONE_BIN_CHUNKS 2 /* a workgroup whose input of a solo turn is at most this many chunks per wave puts all survivors into one bin */
 #endif
-#ifndef PT_SOLO_MAX_BLOCKS
-#define PT_SOLO_MAX_BLOCKS 256 /* output blocks a workgroup can note per bounce; a launch whose shares could need more does not run solo */
-#endif
+/* (PT_SOLO_MAX_BLOCKS: pt_lds_layout.h) */
 template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false, bool LANE_WALK = false /* (PRIMARY && LDS_SCENE: k_bounce_carry) */>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
@@ -2761,7 +2490,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
   __shared__ uint32_t lds_nblk[2];
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
   typedef typename std::conditional<LDS_SCENE, uint16_t, PtThreadOctTag>::type StackT;
-  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(LDS_SCENE, StackT, stack_depth));
+  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(LDS_SCENE, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
   uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
@@ -2791,7 +2520,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
 #endif
   if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; lds_nblk[0] = lds_nblk[1] = 0u; lds_park_n = 0u; lds_park_lock = 0u; }
   if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
-  PtSceneView sv = pt_scene_view<MODE, LDS_SCENE, StackT>(sc, lds_raw, stack_depth); /* LDS_SCENE: ends with the workgroup's only barrier (SOLO: per bounce, two more) */
+  PtSceneView sv = pt_scene_view<MODE, LDS_SCENE>(sc, lds_raw, stack_depth); /* LDS_SCENE: ends with the workgroup's only barrier (SOLO: per bounce, two more) */
   if (!LDS_SCENE) {
     __shared__ double lds_floor[PT_FLOOR_LDS * 10];
     if (MODE == PT_MODE_ARRAY && sc.n_floor > 0) { /* the pre-tested floor triangles: see PtSceneView.floor_lds */
@@ -2805,9 +2534,8 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
   if (gridDim.x > 0) return; /* diagnostic build: launch + the scene image in LDS, nothing else */
 #endif
   /* the shade steps read the slots' kinds and geometry where the walk reads them: the LDS image (generic pointers: flat loads) */
-  static_assert(!PT_SHADE_LDS_GEOM || PT_LDS_SPH_DOUBLES == 4, "the shade step strides sphere records by 4 doubles (6: measured, no gain -- the scan's bank conflicts are not what binds)");
   PtSceneDev scl = sc;
-  if (PT_SHADE_LDS_GEOM && LDS_SCENE) {
+  if (LDS_SCENE) {
     scl.slot_kind = sv.kind;
     scl.sph = sv.sph;
     scl.tri = sv.tri;
@@ -2815,23 +2543,29 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
   /* the wave's five pools: queue indices (32 bits) and hit slots apart -- an LDS-resident scene has fewer than 65536 slots, so
    * its slots take 16 bits: 6 bytes per entry instead of 8, 20 KB of a 1024-thread workgroup's LDS for the scene image */
   typedef typename std::conditional<LDS_SCENE, uint16_t, uint32_t>::type PoolSlotT;
-  uint32_t (*pool_i)[128] = (uint32_t (*)[128])(lds_raw + pool_off) + (size_t)wave * PT_N_SHADE_CAT;
-  PoolSlotT (*pool_s)[128] = (PoolSlotT (*)[128])(lds_raw + pool_off + (size_t)nw * PT_N_SHADE_CAT * 128 * sizeof(uint32_t)) + (size_t)wave * PT_N_SHADE_CAT;
-  uint32_t cnt[PT_N_SHADE_CAT];
-#pragma unroll
-  for (int k = 0; k < PT_N_SHADE_CAT; ++k) cnt[k] = 0u;
   constexpr int CUT = LDS_SCENE ? PT_TAIL_CUT : PT_TAIL_CUT_GLOBAL;
   constexpr bool TAIL = CUT > 0 && !(PRIMARY && LDS_SCENE); /* LDS scenes: camera rays walk as a packet (pt_trace_packet), or one per lane without a cut (LANE_WALK), and finish together */
   constexpr bool TAIL_UV = TAIL && MODE == PT_MODE_ARRAY;
   constexpr bool TAIL_W = TAIL && !LDS_SCENE; /* 32-bit node index and slot: a third 16 bytes (as in k_trace) */
+  /* (the regions behind pool_off: pt_lds_layout.h; of the workgroup's pools a wave's five are its own) */
+  uint32_t (*pool_i)[128];
+  PoolSlotT (*pool_s)[128];
+#define PT_POOL_AT(region, off_) region = (decltype(region))(lds_raw + off_) + (size_t)wave * PT_N_SHADE_CAT
+  PT_LDS_BOUNCE_POOLS(PT_POOL_AT, pool_off, nw);
+#undef PT_POOL_AT
+  uint32_t cnt[PT_N_SHADE_CAT];
+#pragma unroll
+  for (int k = 0; k < PT_N_SHADE_CAT; ++k) cnt[k] = 0u;
   /* Parked walks (PtTailCtl) are pooled per WORKGROUP in LDS, behind the shade pools: whichever wave next looks for work and finds
    * 64 of them walks them as a dense chunk.  (Round 4 kept them per wave, in global memory: a wave had to collect 48 of its own
    * stragglers -- three or four cut chunks -- before it could resume any, which is what held the cut at 16 rays.)  16-byte entries
    * {queue index, node | slot << 16, t}; + {u, v} for triangle hits; + {node, slot} as 32-bit words on the walk from HBM / L2. */
   const uint32_t park_cap = (uint32_t)PT_PARK_CAP(nw, CUT);
-  uint4* const park0 = (uint4*)(lds_raw + pool_off + (size_t)nw * PT_N_SHADE_CAT * 128 * PT_BOUNCE_POOL_ENTRY_BYTES(LDS_SCENE));
-  uint4* const park_uv = park0 + park_cap;
-  uint4* const park_w = park_uv + (TAIL_UV ? park_cap : 0u);
+  uint4 *park0, *park_uv, *park_w, *park_end;
+#define PT_PARK_AT(region, off_) region = (uint4*)(lds_raw + off_)
+#define PT_PARK_AFTER(region, prev, words_) region = prev + (words_)
+  PT_LDS_BOUNCE_PARK(PT_PARK_AT, PT_PARK_AFTER, pool_off, nw, LDS_SCENE, TAIL_UV, park_cap);
+  (void)park_end;
   bool more = true;    /* wave-uniform: the workgroup's share of the queue is not exhausted */
   unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0}; /* COUNT: as in k_trace */
   /* SOLO: the bounce this workgroup is at, its queues, and whether its input is the block list it noted in the bounce before */
@@ -2875,7 +2609,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
       sl = (int)pool_s[K][start + lane];                                                                                   \
       if (LDS_SCENE && sl == 0xffff) sl = -1; /* (misses are filed with slot -1) */                                        \
     }                                                                                                                      \
-    pt_shade_entry<EMIT, PRIMARY, K, LIT>((PT_SHADE_LDS_GEOM && LDS_SCENE) ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
+    pt_shade_entry<EMIT, PRIMARY, K, LIT>(LDS_SCENE ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
   } break;
       switch (c) {
         PT_POOL_STEP(PT_CAT_MISS)
@@ -2974,7 +2708,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
     PT_TM5(c_floor);
     unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the walk's own counters go nowhere) */
     if constexpr (PRIMARY && LDS_SCENE && !LANE_WALK) r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, valid, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
-    else r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, LDS_SCENE ? PT_BOUNCE_DIV_LOOP(MODE) : PT_TRACE_DIV_LOOP(false), LDS_SCENE && !COUNT && MODE == PT_MODE_SIMD /* (Array_leaf kernels have no registers to pin: cornell +0.5 %; the walk from HBM / L2 in assembly: +1.9 %, profiles/r05_ab_oct_asm.txt) */>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
+    else r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, true, LDS_SCENE && !COUNT && MODE == PT_MODE_SIMD /* (Array_leaf kernels have no registers to pin: cornell +0.5 %; the walk from HBM / L2 in assembly: +1.9 %, profiles/r05_ab_oct_asm.txt) */>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
     PT_TM5(c_nodes);
     if (DIAG_T) c_filter[1] += (lane == 0);
     const bool park = TAIL && tc.unfinished;
@@ -2983,10 +2717,8 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
     if (done) {
       /* the hit distance (and a triangle's barycentrics) reach the shade step through memory -- this wave's own L1 / L2
        * lines; the slot travels in the pool entry */
-      if (MODE == PT_MODE_ARRAY && sc.has_triangles) {
-        if (!PT_RECOMPUTE_HIT) hits.tuv[i] = make_double4(r.t, r.u, r.v, 0.0); /* (else the shade step recomputes it: PtHits) */
-      } else hits.t[i] = r.t;
-      cat = r.slot < 0 ? PT_CAT_MISS : (int)((PT_LDS_CAT || !LDS_SCENE) ? sv.cat : sc.slot_cat)[r.slot]; /* (walks from HBM / L2: sv.cat is sc.slot_cat) */
+      if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
+      cat = r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot]; /* (walks from HBM / L2: sv.cat is sc.slot_cat) */
     }
 #pragma unroll
     for (int k = 0; k < PT_N_SHADE_CAT; ++k) {
@@ -3114,7 +2846,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
  * Survivors are binned by the shading category of that hit, a block is single-bin, so a chunk of 64 entries is one category by
  * construction, as a pool step is.  A wave's turn in launch b:
  *     read a chunk densely, once -> pt_shade_entry<CAT> of bounce b on the lane's own entry -> the new ray is in registers ->
- *     walk it at once (bounce b + 1) -> a miss ends the path on the spot (PT_CARRY_MISS_IN_PLACE), a hit is pushed as {new ray,
+ *     walk it at once (bounce b + 1) -> a miss ends the path on the spot, a hit is pushed as {new ray,
  *     path record, slot, t} under its category.
  * (The key of the next walk's length that pt_bin_key takes from the new direction is gone: that direction does not exist until the
  * next launch has shaded.  Predicting it for the checker category from the sampler value the scatter will use, two and four levels,
@@ -3128,11 +2860,6 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
  * slot array (PT_SLOT_HOLE) and skipped before they are shaded.  Same arithmetic, same tests per ray in the same order; which wave
  * does what when, and the order of a queue, change -- which no result depends on.  `hits` belongs to the input queue (launch 0:
  * to the camera samples), `hout` to the output queue. */
-#ifndef PT_CARRY_MISS_IN_PLACE
-#define PT_CARRY_MISS_IN_PLACE 1 /* a walk that ends in a miss is shaded where it ends; 0: pushed under the miss category like any other */
-#endif
-/* 16-byte words of a parked entry: {node | slot << 16, offset, t}, 3 x ray, {attn.x, attn.y}, {attn.z, id} [, 2 x emission] [, {u, v}] */
-#define PT_CARRY_PARK_WORDS(EMIT_, UV_) (6 + ((EMIT_) ? 2 : 0) + ((UV_) ? 1 : 0))
 static_assert(PT_POOL_BINS >= PT_N_SHADE_CAT, "k_bounce_carry: one output bin per shading category");
 
 /* LANE_WALK (PRIMARY launches, PTX_PRIMARY_WALK): the camera rays walk one per lane through pt_trace_ray -- on Simd_leaf scenes the
@@ -3148,7 +2875,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   __shared__ uint32_t lds_park_n, lds_park_lock;
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
   typedef uint16_t StackT;
-  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, StackT, stack_depth));
+  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
   uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
@@ -3158,21 +2885,21 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
   if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; lds_park_n = 0u; lds_park_lock = 0u; }
   if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
-  PtSceneView sv = pt_scene_view<MODE, true, StackT>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
+  PtSceneView sv = pt_scene_view<MODE, true>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
   PtSceneDev scl = sc; /* the shade steps read the slots' kinds and geometry where the walk reads them (k_bounce) */
-  if (PT_SHADE_LDS_GEOM) {
-    scl.slot_kind = sv.kind;
-    scl.sph = sv.sph;
-    scl.tri = sv.tri;
-  }
+  scl.slot_kind = sv.kind;
+  scl.sph = sv.sph;
+  scl.tri = sv.tri;
   constexpr int CUT = PT_TAIL_CUT;
   constexpr bool TAIL = CUT > 0;
   constexpr bool TAIL_UV = TAIL && MODE == PT_MODE_ARRAY;
   /* the workgroup's parked walks behind the scene image (there are no pools): one array of 16-byte words per field (PT_CARRY_PARK_WORDS) */
   const uint32_t park_cap = (uint32_t)PT_PARK_CAP(nw, CUT);
-  uint4* const park0 = (uint4*)(lds_raw + pool_off);
-  uint4* const park_emit = park0 + 6u * park_cap;
-  uint4* const park_uv = park_emit + (EMIT ? 2u * park_cap : 0u);
+  uint4 *park0, *park_emit, *park_uv, *park_end;
+  PT_LDS_CARRY_REGIONS(PT_PARK_AT, PT_PARK_AFTER, pool_off, EMIT, TAIL_UV, park_cap);
+#undef PT_PARK_AT
+#undef PT_PARK_AFTER
+  (void)park_end;
   bool more = true; /* wave-uniform: the workgroup's share of the input (launch 0: of the camera samples) is not exhausted */
   unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0}; /* COUNT: as in k_trace */
   /* PT_DIAG == 8 (tools/diag_phases.py; counting renders of diagnostic builds, the camera launch): where a wave's life goes, in ticks
@@ -3260,7 +2987,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         if (COUNT && !DIAG_T && live) c_seg++;
         PtTraceResult r;
         if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
-          r = pt_trace_ray<MODE, COUNT, true, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
+          r = pt_trace_ray<MODE, COUNT, true, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
         else r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
         if (live) {
           if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
@@ -3292,7 +3019,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
 #define PT_CARRY_STEP(K, ...)                                                                                          \
   if (PRIMARY ? __ballot(my_cat == K) != 0ull : c == K) {                                                              \
     PtShadeOut so;                                                                                                     \
-    pt_shade_entry<EMIT, PRIMARY, K>(PT_SHADE_LDS_GEOM ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, ##__VA_ARGS__); \
+    pt_shade_entry<EMIT, PRIMARY, K>(scl, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, ##__VA_ARGS__); \
     if (so.keep) {                                                                                                     \
       valid = true;                                                                                                    \
       o = so.n_o;                                                                                                      \
@@ -3317,18 +3044,18 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
     tc.min_active = (TAIL && more) ? CUT : 0;
     tc.resume = resume && valid;
     tc.unfinished = false;
-    const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, PT_BOUNCE_DIV_LOOP(MODE), !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
+    const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
     PT_TM8(c_floor);
     const bool park = TAIL && tc.unfinished;
     const bool done = valid && !park;
     const int cat = !done ? PT_CAT_NONE : (r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot]);
     /* a ray that left the scene ends its path here: pt_shade_entry<PT_CAT_MISS>'s one line on the registers that hold its operands
      * (None -> add_mul emit0 attn0 background, integrator.ml:36), instead of an entry for the next launch to read back */
-    if (PT_CARRY_MISS_IN_PLACE && cat == PT_CAT_MISS) {
+    if (cat == PT_CAT_MISS) {
       const V3 result = v3_fma(attn, pt_background(sc, d), EMIT ? emit : v3(0.0, 0.0, 0.0));
       contrib.rgbx[id] = make_double4(result.x, result.y, result.z, 0.0);
     }
-    const bool push = done && !(PT_CARRY_MISS_IN_PLACE && cat == PT_CAT_MISS);
+    const bool push = done && !(cat == PT_CAT_MISS); /* (written `cat != PT_CAT_MISS` the compiler merges the two tests of `cat` another way: other bytes, profiles/pr_lds_layout_identity.txt) */
     if (__ballot(push) != 0ull) {
       const uint32_t dst = pt_pool_reserve(out, push, push ? cat : 0, lds_out); /* the bin: the category, so that a chunk is one category */
       if (push) {

@@ -24,10 +24,8 @@
 /* Layout constants of the images the host builds (scene_host.cpp) and the kernels walk (kernels.hip describes the walks). */
 /* bytes per node of the LDS-resident filter image; the host's "fits LDS" threshold: a tree of n_nodes * PT_SWZ_NODE_BYTES >= 65535
  * bytes is walked from HBM / L2 and gets the per-octant and the top image */
-#ifndef PT_SWZ_NODE_BYTES
 #define PT_SWZ_NODE_BYTES 92 /* 80 used + 12: 23 words, an ODD stride, so that node k starts in LDS bank 21 k mod 64 -- all 64 banks.
                                 With 80 bytes (20 words) the nodes start in 16 of the 64 banks only, with 64 bytes in 4 */
-#endif
 /* the per-octant record (PtSceneDev.nodes32o): word 6 of a leaf = PT_OCT_LEAF_TAG | real slots << PT_OCT_LEAF_FIRST_BITS | first slot,
  * word 7 = the octant's skip link or PT_OCT_END */
 #define PT_OCT_LEAF_FIRST_BITS 22

@@ -375,37 +375,44 @@ int trace_block_lds(const ptx_scene* s) {
   const int b = s->trace_block > 0 ? s->trace_block : (s->sets_in_flight >= 2 ? 512 : PT_TRACE_BLOCK_LDS);
   return std::min(PT_TRACE_BLOCK_LDS, std::max(64, b & ~63));
 }
-constexpr size_t kLdsSceneLimit = 80 * 1024; /* 2 workgroups per CU out of 160 KiB */
+static_assert(PT_TRACE_BLOCK_LDS <= 64 * PT_LDS_MAX_WAVES && PT_BOUNCE_THREADS <= 64 * PT_LDS_MAX_WAVES, "pt_lds_layout.h bounds node addresses for workgroups of PT_LDS_MAX_WAVES waves");
 
-size_t trace_stack_bytes(const ptx_scene* s, bool lds_scene) {
-  const int stack_depth = std::max(1, s->tree_depth + 1);
-  const size_t b = lds_scene ? (size_t)(trace_block_lds(s) / 64) * PT_WAVE_STACK_BYTES(true, uint16_t, stack_depth)
-                             : (size_t)0; /* the walk from HBM / L2 is threaded too (node_skip32): no stack */
-  return (b + 63) & ~(size_t)63;
-}
-/* bytes of the LDS copy of the traversal data (0 = does not fit: traverse from HBM/L2) */
-size_t trace_scene_lds_bytes(const ptx_scene* s) {
-  const size_t total_slots = (size_t)s->dev.n_slots + (size_t)s->dev.n_floor;
-  size_t b = (((size_t)s->dev.n_nodes * PT_SWZ_NODE_BYTES + 63) & ~(size_t)63) + total_slots * PT_LDS_SPH_DOUBLES * sizeof(double);
-  if (s->dev.mode == PT_MODE_ARRAY) {
-    if (s->dev.has_triangles) b += total_slots * 10 * sizeof(double);
-    b += (total_slots + 15) & ~(size_t)15;
+/* Once per instantiation: a kernel's real static LDS must leave the room the layout counts on -- `reserve` bytes beside the largest
+ * dynamic request, and on an LDS scene no more than PT_LDS_STATIC_MAX in front of the image (the 16-bit node addresses) */
+void check_static_lds(const void* kern, const char* name, bool lds_scene, size_t reserve) {
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, kern) != hipSuccess) return;
+  if ((size_t)fa.sharedSizeBytes > reserve || (lds_scene && (size_t)fa.sharedSizeBytes > PT_LDS_STATIC_MAX)) {
+    fprintf(stderr, "ptx: %s holds %zu bytes of static LDS, more than pt_lds_layout.h leaves room for (%zu%s)\n", name, (size_t)fa.sharedSizeBytes, reserve,
+            lds_scene ? ", PT_LDS_STATIC_MAX in front of the scene image" : "");
+    abort(); /* a build error (a new __shared__ array), caught on the first launch of any test */
   }
-  b += (total_slots + 15) & ~(size_t)15; /* the slots' shading categories (PtSceneView.cat) */
-  if (s->dev.lds_nodes64) b += (size_t)s->dev.n_nodes * 48; /* the binary64 bounds for undecided tests (PtSceneView.nodes64) */
-  /* 16-bit node references (0xffff = none, 0xfffe = leaf): byte offsets into the image or, with PT_SWZ_SIGNSEL, absolute LDS
-   * addresses -- the image starts behind the kernel's static words and the largest workgroup's stacks; 16-bit slot indices */
-  if (2048 + (size_t)(PT_TRACE_BLOCK_LDS / 64) * PT_WAVE_STACK_BYTES(true, uint16_t, std::max(1, s->tree_depth + 1)) + (size_t)s->dev.n_nodes * PT_SWZ_NODE_BYTES >= 65534 ||
-      total_slots >= 65536)
-    return 0;
-  return (trace_stack_bytes(s, true) + b <= kLdsSceneLimit) ? b : 0;
 }
+
+/* what pt_lds_layout.h needs to know of a launch of `kernel` (PT_LDS_K_*) with workgroups of `waves` waves */
+PtLdsIn lds_in(const ptx_scene* s, int kernel, int waves, bool from_hbm = false, int n_top = 0) {
+  PtLdsIn in{};
+  in.mode = s->dev.mode;
+  in.n_nodes = s->dev.n_nodes;
+  in.total_slots = s->dev.n_slots + s->dev.n_floor;
+  in.has_triangles = s->dev.has_triangles;
+  in.has_emit = s->dev.has_emit;
+  in.lds_nodes64 = s->dev.lds_nodes64;
+  in.stack_depth = std::max(1, s->tree_depth + 1);
+  in.waves = waves;
+  in.kernel = kernel;
+  in.from_hbm = from_hbm;
+  in.n_top = n_top;
+  return in;
+}
+/* the traversal data fits an LDS copy (else: traverse from HBM/L2) */
+bool scene_in_lds(const ptx_scene* s) { return pt_lds_placement(lds_in(s, PT_LDS_K_TRACE, trace_block_lds(s) / 64)) == PT_PLACE_LDS; }
 
 /* Two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half of what a CU holds (launch_shade_pool).
  * Measured: headline frame 29.7 -> 27.4 ms, 4K spp 256 468 -> 429 ms.  Array_leaf scenes (cornell: the trace kernel needs
  * ~106 VGPRs, one workgroup would be left) and scenes walked from HBM / L2 lose 1-2 % and keep whole-CU grids. */
 bool share_cus(const ptx_scene* s) {
-  return s->sets_in_flight >= 2 && s->dev.mode == PT_MODE_SIMD && trace_scene_lds_bytes(s) > 0;
+  return s->sets_in_flight >= 2 && s->dev.mode == PT_MODE_SIMD && scene_in_lds(s);
 }
 
 struct PrimaryLaunch {
@@ -420,16 +427,17 @@ void launch_trace_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
   const int stack_depth = std::max(1, s->tree_depth + 1);
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   const int top_in_lds = (!LDS_SCENE && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
-  const size_t lds = trace_stack_bytes(s, LDS_SCENE) + (LDS_SCENE ? trace_scene_lds_bytes(s) : (top_in_lds ? (size_t)s->dev.n_top * PT_TOP_NODE_BYTES : 0));
   const int kTraceBlock = LDS_SCENE ? trace_block_lds(s) : PT_TRACE_BLOCK_OF(MODE, LDS_SCENE);
+  const size_t lds = pt_lds_layout(lds_in(s, PT_LDS_K_TRACE, kTraceBlock / 64, !LDS_SCENE, top_in_lds ? s->dev.n_top : 0)).total;
   /* from HBM/L2 one shared node fetch per step serialises the latency (-3 %): packets only on LDS-resident scenes */
   /* (the same template switch selects the per-octant node image on scenes walked from HBM / L2: k_trace) */
-  const bool packet = LDS_SCENE ? (PRIMARY ? PT_PRIMARY_PACKET != 0 : (s->cur_bounce >= 1 && s->cur_bounce <= s->bounce_packet))
+  const bool packet = LDS_SCENE ? (PRIMARY ? true : (s->cur_bounce >= 1 && s->cur_bounce <= s->bounce_packet))
                                 : (s->dev.nodes32o != nullptr && !top_in_lds);
   auto kern = packet ? k_trace<MODE, COUNT, PRIMARY, LDS_SCENE, true> : k_trace<MODE, COUNT, PRIMARY, LDS_SCENE, false>;
   /* the dynamic-LDS limit is a property of (kernel, device): remembered per scene, which is bound to one device */
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
+    check_static_lds((const void*)kern, "k_trace", LDS_SCENE, 1024);
   }
   int blocks_per_cu = LDS_SCENE ? std::min(4, std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(lds, 1)))) : (PT_TRACE_GLOBAL_WAVES * 256) / kTraceBlockGlobal; /* what the registers admit: no stack in LDS any more */
   if (s->trace_wgs_per_cu > 0) blocks_per_cu = std::min(4, s->trace_wgs_per_cu); /* `susp` is sized for 4 */
@@ -448,7 +456,7 @@ void launch_trace_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
 
 template <int MODE, bool COUNT, bool PRIMARY>
 void launch_trace_lds(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper, const PrimaryLaunch& pl, uint32_t* work) {
-  if (trace_scene_lds_bytes(s) > 0) launch_trace_inst<MODE, COUNT, PRIMARY, true>(s, st, q, h, n_upper, pl, work);
+  if (scene_in_lds(s)) launch_trace_inst<MODE, COUNT, PRIMARY, true>(s, st, q, h, n_upper, pl, work);
   else launch_trace_inst<MODE, COUNT, PRIMARY, false>(s, st, q, h, n_upper, pl, work);
 }
 template <int MODE>
@@ -489,7 +497,7 @@ void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
   const int per_cu = s->shade_wgs_per_cu > 0 ? std::min(s->shade_wgs_per_cu, most) : (share_cus(s) ? std::max(1, most / 2) : most);
   const int grid = strided_grid(s, n_upper, threads, per_cu);
   const dim3 gd(grid), bd(threads);
-  const size_t lds = (size_t)(threads / 64) * PT_N_SHADE_CAT * 128 * sizeof(uint2);
+  const size_t lds = pt_lds_shade_pool_bytes(threads / 64);
   if (scene_lit(s)) {
     if (pl.on) hipLaunchKernelGGL((k_shade_pool<true, true, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
     else hipLaunchKernelGGL((k_shade_pool<true, false, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
@@ -506,40 +514,19 @@ void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
  * included (its COUNT instantiations); the scenes walked from HBM / L2 keep the two kernels */
 /* scenes walked from HBM / L2 run k_bounce<..., LDS_SCENE = false> over the per-octant node image (PTX_FUSED_GLOBAL=0: k_trace + k_shade_pool) */
 bool bounce_from_hbm(const ptx_scene* s) {
-  return trace_scene_lds_bytes(s) == 0 && s->dev.nodes32o != nullptr && s->fused_global != 0 && !(s->dev.n_top > 0 && s->trace_top);
+  return !scene_in_lds(s) && s->dev.nodes32o != nullptr && s->fused_global != 0 && !(s->dev.n_top > 0 && s->trace_top);
 }
 int bounce_threads(const ptx_scene* s) {
   const int dflt = bounce_from_hbm(s) ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS;
   return s->bounce_threads > 0 ? std::min(PT_BOUNCE_THREADS, std::max(64, s->bounce_threads & ~63)) : dflt;
 }
-size_t bounce_lds_bytes(const ptx_scene* s, size_t* pool_off, bool carry = false) {
-  const int stack_depth = std::max(1, s->tree_depth + 1), waves = bounce_threads(s) / 64;
-  /* the workgroup's parked walks behind the shade pools (k_bounce): 16 bytes per entry, + 16 for a triangle hit's (u, v), + 16 for
-   * the 32-bit node index and slot of a walk from HBM / L2 */
-  const bool hbm = bounce_from_hbm(s);
-  /* (k_bounce_carry: the parked record is the whole entry, PT_CARRY_PARK_WORDS) */
-  const size_t park = (size_t)PT_PARK_CAP(waves, hbm ? PT_TAIL_CUT_GLOBAL : PT_TAIL_CUT) * 16 *
-                      (carry ? (size_t)PT_CARRY_PARK_WORDS(s->dev.has_emit != 0, s->dev.mode == PT_MODE_ARRAY)
-                             : (size_t)(1 + (s->dev.mode == PT_MODE_ARRAY ? 1 : 0) + (hbm ? 1 : 0)));
-  if (hbm) { /* no stacks, no scene image: the pools only */
-    if (pool_off) *pool_off = 0;
-    return (size_t)waves * PT_N_SHADE_CAT * 128 * PT_BOUNCE_POOL_ENTRY_BYTES(false) + park;
-  }
-  /* (the stacks' size must be what pt_scene_view derives from blockDim: the scene image starts behind them) */
-  const size_t stacks = ((size_t)waves * PT_WAVE_STACK_BYTES(true, uint16_t, stack_depth) + 63) & ~(size_t)63;
-  const size_t off = (stacks + trace_scene_lds_bytes(s) + 63) & ~(size_t)63;
-  if (pool_off) *pool_off = off;
-  if (carry) return off + park; /* (no pools: its parked entries start where they would) */
-  return off + (size_t)waves * PT_N_SHADE_CAT * 128 * PT_BOUNCE_POOL_ENTRY_BYTES(true) + park;
+/* the dynamic LDS of a k_bounce (carry: k_bounce_carry) launch: total, pool_off and whether it fits (PT_LDS_BOUNCE_LIMIT) */
+PtLdsLayout bounce_layout(const ptx_scene* s, bool carry = false) {
+  return pt_lds_layout(lds_in(s, carry ? PT_LDS_K_BOUNCE_CARRY : PT_LDS_K_BOUNCE, bounce_threads(s) / 64, bounce_from_hbm(s)));
 }
-/* dynamic LDS a k_bounce launch may ask for: the 160 KB of a CU less the kernel's own static words -- bins, counters, the floor
- * triangles, and in the instantiation that can run solo its two block lists (2 x PT_SOLO_MAX_BLOCKS words).  A request beyond
- * what the CU has does not fail politely: the queue aborts (HSA_STATUS_ERROR_INVALID_ALLOCATION), so launch_bounce_where also
- * checks the kernel's real static size once per instantiation. */
-constexpr size_t kBounceLdsLimit = (size_t)160 * 1024 - (2 * PT_SOLO_MAX_BLOCKS * sizeof(uint32_t) + 512);
 bool use_fused(const ptx_scene* s, size_t cap_entries) {
-  return s->fused && cap_entries < kPoolMaxEntries && (trace_scene_lds_bytes(s) > 0 || bounce_from_hbm(s)) &&
-         bounce_lds_bytes(s, nullptr) <= kBounceLdsLimit;
+  return s->fused && cap_entries < kPoolMaxEntries && (scene_in_lds(s) || bounce_from_hbm(s)) &&
+         bounce_layout(s).fits;
 }
 /* the shade-first order (k_bounce_carry) is for LDS-resident scenes whose larger parked record still fits, with every bounce a
  * k_bounce launch and no solo run configured.  By default (PTX_BOUNCE_ORDER=2) the scenes binned by elevation take it -- open
@@ -547,8 +534,8 @@ bool use_fused(const ptx_scene* s, size_t cap_entries) {
  * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
  * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
 bool carry_possible(const ptx_scene* s) {
-  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !scene_lit(s) && s->fused >= 2 && s->solo_entries <= 0 && trace_scene_lds_bytes(s) > 0 && !bounce_from_hbm(s) &&
-         bounce_lds_bytes(s, nullptr, true) <= kBounceLdsLimit;
+  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !scene_lit(s) && s->fused >= 2 && s->solo_entries <= 0 && scene_in_lds(s) && !bounce_from_hbm(s) &&
+         bounce_layout(s, true).fits;
 }
 /* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
  * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
@@ -560,22 +547,17 @@ template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false>
 void launch_carry_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
                        const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
   const int stack_depth = std::max(1, s->tree_depth + 1);
-  size_t pool_off = 0;
-  const size_t lds = bounce_lds_bytes(s, &pool_off, true);
+  const PtLdsLayout lds = bounce_layout(s, true);
   auto kern = k_bounce_carry<MODE, COUNT, EMIT, PRIMARY, LANE_WALK>;
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)kern) == hipSuccess && (size_t)fa.sharedSizeBytes + kBounceLdsLimit > (size_t)160 * 1024) {
-      fprintf(stderr, "ptx: k_bounce_carry holds %zu bytes of static LDS, more than kBounceLdsLimit leaves room for\n", (size_t)fa.sharedSizeBytes);
-      abort(); /* a build error (a new __shared__ array), caught on the first launch of any test */
-    }
+    check_static_lds((const void*)kern, "k_bounce_carry", true, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
   }
   const int threads = bounce_threads(s);
   int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
-                     (uint32_t)pool_off, s->counters.p, s->bounce_fence_wg);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
+                     (uint32_t)lds.pool_off, s->counters.p, s->bounce_fence_wg);
 }
 template <int MODE, bool COUNT>
 void launch_carry_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
@@ -604,8 +586,7 @@ template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE, bool LI
 void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                          size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
   const int stack_depth = std::max(1, s->tree_depth + 1);
-  size_t pool_off = 0;
-  const size_t lds = bounce_lds_bytes(s, &pool_off);
+  const PtLdsLayout lds = bounce_layout(s);
   /* the instantiation with the loop over a batch's remaining bounces (PtSolo) only where it can be taken */
   /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
   /* (camera rays of an LDS-resident scene: the packet walk or one ray per lane, primary_lane_walk) */
@@ -614,11 +595,7 @@ void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
                   : ((solo.flag != nullptr && !PRIMARY) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, !PRIMARY && !LIT> : k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false>);
   if (s->attr_done.insert((const void*)kern).second) {
     raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)kern) == hipSuccess && (size_t)fa.sharedSizeBytes + kBounceLdsLimit > (size_t)160 * 1024) {
-      fprintf(stderr, "ptx: k_bounce holds %zu bytes of static LDS, more than kBounceLdsLimit leaves room for\n", (size_t)fa.sharedSizeBytes);
-      abort(); /* a build error (a new __shared__ array), caught on the first launch of any test */
-    }
+    check_static_lds((const void*)kern, "k_bounce", LDS_SCENE, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
   }
   const int threads = bounce_threads(s);
   /* LDS scenes: one workgroup (one scene image) per CU; walks from HBM / L2: what the registers admit (PT_BOUNCE_WAVES per SIMD) --
@@ -626,8 +603,8 @@ void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
   const int per_cu = LDS_SCENE ? 1 : std::max(1, std::min(4, (PT_BOUNCE_WAVES * 256) / threads));
   int grid = strided_grid(s, n_upper, threads, per_cu);
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
-                     (uint32_t)pool_off, s->counters.p, s->bounce_fence_wg, solo);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds.total, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
+                     (uint32_t)lds.pool_off, s->counters.p, s->bounce_fence_wg, solo);
 }
 template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LIT>
 void launch_bounce_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
@@ -709,8 +686,8 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
   HIP_TRY(b.qa.ensure(cap, s->dev.has_emit != 0));
   HIP_TRY(b.qb.ensure(cap, s->dev.has_emit != 0));
   /* {t, u, v, -} records (barycentrics exist for triangle hits only): kept for ptx_intersect_rays, which hands t back; a render's
-   * shade step recomputes them (PtHits, PT_RECOMPUTE_HIT) and the buffer is not even allocated */
-  const bool hit_records = s->dev.has_triangles && (want_hit_records || !PT_RECOMPUTE_HIT);
+   * shade step recomputes them (PtHits) and the buffer is not even allocated */
+  const bool hit_records = s->dev.has_triangles && want_hit_records;
   if (hit_records) HIP_TRY(b.hit_tuv.ensure(cap * 4));
   /* k_bounce_carry reads its input's hits while it writes its output's: entries of even and odd bounces in two halves */
   const bool carry = carry_possible(s) && !hit_records;
@@ -829,7 +806,7 @@ void fill_tree_stats(const ptx_scene* s, ptx_stats* st) {
   st->tree_leaves = s->tree_leaves;
   st->leaf_slots = s->dev.n_slots;
   st->build_ms = s->build_ms;
-  st->traversal_in_lds = (s->device >= 0 && trace_scene_lds_bytes(s) > 0) ? 1 : 0;
+  st->traversal_in_lds = (s->device >= 0 && scene_in_lds(s)) ? 1 : 0;
   st->bvh_built_on_gpu = s->built_on_gpu ? 1 : 0;
 }
 
@@ -1470,12 +1447,8 @@ static int scene_upload(ptx_scene* s) {
   dv.top_nodes = h.top_nodes.empty() ? nullptr : s->top_nodes.p;
   dv.node_skip32_top = h.skip32_top.empty() ? nullptr : s->node_skip32_top.p;
   dv.n_top = (int32_t)(h.top_nodes.size() / 16);
-  /* PtSceneDev.lds_nodes64: only if the scene is LDS-resident without them and stays so, in both schedules, with them */
   dv.lds_nodes64 = 0;
-  if (trace_scene_lds_bytes(s) > 0 && env_int("PTX_LDS_NODES64", 1)) {
-    dv.lds_nodes64 = 1;
-    if (trace_scene_lds_bytes(s) == 0 || bounce_lds_bytes(s, nullptr) > kBounceLdsLimit) dv.lds_nodes64 = 0;
-  }
+  if (scene_in_lds(s) && env_int("PTX_LDS_NODES64", 1)) dv.lds_nodes64 = pt_lds_keep_nodes64(lds_in(s, PT_LDS_K_TRACE, trace_block_lds(s) / 64), bounce_threads(s) / 64);
   return 0;
 }
 

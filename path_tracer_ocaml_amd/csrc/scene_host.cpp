@@ -3,6 +3,8 @@
  * the light table must carry the bits the shade step itself would compute. */
 #include "scene_host.h"
 
+#include "pt_lds_layout.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -29,8 +31,13 @@ bool is_leaf(const PtNode& nd) { return (nd.b >> 30) == PT_NODE_LEAF_AXIS; }
 bool any_triangles(const ptx_scene_desc* d) { return d->n_triangles > 0 || d->n_floor_triangles > 0; }
 V3 vertex(const ptx_scene_desc* d, int i) { return v3(d->vertex_x[i], d->vertex_y[i], d->vertex_z[i]); }
 bool emits(const ptx_material& m) { return m.emit[0] != 0.0 || m.emit[1] != 0.0 || m.emit[2] != 0.0; }
-/* trees that will be walked from HBM / L2: too large for the LDS image */
-bool beyond_lds(const std::vector<PtNode>& nd) { return nd.size() * PT_SWZ_NODE_BYTES >= 65535; }
+/* trees that will be walked from HBM / L2 on images of their own: too large for the LDS image whatever else the scene holds
+ * (pt_lds_placement answers PT_PLACE_HBM_OCT on the node count alone) */
+bool beyond_lds(const std::vector<PtNode>& nd) {
+  PtLdsIn in{};
+  in.n_nodes = (int)std::min<size_t>(nd.size(), 0x7fffffff);
+  return pt_lds_placement(in) == PT_PLACE_HBM_OCT;
+}
 
 /* the emissive tree triangles in build-list order */
 void emissive_list(const ptx_scene_desc* d, PtHostArrays* h) {

@@ -9,6 +9,11 @@
 //   arrays <name> [key=value]   the assembled scene as one JSON line: element count and FNV-1a digest of every vector of
 //                               PtHostArrays, the scalars of its dev, the light table.  Keys: tri_frame, oct_image, top_nodes,
 //                               bin_key (SceneOptions), dump=<dir> (the tree, threading and image vectors as raw files)
+//   layout <name|ints> [key=value]  what csrc/pt_lds_layout.h says of a scene (or of explicit integers), as one JSON line: where it
+//                               is walked from, and for k_trace, k_bounce and k_bounce_carry every region's offset in the dynamic LDS
+//                               buffer and the total.  Keys: mode, n_nodes, total_slots, has_triangles, has_emit, lds_nodes64,
+//                               tree_depth, n_top (a scene's own unless given), trace_waves, waves (workgroup sizes of k_trace / the
+//                               k_bounce family), hbm (the k_bounce family walks from HBM / L2)
 //   hostile                     broken descriptors: each must come back rejected, with its message
 //   png <out.png>               write a small image
 #include <cmath>
@@ -18,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../../path_tracer_ocaml_amd/csrc/pt_lds_layout.h"
 #include "../../path_tracer_ocaml_amd/csrc/scene_host.h"
 #include "../../path_tracer_ocaml_amd/host/host.h"
 
@@ -162,6 +168,85 @@ static int arrays_mode(int argc, char** argv) {
   return 0;
 }
 
+/* ---- layout ---- */
+static void put_image(FILE* f, const PtLdsLayout& l) {
+  put_int(f, "stacks", (long long)l.stacks); put_int(f, "nodes", (long long)l.image.nodes); put_int(f, "sph", (long long)l.image.sph);
+  put_int(f, "tri", (long long)l.image.tri); put_int(f, "kind", (long long)l.image.kind); put_int(f, "cat", (long long)l.image.cat);
+  put_int(f, "nodes64", (long long)l.image.nodes64); put_int(f, "image_end", (long long)l.image.end);
+}
+static int layout_mode(int argc, char** argv) {
+  PtLdsIn in{};
+  int tree_depth = 0, trace_waves = -1, waves = 16, hbm = 0;
+  if (std::string(argv[2]) != "ints") {
+    pth_scene* s = make_scene(argv[2]);
+    if (!s) return 1;
+    Assembled a;
+    std::string msg;
+    const int rc = assemble(pth_scene_desc(s), SceneOptions{}, &a, &msg);
+    pth_scene_free(s);
+    if (rc) return 1;
+    const PtSceneDev& dv = a.h.dev;
+    in.mode = dv.mode; in.n_nodes = dv.n_nodes; in.total_slots = dv.n_slots + dv.n_floor; in.has_triangles = dv.has_triangles;
+    in.has_emit = dv.has_emit; in.n_top = (int)(a.h.top_nodes.size() / 16);
+    tree_depth = a.depth;
+  }
+  for (int i = 3; i < argc; ++i) {
+    const std::string kv = argv[i];
+    const size_t eq = kv.find('=');
+    if (eq == std::string::npos) return 2;
+    const std::string key = kv.substr(0, eq);
+    const int val = std::atoi(kv.substr(eq + 1).c_str());
+    if (key == "mode") in.mode = val;
+    else if (key == "n_nodes") in.n_nodes = val;
+    else if (key == "total_slots") in.total_slots = val;
+    else if (key == "has_triangles") in.has_triangles = val;
+    else if (key == "has_emit") in.has_emit = val;
+    else if (key == "lds_nodes64") in.lds_nodes64 = val;
+    else if (key == "tree_depth") tree_depth = val;
+    else if (key == "n_top") in.n_top = val;
+    else if (key == "trace_waves") trace_waves = val;
+    else if (key == "waves") waves = val;
+    else if (key == "hbm") hbm = val;
+    else return 2;
+  }
+  if (trace_waves < 0) trace_waves = in.mode == PT_MODE_SIMD ? 16 : 8; /* the library's defaults: 1024 / 512 threads */
+  in.stack_depth = tree_depth + 1 > 1 ? tree_depth + 1 : 1;
+  in.kernel = PT_LDS_K_TRACE;
+  in.waves = trace_waves;
+  const int placement = pt_lds_placement(in);
+  FILE* f = stdout;
+  std::fprintf(f, "{\"in\":{");
+  put_int(f, "mode", in.mode); put_int(f, "n_nodes", in.n_nodes); put_int(f, "total_slots", in.total_slots);
+  put_int(f, "has_triangles", in.has_triangles); put_int(f, "has_emit", in.has_emit); put_int(f, "lds_nodes64", in.lds_nodes64);
+  put_int(f, "tree_depth", tree_depth); put_int(f, "n_top", in.n_top); put_int(f, "trace_waves", trace_waves); put_int(f, "waves", waves);
+  put_int(f, "hbm", hbm, "},");
+  put_int(f, "placement", placement); put_int(f, "static_max", (long long)PT_LDS_STATIC_MAX);
+  put_int(f, "lds_nodes64_kept", pt_lds_keep_nodes64(in, waves)); put_int(f, "bounce_limit", (long long)PT_LDS_BOUNCE_LIMIT); put_int(f, "shade_pool", (long long)pt_lds_shade_pool_bytes(waves));
+  in.from_hbm = placement != PT_PLACE_LDS;
+  const int n_top = in.n_top;
+  if (!in.from_hbm) in.n_top = 0;
+  PtLdsLayout l = pt_lds_layout(in);
+  std::fprintf(f, "\"k_trace\":{");
+  put_image(f, l); put_int(f, "top", (long long)l.top); put_int(f, "total", (long long)l.total, "},");
+  in.n_top = n_top;
+  in.waves = waves;
+  in.from_hbm = hbm;
+  in.kernel = PT_LDS_K_BOUNCE;
+  l = pt_lds_layout(in);
+  std::fprintf(f, "\"k_bounce\":{");
+  put_image(f, l); put_int(f, "pool_off", (long long)l.pool_off); put_int(f, "pool_i", (long long)l.work.pool_i);
+  put_int(f, "pool_s", (long long)l.work.pool_s); put_int(f, "park0", (long long)l.work.park0); put_int(f, "park_uv", (long long)l.work.park_uv);
+  put_int(f, "park_w", (long long)l.work.park_w); put_int(f, "total", (long long)l.total); put_int(f, "fits", l.fits, "},");
+  in.kernel = PT_LDS_K_BOUNCE_CARRY;
+  in.from_hbm = 0; /* (k_bounce_carry is for LDS-resident scenes only) */
+  l = pt_lds_layout(in);
+  std::fprintf(f, "\"k_bounce_carry\":{");
+  put_image(f, l); put_int(f, "pool_off", (long long)l.pool_off); put_int(f, "park0", (long long)l.work.park0);
+  put_int(f, "park_emit", (long long)l.work.park_emit); put_int(f, "park_uv", (long long)l.work.park_uv);
+  put_int(f, "total", (long long)l.total); put_int(f, "fits", l.fits, "}}\n");
+  return 0;
+}
+
 /* ---- hostile ---- */
 static int g_accepted = 0;
 static void expect_rejected(const char* what, const ptx_scene_desc& d) {
@@ -298,6 +383,7 @@ int main(int argc, char** argv) {
     return rc;
   }
   if (mode == "arrays") return arrays_mode(argc, argv);
+  if (mode == "layout") return layout_mode(argc, argv);
   if (mode == "png") {
     const int w = 37, h = 11;
     std::vector<double> img((size_t)w * h * 3);
