@@ -184,6 +184,27 @@ constexpr int kMaxSets = 4; /* batches in flight (one HIP stream and one workspa
 /* per bounce kWorkPerBounce words: [0..7] trace feed, [16 + 8 c ..] shade feed of category c (5), [56..60] category list lengths */
 constexpr size_t kSoloFlagWord = 130; /* (counts[0 .. 127] are the bounces' queue counts) k_bounce's PtSolo.flag */
 constexpr size_t kWorkBase = 136, kWorkPerBounce = 64, kCountsWords = kWorkBase + 128 * kWorkPerBounce;
+/* block numbers are 20 bits next to a 12-bit cursor (pt_pool_push); 0xfffff = "no block yet" */
+constexpr size_t kPoolMaxEntries = (size_t)(PT_POOL_NO_BLOCK - 1) * PT_POOL_BLOCK;
+
+/* How a scene's bounces are launched while `sets_in_flight` batches share the chip: every answer the launch path needs.  Computed in one
+ * place (make_schedule) where sets_in_flight, the lighting mode or the uploaded scene changes, and only read in between: by the
+ * workspace's sizes, the bounce loop and the four launch functions, which therefore cannot disagree within a render. */
+struct Schedule {
+  int placement = PT_PLACE_HBM_SHARED; /* where k_trace walks the scene from (pt_lds_placement at k_trace's workgroup size) */
+  bool from_hbm = false;       /* the fused kernel runs as k_bounce<..., LDS_SCENE = false> over the per-octant image in HBM / L2 */
+  bool share_cus = false;      /* two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half a CU */
+  bool lit = false;            /* emitters under lighting mode 1 or 2: the LIT instantiations */
+  bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
+  bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
+  bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
+  int top_in_lds = 0;          /* k_trace from HBM / L2 keeps the tree's top in LDS */
+  int trace_threads = 0, bounce_threads = 0; /* workgroups of k_trace; of k_bounce and k_bounce_carry */
+  size_t trace_lds = 0;        /* dynamic LDS of a k_trace launch */
+  PtLdsLayout bounce{}, carry{}; /* dynamic LDS of a k_bounce, of a k_bounce_carry launch */
+  bool in_lds() const { return placement == PT_PLACE_LDS; }
+  bool fused_ok(size_t cap_entries) const { return fused_possible && cap_entries < kPoolMaxEntries; } /* ... with queues of this capacity */
+};
 
 struct ptx_scene {
   int device = 0;
@@ -265,19 +286,18 @@ struct ptx_scene {
   int grid_div = 1; /* 2 while two batches run concurrently on two streams */
   /* LDS-resident scenes: queued rays of bounces 1 .. bounce_packet also walk the tree as wave packets (0 = camera rays only) */
   int bounce_packet = env_int("PTX_BOUNCE_PACKET", 0);
-  int cur_bounce = 0;
-  uint4* cur_susp = nullptr;                         /* the launching workspace set's parked-walk buffer */
-  int sets_in_flight = 1;                            /* batches sharing the chip during the current render */
+  int sets_in_flight = 1;                            /* batches sharing the chip during the current render ... */
+  Schedule sched;                                    /* ... and how its bounces are launched: written together, by reschedule() */
   /* the last render_raw ran its batch(es) on the caller's stream with workspace set 0 (one set): the lanes of the next one must not
    * start before that stream (slices of different lengths, ptx_render_passes_device, can alternate between one set and two) */
   bool single_set_last = false;
-  int trace_block = env_int("PTX_TRACE_BLOCK", 0); /* 0 = by schedule (trace_block_lds) */
+  int trace_block = env_int("PTX_TRACE_BLOCK", 0); /* 0 = by schedule (make_schedule) */
   int fused = env_int("PTX_FUSED", 2);             /* LDS-resident scenes: one kernel per bounce (k_bounce: walk + shade in the same wave) -- 2: every bounce, 1: all but the camera rays', 0: k_trace + k_shade_pool */
   int bounce_fence_wg = env_int("PTX_BOUNCE_FENCE_WG", 0); /* k_bounce: 1 = workgroup-scope fences around a wave's own records (the safety net; tests run both) */
   int solo_entries = env_int("PTX_SOLO_ENTRIES", 0); /* k_bounce: a launch whose input queue holds at most this many entries runs the batch's remaining bounces by itself (0 = off) */
   int fused_global = env_int("PTX_FUSED_GLOBAL", 1); /* scenes walked from HBM / L2: 1 = k_bounce<..., LDS_SCENE = false> instead of k_trace + k_shade_pool */
-  int bounce_order = env_int("PTX_BOUNCE_ORDER", 2); /* LDS-resident scenes, PTX_FUSED=2: 1 = a bounce launch shades its input's carried hits first and walks the new rays second (k_bounce_carry), 0 = walk first (k_bounce), 2 = by scene (carry_possible) */
-  int primary_walk = env_int("PTX_PRIMARY_WALK", 2); /* LDS-resident scenes, the camera launch of k_bounce / k_bounce_carry: 0 = the tile walks as a wave packet (pt_trace_packet), 1 = one ray per lane (pt_trace_ray), 2 = by scene (primary_lane_walk) */
+  int bounce_order = env_int("PTX_BOUNCE_ORDER", 2); /* LDS-resident scenes, PTX_FUSED=2: 1 = a bounce launch shades its input's carried hits first and walks the new rays second (k_bounce_carry), 0 = walk first (k_bounce), 2 = by scene (Schedule::carry_ok) */
+  int primary_walk = env_int("PTX_PRIMARY_WALK", 2); /* LDS-resident scenes, the camera launch of k_bounce / k_bounce_carry: 0 = the tile walks as a wave packet (pt_trace_packet), 1 = one ray per lane (pt_trace_ray), 2 = by scene (Schedule::lane_walk) */
   int bounce_threads = env_int("PTX_BOUNCE_THREADS", 0); /* k_bounce workgroup size (0 = PT_BOUNCE_THREADS; tests: 64 .. 1024) */
   int bounce_wgs = env_int("PTX_BOUNCE_WGS", 0);         /* k_bounce workgroups per launch (0 = one per CU; tests: a few, so that every wave walks hundreds of chunks) */
   int trace_top = env_int("PTX_TRACE_TOP", 0);     /* scenes walked from HBM / L2: 1 = keep the tree's top in LDS (measured: no gain, the top of the tree is hot in L1 anyway; DESIGN.md section 4) */
@@ -365,16 +385,6 @@ int strided_grid(const ptx_scene* s, size_t n, int block, int blocks_per_cu) {
 }
 
 constexpr int kTraceBlockGlobal = PT_TRACE_BLOCK_GLOBAL; /* traversal data in HBM/L2: u32 stacks */
-/* traversal data copied to LDS once per workgroup (u16 stacks): workgroup size by leaf kind */
-/* Simd_leaf scenes: 1024-thread workgroups when one batch runs alone (one LDS scene copy and one chunk counter per 16
- * waves: trace 22.4 ms against 24.4 ms with 512), 512-thread workgroups when two batches share the chip on two streams (the
- * dispatcher interleaves them with the other batch's shade workgroups at a finer grain: frame 37.3 ms against 38.6 ms).
- * The kernel is compiled for up to PT_TRACE_BLOCK_LDS threads and sizes everything from blockDim. */
-int trace_block_lds(const ptx_scene* s) {
-  if (s->dev.mode != PT_MODE_SIMD) return PT_TRACE_BLOCK_LDS_ARRAY;
-  const int b = s->trace_block > 0 ? s->trace_block : (s->sets_in_flight >= 2 ? 512 : PT_TRACE_BLOCK_LDS);
-  return std::min(PT_TRACE_BLOCK_LDS, std::max(64, b & ~63));
-}
 static_assert(PT_TRACE_BLOCK_LDS <= 64 * PT_LDS_MAX_WAVES && PT_BOUNCE_THREADS <= 64 * PT_LDS_MAX_WAVES, "pt_lds_layout.h bounds node addresses for workgroups of PT_LDS_MAX_WAVES waves");
 
 /* Once per instantiation: a kernel's real static LDS must leave the room the layout counts on -- `reserve` bytes beside the largest
@@ -387,6 +397,14 @@ void check_static_lds(const void* kern, const char* name, bool lds_scene, size_t
             lds_scene ? ", PT_LDS_STATIC_MAX in front of the scene image" : "");
     abort(); /* a build error (a new __shared__ array), caught on the first launch of any test */
   }
+}
+/* A kernel's first launch on this scene's device: its dynamic-LDS limit goes up to the family's `dynamic_limit` (the rest of the
+ * CU's 160 KB is the kernels' static words: chunk counters, bins, the floor triangles) and its static LDS is checked against the
+ * family's `reserve`.  The limit is a property of (kernel, device): remembered per scene, which is bound to one device */
+void prepare_kernel(ptx_scene* s, const void* kern, const char* name, bool lds_scene, size_t dynamic_limit, size_t reserve) {
+  if (!s->attr_done.insert(kern).second) return;
+  raise_dynamic_lds_limit(kern, (int)dynamic_limit);
+  check_static_lds(kern, name, lds_scene, reserve);
 }
 
 /* what pt_lds_layout.h needs to know of a launch of `kernel` (PT_LDS_K_*) with workgroups of `waves` waves */
@@ -405,14 +423,64 @@ PtLdsIn lds_in(const ptx_scene* s, int kernel, int waves, bool from_hbm = false,
   in.n_top = n_top;
   return in;
 }
-/* the traversal data fits an LDS copy (else: traverse from HBM/L2) */
-bool scene_in_lds(const ptx_scene* s) { return pt_lds_placement(lds_in(s, PT_LDS_K_TRACE, trace_block_lds(s) / 64)) == PT_PLACE_LDS; }
 
-/* Two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half of what a CU holds (launch_shade_pool).
- * Measured: headline frame 29.7 -> 27.4 ms, 4K spp 256 468 -> 429 ms.  Array_leaf scenes (cornell: the trace kernel needs
- * ~106 VGPRs, one workgroup would be left) and scenes walked from HBM / L2 lose 1-2 % and keep whole-CU grids. */
-bool share_cus(const ptx_scene* s) {
-  return s->sets_in_flight >= 2 && s->dev.mode == PT_MODE_SIMD && scene_in_lds(s);
+/* The one place that decides how a scene's bounces are launched while `sets` batches share the chip: every answer is a function of
+ * the scene (s->dev, the tree's depth), its PTX_* knobs and `sets`, and holds still for as long as none of them changes.  reschedule()
+ * below is the only writer of ptx_scene::sets_in_flight and ptx_scene::sched. */
+Schedule make_schedule(const ptx_scene* s, int sets) {
+  Schedule c;
+  const bool simd = s->dev.mode == PT_MODE_SIMD;
+  /* k_trace with the traversal data copied to LDS once per workgroup (u16 stacks): workgroup size by leaf kind */
+  /* Simd_leaf scenes: 1024-thread workgroups when one batch runs alone (one LDS scene copy and one chunk counter per 16
+   * waves: trace 22.4 ms against 24.4 ms with 512), 512-thread workgroups when two batches share the chip on two streams (the
+   * dispatcher interleaves them with the other batch's shade workgroups at a finer grain: frame 37.3 ms against 38.6 ms).
+   * The kernel is compiled for up to PT_TRACE_BLOCK_LDS threads and sizes everything from blockDim. */
+  int trace_block_lds = PT_TRACE_BLOCK_LDS_ARRAY;
+  if (simd) {
+    const int b = s->trace_block > 0 ? s->trace_block : (sets >= 2 ? 512 : PT_TRACE_BLOCK_LDS);
+    trace_block_lds = std::min(PT_TRACE_BLOCK_LDS, std::max(64, b & ~63));
+  }
+  /* the traversal data fits an LDS copy (else: traverse from HBM/L2).  8 or 16 waves of stacks can decide it: a one-set and a two-set
+   * render of the same scene may be placed differently */
+  c.placement = pt_lds_placement(lds_in(s, PT_LDS_K_TRACE, trace_block_lds / 64));
+  const bool in_lds = c.in_lds();
+  /* Two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half of what a CU holds (launch_shade_pool).
+   * Measured: headline frame 29.7 -> 27.4 ms, 4K spp 256 468 -> 429 ms.  Array_leaf scenes (cornell: the trace kernel needs
+   * ~106 VGPRs, one workgroup would be left) and scenes walked from HBM / L2 lose 1-2 % and keep whole-CU grids. */
+  c.share_cus = sets >= 2 && simd && in_lds;
+  /* An emissive scene in lighting mode 1 or 2 (PtSceneDev.lighting holds the mode in effect: mode 1 without emitters is mode 0): the
+   * instantiations flagged LIT.  Such a scene takes the walk-first kernel and never runs solo. */
+  c.lit = s->dev.lighting != 0 && s->dev.has_emit != 0;
+  /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
+  c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
+  c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
+  c.trace_lds = pt_lds_layout(lds_in(s, PT_LDS_K_TRACE, c.trace_threads / 64, !in_lds, c.top_in_lds ? s->dev.n_top : 0)).total;
+  /* k_bounce: a bounce of an LDS-resident scene as ONE launch (walk + pooled shade in the same wave), counting renders
+   * included (its COUNT instantiations); the scenes walked from HBM / L2 keep the two kernels */
+  /* scenes walked from HBM / L2 run k_bounce<..., LDS_SCENE = false> over the per-octant node image (PTX_FUSED_GLOBAL=0: k_trace + k_shade_pool) */
+  c.from_hbm = !in_lds && s->dev.nodes32o != nullptr && s->fused_global != 0 && !(s->dev.n_top > 0 && s->trace_top);
+  c.bounce_threads = s->bounce_threads > 0 ? std::min(PT_BOUNCE_THREADS, std::max(64, s->bounce_threads & ~63))
+                                           : (c.from_hbm ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS);
+  /* the dynamic LDS of a k_bounce and of a k_bounce_carry launch: total, pool_off and whether it fits (PT_LDS_BOUNCE_LIMIT) */
+  c.bounce = pt_lds_layout(lds_in(s, PT_LDS_K_BOUNCE, c.bounce_threads / 64, c.from_hbm));
+  c.carry = pt_lds_layout(lds_in(s, PT_LDS_K_BOUNCE_CARRY, c.bounce_threads / 64, c.from_hbm));
+  c.fused_possible = s->fused && (in_lds || c.from_hbm) && c.bounce.fits;
+  /* the shade-first order (k_bounce_carry) is for LDS-resident scenes whose larger parked record still fits, with every bounce a
+   * k_bounce launch and no solo run configured.  By default (PTX_BOUNCE_ORDER=2) the scenes binned by elevation take it -- open
+   * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
+   * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
+   * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
+  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && s->fused >= 2 && s->solo_entries <= 0 &&
+               in_lds && !c.from_hbm && c.carry.fits;
+  /* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
+   * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
+   * scenes, which have no such loop, keep the wave packet (DESIGN.md Appendix A).  1 = per lane everywhere, 0 = the packet everywhere */
+  c.lane_walk = s->primary_walk == 1 || (s->primary_walk >= 2 && simd);
+  return c;
+}
+void reschedule(ptx_scene* s, int sets) {
+  s->sets_in_flight = sets;
+  s->sched = make_schedule(s, sets);
 }
 
 struct PrimaryLaunch {
@@ -421,27 +489,106 @@ struct PrimaryLaunch {
   uint32_t n = 0;
 };
 
-template <int MODE, bool COUNT, bool PRIMARY, bool LDS_SCENE>
-void launch_trace_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper,
-                       const PrimaryLaunch& pl, uint32_t* work) {
+/* ---- one selector per kernel family: the runtime facts of a launch -> the instantiation, as a pointer of the family's one function
+ * type.  Each instantiation is named exactly once, in its selector, so the text below IS the set the library is built with; a name
+ * more is a kernel more (minutes of build, megabytes of code object).  The order of the names is the order of the kernels in the code
+ * object (a kernel is emitted where it is first named; profiles/pr_launch_schedule_identity.txt): moving one moves code, nothing else. ---- */
+using TraceKernel = decltype(&k_trace<PT_MODE_SIMD, false, false, false, false>);
+using ShadePoolKernel = decltype(&k_shade_pool<false, false>);
+using CarryKernel = decltype(&k_bounce_carry<PT_MODE_SIMD, false, false, false>);
+using BounceKernel = decltype(&k_bounce<PT_MODE_SIMD, false, false, false>);
+enum class Shading { none, emit, lit };          /* no emitters; emitters summed as the reference does; emitters under lighting mode 1 or 2 (LIT implies EMIT) */
+enum class Variant { plain, solo, lane_walk };   /* k_bounce: with the loop over a batch's remaining bounces (PtSolo); camera rays one per lane */
+
+/* k_trace: 32 = MODE 2 x COUNT 2 x PRIMARY 2 x LDS_SCENE 2 x PACKET 2, the whole cube.  PACKET is the wave-packet walk on an LDS scene
+ * and the per-octant node image on a walk from HBM / L2, so both values occur on both sides. */
+template <int MODE, bool COUNT>
+TraceKernel trace_kernel_of(bool primary, bool lds_scene, bool packet) {
+  if (primary && lds_scene) return packet ? k_trace<MODE, COUNT, true, true, true> : k_trace<MODE, COUNT, true, true, false>;
+  if (primary) return packet ? k_trace<MODE, COUNT, true, false, true> : k_trace<MODE, COUNT, true, false, false>;
+  if (lds_scene) return packet ? k_trace<MODE, COUNT, false, true, true> : k_trace<MODE, COUNT, false, true, false>;
+  return packet ? k_trace<MODE, COUNT, false, false, true> : k_trace<MODE, COUNT, false, false, false>;
+}
+TraceKernel trace_kernel(int mode, bool count, bool primary, bool lds_scene, bool packet) {
+  if (mode == PT_MODE_SIMD) return count ? trace_kernel_of<PT_MODE_SIMD, true>(primary, lds_scene, packet) : trace_kernel_of<PT_MODE_SIMD, false>(primary, lds_scene, packet);
+  return count ? trace_kernel_of<PT_MODE_ARRAY, true>(primary, lds_scene, packet) : trace_kernel_of<PT_MODE_ARRAY, false>(primary, lds_scene, packet);
+}
+
+/* k_shade_pool: 6 = (EMIT, LIT) in {00, 10, 11} x PRIMARY 2 */
+ShadePoolKernel shade_pool_kernel(Shading shading, bool primary) {
+  if (shading == Shading::lit) return primary ? k_shade_pool<true, true, true> : k_shade_pool<true, false, true>;
+  if (shading == Shading::emit) return primary ? k_shade_pool<true, true> : k_shade_pool<true, false>;
+  return primary ? k_shade_pool<false, true> : k_shade_pool<false, false>;
+}
+
+/* k_bounce_carry: 24 = MODE 2 x COUNT 2 x EMIT 2 x (PRIMARY, LANE_WALK) in {00, 10, 11}: only camera rays walk one per lane (a
+ * lane walk asked of a queued launch is the plain kernel), and a lit scene never takes this kernel (Schedule::carry_ok) */
+template <int MODE, bool COUNT>
+CarryKernel carry_kernel_of(bool emit, bool primary, bool lane_walk) {
+  if (emit) {
+    if (primary) return lane_walk ? k_bounce_carry<MODE, COUNT, true, true, true> : k_bounce_carry<MODE, COUNT, true, true>;
+    return k_bounce_carry<MODE, COUNT, true, false>;
+  }
+  if (primary) return lane_walk ? k_bounce_carry<MODE, COUNT, false, true, true> : k_bounce_carry<MODE, COUNT, false, true>;
+  return k_bounce_carry<MODE, COUNT, false, false>;
+}
+CarryKernel carry_kernel(int mode, bool count, bool emit, bool primary, bool lane_walk) {
+  if (mode == PT_MODE_SIMD) return count ? carry_kernel_of<PT_MODE_SIMD, true>(emit, primary, lane_walk) : carry_kernel_of<PT_MODE_SIMD, false>(emit, primary, lane_walk);
+  return count ? carry_kernel_of<PT_MODE_ARRAY, true>(emit, primary, lane_walk) : carry_kernel_of<PT_MODE_ARRAY, false>(emit, primary, lane_walk);
+}
+
+/* k_bounce: 76 = MODE 2 x COUNT 2 x 19, the 19 being 7 + 7 + 5 by shading.
+ *   none, emit: 7 = a camera launch {plain, lane walk} on an LDS scene and {plain} from HBM / L2, a queued launch {plain, solo} x {LDS, HBM}
+ *   lit:        5 = the same without the two solo kernels (a lit scene never runs solo)
+ * A variant the family does not have is the plain kernel: a lane walk off a camera launch or off LDS, solo on a camera launch or a
+ * lit scene.  Template arguments: <MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, SOLO_T, LIT, LANE_WALK>.  (With emitters the lit kernels stand
+ * beside the unlit plain ones, row by row, and the unlit variants behind them: the order these kernels have always been emitted in.) */
+template <int MODE, bool COUNT>
+BounceKernel bounce_kernel_of(Shading shading, bool primary, bool lds_scene, Variant variant) {
+  const bool lit = shading == Shading::lit;
+  const bool lane_walk = variant == Variant::lane_walk && primary && lds_scene, solo = variant == Variant::solo && !primary && !lit;
+  if (shading != Shading::none) {
+    if (lit || !(lane_walk || solo)) { /* what a lit scene can get, beside the unlit plain kernel of the same launch */
+      if (primary && !lds_scene) return !lit ? k_bounce<MODE, COUNT, true, true, false> : k_bounce<MODE, COUNT, true, true, false, false, true>;
+      if (primary && !lane_walk) return !lit ? k_bounce<MODE, COUNT, true, true, true> : k_bounce<MODE, COUNT, true, true, true, false, true>;
+      if (primary) return k_bounce<MODE, COUNT, true, true, true, false, true, true>;
+      if (!lds_scene) return !lit ? k_bounce<MODE, COUNT, true, false, false> : k_bounce<MODE, COUNT, true, false, false, false, true>;
+      return !lit ? k_bounce<MODE, COUNT, true, false, true> : k_bounce<MODE, COUNT, true, false, true, false, true>;
+    }
+    if (lane_walk) return k_bounce<MODE, COUNT, true, true, true, false, false, true>;
+    return !lds_scene ? k_bounce<MODE, COUNT, true, false, false, true> : k_bounce<MODE, COUNT, true, false, true, true>;
+  }
+  if (primary && !lds_scene) return k_bounce<MODE, COUNT, false, true, false>;
+  if (primary) return !lane_walk ? k_bounce<MODE, COUNT, false, true, true> : k_bounce<MODE, COUNT, false, true, true, false, false, true>;
+  if (!lds_scene) return solo ? k_bounce<MODE, COUNT, false, false, false, true> : k_bounce<MODE, COUNT, false, false, false>;
+  return solo ? k_bounce<MODE, COUNT, false, false, true, true> : k_bounce<MODE, COUNT, false, false, true>;
+}
+BounceKernel bounce_kernel(int mode, bool count, Shading shading, bool primary, bool lds_scene, Variant variant) {
+  if (mode == PT_MODE_SIMD) return count ? bounce_kernel_of<PT_MODE_SIMD, true>(shading, primary, lds_scene, variant) : bounce_kernel_of<PT_MODE_SIMD, false>(shading, primary, lds_scene, variant);
+  return count ? bounce_kernel_of<PT_MODE_ARRAY, true>(shading, primary, lds_scene, variant) : bounce_kernel_of<PT_MODE_ARRAY, false>(shading, primary, lds_scene, variant);
+}
+Shading scene_shading(const ptx_scene* s) { return s->sched.lit ? Shading::lit : (s->dev.has_emit ? Shading::emit : Shading::none); }
+
+/* ---- one launch function per family: the kernel by its selector, prepared once, then grid, block and LDS from the schedule ---- */
+constexpr int kNoBounce = -1; /* launch_trace: the rays are not a numbered bounce of a render (ptx_intersect_rays) */
+/* work: 8 zeroed hand-out counters of this launch (PtChunkFeed); susp: the parked-walk buffer of the launching workspace set; bounce:
+ * 0 for camera rays, b >= 1 for the queued rays of bounce b, kNoBounce */
+void launch_trace(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper, bool count, uint32_t* work,
+                  uint4* susp, int bounce, const PrimaryLaunch& pl = PrimaryLaunch()) {
+  const Schedule& sc = s->sched;
+  const bool lds_scene = sc.in_lds();
   const int stack_depth = std::max(1, s->tree_depth + 1);
-  /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
-  const int top_in_lds = (!LDS_SCENE && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
-  const int kTraceBlock = LDS_SCENE ? trace_block_lds(s) : PT_TRACE_BLOCK_OF(MODE, LDS_SCENE);
-  const size_t lds = pt_lds_layout(lds_in(s, PT_LDS_K_TRACE, kTraceBlock / 64, !LDS_SCENE, top_in_lds ? s->dev.n_top : 0)).total;
+  const int kTraceBlock = sc.trace_threads;
+  const size_t lds = sc.trace_lds;
   /* from HBM/L2 one shared node fetch per step serialises the latency (-3 %): packets only on LDS-resident scenes */
   /* (the same template switch selects the per-octant node image on scenes walked from HBM / L2: k_trace) */
-  const bool packet = LDS_SCENE ? (PRIMARY ? true : (s->cur_bounce >= 1 && s->cur_bounce <= s->bounce_packet))
-                                : (s->dev.nodes32o != nullptr && !top_in_lds);
-  auto kern = packet ? k_trace<MODE, COUNT, PRIMARY, LDS_SCENE, true> : k_trace<MODE, COUNT, PRIMARY, LDS_SCENE, false>;
-  /* the dynamic-LDS limit is a property of (kernel, device): remembered per scene, which is bound to one device */
-  if (s->attr_done.insert((const void*)kern).second) {
-    raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
-    check_static_lds((const void*)kern, "k_trace", LDS_SCENE, 1024);
-  }
-  int blocks_per_cu = LDS_SCENE ? std::min(4, std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(lds, 1)))) : (PT_TRACE_GLOBAL_WAVES * 256) / kTraceBlockGlobal; /* what the registers admit: no stack in LDS any more */
+  const bool packet = lds_scene ? (pl.on ? true : (bounce >= 1 && bounce <= s->bounce_packet))
+                                : (s->dev.nodes32o != nullptr && !sc.top_in_lds);
+  const TraceKernel kern = trace_kernel(s->dev.mode, count, pl.on, lds_scene, packet);
+  prepare_kernel(s, (const void*)kern, "k_trace", lds_scene, 160 * 1024 - 1024, 1024);
+  int blocks_per_cu = lds_scene ? std::min(4, std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(lds, 1)))) : (PT_TRACE_GLOBAL_WAVES * 256) / kTraceBlockGlobal; /* what the registers admit: no stack in LDS any more */
   if (s->trace_wgs_per_cu > 0) blocks_per_cu = std::min(4, s->trace_wgs_per_cu); /* `susp` is sized for 4 */
-  else if (share_cus(s)) {
+  else if (sc.share_cus) {
     /* half of the CU's wave slots (see launch_shade_pool): two 512-thread workgroups, as long as their scene copies fit
      * beside the pools of the shade stage's two 256-thread workgroups (20.5 KB each).  Measured (round 3): the two-stream
      * frame is flat in the size of the scene copy up to that limit and 3-5 ms slower beyond it (108-byte nodes, or 48-byte
@@ -451,190 +598,57 @@ void launch_trace_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
     blocks_per_cu = std::max(1, std::min(std::min(blocks_per_cu, by_lds), 2 * (512 / std::max(64, kTraceBlock))));
   }
   const int grid = strided_grid(s, n_upper, kTraceBlock, blocks_per_cu);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), lds, st, s->dev, q, h, stack_depth, s->counters.p, pl.g, s->alpha.p, pl.n, work, s->cur_susp, top_in_lds);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), lds, st, s->dev, q, h, stack_depth, s->counters.p, pl.g, s->alpha.p, pl.n, work, susp, sc.top_in_lds);
 }
 
-template <int MODE, bool COUNT, bool PRIMARY>
-void launch_trace_lds(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper, const PrimaryLaunch& pl, uint32_t* work) {
-  if (scene_in_lds(s)) launch_trace_inst<MODE, COUNT, PRIMARY, true>(s, st, q, h, n_upper, pl, work);
-  else launch_trace_inst<MODE, COUNT, PRIMARY, false>(s, st, q, h, n_upper, pl, work);
-}
-template <int MODE>
-void launch_trace_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper, bool count, const PrimaryLaunch& pl, uint32_t* work) {
-  if (count) {
-    if (pl.on) launch_trace_lds<MODE, true, true>(s, st, q, h, n_upper, pl, work);
-    else launch_trace_lds<MODE, true, false>(s, st, q, h, n_upper, pl, work);
-  } else {
-    if (pl.on) launch_trace_lds<MODE, false, true>(s, st, q, h, n_upper, pl, work);
-    else launch_trace_lds<MODE, false, false>(s, st, q, h, n_upper, pl, work);
-  }
-}
-/* work: 8 zeroed hand-out counters of this launch (PtChunkFeed) */
-void launch_trace(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, size_t n_upper, bool count,
-                  uint32_t* work, const PrimaryLaunch& pl = PrimaryLaunch()) {
-  if (s->dev.mode == PT_MODE_SIMD) launch_trace_mode<PT_MODE_SIMD>(s, st, q, h, n_upper, count, pl, work);
-  else launch_trace_mode<PT_MODE_ARRAY>(s, st, q, h, n_upper, count, pl, work);
-}
-
-/* An emissive scene in lighting mode 1 or 2 (PtSceneDev.lighting holds the mode in effect: mode 1 without emitters is mode 0): the
- * instantiations flagged LIT.  Such a scene takes the walk-first kernel and never runs solo. */
-bool scene_lit(const ptx_scene* s) { return s->dev.lighting != 0 && s->dev.has_emit != 0; }
-
-/* k_shade_pool leaves holes in its output queue (part-filled blocks): at most one block per (workgroup, bin) */
-/* block numbers are 20 bits next to a 12-bit cursor (pt_pool_push); 0xfffff = "no block yet" */
-constexpr size_t kPoolMaxEntries = (size_t)(PT_POOL_NO_BLOCK - 1) * PT_POOL_BLOCK;
-/* workgroup of k_shade_pool: 256 threads when two batches share every CU (share_cus), else 512 */
-int pool_threads(const ptx_scene* s) { return share_cus(s) ? 256 : PT_POOL_THREADS; }
 /* k_shade_pool leaves holes in its output queue (part-filled blocks): at most one block per (workgroup, bin) */
 size_t shade_pool_slack(const ptx_scene* s) { return (size_t)s->n_cu * (1024 / 256) * PT_POOL_BINS * PT_POOL_BLOCK; }
 void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out,
                        const PtContrib& c, size_t n_upper, int bounce, int last, uint32_t* work, const PrimaryLaunch& pl) {
+  const Schedule& sc = s->sched;
   /* 128 VGPRs: 16 waves per CU.  With two batches in flight each kernel takes HALF of what a CU holds, so that one batch's
    * trace workgroups (vector-issue-bound) and the other's shade workgroups (bound by the memory system) are resident on every
    * CU together instead of taking turns at the chip */
-  const int threads = pool_threads(s);
+  const int threads = sc.share_cus ? 256 : PT_POOL_THREADS; /* 256 threads when two batches share every CU, else 512 */
   const int most = 1024 / threads;
-  const int per_cu = s->shade_wgs_per_cu > 0 ? std::min(s->shade_wgs_per_cu, most) : (share_cus(s) ? std::max(1, most / 2) : most);
+  const int per_cu = s->shade_wgs_per_cu > 0 ? std::min(s->shade_wgs_per_cu, most) : (sc.share_cus ? std::max(1, most / 2) : most);
   const int grid = strided_grid(s, n_upper, threads, per_cu);
-  const dim3 gd(grid), bd(threads);
   const size_t lds = pt_lds_shade_pool_bytes(threads / 64);
-  if (scene_lit(s)) {
-    if (pl.on) hipLaunchKernelGGL((k_shade_pool<true, true, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-    else hipLaunchKernelGGL((k_shade_pool<true, false, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-  } else if (s->dev.has_emit) {
-    if (pl.on) hipLaunchKernelGGL((k_shade_pool<true, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-    else hipLaunchKernelGGL((k_shade_pool<true, false>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-  } else {
-    if (pl.on) hipLaunchKernelGGL((k_shade_pool<false, true>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-    else hipLaunchKernelGGL((k_shade_pool<false, false>), gd, bd, lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
-  }
+  hipLaunchKernelGGL(shade_pool_kernel(scene_shading(s), pl.on), dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
 }
 
-/* k_bounce: a bounce of an LDS-resident scene as ONE launch (walk + pooled shade in the same wave), counting renders
- * included (its COUNT instantiations); the scenes walked from HBM / L2 keep the two kernels */
-/* scenes walked from HBM / L2 run k_bounce<..., LDS_SCENE = false> over the per-octant node image (PTX_FUSED_GLOBAL=0: k_trace + k_shade_pool) */
-bool bounce_from_hbm(const ptx_scene* s) {
-  return !scene_in_lds(s) && s->dev.nodes32o != nullptr && s->fused_global != 0 && !(s->dev.n_top > 0 && s->trace_top);
-}
-int bounce_threads(const ptx_scene* s) {
-  const int dflt = bounce_from_hbm(s) ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS;
-  return s->bounce_threads > 0 ? std::min(PT_BOUNCE_THREADS, std::max(64, s->bounce_threads & ~63)) : dflt;
-}
-/* the dynamic LDS of a k_bounce (carry: k_bounce_carry) launch: total, pool_off and whether it fits (PT_LDS_BOUNCE_LIMIT) */
-PtLdsLayout bounce_layout(const ptx_scene* s, bool carry = false) {
-  return pt_lds_layout(lds_in(s, carry ? PT_LDS_K_BOUNCE_CARRY : PT_LDS_K_BOUNCE, bounce_threads(s) / 64, bounce_from_hbm(s)));
-}
-bool use_fused(const ptx_scene* s, size_t cap_entries) {
-  return s->fused && cap_entries < kPoolMaxEntries && (scene_in_lds(s) || bounce_from_hbm(s)) &&
-         bounce_layout(s).fits;
-}
-/* the shade-first order (k_bounce_carry) is for LDS-resident scenes whose larger parked record still fits, with every bounce a
- * k_bounce launch and no solo run configured.  By default (PTX_BOUNCE_ORDER=2) the scenes binned by elevation take it -- open
- * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
- * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
- * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
-bool carry_possible(const ptx_scene* s) {
-  return (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !scene_lit(s) && s->fused >= 2 && s->solo_entries <= 0 && scene_in_lds(s) && !bounce_from_hbm(s) &&
-         bounce_layout(s, true).fits;
-}
-/* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
- * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
- * scenes, which have no such loop, keep the wave packet (DESIGN.md Appendix A).  1 = per lane everywhere, 0 = the packet everywhere */
-bool primary_lane_walk(const ptx_scene* s) {
-  return s->primary_walk == 1 || (s->primary_walk >= 2 && s->dev.mode == PT_MODE_SIMD);
-}
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false>
-void launch_carry_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
-                       const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
-  const int stack_depth = std::max(1, s->tree_depth + 1);
-  const PtLdsLayout lds = bounce_layout(s, true);
-  auto kern = k_bounce_carry<MODE, COUNT, EMIT, PRIMARY, LANE_WALK>;
-  if (s->attr_done.insert((const void*)kern).second) {
-    raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
-    check_static_lds((const void*)kern, "k_bounce_carry", true, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
-  }
-  const int threads = bounce_threads(s);
-  int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
-  if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
-                     (uint32_t)lds.pool_off, s->counters.p, s->bounce_fence_wg);
-}
-template <int MODE, bool COUNT>
-void launch_carry_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
-                       const PtContrib& c, size_t n_upper, int bounce, int last, const PrimaryLaunch& pl) {
-  if (s->dev.has_emit) {
-    if (pl.on && primary_lane_walk(s)) launch_carry_inst<MODE, COUNT, true, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else if (pl.on) launch_carry_inst<MODE, COUNT, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else launch_carry_inst<MODE, COUNT, true, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-  } else {
-    if (pl.on && primary_lane_walk(s)) launch_carry_inst<MODE, COUNT, false, true, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else if (pl.on) launch_carry_inst<MODE, COUNT, false, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else launch_carry_inst<MODE, COUNT, false, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-  }
-}
 void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
                          const PtContrib& c, size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl) {
-  if (s->dev.mode == PT_MODE_SIMD) {
-    if (count) launch_carry_mode<PT_MODE_SIMD, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else launch_carry_mode<PT_MODE_SIMD, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-  } else {
-    if (count) launch_carry_mode<PT_MODE_ARRAY, true>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-    else launch_carry_mode<PT_MODE_ARRAY, false>(s, st, q, h, out, hout, c, n_upper, bounce, last, pl);
-  }
-}
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE, bool LIT>
-void launch_bounce_where(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
-                         size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
+  const Schedule& sc = s->sched;
   const int stack_depth = std::max(1, s->tree_depth + 1);
-  const PtLdsLayout lds = bounce_layout(s);
-  /* the instantiation with the loop over a batch's remaining bounces (PtSolo) only where it can be taken */
-  /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
-  /* (camera rays of an LDS-resident scene: the packet walk or one ray per lane, primary_lane_walk) */
-  auto kern = (PRIMARY && LDS_SCENE && primary_lane_walk(s)) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT, PRIMARY && LDS_SCENE>
-            : LIT ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false, LIT>
-                  : ((solo.flag != nullptr && !PRIMARY) ? k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, !PRIMARY && !LIT> : k_bounce<MODE, COUNT, EMIT, PRIMARY, LDS_SCENE, false>);
-  if (s->attr_done.insert((const void*)kern).second) {
-    raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 256));
-    check_static_lds((const void*)kern, "k_bounce", LDS_SCENE, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
-  }
-  const int threads = bounce_threads(s);
-  /* LDS scenes: one workgroup (one scene image) per CU; walks from HBM / L2: what the registers admit (PT_BOUNCE_WAVES per SIMD) --
-   * shade_pool_slack and the parked-walk buffer are sized for 4 workgroups per CU */
-  const int per_cu = LDS_SCENE ? 1 : std::max(1, std::min(4, (PT_BOUNCE_WAVES * 256) / threads));
-  int grid = strided_grid(s, n_upper, threads, per_cu);
+  const CarryKernel kern = carry_kernel(s->dev.mode, count, s->dev.has_emit != 0, pl.on, sc.lane_walk);
+  prepare_kernel(s, (const void*)kern, "k_bounce_carry", true, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
+  const int threads = sc.bounce_threads;
+  int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds.total, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
-                     (uint32_t)lds.pool_off, s->counters.p, s->bounce_fence_wg, solo);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), sc.carry.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
+                     (uint32_t)sc.carry.pool_off, s->counters.p, s->bounce_fence_wg);
 }
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LIT>
-void launch_bounce_inst(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
-                        size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (bounce_from_hbm(s)) launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, false, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  else launch_bounce_where<MODE, COUNT, EMIT, PRIMARY, true, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-}
-template <int MODE, bool COUNT, bool EMIT, bool LIT = false>
-void launch_bounce_mode(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
-                        size_t n_upper, int bounce, int last, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (pl.on) launch_bounce_inst<MODE, COUNT, EMIT, true, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  else launch_bounce_inst<MODE, COUNT, EMIT, false, LIT>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-}
-template <int MODE>
-void launch_bounce_count(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
-                         size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (count) {
-    if (scene_lit(s)) launch_bounce_mode<MODE, true, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-    else if (s->dev.has_emit) launch_bounce_mode<MODE, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-    else launch_bounce_mode<MODE, true, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  } else {
-    if (scene_lit(s)) launch_bounce_mode<MODE, false, true, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-    else if (s->dev.has_emit) launch_bounce_mode<MODE, false, true>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-    else launch_bounce_mode<MODE, false, false>(s, st, q, h, out, c, n_upper, bounce, last, pl, solo);
-  }
-}
+
 void launch_bounce(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
                    size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl, const PtSolo& solo) {
-  if (s->dev.mode == PT_MODE_SIMD) launch_bounce_count<PT_MODE_SIMD>(s, st, q, h, out, c, n_upper, bounce, last, count, pl, solo);
-  else launch_bounce_count<PT_MODE_ARRAY>(s, st, q, h, out, c, n_upper, bounce, last, count, pl, solo);
+  const Schedule& sc = s->sched;
+  const bool lds_scene = !sc.from_hbm;
+  const int stack_depth = std::max(1, s->tree_depth + 1);
+  /* the instantiation with the loop over a batch's remaining bounces (PtSolo) only where it can be taken */
+  /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
+  /* (camera rays of an LDS-resident scene: the packet walk or one ray per lane, Schedule::lane_walk) */
+  const Variant variant = pl.on ? (sc.lane_walk ? Variant::lane_walk : Variant::plain) : (solo.flag != nullptr ? Variant::solo : Variant::plain);
+  const BounceKernel kern = bounce_kernel(s->dev.mode, count, scene_shading(s), pl.on, lds_scene, variant);
+  prepare_kernel(s, (const void*)kern, "k_bounce", lds_scene, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
+  const int threads = sc.bounce_threads;
+  /* LDS scenes: one workgroup (one scene image) per CU; walks from HBM / L2: what the registers admit (PT_BOUNCE_WAVES per SIMD) --
+   * shade_pool_slack and the parked-walk buffer are sized for 4 workgroups per CU */
+  const int per_cu = lds_scene ? 1 : std::max(1, std::min(4, (PT_BOUNCE_WAVES * 256) / threads));
+  int grid = strided_grid(s, n_upper, threads, per_cu);
+  if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), sc.bounce.total, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
+                     (uint32_t)sc.bounce.pool_off, s->counters.p, s->bounce_fence_wg, solo);
 }
 
 struct Workspace {
@@ -678,7 +692,7 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
     /* a launch runs solo (k_bounce, PtSolo) only if each queue could hold the worst case of every remaining bounce, and on a small
      * frame -- where it matters -- that is more than the paths themselves: room for a solo run from the first queued bounce on,
      * as far as 16 M extra entries go */
-    const size_t holes = (size_t)s->n_cu * (bounce_from_hbm(s) ? 4 : 1) * PT_POOL_BINS * PT_POOL_BLOCK;
+    const size_t holes = (size_t)s->n_cu * (s->sched.from_hbm ? 4 : 1) * PT_POOL_BINS * PT_POOL_BLOCK;
     const size_t n1 = std::min(cap_paths + holes, (size_t)s->solo_entries);
     const size_t worst = (size_t)((std::min(max_bounces, 16) - 1) / 2 + 1) * (n1 + holes) + n1 + PT_POOL_BLOCK;
     cap = std::max(cap, std::min(worst, cap + ((size_t)16 << 20)));
@@ -690,7 +704,7 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
   const bool hit_records = s->dev.has_triangles && want_hit_records;
   if (hit_records) HIP_TRY(b.hit_tuv.ensure(cap * 4));
   /* k_bounce_carry reads its input's hits while it writes its output's: entries of even and odd bounces in two halves */
-  const bool carry = carry_possible(s) && !hit_records;
+  const bool carry = s->sched.carry_ok && !hit_records;
   if (!hit_records) HIP_TRY(b.hit_t.ensure(((s->solo_entries > 0 || carry) && !s->dev.has_triangles) ? 2 * cap : cap)); /* (PtHits.t_parity_stride: a solo launch keeps the distances of even and odd bounces apart) */
   HIP_TRY(b.hit_slot.ensure(carry ? 2 * cap : cap));
   HIP_TRY(b.contrib.ensure(cap * 4));
@@ -727,15 +741,17 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
 void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int max_bounces, bool count, bool timed,
                  const PrimaryLaunch& pl, int run_only = -1) {
   const int n_run = run_only >= 0 ? run_only : max_bounces;
+  const Schedule& sc = s->sched;
+  const bool fused = sc.fused_ok(w.cap_entries);
   /* the shade-first order: a whole batch from its camera launch on (its launch b shades bounce b and walks bounce b + 1) */
-  const bool carry = pl.on && run_only < 0 && max_bounces >= 2 && w.carry_stride > 0 && carry_possible(s) && use_fused(s, w.cap_entries);
+  /* (w.carry_stride > 0: ensure_workspace sized the hit arrays for it, from the same Schedule) */
+  const bool carry = pl.on && run_only < 0 && max_bounces >= 2 && w.carry_stride > 0 && sc.carry_ok && fused;
   for (int b = 0; b < n_run; ++b) {
     PtQueue in = w.q[b & 1], out = w.q[(b + 1) & 1];
     in.count = w.counts + b;
     out.count = w.counts + b + 1;
     const PrimaryLaunch here = (b == 0) ? pl : PrimaryLaunch();
-    s->cur_bounce = here.on ? 0 : std::max(b, 1); /* list-mode bounce 0 (explicit samples) reads a queue like any bounce */
-    s->cur_susp = w.susp;
+    const int last = (b == max_bounces - 1) ? 1 : 0;
     if (carry) {
       LaunchTimer t(s, st, timed, PTX_KERNEL_BOUNCE);
       PtHits h_in = w.hits, h_out = w.hits;
@@ -745,30 +761,31 @@ void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int
         h_in.t += (size_t)(b & 1) * w.carry_stride;
         h_out.t += (size_t)((b + 1) & 1) * w.carry_stride;
       }
-      launch_bounce_carry(s, st, in, h_in, out, h_out, w.contrib, n_upper, b, b == max_bounces - 1 ? 1 : 0, count, here);
+      launch_bounce_carry(s, st, in, h_in, out, h_out, w.contrib, n_upper, b, last, count, here);
       continue;
     }
-    if ((!here.on || s->fused >= 2) && use_fused(s, w.cap_entries)) { /* PTX_FUSED=2: the camera rays' bounce too */
+    if ((!here.on || s->fused >= 2) && fused) { /* PTX_FUSED=2: the camera rays' bounce too */
       LaunchTimer t(s, st, timed, PTX_KERNEL_BOUNCE);
       /* PtSolo: the first launch whose input has shrunk to s->solo_entries runs the batch's remaining bounces by itself, the
        * later ones return at once (the flag: a word of the batch's counts, zeroed with them).  A partial run (run_only) and a
        * hit-distance array without its second half never run solo. */
       PtSolo solo;
-      solo.flag = (run_only < 0 && s->solo_entries > 0 && !scene_lit(s) && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
+      solo.flag = (run_only < 0 && s->solo_entries > 0 && !sc.lit && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
       solo.max_entries = (uint32_t)std::max(0, s->solo_entries);
       solo.max_bounces = max_bounces;
       solo.cap_entries = (uint32_t)std::min<size_t>(w.cap_entries, 0xffffffffu);
-      launch_bounce(s, st, in, w.hits, out, w.contrib, n_upper, b, b == max_bounces - 1 ? 1 : 0, count, here, solo);
+      launch_bounce(s, st, in, w.hits, out, w.contrib, n_upper, b, last, count, here, solo);
       continue;
     }
     {
       LaunchTimer t(s, st, timed, PTX_KERNEL_TRACE);
-      launch_trace(s, st, in, w.hits, n_upper, count, w.counts + kWorkBase + (size_t)b * kWorkPerBounce, here);
+      /* (list-mode bounce 0, explicit samples, reads a queue like any bounce) */
+      launch_trace(s, st, in, w.hits, n_upper, count, w.counts + kWorkBase + (size_t)b * kWorkPerBounce, w.susp, here.on ? 0 : std::max(b, 1), here);
     }
     {
       LaunchTimer t(s, st, timed, PTX_KERNEL_SHADE);
       uint32_t* wk = w.counts + kWorkBase + (size_t)b * kWorkPerBounce;
-      launch_shade_pool(s, st, in, w.hits, out, w.contrib, n_upper, b, b == max_bounces - 1 ? 1 : 0, wk + 8, here);
+      launch_shade_pool(s, st, in, w.hits, out, w.contrib, n_upper, b, last, wk + 8, here);
     }
   }
 }
@@ -806,7 +823,7 @@ void fill_tree_stats(const ptx_scene* s, ptx_stats* st) {
   st->tree_leaves = s->tree_leaves;
   st->leaf_slots = s->dev.n_slots;
   st->build_ms = s->build_ms;
-  st->traversal_in_lds = (s->device >= 0 && scene_in_lds(s)) ? 1 : 0;
+  st->traversal_in_lds = (s->device >= 0 && s->sched.in_lds()) ? 1 : 0;
   st->bvh_built_on_gpu = s->built_on_gpu ? 1 : 0;
 }
 
@@ -903,7 +920,7 @@ int plan_batches(ptx_scene* s, const ptx_render_params* p, const PassRange& rang
   b.n_sets = (b.n_batches >= 2 && p->max_bounces > 0) ? 2 : 1;
   if (const char* e = getenv("PTX_STREAMS")) b.n_sets = std::max(1, std::min(kMaxSets, atoi(e)));
   b.n_sets = std::min(b.n_sets, b.n_batches);
-  s->sets_in_flight = b.n_sets;
+  reschedule(s, b.n_sets);
   return 0;
 }
 
@@ -1032,7 +1049,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   }
   struct GridDivGuard { /* every exit path, also the HIP_TRY ones, leaves later launches on this scene with whole grids */
     ptx_scene* s;
-    ~GridDivGuard() { s->grid_div = 1; s->sets_in_flight = 1; }
+    ~GridDivGuard() { s->grid_div = 1; reschedule(s, 1); }
   } grid_div_guard{s};
   BatchPlan b;
   int rc = plan_batches(s, p, range, &b);
@@ -1052,7 +1069,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   rc = fork_lanes(s, p, b, st, progress != nullptr, &l);
   if (rc) return rc;
   /* Grids cover the whole chip for every batch in flight; how many workgroups a CU takes of each kernel is decided per launch
-   * (share_cus: half a CU each on Simd_leaf LDS scenes). */
+   * (Schedule::share_cus: half a CU each on Simd_leaf LDS scenes). */
   s->grid_div = std::max(1, env_int("PTX_GRID_DIV", 1));
   std::vector<hipEvent_t> batch_done; /* progress: one event per batch, waited for in order after everything is queued */
   int batch = 0;
@@ -1447,8 +1464,13 @@ static int scene_upload(ptx_scene* s) {
   dv.top_nodes = h.top_nodes.empty() ? nullptr : s->top_nodes.p;
   dv.node_skip32_top = h.skip32_top.empty() ? nullptr : s->node_skip32_top.p;
   dv.n_top = (int32_t)(h.top_nodes.size() / 16);
+  /* lds_nodes64 is decided once, here, by the schedule of the image without them; the schedule the scene leaves with counts them in */
   dv.lds_nodes64 = 0;
-  if (scene_in_lds(s) && env_int("PTX_LDS_NODES64", 1)) dv.lds_nodes64 = pt_lds_keep_nodes64(lds_in(s, PT_LDS_K_TRACE, trace_block_lds(s) / 64), bounce_threads(s) / 64);
+  reschedule(s, s->sets_in_flight);
+  if (s->sched.in_lds() && env_int("PTX_LDS_NODES64", 1)) {
+    dv.lds_nodes64 = pt_lds_keep_nodes64(lds_in(s, PT_LDS_K_TRACE, s->sched.trace_threads / 64), s->sched.bounce_threads / 64);
+    reschedule(s, s->sets_in_flight);
+  }
   return 0;
 }
 
@@ -1606,6 +1628,7 @@ int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
     s->dev.lights = mode == PTX_LIGHTING_SAMPLED ? s->d_lights.p : nullptr;
     s->dev.n_lights = mode == PTX_LIGHTING_SAMPLED ? s->host->n_emissive_tris : 0;
     s->dev.light_area = mode == PTX_LIGHTING_SAMPLED ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
+    reschedule(s, s->sets_in_flight); /* (Schedule::lit, and what follows from it) */
   }
   for (ptx_scene* r : s->replicas) {
     const int rc = ptx_scene_set_lighting(r, mode);
@@ -2468,9 +2491,7 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
     g.first_pass = first; g.n_pass = n_pass;
     pl.n = (uint32_t)((unsigned long long)n_pass * padded);
     HIP_TRY(hipMemsetAsync(s->feat_work.p, 0, sizeof(uint32_t) * 8, st));
-    s->cur_bounce = 0;
-    s->cur_susp = s->feat_susp.p;
-    launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, pl);
+    launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, 0, pl);
     hipLaunchKernelGGL(k_features, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
     HIP_TRY(hipGetLastError());
   }
@@ -2686,7 +2707,7 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
   HIP_TRY(hipSetDevice(s->device));
   RenderBusy busy(s);
   Workspace w;
-  s->sets_in_flight = 1;
+  reschedule(s, 1);
   rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
   if (rc) return rc;
   LocalBuf<int32_t> dx, dy, dp;
@@ -2736,7 +2757,7 @@ int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(s->device));
   Workspace w;
-  s->sets_in_flight = 1;
+  reschedule(s, 1);
   int rc = ensure_workspace(s, (size_t)n, 1, &w, 0, true); /* this entry point hands the hit distances back: keep the records */
   if (rc) return rc;
   LocalBuf<double> d_o, d_d;
@@ -2750,8 +2771,7 @@ int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const
   PtQueue q0 = w.q[0];
   q0.count = w.counts;
   hipLaunchKernelGGL(k_load_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, d_o.p, d_d.p, q0);
-  s->cur_susp = w.susp;
-  launch_trace(s, nullptr, q0, w.hits, (size_t)n, true, w.counts + kWorkBase);
+  launch_trace(s, nullptr, q0, w.hits, (size_t)n, true, w.counts + kWorkBase, w.susp, kNoBounce);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   std::vector<int32_t> slot((size_t)n);
@@ -2817,7 +2837,7 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
   HIP_TRY(hipSetDevice(s->device));
   RenderBusy busy(s);
   Workspace w;
-  s->sets_in_flight = 1;
+  reschedule(s, 1);
   rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
   if (rc) return rc;
   LocalBuf<int32_t> dx, dy, dpp;
