@@ -196,6 +196,11 @@ typedef struct ptx_stats {
    * sizeof(ptx_stats) grows by 8 bytes (the word and its padding), and the library writes the whole struct: a caller must be
    * compiled against this header (the Python, OCaml and host callers of this repository are).  ptx_version() stays 6 */
   int32_t primary_lane_walks;
+  /* renders (1 per ptx_render-family call or slice, summed over the slices of a progressive render) whose non-counting k_bounce_carry launches held
+   * the per-octant LDS node image and walked it (PTX_LDS_OCT; Simd_leaf scenes whose launch buffer fits with it).  0 for counting
+   * renders: they keep the shared image.  APPENDED into the padding behind primary_lane_walks: no offset and not the size of the
+   * struct changes.  ptx_version() stays 6 */
+  int32_t lds_oct_launches;
 } ptx_stats;
 
 /* ---- progressive photon mapping (progressive-photon-map/src/progressive_photon_map.ml) ---- */

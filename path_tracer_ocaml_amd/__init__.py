@@ -162,7 +162,7 @@ def stats_dict(st):
         "traversal_in_lds": bool(st.traversal_in_lds), "bvh_built_on_gpu": bool(st.bvh_built_on_gpu),
         "filter_undecided": st.filter_undecided, "filter_fallback_steps": st.filter_fallback_steps,
         "peer_copies": st.peer_copies, "staged_copies": st.staged_copies, "solo_launches": st.solo_launches,
-        "carry_launches": st.carry_launches, "primary_lane_walks": st.primary_lane_walks,
+        "carry_launches": st.carry_launches, "primary_lane_walks": st.primary_lane_walks, "lds_oct_launches": st.lds_oct_launches,
     }
 
 

@@ -85,7 +85,7 @@ class Stats(C.Structure):
         ("filter_undecided", C.c_int64), ("filter_fallback_steps", C.c_int64),
         ("peer_copies", C.c_int32), ("staged_copies", C.c_int32),
         ("solo_launches", C.c_int32), ("carry_launches", C.c_int32),
-        ("primary_lane_walks", C.c_int32),
+        ("primary_lane_walks", C.c_int32), ("lds_oct_launches", C.c_int32),
     ]
 
 

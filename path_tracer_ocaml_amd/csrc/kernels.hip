@@ -393,6 +393,17 @@ struct PtThreadTag {};
  * instead of 6 MB of image + table).  A pre-order tree needs no lhs link (the lhs child of node k is k + 1), which is what
  * frees the word: inner nodes keep `rhs | axis << 30`, leaves pack `tag << 30 | real slots << 22 | first slot`. */
 struct PtThreadOctTag {};
+/* ... and the LDS walk on ITS per-octant image (PtSceneDev.lds_oct, PT_LOCT_* in pt_scene.h; non-counting k_bounce_carry launches of
+ * Simd_leaf scenes that fit with it, pt_lds_oct_layout): what the per-octant record did for the walk from HBM / L2, for the loop every
+ * segment of the headline goes through.  The shared LDS record serves all eight octants with per-lane offsets: four address adds, two
+ * 16-bit link reads, three 8-byte bound reads and the link pair per visit.  Here a visit is ONE address (record number << 5 beside the
+ * image's LDS address), two 16-byte reads, and a select that takes the hit or the miss half of word 6; "wants a node" is one unsigned
+ * comparison (link < PT_LOCT_LEAF_TAG).  A leaf's hit link is its own record under PT_LOCT_LEAF_TAG: the leaf phase reads the
+ * leaf table's word (first slot | real slots << 16) and goes on at the record's miss link -- two reads per leaf held, 2.3 leaves
+ * a ray against 21 visits.  Same bounds (rounded the same way), same magnitude word, same margin, same binary64 fallback: the
+ * undecided visit is performed in C++ (node_step) on binary64 node `record - octant * n_nodes`. */
+struct PtLdsOctTag {};
+typedef unsigned int pt_u4 __attribute__((ext_vector_type(4)));
 /* Round 5, second layout of the per-octant record: what the tagged links did for the LDS image, for the walk from
  * HBM / L2 -- where four fifths of the visits are answered by the L1 in ~120 clocks and the ~45 vector + ~40 scalar instructions
  * the old record cost per visit were as long a chain as the load.  An octant fixes the sign of every direction component, so
@@ -441,6 +452,7 @@ struct PtSceneView {
   const double* tri;
   const uint8_t* kind;
   const double* nodes64; /* LDS-resident scenes with PtSceneDev.lds_nodes64: six binary64 bounds per node in LDS, else null */
+  uint32_t oct_base, oct_leaf; /* PtLdsOctTag: the LDS addresses of the per-octant image's records and of its leaf table */
   const uint8_t* cat; /* the slots' shading categories: the LDS copy on LDS-resident scenes (k_bounce files a finished ray by it right
                          after the walk: from global memory that one byte was a ~1 us round trip in every chunk's chain) */
   /* scenes walked from HBM / L2: the first n_floor_lds floor triangles (ganesha's Floor, tested before the tree for EVERY ray,
@@ -467,6 +479,8 @@ __device__ __forceinline__ void pt_stack_push(PtThreadTag*, int, uint32_t) {}
 __device__ __forceinline__ uint32_t pt_stack_pop(const PtThreadTag*, int) { return 0u; }
 __device__ __forceinline__ void pt_stack_push(PtThreadOctTag*, int, uint32_t) {}
 __device__ __forceinline__ uint32_t pt_stack_pop(const PtThreadOctTag*, int) { return 0u; }
+__device__ __forceinline__ void pt_stack_push(PtLdsOctTag*, int, uint32_t) {}
+__device__ __forceinline__ uint32_t pt_stack_pop(const PtLdsOctTag*, int) { return 0u; }
 #define PT_STACK_PUSH(stk, sp, val) pt_stack_push((stk), (sp), (uint32_t)(val))
 #define PT_STACK_POP(stk, sp) pt_stack_pop((stk), (sp))
 
@@ -535,23 +549,25 @@ struct PtTraverser {
   int sp;
   /* TAGGED (the LDS image, layout 3): `node` carries the walk's control state in its two low bits (PT_SWZ_TAG_*), `walking` and
    * `leaf_n` are not used between the leaf phases; `lkx` = word 6 of the node visited last (a leaf's first slot | real count << 16) */
-  static constexpr bool TAGGED = SWZ;
+  static constexpr bool LOCT = SWZ && std::is_same<StackT, PtLdsOctTag>::value; /* the per-octant LDS image: `node` is a PT_LOCT_* link */
+  static constexpr bool TAGGED = SWZ && !LOCT;
   static constexpr bool OTAG = OCT; /* the per-octant record: tagged, pre-offset links */
-  static constexpr bool TAGS = TAGGED || OTAG;
+  static constexpr bool TAGS = TAGGED || OTAG || LOCT;
   uint32_t node;
   mutable uint32_t lkx;
   uint32_t lkx_diag = 0u, sdiag = 0u; /* (PT_DIAG_VISIT_*) */
   uint32_t walking; /* 0 / 1: an integer, so that "wants a node step" is ONE unsigned comparison (walking > leaf_n) */
   int leaf_first, leaf_n;
-  __device__ __forceinline__ bool wants_node() const { return OTAG ? node < PT_OCT_LEAF_TAG : (TAGGED ? (node & 3u) == 0u : walking > (uint32_t)leaf_n); }
+  __device__ __forceinline__ bool wants_node() const { return LOCT ? node < PT_LOCT_LEAF_TAG : OTAG ? node < PT_OCT_LEAF_TAG : (TAGGED ? (node & 3u) == 0u : walking > (uint32_t)leaf_n); }
   /* the same as a wave mask, straight from the comparison: the ballot builtin of the very expression the branch tests lets the
    * compiler use ONE v_cmp for both (HIP's __ballot of a boolean that is also branched on costs two more vector instructions
    * per turn; __builtin_amdgcn_uicmp a second compare); 38 = signed greater than, 33 = not equal */
   __device__ __forceinline__ unsigned long long wants_node_mask() const { return __builtin_amdgcn_ballot_w64(wants_node()); }
-  __device__ __forceinline__ bool holds_leaf() const { return OTAG ? (node >> 30) == 1u : (TAGGED ? (node & PT_SWZ_TAG_LEAF) != 0u : leaf_n > 0); }
+  __device__ __forceinline__ bool holds_leaf() const { return LOCT ? (node & PT_LOCT_LEAF_TAG) != 0u : OTAG ? (node >> 30) == 1u : (TAGGED ? (node & PT_SWZ_TAG_LEAF) != 0u : leaf_n > 0); }
   __device__ __forceinline__ unsigned long long holds_leaf_mask() const { return TAGS ? __builtin_amdgcn_ballot_w64(holds_leaf()) : __builtin_amdgcn_sicmp(leaf_n, 0, 38); }
   /* the ray's walk is not over (it wants a node step or holds a leaf) */
   __device__ __forceinline__ bool alive() const {
+    if (LOCT) return node != PT_LOCT_END;
     return OTAG ? (PT_OCT_BATCH_FALLBACK ? (node & PT_OCT_PENDING) != PT_OCT_END : node < PT_OCT_END) : (TAGGED ? node != PT_SWZ_END : (walking != 0u || leaf_n > 0));
   }
   __device__ __forceinline__ bool pending() const { return OTAG && PT_OCT_BATCH_FALLBACK && node >= PT_OCT_PENDING; }
@@ -652,6 +668,10 @@ struct PtTraverser {
     if (TAGGED && sc.n_nodes <= 0) node = PT_SWZ_END;
     if (OTAG) node = skip_off; /* the root's record of this ray's octant */
     if (OTAG && sc.n_nodes <= 0) node = PT_OCT_END;
+    if (LOCT) { /* the root's record of this ray's octant; skip_off = the octant's first record */
+      skip_off = dirs * sv.n_nodes;
+      node = sc.n_nodes > 0 ? skip_off : PT_LOCT_END;
+    }
     lkx = 0u;
     leaf_first = 0;
     leaf_n = 0;
@@ -744,6 +764,67 @@ struct PtTraverser {
           [fny] "v"(fny), [fnz] "v"(fnz), [t32] "v"(t32), [k2] "v"(k2), [c2] "v"(c2), [wmin] "s"(wmin)
         : "vcc", "scc");
     lkx = lk0;
+    return und;
+  }
+  /* The same loop on the per-octant LDS image (LOCT): 17 vector + 2 LDS + 2 waits + 4 scalar instructions per visit, 25 issued
+   * against 37..40 (profiles/pr_lds_oct_isa.txt).  `node` is a record number; the record's address is one shift-add beside the
+   * image's LDS address (a scalar).  The undecided test comes first and leaves through vcc as above; the hit test then sets vcc for
+   * the select, which takes word 6's low half (the hit link) or its high half (the miss link) in one instruction; the tag test
+   * writes exec itself (v_cmpx: the lanes that still want a node).  The exits are one comparison: thr = min(lanes entered, wmin),
+   * go on while the lanes left are >= thr -- while nobody has left that holds, once somebody has it is "fewer than wmin", and an
+   * empty exec is below any thr >= 1: walk_asm's rule, three scalar instructions whether or not a lane has left.
+   * Same arithmetic as node_step's LOCT branch.  (Measured and not kept, DESIGN.md Appendix A: the records as two arrays of
+   * 16-byte words against bank conflicts, one s_waitcnt instead of two.) */
+  __device__ __forceinline__ unsigned long long walk_asm_oct(uint32_t base, int wmin) {
+    register uint32_t nx asm("v120"), ny asm("v121"), nz asm("v122"), fx asm("v123"), fy asm("v124"), fz asm("v125"), lk asm("v126"), mg asm("v127");
+    unsigned long long und, sv_;
+    uint32_t a_, n_, thr_;
+    float tn_, tf_, p_, q_, r_, s_, m2_;
+    asm volatile(
+        "s_mov_b64 %[sv], exec\n"
+        "s_mov_b64 %[und], 0\n"
+        "v_cmpx_gt_u32 vcc, %[lt], %[node]\n"
+        "s_cbranch_execz .Ldone%=\n"
+        "s_bcnt1_i32_b64 %[thr], exec\n"
+        "s_min_u32 %[thr], %[thr], %[wmin]\n"
+        "s_waitcnt lgkmcnt(0)\n" /* (scalar loads return out of order: nothing of the compiler's may be outstanding) */
+        ".Lloop%=:\n"
+        "v_lshl_add_u32 %[a], %[node], 5, %[base]\n"
+        "ds_read_b128 v[120:123], %[a]\n"
+        "ds_read_b128 v[124:127], %[a] offset:16\n"
+        "s_waitcnt lgkmcnt(1)\n"
+        "v_fma_f32 %[tn], %[nx], %[fix], %[fnx]\n"
+        "v_fma_f32 %[p], %[ny], %[fiy], %[fny]\n"
+        "v_fma_f32 %[r], %[nz], %[fiz], %[fnz]\n"
+        "v_fma_f32 %[tf], %[fx], %[fix], %[fnx]\n"
+        "v_max_f32 %[tn], %[tn], %[p]\n"
+        "v_max3_f32 %[tn], %[tn], %[r], 0\n"
+        "s_waitcnt lgkmcnt(0)\n"
+        "v_fma_f32 %[q], %[fy], %[fiy], %[fny]\n"
+        "v_fma_f32 %[s], %[fz], %[fiz], %[fnz]\n"
+        "v_fma_f32 %[m2], %[mg], %[k2], %[c2]\n"
+        "v_min_f32 %[tf], %[tf], %[q]\n"
+        "v_min3_f32 %[tf], %[tf], %[s], %[t32]\n"
+        "v_sub_f32 %[tf], %[tf], %[tn]\n"
+        "v_cmp_nge_f32_e64 vcc, |%[tf]|, %[m2]\n"
+        "s_cbranch_vccnz .Lund%=\n"
+        "v_cmp_ge_f32 vcc, %[tf], %[m2]\n"
+        "v_cndmask_b32_sdwa %[node], %[lk], %[lk], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n"
+        "v_cmpx_gt_u32 vcc, %[lt], %[node]\n"
+        "s_bcnt1_i32_b64 %[n], exec\n"
+        "s_cmp_ge_u32 %[n], %[thr]\n"
+        "s_cbranch_scc1 .Lloop%=\n"
+        "s_branch .Ldone%=\n"
+        ".Lund%=:\n"
+        "s_mov_b64 %[und], vcc\n"
+        ".Ldone%=:\n"
+        "s_mov_b64 exec, %[sv]\n"
+        : [node] "+v"(node), [nx] "=&v"(nx), [ny] "=&v"(ny), [nz] "=&v"(nz), [fx] "=&v"(fx), [fy] "=&v"(fy), [fz] "=&v"(fz), [lk] "=&v"(lk),
+          [mg] "=&v"(mg), [und] "=&s"(und), [sv] "=&s"(sv_), [thr] "=&s"(thr_), [n] "=&s"(n_), [a] "=&v"(a_), [tn] "=&v"(tn_),
+          [tf] "=&v"(tf_), [p] "=&v"(p_), [q] "=&v"(q_), [r] "=&v"(r_), [s] "=&v"(s_), [m2] "=&v"(m2_)
+        : [base] "s"(base), [lt] "s"((uint32_t)PT_LOCT_LEAF_TAG), [fix] "v"(fix), [fiy] "v"(fiy), [fiz] "v"(fiz), [fnx] "v"(fnx), [fny] "v"(fny),
+          [fnz] "v"(fnz), [t32] "v"(t32), [k2] "v"(k2), [c2] "v"(c2), [wmin] "s"(wmin)
+        : "vcc", "scc");
     return und;
   }
 #endif
@@ -930,6 +1011,30 @@ struct PtTraverser {
       node = hit ? oct_link : oct_skip;
       return;
     }
+    if (LOCT) { /* the per-octant LDS record: near xyz, far xyz, hit | miss << 16, magnitude (walk_asm_oct: the same visit) */
+      const uint32_t ad = sv.oct_base + (node << 5), ad1 = ad + 16u;
+      const pt_u4 r0 = *(const __attribute__((address_space(3))) pt_u4*)PT_LDS_AT(ad);
+      const pt_u4 r1 = *(const __attribute__((address_space(3))) pt_u4*)PT_LDS_AT(ad1);
+      const float tnx = __builtin_fmaf(__uint_as_float(r0.x), fix, fnx), tny = __builtin_fmaf(__uint_as_float(r0.y), fiy, fny),
+                  tnz = __builtin_fmaf(__uint_as_float(r0.z), fiz, fnz);
+      const float tfx = __builtin_fmaf(__uint_as_float(r0.w), fix, fnx), tfy = __builtin_fmaf(__uint_as_float(r1.x), fiy, fny),
+                  tfz = __builtin_fmaf(__uint_as_float(r1.y), fiz, fnz);
+      const float a = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), tnz);
+      const float b = __builtin_fminf(__builtin_fminf(tfx, tfy), tfz);
+      const float u = __builtin_fminf(b, t32) - __builtin_fmaxf(a, 0.0f);
+      const float m2 = __builtin_fmaf(__uint_as_float(r1.w), k2, c2);
+      bool hit = u >= m2;
+      if (!(__builtin_fabsf(u) >= m2)) { /* (as on the shared image: the nested-interval rule, then binary64) */
+        if (nested_hit(tnx, tfx, tny, tfy, tnz, tfz, m2)) hit = true;
+        else {
+          const uint32_t k64 = node - skip_off; /* the canonical node: the octant's base off again */
+          hit = sv.nodes64 ? slab64(sv.nodes64 + (size_t)k64 * 6u) : slab64(sv.nodes + k64); /* (wave-uniform choice) */
+        }
+      }
+      static_assert(!(LOCT && COUNT), "the per-octant LDS image has no counting walk: counting launches keep the shared image");
+      node = hit ? (r1.z & 0xffffu) : (r1.z >> 16);
+      return;
+    }
     /* threaded image: where to go once this subtree is done (issued beside the node's own reads) */
     constexpr bool THREAD32 = G32;
     uint32_t skip;
@@ -1012,6 +1117,13 @@ struct PtTraverser {
       leaf_first = (int)(lkx & 0xffffu);
       leaf_n = (int)(lkx >> 16);
       node &= ~PT_SWZ_TAG_LEAF; /* -> the node that follows the leaf, or PT_SWZ_END */
+    }
+    if (LOCT) { /* `node` names the leaf's own record: its packet from the leaf table, then on at the record's miss link */
+      const uint32_t rec = node & (PT_LOCT_LEAF_TAG - 1u);
+      const uint32_t lw = *(const __attribute__((address_space(3))) uint32_t*)PT_LDS_AT(sv.oct_leaf + ((rec - skip_off) << 2));
+      leaf_first = (int)(lw & 0xffffu);
+      leaf_n = (int)(lw >> 16);
+      node = (uint32_t)*(const __attribute__((address_space(3))) uint16_t*)PT_LDS_AT(sv.oct_base + (rec << 5) + 26u);
     }
     if (OTAG) { /* `node` IS the leaf's word; the walk goes on where the leaf's miss link points */
       leaf_first = (int)(node & ((1u << PT_OCT_LEAF_FIRST_BITS) - 1u));
@@ -1180,7 +1292,12 @@ __device__ __forceinline__ PtTraceResult pt_trace_ray(const PtSceneDev& sc, cons
      * PT_WALK_MIN lanes are walking and some lane holds a leaf, the pending packets are intersected first.  Half the SCALAR
      * instructions per turn: +3 % time in k_trace at 8 waves per SIMD (scalar issue is not what binds there), -1 % in k_bounce
      * at 4 (with half the waves, a wave busy with scalar bookkeeping is more often the one the vector pipe is waiting for). */
-    if constexpr (ASM_WALK && (PT_WALK_ASM != 0) && (PT_DIAG == 0) && !COUNT && PtTraverser<MODE, COUNT, ORIGIN_ZERO, StackT, SWZ>::TAGGED) {
+    if constexpr (ASM_WALK && (PT_WALK_ASM != 0) && (PT_DIAG == 0) && !COUNT && PtTraverser<MODE, COUNT, ORIGIN_ZERO, StackT, SWZ>::LOCT) {
+#if PT_WALK_ASM
+      while (tr.walk_asm_oct(sv.oct_base, WALK_MIN) != 0ull)
+        if (tr.wants_node()) tr.node_step(sv, stack, c_nodes, c_prims);
+#endif
+    } else if constexpr (ASM_WALK && (PT_WALK_ASM != 0) && (PT_DIAG == 0) && !COUNT && PtTraverser<MODE, COUNT, ORIGIN_ZERO, StackT, SWZ>::TAGGED) {
 #if PT_WALK_ASM
       /* the node loop in assembly; a visit the binary32 filter cannot decide for some lane is performed here, in binary64 */
       while (tr.walk_asm(WALK_MIN) != 0ull)
@@ -1371,7 +1488,7 @@ __device__ __forceinline__ PtTraceResult pt_trace_packet(const PtSceneDev& sc, c
 
 /* Where this workgroup traverses from.  LDS_SCENE: the whole tree and every leaf packet are first copied into LDS
  * behind the traversal stacks (nodes expanded to the swizzled image on the way); ends with a __syncthreads(). */
-template <int MODE, bool LDS_SCENE>
+template <int MODE, bool LDS_SCENE, bool LOCT = false /* LDS_SCENE with the per-octant image in place of stacks + shared node image (PtLdsOctTag) */>
 __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsigned char* lds_raw, int stack_depth, bool want_top = false) {
   const uint32_t waves_per_block = blockDim.x >> 6;
   PtSceneView sv;
@@ -1398,7 +1515,37 @@ __device__ __forceinline__ PtSceneView pt_scene_view(const PtSceneDev& sc, unsig
   sv.kind = sc.slot_kind;
   sv.cat = sc.slot_cat;
   sv.nodes64 = nullptr;
+  sv.oct_base = sv.oct_leaf = 0u;
   if (!LDS_SCENE && sc.all_triangles) sv.kind = nullptr; /* PtTraverser::packet: the pipelined triangle loop */
+  if constexpr (LDS_SCENE && LOCT) {
+    unsigned char *l_oct, *l_leaf, *l_sph, *l_cat, *l_nodes64, *l_end; /* pt_lds_layout.h, PT_LDS_OCT_REGIONS */
+    const int total_slots = sc.n_slots + sc.n_floor;
+#define PT_VIEW_AT(region, off_) l_##region = lds_raw + (off_)
+    PT_LDS_OCT_REGIONS(PT_VIEW_AT, sc.n_nodes, total_slots, sc.lds_nodes64);
+#undef PT_VIEW_AT
+    (void)l_end;
+    { /* records and leaf table as the host built them: one run of 16-byte words */
+      const uint4* src = (const uint4*)sc.lds_oct;
+      uint4* dst = (uint4*)l_oct;
+      const int n16 = sc.n_nodes * 16 + (int)(PT_LOCT_LEAF_WORDS(sc.n_nodes) / 4u);
+      for (int k = threadIdx.x; k < n16; k += blockDim.x) dst[k] = src[k];
+    }
+    {
+      const uint4* src = (const uint4*)sc.sph;
+      uint4* dst = (uint4*)l_sph;
+      for (int k = threadIdx.x; k < total_slots * 2; k += blockDim.x) dst[k] = src[k];
+    }
+    for (int k = threadIdx.x; k < total_slots; k += blockDim.x) l_cat[k] = sc.slot_cat[k];
+    if (sc.lds_nodes64)
+      for (int k = threadIdx.x; k < sc.n_nodes * 3; k += blockDim.x)
+        ((double2*)l_nodes64)[k] = ((const double2*)(sc.nodes + k / 3))[k % 3];
+    __syncthreads();
+    sv.oct_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)l_oct;
+    sv.oct_leaf = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)l_leaf;
+    sv.sph = (const double*)l_sph;
+    sv.cat = l_cat;
+    if (sc.lds_nodes64) sv.nodes64 = (const double*)l_nodes64;
+  } else
   if (LDS_SCENE) {
     unsigned char *l_nodes, *l_sph, *l_tri, *l_kind, *l_cat, *l_nodes64, *l_end; /* the regions of the image: pt_lds_layout.h */
 #define PT_VIEW_AT(region, off_) l_##region = lds_raw + (off_)
@@ -2864,7 +3011,9 @@ static_assert(PT_POOL_BINS >= PT_N_SHADE_CAT, "k_bounce_carry: one output bin pe
 
 /* LANE_WALK (PRIMARY launches, PTX_PRIMARY_WALK): the camera rays walk one per lane through pt_trace_ray -- on Simd_leaf scenes the
  * assembly node loop the queued rays use -- instead of as a wave packet.  A ray's tests and their order are the same in both. */
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false>
+/* LOCT (Schedule::lds_oct; Simd_leaf, not counting, camera rays one per lane): the workgroup holds the per-octant LDS image (PtLdsOctTag)
+ * in place of the stacks and the shared node image; pool_off is then pt_lds_oct_layout's. */
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false, bool LOCT = false>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_carry(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtHits hout, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
@@ -2874,8 +3023,9 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   __shared__ uint32_t lds_chunk_ctr, lds_done;
   __shared__ uint32_t lds_park_n, lds_park_lock;
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
-  typedef uint16_t StackT;
-  StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
+  static_assert(!LOCT || (MODE == PT_MODE_SIMD && !COUNT && (!PRIMARY || LANE_WALK)), "the per-octant LDS image: Simd_leaf, not counting, no packet walk");
+  typedef typename std::conditional<LOCT, PtLdsOctTag, uint16_t>::type StackT;
+  StackT* stack = LOCT ? nullptr : (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
   uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
@@ -2885,7 +3035,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
   if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; lds_park_n = 0u; lds_park_lock = 0u; }
   if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
-  PtSceneView sv = pt_scene_view<MODE, true>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
+  PtSceneView sv = pt_scene_view<MODE, true, LOCT>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
   PtSceneDev scl = sc; /* the shade steps read the slots' kinds and geometry where the walk reads them (k_bounce) */
   scl.slot_kind = sv.kind;
   scl.sph = sv.sph;

@@ -13,7 +13,9 @@
  *                       (Array_leaf) | {node, slot} (walks from HBM / L2)
  *   [k_bounce_carry, at pool_off]   parked entries, one array of park_cap 16-byte words per field: 6 (PT_CARRY_PARK_WORDS) |
  *                       2 x emission (scenes with emitters) | {u, v} (Array_leaf)
- * A walk from HBM / L2 has no stacks and no image: k_bounce's pools start at 0, k_trace holds the tree's top (n_top x 64 bytes). */
+ * A walk from HBM / L2 has no stacks and no image: k_bounce's pools start at 0, k_trace holds the tree's top (n_top x 64 bytes).
+ * k_bounce_carry's non-counting launches on a Simd_leaf scene that fits with it hold the per-octant node image instead of stacks and
+ * shared image: a region list and an admit decision of their own, PT_LDS_OCT_REGIONS / pt_lds_oct_layout below. */
 #ifndef PT_LDS_LAYOUT_H
 #define PT_LDS_LAYOUT_H
 
@@ -200,6 +202,46 @@ PT_LDS_HD PtLdsLayout pt_lds_layout(const PtLdsIn& in) {
   }
   l.total = l.work.park_end;
   l.fits = in.kernel == PT_LDS_K_TRACE || l.total <= PT_LDS_BOUNCE_LIMIT;
+  return l;
+}
+
+/* ---- the per-octant LDS image (PtSceneDev.lds_oct, PT_LOCT_* in pt_scene.h): k_bounce_carry's non-counting launches on Simd_leaf scenes ----
+ * The buffer of such a launch: NO per-wave stacks (its walks are threaded and its camera rays walk one per lane: nothing reads a
+ * stack), then
+ *   records (8 x n_nodes x 32 B, a multiple of 64) | leaf table (one word per node, to 16) | sphere slots (32 B) | shading categories
+ *   (to 16) | binary64 bounds (48 B per node, in.lds_nodes64)
+ * and, at pool_off = the above to 64, k_bounce_carry's parked entries as in every launch of that kernel. */
+#define PT_LDS_OCT_REGIONS(AT, n_nodes_, total_slots_, lds_nodes64_)                                                     \
+  size_t off = 0;                                                                                                        \
+  AT(oct, off);                                                                                                          \
+  off += (size_t)(n_nodes_) * 8 * PT_LOCT_RECORD_BYTES;                                                                  \
+  AT(leaf, off);                                                                                                         \
+  off += (size_t)PT_LOCT_LEAF_WORDS(n_nodes_) * 4;                                                                       \
+  AT(sph, off);                                                                                                          \
+  off += (size_t)(total_slots_) * 4 * sizeof(double);                                                                    \
+  AT(cat, off);                                                                                                          \
+  off += ((size_t)(total_slots_) + 15) & ~(size_t)15;                                                                    \
+  AT(nodes64, off);                                                                                                      \
+  if (lds_nodes64_) off += (size_t)(n_nodes_) * 48;                                                                      \
+  AT(end, off)
+struct PtLdsOctLayout {
+  size_t oct, leaf, sph, cat, nodes64, end;
+  size_t pool_off;
+  PtLdsWork work;
+  size_t total;
+  int fits; /* the scene is admitted: a Simd_leaf tree of 1 .. PT_LOCT_MAX_NODES nodes whose whole buffer is within PT_LDS_BOUNCE_LIMIT */
+};
+/* in.kernel is taken as PT_LDS_K_BOUNCE_CARRY, in.waves as that launch's; in.stack_depth, in.from_hbm and in.n_top play no part */
+PT_LDS_HD PtLdsOctLayout pt_lds_oct_layout(const PtLdsIn& in) {
+  PtLdsOctLayout l;
+#define PT_LDS_AT_OFFSET(region, off_) l.region = (off_)
+  PT_LDS_OCT_REGIONS(PT_LDS_AT_OFFSET, in.n_nodes, in.total_slots, in.lds_nodes64 != 0);
+#undef PT_LDS_AT_OFFSET
+  l.pool_off = (l.end + 63) & ~(size_t)63;
+  l.work = pt_lds_carry_work(l.pool_off, in.waves, in.has_emit != 0, false);
+  l.total = l.work.park_end;
+  l.fits = in.mode == PT_MODE_SIMD && in.n_nodes >= 1 && in.n_nodes <= PT_LOCT_MAX_NODES && (size_t)in.total_slots < 65536 &&
+           l.total <= PT_LDS_BOUNCE_LIMIT;
   return l;
 }
 

@@ -32,6 +32,16 @@
 #define PT_OCT_LEAF_REAL_MAX 255u
 #define PT_OCT_END 0x80000000u
 #define PT_OCT_LEAF_TAG 0x40000000u
+/* the per-octant LDS image (PtSceneDev.lds_oct; the walk: kernels.hip, PtLdsOctTag): 8 x n_nodes records of 32 bytes -- near xyz,
+ * far xyz for the octant's direction signs, word 6 = hit link | miss link << 16, word 7 = the node's magnitude as the shared LDS image
+ * stores it -- then the leaf table, one word per node (a leaf: first slot | real slots << 16), padded to 16 bytes.  A link is a record
+ * number in the whole image (14 bits: the octant's base added) under two control bits: 00 a node to visit, 01 (a leaf's hit link:
+ * its own record) "this lane holds a leaf", 10 the walk is over.  After its leaf phase a lane goes on at the leaf record's miss link. */
+#define PT_LOCT_RECORD_BYTES 32
+#define PT_LOCT_LEAF_TAG 0x4000u
+#define PT_LOCT_END 0x8000u
+#define PT_LOCT_MAX_NODES 2047 /* 8 x n_nodes record numbers below 2^14 */
+#define PT_LOCT_LEAF_WORDS(n_nodes) (((uint32_t)(n_nodes) + 3u) & ~3u)
 #define PT_TRI_FRAME_DOUBLES 12 /* PtSceneDev.tri_frame: doubles per slot */
 constexpr int kTriFrameMaxSlots = 1024; /* PtSceneDev.tri_frame: <= 96 KB, resident in L1 / L2 */
 
@@ -173,6 +183,10 @@ struct PtSceneDev {
   int32_t n_lights;
   int32_t lighting;
   double light_area; /* the sum of the areas = the last record's running sum */
+  /* Simd_leaf trees of at most PT_LOCT_MAX_NODES nodes: the per-octant LDS image (PT_LOCT_* above), 8 x n_nodes x 8 words of records
+   * and PT_LOCT_LEAF_WORDS(n_nodes) words of leaf table, or NULL.  The non-counting k_bounce_carry launches of a scene whose buffer
+   * fits with it (pt_lds_layout.h, pt_lds_oct_layout; Schedule::lds_oct) copy it into LDS in place of the shared node image. */
+  const uint32_t* lds_oct;
 };
 
 #define PT_LIGHTING_SAMPLED 2 /* = PTX_LIGHTING_SAMPLED */

@@ -198,10 +198,12 @@ struct Schedule {
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
+  bool lds_oct = false;        /* non-counting k_bounce_carry launches hold the per-octant LDS image (PtSceneDev.lds_oct) and walk it */
   int top_in_lds = 0;          /* k_trace from HBM / L2 keeps the tree's top in LDS */
   int trace_threads = 0, bounce_threads = 0; /* workgroups of k_trace; of k_bounce and k_bounce_carry */
   size_t trace_lds = 0;        /* dynamic LDS of a k_trace launch */
   PtLdsLayout bounce{}, carry{}; /* dynamic LDS of a k_bounce, of a k_bounce_carry launch */
+  PtLdsOctLayout carry_oct{};  /* ... of a k_bounce_carry launch on the per-octant LDS image */
   bool in_lds() const { return placement == PT_PLACE_LDS; }
   bool fused_ok(size_t cap_entries) const { return fused_possible && cap_entries < kPoolMaxEntries; } /* ... with queues of this capacity */
 };
@@ -237,7 +239,8 @@ struct ptx_scene {
   DevBuf<PtTexture> textures;
   DevBuf<PtShadeRec> slot_shade;
   DevBuf<uint16_t> node_skip;
-  DevBuf<uint32_t> node_skip32, nodes32, nodes32o, top_nodes, node_skip32_top;
+  DevBuf<uint32_t> node_skip32, nodes32, nodes32o, lds_oct, top_nodes, node_skip32_top;
+  bool lds_oct_launched = false; /* the render in progress has launched a kernel on the per-octant LDS image (ptx_stats.lds_oct_launches) */
   int n_prims = 0;
   int tree_depth = 0, tree_leaves = 0;
   double build_ms = 0.0;
@@ -476,6 +479,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
    * scenes, which have no such loop, keep the wave packet (DESIGN.md Appendix A).  1 = per lane everywhere, 0 = the packet everywhere */
   c.lane_walk = s->primary_walk == 1 || (s->primary_walk >= 2 && simd);
+  /* the per-octant LDS image (PTX_LDS_OCT, read at scene creation: scene_host.cpp builds it or not): wherever the shade-first order
+   * runs with the camera rays one per lane and the whole buffer of such a launch fits with it.  Counting launches keep the shared image */
+  c.carry_oct = pt_lds_oct_layout(lds_in(s, PT_LDS_K_BOUNCE_CARRY, c.bounce_threads / 64));
+  c.lds_oct = s->dev.lds_oct != nullptr && simd && c.carry_ok && c.lane_walk && c.carry_oct.fits;
   return c;
 }
 void reschedule(ptx_scene* s, int sets) {
@@ -522,7 +529,12 @@ ShadePoolKernel shade_pool_kernel(Shading shading, bool primary) {
 }
 
 /* k_bounce_carry: 24 = MODE 2 x COUNT 2 x EMIT 2 x (PRIMARY, LANE_WALK) in {00, 10, 11}: only camera rays walk one per lane (a
- * lane walk asked of a queued launch is the plain kernel), and a lit scene never takes this kernel (Schedule::carry_ok) */
+ * lane walk asked of a queued launch is the plain kernel), and a lit scene never takes this kernel (Schedule::carry_ok);
+ * + 4 on the per-octant LDS image (LOCT; Simd_leaf, not counting): EMIT 2 x {queued, camera with lane walk} */
+CarryKernel carry_kernel_oct(bool emit, bool primary) {
+  if (emit) return primary ? k_bounce_carry<PT_MODE_SIMD, false, true, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, true, false, false, true>;
+  return primary ? k_bounce_carry<PT_MODE_SIMD, false, false, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, false, false, false, true>;
+}
 template <int MODE, bool COUNT>
 CarryKernel carry_kernel_of(bool emit, bool primary, bool lane_walk) {
   if (emit) {
@@ -621,13 +633,15 @@ void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
                          const PtContrib& c, size_t n_upper, int bounce, int last, bool count, const PrimaryLaunch& pl) {
   const Schedule& sc = s->sched;
   const int stack_depth = std::max(1, s->tree_depth + 1);
-  const CarryKernel kern = carry_kernel(s->dev.mode, count, s->dev.has_emit != 0, pl.on, sc.lane_walk);
-  prepare_kernel(s, (const void*)kern, "k_bounce_carry", true, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
+  const bool oct = sc.lds_oct && !count;
+  const CarryKernel kern = oct ? carry_kernel_oct(s->dev.has_emit != 0, pl.on) : carry_kernel(s->dev.mode, count, s->dev.has_emit != 0, pl.on, sc.lane_walk);
+  prepare_kernel(s, (const void*)kern, "k_bounce_carry", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
   const int threads = sc.bounce_threads;
   int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), sc.carry.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
-                     (uint32_t)sc.carry.pool_off, s->counters.p, s->bounce_fence_wg);
+  if (oct) s->lds_oct_launched = true;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n,
+                     stack_depth, (uint32_t)(oct ? sc.carry_oct.pool_off : sc.carry.pool_off), s->counters.p, s->bounce_fence_wg);
 }
 
 void launch_bounce(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtContrib& c,
@@ -1043,6 +1057,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
   RenderBusy busy(s);
   s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
   s->timed.clear();
+  s->lds_oct_launched = false;
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
     fill_tree_stats(s, stats);
@@ -1116,6 +1131,7 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
 #endif
   if (stats) {
     stats->samples = (int64_t)b.per_pass * b.pass_count;
+    stats->lds_oct_launches = s->lds_oct_launched ? 1 : 0;
     if (count) {
       rc = collect_counters(s, stats);
       if (rc) return rc;
@@ -1448,6 +1464,7 @@ static int scene_upload(ptx_scene* s) {
   HIP_TRY(up(s->node_skip32, h.skip32));
   HIP_TRY(up(s->nodes32, h.nodes32));
   HIP_TRY(up(s->nodes32o, h.nodes32o));
+  HIP_TRY(up(s->lds_oct, h.lds_oct));
   HIP_TRY(up(s->top_nodes, h.top_nodes));
   HIP_TRY(up(s->node_skip32_top, h.skip32_top));
   PtSceneDev& dv = s->dev;
@@ -1461,6 +1478,7 @@ static int scene_upload(ptx_scene* s) {
   dv.node_skip32 = s->node_skip32.p;
   dv.nodes32 = s->nodes32.p;
   dv.nodes32o = h.nodes32o.empty() ? nullptr : s->nodes32o.p;
+  dv.lds_oct = h.lds_oct.empty() ? nullptr : s->lds_oct.p;
   dv.top_nodes = h.top_nodes.empty() ? nullptr : s->top_nodes.p;
   dv.node_skip32_top = h.skip32_top.empty() ? nullptr : s->node_skip32_top.p;
   dv.n_top = (int32_t)(h.top_nodes.size() / 16);
@@ -2087,6 +2105,7 @@ void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
   acc->segments += o.segments; acc->nodes_tested += o.nodes_tested; acc->prims_tested += o.prims_tested;
   acc->floor_tested += o.floor_tested; acc->filter_undecided += o.filter_undecided;
   acc->filter_fallback_steps += o.filter_fallback_steps; acc->solo_launches += o.solo_launches; acc->carry_launches += o.carry_launches;
+  acc->lds_oct_launches += o.lds_oct_launches;
   acc->primary_lane_walks += o.primary_lane_walks;
   for (int i = 0; i < PTX_N_KERNELS; ++i) {
     acc->kernel_ms[i] += o.kernel_ms[i];

@@ -249,6 +249,52 @@ void octant_image(const SceneOptions& opt, PtHostArrays* h) {
     }
 }
 
+/* lds_oct: the per-octant LDS image of a small Simd_leaf tree (pt_scene.h, PT_LOCT_*), from nodes32 and skip32 like nodes32o: per
+ * (octant, node) near xyz, far xyz, hit link | miss link << 16, the magnitude word of the shared LDS image; then the leaf table */
+void lds_octant_image(const SceneOptions& opt, PtHostArrays* h) {
+  const std::vector<PtNode>& nd = h->nodes;
+  if (!opt.lds_oct || h->dev.mode != PT_MODE_SIMD || nd.empty() || nd.size() > (size_t)PT_LOCT_MAX_NODES) return;
+  for (const PtNode& k : nd)
+    if (is_leaf(k) && (k.a > 0xffffu || k.pad[0] > 0xffffu)) return;
+  { /* a tree whose image alone, before any parked entry, is beyond what a launch may ask for can never be admitted (pt_lds_oct_layout) */
+    PtLdsIn in{};
+    in.mode = PT_MODE_SIMD;
+    in.n_nodes = (int)nd.size();
+    in.total_slots = h->dev.n_slots + h->dev.n_floor;
+    if (pt_lds_oct_layout(in).end > PT_LDS_BOUNCE_LIMIT) return;
+  }
+  const uint32_t n = (uint32_t)nd.size();
+  h->lds_oct.assign((size_t)n * 64 + PT_LOCT_LEAF_WORDS(n), 0u);
+  for (uint32_t o = 0; o < 8; ++o)
+    for (uint32_t k = 0; k < n; ++k) {
+      uint32_t* w = &h->lds_oct[((size_t)o * n + k) * 8];
+      const uint32_t* b32 = &h->nodes32[(size_t)k * 8]; /* mn.xyz, mx.xyz as binary32 */
+      float mag = 0.0f;
+      for (int a = 0; a < 3; ++a) {
+        const bool pos = (o >> a) & 1u; /* bit a set = component a >= 0: near = mn */
+        w[a] = pos ? b32[a] : b32[3 + a];
+        w[3 + a] = pos ? b32[3 + a] : b32[a];
+        float lo, hi;
+        std::memcpy(&lo, &b32[a], 4);
+        std::memcpy(&hi, &b32[3 + a], 4);
+        mag = std::fmax(mag, std::fmax(std::fabs(lo), std::fabs(hi)));
+      }
+      const uint32_t axis = nd[k].b >> 30, obase = o * n;
+      /* a hit: an inner node's near child (shape_tree.ml:209: lhs first where the component is >= 0), a leaf's own record under
+       * "holds a leaf"; a miss -- and the end of a leaf -- the octant's skip link */
+      const uint32_t hit = is_leaf(nd[k]) ? (PT_LOCT_LEAF_TAG | (obase + k)) : obase + (((o >> axis) & 1u) ? nd[k].a : (nd[k].b & 0x3fffffffu));
+      const uint32_t sk = h->skip32[(size_t)k * 8 + o];
+      w[6] = hit | ((sk == kNone ? PT_LOCT_END : obase + sk) << 16);
+      /* as pt_scene_view stores it in the shared image: rounded up, the two lowest mantissa bits carry the axis */
+      const float up = mag * 1.000001f;
+      uint32_t mb;
+      std::memcpy(&mb, &up, 4);
+      w[7] = ((mb + 4u) & ~3u) | axis;
+    }
+  for (uint32_t k = 0; k < n; ++k)
+    if (is_leaf(nd[k])) h->lds_oct[(size_t)n * 64 + k] = nd[k].a | (nd[k].pad[0] << 16);
+}
+
 /* top_nodes / skip32_top: the top of a tree that is too large for LDS as a whole, a breadth-first prefix */
 void top_image(const SceneOptions& opt, PtHostArrays* h) {
   const std::vector<PtNode>& nd = h->nodes;
@@ -397,6 +443,7 @@ SceneOptions scene_options_from_env() {
   SceneOptions o;
   o.tri_frame = env_int("PTX_TRI_FRAME", 1);
   o.oct_image = env_int("PTX_OCT_IMAGE", 1);
+  o.lds_oct = env_int("PTX_LDS_OCT", 1);
   o.top_nodes = std::max(0, std::min(1023, env_int("PTX_TOP_NODES", 512)));
   if (std::getenv("PTX_BIN_KEY")) { /* any other value: by octant */
     const int k = env_int("PTX_BIN_KEY", 0);
@@ -489,6 +536,7 @@ void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, cons
   thread_octants(h);
   binary32_image(h);
   octant_image(opt, h);
+  lds_octant_image(opt, h);
   top_image(opt, h);
   skip16_copy(h);
   bin_key(boxes, opt, h);

@@ -31,6 +31,7 @@ struct PtHostArrays {
   std::vector<uint32_t> skip32; /* node_skip32: n_nodes x 8 */
   std::vector<uint32_t> nodes32; /* 8 words per node: the binary32 filter image for the walk from HBM / L2 */
   std::vector<uint32_t> nodes32o; /* PtSceneDev.nodes32o: 8 octants x 8 words per node; empty = not built */
+  std::vector<uint32_t> lds_oct; /* PtSceneDev.lds_oct: 8 octants x 8 words per node, then the leaf table; empty = not built */
   std::vector<uint32_t> top_nodes, skip32_top; /* PtSceneDev.top_nodes (16 words per top node) / node_skip32_top; empty = none */
   /* the emissive tree triangles of the build list, in its order: 9 doubles each, kept up to one past PTX_MAX_LIGHT_TRIANGLES;
    * n_emissive_tris counts them all (ptx_scene_set_lighting makes the light table of them) */
@@ -43,6 +44,7 @@ struct PtHostArrays {
 struct SceneOptions {
   int tri_frame = 1;   /* PTX_TRI_FRAME: 0 = no tri_frame table */
   int oct_image = 1;   /* PTX_OCT_IMAGE: 0 = keep the shared image + skip table */
+  int lds_oct = 1;     /* PTX_LDS_OCT: 0 = no per-octant LDS image: every launch keeps the shared one */
   int top_nodes = 512; /* PTX_TOP_NODES: size of the breadth-first top image, clamped to 0 .. 1023 */
   int bin_key = -1;    /* PTX_BIN_KEY: -1 = by scene, 0 octant, 1 elevation, 2 reaches-the-root-box */
 };
