@@ -161,6 +161,36 @@ external set_lighting_int : scene -> int -> unit = "ptx_ml_set_lighting_stub"
 let set_lighting scene lighting =
   set_lighting_int scene (match lighting with Reference -> 0 | Path_order -> 1 | Sampled -> 2)
 
+(* The reconstruction filter the reference hard-wires in Integrator.render (Filter_kernel.Binomial.create ~order:5 ~pixel_radius:1),
+   at any accepted order and radius (ptx_scene_set_film): 1 <= order <= 16, 0 <= pixel_radius <= 7, order >= 2 * pixel_radius + 1 --
+   below that the reference's kernel comes out lopsided, and the library refuses it.  ~renormalise divides a border pixel by the weight
+   that stayed inside the image (the reference lets the border darken).  Sticky: every later render of the scene reads it.  Failure
+   for a refused pair, or while a render runs on the scene. *)
+external set_film_int : scene -> int -> int -> int -> unit = "ptx_ml_set_film_stub"
+external film_int : scene -> int * int * int = "ptx_ml_film_stub"
+
+external film_weights_into
+  :  int
+  -> int
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> unit
+  = "ptx_ml_film_weights_stub"
+
+let set_film ?(renormalise = false) scene ~order ~pixel_radius =
+  set_film_int scene order pixel_radius (if renormalise then 1 else 0)
+
+(* order, pixel_radius, renormalise *)
+let film scene =
+  let order, pixel_radius, flags = film_int scene in
+  order, pixel_radius, flags land 1 <> 0
+
+(* Binomial.create's normalised 1-D weights, 2 * pixel_radius + 1 of them; the 2-D weight is w.(j) *. w.(i) *)
+let film_weights ~order ~pixel_radius =
+  let n = (2 * max 0 (min pixel_radius 7)) + 1 in
+  let out = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout n in
+  film_weights_into order pixel_radius out;
+  Array.init n (fun i -> Bigarray.Array1.get out i)
+
 external render_flat
   :  scene
   -> int (* width *)

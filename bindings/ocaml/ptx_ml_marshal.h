@@ -250,4 +250,29 @@ static __attribute__((unused)) int32_t ptx_ml_render_denoised(ptx_scene* s, cons
   return ptx_render_denoised(s, &p, &pp, &dn, image, err, feat, passes_done, NULL, on_update, user);
 }
 
+/* Ptx.set_film: the film every later render of the scene applies (ptx_scene_set_film) */
+static __attribute__((unused)) int32_t ptx_ml_set_film(ptx_scene* s, int32_t order, int32_t pixel_radius, int32_t flags) {
+  ptx_film_params f;
+  memset(&f, 0, sizeof f);
+  f.order = order;
+  f.pixel_radius = pixel_radius;
+  f.flags = flags;
+  return ptx_scene_set_film(s, &f);
+}
+
+/* Ptx.film_weights: the 2 * pixel_radius + 1 weights into out (n_out doubles); -4 when out is too short for an accepted film (the
+ * library's own refusals keep their codes, and nothing is written) */
+static __attribute__((unused)) int32_t ptx_ml_film_weights(int32_t order, int32_t pixel_radius, double* out, int64_t n_out) {
+  ptx_film_params f;
+  memset(&f, 0, sizeof f);
+  f.order = order;
+  f.pixel_radius = pixel_radius;
+  double w[2 * PTX_FILM_MAX_RADIUS + 1];
+  const int32_t rc = ptx_film_weights(&f, w, NULL);
+  if (rc != 0) return rc;
+  if (!out || n_out < 2 * pixel_radius + 1) return -4;
+  memcpy(out, w, sizeof(double) * (size_t)(2 * pixel_radius + 1));
+  return 0;
+}
+
 #endif /* PTX_ML_MARSHAL_H */

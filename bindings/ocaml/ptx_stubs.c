@@ -269,6 +269,49 @@ CAMLprim value ptx_ml_set_lighting_stub(value handle, value mode) {
   CAMLreturn(Val_unit);
 }
 
+/* external set_film_int : scene -> int -> int -> int -> unit = "ptx_ml_set_film_stub" (ptx_scene_set_film: order, pixel_radius,
+ * flags; Ptx.set_film maps ~renormalise).  The film is what a running render applies at its end: like set_lighting it takes the scene
+ * exclusively and raises Failure while a render runs on another thread or domain, and Failure with the library's message for a
+ * refused (order, pixel_radius). */
+CAMLprim value ptx_ml_set_film_stub(value handle, value order, value pixel_radius, value flags) {
+  CAMLparam4(handle, order, pixel_radius, flags);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_film: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_film: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_set_film(s, (int32_t)Long_val(order), (int32_t)Long_val(pixel_radius), (int32_t)Long_val(flags));
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_film: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external film_int : scene -> int * int * int = "ptx_ml_film_stub" (ptx_scene_film: order, pixel_radius, flags) */
+CAMLprim value ptx_ml_film_stub(value handle) {
+  CAMLparam1(handle);
+  CAMLlocal1(tuple);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.film: scene already destroyed");
+  ptx_film_params f;
+  if (ptx_scene_film(s, &f) != 0) caml_failwith(ptx_last_error());
+  tuple = caml_alloc_tuple(3);
+  Store_field(tuple, 0, Val_long(f.order));
+  Store_field(tuple, 1, Val_long(f.pixel_radius));
+  Store_field(tuple, 2, Val_long(f.flags));
+  CAMLreturn(tuple);
+}
+
+/* external film_weights_into : int -> int -> weights -> unit = "ptx_ml_film_weights_stub" (ptx_film_weights, host only): the 2r + 1
+ * normalised 1-D weights of Binomial.create ~order ~pixel_radius into a Bigarray of at least 2r + 1 doubles */
+CAMLprim value ptx_ml_film_weights_stub(value order, value pixel_radius, value out) {
+  CAMLparam3(order, pixel_radius, out);
+  const int32_t rc = ptx_ml_film_weights((int32_t)Long_val(order), (int32_t)Long_val(pixel_radius), (double*)Caml_ba_data_val(out),
+                                         (int64_t)Caml_ba_array_val(out)->dim[0]);
+  if (rc == -4) caml_invalid_argument("Ptx.film_weights: the output holds fewer than 2 * pixel_radius + 1 doubles");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
 /* What a callback trampoline needs: the closure (a GC root registered by the stub that owns this struct) and the first
  * exception a callback raised.  While `raised` is set no further callbacks are made. */
 typedef struct ptx_ml_cb {

@@ -529,6 +529,63 @@ int32_t ptx_render_denoised(ptx_scene* scene, const ptx_render_params* params, c
                             double* feat_out /* nullable, HOST, W*H*8 means */, int32_t* passes_done_out, ptx_stats* stats,
                             ptx_update_fn on_update, void* user);
 
+/* ---- the film at any order and radius ----
+ * Filter_kernel.Binomial.create ~order ~pixel_radius (filter_kernel.ml:49-85) in full, in front of Film_tile at any radius
+ * (film_tile.ml:15-45).  The default (5, 1, flags 0) is the film every entry point above applies, and runs through the same kernels.
+ *
+ * Accepted: 1 <= order <= PTX_FILM_MAX_ORDER, 0 <= pixel_radius <= PTX_FILM_MAX_RADIUS, order >= 2 * pixel_radius + 1,
+ * flags within PTX_FILM_RENORMALISE, reserved = 0; everything else is PTX_ERR_ARG.  Why order < 2 * pixel_radius + 1 is refused:
+ * there a tap covers less than one cell of the binomial row, the reference's `k = 0` branch (one minus the fractional part of the
+ * tap's start) wins over its `k = len - 1` branch for such one-cell taps, and the kernel comes out lopsided -- (1, 1) gives
+ * [1/2, 1/3, 1/6], (3, 2) gives [0.208, 0.167, 0.333, 0.167, 0.125].  From order >= 2 * pixel_radius + 1 on the reference's rule is
+ * the plain overlap rule (tap i covers [i * order / f, (i + 1) * order / f) of the row, f = 2 * pixel_radius + 1): the 1-D weights
+ * are positive and palindromic bit for bit, and the 2-D weights sum to 1 within 2.3e-16.
+ *
+ * The weights: the reference's sums in exact rationals, float_of_num (to nearest), total = the left fold of + from 0.0 over the
+ * 2r + 1 values, w[i] = w[i] / total; the 2-D weight is W[j][i] = w[j] * w[i], one multiplication.
+ *
+ * The rule, operation for operation (binary64, no contraction), r = pixel_radius, w = the 1-D weights, S = the raw sums:
+ *   for pixel (x, y):  acc_c = 0; ws = 0; clipped = false
+ *     for dy = -r..r (outer), dx = -r..r (inner), W = w[dy + r] * w[dx + r]:
+ *       (sx, sy) = (x - dx, y - dy); outside the image: clipped = true, skip
+ *       acc_c = fma(W, S_c(sx, sy), acc_c);  ws = ws + W
+ *     if PTX_FILM_RENORMALISE and clipped: acc_c = acc_c / ws
+ *     out_c = sqrt(acc_c * (1.0 / spp))
+ * Without PTX_FILM_RENORMALISE the border keeps the reference's darkening (integrator.ml:114-128 drops the taps that fall outside
+ * the image: a 3x3 corner keeps about 59 %).  At (5, 1, 0) this is ptx_film_resolve_device bit for bit.
+ * Banded: S is read in place from the gathered layout, as ptx_film_resolve_banded_device does; band_rows may be smaller than r.
+ * Counts: `same` holds exactly when every in-image tap of the (2r + 1)^2 window has the centre's count n.  If same: the rule above
+ * with spp = n.  Otherwise acc_c = fma(W, S_c(q) * (1.0 / n(q)), acc_c), then the renormalisation, then out_c = sqrt(acc_c). */
+#define PTX_FILM_MAX_ORDER 16
+#define PTX_FILM_MAX_RADIUS 7
+#define PTX_FILM_RENORMALISE 1
+typedef struct ptx_film_params { /* 16 bytes */
+  int32_t order;        /* Binomial.create ~order */
+  int32_t pixel_radius; /* ... ~pixel_radius: a (2r + 1)^2 window */
+  int32_t flags;        /* PTX_FILM_RENORMALISE */
+  int32_t reserved;     /* 0 */
+} ptx_film_params;
+/* order 5, pixel_radius 1, flags 0 */
+int32_t ptx_film_defaults(ptx_film_params* out);
+/* Host only, needs no device: the normalised 1-D weights (w1d_out, 2r + 1 doubles) and, nullable, their outer product (w2d_out,
+ * (2r + 1)^2 doubles, row-major).  PTX_ERR_ARG for NULL film or w1d_out and for refused parameters. */
+int32_t ptx_film_weights(const ptx_film_params* film, double* w1d_out, double* w2d_out);
+/* The film of a scene: sticky state of the handle, like the lighting mode (NULL = the defaults).  Every entry point that films
+ * through the scene reads it -- ptx_render (a pinned image included), ptx_render_multi and n_gpus > 1 (the film of scenes[0] governs:
+ * the film runs there), ptx_render_progressive, ptx_render_adaptive, ptx_render_denoised; the scene-less ptx_film_resolve_device /
+ * _banded_device / _banded_queue / _counts_device stay (5, 1, 0).  A host-only scene accepts it; PTX_ERR_STATE while a render runs on
+ * the scene (from a progress / update / round callback); ptx_scene_replicate copies it. */
+int32_t ptx_scene_set_film(ptx_scene* scene, const ptx_film_params* film);
+int32_t ptx_scene_film(const ptx_scene* scene, ptx_film_params* out);
+/* ptx_film_resolve_device / _banded_device / _counts_device with a film (NULL = the defaults).  Each waits for `stream`. */
+int32_t ptx_film_resolve_ex_device(int32_t device, int32_t width, int32_t height, int32_t samples_per_pixel,
+                                   const ptx_film_params* film, const double* d_raw_full, double* d_rgb_out, void* stream);
+int32_t ptx_film_resolve_banded_ex_device(int32_t device, int32_t width, int32_t height, int32_t samples_per_pixel,
+                                          const ptx_film_params* film, const double* d_gathered, int32_t n_ranks, int32_t band_rows,
+                                          int32_t pad_rows, double* d_rgb_out, void* stream);
+int32_t ptx_film_resolve_counts_ex_device(int32_t device, int32_t width, int32_t height, const ptx_film_params* film,
+                                          const double* d_raw, const int32_t* d_passes, double* d_rgb_out, void* stream);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

@@ -38,6 +38,8 @@ EXPORTS = (
     "ptx_render_pixels_device", "ptx_film_resolve_counts_device", "ptx_pixel_error_counts_device", "ptx_render_adaptive",
     "ptx_scene_set_lighting", "ptx_scene_lighting",
     "ptx_render_features_device", "ptx_denoise_defaults", "ptx_denoise_device", "ptx_render_denoised",
+    "ptx_film_defaults", "ptx_film_weights", "ptx_scene_set_film", "ptx_scene_film", "ptx_film_resolve_ex_device",
+    "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -119,6 +121,16 @@ def lib():
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptx_render_denoised.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.ProgressiveParams),
                                       C.POINTER(abi.DenoiseParams), dp, dp, dp, ip, C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
+    fp = C.POINTER(abi.FilmParams)
+    L.ptx_film_defaults.argtypes = [fp]
+    L.ptx_film_weights.argtypes = [fp, dp, dp]
+    L.ptx_scene_set_film.argtypes = [C.c_void_p, fp]
+    L.ptx_scene_film.argtypes = [C.c_void_p, fp]
+    L.ptx_film_resolve_ex_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ptx_film_resolve_banded_ex_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_void_p, C.c_void_p]
+    L.ptx_film_resolve_counts_ex_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, fp, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
     _LIB = L
     return L
 
@@ -202,6 +214,22 @@ class Scene:
         area = C.c_double(0.0)
         _check(lib().ptx_scene_lighting(self._h, C.byref(mode), C.byref(n), C.byref(area)))
         return mode.value, n.value, area.value
+
+    def set_film(self, order=None, radius=None, renormalise=False):
+        """ptx_scene_set_film: the reconstruction filter Binomial.create ~order ~pixel_radius every later render of this scene films
+        with, and whether border pixels are renormalised by the weight that stayed inside the image.  Sticky; set_film() restores
+        the default (5, 1, no renormalisation)."""
+        if order is None and radius is None:
+            _check(lib().ptx_scene_set_film(self._h, None))
+            return
+        f = abi.film_params((order, radius, renormalise))
+        _check(lib().ptx_scene_set_film(self._h, C.byref(f)))
+
+    def film(self):
+        """ptx_scene_film: (order, radius, renormalise)"""
+        f = abi.FilmParams()
+        _check(lib().ptx_scene_film(self._h, C.byref(f)))
+        return f.order, f.pixel_radius, bool(f.flags & abi.PTX_FILM_RENORMALISE)
 
     def stats(self):
         st = abi.Stats()
@@ -553,8 +581,30 @@ def denoise_device(device, width, height, denoise, passes_done, feature_passes_d
                                     C.c_void_p(stream) if stream else None))
 
 
-def film_resolve_counts_device(device, width, height, d_raw_ptr, d_passes_ptr, d_rgb_ptr, stream=None):
-    """ptx_film_resolve_counts_device: the film of DEVICE raw sums with a per-pixel pass count (int32, H x W)"""
+def film_defaults():
+    """ptx_film_defaults: (order, radius, renormalise) = (5, 1, False)"""
+    f = abi.FilmParams()
+    _check(lib().ptx_film_defaults(C.byref(f)))
+    return f.order, f.pixel_radius, bool(f.flags & abi.PTX_FILM_RENORMALISE)
+
+
+def film_weights(order, radius):
+    """ptx_film_weights (host only): Binomial.create ~order ~pixel_radius as (w1d of 2r + 1 weights, w2d = their outer product)."""
+    f = abi.film_params((order, radius))
+    n = 2 * f.pixel_radius + 1
+    w1, w2 = np.zeros(n), np.zeros((n, n))
+    _check(lib().ptx_film_weights(C.byref(f), _dp(w1), _dp(w2)))
+    return w1, w2
+
+
+def film_resolve_counts_device(device, width, height, d_raw_ptr, d_passes_ptr, d_rgb_ptr, stream=None, film=None):
+    """ptx_film_resolve_counts_device: the film of DEVICE raw sums with a per-pixel pass count (int32, H x W); film: what
+    abi.film_params takes (ptx_film_resolve_counts_ex_device)"""
+    if film is not None:
+        f = abi.film_params(film)
+        _check(lib().ptx_film_resolve_counts_ex_device(device, width, height, C.byref(f), C.c_void_p(d_raw_ptr), C.c_void_p(d_passes_ptr),
+                                                       C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
+        return
     _check(lib().ptx_film_resolve_counts_device(device, width, height, C.c_void_p(d_raw_ptr), C.c_void_p(d_passes_ptr),
                                                 C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
 
@@ -581,14 +631,29 @@ def render_multi(scenes, width, height, samples_per_pixel, max_bounces, progress
 
 
 def film_resolve_banded_device(device, width, height, samples_per_pixel, d_gathered_ptr, n_ranks, band_rows, pad_rows,
-                               d_rgb_ptr, stream=None, wait=True):
-    """wait=False: ptx_film_resolve_banded_queue -- the pass is queued on `stream`, the call does not wait for it."""
+                               d_rgb_ptr, stream=None, wait=True, film=None):
+    """wait=False: ptx_film_resolve_banded_queue -- the pass is queued on `stream`, the call does not wait for it.
+    film: what abi.film_params takes (ptx_film_resolve_banded_ex_device, which always waits)."""
+    if film is not None:
+        if not wait:
+            raise ValueError("a film other than the default has no queued form: wait must be True")
+        f = abi.film_params(film)
+        _check(lib().ptx_film_resolve_banded_ex_device(device, width, height, samples_per_pixel, C.byref(f), C.c_void_p(d_gathered_ptr),
+                                                       n_ranks, band_rows, pad_rows, C.c_void_p(d_rgb_ptr),
+                                                       C.c_void_p(stream) if stream else None))
+        return
     fn = lib().ptx_film_resolve_banded_device if wait else lib().ptx_film_resolve_banded_queue
     _check(fn(device, width, height, samples_per_pixel, C.c_void_p(d_gathered_ptr), n_ranks, band_rows, pad_rows,
               C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
 
 
-def film_resolve_device(device, width, height, samples_per_pixel, d_raw_ptr, d_rgb_ptr, stream=None):
+def film_resolve_device(device, width, height, samples_per_pixel, d_raw_ptr, d_rgb_ptr, stream=None, film=None):
+    """film: what abi.film_params takes (ptx_film_resolve_ex_device)"""
+    if film is not None:
+        f = abi.film_params(film)
+        _check(lib().ptx_film_resolve_ex_device(device, width, height, samples_per_pixel, C.byref(f), C.c_void_p(d_raw_ptr),
+                                                C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
+        return
     _check(lib().ptx_film_resolve_device(device, width, height, samples_per_pixel, C.c_void_p(d_raw_ptr),
                                          C.c_void_p(d_rgb_ptr), C.c_void_p(stream) if stream else None))
 

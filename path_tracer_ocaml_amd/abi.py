@@ -107,6 +107,38 @@ class DenoiseParams(C.Structure):
                 ("sigma_luminance", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
+PTX_FILM_MAX_ORDER, PTX_FILM_MAX_RADIUS = 16, 7
+PTX_FILM_RENORMALISE = 1
+
+
+class FilmParams(C.Structure):
+    _fields_ = [("order", C.c_int32), ("pixel_radius", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def film_params(film=None, renormalise=None):
+    """An abi.FilmParams from None (order 5, radius 1, no renormalisation), an (order, radius) or (order, radius, renormalise)
+    tuple, or a FilmParams; checked as the library checks it (ValueError)."""
+    if isinstance(film, FilmParams):
+        f = FilmParams(film.order, film.pixel_radius, film.flags, film.reserved)
+    else:
+        t = (5, 1) if film is None else tuple(film)
+        if len(t) not in (2, 3):
+            raise ValueError("film must be (order, radius) or (order, radius, renormalise)")
+        f = FilmParams(int(t[0]), int(t[1]), PTX_FILM_RENORMALISE if len(t) == 3 and t[2] else 0, 0)
+    if renormalise is not None:
+        f.flags = PTX_FILM_RENORMALISE if renormalise else 0
+    if not 1 <= f.order <= PTX_FILM_MAX_ORDER:
+        raise ValueError(f"film order must be in [1, {PTX_FILM_MAX_ORDER}] (got {f.order})")
+    if not 0 <= f.pixel_radius <= PTX_FILM_MAX_RADIUS:
+        raise ValueError(f"film radius must be in [0, {PTX_FILM_MAX_RADIUS}] (got {f.pixel_radius})")
+    if f.order < 2 * f.pixel_radius + 1:
+        raise ValueError(f"film order {f.order} is smaller than 2 * radius + 1 = {2 * f.pixel_radius + 1}: the reference's kernel is "
+                         "lopsided there")
+    if f.flags & ~PTX_FILM_RENORMALISE or f.reserved:
+        raise ValueError("unknown bits in the film's flags")
+    return f
+
+
 # ptx_round_fn: (user, round, passes_done, active_next, samples, rel_err, rgb, err, passes) -> non-zero stops the render
 ROUND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                        C.c_void_p)

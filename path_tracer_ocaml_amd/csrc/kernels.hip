@@ -3629,6 +3629,119 @@ __global__ __launch_bounds__(256) void k_film_counts(const double* __restrict__ 
   out[3 * p + 2] = pt_sqrt(b);
 }
 
+/* ------------------------------------------------------------------ the film at any order and radius (ptx_film_params) */
+/* Binomial.create ~order ~pixel_radius for a run-time radius r in 0 .. 7: the rule of include/ptx.h, operation for operation.  A
+ * 256-thread workgroup owns a 32 x 8 tile of output pixels.  It copies the tile and a halo of r pixels into LDS as three planes, one
+ * per channel (the 24-byte pixel stride of the sums would put a wave's reads two to a bank; a plane's row is 32 consecutive doubles
+ * per half wave, one per bank pair), 46 x 22 x 3 doubles = 24288 bytes at r = 7, then runs the (2r + 1)^2 taps from LDS in the rule's
+ * order: dy outer, dx inner, one fma per channel.  Not separable: two 1-D passes would round differently.
+ * The taps outside the image are skipped by clamping the two loop ranges (in-image is a range of dx and a range of dy), so the
+ * interior runs without a per-tap test and the halo cells outside the image are never read (nor written).
+ * COUNTS: a fourth plane holds the per-pixel pass counts n(q) (k_film_counts with a wider window). */
+constexpr int PT_FILM_MAX_R = 7; /* PTX_FILM_MAX_RADIUS */
+constexpr int PT_FILM_TX = 32, PT_FILM_TY = 8;
+constexpr int PT_FILM_LW = PT_FILM_TX + 2 * PT_FILM_MAX_R, PT_FILM_LH = PT_FILM_TY + 2 * PT_FILM_MAX_R; /* the LDS tile: 46 x 22 */
+constexpr int PT_FILM_PLANE = PT_FILM_LW * PT_FILM_LH;
+struct PtFilmWide {
+  int r;
+  double w[2 * PT_FILM_MAX_R + 1]; /* the normalised 1-D weights, 2r + 1 of them */
+};
+/* image rows [row0, row1) (the tiles start at row0); passes != nullptr exactly when COUNTS */
+template <bool COUNTS, bool RENORM>
+__device__ __forceinline__ void pt_film_wide_tile(const double* __restrict__ raw, const int32_t* __restrict__ passes, int width, int height,
+                                                  double spp_inv, const PtFilmWide& kern, const PtBandMap& map, double* __restrict__ out,
+                                                  int row0, int row1, double* lds_s, int32_t* lds_n, double* lds_w) {
+  const int r = kern.r, tid = (int)threadIdx.x;
+  const int x0 = (int)blockIdx.x * PT_FILM_TX, y0 = row0 + (int)blockIdx.y * PT_FILM_TY;
+  const int tw = PT_FILM_TX + 2 * r, th = PT_FILM_TY + 2 * r;
+  if (tid <= 2 * r) lds_w[tid] = kern.w[tid];
+  /* a tile row is 3 * tw consecutive doubles of the sums: consecutive lanes read consecutive doubles */
+  const int row_d = 3 * tw;
+  for (int i = tid; i < th * row_d; i += PT_FILM_TX * PT_FILM_TY) {
+    const int ly = i / row_d, j = i - ly * row_d, lx = j / 3, c = j - 3 * lx;
+    const int sx = x0 - r + lx, sy = y0 - r + ly;
+    if (sx < 0 || sx >= width || sy < 0 || sy >= height) continue;
+    lds_s[c * PT_FILM_PLANE + ly * PT_FILM_LW + lx] = raw[(pt_band_row(map, sy) * width + sx) * 3 + c];
+  }
+  if (COUNTS) {
+    for (int i = tid; i < th * tw; i += PT_FILM_TX * PT_FILM_TY) {
+      const int ly = i / tw, lx = i - ly * tw;
+      const int sx = x0 - r + lx, sy = y0 - r + ly;
+      if (sx < 0 || sx >= width || sy < 0 || sy >= height) continue;
+      lds_n[ly * PT_FILM_LW + lx] = passes[(long long)sy * width + sx];
+    }
+  }
+  __syncthreads();
+  const int tx = tid % PT_FILM_TX, ty = tid / PT_FILM_TX;
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= width || y >= row1) return;
+  /* (x - dx, y - dy) is inside the image for dx in [dx_lo, dx_hi], dy in [dy_lo, dy_hi] */
+  const int dx_lo = x - (width - 1) > -r ? x - (width - 1) : -r, dx_hi = x < r ? x : r;
+  const int dy_lo = y - (height - 1) > -r ? y - (height - 1) : -r, dy_hi = y < r ? y : r;
+  const bool clipped = dx_lo > -r || dx_hi < r || dy_lo > -r || dy_hi < r;
+  const int centre = (ty + r) * PT_FILM_LW + tx + r;
+  bool same = true;
+  int n0 = 1;
+  if (COUNTS) {
+    n0 = lds_n[centre];
+    for (int dy = dy_lo; dy <= dy_hi; ++dy)
+      for (int dx = dx_lo; dx <= dx_hi; ++dx)
+        if (lds_n[centre - dy * PT_FILM_LW - dx] != n0) same = false;
+  }
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, ws = 0.0;
+  for (int dy = dy_lo; dy <= dy_hi; ++dy) {
+    const double wy = lds_w[dy + r];
+    const int qrow = centre - dy * PT_FILM_LW;
+    for (int dx = dx_lo; dx <= dx_hi; ++dx) {
+      const double wgt = wy * lds_w[dx + r];
+      const int q = qrow - dx;
+      double s0 = lds_s[q], s1 = lds_s[PT_FILM_PLANE + q], s2 = lds_s[2 * PT_FILM_PLANE + q];
+      if (COUNTS && !same) {
+        const double inv = 1.0 / (double)lds_n[q];
+        s0 = s0 * inv;
+        s1 = s1 * inv;
+        s2 = s2 * inv;
+      }
+      a0 = pt_fma(wgt, s0, a0);
+      a1 = pt_fma(wgt, s1, a1);
+      a2 = pt_fma(wgt, s2, a2);
+      if (RENORM) ws = ws + wgt;
+    }
+  }
+  if (RENORM && clipped) {
+    a0 = a0 / ws;
+    a1 = a1 / ws;
+    a2 = a2 / ws;
+  }
+  if (same) {
+    const double inv = COUNTS ? 1.0 / (double)n0 : spp_inv;
+    a0 = a0 * inv;
+    a1 = a1 * inv;
+    a2 = a2 * inv;
+  }
+  const long long p = (long long)y * width + x;
+  out[3 * p] = pt_sqrt(a0);
+  out[3 * p + 1] = pt_sqrt(a1);
+  out[3 * p + 2] = pt_sqrt(a2);
+}
+/* k_film at any radius: grid (ceil(width / 32), ceil((row1 - row0) / 8)) */
+template <bool RENORM>
+__global__ __launch_bounds__(PT_FILM_TX * PT_FILM_TY) void k_film_wide(const double* __restrict__ raw, int width, int height, double spp_inv,
+                                                                        PtFilmWide kern, PtBandMap map, double* __restrict__ out, int row0, int row1) {
+  __shared__ double lds_s[3 * PT_FILM_PLANE];
+  __shared__ double lds_w[2 * PT_FILM_MAX_R + 1];
+  pt_film_wide_tile<false, RENORM>(raw, nullptr, width, height, spp_inv, kern, map, out, row0, row1, lds_s, nullptr, lds_w);
+}
+/* k_film_counts at any radius, over the whole image */
+template <bool RENORM>
+__global__ __launch_bounds__(PT_FILM_TX * PT_FILM_TY) void k_film_wide_counts(const double* __restrict__ raw, const int32_t* __restrict__ passes,
+                                                                               int width, int height, PtFilmWide kern, double* __restrict__ out) {
+  __shared__ double lds_s[3 * PT_FILM_PLANE];
+  __shared__ int32_t lds_n[PT_FILM_PLANE];
+  __shared__ double lds_w[2 * PT_FILM_MAX_R + 1];
+  pt_film_wide_tile<true, RENORM>(raw, passes, width, height, 1.0, kern, PtBandMap{1, 1, 0}, out, 0, height, lds_s, lds_n, lds_w);
+}
+
 /* k_pixel_error with the pixel's own pass count k = passes[p]; the partials are k_error_summary's (called with k = 2: a pixel with
  * fewer than 2 passes has se = +inf, which the sums carry) */
 __global__ __launch_bounds__(PT_ERR_THREADS) void k_pixel_error_counts(const double* __restrict__ raw, const double* __restrict__ sq,

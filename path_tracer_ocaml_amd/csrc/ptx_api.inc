@@ -87,6 +87,71 @@ void binomial_3x3(double out[9]) {
   for (int j = 0; j < 9; ++j) out[j] = w[j / 3] * w[j % 3]; /* outer_product */
 }
 
+/* Filter_kernel.Binomial.create ~order ~pixel_radius (filter_kernel.ml:49-85) restated literally, Num as reduced 64-bit rationals
+ * (order <= 16: C(15, k) <= 6435 and 15! < 2^41, the denominators divide 2r + 1 <= 15).  w: the 2r + 1 normalised 1-D weights.
+ * binomial_3x3 above is the (5, 1) instance written out by hand; the default film keeps using it. */
+struct FilmRat {
+  long long n, d; /* d > 0, gcd(n, d) = 1 */
+};
+long long film_gcd(long long a, long long b) {
+  if (a < 0) a = -a;
+  while (b) {
+    const long long t = a % b;
+    a = b;
+    b = t;
+  }
+  return a ? a : 1;
+}
+FilmRat film_rat(long long n, long long d) {
+  const long long g = film_gcd(n, d);
+  return FilmRat{n / g, d / g};
+}
+FilmRat film_add(FilmRat a, FilmRat b) { return film_rat(a.n * b.d + b.n * a.d, a.d * b.d); }
+FilmRat film_sub(FilmRat a, FilmRat b) { return film_rat(a.n * b.d - b.n * a.d, a.d * b.d); }
+FilmRat film_mul(FilmRat a, FilmRat b) { return film_rat(a.n * b.n, a.d * b.d); }
+long long film_floor(FilmRat a) { return a.n >= 0 ? a.n / a.d : -((-a.n + a.d - 1) / a.d); }
+long long film_ceil(FilmRat a) { return -film_floor(FilmRat{-a.n, a.d}); }
+long long film_pow_falling(long long n, long long k) { return k == 0 ? 1 : n * film_pow_falling(n - 1, k - 1); } /* :27 */
+long long film_binomial(long long n, long long k) { return film_pow_falling(n, k) / film_pow_falling(k, k); }    /* :28-29 */
+void film_weights_1d(int order, int pixel_radius, double* w) {
+  const int f_width = 1 + 2 * pixel_radius;
+  const FilmRat ratio = film_rat(order, f_width), one = film_rat(1, 1);
+  long long coeffs[PTX_FILM_MAX_ORDER];
+  for (int k = 0; k < order; ++k) coeffs[k] = film_binomial(order - 1, k);
+  for (int i = 0; i < f_width; ++i) {
+    const FilmRat ip = film_mul(film_rat(i, 1), ratio); /* i' */
+    const FilmRat jp = film_add(ip, ratio);             /* j' */
+    const long long beg = film_floor(ip), end_ = film_ceil(jp), len = end_ - beg;
+    FilmRat sum = film_rat(0, 1);
+    for (long long k = 0; k < len; ++k) {
+      FilmRat weight = one;
+      if (k == 0) weight = film_sub(one, film_sub(ip, film_rat(film_floor(ip), 1))); /* one -/ fractional_part i' */
+      else if (k == len - 1) weight = film_sub(one, film_sub(film_rat(end_, 1), jp));
+      sum = film_add(sum, film_mul(weight, film_rat(coeffs[k + beg], 1)));
+    }
+    w[i] = (double)sum.n / (double)sum.d; /* float_of_num: both are exact in binary64, the quotient rounds to nearest */
+  }
+  double total = 0.0;
+  for (int i = 0; i < f_width; ++i) total = total + w[i]; /* fold_left ( +. ) ~init:0.0, :82 */
+  for (int i = 0; i < f_width; ++i) w[i] = w[i] / total;  /* :83 */
+}
+
+/* the accepted ptx_film_params (include/ptx.h); the message names the rule that refused */
+int film_check(const ptx_film_params* f) {
+  if (f->order < 1 || f->order > PTX_FILM_MAX_ORDER) return fail(PTX_ERR_ARG, "film: order %d is outside 1 .. %d", f->order, PTX_FILM_MAX_ORDER);
+  if (f->pixel_radius < 0 || f->pixel_radius > PTX_FILM_MAX_RADIUS)
+    return fail(PTX_ERR_ARG, "film: pixel_radius %d is outside 0 .. %d", f->pixel_radius, PTX_FILM_MAX_RADIUS);
+  if (f->order < 2 * f->pixel_radius + 1)
+    return fail(PTX_ERR_ARG, "film: order %d is smaller than 2 * pixel_radius + 1 = %d (the reference's kernel is lopsided there)", f->order,
+                2 * f->pixel_radius + 1);
+  if (f->flags & ~PTX_FILM_RENORMALISE) return fail(PTX_ERR_ARG, "film: unknown bits in flags (%d): only PTX_FILM_RENORMALISE is defined", f->flags);
+  if (f->reserved != 0) return fail(PTX_ERR_ARG, "film: reserved must be 0 (got %d)", f->reserved);
+  return 0;
+}
+constexpr ptx_film_params kFilmDefault = {5, 1, 0, 0};
+/* the film the existing kernels apply (k_film, k_film_counts) */
+bool film_is_default(const ptx_film_params& f) { return f.order == 5 && f.pixel_radius == 1 && f.flags == 0; }
+
 /* A device allocation that frees itself: a member of ptx_scene (or a local) cannot be forgotten by a hand-kept release list.
  * hipFree needs the owning device current only for the ordering the runtime gives it; ptx_scene_destroy sets it before the
  * handle's members go. */
@@ -227,6 +292,7 @@ struct ptx_scene {
    * (PT_LIGHT_DOUBLES per record) and its device copy, which lives as long as the handle (queued frames keep reading it);
    * the number of calls that are rendering with this handle right now */
   int lighting = 0;
+  ptx_film_params film = kFilmDefault;      /* ptx_scene_set_film: what every entry point that films through this handle applies */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
   std::atomic<int> busy{0};
@@ -894,6 +960,10 @@ struct PassRange {
 };
 /* ptx_render's tail (below): row slabs of the frame's last accumulate, an event recorded behind each */
 constexpr int kMaxFinalSlabs = 8;
+constexpr int kMinSlabImageRows = 64; /* ptx_render cuts the tail of a pinned image into slabs from this height on */
+/* render_into_pinned films slab k once slab k + 1 has been summed; the film reads pixel_radius rows beyond a slab on both sides, so
+ * every slab must hold at least the largest radius in rows */
+static_assert(kMinSlabImageRows / kMaxFinalSlabs >= PTX_FILM_MAX_RADIUS, "a row slab of a pinned image must be at least PTX_FILM_MAX_RADIUS rows high");
 struct FinalSlabs {
   int n = 0;
   int row[kMaxFinalSlabs + 1] = {};   /* slab k = image rows [row[k], row[k + 1]) */
@@ -1341,13 +1411,36 @@ bool bvh_build_gpu(const std::vector<Box>& boxes, int num_bins, int length_cutof
   return true;
 }
 
-/* rows [row0, row1) of the image (reads raw rows row0 - 1 .. row1); row1 < 0: the whole image */
+/* a checked, non-default film as the k_film_wide kernels take it */
+PtFilmWide film_wide_arg(const ptx_film_params& f) {
+  PtFilmWide k{};
+  k.r = f.pixel_radius;
+  film_weights_1d(f.order, f.pixel_radius, k.w);
+  return k;
+}
+/* PTX_FILM_WIDE=1: the default film runs k_film_wide too (tools/film_cost.py measures it against k_film; same bits) */
+bool film_wide_forced() { return env_int("PTX_FILM_WIDE", 0) != 0; }
+dim3 film_wide_grid(int width, int rows) { return dim3((unsigned)((width + PT_FILM_TX - 1) / PT_FILM_TX), (unsigned)((rows + PT_FILM_TY - 1) / PT_FILM_TY)); }
+
+/* rows [row0, row1) of the image (reads raw rows row0 - r .. row1 - 1 + r, r = the film's radius); row1 < 0: the whole image.
+ * film: checked parameters; the default film runs k_film, every other one k_film_wide */
 int film_resolve(int width, int height, int spp, const double* d_raw, double* d_out, hipStream_t st,
-                 PtBandMap map = PtBandMap{1, 1, 0}, int row0 = 0, int row1 = -1) {
-  PtFilm3 k;
-  binomial_3x3(k.w);
+                 PtBandMap map = PtBandMap{1, 1, 0}, int row0 = 0, int row1 = -1, const ptx_film_params& film = kFilmDefault) {
   const double spp_inv = 1.0 / (double)spp; /* 1 // samples_per_pixel */
   if (row1 < 0) row1 = height;
+  if (!film_is_default(film) || film_wide_forced()) {
+    if (row1 <= row0) return 0;
+    const PtFilmWide kw = film_wide_arg(film);
+    const dim3 grid = film_wide_grid(width, row1 - row0);
+    if (film.flags & PTX_FILM_RENORMALISE)
+      hipLaunchKernelGGL(k_film_wide<true>, grid, dim3(PT_FILM_TX * PT_FILM_TY), 0, st, d_raw, width, height, spp_inv, kw, map, d_out, row0, row1);
+    else
+      hipLaunchKernelGGL(k_film_wide<false>, grid, dim3(PT_FILM_TX * PT_FILM_TY), 0, st, d_raw, width, height, spp_inv, kw, map, d_out, row0, row1);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  PtFilm3 k;
+  binomial_3x3(k.w);
   const long long n = (long long)width * (row1 - row0);
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, spp_inv, k, map, d_out, row0, row1);
@@ -1372,7 +1465,18 @@ int pixel_error_queue(long long npix, int k, const int32_t* d_passes, const doub
 }
 
 /* adaptive sampling: k_film_counts queued on st */
-int film_counts_queue(int width, int height, const double* d_raw, const int32_t* d_passes, double* d_out, hipStream_t st) {
+int film_counts_queue(int width, int height, const double* d_raw, const int32_t* d_passes, double* d_out, hipStream_t st,
+                      const ptx_film_params& film = kFilmDefault) {
+  if (!film_is_default(film) || film_wide_forced()) {
+    const PtFilmWide kw = film_wide_arg(film);
+    const dim3 grid = film_wide_grid(width, height);
+    if (film.flags & PTX_FILM_RENORMALISE)
+      hipLaunchKernelGGL(k_film_wide_counts<true>, grid, dim3(PT_FILM_TX * PT_FILM_TY), 0, st, d_raw, d_passes, width, height, kw, d_out);
+    else
+      hipLaunchKernelGGL(k_film_wide_counts<false>, grid, dim3(PT_FILM_TX * PT_FILM_TY), 0, st, d_raw, d_passes, width, height, kw, d_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   PtFilm3 k;
   binomial_3x3(k.w);
   const long long n = (long long)width * height;
@@ -1664,6 +1768,45 @@ int32_t ptx_scene_lighting(const ptx_scene* s, int32_t* mode_out, int32_t* n_lig
   return 0;
 }
 
+int32_t ptx_film_defaults(ptx_film_params* out) {
+  if (!out) return fail(PTX_ERR_ARG, "NULL argument");
+  *out = kFilmDefault;
+  return 0;
+}
+
+int32_t ptx_film_weights(const ptx_film_params* film, double* w1d_out, double* w2d_out) {
+  if (!film || !w1d_out) return fail(PTX_ERR_ARG, "NULL argument");
+  const int rc = film_check(film);
+  if (rc) return rc;
+  const int f_width = 2 * film->pixel_radius + 1;
+  double w[2 * PTX_FILM_MAX_RADIUS + 1];
+  film_weights_1d(film->order, film->pixel_radius, w);
+  for (int i = 0; i < f_width; ++i) w1d_out[i] = w[i];
+  if (w2d_out)
+    for (int j = 0; j < f_width * f_width; ++j) w2d_out[j] = w[j / f_width] * w[j % f_width]; /* outer_product, :40-47 */
+  return 0;
+}
+
+int32_t ptx_scene_set_film(ptx_scene* s, const ptx_film_params* film) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  const ptx_film_params f = film ? *film : kFilmDefault;
+  int rc = film_check(&f);
+  if (rc) return rc;
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the film cannot change while a render runs on the scene");
+  s->film = f;
+  for (ptx_scene* r : s->replicas) {
+    rc = ptx_scene_set_film(r, &f);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_film(const ptx_scene* s, ptx_film_params* out) {
+  if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
+  *out = s->film;
+  return 0;
+}
+
 int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
   if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
   std::memset(out, 0, sizeof *out);
@@ -1694,8 +1837,23 @@ int32_t ptx_film_resolve_device(int32_t device, int32_t width, int32_t height, i
   return 0;
 }
 
+int32_t ptx_film_resolve_ex_device(int32_t device, int32_t width, int32_t height, int32_t spp, const ptx_film_params* film,
+                                   const double* d_raw_full, double* d_rgb_out, void* stream) {
+  if (!d_raw_full || !d_rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || height <= 0 || spp <= 0) return fail(PTX_ERR_ARG, "bad dimensions");
+  const ptx_film_params f = film ? *film : kFilmDefault;
+  int rc = film_check(&f);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  rc = film_resolve(width, height, spp, d_raw_full, d_rgb_out, (hipStream_t)stream, PtBandMap{1, 1, 0}, 0, -1, f);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return 0;
+}
+
 static int32_t film_resolve_banded(int32_t device, int32_t width, int32_t height, int32_t spp, const double* d_gathered,
-                                   int32_t n_ranks, int32_t band_rows, int32_t pad_rows, double* d_rgb_out, void* stream, bool wait) {
+                                   int32_t n_ranks, int32_t band_rows, int32_t pad_rows, double* d_rgb_out, void* stream, bool wait,
+                                   const ptx_film_params& film = kFilmDefault) {
   if (!d_gathered || !d_rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
   if (width <= 0 || height <= 0 || spp <= 0) return fail(PTX_ERR_ARG, "bad dimensions");
   if (n_ranks < 1 || band_rows < 1) return fail(PTX_ERR_ARG, "need n_ranks >= 1 and band_rows >= 1");
@@ -1707,7 +1865,7 @@ static int32_t film_resolve_banded(int32_t device, int32_t width, int32_t height
     if (local_rows(&q) > pad_rows) return fail(PTX_ERR_ARG, "pad_rows %d is smaller than rank %d's %d rows", pad_rows, r, local_rows(&q));
   }
   HIP_TRY(hipSetDevice(device));
-  int rc = film_resolve(width, height, spp, d_gathered, d_rgb_out, (hipStream_t)stream, PtBandMap{n_ranks, band_rows, pad_rows});
+  int rc = film_resolve(width, height, spp, d_gathered, d_rgb_out, (hipStream_t)stream, PtBandMap{n_ranks, band_rows, pad_rows}, 0, -1, film);
   if (rc) return rc;
   if (wait) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return 0;
@@ -1715,6 +1873,14 @@ static int32_t film_resolve_banded(int32_t device, int32_t width, int32_t height
 int32_t ptx_film_resolve_banded_device(int32_t device, int32_t width, int32_t height, int32_t spp, const double* d_gathered,
                                        int32_t n_ranks, int32_t band_rows, int32_t pad_rows, double* d_rgb_out, void* stream) {
   return film_resolve_banded(device, width, height, spp, d_gathered, n_ranks, band_rows, pad_rows, d_rgb_out, stream, true);
+}
+int32_t ptx_film_resolve_banded_ex_device(int32_t device, int32_t width, int32_t height, int32_t spp, const ptx_film_params* film,
+                                          const double* d_gathered, int32_t n_ranks, int32_t band_rows, int32_t pad_rows, double* d_rgb_out,
+                                          void* stream) {
+  const ptx_film_params f = film ? *film : kFilmDefault;
+  const int rc = film_check(&f);
+  if (rc) return rc;
+  return film_resolve_banded(device, width, height, spp, d_gathered, n_ranks, band_rows, pad_rows, d_rgb_out, stream, true, f);
 }
 int32_t ptx_film_resolve_banded_queue(int32_t device, int32_t width, int32_t height, int32_t spp, const double* d_gathered,
                                       int32_t n_ranks, int32_t band_rows, int32_t pad_rows, double* d_rgb_out, void* stream) {
@@ -1756,6 +1922,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->n_prims = src->n_prims;
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;
+  s->film = src->film;
   if (scene_upload(s) != 0 || (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
     ptx_scene_destroy(s);
     return nullptr;
@@ -1774,14 +1941,14 @@ struct EventPair {
   }
 };
 
-int timed_film(const ptx_render_params& p, const double* d_raw, double* d_rgb, PtBandMap map, ptx_stats* stats) {
+int timed_film(const ptx_render_params& p, const double* d_raw, double* d_rgb, PtBandMap map, ptx_stats* stats, const ptx_film_params& film) {
   EventPair ev;
   if (p.time_kernels) {
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     HIP_TRY(hipEventRecord(ev.a, nullptr));
   }
-  int rc = film_resolve(p.width, p.height, p.samples_per_pixel, d_raw, d_rgb, nullptr, map);
+  int rc = film_resolve(p.width, p.height, p.samples_per_pixel, d_raw, d_rgb, nullptr, map, 0, -1, film);
   if (rc) return rc;
   if (p.time_kernels) {
     HIP_TRY(hipEventRecord(ev.b, nullptr));
@@ -1992,7 +2159,7 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
   if (stats)
     for (int k = 1; k < n; ++k)
       if (scenes[k]->device != root->device) (scenes[k]->peer_ok ? stats->peer_copies : stats->staged_copies) += 1;
-  rc = timed_film(p, root->gather.p, root->rgb.p, PtBandMap{n, p.band_rows, pad_rows}, stats);
+  rc = timed_film(p, root->gather.p, root->rgb.p, PtBandMap{n, p.band_rows, pad_rows}, stats, root->film); /* the film runs on scenes[0]: its film governs */
   if (rc) return rc;
   rc = framebuffer_to_host(root, root->rgb.p, rgb_out, (size_t)p.width * p.height * 3);
   if (rc) return rc;
@@ -2012,6 +2179,13 @@ int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, do
   FinalSlabs fs;
   fs.n = std::min(n_slabs, kMaxFinalSlabs);
   for (int k = 0; k <= fs.n; ++k) fs.row[k] = (int)((long long)p.height * k / fs.n);
+  /* Invariant of the wait below: slab k's film reads s->film.pixel_radius rows beyond it, and "slab k + 1 has been summed" covers
+   * them only if slab k + 1 is at least that high (the slabs before k are behind earlier events of the same stream).  At most
+   * kMaxFinalSlabs slabs over at least kMinSlabImageRows rows gives >= 8 rows >= PTX_FILM_MAX_RADIUS (the static_assert beside the
+   * constants); this refuses, instead of misreading, a caller that breaks it some other way. */
+  for (int k = 0; k < fs.n; ++k)
+    if (fs.row[k + 1] - fs.row[k] < s->film.pixel_radius)
+      return fail(PTX_ERR_STATE, "row slab %d of %d has %d rows, fewer than the film's pixel_radius %d", k, fs.n, fs.row[k + 1] - fs.row[k], s->film.pixel_radius);
   int rc = ensure_copy_stream(s);
   for (int k = 0; k < fs.n && !rc; ++k) {
     rc = ensure_event(&s->ev_slab[k]);
@@ -2025,7 +2199,7 @@ int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, do
   if (rc) return rc;
   for (int k = 0; k < fs.n && fs.used; ++k) {
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, fs.done[std::min(k + 1, fs.n - 1)], 0));
-    rc = film_resolve(p.width, p.height, p.samples_per_pixel, s->raw.p, s->rgb.p, s->copy_stream, PtBandMap{1, 1, 0}, fs.row[k], fs.row[k + 1]);
+    rc = film_resolve(p.width, p.height, p.samples_per_pixel, s->raw.p, s->rgb.p, s->copy_stream, PtBandMap{1, 1, 0}, fs.row[k], fs.row[k + 1], s->film);
     if (rc) return rc;
     const size_t off = (size_t)fs.row[k] * p.width * 3, len = (size_t)(fs.row[k + 1] - fs.row[k]) * p.width * 3;
     if (len) HIP_TRY(hipMemcpyAsync(rgb_out + off, s->rgb.p + off, sizeof(double) * len, hipMemcpyDeviceToHost, s->copy_stream));
@@ -2068,7 +2242,7 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
   HIP_TRY(s->rgb.ensure(n));
   /* an image the caller has pinned takes the frame's tail as a pipeline (render_into_pinned) */
   const bool pinned = s->reg_ptr && rgb_out >= s->reg_ptr && rgb_out + n <= s->reg_ptr + s->reg_n;
-  const int n_slabs = (pinned && !p.count_work && !p.time_kernels && !progress && p.height >= 64 && p.max_bounces > 0) ? env_int("PTX_FINAL_SLABS", 4) : 1;
+  const int n_slabs = (pinned && !p.count_work && !p.time_kernels && !progress && p.height >= kMinSlabImageRows && p.max_bounces > 0) ? env_int("PTX_FINAL_SLABS", 4) : 1;
   bool copied = false;
   if (n_slabs > 1) rc = render_into_pinned(s, p, n_slabs, rgb_out, stats, &copied);
   else rc = render_raw(s, &p, s->raw.p, nullptr, stats, progress, user);
@@ -2077,7 +2251,7 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
     if (stats) stats->render_ms = wall_ms() - t0;
     return 0;
   }
-  rc = timed_film(p, s->raw.p, s->rgb.p, PtBandMap{1, 1, 0}, stats);
+  rc = timed_film(p, s->raw.p, s->rgb.p, PtBandMap{1, 1, 0}, stats, s->film);
   if (rc) return rc;
   rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n);
   if (rc) return rc;
@@ -2283,7 +2457,7 @@ struct ProgressivePolicy {
   PassRange first() const { return slice(0); }
   int queue_update(const PassRange& cur) {
     const int k = cur.first + cur.count;
-    const int rc = film_resolve(p.width, p.height, k, s->raw.p, s->rgb.p, nullptr);
+    const int rc = film_resolve(p.width, p.height, k, s->raw.p, s->rgb.p, nullptr, PtBandMap{1, 1, 0}, 0, -1, s->film);
     if (rc || !want_err()) return rc;
     return pixel_error_queue((long long)p.width * p.height, k, nullptr, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
   }
@@ -2363,6 +2537,22 @@ int32_t ptx_film_resolve_counts_device(int32_t device, int32_t width, int32_t he
   return rc;
 }
 
+int32_t ptx_film_resolve_counts_ex_device(int32_t device, int32_t width, int32_t height, const ptx_film_params* film, const double* d_raw,
+                                          const int32_t* d_passes, double* d_rgb_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the film runs on a HIP device only, no CPU fallback exists", device);
+  if (!d_raw || !d_passes || !d_rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || height <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, height);
+  const ptx_film_params f = film ? *film : kFilmDefault;
+  int rc = film_check(&f);
+  if (rc) return rc;
+  rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  rc = film_counts_queue(width, height, d_raw, d_passes, d_rgb_out, (hipStream_t)stream, f);
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  return rc;
+}
+
 int32_t ptx_pixel_error_counts_device(int32_t device, int32_t width, int32_t rows, const int32_t* d_passes, const double* d_raw,
                                       const double* d_sq, double* d_err_out, double* rel_err_out, void* stream) {
   if (device < 0) return fail(PTX_ERR_STATE, "device %d: the error kernels run on a HIP device only, no CPU fallback exists", device);
@@ -2408,7 +2598,7 @@ struct AdaptivePolicy {
   PassRange first() const { return round(0, std::min(ap.min_passes, p.samples_per_pixel), nullptr, 0); }
   int queue_update(const PassRange& cur) {
     const int W = p.width, H = p.height, b = cur.first + cur.count;
-    int rc = film_counts_queue(W, H, s->raw.p, s->passes.p, s->rgb.p, nullptr);
+    int rc = film_counts_queue(W, H, s->raw.p, s->passes.p, s->rgb.p, nullptr, s->film);
     if (rc) return rc;
     rc = pixel_error_queue(npix(), 0, s->passes.p, s->raw.p, s->sq.p, err_out ? s->err.p : nullptr, s->err_partials.p, nullptr);
     if (rc) return rc;
@@ -2664,7 +2854,7 @@ struct DenoisePolicy {
     if (!rc) rc = pixel_error_queue(npix(), k, nullptr, s->raw.p, s->sq.p, s->err.p, s->err_partials.p, nullptr);
     if (!rc) rc = denoise_queue(p.width, p.height, dp, k, nullptr, kf, s->raw.p, s->err.p, s->feat.p, s->den_guide.p, s->den_cv[0].p, s->den_cv[1].p,
                                 s->den_raw.p, nullptr);
-    if (!rc) rc = film_resolve(p.width, p.height, k, s->den_raw.p, s->rgb.p, nullptr);
+    if (!rc) rc = film_resolve(p.width, p.height, k, s->den_raw.p, s->rgb.p, nullptr, PtBandMap{1, 1, 0}, 0, -1, s->film);
     if (rc || !feat_out) return rc;
     const long long n = npix() * 8;
     hipLaunchKernelGGL(k_feature_means, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)s->feat.p, n, (double)kf, s->feat_mean.p);

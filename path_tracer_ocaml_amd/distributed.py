@@ -87,6 +87,15 @@ class BandGather:
             self.part = torch.zeros(shape, dtype=torch.float64, device=device)
         self._staged = None  # gloo rehearsal with device tensors: host staging buffers, made on first use
 
+    def film(self, samples_per_pixel, rgb, film=None, stream=None, wait=True):
+        """Rank 0: the film of ``gathered`` into the (H, W, 3) device tensor ``rgb``, read in place.  ``film`` None: the default
+        (5, 1) film (ptx_film_resolve_banded_device / _queue); otherwise (order, radius[, renormalise]) through
+        ptx_film_resolve_banded_ex_device."""
+        from . import film_resolve_banded_device
+        film_resolve_banded_device(self.gathered.device.index or 0, self.width, self.height, samples_per_pixel,
+                                   self.gathered.data_ptr(), self.world, self.band_rows, self.pad_rows, rgb.data_ptr(), stream=stream,
+                                   wait=wait, film=film)
+
     def gather(self):
         if self.world == 1:
             return self.gathered

@@ -49,6 +49,8 @@ struct Args {
   double lamp_half_side = 0.0, lamp_y = 0.0, lamp_emit = 0.0;
   int denoise = -1;                      // --denoise[=LEVELS]: a-trous levels (< 0: no denoiser)
   std::string aov;                       // --aov=PREFIX
+  bool have_filter = false;              // --filter=ORDER,RADIUS and / or --filter-renormalise
+  ptx_film_params film{5, 1, 0, 0};      // ptx_film_defaults
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -59,7 +61,7 @@ struct Args {
                "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
                "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
                "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
-               "          [--denoise[=LEVELS]] [--aov=PREFIX]\n",
+               "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -134,6 +136,17 @@ Args parse(int argc, char** argv) {
       if (v.empty()) usage(argv[0], "invalid value for --aov, expected a file name prefix");
       a.aov = v;
     }
+    else if (take_value(argc, argv, i, "filter", nullptr, &v)) {
+      char tail = 0;
+      int order = 0, radius = 0;
+      if (std::sscanf(v.c_str(), "%d,%d%c", &order, &radius, &tail) != 2) usage(argv[0], "invalid value for --filter, expected ORDER,RADIUS");
+      a.film.order = order;
+      a.film.pixel_radius = radius;
+      a.have_filter = true;
+    } else if (!std::strcmp(argv[i], "--filter-renormalise")) {
+      a.film.flags |= PTX_FILM_RENORMALISE;
+      a.have_filter = true;
+    }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
     else if (!std::strcmp(argv[i], "--no-simd")) a.no_simd = true;
@@ -159,6 +172,10 @@ Args parse(int argc, char** argv) {
   if (a.denoise >= 0 && a.gpus > 1) usage(argv[0], "--denoise renders on one GPU (--gpus=1)");
   if (a.denoise >= 0 && a.samples_per_pixel < 2) usage(argv[0], "--denoise requires --samples-per-pixel >= 2");
   if (a.denoise >= 0 && a.progressive == 1) usage(argv[0], "--denoise requires --progressive >= 2");
+  if (a.have_filter) { // the library's own check and message (host only: no device is touched)
+    double w[2 * PTX_FILM_MAX_RADIUS + 1];
+    if (ptx_film_weights(&a.film, w, nullptr) != 0) usage(argv[0], ptx_last_error());
+  }
   return a;
 }
 
@@ -258,6 +275,10 @@ int main(int argc, char** argv) {
   }
   if (a.lighting != PTX_LIGHTING_REFERENCE && ptx_scene_set_lighting(scene, a.lighting) != 0) {
     std::fprintf(stderr, "ptx_scene_set_lighting: %s\n", ptx_last_error());
+    return 1;
+  }
+  if (a.have_filter && ptx_scene_set_film(scene, &a.film) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_film: %s\n", ptx_last_error());
     return 1;
   }
   ptx_stats st;

@@ -54,9 +54,11 @@ class Integrator:
     with (camera, intersect, background) folded into the declarative ``scene``; ``image`` is the (H, W, 3) f64
     array ``render`` fills, like the reference's Bimage.  ``lighting`` stands for the reference's ``~diffuse_plus_light`` slot:
     "reference" (the default: ``Pdf.diffuse`` and the reference's emission formula), "path-order" or "sampled"
-    (Scene.set_lighting); None leaves a Scene that was handed in as it is."""
+    (Scene.set_lighting); None leaves a Scene that was handed in as it is.  ``film`` is the reconstruction filter the reference
+    hard-wires (``Binomial.create ~order:5 ~pixel_radius:1``): (order, radius) or (order, radius, renormalise) for Scene.set_film;
+    None leaves the scene's film as it is."""
 
-    def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None):
+    def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
@@ -64,14 +66,16 @@ class Integrator:
         self._scene = scene if isinstance(scene, Scene) else Scene(scene.ptr, device, keepalive=scene)
         if lighting is not None:
             self._scene.set_lighting(lighting)
+        if film is not None:
+            self._scene.set_film(*film)
         self.stats = None
         self.error = self.passes_done = None  # render_progressive
         self.passes = None  # render_adaptive
         self.features = None  # render_denoised
 
     @classmethod
-    def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None):
-        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting)
+    def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None):
+        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
