@@ -258,6 +258,14 @@ ptx_scene* ptx_scene_create(const ptx_scene_desc* desc, int32_t device);
 void ptx_scene_destroy(ptx_scene* scene);
 /* copies the build statistics (tree_* and build_ms fields) */
 int32_t ptx_scene_stats(const ptx_scene* scene, ptx_stats* out);
+/* Camera tile lists (PTX_TILE_LISTS): of the last render call (or slice) on this handle, out = {camera launches that
+ * scanned their tiles' sphere lists instead of walking the tree, tiles of the image's grid, tiles of it that keep the walk, the
+ * longest list, chunks of camera rays a guard of the scan sent back to the walk}.  All zero when that render scanned no lists: a
+ * counting render, a scene without lists, PTX_TILE_LISTS=0.  The last figure is not per render: it runs on from the handle's first
+ * render that scanned lists (a counting render sets it back to zero), so that no render has to touch it while another is queued.
+ * A handle keeps the lists of at most 8 image sizes (32 bytes per 8 x 8 tile, on the host and on every device it renders on) for
+ * its life; renders of a further size walk the tree.  Waits for the device.  ptx_stats and ptx_version() are unchanged. */
+int32_t ptx_tile_list_stats(const ptx_scene* scene, int64_t out[5]);
 
 /* The lighting mode of a scene: how a path sums emission and what a Diffuse scatter samples.  Sticky state of the handle (default
  * PTX_LIGHTING_REFERENCE), read by every entry point that shades -- ptx_render, _multi, _raw_device, _passes_device, _pixels_device,

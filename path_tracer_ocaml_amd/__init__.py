@@ -39,7 +39,7 @@ EXPORTS = (
     "ptx_scene_set_lighting", "ptx_scene_lighting",
     "ptx_render_features_device", "ptx_denoise_defaults", "ptx_denoise_device", "ptx_render_denoised",
     "ptx_film_defaults", "ptx_film_weights", "ptx_scene_set_film", "ptx_scene_film", "ptx_film_resolve_ex_device",
-    "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device",
+    "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device", "ptx_tile_list_stats",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -74,6 +74,8 @@ def lib():
     L.ptx_scene_create.argtypes = [C.POINTER(abi.SceneDesc), C.c_int32]
     L.ptx_scene_destroy.argtypes = [C.c_void_p]
     L.ptx_scene_stats.argtypes = [C.c_void_p, C.POINTER(abi.Stats)]
+    if hasattr(L, "ptx_tile_list_stats"):  # (a PTX_LIB built from an older tree, in an A/B, has none)
+        L.ptx_tile_list_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.ptx_render.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), dp, C.POINTER(abi.Stats), C.c_void_p, C.c_void_p]
     L.ptx_local_rows.argtypes = [C.POINTER(abi.RenderParams)]
     L.ptx_global_row.argtypes = [C.POINTER(abi.RenderParams), C.c_int32]
@@ -235,6 +237,12 @@ class Scene:
         st = abi.Stats()
         _check(lib().ptx_scene_stats(self._h, C.byref(st)))
         return stats_dict(st)
+
+    def tile_list_stats(self):
+        """ptx_tile_list_stats: the camera tile lists of the last render on this handle"""
+        out = abi.TileListStats()
+        _check(lib().ptx_tile_list_stats(self._h, out))
+        return dict(zip(abi.TILE_LIST_STATS, out))
 
     def tree(self):
         st = self.stats()

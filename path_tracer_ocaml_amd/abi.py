@@ -144,6 +144,10 @@ ROUND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C
                        C.c_void_p)
 
 
+# ptx_tile_list_stats: int64_t out[5]
+TileListStats = C.c_int64 * 5
+TILE_LIST_STATS = ("list_launches", "tiles", "walk_tiles", "longest_list", "fallback_chunks")
+
 PTX_LIGHT_POINT, PTX_LIGHT_SPOT = 0, 1
 
 

@@ -31,6 +31,7 @@
 #include "pt_lds_layout.h"
 #include "pt_scene.h"
 #include "pt_vec.h"
+#include "pt_tile_scan.h"
 
 #define PT_WAVE 64
 
@@ -128,6 +129,7 @@ struct PtCounters { /* device-side work counters (count_work) */
   unsigned long long solo;                      /* k_bounce launches that ran their batch's remaining bounces by themselves (PtSolo) */
   unsigned long long carry;                     /* k_bounce_carry launches */
   unsigned long long lane_walks;                /* camera launches of k_bounce / k_bounce_carry that walked one ray per lane (LANE_WALK) */
+  unsigned long long tile_fallbacks;            /* k_bounce_carry<..., TILE>: chunks of camera rays a guard of the list scan sent back to the walk (non-counting renders) */
 };
 
 /* ------------------------------------------------------------------ small device helpers */
@@ -3013,7 +3015,10 @@ static_assert(PT_POOL_BINS >= PT_N_SHADE_CAT, "k_bounce_carry: one output bin pe
  * assembly node loop the queued rays use -- instead of as a wave packet.  A ray's tests and their order are the same in both. */
 /* LOCT (Schedule::lds_oct; Simd_leaf, not counting, camera rays one per lane): the workgroup holds the per-octant LDS image (PtLdsOctTag)
  * in place of the stacks and the shared node image; pool_off is then pt_lds_oct_layout's. */
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false, bool LOCT = false>
+/* TILE (Schedule::tile_lists; LOCT camera launches): sc.tile_lists holds the image's camera tile lists (scene_host.h, PtTileRec); a chunk
+ * whose tile has a list scans it (pt_tile_scan.h) instead of walking the tree, unless the record says "walk", a live ray's octant is not
+ * the record's, or a guard of the scan fires -- then the chunk walks as without the flag. */
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LANE_WALK = false, bool LOCT = false, bool TILE = false>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_carry(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtHits hout, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
@@ -3024,6 +3029,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   __shared__ uint32_t lds_park_n, lds_park_lock;
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
   static_assert(!LOCT || (MODE == PT_MODE_SIMD && !COUNT && (!PRIMARY || LANE_WALK)), "the per-octant LDS image: Simd_leaf, not counting, no packet walk");
+  static_assert(!TILE || (LOCT && PRIMARY), "camera tile lists: the camera launch on the per-octant LDS image");
   typedef typename std::conditional<LOCT, PtLdsOctTag, uint16_t>::type StackT;
   StackT* stack = LOCT ? nullptr : (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
@@ -3129,14 +3135,45 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
          * a chunk is one 8 x 8 tile of one pass, mostly one category, so there are no pools -- each category present is shaded
          * in turn, its lanes live */
         live = i < n;
+        int tile_x = 0, tile_gy = 0; /* TILE: the lane's pixel column and GLOBAL row (lane 0: the tile's first) */
         if (live) {
           const PtPrimarySample ps = pt_primary_decode(g, i);
           live = ps.valid;
           if (live) d = pt_primary_dir(sc, g, ps, alpha);
+          tile_x = ps.x;
+          tile_gy = ps.gy;
         }
         if (COUNT && !DIAG_T && live) c_seg++;
         PtTraceResult r;
-        if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
+        bool scanned = false; /* wave-uniform */
+        if constexpr (TILE) {
+          /* lane 0 holds the tile's first pixel, inside the image whenever any lane is live; the record's index is checked against the grid */
+          const uint32_t gtx = (uint32_t)(g.width + 7) >> 3, gty = (uint32_t)(g.height + 7) >> 3;
+          const uint32_t tx = (uint32_t)__builtin_amdgcn_readfirstlane(tile_x) >> 3, ty = (uint32_t)__builtin_amdgcn_readfirstlane(tile_gy) >> 3;
+          if (__ballot(live) != 0ull && tx < gtx && ty < gty) {
+            /* the 32-byte record: lane k < 16 reads halfword k, the header and the slot numbers come out of it by readlane and stay scalar */
+            const uint16_t* rec = (const uint16_t*)sc.tile_lists + ((size_t)ty * gtx + tx) * 16u;
+            const int recv = (int)rec[lane & 15];
+            const uint32_t head = (uint32_t)__builtin_amdgcn_readlane(recv, 0);
+            const uint32_t n_list = head & 0xffu, oct = head >> 8;
+            const uint32_t dirs = (d.x >= 0.0 ? 1u : 0u) | (d.y >= 0.0 ? 2u : 0u) | (d.z >= 0.0 ? 4u : 0u); /* PtTraverser::begin */
+            if (n_list != PT_TILE_WALK && __ballot(live && dirs != oct) == 0ull) {
+              const PtTileHit th = pt_tile_scan<true>(sv.sph, [&](int k) { return (uint32_t)__builtin_amdgcn_readlane(recv, k + 1); },
+                                                      [](bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; }, (int)n_list, live, d, PT_MAX_FINITE);
+              if (__ballot(th.guard) == 0ull) {
+                scanned = true;
+                r.t = th.t;
+                r.slot = th.slot;
+                r.u = 0.0;
+                r.v = 0.0;
+              } else if (lane == 0) {
+                atomicAdd(&counters->tile_fallbacks, 1ull);
+              }
+            }
+          }
+        }
+        if (scanned) {
+        } else if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
           r = pt_trace_ray<MODE, COUNT, true, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
         else r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
         if (live) {

@@ -187,7 +187,11 @@ struct PtSceneDev {
    * and PT_LOCT_LEAF_WORDS(n_nodes) words of leaf table, or NULL.  The non-counting k_bounce_carry launches of a scene whose buffer
    * fits with it (pt_lds_layout.h, pt_lds_oct_layout; Schedule::lds_oct) copy it into LDS in place of the shared node image. */
   const uint32_t* lds_oct;
+  /* the camera tile lists of the image being rendered (scene_host.h, PtTileRec: 32 bytes per 8 x 8 tile of the global grid), or NULL.
+   * Set per launch (launch_bounce_carry); read only by k_bounce_carry's TILE instantiations, which are launched only with it. */
+  const uint32_t* tile_lists;
 };
+#define PT_TILE_WALK 0xffu /* a record's count byte: the tile's rays walk the tree */
 
 #define PT_LIGHTING_SAMPLED 2 /* = PTX_LIGHTING_SAMPLED */
 #define PT_LIGHT_DOUBLES 14

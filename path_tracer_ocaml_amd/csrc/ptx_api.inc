@@ -9,6 +9,7 @@
 #include <atomic>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <set>
 #include <tuple>
 #include <string>
@@ -264,6 +265,7 @@ struct Schedule {
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
   bool lds_oct = false;        /* non-counting k_bounce_carry launches hold the per-octant LDS image (PtSceneDev.lds_oct) and walk it */
+  bool tile_lists = false;     /* ... and their camera launch scans the image's camera tile lists where it has them (PTX_TILE_LISTS; tile_lists_for) */
   int top_in_lds = 0;          /* k_trace from HBM / L2 keeps the tree's top in LDS */
   int trace_threads = 0, bounce_threads = 0; /* workgroups of k_trace; of k_bounce and k_bounce_carry */
   size_t trace_lds = 0;        /* dynamic LDS of a k_trace launch */
@@ -271,6 +273,19 @@ struct Schedule {
   PtLdsOctLayout carry_oct{};  /* ... of a k_bounce_carry launch on the per-octant LDS image */
   bool in_lds() const { return placement == PT_PLACE_LDS; }
   bool fused_ok(size_t cap_entries) const { return fused_possible && cap_entries < kPoolMaxEntries; } /* ... with queues of this capacity */
+};
+
+/* The camera tile lists of a scene (scene_host.h, scene_tile_lists), one grid per image size, built at the first render of that size and
+ * kept: the host copies are shared by a scene and its replicas, every device gets its own upload. */
+struct TileListCache {
+  std::mutex mu;
+  std::vector<std::shared_ptr<const PtTileGrid>> grids;
+};
+constexpr size_t kMaxTileGrids = 8;
+const unsigned long long kZero64 = 0ull;
+struct TileListsDev {
+  std::shared_ptr<const PtTileGrid> grid;
+  DevBuf<uint32_t> buf;
 };
 
 struct ptx_scene {
@@ -306,6 +321,12 @@ struct ptx_scene {
   DevBuf<PtShadeRec> slot_shade;
   DevBuf<uint16_t> node_skip;
   DevBuf<uint32_t> node_skip32, nodes32, nodes32o, lds_oct, top_nodes, node_skip32_top;
+  std::shared_ptr<TileListCache> tile_cache;             /* shared with the replicas, like `host` */
+  std::vector<std::unique_ptr<TileListsDev>> tile_dev;   /* this device's uploads: they live as long as the handle (queued frames keep reading them) */
+  const TileListsDev* tile_cur = nullptr;                /* the lists of the render in progress, or none (render_raw) */
+  const TileListsDev* tile_last = nullptr;               /* ptx_tile_list_stats: the lists the last render scanned, and how many launches did */
+  int64_t tile_launches = 0;
+  bool tile_fallbacks_zeroed = false;                    /* PtCounters::tile_fallbacks was zeroed once, before the handle's first list launch */
   bool lds_oct_launched = false; /* the render in progress has launched a kernel on the per-octant LDS image (ptx_stats.lds_oct_launches) */
   int n_prims = 0;
   int tree_depth = 0, tree_leaves = 0;
@@ -549,6 +570,9 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * runs with the camera rays one per lane and the whole buffer of such a launch fits with it.  Counting launches keep the shared image */
   c.carry_oct = pt_lds_oct_layout(lds_in(s, PT_LDS_K_BOUNCE_CARRY, c.bounce_threads / 64));
   c.lds_oct = s->dev.lds_oct != nullptr && simd && c.carry_ok && c.lane_walk && c.carry_oct.fits;
+  /* camera tile lists (PTX_TILE_LISTS, read at scene creation like PTX_LDS_OCT): wherever the camera launch runs on the per-octant LDS image
+   * and the scene can have lists at all (Simd_leaf spheres, no floor) */
+  c.tile_lists = c.lds_oct && s->host && s->host->tile_lists != 0 && scene_tile_lists_possible(*s->host);
   return c;
 }
 void reschedule(ptx_scene* s, int sets) {
@@ -597,7 +621,8 @@ ShadePoolKernel shade_pool_kernel(Shading shading, bool primary) {
 /* k_bounce_carry: 24 = MODE 2 x COUNT 2 x EMIT 2 x (PRIMARY, LANE_WALK) in {00, 10, 11}: only camera rays walk one per lane (a
  * lane walk asked of a queued launch is the plain kernel), and a lit scene never takes this kernel (Schedule::carry_ok);
  * + 4 on the per-octant LDS image (LOCT; Simd_leaf, not counting): EMIT 2 x {queued, camera with lane walk} */
-CarryKernel carry_kernel_oct(bool emit, bool primary) {
+CarryKernel carry_kernel_oct(bool emit, bool primary, bool tile) {
+  if (primary && tile) return emit ? k_bounce_carry<PT_MODE_SIMD, false, true, true, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, false, true, true, true, true>;
   if (emit) return primary ? k_bounce_carry<PT_MODE_SIMD, false, true, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, true, false, false, true>;
   return primary ? k_bounce_carry<PT_MODE_SIMD, false, false, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, false, false, false, true>;
 }
@@ -700,13 +725,21 @@ void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const P
   const Schedule& sc = s->sched;
   const int stack_depth = std::max(1, s->tree_depth + 1);
   const bool oct = sc.lds_oct && !count;
-  const CarryKernel kern = oct ? carry_kernel_oct(s->dev.has_emit != 0, pl.on) : carry_kernel(s->dev.mode, count, s->dev.has_emit != 0, pl.on, sc.lane_walk);
+  /* the camera launch scans tile lists where the render has them (render_raw: s->tile_cur) */
+  const bool tile = oct && pl.on && sc.tile_lists && s->tile_cur != nullptr;
+  PtSceneDev dev = s->dev;
+  dev.tile_lists = tile ? s->tile_cur->buf.p : nullptr;
+  if (tile) {
+    s->tile_launches++;
+    s->tile_last = s->tile_cur;
+  }
+  const CarryKernel kern = oct ? carry_kernel_oct(s->dev.has_emit != 0, pl.on, tile) : carry_kernel(s->dev.mode, count, s->dev.has_emit != 0, pl.on, sc.lane_walk);
   prepare_kernel(s, (const void*)kern, "k_bounce_carry", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
   const int threads = sc.bounce_threads;
   int grid = strided_grid(s, n_upper, threads, 1); /* one workgroup (one scene image) per CU */
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
   if (oct) s->lds_oct_launched = true;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, st, s->dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, st, dev, q, h, out, hout, c, s->alpha.p, bounce, last, pl.g, pl.n,
                      stack_depth, (uint32_t)(oct ? sc.carry_oct.pool_off : sc.carry.pool_off), s->counters.p, s->bounce_fence_wg);
 }
 
@@ -1122,12 +1155,44 @@ int wait_progress(const BatchPlan& b, const std::vector<hipEvent_t>& batch_done,
   return 0;
 }
 
+/* The camera tile lists of a width x height image on this scene's device: the host grid out of the cache shared with the replicas (built
+ * the first time any of them renders that size), uploaded once per device.  nullptr: no lists (the launch walks the tree). */
+const TileListsDev* tile_lists_for(ptx_scene* s, int width, int height) {
+  for (const auto& t : s->tile_dev)
+    if (t->grid->width == width && t->grid->height == height) return t.get();
+  /* at most kMaxTileGrids image sizes per handle: nothing is evicted (a queued frame may still be reading an upload), a further size walks */
+  if (!s->tile_cache || s->tile_dev.size() >= kMaxTileGrids) return nullptr;
+  std::shared_ptr<const PtTileGrid> grid;
+  {
+    std::lock_guard<std::mutex> lock(s->tile_cache->mu);
+    for (const auto& g : s->tile_cache->grids)
+      if (g->width == width && g->height == height) grid = g;
+    if (!grid) {
+      if (s->tile_cache->grids.size() >= kMaxTileGrids) return nullptr;
+      grid = std::make_shared<const PtTileGrid>(scene_tile_lists(*s->host, width, height));
+      s->tile_cache->grids.push_back(grid);
+    }
+  }
+  if (grid->rec.empty()) return nullptr;
+  auto t = std::make_unique<TileListsDev>();
+  t->grid = grid;
+  const size_t words = grid->rec.size() * (sizeof(PtTileRec) / sizeof(uint32_t));
+  if (t->buf.ensure(words) != hipSuccess || hipMemcpy(t->buf.p, grid->rec.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  s->tile_dev.push_back(std::move(t));
+  return s->tile_dev.back().get();
+}
+
 int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStream_t st, ptx_stats* stats,
                ptx_progress_fn progress, void* user, FinalSlabs* slabs = nullptr, const PassRange& range = PassRange()) {
   RenderBusy busy(s);
   s->event_next = 0; /* an earlier call that failed half-way may have left these behind */
   s->timed.clear();
   s->lds_oct_launched = false;
+  s->tile_cur = s->tile_last = nullptr;
+  s->tile_launches = 0;
   if (stats) {
     std::memset(stats, 0, sizeof *stats);
     fill_tree_stats(s, stats);
@@ -1150,6 +1215,17 @@ int render_raw(ptx_scene* s, const ptx_render_params* p, double* d_raw, hipStrea
     if (range.d_sq) HIP_TRY(hipMemsetAsync(range.d_sq, 0, sizeof(double) * (size_t)b.npix * 3, st));
   }
   if (count) HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(PtCounters), st));
+  /* camera tile lists: non-counting renders of whole images, or of bands the global tile grid can be indexed with (a band = whole tile
+   * rows: pt_global_row(g, 8 ty) >> 3); a list render (adaptive rounds) has no camera launch */
+  if (s->sched.tile_lists && !count && !b.list && p->max_bounces >= 2 && (p->band_step <= 1 || (p->band_rows > 0 ? p->band_rows : 32) % 8 == 0)) {
+    s->tile_cur = tile_lists_for(s, p->width, p->height);
+    /* the fallback counter runs on from the handle's first list render (or its last counting render, whose memset above covers it):
+     * zeroing it per render would race with the lanes' camera launches and with a frame still queued */
+    if (s->tile_cur && !s->tile_fallbacks_zeroed) {
+      HIP_TRY(hipMemcpy(&s->counters.p->tile_fallbacks, &kZero64, sizeof kZero64, hipMemcpyHostToDevice));
+      s->tile_fallbacks_zeroed = true;
+    }
+  }
   Lanes l;
   rc = fork_lanes(s, p, b, st, progress != nullptr, &l);
   if (rc) return rc;
@@ -1621,6 +1697,7 @@ static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
   auto ha = std::make_shared<PtHostArrays>();
   if (const int rc = scene_set_tree(d, std::move(tree), ha.get(), &msg)) return fail(rc, "%s", msg.c_str());
   s->host = ha;
+  s->tile_cache = std::make_shared<TileListCache>();
   int rc = 0;
   if (s->device < 0) {
     s->dev.n_slots = ha->dev.n_slots;
@@ -1814,6 +1891,23 @@ int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
   return 0;
 }
 
+int32_t ptx_tile_list_stats(const ptx_scene* s, int64_t out[5]) {
+  if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
+  for (int k = 0; k < 5; ++k) out[k] = 0;
+  if (s->device < 0 || !s->tile_last) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize()); /* (a frame queued with PTX_RENDER_ASYNC may still be counting) */
+  unsigned long long fb = 0;
+  HIP_TRY(hipMemcpy(&fb, &s->counters.p->tile_fallbacks, sizeof fb, hipMemcpyDeviceToHost));
+  const PtTileGrid& g = *s->tile_last->grid;
+  out[0] = s->tile_launches;
+  out[1] = (int64_t)g.rec.size();
+  out[2] = g.n_walk;
+  out[3] = g.longest;
+  out[4] = (int64_t)fb;
+  return 0;
+}
+
 int32_t ptx_render_raw_device(ptx_scene* s, const ptx_render_params* p, double* d_raw_out, void* stream, ptx_stats* stats) {
   if (!s || !d_raw_out) return fail(PTX_ERR_ARG, "NULL argument");
   int rc = check_render_args(s, p, nullptr);
@@ -1919,6 +2013,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
   s->host = src->host;
+  s->tile_cache = src->tile_cache;
   s->n_prims = src->n_prims;
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;

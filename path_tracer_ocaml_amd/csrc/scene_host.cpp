@@ -444,6 +444,7 @@ SceneOptions scene_options_from_env() {
   o.tri_frame = env_int("PTX_TRI_FRAME", 1);
   o.oct_image = env_int("PTX_OCT_IMAGE", 1);
   o.lds_oct = env_int("PTX_LDS_OCT", 1);
+  o.tile_lists = env_int("PTX_TILE_LISTS", 1);
   o.top_nodes = std::max(0, std::min(1023, env_int("PTX_TOP_NODES", 512)));
   if (std::getenv("PTX_BIN_KEY")) { /* any other value: by octant */
     const int k = env_int("PTX_BIN_KEY", 0);
@@ -540,6 +541,7 @@ void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, cons
   top_image(opt, h);
   skip16_copy(h);
   bin_key(boxes, opt, h);
+  h->tile_lists = opt.tile_lists != 0;
 }
 
 /* n = normalize(cross(b - a, c - a)) (pt_tri_normal: the host's pt_hypot chain, like tri_frame) and
@@ -561,4 +563,128 @@ std::vector<double> light_table_build(const PtHostArrays& h) {
     o[PT_LIGHT_CUM] = cum;
   }
   return table;
+}
+
+/* ---- camera tile lists (scene_host.h) ---- */
+bool scene_tile_lists_possible(const PtHostArrays& h) {
+  return h.dev.mode == PT_MODE_SIMD && !h.dev.has_triangles && h.dev.n_floor == 0 && !h.nodes.empty() && h.dev.n_slots > 0 &&
+         h.dev.n_slots <= 0x10000 && h.sph.size() >= (size_t)h.dev.n_slots * 4;
+}
+
+/* What tests/test_tile_lists.py breaks on purpose, in the build of tests/c/tile_lists_driver.cpp alone (host/Makefile defines
+ * PT_TILE_TEST_MUTANTS for it): 1 = no inflation, 2 = lists in slot order.  The library's build has neither the word nor the tests. */
+#ifdef PT_TILE_TEST_MUTANTS
+int pt_tile_test_mutant = 0;
+#define PT_TILE_MUTANT(bit) ((pt_tile_test_mutant & (bit)) != 0)
+#else
+#define PT_TILE_MUTANT(bit) false
+#endif
+
+namespace {
+/* one side of the image's tile grid: per tile column (or row) the bounds [lo, hi] of the un-normalised direction component
+ * ll + v c over the tile's pixels (pt_primary_dir), and the real slots whose inflated sphere is not wholly outside both planes */
+struct TileAxis {
+  std::vector<double> lo, hi;
+  std::vector<std::vector<uint16_t>> pass; /* ascending slot numbers */
+};
+TileAxis tile_axis(const PtHostArrays& h, int n_tiles, int extent, double ll, double v, bool flip, int comp) {
+  TileAxis ax;
+  ax.lo.resize((size_t)n_tiles);
+  ax.hi.resize((size_t)n_tiles);
+  ax.pass.resize((size_t)n_tiles);
+  const double scale = 1.0 / (double)extent;
+  for (int t = 0; t < n_tiles; ++t) {
+    const double p0 = (double)(8 * t) * scale, p1 = (double)std::min(8 * t + 8, extent) * scale;
+    const double a = ll + (v * (flip ? 1.0 - p0 : p0)), b = ll + (v * (flip ? 1.0 - p1 : p1));
+    const double lo = std::fmin(a, b), hi = std::fmax(a, b);
+    ax.lo[(size_t)t] = (a != a || b != b) ? pt_nan() : lo;
+    ax.hi[(size_t)t] = (a != a || b != b) ? pt_nan() : hi;
+    const double nlo = std::sqrt(1.0 + (lo * lo)), nhi = std::sqrt(1.0 + (hi * hi));
+    for (int sl = 0; sl < h.dev.n_slots; ++sl) {
+      if (h.slot_prim[(size_t)sl] < 0) continue; /* NaN padding */
+      const double* s = &h.sph[(size_t)sl * 4];
+      const double r = std::fabs(s[3]);
+      const double len = std::sqrt(((s[0] * s[0]) + (s[1] * s[1])) + (s[2] * s[2]));
+      const double e = PT_TILE_MUTANT(1) ? r : r + (PT_TILE_INFLATE * (len + r));
+      const double dl = s[comp] + (lo * s[2]), dh = s[comp] + (hi * s[2]);
+      if (dl < -(e * nlo) || dh > e * nhi) continue;
+      ax.pass[(size_t)t].push_back((uint16_t)sl);
+    }
+  }
+  return ax;
+}
+}  // namespace
+
+PtTileGrid scene_tile_lists(const PtHostArrays& h, int width, int height) {
+  PtTileGrid g;
+  if (!scene_tile_lists_possible(h) || width < 1 || height < 1) return g;
+  g.width = width;
+  g.height = height;
+  g.tiles_x = (width + 7) / 8;
+  g.tiles_y = (height + 7) / 8;
+  const int n_slots = h.dev.n_slots;
+  const std::vector<PtNode>& nd = h.nodes;
+  /* rank[o][slot]: the position of the slot in the order in which octant o's near-first descent (shape_tree.ml:201,209) meets the leaves */
+  std::vector<uint32_t> rank[4]; /* camera rays have d.z < 0: octants 0 .. 3 */
+  for (uint32_t o = 0; o < 4; ++o) {
+    rank[o].assign((size_t)n_slots, 0u);
+    uint32_t next = 0;
+    std::vector<uint32_t> todo{0u};
+    while (!todo.empty()) {
+      const uint32_t k = todo.back();
+      todo.pop_back();
+      if (is_leaf(nd[k])) {
+        for (uint32_t j = 0; j < (nd[k].b & 0x3fffffffu) && nd[k].a + j < (uint32_t)n_slots; ++j) rank[o][nd[k].a + j] = next++;
+        continue;
+      }
+      const uint32_t axis = nd[k].b >> 30, lhs = nd[k].a, rhs = nd[k].b & 0x3fffffffu;
+      const bool lhs_first = (o >> axis) & 1u;
+      todo.push_back(lhs_first ? rhs : lhs);
+      todo.push_back(lhs_first ? lhs : rhs);
+    }
+  }
+  /* a sphere the scan's guards are not sized for sends its tiles to the walk: non-finite, or |c| > PT_TILE_MAX_CR r */
+  std::vector<uint8_t> odd((size_t)n_slots, 0);
+  for (int sl = 0; sl < n_slots; ++sl) {
+    if (h.slot_prim[(size_t)sl] < 0) continue;
+    const double* s = &h.sph[(size_t)sl * 4];
+    const double len = std::sqrt(((s[0] * s[0]) + (s[1] * s[1])) + (s[2] * s[2]));
+    odd[(size_t)sl] = !(std::isfinite(len) && std::isfinite(s[3]) && len <= PT_TILE_MAX_CR * std::fabs(s[3]));
+  }
+  const TileAxis cols = tile_axis(h, g.tiles_x, width, h.dev.cam_llx, h.dev.cam_vx, false, 0);
+  const TileAxis rows = tile_axis(h, g.tiles_y, height, h.dev.cam_lly, h.dev.cam_vy, true, 1);
+  g.rec.assign((size_t)g.tiles_x * g.tiles_y, PtTileRec{});
+  std::vector<uint8_t> in_row((size_t)n_slots);
+  std::vector<uint16_t> list;
+  for (int ty = 0; ty < g.tiles_y; ++ty) {
+    std::fill(in_row.begin(), in_row.end(), (uint8_t)0);
+    for (uint16_t sl : rows.pass[(size_t)ty]) in_row[sl] = 1;
+    const double ylo = rows.lo[(size_t)ty], yhi = rows.hi[(size_t)ty];
+    for (int tx = 0; tx < g.tiles_x; ++tx) {
+      PtTileRec& r = g.rec[(size_t)ty * g.tiles_x + tx];
+      const double xlo = cols.lo[(size_t)tx], xhi = cols.hi[(size_t)tx];
+      /* one octant for the whole tile: no component's bounds are non-finite, straddle zero or touch it */
+      bool walk = !(std::isfinite(xlo) && std::isfinite(xhi) && std::isfinite(ylo) && std::isfinite(yhi)) || (xlo <= 0.0 && xhi >= 0.0) ||
+                  (ylo <= 0.0 && yhi >= 0.0);
+      const uint32_t o = (xlo > 0.0 ? 1u : 0u) | (ylo > 0.0 ? 2u : 0u);
+      list.clear();
+      for (uint16_t sl : cols.pass[(size_t)tx])
+        if (in_row[sl]) {
+          list.push_back(sl);
+          walk = walk || odd[sl];
+        }
+      if (walk || list.size() > (size_t)PT_TILE_MAX_SLOTS) {
+        r.count = PT_TILE_WALK;
+        g.n_walk++;
+        continue;
+      }
+      if (!PT_TILE_MUTANT(2))
+        std::sort(list.begin(), list.end(), [&](uint16_t a, uint16_t b) { return rank[o][a] < rank[o][b]; });
+      r.count = (uint8_t)list.size();
+      r.octant = (uint8_t)o;
+      for (size_t k = 0; k < list.size(); ++k) r.slot[k] = list[k];
+      g.longest = std::max(g.longest, (int)list.size());
+    }
+  }
+  return g;
 }

@@ -37,6 +37,7 @@ struct PtHostArrays {
    * n_emissive_tris counts them all (ptx_scene_set_lighting makes the light table of them) */
   std::vector<double> emissive_tris;
   int n_emissive_tris = 0;
+  int tile_lists = 0; /* SceneOptions::tile_lists, kept for the schedule: camera launches may scan per-tile sphere lists (scene_tile_lists) */
   PtSceneDev dev{}; /* the scalar fields; device pointers are filled per upload */
 };
 
@@ -45,6 +46,7 @@ struct SceneOptions {
   int tri_frame = 1;   /* PTX_TRI_FRAME: 0 = no tri_frame table */
   int oct_image = 1;   /* PTX_OCT_IMAGE: 0 = keep the shared image + skip table */
   int lds_oct = 1;     /* PTX_LDS_OCT: 0 = no per-octant LDS image: every launch keeps the shared one */
+  int tile_lists = 1;  /* PTX_TILE_LISTS: 0 = camera rays always walk the tree (no per-tile sphere lists) */
   int top_nodes = 512; /* PTX_TOP_NODES: size of the breadth-first top image, clamped to 0 .. 1023 */
   int bin_key = -1;    /* PTX_BIN_KEY: -1 = by scene, 0 octant, 1 elevation, 2 reaches-the-root-box */
 };
@@ -70,5 +72,30 @@ void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, cons
 
 /* The light table of PTX_LIGHTING_SAMPLED: per emissive tree triangle PT_LIGHT_DOUBLES doubles {a, b, c, n, A, cum} */
 std::vector<double> light_table_build(const PtHostArrays& h);
+
+/* ---- camera tile lists: which spheres a camera ray through an 8 x 8 pixel tile can meet ----
+ * One 32-byte record per tile of the GLOBAL tile grid of a width x height image, row-major, tiles_x = ceil(width / 8):
+ *   byte 0      the number of slots listed, 0 .. PT_TILE_MAX_SLOTS, or PT_TILE_WALK (pt_scene.h): the tile's rays walk the tree
+ *   byte 1      the direction octant (PtTraverser::dirs) every ray of the tile has
+ *   bytes 2..31 up to 15 leaf-order slot numbers (uint16), in the order in which a near-first descent of that octant meets their
+ *               leaves, slot order inside a leaf -- the relative order in which the walk tests them
+ * A slot is listed unless its sphere, its radius inflated by PT_TILE_INFLATE (|c| + r), lies wholly outside one of the four side
+ * planes of the pyramid the tile's camera rays span from the origin (rows and columns are tested on their own: separable). */
+#define PT_TILE_MAX_SLOTS 15
+#define PT_TILE_INFLATE 0x1p-40
+#define PT_TILE_MAX_CR 0x1p18 /* a listed sphere with |c| > PT_TILE_MAX_CR r makes its tiles walk: the scan's guard on the discriminant assumes |c| / r <= 2^19 */
+struct PtTileRec {
+  uint8_t count, octant;
+  uint16_t slot[PT_TILE_MAX_SLOTS];
+};
+static_assert(sizeof(PtTileRec) == 32, "one 32-byte record per tile");
+struct PtTileGrid {
+  int width = 0, height = 0, tiles_x = 0, tiles_y = 0;
+  int n_walk = 0, longest = 0; /* tiles marked PT_TILE_WALK; the longest list */
+  std::vector<PtTileRec> rec;  /* tiles_x * tiles_y */
+};
+/* the scene can have tile lists at all: Simd_leaf spheres only, no floor, slot numbers within 16 bits */
+bool scene_tile_lists_possible(const PtHostArrays& h);
+PtTileGrid scene_tile_lists(const PtHostArrays& h, int width, int height);
 
 #endif /* SCENE_HOST_H */
