@@ -191,6 +191,40 @@ let film_weights ~order ~pixel_radius =
   film_weights_into order pixel_radius out;
   Array.init n (fun i -> Bigarray.Array1.get out i)
 
+(* Image textures and a latitude-longitude environment (ptx_scene_set_texture_image / ptx_scene_set_environment; the rule is in
+   include/ptx.h).  [texels] holds width * height * 3 linear binary64 values, texel (ix, iy) at 3 * (iy * width + ix), row 0 = v 0; the
+   library copies them.  set_texture_image: from then on every material that points at entry [index] of the scene's texture table (the
+   order in which [flatten] interned the textures) evaluates the image; ~bilinear interpolates the four nearest texels, ~repeat_u /
+   ~repeat_v wrap around instead of clamping.  set_environment: a ray that leaves the scene returns the image's colour in its
+   direction; [rotation] is the row-major 3 x 3 matrix from camera space to the environment's space (default: identity).  Sticky:
+   every later render of the scene reads them.  Failure for a refused image, or while a render runs on the scene. *)
+type texels = (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+
+external set_texture_image_raw : scene -> int -> int * int * int -> texels -> unit = "ptx_ml_set_texture_image_stub"
+external set_environment_raw : scene -> int * int * int -> texels -> texels -> unit = "ptx_ml_set_environment_stub"
+
+let no_texels () = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0
+
+let set_texture_image ?(bilinear = false) ?(repeat_u = false) ?(repeat_v = false) scene ~index ~width ~height texels =
+  let flags = (if bilinear then 1 else 0) lor (if repeat_u then 2 else 0) lor if repeat_v then 4 else 0 in
+  if width < 1 || height < 1 then invalid_arg "Ptx.set_texture_image: width and height must be >= 1";
+  set_texture_image_raw scene index (width, height, flags) texels
+
+let clear_texture_image scene ~index = set_texture_image_raw scene index (0, 0, 0) (no_texels ())
+
+let set_environment ?(bilinear = true) ?rotation scene ~width ~height texels =
+  if width < 1 || height < 1 then invalid_arg "Ptx.set_environment: width and height must be >= 1";
+  let rot =
+    match rotation with
+    | None -> no_texels ()
+    | Some m ->
+      if Array.length m <> 9 then invalid_arg "Ptx.set_environment: rotation must hold 9 floats (row-major 3 x 3)";
+      Bigarray.Array1.of_array Bigarray.float64 Bigarray.c_layout m
+  in
+  set_environment_raw scene (width, height, if bilinear then 1 else 0) texels rot
+
+let clear_environment scene = set_environment_raw scene (0, 0, 0) (no_texels ()) (no_texels ())
+
 external render_flat
   :  scene
   -> int (* width *)

@@ -275,4 +275,39 @@ static __attribute__((unused)) int32_t ptx_ml_film_weights(int32_t order, int32_
   return 0;
 }
 
+/* Ptx.set_texture_image / Ptx.clear_texture_image: width * height * 3 doubles of `rgb` (n_rgb of them are there) onto entry `index`
+ * of the scene's texture table (ptx_scene_set_texture_image); width = height = 0 restores the descriptor's texture.  -4 when an
+ * accepted size needs more texels than the Bigarray holds (the library's own refusals keep their codes: it checks the size before it
+ * reads a texel). */
+static __attribute__((unused)) int32_t ptx_ml_set_texture_image(ptx_scene* s, int32_t index, int32_t width, int32_t height, int32_t flags,
+                                                                const double* rgb, int64_t n_rgb) {
+  if (width == 0 && height == 0) return ptx_scene_set_texture_image(s, index, NULL);
+  ptx_image img;
+  memset(&img, 0, sizeof img);
+  img.width = width;
+  img.height = height;
+  img.flags = flags;
+  img.rgb = rgb;
+  const int sized = width >= 1 && width <= PTX_IMAGE_MAX_SIZE && height >= 1 && height <= PTX_IMAGE_MAX_SIZE;
+  if (sized && (!rgb || n_rgb < (int64_t)width * height * 3)) return -4;
+  return ptx_scene_set_texture_image(s, index, &img);
+}
+
+/* Ptx.set_environment / Ptx.clear_environment (ptx_scene_set_environment): as above; rot = 9 doubles row-major, or n_rot = 0 for
+ * the identity; -5 for any other length */
+static __attribute__((unused)) int32_t ptx_ml_set_environment(ptx_scene* s, int32_t width, int32_t height, int32_t flags, const double* rgb,
+                                                              int64_t n_rgb, const double* rot, int64_t n_rot) {
+  if (width == 0 && height == 0) return ptx_scene_set_environment(s, NULL, NULL);
+  if (n_rot != 0 && n_rot != 9) return -5;
+  ptx_image img;
+  memset(&img, 0, sizeof img);
+  img.width = width;
+  img.height = height;
+  img.flags = flags;
+  img.rgb = rgb;
+  const int sized = width >= 1 && width <= PTX_IMAGE_MAX_SIZE && height >= 1 && height <= PTX_IMAGE_MAX_SIZE;
+  if (sized && (!rgb || n_rgb < (int64_t)width * height * 3)) return -4;
+  return ptx_scene_set_environment(s, &img, n_rot == 9 ? rot : NULL);
+}
+
 #endif /* PTX_ML_MARSHAL_H */

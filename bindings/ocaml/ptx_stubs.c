@@ -286,6 +286,48 @@ CAMLprim value ptx_ml_set_film_stub(value handle, value order, value pixel_radiu
   CAMLreturn(Val_unit);
 }
 
+/* external set_texture_image_raw : scene -> int -> int * int * int -> texels -> unit = "ptx_ml_set_texture_image_stub"
+ * (ptx_scene_set_texture_image: the entry, (width, height, flags), width * height * 3 doubles; (0, 0, _) restores the descriptor's
+ * texture).  What a running render shades with: like set_lighting it takes the scene exclusively and raises Failure while a render
+ * runs on another thread or domain, and Failure with the library's message for a refused image. */
+CAMLprim value ptx_ml_set_texture_image_stub(value handle, value index, value dims, value texels) {
+  CAMLparam4(handle, index, dims, texels);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_texture_image: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_texture_image: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s)
+    rc = ptx_ml_set_texture_image(s, (int32_t)Long_val(index), (int32_t)Long_val(Field(dims, 0)), (int32_t)Long_val(Field(dims, 1)),
+                                  (int32_t)Long_val(Field(dims, 2)), (const double*)Caml_ba_data_val(texels),
+                                  (int64_t)Caml_ba_array_val(texels)->dim[0]);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_texture_image: scene already destroyed");
+  if (rc == -4) caml_invalid_argument("Ptx.set_texture_image: the texels hold fewer than width * height * 3 doubles");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external set_environment_raw : scene -> int * int * int -> texels -> texels -> unit = "ptx_ml_set_environment_stub"
+ * (ptx_scene_set_environment: (width, height, flags), the texels, the 9 doubles of the rotation or an empty Bigarray for the
+ * identity; (0, 0, _) restores the descriptor's background) */
+CAMLprim value ptx_ml_set_environment_stub(value handle, value dims, value texels, value rotation) {
+  CAMLparam4(handle, dims, texels, rotation);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_environment: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_environment: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s)
+    rc = ptx_ml_set_environment(s, (int32_t)Long_val(Field(dims, 0)), (int32_t)Long_val(Field(dims, 1)), (int32_t)Long_val(Field(dims, 2)),
+                                (const double*)Caml_ba_data_val(texels), (int64_t)Caml_ba_array_val(texels)->dim[0],
+                                (const double*)Caml_ba_data_val(rotation), (int64_t)Caml_ba_array_val(rotation)->dim[0]);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_environment: scene already destroyed");
+  if (rc == -4) caml_invalid_argument("Ptx.set_environment: the texels hold fewer than width * height * 3 doubles");
+  if (rc == -5) caml_invalid_argument("Ptx.set_environment: the rotation must hold 9 doubles (row-major 3 x 3)");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
 /* external film_int : scene -> int * int * int = "ptx_ml_film_stub" (ptx_scene_film: order, pixel_radius, flags) */
 CAMLprim value ptx_ml_film_stub(value handle) {
   CAMLparam1(handle);

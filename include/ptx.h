@@ -594,6 +594,69 @@ int32_t ptx_film_resolve_banded_ex_device(int32_t device, int32_t width, int32_t
 int32_t ptx_film_resolve_counts_ex_device(int32_t device, int32_t width, int32_t height, const ptx_film_params* film,
                                           const double* d_raw, const int32_t* d_passes, double* d_rgb_out, void* stream);
 
+/* ---- image textures and a lat-long environment map ----
+ * Texture.t stops at one colour and a two-colour checker (texture.ml:16-31), Scene.background at a closure; these two sticky
+ * setters put a picture on a texture entry and light the scene with a sky image.  Only entry points and one struct are added: no
+ * existing struct changes, the ABI version stays 6, and a scene without an image launches the kernels it launched before.
+ *
+ * An image is width x height texels of three binary64 values, linear (no colour-space conversion): texel (ix, iy) is
+ * rgb[3 * (iy * width + ix) ..], row 0 is v = 0.  1 <= width, height <= PTX_IMAGE_MAX_SIZE, every value finite.  The library
+ * copies the texels (on the device: one 32-byte record {r, g, b, -} per texel, bit for bit).
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction), for texture coordinates (u, v), W = width, H = height:
+ *   wrap of an integer index i on an axis of n texels:  repeat ((i % n) + n) % n;  clamp min(max(i, 0), n - 1)
+ *     (PTX_IMAGE_REPEAT_U / _V choose repeat for that axis, otherwise it clamps)
+ *   p = u * (double)W, q = v * (double)H;  a product that is NaN or not below 2^62 in magnitude is replaced by 0.0
+ *   nearest:   ix = wrap((long long)p), iy = wrap((long long)q): truncation toward zero, the checker's Float.to_int;
+ *              the colour is texel (ix, iy)
+ *   bilinear:  x = p - 0.5;  x0 = floor(x);  fx = x - x0;  ix0 = wrap((long long)x0), ix1 = wrap((long long)x0 + 1)
+ *              y = q - 0.5;  y0 = floor(y);  fy = y - y0;  iy0, iy1 likewise;  then per channel, c(i, j) = texel (i, j):
+ *              top = c(ix0, iy0) * (1 - fx) + c(ix1, iy0) * fx
+ *              bot = c(ix0, iy1) * (1 - fx) + c(ix1, iy1) * fx
+ *              result = top * (1 - fy) + bot * fy
+ * The environment, for a ray direction d and the caller's row-major 3x3 matrix R (camera space -> environment space; geometry
+ * arrives in camera space):
+ *   e = normalize(d) as the sky gradient does;  m_k = (R[3k] * e.x + R[3k+1] * e.y) + R[3k+2] * e.z, k = 0, 1, 2
+ *   u = (pi + atan2(-m.z, m.x)) * (1 / (2 pi));  v = acos(-min(max(m.y, -1), 1)) * (1 / pi)
+ * -- Sphere.tex_coord (sphere.ml:25-33) with the functions of pt_math.h: the environment is the texture of an infinitely large
+ * sphere seen from inside -- then the image rule with repeat in u and clamp in v.  A miss returns that colour where it returned
+ * Scene.background before.
+ *
+ * Both setters are sticky state of the handle, read by everything that shades through the scene: the ptx_render family
+ * (progressive, adaptive, denoised, n_gpus > 1), ptx_trace_samples, ptx_debug_first_scatter, ptx_render_features_device (the albedo
+ * is the texel; a miss's albedo the environment colour), ptx_ppm_render's shading, all three lighting modes.  The replicas a scene
+ * owns follow it, and ptx_scene_replicate copies both.  A host-only scene accepts a valid call, as ptx_scene_set_lighting does.
+ * Every argument is checked before any device call.  PTX_ERR_STATE while a render runs on the scene; a setter waits for the
+ * device (frames queued with PTX_RENDER_ASYNC have finished when it returns).
+ * A scene with an image or an environment takes the walk-first kernels' image instantiations: no shade-first
+ * order, no per-octant LDS image, no camera tile lists.
+ * Out of scope: importance-sampling the environment (PTX_LIGHTING_SAMPLED keeps sampling emissive triangles only; the environment
+ * is found by scattering), mip maps and anisotropic filtering, 8-bit or binary32 texels, image decoders other than the hosts' PFM
+ * reader, image-driven emission, roughness or normals. */
+#define PTX_IMAGE_BILINEAR 1
+#define PTX_IMAGE_REPEAT_U 2
+#define PTX_IMAGE_REPEAT_V 4
+#define PTX_IMAGE_MAX_SIZE 16384
+typedef struct ptx_image { /* 24 bytes */
+  int32_t width, height;
+  int32_t flags;    /* PTX_IMAGE_*; unknown bits are PTX_ERR_ARG */
+  int32_t reserved; /* 0 */
+  const double* rgb; /* width * height * 3; NULL in what the getters return */
+} ptx_image;
+/* From now on every material that points at entry texture_index of the scene's texture table evaluates the image (an entry declared
+ * solid included); NULL restores the descriptor's texture. */
+int32_t ptx_scene_set_texture_image(ptx_scene* scene, int32_t texture_index, const ptx_image* image);
+/* NULL image restores the descriptor's background; NULL R is the identity; of the flags only PTX_IMAGE_BILINEAR is accepted. */
+int32_t ptx_scene_set_environment(ptx_scene* scene, const ptx_image* image, const double R[9]);
+/* Dimensions and flags of what is set, rgb NULL; width 0 = none.  R_out (nullable) receives the matrix (the identity when none). */
+int32_t ptx_scene_texture_image(const ptx_scene* scene, int32_t texture_index, ptx_image* out);
+int32_t ptx_scene_environment(const ptx_scene* scene, ptx_image* out, double R_out[9]);
+/* Diagnostics, in the family of ptx_math_eval: the device's own evaluation functions on explicit inputs.  uv: n x 2, dirs: n x 3,
+ * rgb_out: n x 3, HOST.  ptx_texture_eval on an entry without an image evaluates its solid or checker texture;
+ * ptx_environment_eval without an environment evaluates the descriptor's background. */
+int32_t ptx_texture_eval(ptx_scene* scene, int32_t texture_index, int64_t n, const double* uv, double* rgb_out);
+int32_t ptx_environment_eval(ptx_scene* scene, int64_t n, const double* dirs, double* rgb_out);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

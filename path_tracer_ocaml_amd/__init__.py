@@ -40,6 +40,8 @@ EXPORTS = (
     "ptx_render_features_device", "ptx_denoise_defaults", "ptx_denoise_device", "ptx_render_denoised",
     "ptx_film_defaults", "ptx_film_weights", "ptx_scene_set_film", "ptx_scene_film", "ptx_film_resolve_ex_device",
     "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device", "ptx_tile_list_stats",
+    "ptx_scene_set_texture_image", "ptx_scene_set_environment", "ptx_scene_texture_image", "ptx_scene_environment",
+    "ptx_texture_eval", "ptx_environment_eval",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -133,6 +135,14 @@ def lib():
                                                     C.c_int32, C.c_void_p, C.c_void_p]
     L.ptx_film_resolve_counts_ex_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, fp, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
+    if hasattr(L, "ptx_scene_set_texture_image"):  # (a PTX_LIB built from an older tree, in an A/B, has none)
+        imp = C.POINTER(abi.Image)
+        L.ptx_scene_set_texture_image.argtypes = [C.c_void_p, C.c_int32, imp]
+        L.ptx_scene_set_environment.argtypes = [C.c_void_p, imp, dp]
+        L.ptx_scene_texture_image.argtypes = [C.c_void_p, C.c_int32, imp]
+        L.ptx_scene_environment.argtypes = [C.c_void_p, imp, dp]
+        L.ptx_texture_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp]
+        L.ptx_environment_eval.argtypes = [C.c_void_p, C.c_int64, dp, dp]
     _LIB = L
     return L
 
@@ -232,6 +242,64 @@ class Scene:
         f = abi.FilmParams()
         _check(lib().ptx_scene_film(self._h, C.byref(f)))
         return f.order, f.pixel_radius, bool(f.flags & abi.PTX_FILM_RENORMALISE)
+
+    def set_texture_image(self, index, image, bilinear=False, repeat=(False, False)):
+        """ptx_scene_set_texture_image: from now on every material that points at entry `index` of the scene's texture table
+        evaluates `image`, an (H, W, 3) array of linear binary64 texels (row 0 is v = 0; the library copies it); None restores the
+        descriptor's texture.  bilinear: interpolate the four nearest texels instead of taking the one (u, v) falls into;
+        repeat = (in u, in v): wrap around instead of clamping to the edge.  Sticky; every later render of this scene reads it."""
+        if image is None:
+            _check(lib().ptx_scene_set_texture_image(self._h, int(index), None))
+            return
+        flags = ((abi.PTX_IMAGE_BILINEAR if bilinear else 0) | (abi.PTX_IMAGE_REPEAT_U if repeat[0] else 0)
+                 | (abi.PTX_IMAGE_REPEAT_V if repeat[1] else 0))
+        img, keep = abi.image(image, flags)
+        _check(lib().ptx_scene_set_texture_image(self._h, int(index), C.byref(img)))
+        del keep
+
+    def texture_image(self, index):
+        """ptx_scene_texture_image: (width, height, flags) of the image on entry `index`, or None"""
+        out = abi.Image()
+        _check(lib().ptx_scene_texture_image(self._h, int(index), C.byref(out)))
+        return (out.width, out.height, out.flags) if out.width else None
+
+    def set_environment(self, image, rotation=None, bilinear=True):
+        """ptx_scene_set_environment: a ray that leaves the scene returns the colour `image` (an (H, W, 3) array, latitude-longitude:
+        u runs once around the y axis, v from -y (row 0) to +y) holds in its direction; rotation: the row-major 3 x 3 matrix from
+        camera space to the environment's space (None = identity).  None restores the descriptor's background.  Sticky."""
+        if image is None:
+            _check(lib().ptx_scene_set_environment(self._h, None, None))
+            return
+        img, keep = abi.image(image, abi.PTX_IMAGE_BILINEAR if bilinear else 0)
+        rot = None
+        if rotation is not None:
+            rot = np.ascontiguousarray(rotation, dtype=np.float64).reshape(-1)
+            if rot.size != 9:
+                raise ValueError("rotation must be a 3 x 3 matrix")
+        _check(lib().ptx_scene_set_environment(self._h, C.byref(img), _dp(rot) if rot is not None else None))
+        del keep
+
+    def environment(self):
+        """ptx_scene_environment: ((width, height, flags), the 3 x 3 rotation), or None"""
+        out = abi.Image()
+        rot = np.zeros(9)
+        _check(lib().ptx_scene_environment(self._h, C.byref(out), _dp(rot)))
+        return ((out.width, out.height, out.flags), rot.reshape(3, 3)) if out.width else None
+
+    def texture_eval(self, index, uv):
+        """ptx_texture_eval: entry `index` of the texture table (its image, or its solid / checker texture) evaluated on the device
+        at the (n, 2) texture coordinates uv -> (n, 3)"""
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros((len(uv), 3))
+        _check(lib().ptx_texture_eval(self._h, int(index), len(uv), _dp(uv), _dp(out)))
+        return out
+
+    def environment_eval(self, directions):
+        """ptx_environment_eval: what a ray leaving the scene in each of the (n, 3) directions returns -> (n, 3)"""
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros((len(d), 3))
+        _check(lib().ptx_environment_eval(self._h, len(d), _dp(d), _dp(out)))
+        return out
 
     def stats(self):
         st = abi.Stats()

@@ -139,6 +139,24 @@ def film_params(film=None, renormalise=None):
     return f
 
 
+PTX_IMAGE_BILINEAR, PTX_IMAGE_REPEAT_U, PTX_IMAGE_REPEAT_V = 1, 2, 4
+PTX_IMAGE_MAX_SIZE = 16384
+
+
+class Image(C.Structure):  # ptx_image
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("rgb", c_double_p)]
+
+
+def image(array, flags=0):
+    """(abi.Image, the array it points into) from an (H, W, 3) array of linear binary64 texels, row 0 = v 0; the caller keeps the
+    second value alive for the duration of the call (the library copies the texels)."""
+    import numpy as np
+    a = np.ascontiguousarray(array, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("an image must be an array of shape (height, width, 3)")
+    return Image(a.shape[1], a.shape[0], int(flags), 0, a.ctypes.data_as(c_double_p)), a
+
+
 # ptx_round_fn: (user, round, passes_done, active_next, samples, rel_err, rgb, err, passes) -> non-zero stops the render
 ROUND_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                        C.c_void_p)

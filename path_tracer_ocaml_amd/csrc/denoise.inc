@@ -12,13 +12,14 @@ struct PtFeature {
   V3 albedo, normal;
   double depth, hit;
 };
+template <bool IMG>
 __device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, const PtGenParams& g, const PtPrimarySample& ps,
                                                        const PtHits& hits, const double* __restrict__ alpha, uint32_t i) {
   PtFeature f;
   const V3 o = v3(0.0, 0.0, 0.0), d = pt_primary_dir(sc, g, ps, alpha);
   const int slot = hits.slot[i];
   if (slot < 0) {
-    f.albedo = pt_background(sc, d);
+    f.albedo = pt_background<IMG>(sc, d);
     f.normal = v3(0.0, 0.0, 0.0);
     f.depth = 0.0;
     f.hit = 0.0;
@@ -48,7 +49,7 @@ __device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, con
   const PtMatRegs m = pt_mat_load<PT_CAT_NONE, false>(sc.slot_shade + slot);
   const bool is_tri = geom.kind != PT_SLOT_SPHERE;
   const PtSurface sf = pt_surface_hit<PT_CAT_NONE>(sc, o, d, slot, t_hit, is_tri ? bu : 0.0, is_tri ? bv : 0.0, m, geom);
-  f.albedo = m.kind == 2 ? v3(1.0, 1.0, 1.0) : pt_texture_eval(m, sf.tu, sf.tv);
+  f.albedo = m.kind == 2 ? v3(1.0, 1.0, 1.0) : pt_texture_eval<IMG>(m, sf.tu, sf.tv);
   f.normal = sf.normal;
   f.depth = t_hit;
   f.hit = 1.0;
@@ -58,6 +59,7 @@ __device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, con
 /* feat[pixel] += the records of the batch's n_pass passes, in pass order.  One thread per entry j of ONE pass of the virtual primary
  * queue (8x8 tiles, ragged edges padded: neighbouring lanes read neighbouring hit records); it owns its pixel, so the sums need no
  * atomics and a pixel's additions run in pass order.  The 64-byte record goes in and out as four 16-byte accesses. */
+template <bool IMG = false> /* IMG: scenes with an image texture or an environment (pt_shade_entry) */
 __global__ __launch_bounds__(256) void k_features(PtSceneDev sc, PtGenParams g, PtHits hits, const double* __restrict__ alpha,
                                                   double* __restrict__ feat) {
   const uint32_t per_pass = (uint32_t)(g.tiles_x * g.tiles_y) * 64u;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void k_features(PtSceneDev sc, PtGenParams g, 
   for (int k = 0; k < g.n_pass; ++k) {
     const uint32_t i = (uint32_t)k * per_pass + j;
     const PtPrimarySample ps = pt_primary_decode(g, i);
-    const PtFeature f = pt_feature_sample(sc, g, ps, hits, alpha, i);
+    const PtFeature f = pt_feature_sample<IMG>(sc, g, ps, hits, alpha, i);
     r0.x = r0.x + f.albedo.x;
     r0.y = r0.y + f.albedo.y;
     r1.x = r1.x + f.albedo.z;

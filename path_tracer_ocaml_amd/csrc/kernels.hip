@@ -1881,11 +1881,13 @@ struct PtMatRegs {
   double index;
   V3 even, odd, emit;
 };
-template <int CAT, bool EMIT>
+/* IMG (scenes with an image or an environment only): a slot of the textured-Lambertian category may carry an image (PT_TEX_IMAGE),
+ * so its texture kind is read, not known */
+template <int CAT, bool EMIT, bool IMG = false>
 __device__ __forceinline__ PtMatRegs pt_mat_load(const PtShadeRec* m) {
   PtMatRegs r;
   r.kind = (CAT == PT_CAT_LAMBERT_SOLID || CAT == PT_CAT_LAMBERT_CHECKER) ? 0 : (CAT == PT_CAT_METAL ? 1 : (CAT == PT_CAT_DIELECTRIC ? 2 : m->kind));
-  r.tex_kind = CAT == PT_CAT_LAMBERT_SOLID ? 0 : (CAT == PT_CAT_LAMBERT_CHECKER ? 1 : (CAT == PT_CAT_DIELECTRIC ? 0 : m->tex_kind));
+  r.tex_kind = CAT == PT_CAT_LAMBERT_SOLID ? 0 : ((CAT == PT_CAT_LAMBERT_CHECKER && !IMG) ? 1 : (CAT == PT_CAT_DIELECTRIC ? 0 : m->tex_kind));
   const bool tex = CAT != PT_CAT_DIELECTRIC;
   const bool checker = CAT != PT_CAT_DIELECTRIC && CAT != PT_CAT_LAMBERT_SOLID;
   r.tex_w = checker ? m->tex_w : 1;
@@ -1897,8 +1899,74 @@ __device__ __forceinline__ PtMatRegs pt_mat_load(const PtShadeRec* m) {
   return r;
 }
 
-/* Texture.eval (texture.ml:16-31) */
+/* ------------------------------------------------------------------ image textures (include/ptx.h states the rule; every expression
+ * below keeps its grouping, and the build has -ffp-contract=off) */
+/* p = u * W of the rule: a product that is NaN or reaches 2^62 in magnitude counts as 0 */
+__device__ __forceinline__ double pt_image_scale(double u, int n) {
+  const double p = u * (double)n;
+  return pt_fabs(p) < 0x1p62 ? p : 0.0;
+}
+/* wrap of the rule for an index given as the integer-valued double i (|i| <= 2^62), 1 <= n <= 16384, without a 64-bit division (the
+ * GPU has no integer divide: a 64-bit one is ~100 instructions and a dozen registers, in kernels held to 128 VGPRs).
+ *   clamp   min(max(i, 0), n - 1), taken on the double: exact.
+ *   repeat  ((i % n) + n) % n with C's truncating % is m for i >= 0 and (n - m) % n for i < 0, m = |i| mod n.  |i| < 2^32 -- every
+ *           coordinate a scene produces -- is one 32-bit remainder; beyond it (a rare, cold branch) |i| = hi 2^32 + lo and
+ *           m = ((hi mod n) (2^32 mod n) + lo mod n) mod n, every product below 2^28. */
+__device__ __forceinline__ int pt_image_wrap(double i, int n, bool repeat) {
+  if (!repeat) {
+    const double last = (double)(n - 1);
+    return (int)(i < 0.0 ? 0.0 : (i > last ? last : i));
+  }
+  const double a = pt_fabs(i);
+  const uint32_t un = (uint32_t)n;
+  uint32_t m;
+  if (__builtin_expect(a < 0x1p32, 1)) {
+    m = (uint32_t)a % un;
+  } else {
+    const unsigned long long big = (unsigned long long)a;
+    const uint32_t hi = (uint32_t)(big >> 32), lo = (uint32_t)big;
+    const uint32_t two32 = (0xffffffffu % un + 1u) % un; /* 2^32 mod n */
+    m = ((hi % un) * two32 + lo % un) % un;
+  }
+  return (int)((i < 0.0 && m != 0u) ? un - m : m);
+}
+/* wrap(i + 1) from i0 = wrap(i): repeat steps round the axis; clamp stays at 0 for i < 0 (then i + 1 <= 0) and stops at n - 1 */
+__device__ __forceinline__ int pt_image_next(double i, int i0, int n, bool repeat) {
+  if (repeat) return i0 + 1 == n ? 0 : i0 + 1;
+  return i < 0.0 ? 0 : (i0 + 1 > n - 1 ? n - 1 : i0 + 1);
+}
+/* texels: 32-byte records {r, g, b, -}.  All loads of a lookup are issued together, before the first use: two 16-byte loads for
+ * nearest, eight for bilinear -- the texel address depends on the tex coords, so this is the shade step's second dependent round
+ * trip, and its last. */
+__device__ __forceinline__ V3 pt_image_eval(const double* __restrict__ texels, int w, int h, int flags, double u, double v) {
+  const bool rep_u = (flags & PT_IMAGE_REPEAT_U) != 0, rep_v = (flags & PT_IMAGE_REPEAT_V) != 0;
+  const double p = pt_image_scale(u, w), q = pt_image_scale(v, h);
+  const double2* t = (const double2*)texels;
+  if (!(flags & PT_IMAGE_BILINEAR)) {
+    const int ix = pt_image_wrap(__builtin_trunc(p), w, rep_u), iy = pt_image_wrap(__builtin_trunc(q), h, rep_v); /* (long long)p */
+    const double2* c = t + 2u * (uint32_t)(iy * w + ix);
+    const double2 c0 = c[0], c1 = c[1];
+    return v3(c0.x, c0.y, c1.x);
+  }
+  const double x = p - 0.5, y = q - 0.5;
+  const double x0 = __builtin_floor(x), y0 = __builtin_floor(y);
+  const double fx = x - x0, fy = y - y0;
+  const int ix0 = pt_image_wrap(x0, w, rep_u), iy0 = pt_image_wrap(y0, h, rep_v);
+  const int ix1 = pt_image_next(x0, ix0, w, rep_u), iy1 = pt_image_next(y0, iy0, h, rep_v);
+  const uint32_t row0 = (uint32_t)(iy0 * w), row1 = (uint32_t)(iy1 * w);
+  const double2 *p00 = t + 2u * (row0 + (uint32_t)ix0), *p10 = t + 2u * (row0 + (uint32_t)ix1);
+  const double2 *p01 = t + 2u * (row1 + (uint32_t)ix0), *p11 = t + 2u * (row1 + (uint32_t)ix1);
+  const double2 a0 = p00[0], a1 = p00[1], b0 = p10[0], b1 = p10[1], c0 = p01[0], c1 = p01[1], d0 = p11[0], d1 = p11[1];
+  const V3 c00 = v3(a0.x, a0.y, a1.x), c10 = v3(b0.x, b0.y, b1.x), c01 = v3(c0.x, c0.y, c1.x), c11 = v3(d0.x, d0.y, d1.x);
+  const V3 top = v3_lerp(fx, c00, c10), bot = v3_lerp(fx, c01, c11);
+  return v3_lerp(fy, top, bot);
+}
+
+/* Texture.eval (texture.ml:16-31); IMG: and the image arm (PtShadeRec: the texels' address and the flags in the bits of `even`) */
+template <bool IMG = false>
 __device__ __forceinline__ V3 pt_texture_eval(const PtMatRegs& t, double u, double v) {
+  if (IMG && t.tex_kind == PT_TEX_IMAGE)
+    return pt_image_eval((const double*)(uintptr_t)__double_as_longlong(t.even.x), t.tex_w, t.tex_h, (int)__double_as_longlong(t.even.y), u, v);
   if (t.tex_kind == 0) return t.even;
   const double width = (double)(t.tex_w - 1), height = (double)(t.tex_h - 1);
   const double xp = u * width, yp = v * height;
@@ -1914,8 +1982,24 @@ __device__ __forceinline__ double pt_schlick(double cos_theta, double index) {
   return r0 + ((1.0 - r0) * pt_pow5(1.0 - cos_theta));
 }
 
-/* Scene.background (shirley_spheres/bin/main.ml:104-110) */
+/* the environment (include/ptx.h): Sphere.tex_coord of the rotated unit direction, then the image rule, repeat in u, clamp in v */
+__device__ __forceinline__ V3 pt_environment(const PtSceneDev& sc, V3 dir) {
+  const double pi = 3.14159265358979323846;
+  const V3 e = v3_normalize(dir);
+  const double* R = sc.env_rot;
+  const double mx = (R[0] * e.x + R[1] * e.y) + R[2] * e.z;
+  const double my = (R[3] * e.x + R[4] * e.y) + R[5] * e.z;
+  const double mz = (R[6] * e.x + R[7] * e.y) + R[8] * e.z;
+  const double one_over_pi = 1.0 / pi, one_over_two_pi = 1.0 / (2.0 * pi);
+  const double cy = my < -1.0 ? -1.0 : (my > 1.0 ? 1.0 : my); /* min(max(m.y, -1), 1); a NaN stays (acos gives NaN, which counts as v = 0) */
+  const double u = (pi + pt_atan2(-mz, mx)) * one_over_two_pi;
+  const double v = pt_acos(-cy) * one_over_pi;
+  return pt_image_eval(sc.env, sc.env_w, sc.env_h, (sc.env_flags & PT_IMAGE_BILINEAR) | PT_IMAGE_REPEAT_U, u, v);
+}
+/* Scene.background (shirley_spheres/bin/main.ml:104-110); IMG: and the environment arm */
+template <bool IMG = false>
 __device__ __forceinline__ V3 pt_background(const PtSceneDev& sc, V3 dir) {
+  if (IMG && sc.bg_kind == PT_BG_ENV) return pt_environment(sc, dir);
   if (sc.bg_kind == 0) return v3(0.0, 0.0, 0.0);
   const V3 d = v3_normalize(dir);
   const double t = 0.5 * (v3_dot(d, v3(0.0, 1.0, 0.0)) + 1.0);
@@ -2019,7 +2103,7 @@ struct PtScatter {
   int kind;
   V3 attenuation, wo;
 };
-template <int CAT = PT_CAT_NONE>
+template <int CAT = PT_CAT_NONE, bool IMG = false>
 __device__ __forceinline__ PtScatter pt_material_scatter(const PtSceneDev& sc, const PtSurface& sf, const PtMatRegs& m, double su) {
   const V3 omega_i = sf.omega_i;
   PtScatter r;
@@ -2029,14 +2113,14 @@ __device__ __forceinline__ PtScatter pt_material_scatter(const PtSceneDev& sc, c
                     : (CAT == PT_CAT_METAL ? 1 : (CAT == PT_CAT_DIELECTRIC ? 2 : m.kind));
   if (mkind == 0) {
     r.kind = 2;
-    r.attenuation = pt_texture_eval(m, sf.tu, sf.tv);
+    r.attenuation = pt_texture_eval<IMG>(m, sf.tu, sf.tv);
   } else if (mkind == 1) {
     const V3 omega_r = v3(-omega_i.x, -omega_i.y, omega_i.z); /* Shader_space.reflect */
     if (omega_r.z <= 0.0) {
       r.kind = 0;
     } else {
       r.kind = 1;
-      const V3 a = pt_texture_eval(m, sf.tu, sf.tv);
+      const V3 a = pt_texture_eval<IMG>(m, sf.tu, sf.tv);
       const double sp5 = pt_pow5(1.0 - omega_i.z);
       const V3 c = v3_scale(v3_sub(v3(1.0, 1.0, 1.0), a), sp5);
       r.attenuation = v3_add(a, c);
@@ -2145,8 +2229,10 @@ __device__ __forceinline__ double pt_light_pd(const PtSceneDev& sc, V3 p, V3 w) 
  * entry i = a camera sample).  CAT = the entry's shading category if the kernel is specialised for one.
  * LIT (emissive scenes in lighting modes 1 and 2 only; mode 0 never launches it): emission is summed in path order,
  * emit0' = fma(attn0, emit, emit0), and in mode 2 (a wave-uniform branch) a Diffuse scatter samples and divides by
- * diffuse_plus_light = 1/2 cosine + 1/2 emissive triangles. */
-template <bool EMIT, bool PRIMARY, int CAT, bool LIT = false>
+ * diffuse_plus_light = 1/2 cosine + 1/2 emissive triangles.
+ * IMG (scenes with an image texture or an environment only; no other scene launches it): pt_texture_eval's image arm and
+ * pt_background's environment arm. */
+template <bool EMIT, bool PRIMARY, int CAT, bool LIT = false, bool IMG = false>
 __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQueue& q, const PtHits& hits, const PtContrib& contrib,
                                                const double* __restrict__ alpha, int bounce, int last_bounce,
                                                const PtGenParams& g, uint32_t i, bool live, PtShadeOut& so,
@@ -2178,7 +2264,7 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
       bool done = true;
       if (CAT == PT_CAT_MISS || (CAT == PT_CAT_NONE && slot < 0)) {
         /* None -> add_mul emit0 attn0 (background ray), integrator.ml:36 */
-        result = v3_fma(attn0, pt_background(sc, d), emit0);
+        result = v3_fma(attn0, pt_background<IMG>(sc, d), emit0);
       } else {
         /* the rest of the segment's inputs, requested in the same round as the queue records above (PtMatRegs): the hit
          * distance, the slot's shading record, and its geometry (or, with triangles in the scene, its kind) */
@@ -2207,7 +2293,7 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
           geom.cy = s0.y;
           geom.cz = s1.x;
         }
-        const PtMatRegs m = pt_mat_load<CAT, EMIT>(sc.slot_shade + slot);
+        const PtMatRegs m = pt_mat_load<CAT, EMIT, IMG>(sc.slot_shade + slot);
         const bool is_tri = geom.kind != PT_SLOT_SPHERE;
         const PtSurface sf = pt_surface_hit<CAT>(sc, o, d, slot, t_hit, is_tri ? bu : 0.0, is_tri ? bv : 0.0, m, geom);
         const V3 point = sf.point;
@@ -2216,7 +2302,7 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
         /* take_2d (), integrator.ml:20-28,39: dims 2+2k, 3+2k for the k-th hit */
         const double su = pt_lds_get(alpha, offset, 2 + 2 * bounce);
         const double sv = pt_lds_get(alpha, offset, 3 + 2 * bounce);
-        const PtScatter scat = pt_material_scatter<CAT>(sc, sf, m, su);
+        const PtScatter scat = pt_material_scatter<CAT, IMG>(sc, sf, m, su);
         const int sc_kind = scat.kind;
         V3 attenuation = scat.attenuation;
         V3 wo = scat.wo;
@@ -2284,6 +2370,13 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
 #ifndef PT_SHADE_WAVES
 #define PT_SHADE_WAVES 4
 #endif
+/* The IMG instantiations of k_bounce and k_shade_pool (scenes with an image texture or an environment) get 3 waves per SIMD instead of
+ * 4, i.e. 168 VGPRs instead of 128: at 128 the image arm's live values -- the texel address, the two fractions, and for bilinear 32
+ * registers of texels in flight -- went to scratch in 64 of the 71 kernels; at 168 none of them spills a register (DESIGN.md section
+ * 4).  Their workgroups are sized to match: 768 threads of k_bounce (12 waves: 3 per SIMD), 256 of k_shade_pool (3 per CU). */
+#define PT_IMG_WAVES 3
+#define PT_BOUNCE_THREADS_IMG 768
+#define PT_POOL_THREADS_IMG 256
 #ifndef PT_SHADE_TIMING
 #define PT_SHADE_TIMING 0
 #endif
@@ -2405,8 +2498,8 @@ __device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue
   if (so.keep) pt_q_store<EMIT>(out, dst, so.n_o, so.n_d, so.n_attn, so.n_emit, so.id, so.offset);
 }
 
-template <bool EMIT, bool PRIMARY, bool LIT = false>
-__global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
+template <bool EMIT, bool PRIMARY, bool LIT = false, bool IMG = false>
+__global__ __launch_bounds__(IMG ? PT_POOL_THREADS_IMG : PT_POOL_THREADS, IMG ? PT_IMG_WAVES : PT_SHADE_WAVES) void k_shade_pool(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                 const double* __restrict__ alpha, int bounce, int last_bounce,
                                                 PtGenParams g, uint32_t n_primary, uint32_t* work) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_pool_raw[]; /* [waves][PT_N_SHADE_CAT][128] x (queue index, hit slot) */
@@ -2485,7 +2578,7 @@ __global__ __launch_bounds__(PT_POOL_THREADS, PT_SHADE_WAVES) void k_shade_pool(
       i = e.x;                                                                                                             \
       sl = (int)e.y;                                                                                                       \
     }                                                                                                                      \
-    pt_shade_entry<EMIT, PRIMARY, K, LIT>(sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
+    pt_shade_entry<EMIT, PRIMARY, K, LIT, IMG>(sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
   } break;
       switch (c) {
         PT_POOL_STEP(PT_CAT_MISS)
@@ -2623,8 +2716,8 @@ struct PtSolo {
 #define PT_SOLO_ONE_BIN_CHUNKS 2 /* a workgroup whose input of a solo turn is at most this many chunks per wave puts all survivors into one bin */
 #endif
 /* (PT_SOLO_MAX_BLOCKS: pt_lds_layout.h) */
-template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false, bool LANE_WALK = false /* (PRIMARY && LDS_SCENE: k_bounce_carry) */>
-__global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
+template <int MODE, bool COUNT, bool EMIT, bool PRIMARY, bool LDS_SCENE = true, bool SOLO_T = false, bool LIT = false, bool LANE_WALK = false /* (PRIMARY && LDS_SCENE: k_bounce_carry) */, bool IMG = false>
+__global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IMG ? PT_IMG_WAVES : PT_BOUNCE_WAVES) void k_bounce(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                                  const double* __restrict__ alpha, int bounce, int last_bounce, PtGenParams g,
                                                                  uint32_t n_primary, int stack_depth, uint32_t pool_off,
                                                                  PtCounters* counters, int fence_wg, PtSolo solo) {
@@ -2758,7 +2851,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce(P
       sl = (int)pool_s[K][start + lane];                                                                                   \
       if (LDS_SCENE && sl == 0xffff) sl = -1; /* (misses are filed with slot -1) */                                        \
     }                                                                                                                      \
-    pt_shade_entry<EMIT, PRIMARY, K, LIT>(LDS_SCENE ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
+    pt_shade_entry<EMIT, PRIMARY, K, LIT, IMG>(LDS_SCENE ? scl : sc, q, hits, contrib, alpha, bounce, last_bounce, g, i, live, so, ##__VA_ARGS__); \
   } break;
       switch (c) {
         PT_POOL_STEP(PT_CAT_MISS)
@@ -3819,6 +3912,25 @@ __global__ void k_math_eval(int fn, long long n, const double* __restrict__ a, c
     default: r = pt_nan(); break;
   }
   out[i] = r;
+}
+
+/* ptx_texture_eval / ptx_environment_eval: the shade step's own evaluation functions (the IMG arms) on explicit inputs */
+__global__ void k_texture_eval(PtShadeRec rec, long long n, const double* __restrict__ uv, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PtMatRegs m = pt_mat_load<PT_CAT_NONE, false, true>(&rec);
+  const V3 c = pt_texture_eval<true>(m, uv[2 * i], uv[2 * i + 1]);
+  out[3 * i] = c.x;
+  out[3 * i + 1] = c.y;
+  out[3 * i + 2] = c.z;
+}
+__global__ void k_environment_eval(PtSceneDev sc, long long n, const double* __restrict__ dirs, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 c = pt_background<true>(sc, v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+  out[3 * i] = c.x;
+  out[3 * i + 1] = c.y;
+  out[3 * i + 2] = c.z;
 }
 
 /* copies explicit rays into a queue (ptx_intersect_rays) */

@@ -54,7 +54,7 @@ __device__ __forceinline__ void pt_light_random_ray(const PtLightDev& l, double 
   *d = dir;
 }
 
-template <int MODE>
+template <int MODE, bool IMG = false> /* IMG: scenes with an image texture (pt_shade_entry) */
 __global__ __launch_bounds__(256) void k_ppm_photons(PtSceneDev sc, int stack_depth, const PtLightDev* __restrict__ lights,
                                                      int n_lights, const int* __restrict__ light_first /* n_lights+1 */,
                                                      int base_offset, const double* __restrict__ alpha, int max_bounces,
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_ppm_photons(PtSceneDev sc, int stack_de
       if (r.slot < 0) break;
       const PtMatRegs mat = pt_mat_load<PT_CAT_NONE, false>(sc.slot_shade + r.slot);
       const PtSurface sf = pt_surface_hit(sc, o, d, r.slot, r.t, r.u, r.v, mat, pt_slot_geom(sc, r.slot));
-      const PtScatter scat = pt_material_scatter(sc, sf, mat, u);
+      const PtScatter scat = pt_material_scatter<PT_CAT_NONE, IMG>(sc, sf, mat, u);
       if (scat.kind == 0) break;
       const Quat rot_inv = pt_quat_conj(sf.rot);
       if (scat.kind == 1) {
@@ -132,7 +132,7 @@ __device__ __forceinline__ bool pt_box_mem(const PtNode* n, V3 p) {
   return n->mn[0] <= p.x && p.x <= n->mx[0] && n->mn[1] <= p.y && p.y <= n->mx[1] && n->mn[2] <= p.z && p.z <= n->mx[2];
 }
 
-template <int MODE>
+template <int MODE, bool IMG = false>
 __global__ __launch_bounds__(256) void k_ppm_gather(PtSceneDev sc, int stack_depth, PtPhotonMapDev pm, double radius,
                                                     const double* __restrict__ alpha, int eye_base, int width, int height,
                                                     int max_bounces, double inv_photon_count, double* __restrict__ img_sum,
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_ppm_gather(PtSceneDev sc, int stack_dep
       const double u = pt_lds_get(alpha, offset, dimension);
       const PtMatRegs mat = pt_mat_load<PT_CAT_NONE, false>(sc.slot_shade + r.slot);
       const PtSurface sf = pt_surface_hit(sc, o, d, r.slot, r.t, r.u, r.v, mat, pt_slot_geom(sc, r.slot));
-      const PtScatter scat = pt_material_scatter(sc, sf, mat, u);
+      const PtScatter scat = pt_material_scatter<PT_CAT_NONE, IMG>(sc, sf, mat, u);
       if (scat.kind == 0) break;
       if (scat.kind == 1) {
         beta = v3_mul(scat.attenuation, beta);

@@ -93,13 +93,22 @@ struct PtTexture { /* 64 B */
  * s_waitcnt); now the hop after the hit slot is the last one. */
 struct __attribute__((aligned(16))) PtShadeRec {
   int32_t kind;     /* PTX_MAT_* */
-  int32_t tex_kind; /* PTX_TEX_* (Lambertian / Metal) */
+  int32_t tex_kind; /* PTX_TEX_* (Lambertian / Metal), or PT_TEX_IMAGE */
   int32_t tex_w, tex_h;
   double index;
   double even[3];
   double odd[3];
   double emit[3];
 };
+/* An entry of the texture table that carries an image (ptx_scene_set_texture_image): tex_w x tex_h texels, and in place of the two
+ * colours, which an image does not use, the bits of even[0] = the device address of the texels (32-byte records {r, g, b, -}) and
+ * of even[1] = the PTX_IMAGE_* flags -- the hop after the hit slot stays the last one before the texels.  Only the instantiations
+ * flagged IMG look for it, and only scenes with an image or an environment launch those. */
+#define PT_TEX_IMAGE 2
+#define PT_BG_ENV 2 /* PtSceneDev.bg_kind: the environment image (ptx_scene_set_environment) */
+#define PT_IMAGE_BILINEAR 1 /* = PTX_IMAGE_* */
+#define PT_IMAGE_REPEAT_U 2
+#define PT_IMAGE_REPEAT_V 4
 
 /* everything a kernel needs, passed by value (pointers are device pointers) */
 struct PtSceneDev {
@@ -190,6 +199,14 @@ struct PtSceneDev {
   /* the camera tile lists of the image being rendered (scene_host.h, PtTileRec: 32 bytes per 8 x 8 tile of the global grid), or NULL.
    * Set per launch (launch_bounce_carry); read only by k_bounce_carry's TILE instantiations, which are launched only with it. */
   const uint32_t* tile_lists;
+  /* ptx_scene_set_texture_image / _set_environment: how many entries of the texture table carry an image; the environment's texels
+   * (32-byte records, NULL = none: bg_kind then is the descriptor's), its size, its PTX_IMAGE_BILINEAR flag and the row-major matrix
+   * from camera space to environment space.  Read only by the instantiations flagged IMG. */
+  const double* env;
+  int32_t env_w, env_h;
+  int32_t env_flags;
+  int32_t n_images;
+  double env_rot[9];
 };
 #define PT_TILE_WALK 0xffu /* a record's count byte: the tile's rays walk the tree */
 

@@ -261,6 +261,7 @@ struct Schedule {
   bool from_hbm = false;       /* the fused kernel runs as k_bounce<..., LDS_SCENE = false> over the per-octant image in HBM / L2 */
   bool share_cus = false;      /* two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half a CU */
   bool lit = false;            /* emitters under lighting mode 1 or 2: the LIT instantiations */
+  bool img = false;            /* an image texture or an environment: the IMG instantiations */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
@@ -310,6 +311,22 @@ struct ptx_scene {
   ptx_film_params film = kFilmDefault;      /* ptx_scene_set_film: what every entry point that films through this handle applies */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
+  /* Images (ptx_scene_set_texture_image / _set_environment): per entry of the texture table and for the environment, the host copy of
+   * the texel records (shared with the replicas) and this device's upload; the slot categories and shading records with the images in
+   * place (scene_image_overrides) and their uploads, which dev.slot_cat / dev.slot_shade point at while any entry carries an image */
+  struct ImageHost {
+    int32_t width = 0, height = 0, flags = 0;
+    std::vector<double> rec; /* 4 doubles per texel */
+  };
+  struct ImageSlot {
+    std::shared_ptr<const ImageHost> host;
+    DevBuf<double> dev;
+  };
+  std::vector<std::unique_ptr<ImageSlot>> images; /* one per texture entry once any was set; host == nullptr: none */
+  ImageSlot env;
+  double env_rot[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  DevBuf<uint8_t> slot_cat_img;
+  DevBuf<PtShadeRec> slot_shade_img;
   std::atomic<int> busy{0};
   /* owned device memory */
   DevBuf<PtNode> nodes;
@@ -541,6 +558,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
   /* An emissive scene in lighting mode 1 or 2 (PtSceneDev.lighting holds the mode in effect: mode 1 without emitters is mode 0): the
    * instantiations flagged LIT.  Such a scene takes the walk-first kernel and never runs solo. */
   c.lit = s->dev.lighting != 0 && s->dev.has_emit != 0;
+  /* A scene with an image on a texture entry or an environment (ptx_scene_set_texture_image / _set_environment): the instantiations
+   * flagged IMG, which only the walk-first k_bounce, k_shade_pool, the feature kernel and the photon passes have.  Like a lit scene
+   * it never takes the shade-first order -- hence no per-octant LDS image and no tile lists either -- and never runs solo. */
+  c.img = s->dev.n_images != 0 || s->dev.env != nullptr;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
   c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
@@ -549,8 +570,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * included (its COUNT instantiations); the scenes walked from HBM / L2 keep the two kernels */
   /* scenes walked from HBM / L2 run k_bounce<..., LDS_SCENE = false> over the per-octant node image (PTX_FUSED_GLOBAL=0: k_trace + k_shade_pool) */
   c.from_hbm = !in_lds && s->dev.nodes32o != nullptr && s->fused_global != 0 && !(s->dev.n_top > 0 && s->trace_top);
-  c.bounce_threads = s->bounce_threads > 0 ? std::min(PT_BOUNCE_THREADS, std::max(64, s->bounce_threads & ~63))
-                                           : (c.from_hbm ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS);
+  /* (the IMG instantiations are compiled for 3 waves per SIMD: at most PT_BOUNCE_THREADS_IMG threads a workgroup) */
+  const int bounce_max = c.img ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS;
+  c.bounce_threads = s->bounce_threads > 0 ? std::min(bounce_max, std::max(64, s->bounce_threads & ~63))
+                                           : std::min(bounce_max, c.from_hbm ? PT_BOUNCE_THREADS_GLOBAL : PT_BOUNCE_THREADS);
   /* the dynamic LDS of a k_bounce and of a k_bounce_carry launch: total, pool_off and whether it fits (PT_LDS_BOUNCE_LIMIT) */
   c.bounce = pt_lds_layout(lds_in(s, PT_LDS_K_BOUNCE, c.bounce_threads / 64, c.from_hbm));
   c.carry = pt_lds_layout(lds_in(s, PT_LDS_K_BOUNCE_CARRY, c.bounce_threads / 64, c.from_hbm));
@@ -560,7 +583,7 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
    * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
    * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
-  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && s->fused >= 2 && s->solo_entries <= 0 &&
+  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && !c.img && s->fused >= 2 && s->solo_entries <= 0 &&
                in_lds && !c.from_hbm && c.carry.fits;
   /* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
    * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
@@ -611,8 +634,13 @@ TraceKernel trace_kernel(int mode, bool count, bool primary, bool lds_scene, boo
   return count ? trace_kernel_of<PT_MODE_ARRAY, true>(primary, lds_scene, packet) : trace_kernel_of<PT_MODE_ARRAY, false>(primary, lds_scene, packet);
 }
 
-/* k_shade_pool: 6 = (EMIT, LIT) in {00, 10, 11} x PRIMARY 2 */
-ShadePoolKernel shade_pool_kernel(Shading shading, bool primary) {
+/* k_shade_pool: 12 = (EMIT, LIT) in {00, 10, 11} x PRIMARY 2 x IMG 2 */
+ShadePoolKernel shade_pool_kernel(Shading shading, bool primary, bool img) {
+  if (img) {
+    if (shading == Shading::lit) return primary ? k_shade_pool<true, true, true, true> : k_shade_pool<true, false, true, true>;
+    if (shading == Shading::emit) return primary ? k_shade_pool<true, true, false, true> : k_shade_pool<true, false, false, true>;
+    return primary ? k_shade_pool<false, true, false, true> : k_shade_pool<false, false, false, true>;
+  }
   if (shading == Shading::lit) return primary ? k_shade_pool<true, true, true> : k_shade_pool<true, false, true>;
   if (shading == Shading::emit) return primary ? k_shade_pool<true, true> : k_shade_pool<true, false>;
   return primary ? k_shade_pool<false, true> : k_shade_pool<false, false>;
@@ -666,7 +694,25 @@ BounceKernel bounce_kernel_of(Shading shading, bool primary, bool lds_scene, Var
   if (!lds_scene) return solo ? k_bounce<MODE, COUNT, false, false, false, true> : k_bounce<MODE, COUNT, false, false, false>;
   return solo ? k_bounce<MODE, COUNT, false, false, true, true> : k_bounce<MODE, COUNT, false, false, true>;
 }
-BounceKernel bounce_kernel(int mode, bool count, Shading shading, bool primary, bool lds_scene, Variant variant) {
+/* + 60 with an image texture or an environment (IMG) = MODE 2 x COUNT 2 x shading 3 x 5, the lit scene's five: such a scene never runs solo */
+template <int MODE, bool COUNT, bool EMIT, bool LIT>
+BounceKernel bounce_kernel_img_of(bool primary, bool lds_scene, bool lane_walk) {
+  if (primary && !lds_scene) return k_bounce<MODE, COUNT, EMIT, true, false, false, LIT, false, true>;
+  if (primary) return lane_walk ? k_bounce<MODE, COUNT, EMIT, true, true, false, LIT, true, true> : k_bounce<MODE, COUNT, EMIT, true, true, false, LIT, false, true>;
+  return lds_scene ? k_bounce<MODE, COUNT, EMIT, false, true, false, LIT, false, true> : k_bounce<MODE, COUNT, EMIT, false, false, false, LIT, false, true>;
+}
+template <int MODE, bool COUNT>
+BounceKernel bounce_kernel_img(Shading shading, bool primary, bool lds_scene, Variant variant) {
+  const bool lane_walk = variant == Variant::lane_walk && primary && lds_scene;
+  if (shading == Shading::lit) return bounce_kernel_img_of<MODE, COUNT, true, true>(primary, lds_scene, lane_walk);
+  if (shading == Shading::emit) return bounce_kernel_img_of<MODE, COUNT, true, false>(primary, lds_scene, lane_walk);
+  return bounce_kernel_img_of<MODE, COUNT, false, false>(primary, lds_scene, lane_walk);
+}
+BounceKernel bounce_kernel(int mode, bool count, Shading shading, bool primary, bool lds_scene, Variant variant, bool img) {
+  if (img) {
+    if (mode == PT_MODE_SIMD) return count ? bounce_kernel_img<PT_MODE_SIMD, true>(shading, primary, lds_scene, variant) : bounce_kernel_img<PT_MODE_SIMD, false>(shading, primary, lds_scene, variant);
+    return count ? bounce_kernel_img<PT_MODE_ARRAY, true>(shading, primary, lds_scene, variant) : bounce_kernel_img<PT_MODE_ARRAY, false>(shading, primary, lds_scene, variant);
+  }
   if (mode == PT_MODE_SIMD) return count ? bounce_kernel_of<PT_MODE_SIMD, true>(shading, primary, lds_scene, variant) : bounce_kernel_of<PT_MODE_SIMD, false>(shading, primary, lds_scene, variant);
   return count ? bounce_kernel_of<PT_MODE_ARRAY, true>(shading, primary, lds_scene, variant) : bounce_kernel_of<PT_MODE_ARRAY, false>(shading, primary, lds_scene, variant);
 }
@@ -712,12 +758,12 @@ void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
   /* 128 VGPRs: 16 waves per CU.  With two batches in flight each kernel takes HALF of what a CU holds, so that one batch's
    * trace workgroups (vector-issue-bound) and the other's shade workgroups (bound by the memory system) are resident on every
    * CU together instead of taking turns at the chip */
-  const int threads = sc.share_cus ? 256 : PT_POOL_THREADS; /* 256 threads when two batches share every CU, else 512 */
-  const int most = 1024 / threads;
+  const int threads = (sc.share_cus || sc.img) ? 256 : PT_POOL_THREADS; /* 256 threads when two batches share every CU and for the IMG kernels, else 512 */
+  const int most = (sc.img ? PT_IMG_WAVES * 256 : 1024) / threads;
   const int per_cu = s->shade_wgs_per_cu > 0 ? std::min(s->shade_wgs_per_cu, most) : (sc.share_cus ? std::max(1, most / 2) : most);
   const int grid = strided_grid(s, n_upper, threads, per_cu);
   const size_t lds = pt_lds_shade_pool_bytes(threads / 64);
-  hipLaunchKernelGGL(shade_pool_kernel(scene_shading(s), pl.on), dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
+  hipLaunchKernelGGL(shade_pool_kernel(scene_shading(s), pl.on, sc.img), dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
 }
 
 void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
@@ -752,12 +798,12 @@ void launch_bounce(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits&
   /* (LIT: the walk-first kernel without the solo loop, whatever PTX_SOLO_ENTRIES says -- run_bounces hands it no flag) */
   /* (camera rays of an LDS-resident scene: the packet walk or one ray per lane, Schedule::lane_walk) */
   const Variant variant = pl.on ? (sc.lane_walk ? Variant::lane_walk : Variant::plain) : (solo.flag != nullptr ? Variant::solo : Variant::plain);
-  const BounceKernel kern = bounce_kernel(s->dev.mode, count, scene_shading(s), pl.on, lds_scene, variant);
+  const BounceKernel kern = bounce_kernel(s->dev.mode, count, scene_shading(s), pl.on, lds_scene, variant, sc.img);
   prepare_kernel(s, (const void*)kern, "k_bounce", lds_scene, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
   const int threads = sc.bounce_threads;
   /* LDS scenes: one workgroup (one scene image) per CU; walks from HBM / L2: what the registers admit (PT_BOUNCE_WAVES per SIMD) --
    * shade_pool_slack and the parked-walk buffer are sized for 4 workgroups per CU */
-  const int per_cu = lds_scene ? 1 : std::max(1, std::min(4, (PT_BOUNCE_WAVES * 256) / threads));
+  const int per_cu = lds_scene ? 1 : std::max(1, std::min(4, ((sc.img ? PT_IMG_WAVES : PT_BOUNCE_WAVES) * 256) / threads));
   int grid = strided_grid(s, n_upper, threads, per_cu);
   if (s->bounce_wgs > 0) grid = std::max(1, std::min(grid, s->bounce_wgs));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), sc.bounce.total, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, stack_depth,
@@ -883,7 +929,7 @@ void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int
        * later ones return at once (the flag: a word of the batch's counts, zeroed with them).  A partial run (run_only) and a
        * hit-distance array without its second half never run solo. */
       PtSolo solo;
-      solo.flag = (run_only < 0 && s->solo_entries > 0 && !sc.lit && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
+      solo.flag = (run_only < 0 && s->solo_entries > 0 && !sc.lit && !sc.img && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
       solo.max_entries = (uint32_t)std::max(0, s->solo_entries);
       solo.max_bounces = max_bounces;
       solo.cap_entries = (uint32_t)std::min<size_t>(w.cap_entries, 0xffffffffu);
@@ -1884,6 +1930,222 @@ int32_t ptx_scene_film(const ptx_scene* s, ptx_film_params* out) {
   return 0;
 }
 
+/* ---- image textures and the environment ---- */
+/* A setter changes a scene and its replicas together or not at all: everything that can fail -- the uploads of the texels and of
+ * the slot categories and shading records made of them -- goes into fresh buffers first, for every scene (stage); only when all of
+ * them stand are the buffers swapped in (commit: moves and assignments, nothing that fails).  The caller has checked the arguments. */
+struct ImageStage {
+  using Host = std::shared_ptr<const ptx_scene::ImageHost>;
+  ptx_scene* s = nullptr;
+  DevBuf<double> texels;
+  DevBuf<uint8_t> cat;
+  DevBuf<PtShadeRec> shade;
+  int n_images = 0;
+};
+static int stage_texels(ptx_scene* s, const ImageStage::Host& host, ImageStage* st) {
+  st->s = s;
+  if (s->device < 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize()); /* frames queued with PTX_RENDER_ASYNC still read the buffers the commit replaces */
+  if (host) {
+    HIP_TRY(st->texels.ensure(host->rec.size()));
+    HIP_TRY(hipMemcpy(st->texels.p, host->rec.data(), sizeof(double) * host->rec.size(), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+/* the image for entry `index` of one scene's texture table (host == nullptr: none), and the slot categories and shading records with
+ * every image in place (scene_image_overrides) */
+static int stage_texture_image(ptx_scene* s, int32_t index, const ImageStage::Host& host, ImageStage* st) {
+  const int rc = stage_texels(s, host, st);
+  if (rc || s->device < 0) return rc;
+  std::vector<PtImageEntry> entries((size_t)s->host->n_textures);
+  for (size_t i = 0; i < entries.size(); ++i) {
+    const bool mine = i == (size_t)index;
+    const ptx_scene::ImageHost* h = mine ? host.get() : (s->images.empty() ? nullptr : s->images[i]->host.get());
+    if (!h) continue;
+    entries[i].width = h->width;
+    entries[i].height = h->height;
+    entries[i].flags = h->flags;
+    entries[i].texels = (uint64_t)(uintptr_t)(mine ? st->texels.p : s->images[i]->dev.p);
+    ++st->n_images;
+  }
+  if (st->n_images) {
+    std::vector<uint8_t> cat;
+    std::vector<PtShadeRec> shade;
+    scene_image_overrides(*s->host, entries, &cat, &shade);
+    HIP_TRY(st->cat.ensure(cat.size()));
+    HIP_TRY(st->shade.ensure(shade.size()));
+    HIP_TRY(hipMemcpy(st->cat.p, cat.data(), cat.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st->shade.p, shade.data(), sizeof(PtShadeRec) * shade.size(), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+static void commit_texture_image(ImageStage* st, int32_t index, const ImageStage::Host& host) {
+  ptx_scene* s = st->s;
+  if (s->images.empty()) {
+    s->images.resize((size_t)s->host->n_textures);
+    for (auto& e : s->images) e = std::make_unique<ptx_scene::ImageSlot>();
+  }
+  if (s->device >= 0) (void)hipSetDevice(s->device); /* (the buffers the moves below release are this device's) */
+  ptx_scene::ImageSlot& slot = *s->images[(size_t)index];
+  slot.dev = std::move(st->texels);
+  slot.host = host;
+  if (s->device < 0) return;
+  s->slot_cat_img = std::move(st->cat);
+  s->slot_shade_img = std::move(st->shade);
+  s->dev.n_images = st->n_images;
+  s->dev.slot_cat = st->n_images ? s->slot_cat_img.p : s->slot_cat.p;
+  s->dev.slot_shade = st->n_images ? s->slot_shade_img.p : s->slot_shade.p;
+  reschedule(s, s->sets_in_flight); /* (Schedule::img, and what follows from it) */
+}
+static void commit_environment(ImageStage* st, const ImageStage::Host& host, const double* rot) {
+  ptx_scene* s = st->s;
+  if (s->device >= 0) (void)hipSetDevice(s->device);
+  s->env.dev = std::move(st->texels);
+  s->env.host = host;
+  std::memcpy(s->env_rot, rot, sizeof s->env_rot);
+  if (s->device < 0) return;
+  const ptx_scene::ImageHost* e = host.get();
+  s->dev.env = e ? s->env.dev.p : nullptr;
+  s->dev.env_w = e ? e->width : 0;
+  s->dev.env_h = e ? e->height : 0;
+  s->dev.env_flags = e ? e->flags : 0;
+  std::memcpy(s->dev.env_rot, s->env_rot, sizeof s->env_rot);
+  s->dev.bg_kind = e ? PT_BG_ENV : s->host->dev.bg_kind;
+  reschedule(s, s->sets_in_flight);
+}
+/* the scene, then its replicas */
+static std::vector<ptx_scene*> scene_family(ptx_scene* s) {
+  std::vector<ptx_scene*> all{s};
+  all.insert(all.end(), s->replicas.begin(), s->replicas.end());
+  return all;
+}
+static int family_take_texture_image(const std::vector<ptx_scene*>& all, int32_t index, const ImageStage::Host& host) {
+  std::vector<ImageStage> stages(all.size());
+  for (size_t k = 0; k < all.size(); ++k)
+    if (const int rc = stage_texture_image(all[k], index, host, &stages[k])) return rc; /* nothing has changed yet */
+  for (ImageStage& st : stages) commit_texture_image(&st, index, host);
+  return 0;
+}
+static int family_take_environment(const std::vector<ptx_scene*>& all, const ImageStage::Host& host, const double* rot) {
+  std::vector<ImageStage> stages(all.size());
+  for (size_t k = 0; k < all.size(); ++k)
+    if (const int rc = stage_texels(all[k], host, &stages[k])) return rc;
+  for (ImageStage& st : stages) commit_environment(&st, host, rot);
+  return 0;
+}
+static std::shared_ptr<const ptx_scene::ImageHost> image_host_copy(const ptx_image* img) {
+  auto h = std::make_shared<ptx_scene::ImageHost>();
+  h->width = img->width;
+  h->height = img->height;
+  h->flags = img->flags;
+  h->rec = scene_image_records(img);
+  return h;
+}
+static int check_texture_index(const ptx_scene* s, int32_t index) {
+  if (index < 0 || index >= s->host->n_textures) return fail(PTX_ERR_ARG, "texture index %d out of range (the scene's texture table has %d entries)", index, s->host->n_textures);
+  return 0;
+}
+static const double kIdentity3[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+
+int32_t ptx_scene_set_texture_image(ptx_scene* s, int32_t index, const ptx_image* img) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  int rc = check_texture_index(s, index);
+  if (rc) return rc;
+  if (img) {
+    std::string msg;
+    if ((rc = scene_check_image(img, false, &msg)) != 0) return fail(rc, "%s", msg.c_str());
+  }
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "a texture image cannot change while a render runs on the scene");
+  if (!img && s->images.empty()) return 0; /* nothing was ever set */
+  std::shared_ptr<const ptx_scene::ImageHost> host = img ? image_host_copy(img) : nullptr;
+  return family_take_texture_image(scene_family(s), index, host);
+}
+
+int32_t ptx_scene_set_environment(ptx_scene* s, const ptx_image* img, const double* R) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  int rc = 0;
+  if (img) {
+    std::string msg;
+    if ((rc = scene_check_image(img, true, &msg)) != 0) return fail(rc, "%s", msg.c_str());
+  }
+  if (R)
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(R[k])) return fail(PTX_ERR_ARG, "environment: R[%d] is not finite", k);
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the environment cannot change while a render runs on the scene");
+  const double* rot = (img && R) ? R : kIdentity3;
+  std::shared_ptr<const ptx_scene::ImageHost> host = img ? image_host_copy(img) : nullptr;
+  return family_take_environment(scene_family(s), host, rot);
+}
+
+static void image_describe(const ptx_scene::ImageHost* h, ptx_image* out) {
+  std::memset(out, 0, sizeof *out);
+  if (!h) return;
+  out->width = h->width;
+  out->height = h->height;
+  out->flags = h->flags;
+}
+int32_t ptx_scene_texture_image(const ptx_scene* s, int32_t index, ptx_image* out) {
+  if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
+  const int rc = check_texture_index(s, index);
+  if (rc) return rc;
+  image_describe(s->images.empty() ? nullptr : s->images[(size_t)index]->host.get(), out);
+  return 0;
+}
+int32_t ptx_scene_environment(const ptx_scene* s, ptx_image* out, double* R_out) {
+  if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
+  image_describe(s->env.host.get(), out);
+  if (R_out) std::memcpy(R_out, s->env_rot, sizeof s->env_rot);
+  return 0;
+}
+
+int32_t ptx_texture_eval(ptx_scene* s, int32_t index, int64_t n, const double* uv, double* rgb_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  int rc = check_texture_index(s, index);
+  if (rc) return rc;
+  if (n < 0 || !uv || !rgb_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  /* the record a slot whose material points at this entry holds: the descriptor's texture, or the image in its place */
+  PtShadeRec rec{};
+  const PtTexture& t = s->host->texs[(size_t)index];
+  rec.kind = PTX_MAT_LAMBERTIAN;
+  rec.tex_kind = t.kind; rec.tex_w = t.width; rec.tex_h = t.height;
+  std::memcpy(rec.even, t.even, sizeof rec.even);
+  std::memcpy(rec.odd, t.odd, sizeof rec.odd);
+  if (!s->images.empty() && s->images[(size_t)index]->host) {
+    const ptx_scene::ImageSlot& e = *s->images[(size_t)index];
+    const uint64_t texels = (uint64_t)(uintptr_t)e.dev.p, flags = (uint64_t)(uint32_t)e.host->flags;
+    rec.tex_kind = PT_TEX_IMAGE; rec.tex_w = e.host->width; rec.tex_h = e.host->height;
+    std::memset(rec.even, 0, sizeof rec.even);
+    std::memcpy(&rec.even[0], &texels, sizeof texels);
+    std::memcpy(&rec.even[1], &flags, sizeof flags);
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_uv, d_out;
+  HIP_TRY(d_uv.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
+  HIP_TRY(hipMemcpy(d_uv.p, uv, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_texture_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, rec, (long long)n, d_uv.p, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(rgb_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int32_t ptx_environment_eval(ptx_scene* s, int64_t n, const double* dirs, double* rgb_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (n < 0 || !dirs || !rgb_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_dirs, d_out;
+  HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n * 3));
+  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_environment_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_dirs.p, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(rgb_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
   if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
   std::memset(out, 0, sizeof *out);
@@ -2019,6 +2281,16 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->tree_leaves = src->tree_leaves;
   s->film = src->film;
   if (scene_upload(s) != 0 || (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
+    ptx_scene_destroy(s);
+    return nullptr;
+  }
+  /* the images and the environment: the host copies are shared, this device gets its own uploads */
+  for (size_t i = 0; i < src->images.size(); ++i)
+    if (src->images[i]->host && family_take_texture_image({s}, (int32_t)i, src->images[i]->host) != 0) {
+      ptx_scene_destroy(s);
+      return nullptr;
+    }
+  if (src->env.host && family_take_environment({s}, src->env.host, src->env_rot) != 0) {
     ptx_scene_destroy(s);
     return nullptr;
   }
@@ -2796,7 +3068,7 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
     pl.n = (uint32_t)((unsigned long long)n_pass * padded);
     HIP_TRY(hipMemsetAsync(s->feat_work.p, 0, sizeof(uint32_t) * 8, st));
     launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, 0, pl);
-    hipLaunchKernelGGL(k_features, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
+    hipLaunchKernelGGL(s->sched.img ? k_features<true> : k_features<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -3300,8 +3572,10 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
       const int depth = std::max(1, s->tree_depth + 1);
       const size_t lds = (size_t)4 * depth * PT_WAVE * sizeof(uint32_t);
       const dim3 gd((unsigned)((total + 255) / 256)), bd(256);
-      if (array_mode) hipLaunchKernelGGL((k_ppm_photons<PT_MODE_ARRAY>), gd, bd, lds, nullptr, s->dev, depth, d_lights.p, n_lights, d_first.p, it * p->photon_count, d_palpha.p, mb, po, d_cnt.p);
-      else hipLaunchKernelGGL((k_ppm_photons<PT_MODE_SIMD>), gd, bd, lds, nullptr, s->dev, depth, d_lights.p, n_lights, d_first.p, it * p->photon_count, d_palpha.p, mb, po, d_cnt.p);
+      /* (a scene with an image texture: the IMG instantiations, as in a render) */
+      const auto kern = s->dev.n_images != 0 ? (array_mode ? k_ppm_photons<PT_MODE_ARRAY, true> : k_ppm_photons<PT_MODE_SIMD, true>)
+                                             : (array_mode ? k_ppm_photons<PT_MODE_ARRAY> : k_ppm_photons<PT_MODE_SIMD>);
+      hipLaunchKernelGGL(kern, gd, bd, lds, nullptr, s->dev, depth, d_lights.p, n_lights, d_first.p, it * p->photon_count, d_palpha.p, mb, po, d_cnt.p);
       PPM_TRY(hipGetLastError());
     }
     PPM_TRY(hipDeviceSynchronize());
@@ -3395,12 +3669,10 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
       const size_t lds = (size_t)4 * depth * PT_WAVE * sizeof(uint32_t);
       if (lds > 160 * 1024) { release(); return fail(PTX_ERR_STATE, "photon tree too deep for the LDS stack"); }
       const dim3 gd((unsigned)(((size_t)W * H + 255) / 256)), bd(256);
-      if (lds > 64 * 1024) {
-        raise_dynamic_lds_limit((const void*)k_ppm_gather<PT_MODE_ARRAY>, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
-        raise_dynamic_lds_limit((const void*)k_ppm_gather<PT_MODE_SIMD>, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
-      }
-      if (array_mode) hipLaunchKernelGGL((k_ppm_gather<PT_MODE_ARRAY>), gd, bd, lds, nullptr, s->dev, depth, pm, radius, d_ealpha.p, it * W * H, W, H, mb, inv_photon_count, d_img.p, d_cnt.p + 1);
-      else hipLaunchKernelGGL((k_ppm_gather<PT_MODE_SIMD>), gd, bd, lds, nullptr, s->dev, depth, pm, radius, d_ealpha.p, it * W * H, W, H, mb, inv_photon_count, d_img.p, d_cnt.p + 1);
+      const auto kern = s->dev.n_images != 0 ? (array_mode ? k_ppm_gather<PT_MODE_ARRAY, true> : k_ppm_gather<PT_MODE_SIMD, true>)
+                                             : (array_mode ? k_ppm_gather<PT_MODE_ARRAY> : k_ppm_gather<PT_MODE_SIMD>);
+      if (lds > 64 * 1024) raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
+      hipLaunchKernelGGL(kern, gd, bd, lds, nullptr, s->dev, depth, pm, radius, d_ealpha.p, it * W * H, W, H, mb, inv_photon_count, d_img.p, d_cnt.p + 1);
       PPM_TRY(hipGetLastError());
       PPM_TRY(hipDeviceSynchronize());
     }

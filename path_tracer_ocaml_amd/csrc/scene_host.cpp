@@ -524,6 +524,7 @@ int scene_set_tree(const ptx_scene_desc* d, BvhResult&& tree, PtHostArrays* h, s
   h->dev.n_nodes = (int)h->nodes.size();
   h->dev.n_slots = (int)h->slot_prim.size();
   h->dev.depth = tree.depth;
+  h->n_textures = d->n_textures;
   for (int f = 0; f < d->n_floor_triangles; ++f) h->slot_prim.push_back(d->n_triangles + d->n_spheres + f);
   emissive_list(d, h);
   return 0;
@@ -563,6 +564,54 @@ std::vector<double> light_table_build(const PtHostArrays& h) {
     o[PT_LIGHT_CUM] = cum;
   }
   return table;
+}
+
+/* ---- image textures and the environment (scene_host.h) ---- */
+int scene_check_image(const ptx_image* img, bool environment, std::string* msg) {
+  const char* what = environment ? "environment" : "texture image";
+  if (img->width < 1 || img->width > PTX_IMAGE_MAX_SIZE || img->height < 1 || img->height > PTX_IMAGE_MAX_SIZE)
+    return reject(msg, "%s size %d x %d: width and height must be in [1, %d]", what, img->width, img->height, PTX_IMAGE_MAX_SIZE);
+  const int known = PTX_IMAGE_BILINEAR | PTX_IMAGE_REPEAT_U | PTX_IMAGE_REPEAT_V;
+  if (img->flags & ~known) return reject(msg, "%s: unknown bits in flags (0x%x)", what, (unsigned)img->flags);
+  if (environment && (img->flags & ~PTX_IMAGE_BILINEAR))
+    return reject(msg, "environment: a repeat flag is not accepted (an environment repeats in u and clamps in v); only PTX_IMAGE_BILINEAR is");
+  if (img->reserved != 0) return reject(msg, "%s: reserved must be 0 (got %d)", what, img->reserved);
+  if (!img->rgb) return reject(msg, "%s: rgb is NULL", what);
+  const size_t n = (size_t)img->width * (size_t)img->height * 3;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(img->rgb[i]))
+      return reject(msg, "%s: texel (%zu, %zu) channel %zu is not finite", what, (i / 3) % (size_t)img->width, (i / 3) / (size_t)img->width, i % 3);
+  return 0;
+}
+
+std::vector<double> scene_image_records(const ptx_image* img) {
+  const size_t n = (size_t)img->width * (size_t)img->height;
+  std::vector<double> rec(n * 4, 0.0);
+  for (size_t i = 0; i < n; ++i) std::memcpy(&rec[i * 4], &img->rgb[i * 3], sizeof(double) * 3);
+  return rec;
+}
+
+void scene_image_overrides(const PtHostArrays& h, const std::vector<PtImageEntry>& entries, std::vector<uint8_t>* cat,
+                           std::vector<PtShadeRec>* shade) {
+  *cat = h.cat;
+  *shade = h.shade;
+  for (size_t sl = 0; sl < h.kind.size(); ++sl) {
+    if (h.kind[sl] == PT_SLOT_PAD) continue;
+    const PtMaterial& m = h.mats[(size_t)h.slot_mat[sl]];
+    if (m.kind == PTX_MAT_DIELECTRIC || (size_t)m.texture >= entries.size()) continue;
+    const PtImageEntry& e = entries[(size_t)m.texture];
+    if (e.width == 0) continue;
+    PtShadeRec& r = (*shade)[sl];
+    r.tex_kind = PT_TEX_IMAGE;
+    r.tex_w = e.width;
+    r.tex_h = e.height;
+    const uint64_t flags = (uint64_t)(uint32_t)e.flags;
+    std::memset(r.even, 0, sizeof r.even);
+    std::memset(r.odd, 0, sizeof r.odd);
+    std::memcpy(&r.even[0], &e.texels, sizeof(uint64_t));
+    std::memcpy(&r.even[1], &flags, sizeof(uint64_t));
+    if (m.kind == PTX_MAT_LAMBERTIAN) (*cat)[sl] = PT_CAT_LAMBERT_CHECKER;
+  }
 }
 
 /* ---- camera tile lists (scene_host.h) ---- */

@@ -37,6 +37,7 @@ struct PtHostArrays {
    * n_emissive_tris counts them all (ptx_scene_set_lighting makes the light table of them) */
   std::vector<double> emissive_tris;
   int n_emissive_tris = 0;
+  int n_textures = 0; /* the descriptor's texture table (ptx_scene_set_texture_image checks its index against it, host-only scenes too) */
   int tile_lists = 0; /* SceneOptions::tile_lists, kept for the schedule: camera launches may scan per-tile sphere lists (scene_tile_lists) */
   PtSceneDev dev{}; /* the scalar fields; device pointers are filled per upload */
 };
@@ -72,6 +73,24 @@ void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, cons
 
 /* The light table of PTX_LIGHTING_SAMPLED: per emissive tree triangle PT_LIGHT_DOUBLES doubles {a, b, c, n, A, cum} */
 std::vector<double> light_table_build(const PtHostArrays& h);
+
+/* ---- image textures and the environment (include/ptx.h) ----
+ * Every check of a caller's ptx_image: size, flags (an environment accepts PTX_IMAGE_BILINEAR only), reserved, every texel finite.
+ * 0, or PTX_ERR_ARG with *msg naming what was wrong. */
+int scene_check_image(const ptx_image* img, bool environment, std::string* msg);
+/* the texels as the device holds them: one 32-byte record {r, g, b, 0} per texel, bit for bit */
+std::vector<double> scene_image_records(const ptx_image* img);
+/* One entry of the texture table that carries an image: its size and flags and where one device holds its texels (width 0 = the entry
+ * keeps the descriptor's texture). */
+struct PtImageEntry {
+  int32_t width = 0, height = 0, flags = 0;
+  uint64_t texels = 0; /* device address of the records */
+};
+/* h.cat and h.shade with the images of `entries` (one per texture-table entry) in place: a slot whose material points at such an entry
+ * gets tex_kind PT_TEX_IMAGE, the size, and the address and flags in the bits of even[0] / even[1] (pt_scene.h); a Lambertian one moves
+ * to the textured-Lambertian category, whose shade step computes tex coords. */
+void scene_image_overrides(const PtHostArrays& h, const std::vector<PtImageEntry>& entries, std::vector<uint8_t>* cat,
+                           std::vector<PtShadeRec>* shade);
 
 /* ---- camera tile lists: which spheres a camera ray through an 8 x 8 pixel tile can meet ----
  * One 32-byte record per tile of the GLOBAL tile grid of a width x height image, row-major, tiles_x = ceil(width / 8):

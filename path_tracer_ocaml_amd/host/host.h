@@ -2,6 +2,7 @@
  * Render_command (the parts of the reference that sit ABOVE the integrator boundary). */
 #ifndef PT_HOST_H
 #define PT_HOST_H
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/ptx.h"
@@ -54,6 +55,24 @@ const int64_t* pth_ply_rows(pth_ply* p, const char* list_property, const int32_t
 pth_scene* pth_scene_ganesha_ply(const char* path, int32_t width, int32_t height);
 /* the synthetic stand-in mesh written as a PLY file with the real model's layout */
 int32_t pth_write_ganesha_like_ply(const char* path, int32_t n_target, uint64_t seed);
+
+/* ---- PFM images (pfm.cpp): the hosts' one image decoder, for --envmap and --ground-texture ----
+ * "PF" / "Pf" (grey: r = g = b), either byte order by the sign of the scale, rows bottom to top = the image rule's v = 0 first
+ * (include/ptx.h).  NULL + pth_image_error() on a file that cannot be opened or is malformed. */
+typedef struct pth_image pth_image;
+const char* pth_image_error(void);
+pth_image* pth_pfm_load(const char* path);
+pth_image* pth_pfm_parse(const unsigned char* bytes, size_t n);
+void pth_image_free(pth_image* img);
+int32_t pth_image_width(const pth_image* img);
+int32_t pth_image_height(const pth_image* img);
+int32_t pth_image_channels(const pth_image* img); /* of the file: 3 or 1 */
+const double* pth_image_rgb(const pth_image* img); /* width * height * 3 */
+/* the row-major matrix of a rotation by `degrees` about the camera-space y axis (ptx_scene_set_environment's R) */
+void pth_rotation_y(double degrees, double R[9]);
+/* the texture-table entry --ground-texture replaces: the floor triangles' material's texture, else the first checker (Shirley's
+ * ground); -1 when the scene has neither */
+int32_t pth_ground_texture(const ptx_scene_desc* d);
 
 /* Bimage_unix.Stb.write of the f64 image (render_command.ml:66-70): 8-bit RGB PNG, v -> int(v*255) clamped.
  * returns 0 on success */

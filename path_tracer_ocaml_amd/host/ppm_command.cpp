@@ -23,6 +23,7 @@ extern "C" void pth_ppm_gamma(const double* img_sum, int64_t count, int32_t n, d
 #endif
 
 #if defined(PPM_SCENE_CORNELL) || defined(PPM_SCENE_GANESHA)
+#include "image_flags.h"
 namespace {
 struct Ctx {
   std::string output;
@@ -50,6 +51,8 @@ int main(int argc, char** argv) {
   std::string output = "output.png", ply;
   bool stop_after_bvh = false;
   int n_tri = 150000;
+  ImageFlags images; // --envmap=FILE.pfm [--envmap-rotate=DEG] [--ground-texture=FILE.pfm [--texture-nearest]] (image_flags.h)
+  std::string bad;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> const char* {
@@ -69,12 +72,31 @@ int main(int argc, char** argv) {
     else if (a == "-stop-after-bvh") stop_after_bvh = true;
     else if (a == "-triangles") n_tri = std::atoi(val());
 #endif
+    else if (image_flag(a, &images, &bad)) {
+      if (!bad.empty()) { std::fprintf(stderr, "%s: %s\n", argv[0], bad.c_str()); return 2; }
+    }
     else if (a == "-help" || a == "--help") {
       std::printf("Defaults: width = 600, height = 600, output = output.png\n");
+#ifdef PPM_SCENE_GANESHA
+      std::printf("Images: " PTH_IMAGE_FLAGS_USAGE "\n");
+#else
+      std::printf("Images: [--envmap=FILE.pfm] [--envmap-rotate=DEG]\n");
+#endif
+      std::printf("  (the photon mapper's paths end where they leave the scene: an environment is loaded and checked, and no pixel sees it)\n");
       return 0;
     } else { std::fprintf(stderr, "%s: unknown option '%s'.\n", argv[0], a.c_str()); return 2; } // Stdlib.Arg exits 2
   }
   if (p.height < 0) p.height = p.width; // `let height = ref !width`
+  {
+#ifdef PPM_SCENE_GANESHA
+    bad = image_flags_check(images, true);
+#else
+    bad = image_flags_check(images, false);
+#endif
+    if (!bad.empty()) { std::fprintf(stderr, "%s: %s\n", argv[0], bad.c_str()); return 2; }
+    if (!images.envmap.empty())
+      std::fprintf(stderr, "%s: note: the photon mapper's paths end where they leave the scene; --envmap is checked and has no effect here\n", argv[0]);
+  }
   (void)stop_after_bvh; (void)n_tri;
   pth_scene* hs;
   ptx_light lights[2];
@@ -92,6 +114,10 @@ int main(int argc, char** argv) {
   const double t_build = now_ms();
   ptx_scene* scene = ptx_scene_create(&d, 0);
   if (!scene) { std::fprintf(stderr, "ptx_scene_create: %s\n", ptx_last_error()); return 1; }
+  { // (the photon mapper's paths end where they leave the scene, progressive_photon_map.ml:326: an environment is accepted and not seen)
+    std::string err;
+    if (apply_image_flags(scene, &d, images, &err) != 0) { std::fprintf(stderr, "%s: %s\n", argv[0], err.c_str()); return 1; }
+  }
 #ifdef PPM_SCENE_GANESHA
   ptx_stats bs;
   ptx_scene_stats(scene, &bs);

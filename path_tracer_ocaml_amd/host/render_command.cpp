@@ -15,6 +15,9 @@
 // --denoise[=LEVELS]: the image of every update filtered by the variance-guided a-trous denoiser (ptx_render_denoised; with
 // --progressive=K an update every K passes, without it one update after the last pass); --aov=PREFIX (with --denoise) also writes the
 // first-hit feature means as PREFIX-albedo.png, PREFIX-normal.png (n / 2 + 1 / 2) and PREFIX-depth.png (z / max z).
+// --envmap=FILE.pfm [--envmap-rotate=DEG]: a latitude-longitude environment in place of the background (ptx_scene_set_environment; the
+// rotation is about the camera-space y axis); --ground-texture=FILE.pfm [--texture-nearest]: an image, repeated on both axes, on
+// the ground (shirley) or floor (ganesha) material (ptx_scene_set_texture_image); image_flags.h.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "host.h"
+#include "image_flags.h"
 
 namespace {
 
@@ -51,6 +55,7 @@ struct Args {
   std::string aov;                       // --aov=PREFIX
   bool have_filter = false;              // --filter=ORDER,RADIUS and / or --filter-renormalise
   ptx_film_params film{5, 1, 0, 0};      // ptx_film_defaults
+  ImageFlags images;                     // --envmap, --envmap-rotate, --ground-texture, --texture-nearest
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -61,7 +66,8 @@ struct Args {
                "          [--ganesha-ply=PATH] [--triangles=INT] [--ceiling-emit=FLOAT]\n"
                "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
                "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
-               "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n",
+               "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n"
+               "          " PTH_IMAGE_FLAGS_USAGE "\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -89,8 +95,10 @@ Args parse(int argc, char** argv) {
   Args a;
   bool have_dim = false;
   for (int i = 1; i < argc; ++i) {
-    std::string v;
-    if (take_value(argc, argv, i, "dimension", "d", &v)) {
+    std::string v, bad;
+    if (image_flag(argv[i], &a.images, &bad)) {
+      if (!bad.empty()) usage(argv[0], bad.c_str());
+    } else if (take_value(argc, argv, i, "dimension", "d", &v)) {
       if (std::sscanf(v.c_str(), "%d,%d", &a.width, &a.height) != 2) usage(argv[0], "invalid value for --dimension, expected WIDTH,HEIGHT");
       have_dim = true;
     } else if (take_value(argc, argv, i, "samples-per-pixel", nullptr, &v)) a.samples_per_pixel = std::atoi(v.c_str());
@@ -172,6 +180,10 @@ Args parse(int argc, char** argv) {
   if (a.denoise >= 0 && a.gpus > 1) usage(argv[0], "--denoise renders on one GPU (--gpus=1)");
   if (a.denoise >= 0 && a.samples_per_pixel < 2) usage(argv[0], "--denoise requires --samples-per-pixel >= 2");
   if (a.denoise >= 0 && a.progressive == 1) usage(argv[0], "--denoise requires --progressive >= 2");
+  {
+    const std::string bad = image_flags_check(a.images, a.scene != "cornell");
+    if (!bad.empty()) usage(argv[0], bad.c_str());
+  }
   if (a.have_filter) { // the library's own check and message (host only: no device is touched)
     double w[2 * PTX_FILM_MAX_RADIUS + 1];
     if (ptx_film_weights(&a.film, w, nullptr) != 0) usage(argv[0], ptx_last_error());
@@ -280,6 +292,13 @@ int main(int argc, char** argv) {
   if (a.have_filter && ptx_scene_set_film(scene, &a.film) != 0) {
     std::fprintf(stderr, "ptx_scene_set_film: %s\n", ptx_last_error());
     return 1;
+  }
+  {
+    std::string err;
+    if (apply_image_flags(scene, d, a.images, &err) != 0) {
+      std::fprintf(stderr, "%s: %s\n", argv[0], err.c_str());
+      return 1;
+    }
   }
   ptx_stats st;
   ptx_scene_stats(scene, &st);

@@ -56,9 +56,12 @@ class Integrator:
     "reference" (the default: ``Pdf.diffuse`` and the reference's emission formula), "path-order" or "sampled"
     (Scene.set_lighting); None leaves a Scene that was handed in as it is.  ``film`` is the reconstruction filter the reference
     hard-wires (``Binomial.create ~order:5 ~pixel_radius:1``): (order, radius) or (order, radius, renormalise) for Scene.set_film;
-    None leaves the scene's film as it is."""
+    None leaves the scene's film as it is.  ``environment``: an (H, W, 3) latitude-longitude image, or (image, rotation) or
+    (image, rotation, bilinear), for Scene.set_environment; ``images``: {texture index: image or (image, bilinear, repeat)} for
+    Scene.set_texture_image.  None leaves the scene's as they are."""
 
-    def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None):
+    def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
+                 environment=None, images=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
@@ -68,14 +71,19 @@ class Integrator:
             self._scene.set_lighting(lighting)
         if film is not None:
             self._scene.set_film(*film)
+        if environment is not None:
+            self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
+        for index, img in (images or {}).items():
+            self._scene.set_texture_image(index, *(img if isinstance(img, tuple) else (img,)))
         self.stats = None
         self.error = self.passes_done = None  # render_progressive
         self.passes = None  # render_adaptive
         self.features = None  # render_denoised
 
     @classmethod
-    def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None):
-        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film)
+    def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
+               environment=None, images=None):
+        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
