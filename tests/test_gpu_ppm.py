@@ -92,6 +92,86 @@ def test_ppm_shirley_simd_leaf_one_bounce_deep(P, oracle):
     _check(P, oracle, d, [light], abi.ppm_params(w, h, iterations=2, photon_count=15000, max_bounces=8))
 
 
+# ---- image textures and the environment in the photon mapper (the IMG instantiations of both passes) ----
+def _ppm_image_check(P, oracle, src, index, cells, lights, params):
+    """the even checker on entry `index` as an image (nearest, repeat on both axes) on the GPU against the oracle on the checker
+    descriptor: img_sum bit for bit, the stats equal.  Returns (the GPU scene with the image set, the oracle's image)."""
+    import ctypes as C
+    import texture_reference as T
+    import texture_support as S
+    d, keep = S.with_checker(src, index, cells[0] + 1, cells[1] + 1)
+    o = oracle.Scene(C.pointer(d), keep)
+    o_img, o_st = o.ppm_render(params, lights)
+    o.close()
+    even, odd = S.checker_colours(d, index)
+    g = P.Scene(C.pointer(d), 0, keepalive=keep)
+    g.set_texture_image(index, T.checker_image(cells[0], cells[1], even, odd), repeat=(True, True))
+    g_img, g_st = g.ppm_render(params, lights)
+    for k in ("photons_stored", "photon_rays", "eye_rays", "neighbors", "last_radius"):
+        assert g_st[k] == o_st[k], (k, g_st[k], o_st[k])
+    assert o_img.max() > 0
+    nbad = int((g_img.view(np.uint64) != o_img.view(np.uint64)).sum())
+    assert nbad == 0, f"{nbad} of {o_img.size} img_sum values differ from the oracle"
+    return g, o_img
+
+
+@pytest.mark.parametrize("host_list", [False, True])
+def test_ppm_cornell_with_a_checker_image(P, oracle, monkeypatch, host_list):
+    """Array_leaf mode, the shape of test_ppm_host_side_list_and_tree, on both list paths; then the controls: an image that is not
+    the checker (its two colours exchanged) gives another img_sum, removing it the checker's bits again"""
+    import texture_reference as T
+    import texture_support as S
+    from path_tracer_ocaml_amd import abi
+    if host_list:
+        monkeypatch.setenv("PTX_PPM_HOST_LIST", "1")
+    w = h = 96
+    lights, params = oracle.lights_cornell(w, h), abi.ppm_params(w, h, iterations=2, photon_count=12000)
+    g, o_img = _ppm_image_check(P, oracle, oracle.desc_cornell(w, h, 0.0), 4, (10, 10), lights, params)
+    try:
+        if not host_list:
+            even, odd = S.checker_colours(oracle.desc_cornell(w, h, 0.0).d, 4)  # (with_checker keeps a checker entry's colours)
+            g.set_texture_image(4, T.checker_image(10, 10, odd, even), repeat=(True, True))
+            other, _ = g.ppm_render(params, lights)
+            assert not np.array_equal(other, o_img)
+            g.set_texture_image(4, None)
+            back, _ = g.ppm_render(params, lights)
+            assert np.array_equal(back.view(np.uint64), o_img.view(np.uint64))
+    finally:
+        g.close()
+
+
+def test_ppm_shirley_simd_leaf_with_a_checker_image(P, oracle):
+    """the PT_MODE_SIMD instantiations: the checker on the ground, the lights and shape of
+    test_ppm_shirley_simd_leaf_one_bounce_deep"""
+    from path_tracer_ocaml_amd import abi
+    w, h = 120, 60
+    light = abi.Light()
+    light.kind = abi.PTX_LIGHT_POINT
+    light.position[:] = [0.0, 6.0, -12.0]
+    light.color[:] = [1.0, 0.9, 0.8]
+    light.power = 50.0
+    g, _ = _ppm_image_check(P, oracle, oracle.desc_shirley(w, h), 0, (10, 20), [light],
+                            abi.ppm_params(w, h, iterations=2, photon_count=15000, max_bounces=8))
+    g.close()
+
+
+def test_ppm_ignores_an_environment(P, oracle):
+    """a miss ends a photon path and an eye path, so an environment alone changes nothing: the oracle's bits"""
+    import texture_support as S
+    from path_tracer_ocaml_amd import abi
+    w = h = 48
+    d = oracle.desc_cornell(w, h, 0.0)
+    lights, params = oracle.lights_cornell(w, h), abi.ppm_params(w, h, iterations=2, photon_count=4000)
+    o_img, o_st = oracle.Scene(d.ptr, d).ppm_render(params, lights)
+    g = P.Scene(d.ptr, 0, keepalive=d)
+    g.set_environment(S.random_environment(16, 8, 5), rotation=S.rotation([0.3, 1.0, 0.2], 50.0))
+    g_img, g_st = g.ppm_render(params, lights)
+    g.close()
+    assert o_img.max() > 0 and np.array_equal(g_img.view(np.uint64), o_img.view(np.uint64))
+    for k in ("photons_stored", "photon_rays", "eye_rays", "neighbors", "last_radius"):
+        assert g_st[k] == o_st[k], k
+
+
 def test_ppm_rejects_bad_arguments(P, oracle):
     from path_tracer_ocaml_amd import abi
     d = oracle.desc_cornell(16, 16, 0.0)

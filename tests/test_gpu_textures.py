@@ -1,14 +1,15 @@
 """Image textures and the environment on the GPU, bit for bit.
 
 * The rule itself: ptx_texture_eval / ptx_environment_eval (the device's own evaluation functions on explicit inputs) against the
-  numpy restatement tests/texture_reference.py.
+  numpy restatement tests/texture_reference.py, up to PTX_IMAGE_MAX_SIZE texels and indices beyond 2^32.
 * Checker equivalence through the whole path: a checker of EVEN cell counts and the image whose texels repeat it (nearest, repeat on
   both axes) trace the same samples -- against the CPU oracle on the checker scene, against the GPU's own checker render, with
   PTX_FUSED=0 and under count_work with the work counters equal -- on Shirley's ground (tree in LDS, Simd_leaf), cornell's wall
   (triangles in LDS) and the floor of a mesh walked from HBM / L2.  Restoring the descriptor's texture restores the old schedule.
 * The environment: depth 1 against the restated colour of every camera ray, depth 8 against tests/c/texture_oracle.c, an all-zero
   environment against PTX_BG_BLACK.
-* Composition: the feature pass's albedo, progressive = plain, two replicas = one, sampled lighting on an image wall."""
+* Composition: the feature pass's albedo, progressive = plain, two replicas = one, sampled lighting on an image wall.
+Non-periodic images along whole paths are in test_gpu_texture_paths.py."""
 import ctypes as C
 
 import numpy as np
@@ -72,6 +73,26 @@ def test_texture_eval_is_the_rule(P, cornell, Wt, Ht):
         g.set_texture_image(index, None)
 
 
+@pytest.mark.parametrize("Wt,Ht", T.LIMIT_SIZES)
+def test_texture_eval_is_the_rule_at_the_size_limit(P, cornell, Wt, Ht):
+    """axes of up to PTX_IMAGE_MAX_SIZE texels and indices that leave 32 bits (the wrap's branch for |i| >= 2^32, whose products are
+    largest for n near 16384): both filters, all four wrap combinations.  T.limit_case asserts that the coordinates reach there."""
+    g, d = cornell
+    img, u, v = T.limit_case(Wt, Ht)
+    uv = np.stack([u, v], axis=1)
+    try:
+        for bilinear in (False, True):
+            for ru in (False, True):
+                for rv in (False, True):
+                    g.set_texture_image(4, img, bilinear=bilinear, repeat=(ru, rv))
+                    flags = (T.BILINEAR if bilinear else 0) | (T.REPEAT_U if ru else 0) | (T.REPEAT_V if rv else 0)
+                    assert g.texture_image(4) == (Wt, Ht, flags)
+                    got = g.texture_eval(4, uv)
+                    assert np.array_equal(bits(got), bits(T.image_eval(img, flags, u, v))), flags
+    finally:
+        g.set_texture_image(4, None)
+
+
 def test_texture_eval_without_an_image_is_the_descriptors_texture(P, cornell):
     g, d = cornell
     u, v = T.edge_coordinates(10, 10, np.random.default_rng(5), 2000)
@@ -114,11 +135,7 @@ def test_environment_eval_is_the_rule(P, oracle, cornell, bilinear):
 # ------------------------------------------------------------------------------------------------------------ checker equivalence
 def equivalence_case(name, oracle):
     """(descriptor with the even checker, keepalive, texture index, cells (W, H), frame width, height)"""
-    if name == "shirley":
-        return (*S.with_checker(oracle.desc_shirley(W, H), 0, 11, 21), 0, (10, 20), W, H)
-    if name == "cornell":
-        return (*S.with_checker(oracle.desc_cornell(W, H), 4, 11, 11), 4, (10, 10), W, H)
-    return (*S.with_checker(oracle.desc_ganesha_like(W, H, n_target=6000), 1, 21, 11), 1, (20, 10), W, H)
+    return S.equivalence_case(name, oracle, W, H)
 
 
 def raw_sums(P, torch, g, w, h, **kw):

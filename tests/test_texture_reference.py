@@ -1,6 +1,8 @@
 """The numpy restatement of the image rule (tests/texture_reference.py) checks itself, and the C restatement
 (tests/c/texture_oracle.c: the oracle's source included unchanged, the rule written out in C from include/ptx.h) agrees with it bit
-for bit -- on explicit coordinates, on directions, and on a depth-1 frame traced under an environment.  No GPU."""
+for bit -- on explicit coordinates (up to the size limit and indices beyond 2^32), on directions, and on a depth-1 frame traced under
+an environment.  The image-table tracer is held to the oracle where the two must agree, and the scenes and images of the GPU's
+whole-path tests (texture_support.path_case) are shown to tell each way of getting the lookup wrong from the rule.  No GPU."""
 import numpy as np
 import pytest
 
@@ -127,3 +129,140 @@ def test_depth_one_frame_under_an_environment(oracle):
     assert 0.1 < miss.mean() < 0.9
     want = np.where(miss[:, None], T.environment_eval(env, T.BILINEAR, R, dirs), 0.0)
     assert np.array_equal(S.bits(got), S.bits(want + 0.0))  # (fma(1, c, 0) = c; a hit's fma(attn, 0, 0) = +0)
+
+
+# ---------------------------------------------------------------------------------------------- the size limit (PTX_IMAGE_MAX_SIZE)
+@pytest.mark.parametrize("W,H", T.LIMIT_SIZES)
+def test_c_restatement_equals_numpy_at_the_size_limit(W, H):
+    """products up to 2^62 on axes of up to 16384 texels: long long arithmetic in C against int64 in numpy"""
+    img, u, v = T.limit_case(W, H)
+    for bilinear in (0, T.BILINEAR):
+        for wrap in WRAPS:
+            got = S.c_image_eval(img, bilinear | wrap, u, v)
+            assert np.array_equal(S.bits(got), S.bits(T.image_eval(img, bilinear | wrap, u, v))), (bilinear, wrap)
+
+
+def test_the_size_limit_coordinates_tell_repeat_from_clamp_and_a_wrong_modulus():
+    """what the case can see: beyond 2^32 a repeat axis lands on many texels (a clamp axis on the two edge ones), and an index reduced
+    modulo 2^32 first (a 32-bit wrap) lands elsewhere for an n that does not divide 2^32"""
+    W, H = 12289, 1
+    img, u, v = T.limit_case(W, H)
+    p = u * np.float64(W)
+    far = (np.abs(p) >= 2.0 ** 32) & (np.abs(p) < 2.0 ** 62)
+    ix = T._wrap(np.trunc(p[far]).astype(np.int64), W, True)
+    assert len(np.unique(ix)) > 100
+    narrow = T._wrap(np.trunc(p[far]).astype(np.int64) & 0xFFFFFFFF, W, True)
+    assert (narrow != ix).sum() > 100
+
+
+# ------------------------------------------------------------------------------------------------ whole paths with an image table
+PW, PH, PSPP, PDEPTH = S.PATH_W, S.PATH_H, S.PATH_SPP, S.PATH_DEPTH
+
+
+def plain_desc(name, oracle):
+    return {"shirley": lambda: oracle.desc_shirley(PW, PH), "cornell": lambda: oracle.desc_cornell(PW, PH),
+            "mesh": lambda: oracle.desc_ganesha_like(PW, PH, n_target=6000)}[name]()
+
+
+@pytest.mark.parametrize("name", ["shirley", "cornell", "mesh"])
+def test_no_image_and_no_environment_is_the_oracle(oracle, name):
+    d = plain_desc(name, oracle)
+    xs, ys, ps = S.all_samples(PW, PH, PSPP)
+    o = oracle.Scene(d.ptr, d)
+    want, _ = o.trace_samples(PW, PH, PSPP, PDEPTH, xs, ys, ps)
+    o.close()
+    ref = S.Restatement(d.ptr, d)
+    assert np.array_equal(S.bits(ref.trace_samples_images(None, PW, PH, PSPP, PDEPTH, xs, ys, ps)), S.bits(want))
+    # a table without an image is no table
+    none = {0: (np.zeros((0, 0, 3)), 0)}
+    assert np.array_equal(S.bits(ref.trace_samples_images(none, PW, PH, PSPP, PDEPTH, xs, ys, ps)), S.bits(want))
+    ref.close()
+
+
+@pytest.mark.parametrize("name", ["shirley", "cornell", "mesh"])
+def test_the_even_checker_image_is_the_checker_along_whole_paths(oracle, name):
+    import ctypes as C
+    d, keep, index, (cw, ch), w, h = S.equivalence_case(name, oracle)
+    ptr = C.pointer(d)
+    xs, ys, ps = S.all_samples(w, h, PSPP)
+    o = oracle.Scene(ptr, keep)
+    want, _ = o.trace_samples(w, h, PSPP, PDEPTH, xs, ys, ps)
+    o.close()
+    even, odd = S.checker_colours(d, index)
+    images = {index: (T.checker_image(cw, ch, even, odd), T.REPEAT_U | T.REPEAT_V)}
+    ref = S.Restatement(ptr, keep)
+    got = ref.trace_samples_images(images, w, h, PSPP, PDEPTH, xs, ys, ps)
+    ref.close()
+    assert np.array_equal(S.bits(got), S.bits(want))
+
+
+@pytest.mark.parametrize("name", ["shirley", "mesh"])
+def test_an_environment_alone_is_the_environment_tracer(oracle, name):
+    d = plain_desc(name, oracle)
+    env, R = S.random_environment(32, 16, 21), S.rotation([0.0, 1.0, 0.0], 75.0)
+    xs, ys, ps = S.all_samples(PW, PH, PSPP)
+    ref = S.Restatement(d.ptr, d)
+    for flags in (0, T.BILINEAR):
+        want = ref.trace_samples(env, flags, R, PW, PH, PSPP, PDEPTH, xs, ys, ps)
+        got = ref.trace_samples_images(None, PW, PH, PSPP, PDEPTH, xs, ys, ps, env=env, env_flags=flags, R=R)
+        assert np.array_equal(S.bits(got), S.bits(want)), flags
+    ref.close()
+
+
+def test_first_hit_albedo_is_the_numpy_rule_on_the_hits_own_coordinates(oracle):
+    """cornell's image set: bilinear on the floor (4) and the metal sphere (6), nearest on the ceiling (5) and a wall (3); a
+    dielectric shows (1, 1, 1), a miss the background, an entry without an image its texture"""
+    case = S.path_case("cornell", oracle)
+    d, images = case["desc"], case["images"]
+    xs, ys, ps = S.all_samples(PW, PH, PSPP)
+    ref = S.Restatement(d.ptr, d)
+    albedo, hit, tex, uv = ref.first_hits(images, PW, PH, PSPP, PDEPTH, xs, ys, ps)
+    plain, hit0, tex0, _ = ref.first_hits(None, PW, PH, PSPP, PDEPTH, xs, ys, ps)
+    ref.close()
+    assert np.array_equal(hit, hit0) and np.array_equal(tex, tex0)
+    filters = set()
+    for index, (img, flags) in images.items():
+        on = tex == index
+        assert on.sum() >= 32
+        filters.add(flags & T.BILINEAR)
+        assert np.array_equal(S.bits(albedo[on]), S.bits(T.image_eval(img, flags, uv[on, 0], uv[on, 1]))), index
+    assert filters == {0, T.BILINEAR}
+    rest = ~np.isin(tex, list(images))
+    assert np.array_equal(S.bits(albedo[rest]), S.bits(plain[rest]))
+    glass = (hit == 1) & (tex < 0)
+    assert glass.sum() > 0 and (albedo[glass] == 1.0).all()
+    assert (hit == 0).sum() > 0 and (albedo[hit == 0] == 0.0).all()  # cornell's background is black
+
+
+# The conditions under which the GPU tests of whole paths mean something: on every scene and image set they use, each way of
+# getting the lookup wrong changes the frame, and every imaged entry is seen directly.
+SENSITIVITY_CASES = [("shirley", False), ("shirley", True), ("shirley_array", False), ("cornell", False), ("mesh", True)]
+
+
+@pytest.mark.parametrize("name,with_env", SENSITIVITY_CASES)
+def test_every_mistake_changes_the_frame(oracle, name, with_env):
+    case = S.path_case(name, oracle)
+    d, images = case["desc"], case["images"]
+    env = dict(zip(("env", "env_flags", "R"), case["env"])) if with_env else {}
+    xs, ys, ps = S.all_samples(PW, PH, PSPP)
+    assert len(xs) == 8192
+    ref = S.Restatement(d.ptr, d)
+    want = ref.trace_samples_images(images, PW, PH, PSPP, PDEPTH, xs, ys, ps, **env)
+    _, _, tex, uv = ref.first_hits(images, PW, PH, PSPP, PDEPTH, xs, ys, ps, **env)
+    for index in images:
+        assert (tex == index).sum() >= 32, (index, int((tex == index).sum()))
+    if name.startswith("shirley"):  # a sphere's atan2 seam, where u reaches 0 and 1, is seen directly on an imaged entry
+        assert any(uv[tex == i, 0].min() < 0.01 and uv[tex == i, 0].max() > 0.99 for i in images)
+
+    def changed(got):
+        return int((S.bits(got) != S.bits(want)).any(axis=1).sum())
+
+    counts = {}
+    for what, mutant in S.MUTANTS.items():
+        counts[what] = changed(ref.trace_samples_images(images, PW, PH, PSPP, PDEPTH, xs, ys, ps, mutant=mutant, **env))
+    counts["texture indices swapped"] = changed(ref.trace_samples_images(S.swapped(images, *case["swap"]), PW, PH, PSPP, PDEPTH, xs, ys,
+                                                                         ps, **env))
+    ref.close()
+    print(name, "env" if with_env else "sky", counts)
+    failed = {what: n for what, n in counts.items() if n < (8 if "toggled" in what else 64)}
+    assert not failed, failed

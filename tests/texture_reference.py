@@ -104,3 +104,38 @@ def edge_coordinates(W, H, rng, n_random):
     gu, gv = np.meshgrid(au, av, indexing="ij")
     ru, rv = rng.uniform(-3.0, 3.0, n_random), rng.uniform(-3.0, 3.0, n_random)
     return np.concatenate([gu.ravel(), ru]), np.concatenate([gv.ravel(), rv])
+
+
+def limit_coordinates(n, rng):
+    """coordinates for an axis of n texels, n up to MAX_SIZE, where edge_coordinates' grid would be too large: random values in
+    [-3, 3]; the first and last texel edges with their nextafter neighbours; k 2^32 / n with its neighbours, k = 1..8, both signs
+    (where the 64-bit index leaves 32 bits); +-2^61 / n and (2^62 - 2^10) / n (the last products that still count); random values
+    with |u n| in [2^31, 2^33].  A few thousand values."""
+    def around(x):
+        x = np.asarray(x, dtype=np.float64)
+        return np.concatenate([x, np.nextafter(x, np.inf), np.nextafter(x, -np.inf)])
+    edges = around(np.array([0.0, 1.0, n - 1.0, float(n), -1.0, -(n - 1.0), -float(n), 0.5, n - 0.5]) / n)
+    k = np.arange(1.0, 9.0)
+    big = around(np.concatenate([k, -k]) * 2.0 ** 32 / n)
+    last = around(np.array([2.0 ** 61, -2.0 ** 61, 2.0 ** 62 - 2.0 ** 10, -(2.0 ** 62 - 2.0 ** 10)]) / n)
+    below = rng.uniform(2.0 ** 31, 2.0 ** 32, 600) * rng.choice([-1.0, 1.0], 600) / n
+    above = rng.uniform(2.0 ** 32, 2.0 ** 33, 600) * rng.choice([-1.0, 1.0], 600) / n
+    return np.concatenate([rng.uniform(-3.0, 3.0, 1500), edges, np.array([-0.0]), big, last, below, above])
+
+
+LIMIT_SIZES = [(16384, 1), (1, 16384), (16383, 2), (12289, 1), (4099, 3)]  # (W, H)
+
+
+def limit_case(W, H):
+    """(img, u, v) of the rule tests at the size limit: the axis coordinates of both axes, paired in a seeded shuffle, and the
+    conditions that make the case one -- from the reference's own p = u * n, on the axis that is long, at least 200 coordinates with
+    2^32 <= |p| < 2^62 and at least 200 with 2^31 <= |p| < 2^32"""
+    rng = np.random.default_rng(W * 7 + H)
+    img = rng.uniform(0.0, 4.0, (H, W, 3))
+    u, v = limit_coordinates(W, rng), limit_coordinates(H, rng)
+    assert len(u) == len(v) and len(u) < 6000
+    v = v[rng.permutation(len(v))]
+    for c, n in ((u, W), (v, H)):
+        p = np.abs(c * np.float64(n))
+        assert ((p >= 2.0 ** 32) & (p < 2.0 ** 62)).sum() >= 200 and ((p >= 2.0 ** 31) & (p < 2.0 ** 32)).sum() >= 200, (W, H, n)
+    return img, u, v
