@@ -673,6 +673,31 @@ int32_t ptx_intersect_rays(ptx_scene* scene, int64_t n, const double* origins,
                            const double* directions, double* t_out, int32_t* prim_out,
                            ptx_stats* stats);
 
+/* Diagnostic, in the family of ptx_math_eval: the walks the bounce kernels run on LDS-resident scenes -- which ptx_intersect_rays,
+ * whose kernel has its own node loop, does not -- on explicit rays.  Arguments and results as ptx_intersect_rays (prim_out = -1 and
+ * t_out = 0 on a miss).  `walk` names one walk; a walk the scene cannot take is PTX_ERR_STATE, and so is a host-only scene:
+ *   SHARED_ASM   the assembly node loop on the shared LDS image          Simd_leaf, LDS-resident
+ *   OCT_ASM      the assembly node loop on the per-octant LDS image      Simd_leaf, the per-octant image exists and a launch fits with it
+ *   SHARED_DIV   the divergent node loop on the shared LDS image         Array_leaf, LDS-resident
+ *   PACKET       the camera rays' wave-packet walk                       LDS-resident, either leaf kind
+ *   ..._ZERO     the camera launch's form of the first three: the origin is taken as (+0, +0, +0) without being read
+ *   ..._TAIL     the first three with the tail cut: a chunk of 64 rays stops once fewer than 16 are walking, and the walks it cut
+ *                short are resumed from (node, closest hit) as the bounce kernels resume their parked walks
+ * PACKET and the _ZERO walks need every origin component to have the bits of +0.0: anything else (-0.0 included) is PTX_ERR_ARG.
+ * Nothing is launched when an error is returned; n == 0 returns 0. */
+#define PTX_WALK_SHARED_ASM 0
+#define PTX_WALK_OCT_ASM 1
+#define PTX_WALK_SHARED_DIV 2
+#define PTX_WALK_PACKET 3
+#define PTX_WALK_SHARED_ASM_ZERO 4
+#define PTX_WALK_OCT_ASM_ZERO 5
+#define PTX_WALK_SHARED_DIV_ZERO 6
+#define PTX_WALK_SHARED_ASM_TAIL 7
+#define PTX_WALK_OCT_ASM_TAIL 8
+#define PTX_WALK_SHARED_DIV_TAIL 9
+int32_t ptx_walk_rays(ptx_scene* scene, int32_t walk, int64_t n, const double* origins, const double* directions,
+                      double* t_out, int32_t* prim_out);
+
 /* Replaces Progressive_photon_map.Make(Scene).go (:420-451) up to, but not including, the per-iteration
  * gamma + PNG write: img_sum_out (HOST, width*height*3, row 0 = top as Bimage stores it) receives the
  * reference's img_sum after `iterations` iterations, i.e. the sum over iterations of estimate / photon_count.

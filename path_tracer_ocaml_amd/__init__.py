@@ -41,7 +41,7 @@ EXPORTS = (
     "ptx_film_defaults", "ptx_film_weights", "ptx_scene_set_film", "ptx_scene_film", "ptx_film_resolve_ex_device",
     "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device", "ptx_tile_list_stats",
     "ptx_scene_set_texture_image", "ptx_scene_set_environment", "ptx_scene_texture_image", "ptx_scene_environment",
-    "ptx_texture_eval", "ptx_environment_eval",
+    "ptx_texture_eval", "ptx_environment_eval", "ptx_walk_rays",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -143,6 +143,8 @@ def lib():
         L.ptx_scene_environment.argtypes = [C.c_void_p, imp, dp]
         L.ptx_texture_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp]
         L.ptx_environment_eval.argtypes = [C.c_void_p, C.c_int64, dp, dp]
+    if hasattr(L, "ptx_walk_rays"):  # (likewise)
+        L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
     _LIB = L
     return L
 
@@ -544,6 +546,17 @@ class Scene:
         st = abi.Stats()
         _check(lib().ptx_intersect_rays(self._h, n, _dp(o), _dp(d), _dp(t), _ip(prim), C.byref(st)))
         return t, prim, stats_dict(st)
+
+    def walk_rays(self, walk, origins, directions):
+        """ptx_walk_rays: one of the bounce kernels' walks (abi.PTX_WALK_*) on explicit rays -> (t, prim) as intersect_rays gives
+        them.  PtxError for a walk the scene cannot take, and for a PACKET or _ZERO walk with an origin that is not +0.0."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        n = o.shape[0]
+        t = np.zeros(n)
+        prim = np.zeros(n, dtype=np.int32)
+        _check(lib().ptx_walk_rays(self._h, int(walk), n, _dp(o), _dp(d), _dp(t), _ip(prim)))
+        return t, prim
 
     def ppm_render(self, params, lights, callback=None):
         """ptx_ppm_render: Progressive_photon_map.Make(Scene).go without the gamma / PNG step -> img_sum (H, W, 3).

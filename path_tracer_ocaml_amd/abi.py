@@ -142,6 +142,10 @@ def film_params(film=None, renormalise=None):
 PTX_IMAGE_BILINEAR, PTX_IMAGE_REPEAT_U, PTX_IMAGE_REPEAT_V = 1, 2, 4
 PTX_IMAGE_MAX_SIZE = 16384
 
+# ptx_walk_rays: which of the bounce kernels' walks to run (include/ptx.h)
+(PTX_WALK_SHARED_ASM, PTX_WALK_OCT_ASM, PTX_WALK_SHARED_DIV, PTX_WALK_PACKET, PTX_WALK_SHARED_ASM_ZERO, PTX_WALK_OCT_ASM_ZERO,
+ PTX_WALK_SHARED_DIV_ZERO, PTX_WALK_SHARED_ASM_TAIL, PTX_WALK_OCT_ASM_TAIL, PTX_WALK_SHARED_DIV_TAIL) = range(10)
+
 
 class Image(C.Structure):  # ptx_image
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("rgb", c_double_p)]

@@ -3940,6 +3940,81 @@ __global__ void k_load_rays(long long n, const double* __restrict__ o, const dou
   pt_q_store_ray(q, (uint32_t)i, v3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
 }
 
+/* ptx_walk_rays: the walks of k_bounce / k_bounce_carry on LDS-resident scenes, on explicit rays.  Nothing of a walk is restated here:
+ * the workgroup builds the scene image k_bounce_carry builds (pt_scene_view: the shared image behind the stacks, or the per-octant
+ * one with LOCT) in a dynamic buffer of that kernel's size, and every wave hands 64 consecutive rays at a time to the instantiation of
+ * pt_trace_ray / pt_trace_packet the bounce kernels use -- MODE == PT_MODE_SIMD: the assembly node loops (walk_asm, LOCT: walk_asm_oct),
+ * else the divergent loop; ZERO: the camera launch's ORIGIN_ZERO forms (the origins are +0.0, the host has checked); PACKET: the
+ * camera rays' wave packet.  Same launch bounds as k_bounce_carry: the assembly loops name v120..v127.
+ * TAIL: a chunk stops where k_bounce_carry's would (PtTailCtl, min_active = PT_TAIL_CUT) and the walks it cut short go in again, with
+ * the finished lanes idle, until none is left.  In between a walk is what k_bounce_carry's parked record keeps of it (word 0 of the
+ * entry, written after its walk and read back before it: the node in 16 bits, the slot in 16 with 0xffff for none; t, and u, v on
+ * Array_leaf scenes, as they are) -- restated below, the kernel's own pool, lock and ray words are not needed for 64 lanes that
+ * keep their rays in registers. */
+template <int MODE, bool PACKET, bool LOCT, bool ZERO, bool TAIL>
+__global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_walk_eval(PtSceneDev sc, long long n, const double* __restrict__ o3,
+                                                                                    const double* __restrict__ d3, double* __restrict__ t_out,
+                                                                                    int32_t* __restrict__ slot_out, int stack_depth) {
+  extern __shared__ __attribute__((aligned(64))) unsigned char lds_raw[];
+  static_assert(!LOCT || (MODE == PT_MODE_SIMD && !PACKET), "the per-octant LDS image: Simd_leaf, no packet walk");
+  static_assert(!PACKET || (ZERO && !TAIL), "the packet walk is the camera rays': origin zero, no tail cut");
+  static_assert(!(ZERO && TAIL), "the camera launch has no tail cut");
+  typedef typename std::conditional<LOCT, PtLdsOctTag, uint16_t>::type StackT;
+  const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+  StackT* stack = LOCT ? nullptr : (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
+  PtSceneView sv = pt_scene_view<MODE, true, LOCT>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
+  const long long chunks = (n + PT_WAVE - 1) / PT_WAVE;
+  unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0; /* (not counting: the walks leave them alone) */
+  for (long long c = (long long)blockIdx.x * nw + wave; c < chunks; c += (long long)gridDim.x * nw) { /* wave-uniform */
+    const long long i = c * PT_WAVE + lane;
+    const bool valid = i < n;
+    V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0);
+    if (valid) {
+      if (!ZERO) o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]);
+      d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+    }
+    PtTraceResult r;
+    if constexpr (PACKET) {
+      r = pt_trace_packet<MODE, false, true, true>(sc, sv, (uint32_t*)stack, valid, o, d, c_nodes, c_prims, c_floor);
+    } else if constexpr (!TAIL) {
+      r = pt_trace_ray<MODE, false, ZERO, StackT, true, true, MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, valid);
+    } else {
+      bool todo = valid; /* this lane's walk is not finished */
+      PtTailCtl tc;
+      tc.min_active = PT_TAIL_CUT;
+      tc.resume = false;
+      tc.node = 0u;
+      tc.slot = -1;
+      tc.t = tc.u = tc.v = 0.0;
+      r.t = PT_MAX_FINITE;
+      r.u = r.v = 0.0;
+      r.slot = -1;
+      for (;;) {
+        tc.unfinished = false;
+        const PtTraceResult rr = pt_trace_ray<MODE, false, false, StackT, true, true, MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, c_nodes, c_prims, c_floor, todo, &tc);
+        if (todo && !tc.unfinished) {
+          r = rr;
+          todo = false;
+        }
+        if (todo) { /* k_bounce_carry: p[0] = {tc.node | slot << 16, .., t} when it parks, h.x & 0xffff / h.x >> 16 when it takes the walk up again */
+          const uint32_t w = tc.node | ((uint32_t)(rr.slot < 0 ? 0xffff : rr.slot) << 16);
+          tc.node = w & 0xffffu;
+          tc.slot = (int)(w >> 16) == 0xffff ? -1 : (int)(w >> 16);
+          tc.t = rr.t;
+          tc.u = MODE == PT_MODE_ARRAY ? rr.u : 0.0; /* (park_uv: Array_leaf scenes only) */
+          tc.v = MODE == PT_MODE_ARRAY ? rr.v : 0.0;
+        }
+        tc.resume = todo;
+        if (__ballot(todo) == 0ull) break;
+      }
+    }
+    if (valid) {
+      t_out[i] = r.t;
+      slot_out[i] = r.slot;
+    }
+  }
+}
+
 #if PT_FILTER_DEBUG
 /* Diagnostic builds only: the PRODUCTION box test of the walk from HBM / L2 (PtTraverser::begin + test_box on the tagged per-octant
  * record) on a list of (ray, node, closest hit so far) triples, and beside it the reference's binary64 quantities of the same test

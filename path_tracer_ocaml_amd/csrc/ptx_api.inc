@@ -3375,6 +3375,84 @@ int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const
   return 0;
 }
 
+namespace {
+/* k_walk_eval: 11 = on the shared image {assembly loop, divergent loop} x {plain, origin zero, tail cut}, on the per-octant image the
+ * assembly loop x the same three, and the packet walk per leaf kind.  Template arguments: <MODE, PACKET, LOCT, ZERO, TAIL>. */
+using WalkKernel = decltype(&k_walk_eval<PT_MODE_SIMD, false, false, false, false>);
+WalkKernel walk_kernel(int walk, int mode) {
+  switch (walk) {
+    case PTX_WALK_SHARED_ASM: return k_walk_eval<PT_MODE_SIMD, false, false, false, false>;
+    case PTX_WALK_SHARED_ASM_ZERO: return k_walk_eval<PT_MODE_SIMD, false, false, true, false>;
+    case PTX_WALK_SHARED_ASM_TAIL: return k_walk_eval<PT_MODE_SIMD, false, false, false, true>;
+    case PTX_WALK_OCT_ASM: return k_walk_eval<PT_MODE_SIMD, false, true, false, false>;
+    case PTX_WALK_OCT_ASM_ZERO: return k_walk_eval<PT_MODE_SIMD, false, true, true, false>;
+    case PTX_WALK_OCT_ASM_TAIL: return k_walk_eval<PT_MODE_SIMD, false, true, false, true>;
+    case PTX_WALK_SHARED_DIV: return k_walk_eval<PT_MODE_ARRAY, false, false, false, false>;
+    case PTX_WALK_SHARED_DIV_ZERO: return k_walk_eval<PT_MODE_ARRAY, false, false, true, false>;
+    case PTX_WALK_SHARED_DIV_TAIL: return k_walk_eval<PT_MODE_ARRAY, false, false, false, true>;
+    case PTX_WALK_PACKET: return mode == PT_MODE_SIMD ? k_walk_eval<PT_MODE_SIMD, true, false, true, false> : k_walk_eval<PT_MODE_ARRAY, true, false, true, false>;
+    default: return nullptr;
+  }
+}
+}  // namespace
+
+int32_t ptx_walk_rays(ptx_scene* s, int32_t walk, int64_t n, const double* origins, const double* directions, double* t_out,
+                      int32_t* prim_out) {
+  if (!s || !origins || !directions || !t_out || !prim_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (walk < 0 || walk > PTX_WALK_SHARED_DIV_TAIL) return fail(PTX_ERR_ARG, "unknown walk %d", walk);
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad ray count");
+  HIP_TRY(hipSetDevice(s->device));
+  reschedule(s, 1);
+  const Schedule& sc = s->sched;
+  /* what the scene can take: the bounce kernels' own conditions (make_schedule), less the knobs that choose between possible walks */
+  const bool simd = s->dev.mode == PT_MODE_SIMD;
+  const bool oct = walk == PTX_WALK_OCT_ASM || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_OCT_ASM_TAIL;
+  const bool asm_shared = walk == PTX_WALK_SHARED_ASM || walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_SHARED_ASM_TAIL;
+  const bool div = walk == PTX_WALK_SHARED_DIV || walk == PTX_WALK_SHARED_DIV_ZERO || walk == PTX_WALK_SHARED_DIV_TAIL;
+  const bool zero = walk == PTX_WALK_PACKET || walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_SHARED_DIV_ZERO;
+  if (!sc.in_lds() || sc.from_hbm) return fail(PTX_ERR_STATE, "walk %d: the scene is walked from HBM / L2, these walks run on LDS-resident scenes", walk);
+  if ((oct || asm_shared) && !simd) return fail(PTX_ERR_STATE, "walk %d is a Simd_leaf walk and the scene is Array_leaf", walk);
+  if (div && simd) return fail(PTX_ERR_STATE, "walk %d is the Array_leaf walk and the scene is Simd_leaf", walk);
+  if (oct && (s->dev.lds_oct == nullptr || !sc.carry_oct.fits)) return fail(PTX_ERR_STATE, "walk %d: the scene has no per-octant LDS image, or a launch does not fit with it", walk);
+  if (!oct && !sc.carry.fits) return fail(PTX_ERR_STATE, "walk %d: a launch of the bounce kernel does not fit LDS with the scene's image", walk);
+  if (sc.bounce_threads > PT_BOUNCE_THREADS) return fail(PTX_ERR_STATE, "walk %d: workgroups of %d threads", walk, sc.bounce_threads);
+  if (zero) {
+    const double pz = 0.0;
+    for (int64_t k = 0; k < 3 * n; ++k)
+      if (std::memcmp(&origins[k], &pz, sizeof pz) != 0)
+        return fail(PTX_ERR_ARG, "walk %d takes the origin as (+0, +0, +0): component %lld of the origins is %a", walk, (long long)k, origins[k]);
+  }
+  if (n == 0) return 0;
+  LocalBuf<double> d_o, d_d, d_t;
+  LocalBuf<int32_t> d_s;
+  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3)); HIP_TRY(d_t.ensure((size_t)n)); HIP_TRY(d_s.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  const WalkKernel kern = walk_kernel(walk, s->dev.mode);
+  /* k_bounce_carry's launch: its workgroup, its dynamic LDS for this image, one workgroup (one scene image) per CU */
+  prepare_kernel(s, (const void*)kern, "k_walk_eval", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
+  const int threads = sc.bounce_threads;
+  const int grid = strided_grid(s, (size_t)n, threads, 1);
+  const int stack_depth = std::max(1, s->tree_depth + 1);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, nullptr, s->dev, (long long)n, d_o.p, d_d.p, d_t.p, d_s.p, stack_depth);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int32_t> slot((size_t)n);
+  HIP_TRY(hipMemcpy(t_out, d_t.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slot.data(), d_s.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    const int sl = slot[(size_t)i];
+    if (sl < 0) {
+      prim_out[i] = -1;
+      t_out[i] = 0.0;
+    } else {
+      prim_out[i] = s->host->slot_prim[(size_t)sl];
+    }
+  }
+  return 0;
+}
+
 int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, int32_t node_capacity,
                        int32_t* prim_order_out, int32_t slot_capacity) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");

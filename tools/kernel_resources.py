@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / scratch usage of every kernel in kernels.hip as hipcc reports it (-Rpass-analysis=kernel-resource-usage).
-usage: tools/kernel_resources.py [extra hipcc flags]  -> table: VGPRs, VGPR spills, scratch B/lane, SGPR spills, occupancy, LDS"""
+usage: tools/kernel_resources.py [extra hipcc flags]  -> table: VGPRs, SGPRs, VGPR spills, scratch B/lane, SGPR spills, occupancy, LDS"""
 import os
 import re
 import subprocess
@@ -27,9 +27,9 @@ for line in out.splitlines():
 if cur:
     rows.append(cur)
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.splitlines()
-print("%5s %6s %7s %6s %3s %6s  kernel" % ("VGPR", "vspill", "scratch", "sspill", "occ", "LDS"))
+print("%5s %5s %6s %7s %6s %3s %6s  kernel" % ("VGPR", "SGPR", "vspill", "scratch", "sspill", "occ", "LDS"))
 for r, n in zip(rows, names):
     n = re.sub(r"^void ", "", n)
     n = re.sub(r"\(.*$", "", n)
-    print("%5s %6s %7s %6s %3s %6s  %s" % (r.get("VGPRs", "?"), r.get("VGPRs Spill", "?"), r.get("ScratchSize [bytes/lane]", "?"),
+    print("%5s %5s %6s %7s %6s %3s %6s  %s" % (r.get("VGPRs", "?"), r.get("TotalSGPRs", "?"), r.get("VGPRs Spill", "?"), r.get("ScratchSize [bytes/lane]", "?"),
                                           r.get("SGPRs Spill", "?"), r.get("Occupancy [waves/SIMD]", "?"), r.get("LDS Size [bytes/block]", "?"), n))
