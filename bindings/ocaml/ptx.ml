@@ -225,6 +225,20 @@ let set_environment ?(bilinear = true) ?rotation scene ~width ~height texels =
 
 let clear_environment scene = set_environment_raw scene (0, 0, 0) (no_texels ()) (no_texels ())
 
+(* Importance-sampling the environment (ptx_scene_set_environment_sampling; the rule is in include/ptx.h): with [Sampled] lighting a
+   Diffuse scatter also draws directions from the environment image, in proportion to luminance x sin theta per texel, and [Sampled]
+   then accepts a scene without emissive triangles.  Needs an environment whose rotation is orthonormal and whose total weight is
+   positive.  Sticky.  Failure when a condition fails, when turning it off would leave [Sampled] nothing to sample, or while a render
+   runs on the scene.  environment_sampling: (on, the density's total weight). *)
+external set_environment_sampling_int : scene -> int -> unit = "ptx_ml_set_environment_sampling_stub"
+external environment_sampling_raw : scene -> int * float = "ptx_ml_environment_sampling_stub"
+
+let set_environment_sampling scene on = set_environment_sampling_int scene (if on then 1 else 0)
+
+let environment_sampling scene =
+  let on, total = environment_sampling_raw scene in
+  on <> 0, total
+
 external render_flat
   :  scene
   -> int (* width *)

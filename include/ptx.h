@@ -280,6 +280,8 @@ int32_t ptx_tile_list_stats(const ptx_scene* scene, int64_t out[5]);
  *               this mode is set: the tree triangles whose material has a non-zero emit, in build-list order.  Emissive spheres and
  *               floor triangles are not sampled (they still emit when hit; the cosine half keeps the estimator unbiased).
  *               PTX_ERR_ARG when the scene has no emissive tree triangle or more than PTX_MAX_LIGHT_TRIANGLES of them.
+ *               (With ptx_scene_set_environment_sampling on, a scene without emissive tree triangles is accepted and the environment is
+ *               sampled too: see there.)
  * A host-only scene accepts the call (the light list can be inspected without a GPU).  PTX_ERR_STATE while a render runs on the
  * scene (from a progress or update callback); PTX_ERR_ARG for an unknown mode. */
 #define PTX_LIGHTING_REFERENCE 0
@@ -630,9 +632,8 @@ int32_t ptx_film_resolve_counts_ex_device(int32_t device, int32_t width, int32_t
  * device (frames queued with PTX_RENDER_ASYNC have finished when it returns).
  * A scene with an image or an environment takes the walk-first kernels' image instantiations: no shade-first
  * order, no per-octant LDS image, no camera tile lists.
- * Out of scope: importance-sampling the environment (PTX_LIGHTING_SAMPLED keeps sampling emissive triangles only; the environment
- * is found by scattering), mip maps and anisotropic filtering, 8-bit or binary32 texels, image decoders other than the hosts' PFM
- * reader, image-driven emission, roughness or normals. */
+ * Out of scope: mip maps and anisotropic filtering, 8-bit or binary32 texels, image decoders other than the hosts' PFM reader,
+ * image-driven emission, roughness or normals.  (Importance-sampling the environment: ptx_scene_set_environment_sampling below.) */
 #define PTX_IMAGE_BILINEAR 1
 #define PTX_IMAGE_REPEAT_U 2
 #define PTX_IMAGE_REPEAT_V 4
@@ -656,6 +657,64 @@ int32_t ptx_scene_environment(const ptx_scene* scene, ptx_image* out, double R_o
  * ptx_environment_eval without an environment evaluates the descriptor's background. */
 int32_t ptx_texture_eval(ptx_scene* scene, int32_t texture_index, int64_t n, const double* uv, double* rgb_out);
 int32_t ptx_environment_eval(ptx_scene* scene, int64_t n, const double* dirs, double* rgb_out);
+
+/* ---- importance-sampling the environment in PTX_LIGHTING_SAMPLED ----
+ * Integrator.create ~diffuse_plus_light (integrator.ml:48-66) with a light density over the environment image: a sky whose sun covers
+ * a few texels is found by sampling it, not by scattering alone.  Only entry points are added; the ABI version stays 6.
+ *
+ * ptx_scene_set_environment_sampling(scene, on): sticky state of the handle, default off; the replicas a scene owns follow it and
+ * ptx_scene_replicate copies it; a host-only scene accepts it.  Turning it on builds the density below and needs
+ *   an environment (ptx_scene_set_environment with an image),
+ *   a matrix R with max |R R^T - I| <= 1e-9 (row-major products, (R[3i] R[3j] + R[3i+1] R[3j+1]) + R[3i+2] R[3j+2]): the density
+ *     assumes a rotation,
+ *   a total weight T that is finite and greater than 0;
+ * anything else is PTX_ERR_ARG with a message that names the rule, and nothing changes.  PTX_ERR_STATE while a render runs on the scene.
+ * While it is on: ptx_scene_set_lighting(PTX_LIGHTING_SAMPLED) also accepts a scene without emissive tree triangles (the light half is
+ * then the environment alone); ptx_scene_set_environment with a new image or R rebuilds the density, and refuses (the old state kept)
+ * an image or R that fails the conditions above; clearing the environment (NULL) is PTX_ERR_STATE, "turn environment sampling off
+ * first"; turning sampling off while the mode is PTX_LIGHTING_SAMPLED and the light list is empty is PTX_ERR_STATE likewise ("set another
+ * lighting mode first").  In modes 0 and 1 the flag has no effect on a pixel.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction; sin, cos, atan2, acos are pt_math.h's), W x H the image:
+ *   The density (built on the host), texel (ix, iy) = (r, g, b):
+ *     lum = (r + g) + b, taken as 0.0 unless lum > 0;   s_iy = sin(pi * (((double)iy + 0.5) / (double)H));   w(ix, iy) = lum * s_iy
+ *     c_iy[ix] = c_iy[ix - 1] + w(ix, iy) from 0.0, left to right;  r_iy = c_iy[W - 1]
+ *     m[iy] = m[iy - 1] + r_iy from 0.0, top to bottom;              T = m[H - 1]
+ *   Sample, from (a, b) in [0, 1)^2:
+ *     x = a * T;  iy = the first row with x < m[iy], or the last row with r_iy > 0 if there is none
+ *     fy = min((x - (iy > 0 ? m[iy - 1] : 0.0)) / r_iy, 1.0)
+ *     y = b * r_iy;  ix = the first column with y < c_iy[ix], or the last column of the row with w > 0 if there is none
+ *     fx = min((y - (ix > 0 ? c_iy[ix - 1] : 0.0)) / w(ix, iy), 1.0)
+ *     u = ((double)ix + fx) / (double)W;  v = ((double)iy + fy) / (double)H
+ *     al = u * (2.0 * pi) - pi;  th = v * pi;  (sa, ca) = sincos(al);  (st, ct) = sincos(th)
+ *     m = (st * ca, -ct, -(st * sa));  d_k = (R[k] * m.x + R[3 + k] * m.y) + R[6 + k] * m.z, k = 0, 1, 2 (R^T m);  direction = normalize(d)
+ *     (both searches are binary searches whose result is the linear "first with" above: m and c_iy never decrease)
+ *   Density of a direction w (per solid angle):
+ *     e = normalize(w);  m = R e, u, v as in the environment rule above
+ *     ix = min((long long)(u * (double)W), W - 1), iy = min((long long)(v * (double)H), H - 1), either taken as 0 when the product is NaN
+ *     st = sin(v * pi);  pd = st > 0 ? ((w(ix, iy) / T) * ((double)W * (double)H)) / ((2.0 * (pi * pi)) * st) : 0.0
+ *     -- piecewise constant per texel whatever PTX_IMAGE_BILINEAR says: the cosine half keeps the estimator unbiased.
+ *   The mixture, at a Diffuse scatter in PTX_LIGHTING_SAMPLED with sampling on, (su, sv) the hit's two sampler dimensions:
+ *     with light triangles:  su < 0.25         the triangle rule with its 2u := 4.0 * su
+ *                            0.25 <= su < 0.5  the environment on (4.0 * su - 1.0, sv)
+ *                            otherwise         the cosine half on (2.0 * su - 1.0, sv)
+ *                            divisor = (0.5 * diffuse_pd + 0.25 * light_pd) + 0.25 * env_pd
+ *     environment only:      su < 0.5 the environment on (2.0 * su, sv), otherwise the cosine half;
+ *                            divisor = 0.5 * diffuse_pd + 0.5 * env_pd
+ *     The environment direction is rotated into shader space and back exactly as the triangle direction is; env_pd is evaluated for
+ *     the world direction the scattered ray will have.  Everything else of PTX_LIGHTING_SAMPLED, where a path ends included, is unchanged.
+ * What it does not help: an environment behind glass or seen in a mirror (specular scatters do not sample), emissive spheres, and the
+ * bilinear interpolant's departure from the per-texel density (variance only).  No shadow rays, no multiple importance sampling. */
+int32_t ptx_scene_set_environment_sampling(ptx_scene* scene, int32_t on);
+/* The flag and, while it is on, the total weight T (0.0 while off).  Either out pointer may be NULL. */
+int32_t ptx_scene_environment_sampling(const ptx_scene* scene, int32_t* on_out, double* total_out);
+/* Host-only inspection of the density (needs sampling on; works on a host-only scene): marginal_out (nullable) H doubles m[iy],
+ * conditional_out (nullable) H x W doubles c_iy[ix], row-major.  PTX_ERR_STATE while sampling is off. */
+int32_t ptx_environment_distribution(const ptx_scene* scene, double* marginal_out, double* conditional_out);
+/* Diagnostics, in the family of ptx_environment_eval: the shade step's own two device functions on explicit HOST inputs (sampling must
+ * be on).  ab: n x 2 -> dirs_out: n x 3 and texel_out (nullable): n x 2 {ix, iy} as drawn;  dirs: n x 3 -> pd_out: n. */
+int32_t ptx_environment_sample(ptx_scene* scene, int64_t n, const double* ab, double* dirs_out, int32_t* texel_out);
+int32_t ptx_environment_pdf(ptx_scene* scene, int64_t n, const double* dirs, double* pd_out);
 
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.

@@ -42,6 +42,8 @@ EXPORTS = (
     "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device", "ptx_tile_list_stats",
     "ptx_scene_set_texture_image", "ptx_scene_set_environment", "ptx_scene_texture_image", "ptx_scene_environment",
     "ptx_texture_eval", "ptx_environment_eval", "ptx_walk_rays",
+    "ptx_scene_set_environment_sampling", "ptx_scene_environment_sampling", "ptx_environment_distribution",
+    "ptx_environment_sample", "ptx_environment_pdf",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -143,6 +145,12 @@ def lib():
         L.ptx_scene_environment.argtypes = [C.c_void_p, imp, dp]
         L.ptx_texture_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp]
         L.ptx_environment_eval.argtypes = [C.c_void_p, C.c_int64, dp, dp]
+    if hasattr(L, "ptx_scene_set_environment_sampling"):  # (likewise)
+        L.ptx_scene_set_environment_sampling.argtypes = [C.c_void_p, C.c_int32]
+        L.ptx_scene_environment_sampling.argtypes = [C.c_void_p, ip, dp]
+        L.ptx_environment_distribution.argtypes = [C.c_void_p, dp, dp]
+        L.ptx_environment_sample.argtypes = [C.c_void_p, C.c_int64, dp, dp, ip]
+        L.ptx_environment_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp]
     if hasattr(L, "ptx_walk_rays"):  # (likewise)
         L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
     _LIB = L
@@ -287,6 +295,45 @@ class Scene:
         rot = np.zeros(9)
         _check(lib().ptx_scene_environment(self._h, C.byref(out), _dp(rot)))
         return ((out.width, out.height, out.flags), rot.reshape(3, 3)) if out.width else None
+
+    def set_environment_sampling(self, on=True):
+        """ptx_scene_set_environment_sampling: in "sampled" lighting a Diffuse scatter also draws directions from the environment
+        image, in proportion to luminance x sin(theta) per texel (and "sampled" then accepts a scene without emissive triangles).
+        Needs an environment whose rotation is orthonormal and whose total weight is positive.  Sticky."""
+        _check(lib().ptx_scene_set_environment_sampling(self._h, 1 if on else 0))
+
+    def environment_sampling(self):
+        """ptx_scene_environment_sampling: (on, the density's total weight T; 0.0 while off)"""
+        on = C.c_int32(0)
+        total = C.c_double(0.0)
+        _check(lib().ptx_scene_environment_sampling(self._h, C.byref(on), C.byref(total)))
+        return bool(on.value), total.value
+
+    def environment_distribution(self):
+        """ptx_environment_distribution (host only, sampling must be on): (the running sums of the rows m (H,), the running sums
+        inside every row c (H, W))"""
+        env = self.environment()
+        if env is None:
+            raise PtxError("environment_distribution: the scene has no environment")
+        w, h = env[0][0], env[0][1]
+        m, c = np.zeros(h), np.zeros((h, w))
+        _check(lib().ptx_environment_distribution(self._h, _dp(m), _dp(c)))
+        return m, c
+
+    def environment_sample(self, ab):
+        """ptx_environment_sample: the device's own sampling function on the (n, 2) pairs ab -> (unit directions (n, 3), the texels
+        drawn (n, 2) as (ix, iy))"""
+        ab = np.ascontiguousarray(ab, dtype=np.float64).reshape(-1, 2)
+        dirs, texel = np.zeros((len(ab), 3)), np.zeros((len(ab), 2), dtype=np.int32)
+        _check(lib().ptx_environment_sample(self._h, len(ab), _dp(ab), _dp(dirs), _ip(texel)))
+        return dirs, texel
+
+    def environment_pdf(self, directions):
+        """ptx_environment_pdf: the density per solid angle with which environment sampling draws each of the (n, 3) directions"""
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(len(d))
+        _check(lib().ptx_environment_pdf(self._h, len(d), _dp(d), _dp(out)))
+        return out
 
     def texture_eval(self, index, uv):
         """ptx_texture_eval: entry `index` of the texture table (its image, or its solid / checker texture) evaluated on the device

@@ -2225,13 +2225,92 @@ __device__ __forceinline__ double pt_light_pd(const PtSceneDev& sc, V3 p, V3 w) 
   return pd;
 }
 
+/* ------------------------------------------------------------------ environment sampling (ptx_scene_set_environment_sampling;
+ * include/ptx.h states the rule, DESIGN.md section 7 the mixture).  The table lies behind the environment's texels: PT_ENVD_* of
+ * pt_scene.h; its two scalars (T, the last row) are read through the constant address space, at a wave-uniform address: scalar loads.
+ * Pdf.sample of the environment half: a texel drawn with probability w / T, a point uniform inside it, the world-space unit direction
+ * that the environment rule maps there.  Two binary searches, log2 H + log2 W dependent loads a lane: the row sums are one small table
+ * every lane reads (H doubles: L1 / L2 resident), the row's running sums are the lane's own.  Each search ends at the first entry above
+ * the target, as the linear scan of the rule does (the sums never decrease).  What a search's result decides -- the sum before it, the
+ * row's total, the texel's weight -- is requested in one round behind it.  Every index is in range whatever (a, b) are: a target that
+ * no entry exceeds (a NaN included) takes the row or column the host found. */
+__device__ __forceinline__ const double* pt_env_table(const PtSceneDev& sc) {
+  return sc.env + 4 * ((size_t)sc.env_w * (size_t)sc.env_h);
+}
+__device__ __forceinline__ V3 pt_env_sample(const PtSceneDev& sc, double a, double b, int* ix_out, int* iy_out) {
+  const double pi = 3.14159265358979323846;
+  const int W = sc.env_w, H = sc.env_h;
+  const double* __restrict__ table = pt_env_table(sc);
+  const double* __restrict__ m = table + PT_ENVD_ROWS;
+  const double total = ((const PtConstDouble*)table)[PT_ENVD_TOTAL];
+  const int last_row = (int)((const PtConstDouble*)table)[PT_ENVD_LAST_ROW];
+  const double x = a * total;
+  int lo = 0, hi = H;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (x < m[mid]) hi = mid;
+    else lo = mid + 1;
+  }
+  const int iy = lo < H ? lo : last_row;
+  const double* __restrict__ c = table + PT_ENVD_COND(H) + (size_t)iy * (size_t)W;
+  const double before_y = m[iy > 0 ? iy - 1 : 0], r = c[W - 1], last_x = table[PT_ENVD_LASTX(H) + (size_t)iy];
+  const double fy = pt_base_min((x - (iy > 0 ? before_y : 0.0)) / r, 1.0);
+  const double y = b * r;
+  lo = 0;
+  hi = W;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (y < c[mid]) hi = mid;
+    else lo = mid + 1;
+  }
+  const int ix = lo < W ? lo : (int)last_x;
+  const double before_x = c[ix > 0 ? ix - 1 : 0], wt = c[(size_t)W * (size_t)H + (size_t)ix]; /* (the weights lie W x H behind the sums) */
+  const double fx = pt_base_min((y - (ix > 0 ? before_x : 0.0)) / wt, 1.0);
+  *ix_out = ix;
+  *iy_out = iy;
+  const double u = ((double)ix + fx) / (double)W, v = ((double)iy + fy) / (double)H;
+  const double al = u * (2.0 * pi) - pi, th = v * pi;
+  double sa, ca, st, ct;
+  pt_sincos(al, &sa, &ca);
+  pt_sincos(th, &st, &ct);
+  const V3 mm = v3(st * ca, -ct, -(st * sa));
+  const double* R = sc.env_rot;
+  return v3_normalize(v3((R[0] * mm.x + R[3] * mm.y) + R[6] * mm.z, (R[1] * mm.x + R[4] * mm.y) + R[7] * mm.z,
+                         (R[2] * mm.x + R[5] * mm.y) + R[8] * mm.z));
+}
+/* Pdf.eval of the environment half for the world direction w: the texel the environment rule's tex coords fall in (nearest, whatever
+ * the image's filter), its share w / T of the draws over its solid angle (2 pi / W) (pi / H) sin(theta).  One load, its address known
+ * once the tex coords are. */
+__device__ __forceinline__ double pt_env_pd(const PtSceneDev& sc, V3 w) {
+  const double pi = 3.14159265358979323846;
+  const int W = sc.env_w, H = sc.env_h;
+  const double* __restrict__ table = pt_env_table(sc);
+  const double total = ((const PtConstDouble*)table)[PT_ENVD_TOTAL];
+  /* (u, v) of the environment rule, as pt_environment computes them */
+  const V3 e = v3_normalize(w);
+  const double* R = sc.env_rot;
+  const double mx = (R[0] * e.x + R[1] * e.y) + R[2] * e.z;
+  const double my = (R[3] * e.x + R[4] * e.y) + R[5] * e.z;
+  const double mz = (R[6] * e.x + R[7] * e.y) + R[8] * e.z;
+  const double one_over_pi = 1.0 / pi, one_over_two_pi = 1.0 / (2.0 * pi);
+  const double cy = my < -1.0 ? -1.0 : (my > 1.0 ? 1.0 : my);
+  const double u = (pi + pt_atan2(-mz, mx)) * one_over_two_pi;
+  const double v = pt_acos(-cy) * one_over_pi;
+  const int ix = pt_image_wrap(__builtin_trunc(pt_image_scale(u, W)), W, false), iy = pt_image_wrap(__builtin_trunc(pt_image_scale(v, H)), H, false);
+  const double wt = table[PT_ENVD_WEIGHT(W, H) + (size_t)iy * (size_t)W + (size_t)ix];
+  const double st = pt_sin(v * pi);
+  return st > 0.0 ? ((wt / total) * ((double)W * (double)H)) / ((2.0 * (pi * pi)) * st) : 0.0;
+}
+
 /* The body of `loop` in Integrator.path_tracer (integrator.ml:30-66) for entry i of the queue (PRIMARY: virtual
  * entry i = a camera sample).  CAT = the entry's shading category if the kernel is specialised for one.
  * LIT (emissive scenes in lighting modes 1 and 2 only; mode 0 never launches it): emission is summed in path order,
  * emit0' = fma(attn0, emit, emit0), and in mode 2 (a wave-uniform branch) a Diffuse scatter samples and divides by
  * diffuse_plus_light = 1/2 cosine + 1/2 emissive triangles.
  * IMG (scenes with an image texture or an environment only; no other scene launches it): pt_texture_eval's image arm and
- * pt_background's environment arm. */
+ * pt_background's environment arm.
+ * LIT && IMG, in mode 2 with PtSceneDev.env_sample (wave-uniform as well): the light half is shared with, or is, the environment's
+ * density (include/ptx.h, ptx_scene_set_environment_sampling). */
 template <bool EMIT, bool PRIMARY, int CAT, bool LIT = false, bool IMG = false>
 __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQueue& q, const PtHits& hits, const PtContrib& contrib,
                                                const double* __restrict__ alpha, int bounce, int last_bounce,
@@ -2315,9 +2394,16 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
             /* Pdf.sample / Pdf.eval (pdf.ml:5-15, shader_space.ml:56-64) */
             /* mode 2: Pdf.sample diffuse_plus_light -- u < 0.5 the light half, else the cosine half on (2u - 1, v) */
             const bool sampled = LIT && sc.lighting == PT_LIGHTING_SAMPLED; /* (wave-uniform) */
+            /* ... with environment sampling: su < 0.25 the triangles on 2u := 4 su, su < 0.5 the environment on (4 su - 1, v); without
+             * light triangles su < 0.5 the environment on (2 su, v) (both wave-uniform) */
+            const bool env_on = LIT && IMG && sampled && sc.env_sample != 0;
+            const bool tri_on = sampled && !(env_on && sc.n_lights == 0);
             const double hu = sampled ? 2.0 * su - 1.0 : su;
-            if (sampled && su < 0.5) {
-              wo = pt_quat_transform(sf.rot, pt_light_sample(sc, point, su, sv)); /* Pdf.sample returns a shader-space direction */
+            if (tri_on && su < (env_on ? 0.25 : 0.5)) {
+              wo = pt_quat_transform(sf.rot, pt_light_sample(sc, point, env_on ? 2.0 * su : su, sv)); /* Pdf.sample returns a shader-space direction */
+            } else if (env_on && su < 0.5) {
+              int tx, ty;
+              wo = pt_quat_transform(sf.rot, pt_env_sample(sc, tri_on ? 4.0 * su - 1.0 : 2.0 * su, sv, &tx, &ty));
             } else {
               const double r = pt_sqrt_nonneg(hu);
               const double theta = sv * 2.0 * pi;
@@ -2330,7 +2416,13 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
               scatter_ok = false;
             } else {
               double divisor = diffuse_pd; /* modes 0 and 1: divisor = Pdf.eval diffuse_plus_light = the same */
-              if (sampled) divisor = 0.5 * diffuse_pd + 0.5 * pt_light_pd(sc, point, pt_quat_transform(rot_inv, wo));
+              if (sampled && !env_on) divisor = 0.5 * diffuse_pd + 0.5 * pt_light_pd(sc, point, pt_quat_transform(rot_inv, wo));
+              if (env_on) {
+                const V3 wdir = pt_quat_transform(rot_inv, wo); /* the direction world_ray will trace */
+                const double env_pd = pt_env_pd(sc, wdir);
+                if (tri_on) divisor = (0.5 * diffuse_pd + 0.25 * pt_light_pd(sc, point, wdir)) + 0.25 * env_pd;
+                else divisor = 0.5 * diffuse_pd + 0.5 * env_pd;
+              }
               const double pd = diffuse_pd / divisor;
               if (!pt_isfinite(pd)) scatter_ok = false;
               else attenuation = v3_scale(attenuation, pd);
@@ -3931,6 +4023,25 @@ __global__ void k_environment_eval(PtSceneDev sc, long long n, const double* __r
   out[3 * i] = c.x;
   out[3 * i + 1] = c.y;
   out[3 * i + 2] = c.z;
+}
+/* ptx_environment_sample / ptx_environment_pdf: the shade step's two environment-sampling functions on explicit inputs */
+__global__ void k_environment_sample(PtSceneDev sc, long long n, const double* __restrict__ ab, double* __restrict__ dirs, int32_t* __restrict__ texel) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int ix, iy;
+  const V3 d = pt_env_sample(sc, ab[2 * i], ab[2 * i + 1], &ix, &iy);
+  dirs[3 * i] = d.x;
+  dirs[3 * i + 1] = d.y;
+  dirs[3 * i + 2] = d.z;
+  if (texel) {
+    texel[2 * i] = ix;
+    texel[2 * i + 1] = iy;
+  }
+}
+__global__ void k_environment_pdf(PtSceneDev sc, long long n, const double* __restrict__ dirs, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = pt_env_pd(sc, v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
 }
 
 /* copies explicit rays into a queue (ptx_intersect_rays) */

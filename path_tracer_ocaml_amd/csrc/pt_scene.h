@@ -182,7 +182,10 @@ struct PtSceneDev {
   float pad_f;
   double cam_llx, cam_lly, cam_vx, cam_vy;
   int32_t bg_kind;
-  int32_t pad0;
+  union { /* (one word, two names: scenes without environment sampling, and everything that only copies the struct, see padding) */
+    int32_t pad0;
+    int32_t env_sample; /* ptx_scene_set_environment_sampling is on: the density table lies behind the environment's texels (PT_ENVD_* below) */
+  };
   double bg_horizon[3];
   double bg_zenith[3];
   /* The lighting mode in effect (PTX_LIGHTING_*; ptx_scene_set_lighting) and, in mode 2, the light table: n_lights records of
@@ -208,6 +211,21 @@ struct PtSceneDev {
   int32_t n_images;
   double env_rot[9];
 };
+/* ptx_scene_set_environment_sampling keeps PtSceneDev as it is (its size is every kernel's argument layout): env_sample takes the place of
+ * a padding word, and while it is set the density table lies in the environment's own buffer, right behind the W x H texel records
+ * (env + 4 W H doubles).  env_sample is read only by the LIT && IMG instantiations, in lighting mode 2 (a wave-uniform branch,
+ * pt_shade_entry); a scene with it on and no emitter still has has_emit = 1: it is scheduled as a lit scene, with the queue's emission
+ * record, which then stays zero.
+ * The density table (scene_host.h, PtEnvDensity), offsets in doubles for a W x H image: the total weight T and the last row with a
+ * positive weight (as a double); the running sums of the rows m[H]; per row the last column with w > 0 [H] (as doubles); the running
+ * sums inside the rows c[H x W]; the weights w[H x W] */
+#define PT_ENVD_TOTAL 0
+#define PT_ENVD_LAST_ROW 1
+#define PT_ENVD_ROWS 2
+#define PT_ENVD_LASTX(H) (2 + (size_t)(H))
+#define PT_ENVD_COND(H) (2 + 2 * (size_t)(H))
+#define PT_ENVD_WEIGHT(W, H) (2 + 2 * (size_t)(H) + (size_t)(W) * (size_t)(H))
+#define PT_ENVD_SIZE(W, H) (2 + 2 * (size_t)(H) + 2 * (size_t)(W) * (size_t)(H))
 #define PT_TILE_WALK 0xffu /* a record's count byte: the tile's rays walk the tree */
 
 #define PT_LIGHTING_SAMPLED 2 /* = PTX_LIGHTING_SAMPLED */

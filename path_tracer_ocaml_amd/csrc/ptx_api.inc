@@ -325,6 +325,10 @@ struct ptx_scene {
   std::vector<std::unique_ptr<ImageSlot>> images; /* one per texture entry once any was set; host == nullptr: none */
   ImageSlot env;
   double env_rot[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  /* Environment sampling (ptx_scene_set_environment_sampling): the flag; while it is on the density of env.host (shared with the
+   * replicas), and env.dev holds its table behind the texels (pt_scene.h, PT_ENVD_*) */
+  bool env_sampling = false;
+  std::shared_ptr<const PtEnvDensity> env_density;
   DevBuf<uint8_t> slot_cat_img;
   DevBuf<PtShadeRec> slot_shade_img;
   std::atomic<int> busy{0};
@@ -1852,29 +1856,41 @@ void ptx_scene_destroy(ptx_scene* s) {
   delete s;
 }
 
+/* The one place that writes what the kernels read of the lighting state -- PtSceneDev.lighting, the light table, env_sample and the
+ * density, has_emit -- from the handle's own (lighting, light_table, env_sampling, env_density), then reschedules.  A scene in mode 2
+ * with environment sampling on is a lit scene whether or not anything in it emits: has_emit = 1 gives it the queue's emission record
+ * (which stays zero without emitters), and Schedule::lit and every size taken from has_emit follow from the same field. */
+static void apply_lighting(ptx_scene* s) {
+  if (s->device < 0) return;
+  const int mode = s->lighting;
+  const bool sampled = mode == PTX_LIGHTING_SAMPLED, env_on = s->env_sampling && s->env_density && s->env.dev.p;
+  s->dev.has_emit = (s->host->dev.has_emit || (sampled && env_on)) ? 1 : 0;
+  /* the mode in effect: without emitters there is no emission to order, and mode 1 is mode 0 */
+  s->dev.lighting = s->dev.has_emit ? mode : PTX_LIGHTING_REFERENCE;
+  const bool lights = sampled && !s->light_table.empty();
+  s->dev.lights = lights ? s->d_lights.p : nullptr;
+  s->dev.n_lights = lights ? s->host->n_emissive_tris : 0;
+  s->dev.light_area = lights ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
+  s->dev.env_sample = env_on ? 1 : 0;
+  reschedule(s, s->sets_in_flight); /* (Schedule::lit, and what follows from it) */
+}
+
 int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");
   if (mode != PTX_LIGHTING_REFERENCE && mode != PTX_LIGHTING_PATH_ORDER && mode != PTX_LIGHTING_SAMPLED) return fail(PTX_ERR_ARG, "unknown lighting mode %d", mode);
   if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lighting mode cannot change while a render runs on the scene");
   if (mode == PTX_LIGHTING_SAMPLED) {
-    if (s->host->n_emissive_tris == 0) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
+    if (s->host->n_emissive_tris == 0 && !s->env_sampling) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
     if (s->host->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return fail(PTX_ERR_ARG, "%d emissive tree triangles, more than PTX_MAX_LIGHT_TRIANGLES = %d (no light hierarchy)", s->host->n_emissive_tris, PTX_MAX_LIGHT_TRIANGLES);
     if (s->light_table.empty()) s->light_table = light_table_build(*s->host);
-    if (s->device >= 0 && !s->d_lights.p) {
+    if (s->device >= 0 && !s->d_lights.p && !s->light_table.empty()) {
       HIP_TRY(hipSetDevice(s->device));
       HIP_TRY(s->d_lights.ensure(s->light_table.size()));
       HIP_TRY(hipMemcpy(s->d_lights.p, s->light_table.data(), sizeof(double) * s->light_table.size(), hipMemcpyHostToDevice));
     }
   }
   s->lighting = mode;
-  if (s->device >= 0) {
-    /* the mode in effect: without emitters there is no emission to order, and mode 1 is mode 0 */
-    s->dev.lighting = s->dev.has_emit ? mode : PTX_LIGHTING_REFERENCE;
-    s->dev.lights = mode == PTX_LIGHTING_SAMPLED ? s->d_lights.p : nullptr;
-    s->dev.n_lights = mode == PTX_LIGHTING_SAMPLED ? s->host->n_emissive_tris : 0;
-    s->dev.light_area = mode == PTX_LIGHTING_SAMPLED ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
-    reschedule(s, s->sets_in_flight); /* (Schedule::lit, and what follows from it) */
-  }
+  apply_lighting(s);
   for (ptx_scene* r : s->replicas) {
     const int rc = ptx_scene_set_lighting(r, mode);
     if (rc) return rc;
@@ -1942,14 +1958,28 @@ struct ImageStage {
   DevBuf<PtShadeRec> shade;
   int n_images = 0;
 };
-static int stage_texels(ptx_scene* s, const ImageStage::Host& host, ImageStage* st) {
+using EnvDensityRef = std::shared_ptr<const PtEnvDensity>;
+/* the density of an environment under a matrix, or why it has none */
+static int env_density_make(const ptx_scene::ImageHost& host, const double* rot, EnvDensityRef* out) {
+  std::string msg;
+  int rc = scene_check_env_rotation(rot, &msg);
+  if (rc) return fail(rc, "%s", msg.c_str());
+  auto d = std::make_shared<PtEnvDensity>();
+  if ((rc = scene_env_density(host.rec.data(), host.width, host.height, d.get(), &msg)) != 0) return fail(rc, "%s", msg.c_str());
+  *out = d;
+  return 0;
+}
+/* density (an environment that is sampled only): its table goes behind the texels, in the same buffer (pt_scene.h, PT_ENVD_*) */
+static int stage_texels(ptx_scene* s, const ImageStage::Host& host, ImageStage* st, const PtEnvDensity* density = nullptr) {
   st->s = s;
   if (s->device < 0) return 0;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipDeviceSynchronize()); /* frames queued with PTX_RENDER_ASYNC still read the buffers the commit replaces */
   if (host) {
-    HIP_TRY(st->texels.ensure(host->rec.size()));
+    HIP_TRY(st->texels.ensure(host->rec.size() + (density ? density->table.size() : 0)));
     HIP_TRY(hipMemcpy(st->texels.p, host->rec.data(), sizeof(double) * host->rec.size(), hipMemcpyHostToDevice));
+    if (density)
+      HIP_TRY(hipMemcpy(st->texels.p + host->rec.size(), density->table.data(), sizeof(double) * density->table.size(), hipMemcpyHostToDevice));
   }
   return 0;
 }
@@ -2027,11 +2057,35 @@ static int family_take_texture_image(const std::vector<ptx_scene*>& all, int32_t
   for (ImageStage& st : stages) commit_texture_image(&st, index, host);
   return 0;
 }
-static int family_take_environment(const std::vector<ptx_scene*>& all, const ImageStage::Host& host, const double* rot) {
+/* density: the new environment's, where the family samples it (the flag stays as it is) */
+static int family_take_environment(const std::vector<ptx_scene*>& all, const ImageStage::Host& host, const double* rot,
+                                   const EnvDensityRef& density = nullptr) {
   std::vector<ImageStage> stages(all.size());
   for (size_t k = 0; k < all.size(); ++k)
-    if (const int rc = stage_texels(all[k], host, &stages[k])) return rc;
-  for (ImageStage& st : stages) commit_environment(&st, host, rot);
+    if (const int rc = stage_texels(all[k], host, &stages[k], density.get())) return rc;
+  for (ImageStage& st : stages) {
+    st.s->env_density = density;
+    commit_environment(&st, host, rot);
+    apply_lighting(st.s);
+  }
+  return 0;
+}
+/* the environment's texels again, with (on) or without the density table behind them */
+static int family_take_env_sampling(const std::vector<ptx_scene*>& all, bool on, const EnvDensityRef& density) {
+  std::vector<ImageStage> stages(all.size());
+  for (size_t k = 0; k < all.size(); ++k)
+    if (const int rc = stage_texels(all[k], all[k]->env.host, &stages[k], density.get())) return rc;
+  for (ImageStage& st : stages) {
+    ptx_scene* s = st.s;
+    s->env_sampling = on;
+    s->env_density = density;
+    if (s->device >= 0) {
+      (void)hipSetDevice(s->device);
+      s->env.dev = std::move(st.texels);
+      s->dev.env = s->env.host ? s->env.dev.p : nullptr;
+    }
+    apply_lighting(s);
+  }
   return 0;
 }
 static std::shared_ptr<const ptx_scene::ImageHost> image_host_copy(const ptx_image* img) {
@@ -2074,8 +2128,43 @@ int32_t ptx_scene_set_environment(ptx_scene* s, const ptx_image* img, const doub
       if (!std::isfinite(R[k])) return fail(PTX_ERR_ARG, "environment: R[%d] is not finite", k);
   if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the environment cannot change while a render runs on the scene");
   const double* rot = (img && R) ? R : kIdentity3;
+  if (s->env_sampling && !img) return fail(PTX_ERR_STATE, "the environment is being sampled: turn environment sampling off first");
   std::shared_ptr<const ptx_scene::ImageHost> host = img ? image_host_copy(img) : nullptr;
-  return family_take_environment(scene_family(s), host, rot);
+  EnvDensityRef density;
+  if (s->env_sampling && (rc = env_density_make(*host, rot, &density)) != 0) return rc; /* (refused: the old state stays) */
+  return family_take_environment(scene_family(s), host, rot, density);
+}
+
+int32_t ptx_scene_set_environment_sampling(ptx_scene* s, int32_t on) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "environment sampling cannot change while a render runs on the scene");
+  EnvDensityRef density;
+  if (on) {
+    if (!s->env.host) return fail(PTX_ERR_ARG, "environment sampling needs an environment (ptx_scene_set_environment with an image)");
+    if (const int rc = env_density_make(*s->env.host, s->env_rot, &density)) return rc;
+  } else {
+    if (!s->env_sampling) return 0;
+    if (s->lighting == PTX_LIGHTING_SAMPLED && s->host->n_emissive_tris == 0)
+      return fail(PTX_ERR_STATE, "sampled lighting has nothing but the environment to sample: set another lighting mode first");
+  }
+  return family_take_env_sampling(scene_family(s), on != 0, density);
+}
+
+int32_t ptx_scene_environment_sampling(const ptx_scene* s, int32_t* on_out, double* total_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (on_out) *on_out = s->env_sampling ? 1 : 0;
+  if (total_out) *total_out = (s->env_sampling && s->env_density) ? s->env_density->total : 0.0;
+  return 0;
+}
+
+int32_t ptx_environment_distribution(const ptx_scene* s, double* marginal_out, double* conditional_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (!s->env_sampling || !s->env_density) return fail(PTX_ERR_STATE, "environment sampling is off: there is no density to inspect");
+  const PtEnvDensity& d = *s->env_density;
+  const size_t W = (size_t)d.width, H = (size_t)d.height;
+  if (marginal_out) std::memcpy(marginal_out, d.table.data() + PT_ENVD_ROWS, sizeof(double) * H);
+  if (conditional_out) std::memcpy(conditional_out, d.table.data() + PT_ENVD_COND(H), sizeof(double) * W * H);
+  return 0;
 }
 
 static void image_describe(const ptx_scene::ImageHost* h, ptx_image* out) {
@@ -2143,6 +2232,42 @@ int32_t ptx_environment_eval(ptx_scene* s, int64_t n, const double* dirs, double
   hipLaunchKernelGGL(k_environment_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_dirs.p, d_out.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(rgb_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+static int env_sampling_ready(const ptx_scene* s) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (!s->env_sampling || !s->dev.env_sample) return fail(PTX_ERR_STATE, "environment sampling is off (ptx_scene_set_environment_sampling)");
+  return 0;
+}
+int32_t ptx_environment_sample(ptx_scene* s, int64_t n, const double* ab, double* dirs_out, int32_t* texel_out) {
+  if (const int rc = env_sampling_ready(s)) return rc;
+  if (n < 0 || !ab || !dirs_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_ab, d_out;
+  LocalBuf<int32_t> d_texel;
+  HIP_TRY(d_ab.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
+  if (texel_out) HIP_TRY(d_texel.ensure((size_t)n * 2));
+  HIP_TRY(hipMemcpy(d_ab.p, ab, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_environment_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_ab.p, d_out.p, texel_out ? d_texel.p : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(dirs_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  if (texel_out) HIP_TRY(hipMemcpy(texel_out, d_texel.p, sizeof(int32_t) * (size_t)n * 2, hipMemcpyDeviceToHost));
+  return 0;
+}
+int32_t ptx_environment_pdf(ptx_scene* s, int64_t n, const double* dirs, double* pd_out) {
+  if (const int rc = env_sampling_ready(s)) return rc;
+  if (n < 0 || !dirs || !pd_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_dirs, d_out;
+  HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_environment_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_dirs.p, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(pd_out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2280,7 +2405,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;
   s->film = src->film;
-  if (scene_upload(s) != 0 || (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
+  if (scene_upload(s) != 0) {
     ptx_scene_destroy(s);
     return nullptr;
   }
@@ -2291,6 +2416,12 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
       return nullptr;
     }
   if (src->env.host && family_take_environment({s}, src->env.host, src->env_rot) != 0) {
+    ptx_scene_destroy(s);
+    return nullptr;
+  }
+  /* environment sampling (the density is shared too), then the lighting mode, which may need it */
+  if ((src->env_sampling && family_take_env_sampling({s}, true, src->env_density) != 0) ||
+      (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
     ptx_scene_destroy(s);
     return nullptr;
   }

@@ -614,6 +614,57 @@ void scene_image_overrides(const PtHostArrays& h, const std::vector<PtImageEntry
   }
 }
 
+/* ---- the density over the environment image (include/ptx.h states the rule; every expression keeps its grouping) ---- */
+int scene_check_env_rotation(const double R[9], std::string* msg) {
+  double worst = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
+      const double e = std::fabs(g - (i == j ? 1.0 : 0.0));
+      if (!(e <= worst)) worst = e; /* (a NaN stays) */
+    }
+  if (!(worst <= 1e-9))
+    return reject(msg, "environment sampling needs a rotation: max |R R^T - I| = %g exceeds 1e-9", worst);
+  return 0;
+}
+
+int scene_env_density(const double* rec, int32_t width, int32_t height, PtEnvDensity* out, std::string* msg) {
+  const double pi = 3.14159265358979323846;
+  const size_t W = (size_t)width, H = (size_t)height;
+  out->width = width;
+  out->height = height;
+  out->last_row = 0;
+  out->table.assign(PT_ENVD_SIZE(W, H), 0.0);
+  double* m = out->table.data() + PT_ENVD_ROWS;
+  double* lastx = out->table.data() + PT_ENVD_LASTX(H);
+  double* cond = out->table.data() + PT_ENVD_COND(H);
+  double* wt = out->table.data() + PT_ENVD_WEIGHT(W, H);
+  double total = 0.0;
+  for (size_t iy = 0; iy < H; ++iy) {
+    const double s = pt_sin(pi * (((double)iy + 0.5) / (double)height));
+    double run = 0.0;
+    for (size_t ix = 0; ix < W; ++ix) {
+      const double* t = rec + 4 * (iy * W + ix);
+      double lum = (t[0] + t[1]) + t[2];
+      if (!(lum > 0.0)) lum = 0.0;
+      const double w = lum * s;
+      run = run + w;
+      cond[iy * W + ix] = run;
+      wt[iy * W + ix] = w;
+      if (w > 0.0) lastx[iy] = (double)ix;
+    }
+    if (run > 0.0) out->last_row = (int32_t)iy;
+    total = total + run;
+    m[iy] = total;
+  }
+  out->total = total;
+  out->table[PT_ENVD_TOTAL] = total;
+  out->table[PT_ENVD_LAST_ROW] = (double)out->last_row;
+  if (!std::isfinite(total) || !(total > 0.0))
+    return reject(msg, "environment sampling needs a total weight (sum of luminance x sin theta) that is finite and greater than 0 (got %g)", total);
+  return 0;
+}
+
 /* ---- camera tile lists (scene_host.h) ---- */
 bool scene_tile_lists_possible(const PtHostArrays& h) {
   return h.dev.mode == PT_MODE_SIMD && !h.dev.has_triangles && h.dev.n_floor == 0 && !h.nodes.empty() && h.dev.n_slots > 0 &&

@@ -92,6 +92,21 @@ struct PtImageEntry {
 void scene_image_overrides(const PtHostArrays& h, const std::vector<PtImageEntry>& entries, std::vector<uint8_t>* cat,
                            std::vector<PtShadeRec>* shade);
 
+/* ---- the density over the environment image (include/ptx.h, ptx_scene_set_environment_sampling) ----
+ * One table of doubles, as the device holds it behind the environment's texels (pt_scene.h, PT_ENVD_*): T, last_row, m[H], per row the
+ * last column with w > 0 (0 for a row without one) [H], c_iy[ix] [H x W], w(ix, iy) [H x W]; last_row = the last row with r_iy > 0,
+ * total = T. */
+struct PtEnvDensity {
+  int32_t width = 0, height = 0, last_row = 0;
+  double total = 0.0;
+  std::vector<double> table;
+};
+/* max |R R^T - I| <= 1e-9, or PTX_ERR_ARG with *msg naming the rule */
+int scene_check_env_rotation(const double R[9], std::string* msg);
+/* The density of the texel records `rec` (4 doubles per texel, scene_image_records).  0, or PTX_ERR_ARG with *msg set when the total
+ * weight is not finite or not greater than 0 (*out is then unspecified). */
+int scene_env_density(const double* rec, int32_t width, int32_t height, PtEnvDensity* out, std::string* msg);
+
 /* ---- camera tile lists: which spheres a camera ray through an 8 x 8 pixel tile can meet ----
  * One 32-byte record per tile of the GLOBAL tile grid of a width x height image, row-major, tiles_x = ceil(width / 8):
  *   byte 0      the number of slots listed, 0 .. PT_TILE_MAX_SLOTS, or PT_TILE_WALK (pt_scene.h): the tile's rays walk the tree

@@ -18,6 +18,8 @@
 // --envmap=FILE.pfm [--envmap-rotate=DEG]: a latitude-longitude environment in place of the background (ptx_scene_set_environment; the
 // rotation is about the camera-space y axis); --ground-texture=FILE.pfm [--texture-nearest]: an image, repeated on both axes, on
 // the ground (shirley) or floor (ganesha) material (ptx_scene_set_texture_image); image_flags.h.
+// --envmap-sample (with --envmap and --lighting=sampled): the environment is importance-sampled (ptx_scene_set_environment_sampling),
+// and sampled lighting then needs no emissive triangle.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -56,6 +58,7 @@ struct Args {
   bool have_filter = false;              // --filter=ORDER,RADIUS and / or --filter-renormalise
   ptx_film_params film{5, 1, 0, 0};      // ptx_film_defaults
   ImageFlags images;                     // --envmap, --envmap-rotate, --ground-texture, --texture-nearest
+  bool envmap_sample = false;            // --envmap-sample
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -67,7 +70,7 @@ struct Args {
                "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
                "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
                "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n"
-               "          " PTH_IMAGE_FLAGS_USAGE "\n",
+               "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -96,7 +99,8 @@ Args parse(int argc, char** argv) {
   bool have_dim = false;
   for (int i = 1; i < argc; ++i) {
     std::string v, bad;
-    if (image_flag(argv[i], &a.images, &bad)) {
+    if (!std::strcmp(argv[i], "--envmap-sample")) a.envmap_sample = true;
+    else if (image_flag(argv[i], &a.images, &bad)) {
       if (!bad.empty()) usage(argv[0], bad.c_str());
     } else if (take_value(argc, argv, i, "dimension", "d", &v)) {
       if (std::sscanf(v.c_str(), "%d,%d", &a.width, &a.height) != 2) usage(argv[0], "invalid value for --dimension, expected WIDTH,HEIGHT");
@@ -184,6 +188,8 @@ Args parse(int argc, char** argv) {
     const std::string bad = image_flags_check(a.images, a.scene != "cornell");
     if (!bad.empty()) usage(argv[0], bad.c_str());
   }
+  if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
+  if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
   if (a.have_filter) { // the library's own check and message (host only: no device is touched)
     double w[2 * PTX_FILM_MAX_RADIUS + 1];
     if (ptx_film_weights(&a.film, w, nullptr) != 0) usage(argv[0], ptx_last_error());
@@ -285,7 +291,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ptx_scene_create: %s\n", ptx_last_error());
     return 1;
   }
-  if (a.lighting != PTX_LIGHTING_REFERENCE && ptx_scene_set_lighting(scene, a.lighting) != 0) {
+  // (with --envmap-sample the mode is set behind the environment and its sampling, which it may need)
+  if (!a.envmap_sample && a.lighting != PTX_LIGHTING_REFERENCE && ptx_scene_set_lighting(scene, a.lighting) != 0) {
     std::fprintf(stderr, "ptx_scene_set_lighting: %s\n", ptx_last_error());
     return 1;
   }
@@ -297,6 +304,16 @@ int main(int argc, char** argv) {
     std::string err;
     if (apply_image_flags(scene, d, a.images, &err) != 0) {
       std::fprintf(stderr, "%s: %s\n", argv[0], err.c_str());
+      return 1;
+    }
+  }
+  if (a.envmap_sample) {
+    if (ptx_scene_set_environment_sampling(scene, 1) != 0) {
+      std::fprintf(stderr, "ptx_scene_set_environment_sampling: %s\n", ptx_last_error());
+      return 1;
+    }
+    if (ptx_scene_set_lighting(scene, a.lighting) != 0) {
+      std::fprintf(stderr, "ptx_scene_set_lighting: %s\n", ptx_last_error());
       return 1;
     }
   }

@@ -58,21 +58,27 @@ class Integrator:
     hard-wires (``Binomial.create ~order:5 ~pixel_radius:1``): (order, radius) or (order, radius, renormalise) for Scene.set_film;
     None leaves the scene's film as it is.  ``environment``: an (H, W, 3) latitude-longitude image, or (image, rotation) or
     (image, rotation, bilinear), for Scene.set_environment; ``images``: {texture index: image or (image, bilinear, repeat)} for
-    Scene.set_texture_image.  None leaves the scene's as they are."""
+    Scene.set_texture_image.  None leaves the scene's as they are.  ``environment_sampling``: True / False for
+    Scene.set_environment_sampling -- with "sampled" lighting the light density then includes (or, on a scene without emissive
+    triangles, is) the environment's; True is applied after the environment and before the lighting mode, which may need it."""
 
     def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-                 environment=None, images=None):
+                 environment=None, images=None, environment_sampling=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
         self.samples_per_pixel, self.max_bounces = samples_per_pixel, max_bounces
         self._scene = scene if isinstance(scene, Scene) else Scene(scene.ptr, device, keepalive=scene)
-        if lighting is not None:
+        if lighting is not None and not environment_sampling:
             self._scene.set_lighting(lighting)
         if film is not None:
             self._scene.set_film(*film)
         if environment is not None:
             self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
+        if environment_sampling is not None:
+            self._scene.set_environment_sampling(bool(environment_sampling))
+        if lighting is not None and environment_sampling:
+            self._scene.set_lighting(lighting)
         for index, img in (images or {}).items():
             self._scene.set_texture_image(index, *(img if isinstance(img, tuple) else (img,)))
         self.stats = None
@@ -82,8 +88,9 @@ class Integrator:
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-               environment=None, images=None):
-        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images)
+               environment=None, images=None, environment_sampling=None):
+        return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images,
+                   environment_sampling)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
