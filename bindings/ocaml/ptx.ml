@@ -239,6 +239,22 @@ let environment_sampling scene =
   let on, total = environment_sampling_raw scene in
   on <> 0, total
 
+(* The thin-lens camera (ptx_scene_set_lens; the rule is in include/ptx.h): a lens of [radius] around the camera's origin, focused on
+   the plane [focus_distance] in front of it, so that what lies off that plane blurs.  [radius] 0. switches the lens off, which is a
+   scene's first state: the pinhole Camera.ray, bit for bit.  Sticky: every later render of the scene reads it.  Failure for a negative
+   or non-finite radius, a focus distance that is not positive and finite, or while a render runs on the scene.
+   lens: (radius, focus_distance). *)
+external set_lens_raw
+  :  scene
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> unit
+  = "ptx_ml_set_lens_stub"
+
+external lens : scene -> float * float = "ptx_ml_lens_stub"
+
+let set_lens scene ~radius ~focus_distance =
+  set_lens_raw scene (Bigarray.Array1.of_array Bigarray.float64 Bigarray.c_layout [| radius; focus_distance |])
+
 external render_flat
   :  scene
   -> int (* width *)

@@ -260,6 +260,15 @@ static __attribute__((unused)) int32_t ptx_ml_set_film(ptx_scene* s, int32_t ord
   return ptx_scene_set_film(s, &f);
 }
 
+/* Ptx.set_lens / Ptx.lens: the thin lens every later render of the scene looks through (ptx_scene_set_lens; radius 0 = off) */
+static __attribute__((unused)) int32_t ptx_ml_set_lens(ptx_scene* s, const double* pair, int64_t n_pair) {
+  if (n_pair != 2) return -4; /* (radius, focus_distance) */
+  return ptx_scene_set_lens(s, pair[0], pair[1]);
+}
+static __attribute__((unused)) int32_t ptx_ml_lens(const ptx_scene* s, double* radius, double* focus_distance) {
+  return ptx_scene_lens(s, radius, focus_distance);
+}
+
 /* Ptx.film_weights: the 2 * pixel_radius + 1 weights into out (n_out doubles); -4 when out is too short for an accepted film (the
  * library's own refusals keep their codes, and nothing is written) */
 static __attribute__((unused)) int32_t ptx_ml_film_weights(int32_t order, int32_t pixel_radius, double* out, int64_t n_out) {

@@ -360,6 +360,39 @@ CAMLprim value ptx_ml_environment_sampling_stub(value handle) {
   CAMLreturn(tuple);
 }
 
+/* external set_lens_raw : scene -> texels -> unit = "ptx_ml_set_lens_stub" (ptx_scene_set_lens: a Bigarray of the two doubles radius,
+ * focus_distance, as the other stubs take their doubles; radius 0 switches the lens off).  What a running render's camera rays are made of: like set_lighting it takes the scene exclusively and raises
+ * Failure while a render runs on another thread or domain, and Failure with the library's message for a refused pair. */
+CAMLprim value ptx_ml_set_lens_stub(value handle, value pair) {
+  CAMLparam2(handle, pair);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_lens: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_lens: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_set_lens(s, (const double*)Caml_ba_data_val(pair), (int64_t)Caml_ba_array_val(pair)->dim[0]);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_lens: scene already destroyed");
+  if (rc == -4) caml_invalid_argument("Ptx.set_lens: the pair must hold 2 doubles (radius, focus_distance)");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external lens : scene -> float * float = "ptx_ml_lens_stub" (ptx_scene_lens: radius, focus_distance) */
+CAMLprim value ptx_ml_lens_stub(value handle) {
+  CAMLparam1(handle);
+  CAMLlocal3(tuple, radius_v, focus_v);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.lens: scene already destroyed");
+  double radius = 0.0, focus = 0.0;
+  if (ptx_ml_lens(s, &radius, &focus) != 0) caml_failwith(ptx_last_error());
+  radius_v = caml_copy_double(radius);
+  focus_v = caml_copy_double(focus);
+  tuple = caml_alloc_tuple(2);
+  Store_field(tuple, 0, radius_v);
+  Store_field(tuple, 1, focus_v);
+  CAMLreturn(tuple);
+}
+
 /* external film_int : scene -> int * int * int = "ptx_ml_film_stub" (ptx_scene_film: order, pixel_radius, flags) */
 CAMLprim value ptx_ml_film_stub(value handle) {
   CAMLparam1(handle);

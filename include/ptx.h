@@ -716,6 +716,52 @@ int32_t ptx_environment_distribution(const ptx_scene* scene, double* marginal_ou
 int32_t ptx_environment_sample(ptx_scene* scene, int64_t n, const double* ab, double* dirs_out, int32_t* texel_out);
 int32_t ptx_environment_pdf(ptx_scene* scene, int64_t n, const double* dirs, double* pd_out);
 
+/* ---- thin-lens camera: aperture and focus distance ----
+ * Camera.ray (camera.ml:93-102) is a pinhole: every ray starts at P3.origin.  ptx_scene_set_lens gives the camera a lens, and with it
+ * depth of field.  Only entry points are added: no struct changes and the ABI version stays 6.
+ *
+ * ptx_scene_set_lens(scene, radius, focus_distance): sticky state of the handle.  radius == 0 switches the lens OFF, which is the
+ * state of every scene that never called the setter; an off scene renders through the pinhole's own path, kernels and alpha table,
+ * bit for bit (radius 0 does not mean "a lens of radius 0": normalize(F * q) rounds differently from normalize(q)).  Accepted:
+ * radius >= 0, focus_distance > 0, both finite; anything else is PTX_ERR_ARG with a message that names the rule ("lens: ...").
+ * PTX_ERR_STATE while a render runs on the scene.  A host-only scene accepts it; the replicas a scene owns follow it and
+ * ptx_scene_replicate copies it.  ptx_scene_lens returns what was set (radius 0 and the focus last given, 1.0 at first); either
+ * out pointer may be NULL.
+ *
+ * Camera space is the existing one: the camera at the origin looking down -z.  The lens is the disc of radius A = radius around the
+ * origin in the plane z = 0; the plane of focus is z = -F, F = focus_distance.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction; sqrt is IEEE, sin and cos are pt_math.h's), for a sample
+ * with film coordinates (cx, cy) -- computed exactly as for the pinhole -- and the camera's (llx, lly, vx, vy):
+ *   q  = (llx + (vx * cx), lly + (vy * cy), -1.0)            the pinhole's direction before it is normalised
+ *   P  = (F * q.x, F * q.y, F * q.z)                         where the pinhole ray meets the plane of focus (P.z = -F exactly)
+ *   r  = sqrt(u);  th = (v * 2.0) * pi;  lx = r * cos(th);  ly = r * sin(th)
+ *                                                            the first two components of Shader_space.unit_square_to_hemisphere u v
+ *   L  = (A * lx, A * ly, +0.0)                              the ray's origin
+ *   e  = (P.x - L.x, P.y - L.y, P.z - L.z)
+ *   d  = V3.normalize e = (s * e.x, s * e.y, s * e.z), s = 1 / hypot(e.x, hypot(e.y, e.z))      the ray's direction
+ *   1/d = (1 / d.x, 1 / d.y, 1 / d.z) as Ray.create makes it
+ * Every sample's ray passes through P (within rounding), so what lies in the plane of focus is sharp.
+ *
+ * Sampler dimensions.  A lens render's sampler has d = 4 + 2 * max_bounces dimensions (Low_discrepancy_sequence.create d).  The pixel
+ * jitter stays in dimensions 0 and 1 and bounce k in 2 + 2k and 3 + 2k; (u, v) of the lens are the LAST two, d - 2 and d - 1, at the
+ * sample's own offset.  The sequence's alpha_i = 1 / phi_d^(i + 1) depends on d through phi_d, so EVERY dimension of a lens render
+ * differs from the same dimension of a pinhole render of the same depth: the jitter and the scatters too, not the lens pair alone.
+ * max_bounces stays capped at 126: d = 256 then, which the 256-entry tables of the sampler's restatements still hold.
+ *
+ * Entry points.  The lens is read by ptx_render, ptx_render_multi (every scene passed must carry the same lens: PTX_ERR_ARG
+ * otherwise), ptx_render_raw_device (bands and PTX_RENDER_ASYNC included), _passes_device, _pixels_device, _progressive, _adaptive,
+ * _denoised, ptx_render_features_device (the first hit of the LENS ray; depth is t along that ray) and ptx_trace_samples.
+ * ptx_ppm_render and ptx_debug_first_scatter return PTX_ERR_STATE on a scene whose lens is on ("... ptx_scene_set_lens(scene, 0, f)
+ * first"); ptx_intersect_rays and ptx_walk_rays take explicit rays and are unaffected.
+ * A lens render writes its camera rays into a path queue (one launch per batch, counted under PTX_KERNEL_GENERATE) and bounces them
+ * from there in the walk-first order: no fused camera launch, no shade-first order, no per-octant LDS image,
+ * no camera tile lists, no solo run.  The queue keeps the fused launch's order -- 64 consecutive entries are one 8 x 8 pixel tile
+ * of one pass; the lanes of a ragged tile that fall off the image are holes, marked as the queues mark theirs.
+ * Out of scope: polygonal or anamorphic apertures, focus by picking a pixel, motion blur, a lens in the photon mapper. */
+int32_t ptx_scene_set_lens(ptx_scene* scene, double radius, double focus_distance);
+int32_t ptx_scene_lens(const ptx_scene* scene, double* radius_out, double* focus_distance_out);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

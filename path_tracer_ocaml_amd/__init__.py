@@ -44,6 +44,7 @@ EXPORTS = (
     "ptx_texture_eval", "ptx_environment_eval", "ptx_walk_rays",
     "ptx_scene_set_environment_sampling", "ptx_scene_environment_sampling", "ptx_environment_distribution",
     "ptx_environment_sample", "ptx_environment_pdf",
+    "ptx_scene_set_lens", "ptx_scene_lens",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -153,6 +154,9 @@ def lib():
         L.ptx_environment_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp]
     if hasattr(L, "ptx_walk_rays"):  # (likewise)
         L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
+    if hasattr(L, "ptx_scene_set_lens"):  # (likewise)
+        L.ptx_scene_set_lens.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.ptx_scene_lens.argtypes = [C.c_void_p, dp, dp]
     _LIB = L
     return L
 
@@ -252,6 +256,18 @@ class Scene:
         f = abi.FilmParams()
         _check(lib().ptx_scene_film(self._h, C.byref(f)))
         return f.order, f.pixel_radius, bool(f.flags & abi.PTX_FILM_RENORMALISE)
+
+    def set_lens(self, radius, focus_distance):
+        """ptx_scene_set_lens: a thin lens of this radius around the camera's origin, focused on the plane at focus_distance in
+        front of it; every later render of this scene has its depth of field.  Sticky; radius 0 switches the lens off (the
+        pinhole, bit for bit)."""
+        _check(lib().ptx_scene_set_lens(self._h, float(radius), float(focus_distance)))
+
+    def lens(self):
+        """ptx_scene_lens: (radius, focus_distance); radius 0.0 = off"""
+        r, f = C.c_double(), C.c_double()
+        _check(lib().ptx_scene_lens(self._h, C.byref(r), C.byref(f)))
+        return r.value, f.value
 
     def set_texture_image(self, index, image, bilinear=False, repeat=(False, False)):
         """ptx_scene_set_texture_image: from now on every material that points at entry `index` of the scene's texture table

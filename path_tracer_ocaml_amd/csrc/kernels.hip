@@ -4171,5 +4171,6 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "bvh_build_gpu.inc"
 #include "ppm.inc"
 #include "denoise.inc"
+#include "lens.inc"
 #include "ptx_api.inc"
 #endif

@@ -262,6 +262,7 @@ struct Schedule {
   bool share_cus = false;      /* two batches in flight on a Simd_leaf scene held in LDS: every kernel takes half a CU */
   bool lit = false;            /* emitters under lighting mode 1 or 2: the LIT instantiations */
   bool img = false;            /* an image texture or an environment: the IMG instantiations */
+  bool lens = false;           /* a thin lens (ptx_scene_set_lens): camera rays are generated into a queue, never a PRIMARY launch; the walk-first order */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
@@ -309,6 +310,7 @@ struct ptx_scene {
    * the number of calls that are rendering with this handle right now */
   int lighting = 0;
   ptx_film_params film = kFilmDefault;      /* ptx_scene_set_film: what every entry point that films through this handle applies */
+  double lens_radius = 0.0, lens_focus = 1.0; /* ptx_scene_set_lens: radius 0 = off, the pinhole */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
   /* Images (ptx_scene_set_texture_image / _set_environment): per entry of the texture table and for the environment, the host copy of
@@ -365,7 +367,7 @@ struct ptx_scene {
   } wb[kMaxSets];
   hipStream_t streams[kMaxSets] = {};
   hipEvent_t ev_fork = nullptr, ev_accum[kMaxSets] = {}, ev_join[kMaxSets] = {};
-  /* The sampler's alpha table (L.create, low_discrepancy_sequence.ml:8-31) depends on the dimension = 2 + 2 max_bounces only.
+  /* The sampler's alpha table (L.create, low_discrepancy_sequence.ml:8-31) depends on the dimension only (sampler_dimension).
    * One device copy per distinct dimension, uploaded the first time it is asked for and never written again: frames queued
    * with PTX_RENDER_ASYNC (possibly with different max_bounces, on any stream) keep reading the table they were launched
    * with, and a render call no longer copies anything on the NULL stream. */
@@ -384,6 +386,7 @@ struct ptx_scene {
    * hand-out words and parked walks -- its own, because a queued slice of a render may be running on the workspace sets meanwhile;
    * ptx_render_denoised: the feature sums, their means for the host, the filter's guide and {c, V} pair, the denoised sums */
   DevBuf<int32_t> feat_slot;
+  DevBuf<PtRayRec> feat_ray; /* a lens's feature slices: the camera rays k_trace walks (k_generate_lens<false>) */
   DevBuf<double> feat_t;
   DevBuf<uint32_t> feat_work;
   DevBuf<uint4> feat_susp;
@@ -566,6 +569,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * flagged IMG, which only the walk-first k_bounce, k_shade_pool, the feature kernel and the photon passes have.  Like a lit scene
    * it never takes the shade-first order -- hence no per-octant LDS image and no tile lists either -- and never runs solo. */
   c.img = s->dev.n_images != 0 || s->dev.env != nullptr;
+  /* A scene with a lens: its camera rays have an origin, which no fused camera launch can take, so they are written into a queue
+   * (k_generate_lens) and bounced like a list's.  The shade-first order starts at a camera launch: a lens scene keeps the walk-first
+   * order, and with it has no per-octant LDS image and no tile lists. */
+  c.lens = s->lens_radius > 0.0;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
   c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
@@ -587,7 +594,7 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
    * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
    * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
-  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && !c.img && s->fused >= 2 && s->solo_entries <= 0 &&
+  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && !c.img && !c.lens && s->fused >= 2 && s->solo_entries <= 0 &&
                in_lds && !c.from_hbm && c.carry.fits;
   /* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
    * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
@@ -826,10 +833,15 @@ struct Workspace {
   size_t contrib_n = 0;
 };
 
-/* The sampler's alpha table for renders of this depth becomes the scene's current one (ptx_scene.alpha): looked up, or made and
+/* The sampler's dimension for renders of this depth: 2 + 2 max_bounces, and two more -- the last two, the lens pair -- while the
+ * scene has a lens (include/ptx.h: every alpha of the table then differs from the pinhole's) */
+int sampler_dimension(const ptx_scene* s, int max_bounces) { return 2 + 2 * std::max(max_bounces, 0) + (s->lens_radius > 0.0 ? 2 : 0); }
+/* the lens of a launch (Schedule::lens) */
+PtLens scene_lens(const ptx_scene* s, int max_bounces) { return PtLens{s->lens_radius, s->lens_focus, sampler_dimension(s, max_bounces)}; }
+
+/* The sampler's alpha table of this dimension becomes the scene's current one (ptx_scene.alpha): looked up, or made and
  * uploaded the first time the dimension is asked for */
-int use_alpha_table(ptx_scene* s, int max_bounces) {
-  const int dim = 2 + 2 * std::max(max_bounces, 0);
+int use_alpha_table(ptx_scene* s, int dim) {
   double* table = nullptr;
   for (const auto& t : s->alpha_tables)
     if (t.first == dim) table = t.second;
@@ -876,7 +888,7 @@ int ensure_workspace(ptx_scene* s, size_t cap, int max_bounces, Workspace* w, in
   HIP_TRY(b.susp.ensure((size_t)s->n_cu * 4 * 16 * PT_WAVE * 3));
   HIP_TRY(s->counters.ensure(1));
   { /* (every set: a cached lookup) */
-    const int rc = use_alpha_table(s, max_bounces);
+    const int rc = use_alpha_table(s, sampler_dimension(s, max_bounces));
     if (rc) return rc;
   }
   /* views must use the capacity the buffers were SIZED with */
@@ -1146,8 +1158,12 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     q0.count = w.counts;
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-      hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                         p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
+      if (s->sched.lens)
+        hipLaunchKernelGGL(k_generate_pixels_lens, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+      else
+        hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
     }
     run_bounces(s, ls, w, n_paths, p->max_bounces, count, timed, PrimaryLaunch());
   } else {
@@ -1159,7 +1175,18 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     g.tiles_x = (p->width + 7) / 8; g.tiles_y = (b.rows + 7) / 8;
     g.first_pass = first; g.n_pass = n_pass;
     pl.n = (uint32_t)((size_t)n_pass * (size_t)g.tiles_x * (size_t)g.tiles_y * 64u);
-    run_bounces(s, ls, w, std::max<size_t>(n_paths, pl.n), p->max_bounces, count, timed, pl);
+    if (s->sched.lens) {
+      /* the fused camera launch's virtual queue made real: pl.n entries in its order (b.cap is sized for them), then queued bounces */
+      PtQueue q0 = w.q[0];
+      q0.count = w.counts;
+      {
+        LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
+        hipLaunchKernelGGL(k_generate_lens<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+      }
+      run_bounces(s, ls, w, (size_t)pl.n, p->max_bounces, count, timed, PrimaryLaunch());
+    } else {
+      run_bounces(s, ls, w, std::max<size_t>(n_paths, pl.n), p->max_bounces, count, timed, pl);
+    }
   }
   return 0;
 }
@@ -1946,6 +1973,28 @@ int32_t ptx_scene_film(const ptx_scene* s, ptx_film_params* out) {
   return 0;
 }
 
+int32_t ptx_scene_set_lens(ptx_scene* s, double radius, double focus_distance) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (!std::isfinite(radius) || !(radius >= 0.0)) return fail(PTX_ERR_ARG, "lens: radius must be finite and >= 0 (got %g); 0 switches the lens off", radius);
+  if (!std::isfinite(focus_distance) || !(focus_distance > 0.0)) return fail(PTX_ERR_ARG, "lens: focus_distance must be finite and > 0 (got %g)", focus_distance);
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lens cannot change while a render runs on the scene");
+  s->lens_radius = radius;
+  s->lens_focus = focus_distance;
+  if (s->device >= 0) reschedule(s, s->sets_in_flight); /* (Schedule::lens, and what follows from it) */
+  for (ptx_scene* r : s->replicas) {
+    const int rc = ptx_scene_set_lens(r, radius, focus_distance);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_lens(const ptx_scene* s, double* radius_out, double* focus_distance_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (radius_out) *radius_out = s->lens_radius;
+  if (focus_distance_out) *focus_distance_out = s->lens_focus;
+  return 0;
+}
+
 /* ---- image textures and the environment ---- */
 /* A setter changes a scene and its replicas together or not at all: everything that can fail -- the uploads of the texels and of
  * the slot categories and shading records made of them -- goes into fresh buffers first, for every scene (stage); only when all of
@@ -2405,6 +2454,8 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->tree_depth = src->tree_depth;
   s->tree_leaves = src->tree_leaves;
   s->film = src->film;
+  s->lens_radius = src->lens_radius; /* (scene_upload schedules, like every setter) */
+  s->lens_focus = src->lens_focus;
   if (scene_upload(s) != 0) {
     ptx_scene_destroy(s);
     return nullptr;
@@ -2544,6 +2595,8 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
       if (scenes[j] == scenes[k]) return fail(PTX_ERR_ARG, "scene %d is the same handle as scene %d (one render per handle at a time)", k, j);
     if (scenes[k]->host != scenes[0]->host && (scenes[k]->dev.n_nodes != scenes[0]->dev.n_nodes || scenes[k]->dev.n_slots != scenes[0]->dev.n_slots))
       return fail(PTX_ERR_ARG, "scene %d is not a replica of scene 0", k);
+    if (scenes[k]->lens_radius != scenes[0]->lens_radius || (scenes[0]->lens_radius > 0.0 && scenes[k]->lens_focus != scenes[0]->lens_focus))
+      return fail(PTX_ERR_ARG, "scene %d does not carry the lens of scene 0 (ptx_scene_set_lens): the bands would not be one image", k);
   }
   int rc = check_params(p_in);
   if (rc) return rc;
@@ -3178,10 +3231,12 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
   const size_t cap = (size_t)ppb * (size_t)padded;
   HIP_TRY(s->feat_slot.ensure(cap));
   if (!s->dev.has_triangles) HIP_TRY(s->feat_t.ensure(cap));
-  HIP_TRY(s->feat_work.ensure(8));
+  const bool lens = s->sched.lens;
+  if (lens) HIP_TRY(s->feat_ray.ensure(cap));
+  HIP_TRY(s->feat_work.ensure(16)); /* [0..7] k_trace's hand-out words, [8] the entry count of a lens's ray queue */
   HIP_TRY(s->feat_susp.ensure((size_t)s->n_cu * 4 * 16 * PT_WAVE * 3)); /* as a workspace set's (ensure_workspace) */
   HIP_TRY(s->counters.ensure(1));
-  int rc = use_alpha_table(s, p->max_bounces);
+  int rc = use_alpha_table(s, sampler_dimension(s, p->max_bounces));
   if (rc) return rc;
   const double* alpha = s->alpha.p;
   PtHits h{};
@@ -3198,6 +3253,16 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
     g.first_pass = first; g.n_pass = n_pass;
     pl.n = (uint32_t)((unsigned long long)n_pass * padded);
     HIP_TRY(hipMemsetAsync(s->feat_work.p, 0, sizeof(uint32_t) * 8, st));
+    if (lens) {
+      /* the same entries as rays in a queue of their own (48 bytes per entry more), walked as ptx_intersect_rays' are */
+      const PtLens ln = scene_lens(s, p->max_bounces);
+      PtQueue q{s->feat_ray.p, nullptr, s->feat_work.p + 8};
+      hipLaunchKernelGGL(k_generate_lens<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, ln, alpha, q);
+      launch_trace(s, st, q, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, kNoBounce);
+      hipLaunchKernelGGL(s->sched.img ? k_features_lens<true> : k_features_lens<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, q, h, d_feat);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
     launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, 0, pl);
     hipLaunchKernelGGL(s->sched.img ? k_features<true> : k_features<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
     HIP_TRY(hipGetLastError());
@@ -3429,8 +3494,12 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
   if (p->max_bounces > 0) {
     PtQueue q0 = w.q[0];
     q0.count = w.counts;
-    hipLaunchKernelGGL(k_generate_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx.p, dy.p, dp.p, s->alpha.p, q0);
+    if (s->sched.lens)
+      hipLaunchKernelGGL(k_generate_list_lens, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
+                         p->samples_per_pixel, (long long)n, dx.p, dy.p, dp.p, scene_lens(s, p->max_bounces), s->alpha.p, q0);
+    else
+      hipLaunchKernelGGL(k_generate_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
+                         p->samples_per_pixel, (long long)n, dx.p, dy.p, dp.p, s->alpha.p, q0);
     run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, count, false, PrimaryLaunch());
   }
   HIP_TRY(hipGetLastError());
@@ -3619,6 +3688,7 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
   int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
+  if (s->lens_radius > 0.0) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the pinhole's rays: switch the lens off with ptx_scene_set_lens(scene, 0, f) first");
   HIP_TRY(hipSetDevice(s->device));
   RenderBusy busy(s);
   Workspace w;
@@ -3675,6 +3745,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   if ((long long)p->iterations * ((long long)p->width * p->height > p->photon_count ? (long long)p->width * p->height : p->photon_count) >= 2147483647LL)
     return fail(PTX_ERR_ARG, "sampler offset does not fit 32 bits");
   if (s->host->nodes.empty()) return fail(PTX_ERR_STATE, "scene has no tree (Scene.bbox undefined)");
+  if (s->lens_radius > 0.0) return fail(PTX_ERR_STATE, "the photon mapper's eye pass is a pinhole: switch the lens off with ptx_scene_set_lens(scene, 0, f) first");
   HIP_TRY(hipSetDevice(s->device));
   const double t_total0 = wall_ms();
   ptx_ppm_stats st;

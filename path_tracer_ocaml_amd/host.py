@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
-EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_camera_create", "pth_scene_shirley", "pth_scene_cornell", "pth_scene_cornell_lamp",
+EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_camera_create", "pth_scene_shirley", "pth_scene_cornell", "pth_scene_cornell_lamp",
            "pth_scene_ganesha_like", "pth_write_png", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
@@ -25,6 +25,8 @@ def lib():
         L.pth_scene_desc.restype = C.POINTER(abi.SceneDesc)
         L.pth_scene_desc.argtypes = [C.c_void_p]
         L.pth_scene_free.argtypes = [C.c_void_p]
+        L.pth_scene_focus_distance.restype = C.c_double
+        L.pth_scene_focus_distance.argtypes = [C.c_void_p]
         L.pth_camera_create.argtypes = [abi.c_double_p, abi.c_double_p, abi.c_double_p, C.c_double, C.c_double,
                                         C.POINTER(abi.Camera), abi.c_double_p]
         L.pth_scene_shirley.restype = C.c_void_p
@@ -70,6 +72,11 @@ class HostScene:
     @property
     def d(self):
         return self.ptr.contents
+
+    @property
+    def focus_distance(self):
+        """the distance from the eye to the look-at target of the scene's camera: a thin lens's default focus (Scene.set_lens)"""
+        return lib().pth_scene_focus_distance(self._h)
 
     def arrays(self):
         d = self.d

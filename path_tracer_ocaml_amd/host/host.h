@@ -15,6 +15,8 @@ typedef struct pth_scene pth_scene; /* owns the arrays a ptx_scene_desc points i
 
 const ptx_scene_desc* pth_scene_desc(pth_scene* s);
 void pth_scene_free(pth_scene* s);
+/* the distance from the eye to the look-at target of the scene's camera: the default focus distance of a thin lens (ptx_scene_set_lens) */
+double pth_scene_focus_distance(const pth_scene* s);
 
 /* Camera.create (path_tracer/src/camera.ml:58-83): view = the four fields Camera.ray reads;
  * look_at (optional) = Mat4.look_at rows, row-major 4x4 */

@@ -18,9 +18,11 @@
 // --envmap=FILE.pfm [--envmap-rotate=DEG]: a latitude-longitude environment in place of the background (ptx_scene_set_environment; the
 // rotation is about the camera-space y axis); --ground-texture=FILE.pfm [--texture-nearest]: an image, repeated on both axes, on
 // the ground (shirley) or floor (ganesha) material (ptx_scene_set_texture_image); image_flags.h.
+// --lens-radius=R [--focus-distance=F]: a thin lens (ptx_scene_set_lens); without F it focuses on the camera's look-at target.
 // --envmap-sample (with --envmap and --lighting=sampled): the environment is importance-sampled (ptx_scene_set_environment_sampling),
 // and sampled lighting then needs no emissive triangle.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +61,8 @@ struct Args {
   ptx_film_params film{5, 1, 0, 0};      // ptx_film_defaults
   ImageFlags images;                     // --envmap, --envmap-rotate, --ground-texture, --texture-nearest
   bool envmap_sample = false;            // --envmap-sample
+  double lens_radius = 0.0;              // --lens-radius=R (0: the pinhole)
+  double focus_distance = 0.0;           // --focus-distance=F (0: not given -- the distance from the eye to the look-at target)
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -70,7 +74,8 @@ struct Args {
                "          [--progressive=K] [--target-error=FLOAT] [--adaptive=FLOAT] [--min-passes=M]\n"
                "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
                "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n"
-               "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n",
+               "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n"
+               "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -159,6 +164,15 @@ Args parse(int argc, char** argv) {
       a.film.flags |= PTX_FILM_RENORMALISE;
       a.have_filter = true;
     }
+    else if (take_value(argc, argv, i, "lens-radius", nullptr, &v)) {
+      char* end = nullptr;
+      a.lens_radius = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.lens_radius >= 0.0) || !std::isfinite(a.lens_radius)) usage(argv[0], "invalid value for --lens-radius, must be >= 0");
+    } else if (take_value(argc, argv, i, "focus-distance", nullptr, &v)) {
+      char* end = nullptr;
+      a.focus_distance = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.focus_distance > 0.0) || !std::isfinite(a.focus_distance)) usage(argv[0], "invalid value for --focus-distance, must be > 0");
+    }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
     else if (!std::strcmp(argv[i], "--no-simd")) a.no_simd = true;
@@ -188,6 +202,7 @@ Args parse(int argc, char** argv) {
     const std::string bad = image_flags_check(a.images, a.scene != "cornell");
     if (!bad.empty()) usage(argv[0], bad.c_str());
   }
+  if (a.focus_distance > 0.0 && !(a.lens_radius > 0.0)) usage(argv[0], "--focus-distance requires --lens-radius > 0");
   if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
   if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
   if (a.have_filter) { // the library's own check and message (host only: no device is touched)
@@ -294,6 +309,11 @@ int main(int argc, char** argv) {
   // (with --envmap-sample the mode is set behind the environment and its sampling, which it may need)
   if (!a.envmap_sample && a.lighting != PTX_LIGHTING_REFERENCE && ptx_scene_set_lighting(scene, a.lighting) != 0) {
     std::fprintf(stderr, "ptx_scene_set_lighting: %s\n", ptx_last_error());
+    return 1;
+  }
+  // the thin lens: without --focus-distance it focuses on the camera's look-at target
+  if (a.lens_radius > 0.0 && ptx_scene_set_lens(scene, a.lens_radius, a.focus_distance > 0.0 ? a.focus_distance : pth_scene_focus_distance(hs)) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_lens: %s\n", ptx_last_error());
     return 1;
   }
   if (a.have_filter && ptx_scene_set_film(scene, &a.film) != 0) {

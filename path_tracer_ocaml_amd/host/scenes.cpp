@@ -165,6 +165,8 @@ struct pth_scene {
   std::vector<int32_t> floor_m;
   std::vector<ptx_material> mats;
   std::vector<ptx_texture> texs;
+  double focus = 1.0; // |target - eye| of the scene's camera: what a thin lens focuses on by default (pth_scene_focus_distance)
+  void look(V3 eye, V3 target) { focus = std::sqrt((target.x - eye.x) * (target.x - eye.x) + (target.y - eye.y) * (target.y - eye.y) + (target.z - eye.z) * (target.z - eye.z)); }
 
   int solid(double r, double g, double b) {
     ptx_texture t{};
@@ -262,6 +264,7 @@ const ptx_scene_desc* pth_scene_desc(pth_scene* s) {
   return &s->d;
 }
 void pth_scene_free(pth_scene* s) { delete s; }
+double pth_scene_focus_distance(const pth_scene* s) { return s ? s->focus : 0.0; }
 
 void pth_camera_create(const double eye[3], const double target[3], const double up[3], double aspect, double fov_deg,
                        ptx_camera* view_out, double look_at_out[16]) {
@@ -276,6 +279,7 @@ pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int
   pth_scene* s = new pth_scene();
   BaseRandom rng(seed);
   const Camera cam = camera_create(v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, 20.0);
+  s->look(v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0));
   const double ga[3] = {0.2, 0.3, 0.1}, gb[3] = {0.9, 0.9, 0.9};
   s->sphere(v3(0.0, -1000.0, 0.0), 1000.0, s->material(PTX_MAT_LAMBERTIAN, s->checker(1000, 2000, ga, gb))); // ground
   const int glass = s->material(PTX_MAT_DIELECTRIC, 0, 1.5); // Material.glass
@@ -327,6 +331,7 @@ static pth_scene* cornell_build(int32_t width, int32_t height, double ceiling_em
   pth_scene* s = new pth_scene();
   const double fov = (2.0 * std::atan(0.5)) * 180.0 / kPi;
   const Camera cam = camera_create(v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, fov);
+  s->look(v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0));
   const V3 ux = v3(1.0, 0.0, 0.0), uy = v3(0.0, 1.0, 0.0), uz = v3(0.0, 0.0, 1.0), org = v3(0.0, 0.0, 0.0);
   auto emit = [&](const std::vector<Tri>& tris) {
     for (const Tri& t : tris) {
@@ -450,6 +455,7 @@ pth_scene* pth_scene_ganesha_from_mesh(int32_t width, int32_t height, const std:
                                        const std::vector<double>& Z, const std::vector<int32_t>& tri, bool sky_bg) {
   pth_scene* s = new pth_scene();
   const Camera cam = camera_create(v3(328.0, 70.282, 345.0), v3(328.0, 10.0, 0.0), v3(-0.00212272, 0.998201, -0.0599264), (double)width / (double)height, 30.0);
+  s->look(v3(328.0, 70.282, 345.0), v3(328.0, 10.0, 0.0));
   const int mat = s->material(PTX_MAT_LAMBERTIAN, s->solid(0.1, 0.7, 0.2));
   for (size_t i = 0; i < X.size(); ++i) s->vertex(camera_transform(cam, v3(X[i], Y[i], Z[i])));
   double uv[6];

@@ -60,10 +60,11 @@ class Integrator:
     (image, rotation, bilinear), for Scene.set_environment; ``images``: {texture index: image or (image, bilinear, repeat)} for
     Scene.set_texture_image.  None leaves the scene's as they are.  ``environment_sampling``: True / False for
     Scene.set_environment_sampling -- with "sampled" lighting the light density then includes (or, on a scene without emissive
-    triangles, is) the environment's; True is applied after the environment and before the lighting mode, which may need it."""
+    triangles, is) the environment's; True is applied after the environment and before the lighting mode, which may need it.
+    ``lens``: (radius, focus_distance) for Scene.set_lens, the thin-lens camera; None leaves the scene's as it is."""
 
     def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-                 environment=None, images=None, environment_sampling=None):
+                 environment=None, images=None, environment_sampling=None, lens=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
@@ -73,6 +74,8 @@ class Integrator:
             self._scene.set_lighting(lighting)
         if film is not None:
             self._scene.set_film(*film)
+        if lens is not None:
+            self._scene.set_lens(*lens)
         if environment is not None:
             self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
         if environment_sampling is not None:
@@ -88,9 +91,9 @@ class Integrator:
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-               environment=None, images=None, environment_sampling=None):
+               environment=None, images=None, environment_sampling=None, lens=None):
         return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images,
-                   environment_sampling)
+                   environment_sampling, lens)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
