@@ -15,6 +15,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import update_reference as R
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -254,60 +256,17 @@ def test_error_with_counts(P, torch, prefixes):
 
 
 # ---------------------------------------------------------------- 5. the rule, restated
-def _ratio(s1, s2, k):
-    kd = float(k)
-    se = np.sqrt(np.maximum(0.0, s2 - s1 * s1 / kd) / (kd * (kd - 1.0)))
-    m = s1 / kd
-    e = np.sqrt((se[..., 0] * se[..., 0] + se[..., 1] * se[..., 1]) + se[..., 2] * se[..., 2])
-    d = np.sqrt((m[..., 0] * m[..., 0] + m[..., 1] * m[..., 1]) + m[..., 2] * m[..., 2])
-    return e, d
-
-
 def _restate(pref, M, K, T, F):
-    """the pass map the rounds give, and each round's count of pixels for the next round"""
-    b = min(M, N)
-    passes = np.full((H, W), b, dtype=np.int32)
-    active = np.ones((H, W), dtype=bool)
-    actives = []
-    while b < N:
-        e, d = _ratio(*pref[b], b)
-        if T > 0:
-            active &= ~(e <= T * np.maximum(d, F))
-        actives.append(int(active.sum()))
-        if not active.any():
-            return passes, actives
-        b = min(b + K, N)
-        passes[active] = b
-    actives.append(0)
-    return passes, actives
+    """the pass map the rounds give, and each round's count of pixels for the next round (tests/update_reference.py)"""
+    return R.restate_rounds(pref, W, H, N, M, K, T, F)
 
 
 def _targets(pref, M, K, F):
     """two targets at least 1e-6 relative from every pixel's e / d at every round boundary"""
-    ratios = []
-    for b in range(min(M, N), N, K):
-        e, d = _ratio(*pref[b], b)
-        ratios.append((e / np.maximum(d, F)).ravel())
-    r = np.unique(np.concatenate(ratios))
-    r = r[np.isfinite(r) & (r > 0)]
-    out = []
-    for q in (0.35, 0.6):
-        i = int(q * len(r))
-        while True:
-            t = 0.5 * (r[i] + r[i + 1])
-            if np.abs(r - t).min() >= 1e-6 * t:
-                break
-            i += 1
-        out.append(t)
-    return out
+    return R.targets(pref, N, M, K, F)
 
 
-def _assembled(pref, passes):
-    s1, s2 = np.zeros((H, W, 3)), np.zeros((H, W, 3))
-    for k in np.unique(passes):
-        at = passes == k
-        s1[at], s2[at] = pref[int(k)][0][at], pref[int(k)][1][at]
-    return s1, s2
+_assembled = R.assembled
 
 
 @pytest.mark.parametrize("kind", KINDS)
