@@ -2302,6 +2302,31 @@ __device__ __forceinline__ double pt_env_pd(const PtSceneDev& sc, V3 w) {
   return st > 0.0 ? ((wt / total) * ((double)W * (double)H)) / ((2.0 * (pi * pi)) * st) : 0.0;
 }
 
+/* PT_CAMERA_CARRY (default 1): the camera launches of k_bounce_carry hand shade 0 the decoded sample, the camera direction and the hit
+ * distance the same lane held a few instructions earlier (PtCameraCarry), instead of storing hits.t[i] behind a pair of fences and
+ * having every category step decode the index, derive the direction and load the distance again.  The same values, so the same
+ * arithmetic on them.  With it the TILE launches request their chunk's tile record before the camera direction is derived instead of
+ * where it is used.  0: the camera branch without either (tools/build_variant.sh builds the A/B partner with -DPT_CAMERA_CARRY=0). */
+#ifndef PT_CAMERA_CARRY
+#define PT_CAMERA_CARRY 1
+#endif
+/* of ps only id, offset and valid are read after the walk: the caller leaves the rest zero and the registers go */
+struct PtCameraCarry {
+  PtPrimarySample ps;
+  V3 d;
+  double t; /* sphere scenes; with triangles in the scene the shade step recomputes it as for a queued ray */
+};
+__device__ __forceinline__ PtCameraCarry pt_camera_carry(uint32_t id, int offset, bool valid, V3 d, double t) {
+  PtCameraCarry c;
+  c.ps.x = c.ps.y = c.ps.gy = c.ps.pass_in_batch = 0;
+  c.ps.id = id;
+  c.ps.offset = offset;
+  c.ps.valid = valid;
+  c.d = d;
+  c.t = t;
+  return c;
+}
+
 /* The body of `loop` in Integrator.path_tracer (integrator.ml:30-66) for entry i of the queue (PRIMARY: virtual
  * entry i = a camera sample).  CAT = the entry's shading category if the kernel is specialised for one.
  * LIT (emissive scenes in lighting modes 1 and 2 only; mode 0 never launches it): emission is summed in path order,
@@ -2315,7 +2340,8 @@ template <bool EMIT, bool PRIMARY, int CAT, bool LIT = false, bool IMG = false>
 __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQueue& q, const PtHits& hits, const PtContrib& contrib,
                                                const double* __restrict__ alpha, int bounce, int last_bounce,
                                                const PtGenParams& g, uint32_t i, bool live, PtShadeOut& so,
-                                               int known_slot = PT_SLOT_HOLE /* the entry's hit slot if the caller holds it */) {
+                                               int known_slot = PT_SLOT_HOLE /* the entry's hit slot if the caller holds it */,
+                                               const PtCameraCarry* cam = nullptr /* PRIMARY: the sample, its ray and its hit distance if the caller's lane holds them */) {
     const double pi = 3.14159265358979323846;
     bool keep = false;
     V3 n_o = v3(0, 0, 0), n_d = v3(0, 0, 0), n_attn = v3(0, 0, 0), n_emit = v3(0, 0, 0);
@@ -2323,14 +2349,17 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
     int offset = 0;
     PtPrimarySample ps;
     if (PRIMARY && live) {
-      ps = pt_primary_decode(g, i);
+      ps = cam ? cam->ps : pt_primary_decode(g, i);
       live = ps.valid;
     }
     if (live) {
       V3 o, d, attn0, emit0 = v3(0.0, 0.0, 0.0);
       if (PRIMARY) {
         o = v3(0.0, 0.0, 0.0);
-        d = pt_primary_dir(sc, g, ps, alpha); /* (handed over by the walk as a 32-byte {t, direction} record instead: headline +-0, cornell +2 %, mesh +3 %: profiles/r05_ab_primary_dir.txt) */
+        /* derived again for a ray that another lane or an earlier launch walked (k_shade_pool, k_bounce's pool steps): handing it over
+         * through memory as a 32-byte {t, direction} record measured headline +-0, cornell +2 %, mesh +3 % (profiles/r05_ab_primary_dir.txt).
+         * k_bounce_carry's camera launch shades in the lane that walked, and no byte moves: cam (profiles/pr_ab_camera_carry.txt) */
+        d = cam ? cam->d : pt_primary_dir(sc, g, ps, alpha);
         attn0 = v3(1.0, 1.0, 1.0); /* Color.white, integrator.ml:68 */
         id = ps.id;
         offset = ps.offset;
@@ -2365,7 +2394,7 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
             (void)pt_triangle_intersect(pt_load_v3(tvx), pt_load_v3(tvx + 3), pt_load_v3(tvx + 6), o, d, 0.0, PT_MAX_FINITE, &t_hit, &bu, &bv);
           }
         } else {
-          t_hit = hits.t[i];
+          t_hit = (PRIMARY && cam) ? cam->t : hits.t[i];
           const double2* sp = (const double2*)(sc.sph + (size_t)slot * 4);
           const double2 s0 = sp[0], s1 = sp[1];
           geom.cx = s0.x;
@@ -3321,6 +3350,38 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
          * in turn, its lanes live */
         live = i < n;
         int tile_x = 0, tile_gy = 0; /* TILE: the lane's pixel column and GLOBAL row (lane 0: the tile's first) */
+#if PT_CAMERA_CARRY
+        PtPrimarySample ps;
+        ps.x = ps.y = ps.gy = ps.pass_in_batch = ps.offset = 0;
+        ps.id = 0u;
+        ps.valid = false;
+        if (live) {
+          ps = pt_primary_decode(g, i);
+          live = ps.valid;
+          tile_x = ps.x;
+          tile_gy = ps.gy;
+        }
+        /* TILE: the chunk's record is requested here, as soon as lane 0's tile is known, so that the camera direction's arithmetic
+         * covers the load (lane 0 holds the tile's first pixel, inside the image whenever any lane is live; the record's index is
+         * checked against the grid before it forms an address) */
+        int recv = 0;
+        bool rec_ok = false; /* wave-uniform */
+        if constexpr (TILE) {
+          const uint32_t gtx = (uint32_t)(g.width + 7) >> 3, gty = (uint32_t)(g.height + 7) >> 3;
+          const uint32_t tx = (uint32_t)__builtin_amdgcn_readfirstlane(tile_x) >> 3, ty = (uint32_t)__builtin_amdgcn_readfirstlane(tile_gy) >> 3;
+          rec_ok = __ballot(live) != 0ull && tx < gtx && ty < gty;
+          if (rec_ok) {
+            /* the 32-byte record: lane k < 16 reads halfword k, the header and the slot numbers come out of it by readlane and stay scalar */
+            const uint16_t* rec = (const uint16_t*)sc.tile_lists + ((size_t)ty * gtx + tx) * 16u;
+            recv = (int)rec[lane & 15];
+          }
+        }
+        if (live) {
+          d = pt_primary_dir(sc, g, ps, alpha);
+          id = ps.id; /* (what a survivor of shade 0 is pushed with: the step leaves them alone) */
+          offset = ps.offset;
+        }
+#else
         if (live) {
           const PtPrimarySample ps = pt_primary_decode(g, i);
           live = ps.valid;
@@ -3328,10 +3389,14 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
           tile_x = ps.x;
           tile_gy = ps.gy;
         }
+#endif
         if (COUNT && !DIAG_T && live) c_seg++;
         PtTraceResult r;
         bool scanned = false; /* wave-uniform */
         if constexpr (TILE) {
+#if PT_CAMERA_CARRY
+          if (rec_ok) {
+#else
           /* lane 0 holds the tile's first pixel, inside the image whenever any lane is live; the record's index is checked against the grid */
           const uint32_t gtx = (uint32_t)(g.width + 7) >> 3, gty = (uint32_t)(g.height + 7) >> 3;
           const uint32_t tx = (uint32_t)__builtin_amdgcn_readfirstlane(tile_x) >> 3, ty = (uint32_t)__builtin_amdgcn_readfirstlane(tile_gy) >> 3;
@@ -3339,6 +3404,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
             /* the 32-byte record: lane k < 16 reads halfword k, the header and the slot numbers come out of it by readlane and stay scalar */
             const uint16_t* rec = (const uint16_t*)sc.tile_lists + ((size_t)ty * gtx + tx) * 16u;
             const int recv = (int)rec[lane & 15];
+#endif
             const uint32_t head = (uint32_t)__builtin_amdgcn_readlane(recv, 0);
             const uint32_t n_list = head & 0xffu, oct = head >> 8;
             const uint32_t dirs = (d.x >= 0.0 ? 1u : 0u) | (d.y >= 0.0 ? 2u : 0u) | (d.z >= 0.0 ? 4u : 0u); /* PtTraverser::begin */
@@ -3361,6 +3427,18 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         } else if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
           r = pt_trace_ray<MODE, COUNT, true, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
         else r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
+#if PT_CAMERA_CARRY
+        /* shade 0 runs in this lane on what it holds: the sample, the direction and the hit distance stay in registers; nothing is
+         * stored to hits.t and there is nothing to fence (fence_wg: the queued launches never used it either).  They stay in the
+         * registers of what the turn walks next, which a lane does not need before its own category step has run: the path id and the
+         * sampler offset where a survivor's are, the camera direction in d, the hit distance in o.x (a camera ray's origin is zero) */
+        if (live) {
+          sl = r.slot;
+          my_cat = r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot];
+        }
+        o = v3(r.t, 0.0, 0.0);
+        (void)fence_wg;
+#else
         if (live) {
           if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
           sl = r.slot;
@@ -3376,6 +3454,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         }
         o = v3(0.0, 0.0, 0.0);
         d = v3(0.0, 0.0, -1.0);
+#endif
         PT_TM8(c_nodes);
         if (DIAG_T) c_filter[1] += (lane == 0);
       } else {
@@ -3388,26 +3467,34 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         c = __builtin_amdgcn_readlane(my_cat, __ffsll((long long)lm) - 1);
       }
       /* (PRIMARY: every category some lane holds, in turn; else the chunk's one) */
-#define PT_CARRY_STEP(K, ...)                                                                                          \
+#define PT_CARRY_STEP(K, SLOT)                                                                                         \
   if (PRIMARY ? __ballot(my_cat == K) != 0ull : c == K) {                                                              \
     PtShadeOut so;                                                                                                     \
-    pt_shade_entry<EMIT, PRIMARY, K>(scl, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, ##__VA_ARGS__); \
+    const PtCameraCarry cam = pt_camera_carry(id, offset, live, d, o.x);                                               \
+    pt_shade_entry<EMIT, PRIMARY, K>(scl, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, SLOT, CAM_CARRY ? &cam : nullptr); \
     if (so.keep) {                                                                                                     \
       valid = true;                                                                                                    \
       o = so.n_o;                                                                                                      \
       d = so.n_d;                                                                                                      \
       attn = so.n_attn;                                                                                                \
       emit = so.n_emit;                                                                                                \
-      id = so.id;                                                                                                      \
-      offset = so.offset;                                                                                              \
+      if (!CAM_CARRY) {                                                                                                \
+        id = so.id;                                                                                                    \
+        offset = so.offset;                                                                                            \
+      }                                                                                                                \
     }                                                                                                                  \
   }
-      PT_CARRY_STEP(PT_CAT_MISS)
+      constexpr bool CAM_CARRY = PRIMARY && PT_CAMERA_CARRY != 0;
+      PT_CARRY_STEP(PT_CAT_MISS, PT_SLOT_HOLE)
       PT_CARRY_STEP(PT_CAT_LAMBERT_SOLID, sl)
       PT_CARRY_STEP(PT_CAT_LAMBERT_CHECKER, sl)
       PT_CARRY_STEP(PT_CAT_METAL, sl)
       PT_CARRY_STEP(PT_CAT_DIELECTRIC, sl)
 #undef PT_CARRY_STEP
+      if (CAM_CARRY && !valid) { /* no ray to walk: the lane's registers as every other turn leaves them */
+        o = v3(0.0, 0.0, 0.0);
+        d = v3(0.0, 0.0, -1.0);
+      }
       PT_TM8(c_prims);
       if (last_bounce || __ballot(valid) == 0ull) continue; /* nothing survives the step */
       if (COUNT && !DIAG_T && valid) c_seg++;
