@@ -239,6 +239,20 @@ let environment_sampling scene =
   let on, total = environment_sampling_raw scene in
   on <> 0, total
 
+(* Cone-sampling emissive spheres (ptx_scene_set_sphere_light_sampling; the rule is in include/ptx.h): with [Sampled] lighting the
+   light half also draws directions towards the scene's emissive spheres, uniformly over the cone each spans from the hit, and
+   [Sampled] then accepts a scene without emissive triangles.  Needs 1 .. 64 emissive spheres.  Sticky.  Failure when the count is
+   outside that, when turning it off would leave [Sampled] nothing to sample, or while a render runs on the scene.
+   sphere_lights: (on, the number of sphere lights, the joined light table's total weight). *)
+external set_sphere_light_sampling_int : scene -> int -> unit = "ptx_ml_set_sphere_light_sampling_stub"
+external sphere_lights_raw : scene -> int * int * float = "ptx_ml_sphere_lights_stub"
+
+let set_sphere_light_sampling scene on = set_sphere_light_sampling_int scene (if on then 1 else 0)
+
+let sphere_lights scene =
+  let on, n, total = sphere_lights_raw scene in
+  on <> 0, n, total
+
 (* The thin-lens camera (ptx_scene_set_lens; the rule is in include/ptx.h): a lens of [radius] around the camera's origin, focused on
    the plane [focus_distance] in front of it, so that what lies off that plane blurs.  [radius] 0. switches the lens off, which is a
    scene's first state: the pinhole Camera.ray, bit for bit.  Sticky: every later render of the scene reads it.  Failure for a negative

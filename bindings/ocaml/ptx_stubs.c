@@ -360,6 +360,39 @@ CAMLprim value ptx_ml_environment_sampling_stub(value handle) {
   CAMLreturn(tuple);
 }
 
+/* external set_sphere_light_sampling_int : scene -> int -> unit = "ptx_ml_set_sphere_light_sampling_stub"
+ * (ptx_scene_set_sphere_light_sampling).  What a running render samples: like set_lighting it takes the scene exclusively and raises
+ * Failure while a render runs on another thread or domain, and Failure with the library's message for a refused call. */
+CAMLprim value ptx_ml_set_sphere_light_sampling_stub(value handle, value on) {
+  CAMLparam2(handle, on);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_sphere_light_sampling: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_sphere_light_sampling: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_scene_set_sphere_light_sampling(s, Long_val(on) != 0 ? 1 : 0);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_sphere_light_sampling: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external sphere_lights_raw : scene -> int * int * float = "ptx_ml_sphere_lights_stub" (ptx_scene_sphere_lights) */
+CAMLprim value ptx_ml_sphere_lights_stub(value handle) {
+  CAMLparam1(handle);
+  CAMLlocal2(tuple, total_v);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.sphere_lights: scene already destroyed");
+  int32_t on = 0, n = 0;
+  double total = 0.0;
+  if (ptx_scene_sphere_lights(s, &on, &n, &total) != 0) caml_failwith(ptx_last_error());
+  total_v = caml_copy_double(total);
+  tuple = caml_alloc_tuple(3);
+  Store_field(tuple, 0, Val_long(on));
+  Store_field(tuple, 1, Val_long(n));
+  Store_field(tuple, 2, total_v);
+  CAMLreturn(tuple);
+}
+
 /* external set_lens_raw : scene -> texels -> unit = "ptx_ml_set_lens_stub" (ptx_scene_set_lens: a Bigarray of the two doubles radius,
  * focus_distance, as the other stubs take their doubles; radius 0 switches the lens off).  What a running render's camera rays are made of: like set_lighting it takes the scene exclusively and raises
  * Failure while a render runs on another thread or domain, and Failure with the library's message for a refused pair. */

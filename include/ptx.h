@@ -277,11 +277,13 @@ int32_t ptx_tile_list_stats(const ptx_scene* scene, int64_t out[5]);
  *               without emitters this is REFERENCE (there is no emission to order).
  *   SAMPLED     PATH_ORDER with diffuse_plus_light = 1/2 cosine + 1/2 the emissive triangles, sampled uniformly by area from the hit's
  *               own two sampler dimensions (the sampler's dimension stays 2 + 2 * max_bounces).  The light list is built the first time
- *               this mode is set: the tree triangles whose material has a non-zero emit, in build-list order.  Emissive spheres and
- *               floor triangles are not sampled (they still emit when hit; the cosine half keeps the estimator unbiased).
+ *               this mode is set: the tree triangles whose material has a non-zero emit, in build-list order.  Floor triangles are
+ *               not sampled, and emissive spheres only with ptx_scene_set_sphere_light_sampling (they still emit when hit; the cosine
+ *               half keeps the estimator unbiased).
  *               PTX_ERR_ARG when the scene has no emissive tree triangle or more than PTX_MAX_LIGHT_TRIANGLES of them.
  *               (With ptx_scene_set_environment_sampling on, a scene without emissive tree triangles is accepted and the environment is
- *               sampled too: see there.)
+ *               sampled too: see there.  With ptx_scene_set_sphere_light_sampling on, likewise, and the emissive spheres are sampled
+ *               beside the triangles: see there.)
  * A host-only scene accepts the call (the light list can be inspected without a GPU).  PTX_ERR_STATE while a render runs on the
  * scene (from a progress or update callback); PTX_ERR_ARG for an unknown mode. */
 #define PTX_LIGHTING_REFERENCE 0
@@ -703,7 +705,7 @@ int32_t ptx_environment_eval(ptx_scene* scene, int64_t n, const double* dirs, do
  *                            divisor = 0.5 * diffuse_pd + 0.5 * env_pd
  *     The environment direction is rotated into shader space and back exactly as the triangle direction is; env_pd is evaluated for
  *     the world direction the scattered ray will have.  Everything else of PTX_LIGHTING_SAMPLED, where a path ends included, is unchanged.
- * What it does not help: an environment behind glass or seen in a mirror (specular scatters do not sample), emissive spheres, and the
+ * What it does not help: an environment behind glass or seen in a mirror (specular scatters do not sample), and the
  * bilinear interpolant's departure from the per-texel density (variance only).  No shadow rays, no multiple importance sampling. */
 int32_t ptx_scene_set_environment_sampling(ptx_scene* scene, int32_t on);
 /* The flag and, while it is on, the total weight T (0.0 while off).  Either out pointer may be NULL. */
@@ -715,6 +717,65 @@ int32_t ptx_environment_distribution(const ptx_scene* scene, double* marginal_ou
  * be on).  ab: n x 2 -> dirs_out: n x 3 and texel_out (nullable): n x 2 {ix, iy} as drawn;  dirs: n x 3 -> pd_out: n. */
 int32_t ptx_environment_sample(ptx_scene* scene, int64_t n, const double* ab, double* dirs_out, int32_t* texel_out);
 int32_t ptx_environment_pdf(ptx_scene* scene, int64_t n, const double* dirs, double* pd_out);
+
+/* ---- cone-sampling emissive spheres in PTX_LIGHTING_SAMPLED ----
+ * The light half of Integrator.create ~diffuse_plus_light with the scene's emissive tree spheres beside its emissive triangles, under one
+ * table: a small lamp sphere is found by sampling the cone it spans, not by scattering alone.  Only entry points are added: no struct
+ * changes and the ABI version stays 6.
+ *
+ * ptx_scene_set_sphere_light_sampling(scene, on): sticky state of the handle, default off; the replicas a scene owns follow it and
+ * ptx_scene_replicate copies it; a host-only scene accepts it.  Turning it on needs at least one emissive tree sphere (a sphere whose
+ * material has a non-zero emit) and at most PTX_MAX_LIGHT_SPHERES of them: anything else is PTX_ERR_ARG with a message that names the
+ * count, and nothing changes.  PTX_ERR_STATE while a render runs on the scene.  While it is on,
+ * ptx_scene_set_lighting(PTX_LIGHTING_SAMPLED) also accepts a scene without emissive tree triangles; turning it off while the mode is
+ * PTX_LIGHTING_SAMPLED and nothing else is left to sample is PTX_ERR_STATE ("set another lighting mode first").  While it is off nothing
+ * differs from a handle that never heard of it: emissive spheres emit when hit and none is sampled.  In modes 0 and 1 the flag has no
+ * effect on a pixel.
+ *
+ * The rule, operation for operation (binary64, no contraction; dot a b = fma(a.x, b.x, fma(a.y, b.y, a.z * b.z)) as everywhere in the
+ * shade step; sqrt is IEEE; sin, cos and the hypot inside normalize are pt_math.h's; pi = 3.14159265358979323846):
+ *   The list (built on the host): the tree spheres whose material emits, in build-list order; sphere light k holds its centre c_k, r_k,
+ *     r2_k = r_k * r_k and W_k = (2.0 * pi) * r2_k -- the area a point outside can see at most, what a two-sided triangle's A is.
+ *     cum continues the triangles' running sum: cum_k = cum_(k-1) + W_k, starting from the triangles' A_total (0.0 without any).  The
+ *     triangles' records keep their bits.  W_total = the last running sum of the joined table (triangles first, spheres behind them);
+ *     it stands wherever the triangle rule says A_total.  Emission does not weight the pick.
+ *   Sample, in the light half, at the point p, from the rule's (2u, v):
+ *     x = 2u * W_total;  k = the first entry of the joined table with x < cum_k, or the last entry if there is none;
+ *     before = cum_(k-1), 0.0 for k = 0;  u2 = min((x - before) / W_k, 1.0) (A_k for a triangle, which then goes on as the triangle rule says)
+ *     k a sphere:  f = c_k - p;  d2 = dot f f;  phi = (v * 2.0) * pi;  (sn, cs) = sincos(phi)
+ *       d2 <= r2_k (p inside or on the light: the whole sphere of directions, world space, no frame):
+ *         z = 1.0 - 2.0 * u2;  m = 1.0 - z * z, taken as 0.0 unless m > 0;  s = sqrt(m);  w = (s * cs, s * sn, z)
+ *       otherwise:
+ *         s2 = r2_k / d2;  q = s2 / (1.0 + sqrt(1.0 - s2))   (1 - cos(theta_max) without the cancellation)
+ *         t = u2 * q;  ct = 1.0 - t;  st = sqrt(t * (2.0 - t))
+ *         w = rotate_inv (Shader_space.create (normalize f)) (st * cs, st * sn, ct)   -- the shade step's own frame rule
+ *           (shader_space.ml:11-23 with Quaternion.normalize and Quaternion.transform, as at every hit)
+ *     The world direction w is rotated into the hit's shader space and back exactly as the triangle direction is.
+ *   Density of the world direction w at p, added to the triangles' sum (whose terms read t^2 / (W_total * |n . w|)), sphere lights in
+ *   list order:
+ *     f, d2 as above;  share = W_k / W_total
+ *     d2 <= r2_k:  pd = pd + share / (4.0 * pi)
+ *     otherwise:   bp = dot f w;  g = f - bp * w (per component);  if bp > 0 and r2_k - dot g g >= 0:  pd = pd + share / ((2.0 * pi) * q)
+ *     -- the cone test is the discriminant on the perpendicular offset, not d2 - bp^2: a far, small lamp is decided without cancellation.
+ *   The mixture is PTX_LIGHTING_SAMPLED's own with "the triangles" read as "the joined table": 1/2 cosine + 1/2 lights; with
+ *   environment sampling on 1/2 + 1/4 + 1/4, and 1/2 + 1/2 environment when the joined table is empty.  Emission stays in path order.
+ * What it does not help: lamps behind glass or seen in a mirror (specular scatters do not sample), floor triangles, scenes with more
+ * than 64 lights of a kind (no light hierarchy), and a lamp hidden from the point (no shadow rays: the draw is spent on the occluder). */
+#define PTX_MAX_LIGHT_SPHERES 64
+int32_t ptx_scene_set_sphere_light_sampling(ptx_scene* scene, int32_t on);
+/* The flag, and while it is on the number of sphere lights and W_total, the joined table's last running sum (0 and 0.0 while off).
+ * ptx_scene_lighting keeps reporting the triangles' own count and area.  Any out pointer may be NULL. */
+int32_t ptx_scene_sphere_lights(const ptx_scene* scene, int32_t* on_out, int32_t* n_out, double* weight_out);
+/* Host-only inspection of the joined table (works on a host-only scene): triangles_out (nullable) 14 doubles per light triangle
+ * {a, b, c, unit normal, A, cum} -- filled once PTX_LIGHTING_SAMPLED has been set, ptx_scene_lighting gives the count -- and
+ * spheres_out (nullable) 8 doubles per sphere light {c, r, r2, W, cum, 0.0}, filled while sphere light sampling is on. */
+int32_t ptx_light_table(const ptx_scene* scene, double* triangles_out, double* spheres_out);
+/* Diagnostics, in the family of ptx_environment_sample / _pdf: the shade step's own two light-half functions, triangles and spheres
+ * together, on explicit HOST inputs; the lighting mode must be PTX_LIGHTING_SAMPLED with a non-empty joined table.  points: n x 3;
+ * uv: n x 2 = the hit's two sampler dimensions as the light half takes them (x = (2.0 * u) * W_total);  dir_out: n x 3 world-space unit
+ * directions;  index_out (nullable): n, the joined table's entry drawn.  dirs: n x 3 world directions -> pd_out: n. */
+int32_t ptx_light_sample(ptx_scene* scene, int64_t n, const double* points, const double* uv, double* dir_out, int32_t* index_out);
+int32_t ptx_light_pdf(ptx_scene* scene, int64_t n, const double* points, const double* dirs, double* pd_out);
 
 /* ---- thin-lens camera: aperture and focus distance ----
  * Camera.ray (camera.ml:93-102) is a pinhole: every ray starts at P3.origin.  ptx_scene_set_lens gives the camera a lens, and with it

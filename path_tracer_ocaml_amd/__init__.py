@@ -45,6 +45,7 @@ EXPORTS = (
     "ptx_scene_set_environment_sampling", "ptx_scene_environment_sampling", "ptx_environment_distribution",
     "ptx_environment_sample", "ptx_environment_pdf",
     "ptx_scene_set_lens", "ptx_scene_lens",
+    "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -152,6 +153,12 @@ def lib():
         L.ptx_environment_distribution.argtypes = [C.c_void_p, dp, dp]
         L.ptx_environment_sample.argtypes = [C.c_void_p, C.c_int64, dp, dp, ip]
         L.ptx_environment_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp]
+    if hasattr(L, "ptx_scene_set_sphere_light_sampling"):  # (likewise)
+        L.ptx_scene_set_sphere_light_sampling.argtypes = [C.c_void_p, C.c_int32]
+        L.ptx_scene_sphere_lights.argtypes = [C.c_void_p, ip, ip, dp]
+        L.ptx_light_table.argtypes = [C.c_void_p, dp, dp]
+        L.ptx_light_sample.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp, ip]
+        L.ptx_light_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp]
     if hasattr(L, "ptx_walk_rays"):  # (likewise)
         L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
     if hasattr(L, "ptx_scene_set_lens"):  # (likewise)
@@ -349,6 +356,50 @@ class Scene:
         d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
         out = np.zeros(len(d))
         _check(lib().ptx_environment_pdf(self._h, len(d), _dp(d), _dp(out)))
+        return out
+
+    def set_sphere_light_sampling(self, on=True):
+        """ptx_scene_set_sphere_light_sampling: in "sampled" lighting the light half also draws directions towards the scene's
+        emissive tree spheres, uniformly over the cone each spans from the hit (and "sampled" then accepts a scene without emissive
+        triangles).  Needs 1 .. 64 emissive spheres.  Sticky."""
+        _check(lib().ptx_scene_set_sphere_light_sampling(self._h, 1 if on else 0))
+
+    def sphere_lights(self):
+        """ptx_scene_sphere_lights: (on, the number of sphere lights, W_total = the joined light table's last running sum; 0 and
+        0.0 while off)"""
+        on, n = C.c_int32(0), C.c_int32(0)
+        total = C.c_double(0.0)
+        _check(lib().ptx_scene_sphere_lights(self._h, C.byref(on), C.byref(n), C.byref(total)))
+        return bool(on.value), n.value, total.value
+
+    def light_table(self):
+        """ptx_light_table (host only): (the light triangles' records (n, 14) {a, b, c, normal, A, cum}, the sphere lights'
+        records (n, 8) {c, r, r2, W, cum, 0})"""
+        n_tri = self.lighting()[1]
+        n_sph = self.sphere_lights()[1]
+        tri, sph = np.zeros((n_tri, 14)), np.zeros((n_sph, 8))
+        _check(lib().ptx_light_table(self._h, _dp(tri) if n_tri else None, _dp(sph) if n_sph else None))
+        return tri, sph
+
+    def light_sample(self, points, uv):
+        """ptx_light_sample: the shade step's own light-half sampling function, triangles and spheres together, at the (n, 3) points
+        on the (n, 2) sampler pairs uv -> (world-space unit directions (n, 3), the joined table's entry drawn (n,))"""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+        if len(p) != len(uv):
+            raise ValueError("points and uv must have the same length")
+        dirs, index = np.zeros((len(p), 3)), np.zeros(len(p), dtype=np.int32)
+        _check(lib().ptx_light_sample(self._h, len(p), _dp(p), _dp(uv), _dp(dirs), _ip(index)))
+        return dirs, index
+
+    def light_pdf(self, points, directions):
+        """ptx_light_pdf: the light half's density per solid angle of each of the (n, 3) world directions at the (n, 3) points"""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if len(p) != len(d):
+            raise ValueError("points and directions must have the same length")
+        out = np.zeros(len(p))
+        _check(lib().ptx_light_pdf(self._h, len(p), _dp(p), _dp(d), _dp(out)))
         return out
 
     def texture_eval(self, index, uv):

@@ -2196,12 +2196,77 @@ struct PtShadeOut {
 /* (the table through the constant address space: it is never written while a kernel runs, and a load whose address is wave-uniform
  * is then a scalar load whatever the kernel has stored before it -- from the global address space the compiler keeps vector loads) */
 typedef const double __attribute__((address_space(4))) PtConstDouble;
-__device__ __forceinline__ V3 pt_light_sample(const PtSceneDev& sc, V3 p, double u, double v) {
+/* ptx_scene_set_sphere_light_sampling (include/ptx.h states the rule).  The sphere lights' records lie behind the triangles' in the
+ * light table (pt_scene.h, PT_SLIGHT_*).  The two sphere arms are inlined.  Measured both ways (tools/kernel_resources.py against the
+ * parent): inline, the 22 LIT kernels without IMG (128 VGPRs, 4 waves) go from 14..28 spilled VGPRs and 28..128 bytes of scratch to
+ * 17..45 and 48..168, and the 22 LIT && IMG ones (168 VGPRs) keep theirs; as __noinline__ functions all 44 are worse (26..60 spilled
+ * VGPRs, 112..240 bytes; the IMG ones 0 -> 32..64 bytes), one arm inlined and one not lies between, and marking the branch unlikely
+ * changes nothing.  No kernel loses a wave per SIMD.  DESIGN.md section 7 has the cost with the option off.
+ * 1 - cos(theta_max) of the cone a sphere of squared radius r2 spans from a point at squared distance d2 > r2 of its centre, without
+ * the cancellation: */
+__device__ __forceinline__ double pt_sphere_cone_q(double r2, double d2) {
+  const double s2 = r2 / d2;
+  return s2 / (1.0 + pt_sqrt_nonneg(1.0 - s2));
+}
+/* the sphere arm of Pdf.sample's light half: sphere light record S (a per-lane gather), (u2, v) in [0, 1]^2; the world-space unit
+ * direction -- uniform over the cone the sphere spans from p, over the whole sphere of directions for a p inside or on it */
+__device__ __forceinline__ V3 pt_sphere_light_sample(const double* __restrict__ S, V3 p, double u2, double v) {
+  const double pi = 3.14159265358979323846;
+  const double r2 = S[PT_SLIGHT_R2];
+  const V3 f = v3_sub(v3(S[0], S[1], S[2]), p);
+  const double d2 = v3_dot(f, f);
+  const double phi = (v * 2.0) * pi;
+  double sn, cs;
+  pt_sincos(phi, &sn, &cs);
+  if (d2 <= r2) {
+    const double z = 1.0 - 2.0 * u2;
+    const double m = 1.0 - z * z;
+    const double s = pt_sqrt_nonneg(m > 0.0 ? m : 0.0);
+    return v3(s * cs, s * sn, z);
+  }
+  const double t = u2 * pt_sphere_cone_q(r2, d2);
+  const double ct = 1.0 - t, st = pt_sqrt_nonneg(t * (2.0 - t));
+  return pt_quat_transform(pt_quat_conj(pt_shader_rotation(v3_normalize(f))), v3(st * cs, st * sn, ct));
+}
+/* the sphere lights' part of Pdf.eval's light half: to pd, the triangles' running sum, every sphere light whose cone holds w adds, in
+ * list order, its share W_k / W_total of the draws over the cone's solid angle.  The table is indexed uniformly: scalar loads. */
+__device__ __forceinline__ double pt_sphere_light_pd(const PtConstDouble* __restrict__ stable, int ns, double total, V3 p, V3 w, double pd) {
+  const double pi = 3.14159265358979323846;
+  for (int k = 0; k < ns; ++k) {
+    const PtConstDouble* S = stable + k * PT_SLIGHT_DOUBLES;
+    const double r2 = S[PT_SLIGHT_R2], share = S[PT_SLIGHT_W] / total;
+    const V3 f = v3_sub(v3(S[0], S[1], S[2]), p);
+    const double d2 = v3_dot(f, f);
+    if (d2 <= r2) {
+      pd = pd + share / (4.0 * pi);
+    } else {
+      const double bp = v3_dot(f, w);
+      const V3 g = v3_sub(f, v3_scale(w, bp));
+      if (bp > 0.0 && r2 - v3_dot(g, g) >= 0.0) pd = pd + share / ((2.0 * pi) * pt_sphere_cone_q(r2, d2));
+    }
+  }
+  return pd;
+}
+/* Pdf.sample of the light half over the joined table, triangles first and the sphere lights behind them (none unless
+ * ptx_scene_set_sphere_light_sampling is on: the branch on their count is wave-uniform).  k_out: the index of the light drawn. */
+__device__ __forceinline__ V3 pt_light_sample(const PtSceneDev& sc, V3 p, double u, double v, int* k_out = nullptr) {
   const double x = (2.0 * u) * sc.light_area;
   const PtConstDouble* table = (const PtConstDouble*)sc.lights;
-  int k = sc.n_lights - 1;
-  for (int j = sc.n_lights - 2; j >= 0; --j)
+  const int nt = sc.n_lights, ns = sc.n_sphere_lights;
+  int k = nt + ns - 1;
+  if (ns > 0) { /* (wave-uniform) */
+    const PtConstDouble* stable = table + nt * PT_LIGHT_DOUBLES;
+    for (int j = ns - 2; j >= 0; --j)
+      if (x < stable[j * PT_SLIGHT_DOUBLES + PT_SLIGHT_CUM]) k = nt + j;
+  }
+  for (int j = ns > 0 ? nt - 1 : nt - 2; j >= 0; --j)
     if (x < table[j * PT_LIGHT_DOUBLES + PT_LIGHT_CUM]) k = j; /* ends at the FIRST k with x < cum_k (the last if none) */
+  if (k_out) *k_out = k;
+  if (ns > 0 && k >= nt) {
+    const double* S = sc.lights + (size_t)nt * PT_LIGHT_DOUBLES + (size_t)(k - nt) * PT_SLIGHT_DOUBLES;
+    const double before = k > nt ? S[PT_SLIGHT_CUM - PT_SLIGHT_DOUBLES] : (nt > 0 ? S[PT_LIGHT_CUM - PT_LIGHT_DOUBLES] : 0.0);
+    return pt_sphere_light_sample(S, p, pt_base_min((x - before) / S[PT_SLIGHT_W], 1.0), v);
+  }
   const double* L = sc.lights + (size_t)k * PT_LIGHT_DOUBLES;
   const double before = k > 0 ? L[PT_LIGHT_CUM - PT_LIGHT_DOUBLES] : 0.0;
   const double u2 = pt_base_min((x - before) / L[PT_LIGHT_AREA], 1.0);
@@ -2212,7 +2277,8 @@ __device__ __forceinline__ V3 pt_light_sample(const PtSceneDev& sc, V3 p, double
   return v3_normalize(v3_sub(q, p));
 }
 /* Pdf.eval of the light half for the world direction w at p: every light the ray (p, w) meets, by the walk's own element test,
- * contributes its solid-angle density t^2 / (A_total |n . w|).  The table is indexed uniformly: scalar loads. */
+ * contributes its solid-angle density t^2 / (A_total |n . w|), and the sphere lights theirs.  The table is indexed uniformly: scalar
+ * loads. */
 __device__ __forceinline__ double pt_light_pd(const PtSceneDev& sc, V3 p, V3 w) {
   double pd = 0.0;
   const PtConstDouble* table = (const PtConstDouble*)sc.lights;
@@ -2222,6 +2288,8 @@ __device__ __forceinline__ double pt_light_pd(const PtSceneDev& sc, V3 p, V3 w) 
     if (pt_triangle_intersect(v3(L[0], L[1], L[2]), v3(L[3], L[4], L[5]), v3(L[6], L[7], L[8]), p, w, 0.0, PT_MAX_FINITE, &t, &bu, &bv))
       pd = pd + (t * t) / (sc.light_area * pt_fabs(v3_dot(v3(L[9], L[10], L[11]), w)));
   }
+  if (sc.n_sphere_lights > 0) /* (wave-uniform) */
+    pd = pt_sphere_light_pd(table + sc.n_lights * PT_LIGHT_DOUBLES, sc.n_sphere_lights, sc.light_area, p, w, pd);
   return pd;
 }
 
@@ -2426,7 +2494,7 @@ __device__ __forceinline__ void pt_shade_entry(const PtSceneDev& sc, const PtQue
             /* ... with environment sampling: su < 0.25 the triangles on 2u := 4 su, su < 0.5 the environment on (4 su - 1, v); without
              * light triangles su < 0.5 the environment on (2 su, v) (both wave-uniform) */
             const bool env_on = LIT && IMG && sampled && sc.env_sample != 0;
-            const bool tri_on = sampled && !(env_on && sc.n_lights == 0);
+            const bool tri_on = sampled && !(env_on && sc.n_lights + sc.n_sphere_lights == 0);
             const double hu = sampled ? 2.0 * su - 1.0 : su;
             if (tri_on && su < (env_on ? 0.25 : 0.5)) {
               wo = pt_quat_transform(sf.rot, pt_light_sample(sc, point, env_on ? 2.0 * su : su, sv)); /* Pdf.sample returns a shader-space direction */
@@ -4129,6 +4197,24 @@ __global__ void k_environment_pdf(PtSceneDev sc, long long n, const double* __re
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   out[i] = pt_env_pd(sc, v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+}
+
+/* ptx_light_sample / ptx_light_pdf: the shade step's two light-half functions, triangles and spheres together, on explicit inputs */
+__global__ void k_light_sample(PtSceneDev sc, long long n, const double* __restrict__ points, const double* __restrict__ uv,
+                               double* __restrict__ dirs, int32_t* __restrict__ index) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int k;
+  const V3 d = pt_light_sample(sc, v3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), uv[2 * i], uv[2 * i + 1], &k);
+  dirs[3 * i] = d.x;
+  dirs[3 * i + 1] = d.y;
+  dirs[3 * i + 2] = d.z;
+  if (index) index[i] = k;
+}
+__global__ void k_light_pdf(PtSceneDev sc, long long n, const double* __restrict__ points, const double* __restrict__ dirs, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = pt_light_pd(sc, v3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
 }
 
 /* copies explicit rays into a queue (ptx_intersect_rays) */

@@ -179,7 +179,13 @@ struct PtSceneDev {
    * the root box, so this bounds every node's magnitude.  The binary32 node filter applies to a ray only if
    * (root_mag + max|o|) * max|1/d| < 2^100 -- then no binary32 intermediate of the filter can overflow (kernels.hip, begin()). */
   float root_mag;
-  float pad_f;
+  union { /* (one word, two names, like env_sample below) */
+    float pad_f;
+    /* ptx_scene_set_sphere_light_sampling is on, in lighting mode 2: this many sphere light records lie behind the n_lights triangle
+     * records of `lights` (PT_SLIGHT_* below), and light_area is the joined table's last running sum.  Read only by the instantiations
+     * flagged LIT, behind a wave-uniform branch */
+    int32_t n_sphere_lights;
+  };
   double cam_llx, cam_lly, cam_vx, cam_vy;
   int32_t bg_kind;
   union { /* (one word, two names: scenes without environment sampling, and everything that only copies the struct, see padding) */
@@ -232,5 +238,15 @@ struct PtSceneDev {
 #define PT_LIGHT_DOUBLES 14
 #define PT_LIGHT_AREA 12
 #define PT_LIGHT_CUM 13
+/* ptx_scene_set_sphere_light_sampling keeps PtSceneDev as it is, as environment sampling does (its size is every kernel's argument
+ * layout: a pointer and a count appended at its end changed the register and scratch figures of kernels that never look at a light,
+ * profiles/pr_sphere_lights_kernel_resources_*.txt): the count takes a padding word, and the records lie in the light table's own
+ * buffer, right behind the triangles' (lights + n_lights * PT_LIGHT_DOUBLES), 8 doubles each: {c, r, r * r, W = (2 pi) r^2, running sum
+ * continuing the triangles', 0} */
+#define PT_SLIGHT_DOUBLES 8 /* one 64-byte record per sphere light */
+#define PT_SLIGHT_R 3
+#define PT_SLIGHT_R2 4
+#define PT_SLIGHT_W 5
+#define PT_SLIGHT_CUM 6
 
 #endif /* PT_SCENE_H */

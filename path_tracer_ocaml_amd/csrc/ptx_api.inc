@@ -313,6 +313,13 @@ struct ptx_scene {
   double lens_radius = 0.0, lens_focus = 1.0; /* ptx_scene_set_lens: radius 0 = off, the pinhole */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
+  /* Sphere light sampling (ptx_scene_set_sphere_light_sampling): the flag; the sphere light table made when it is first set
+   * (PT_SLIGHT_DOUBLES per record, its running sums continuing the triangles') and the device copy of the JOINED table -- the
+   * triangles' records as light_table_build gives them, then the spheres' -- which like d_lights is never freed or rewritten before the
+   * handle goes (queued frames keep reading it) */
+  bool sphere_sampling = false;
+  std::vector<double> sphere_table;
+  DevBuf<double> d_joined_lights;
   /* Images (ptx_scene_set_texture_image / _set_environment): per entry of the texture table and for the environment, the host copy of
    * the texel records (shared with the replicas) and this device's upload; the slot categories and shading records with the images in
    * place (scene_image_overrides) and their uploads, which dev.slot_cat / dev.slot_shade point at while any entry carries an image */
@@ -1898,6 +1905,13 @@ static void apply_lighting(ptx_scene* s) {
   s->dev.lights = lights ? s->d_lights.p : nullptr;
   s->dev.n_lights = lights ? s->host->n_emissive_tris : 0;
   s->dev.light_area = lights ? s->light_table[s->light_table.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM] : 0.0;
+  const bool spheres = sampled && s->sphere_sampling && !s->sphere_table.empty();
+  s->dev.n_sphere_lights = spheres ? (int32_t)(s->sphere_table.size() / PT_SLIGHT_DOUBLES) : 0; /* (0 is pad_f's 0.0f) */
+  if (spheres) { /* the joined table: the triangles' records again, the spheres' behind them */
+    s->dev.lights = s->d_joined_lights.p;
+    s->dev.n_lights = s->host->n_emissive_tris >= 1 && s->host->n_emissive_tris <= PTX_MAX_LIGHT_TRIANGLES ? s->host->n_emissive_tris : 0;
+    s->dev.light_area = s->sphere_table[s->sphere_table.size() - PT_SLIGHT_DOUBLES + PT_SLIGHT_CUM]; /* W_total */
+  }
   s->dev.env_sample = env_on ? 1 : 0;
   reschedule(s, s->sets_in_flight); /* (Schedule::lit, and what follows from it) */
 }
@@ -1907,7 +1921,7 @@ int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
   if (mode != PTX_LIGHTING_REFERENCE && mode != PTX_LIGHTING_PATH_ORDER && mode != PTX_LIGHTING_SAMPLED) return fail(PTX_ERR_ARG, "unknown lighting mode %d", mode);
   if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lighting mode cannot change while a render runs on the scene");
   if (mode == PTX_LIGHTING_SAMPLED) {
-    if (s->host->n_emissive_tris == 0 && !s->env_sampling) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
+    if (s->host->n_emissive_tris == 0 && !s->env_sampling && !s->sphere_sampling) return fail(PTX_ERR_ARG, "sampled lighting needs an emissive triangle in the tree (emissive spheres and floor triangles are not sampled)");
     if (s->host->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return fail(PTX_ERR_ARG, "%d emissive tree triangles, more than PTX_MAX_LIGHT_TRIANGLES = %d (no light hierarchy)", s->host->n_emissive_tris, PTX_MAX_LIGHT_TRIANGLES);
     if (s->light_table.empty()) s->light_table = light_table_build(*s->host);
     if (s->device >= 0 && !s->d_lights.p && !s->light_table.empty()) {
@@ -1922,6 +1936,104 @@ int32_t ptx_scene_set_lighting(ptx_scene* s, int32_t mode) {
     const int rc = ptx_scene_set_lighting(r, mode);
     if (rc) return rc;
   }
+  return 0;
+}
+
+/* the records the sphere lights' running sums continue: the triangles' as light_table_build gives them, none for a scene whose
+ * triangles mode 2 would not take */
+static std::vector<double> light_triangle_records(const ptx_scene* s) {
+  if (s->host->n_emissive_tris < 1 || s->host->n_emissive_tris > PTX_MAX_LIGHT_TRIANGLES) return {};
+  return s->light_table.empty() ? light_table_build(*s->host) : s->light_table;
+}
+/* one scene takes the flag: everything that can fail comes before anything changes */
+static int take_sphere_sampling(ptx_scene* s, bool on) {
+  if (on && s->sphere_table.empty()) {
+    std::vector<double> joined = light_triangle_records(s);
+    std::vector<double> table = sphere_light_table_build(*s->host, joined.empty() ? 0.0 : joined[joined.size() - PT_LIGHT_DOUBLES + PT_LIGHT_CUM]);
+    if (s->device >= 0) {
+      joined.insert(joined.end(), table.begin(), table.end());
+      HIP_TRY(hipSetDevice(s->device));
+      HIP_TRY(s->d_joined_lights.ensure(joined.size()));
+      HIP_TRY(hipMemcpy(s->d_joined_lights.p, joined.data(), sizeof(double) * joined.size(), hipMemcpyHostToDevice));
+    }
+    s->sphere_table = std::move(table);
+  }
+  s->sphere_sampling = on;
+  apply_lighting(s);
+  return 0;
+}
+
+int32_t ptx_scene_set_sphere_light_sampling(ptx_scene* s, int32_t on) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "sphere light sampling cannot change while a render runs on the scene");
+  if (on) {
+    const int n = s->host->n_emissive_spheres;
+    if (n == 0) return fail(PTX_ERR_ARG, "sphere light sampling needs an emissive sphere in the tree: the scene has 0");
+    if (n > PTX_MAX_LIGHT_SPHERES) return fail(PTX_ERR_ARG, "%d emissive tree spheres, more than PTX_MAX_LIGHT_SPHERES = %d (no light hierarchy)", n, PTX_MAX_LIGHT_SPHERES);
+  } else {
+    if (!s->sphere_sampling) return 0;
+    if (s->lighting == PTX_LIGHTING_SAMPLED && s->host->n_emissive_tris == 0 && !s->env_sampling)
+      return fail(PTX_ERR_STATE, "sampled lighting has nothing but the sphere lights to sample: set another lighting mode first");
+  }
+  if (const int rc = take_sphere_sampling(s, on != 0)) return rc;
+  for (ptx_scene* r : s->replicas)
+    if (const int rc = take_sphere_sampling(r, on != 0)) return rc;
+  return 0;
+}
+
+int32_t ptx_scene_sphere_lights(const ptx_scene* s, int32_t* on_out, int32_t* n_out, double* weight_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  const bool on = s->sphere_sampling && !s->sphere_table.empty();
+  if (on_out) *on_out = s->sphere_sampling ? 1 : 0;
+  if (n_out) *n_out = on ? (int32_t)(s->sphere_table.size() / PT_SLIGHT_DOUBLES) : 0;
+  if (weight_out) *weight_out = on ? s->sphere_table[s->sphere_table.size() - PT_SLIGHT_DOUBLES + PT_SLIGHT_CUM] : 0.0;
+  return 0;
+}
+
+int32_t ptx_light_table(const ptx_scene* s, double* triangles_out, double* spheres_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (triangles_out && !s->light_table.empty()) std::memcpy(triangles_out, s->light_table.data(), sizeof(double) * s->light_table.size());
+  if (spheres_out && s->sphere_sampling && !s->sphere_table.empty())
+    std::memcpy(spheres_out, s->sphere_table.data(), sizeof(double) * s->sphere_table.size());
+  return 0;
+}
+
+static int light_half_ready(const ptx_scene* s) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (s->dev.lighting != PTX_LIGHTING_SAMPLED || s->dev.n_lights + s->dev.n_sphere_lights < 1)
+    return fail(PTX_ERR_STATE, "the light half needs PTX_LIGHTING_SAMPLED and a light triangle or a sphere light to sample");
+  return 0;
+}
+int32_t ptx_light_sample(ptx_scene* s, int64_t n, const double* points, const double* uv, double* dir_out, int32_t* index_out) {
+  if (const int rc = light_half_ready(s)) return rc;
+  if (n < 0 || !points || !uv || !dir_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_p, d_uv, d_out;
+  LocalBuf<int32_t> d_index;
+  HIP_TRY(d_p.ensure((size_t)n * 3)); HIP_TRY(d_uv.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
+  if (index_out) HIP_TRY(d_index.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(d_p.p, points, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_uv.p, uv, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_light_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_p.p, d_uv.p, d_out.p, index_out ? d_index.p : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(dir_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
+  if (index_out) HIP_TRY(hipMemcpy(index_out, d_index.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+int32_t ptx_light_pdf(ptx_scene* s, int64_t n, const double* points, const double* dirs, double* pd_out) {
+  if (const int rc = light_half_ready(s)) return rc;
+  if (n < 0 || !points || !dirs || !pd_out) return fail(PTX_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  LocalBuf<double> d_p, d_dirs, d_out;
+  HIP_TRY(d_p.ensure((size_t)n * 3)); HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(d_p.p, points, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_light_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_p.p, d_dirs.p, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(pd_out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2193,7 +2305,7 @@ int32_t ptx_scene_set_environment_sampling(ptx_scene* s, int32_t on) {
     if (const int rc = env_density_make(*s->env.host, s->env_rot, &density)) return rc;
   } else {
     if (!s->env_sampling) return 0;
-    if (s->lighting == PTX_LIGHTING_SAMPLED && s->host->n_emissive_tris == 0)
+    if (s->lighting == PTX_LIGHTING_SAMPLED && s->host->n_emissive_tris == 0 && !s->sphere_sampling)
       return fail(PTX_ERR_STATE, "sampled lighting has nothing but the environment to sample: set another lighting mode first");
   }
   return family_take_env_sampling(scene_family(s), on != 0, density);
@@ -2472,6 +2584,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   }
   /* environment sampling (the density is shared too), then the lighting mode, which may need it */
   if ((src->env_sampling && family_take_env_sampling({s}, true, src->env_density) != 0) ||
+      (src->sphere_sampling && take_sphere_sampling(s, true) != 0) ||
       (src->lighting != 0 && ptx_scene_set_lighting(s, src->lighting) != 0)) {
     ptx_scene_destroy(s);
     return nullptr;

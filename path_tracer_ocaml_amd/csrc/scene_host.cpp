@@ -53,6 +53,17 @@ void emissive_list(const ptx_scene_desc* d, PtHostArrays* h) {
   }
 }
 
+/* the emissive tree spheres in build-list order */
+void emissive_sphere_list(const ptx_scene_desc* d, PtHostArrays* h) {
+  h->n_emissive_spheres = 0;
+  h->emissive_spheres.clear();
+  for (int i = 0; i < d->n_spheres; ++i) {
+    if (!emits(d->materials[d->sphere_material[i]])) continue;
+    if (h->n_emissive_spheres++ > PTX_MAX_LIGHT_SPHERES) continue;
+    h->emissive_spheres.insert(h->emissive_spheres.end(), {d->sphere_x[i], d->sphere_y[i], d->sphere_z[i], d->sphere_r[i]});
+  }
+}
+
 /* sph / tri / tri_uv / kind / slot_mat in the order of h->slot_prim: leaf order, then the floor */
 void slot_arrays(const ptx_scene_desc* d, PtHostArrays* h) {
   const int n_tri = d->n_triangles, n_slots = h->dev.n_slots, total_slots = (int)h->slot_prim.size();
@@ -527,6 +538,7 @@ int scene_set_tree(const ptx_scene_desc* d, BvhResult&& tree, PtHostArrays* h, s
   h->n_textures = d->n_textures;
   for (int f = 0; f < d->n_floor_triangles; ++f) h->slot_prim.push_back(d->n_triangles + d->n_spheres + f);
   emissive_list(d, h);
+  emissive_sphere_list(d, h);
   return 0;
 }
 
@@ -562,6 +574,24 @@ std::vector<double> light_table_build(const PtHostArrays& h) {
     o[9] = nrm.x; o[10] = nrm.y; o[11] = nrm.z;
     o[PT_LIGHT_AREA] = area;
     o[PT_LIGHT_CUM] = cum;
+  }
+  return table;
+}
+
+/* include/ptx.h, "cone-sampling emissive spheres": r2 = r * r, W = (2.0 * pi) * r2, cum runs on from the triangles' total */
+std::vector<double> sphere_light_table_build(const PtHostArrays& h, double cum) {
+  const double pi = 3.14159265358979323846;
+  const int n = std::min(h.n_emissive_spheres, (int)(h.emissive_spheres.size() / 4));
+  std::vector<double> table((size_t)n * PT_SLIGHT_DOUBLES, 0.0);
+  for (int k = 0; k < n; ++k) {
+    const double* sp = &h.emissive_spheres[(size_t)k * 4];
+    double* o = &table[(size_t)k * PT_SLIGHT_DOUBLES];
+    const double r2 = sp[3] * sp[3], w = (2.0 * pi) * r2;
+    cum = cum + w;
+    std::memcpy(o, sp, sizeof(double) * 4);
+    o[PT_SLIGHT_R2] = r2;
+    o[PT_SLIGHT_W] = w;
+    o[PT_SLIGHT_CUM] = cum;
   }
   return table;
 }

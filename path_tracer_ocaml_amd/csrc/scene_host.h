@@ -37,6 +37,10 @@ struct PtHostArrays {
    * n_emissive_tris counts them all (ptx_scene_set_lighting makes the light table of them) */
   std::vector<double> emissive_tris;
   int n_emissive_tris = 0;
+  /* the emissive tree spheres of the build list, in its order: {x, y, z, r} each, kept up to one past PTX_MAX_LIGHT_SPHERES;
+   * n_emissive_spheres counts them all (ptx_scene_set_sphere_light_sampling makes the sphere light table of them) */
+  std::vector<double> emissive_spheres;
+  int n_emissive_spheres = 0;
   int n_textures = 0; /* the descriptor's texture table (ptx_scene_set_texture_image checks its index against it, host-only scenes too) */
   int tile_lists = 0; /* SceneOptions::tile_lists, kept for the schedule: camera launches may scan per-tile sphere lists (scene_tile_lists) */
   PtSceneDev dev{}; /* the scalar fields; device pointers are filled per upload */
@@ -73,6 +77,9 @@ void scene_assemble(const ptx_scene_desc* d, const std::vector<Box>& boxes, cons
 
 /* The light table of PTX_LIGHTING_SAMPLED: per emissive tree triangle PT_LIGHT_DOUBLES doubles {a, b, c, n, A, cum} */
 std::vector<double> light_table_build(const PtHostArrays& h);
+/* The sphere lights of ptx_scene_set_sphere_light_sampling: per emissive tree sphere PT_SLIGHT_DOUBLES doubles {c, r, r2, W, cum, 0};
+ * cum = the running sum the first record continues (the triangles' total area, 0.0 without light triangles) */
+std::vector<double> sphere_light_table_build(const PtHostArrays& h, double cum);
 
 /* ---- image textures and the environment (include/ptx.h) ----
  * Every check of a caller's ptx_image: size, flags (an environment accepts PTX_IMAGE_BILINEAR only), reserved, every texel finite.

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
-EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_camera_create", "pth_scene_shirley", "pth_scene_cornell", "pth_scene_cornell_lamp",
+EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_camera_create", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
            "pth_scene_ganesha_like", "pth_write_png", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
@@ -35,6 +35,8 @@ def lib():
         L.pth_scene_cornell.argtypes = [C.c_int32, C.c_int32, C.c_double]
         L.pth_scene_cornell_lamp.restype = C.c_void_p
         L.pth_scene_cornell_lamp.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]
+        L.pth_scene_shirley_lamp.restype = C.c_void_p
+        L.pth_scene_shirley_lamp.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [C.c_double] * 5
         L.pth_scene_ganesha_like.restype = C.c_void_p
         L.pth_scene_ganesha_like.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64]
         L.pth_write_png.argtypes = [C.c_char_p, C.c_int32, C.c_int32, abi.c_double_p]
@@ -129,6 +131,12 @@ class HostScene:
 def shirley_spheres(width, height, no_simd=False, seed=42):
     """shirley_spheres/bin/main.ml: Random.init 42; Shirley_spheres.spheres (); camera (width // height)."""
     return HostScene(lib().pth_scene_shirley(width, height, int(no_simd), seed))
+
+
+def shirley_lamp(width, height, lamp, no_simd=False, seed=42):
+    """shirley_spheres plus a white Lambertian lamp sphere lamp = (x, y, z, r, emit) in world coordinates, appended after the random
+    spheres: the scene Scene.set_sphere_light_sampling is for."""
+    return HostScene(lib().pth_scene_shirley_lamp(width, height, int(no_simd), seed, *[float(v) for v in lamp]))
 
 
 def cornell_box(width, height, ceiling_emit=12.0):

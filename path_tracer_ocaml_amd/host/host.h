@@ -25,6 +25,10 @@ void pth_camera_create(const double eye[3], const double target[3], const double
 
 /* shirley_spheres/bin/main.ml (Random.init seed; the reference uses 42) */
 pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed);
+/* the same scene with a white Lambertian lamp sphere of radius r that emits (emit, emit, emit) at the WORLD point (x, y, z), moved to
+ * camera space like every other sphere; it is appended after the random spheres, so everything before it is pth_scene_shirley's */
+pth_scene* pth_scene_shirley_lamp(int32_t width, int32_t height, int32_t no_simd, int64_t seed, double x, double y, double z, double r,
+                                  double emit);
 /* cornell-box/bin/main.ml geometry + documented ceiling emitter */
 pth_scene* pth_scene_cornell(int32_t width, int32_t height, double ceiling_emit);
 /* pth_scene_cornell plus a lamp, two triangles appended after all others: a horizontal square of half side lamp_half_side centred at

@@ -21,6 +21,9 @@
 // --lens-radius=R [--focus-distance=F]: a thin lens (ptx_scene_set_lens); without F it focuses on the camera's look-at target.
 // --envmap-sample (with --envmap and --lighting=sampled): the environment is importance-sampled (ptx_scene_set_environment_sampling),
 // and sampled lighting then needs no emissive triangle.
+// --sphere-lamp=X,Y,Z,R,EMIT (with --scene=shirley): a white Lambertian lamp sphere at that world point (pth_scene_shirley_lamp);
+// --light-spheres (with --lighting=sampled): the emissive spheres are cone-sampled (ptx_scene_set_sphere_light_sampling), and sampled
+// lighting then needs no emissive triangle.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -61,6 +64,9 @@ struct Args {
   ptx_film_params film{5, 1, 0, 0};      // ptx_film_defaults
   ImageFlags images;                     // --envmap, --envmap-rotate, --ground-texture, --texture-nearest
   bool envmap_sample = false;            // --envmap-sample
+  bool light_spheres = false;            // --light-spheres
+  bool have_sphere_lamp = false;         // --sphere-lamp=X,Y,Z,R,EMIT
+  double sphere_lamp[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   double lens_radius = 0.0;              // --lens-radius=R (0: the pinhole)
   double focus_distance = 0.0;           // --focus-distance=F (0: not given -- the distance from the eye to the look-at target)
 };
@@ -75,7 +81,8 @@ struct Args {
                "          [--lighting=reference|path-order|sampled] [--lamp=HALF_SIDE,Y,EMIT]\n"
                "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n"
                "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n"
-               "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n",
+               "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n"
+               "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -105,6 +112,17 @@ Args parse(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     std::string v, bad;
     if (!std::strcmp(argv[i], "--envmap-sample")) a.envmap_sample = true;
+    else if (!std::strcmp(argv[i], "--light-spheres")) a.light_spheres = true;
+    else if (take_value(argc, argv, i, "sphere-lamp", nullptr, &v)) {
+      char tail = 0;
+      double* l = a.sphere_lamp;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf,%lf%c", &l[0], &l[1], &l[2], &l[3], &l[4], &tail) != 5)
+        usage(argv[0], "invalid value for --sphere-lamp, expected X,Y,Z,R,EMIT");
+      for (int k = 0; k < 5; ++k)
+        if (!std::isfinite(l[k])) usage(argv[0], "invalid value for --sphere-lamp, every number must be finite");
+      if (!(l[3] > 0.0) || !(l[4] > 0.0)) usage(argv[0], "invalid value for --sphere-lamp, R and EMIT must be > 0");
+      a.have_sphere_lamp = true;
+    }
     else if (image_flag(argv[i], &a.images, &bad)) {
       if (!bad.empty()) usage(argv[0], bad.c_str());
     } else if (take_value(argc, argv, i, "dimension", "d", &v)) {
@@ -205,6 +223,8 @@ Args parse(int argc, char** argv) {
   if (a.focus_distance > 0.0 && !(a.lens_radius > 0.0)) usage(argv[0], "--focus-distance requires --lens-radius > 0");
   if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
   if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
+  if (a.have_sphere_lamp && a.scene != "shirley") usage(argv[0], "--sphere-lamp requires --scene=shirley");
+  if (a.light_spheres && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--light-spheres requires --lighting=sampled");
   if (a.have_filter) { // the library's own check and message (host only: no device is touched)
     double w[2 * PTX_FILM_MAX_RADIUS + 1];
     if (ptx_film_weights(&a.film, w, nullptr) != 0) usage(argv[0], ptx_last_error());
@@ -286,7 +306,10 @@ int write_aovs(const std::string& prefix, int width, int height, const std::vect
 int main(int argc, char** argv) {
   const Args a = parse(argc, argv);
   pth_scene* hs = nullptr;
-  if (a.scene == "shirley") hs = pth_scene_shirley(a.width, a.height, a.no_simd ? 1 : 0, 42); // Random.init 42
+  if (a.scene == "shirley")
+    hs = a.have_sphere_lamp ? pth_scene_shirley_lamp(a.width, a.height, a.no_simd ? 1 : 0, 42, a.sphere_lamp[0], a.sphere_lamp[1], a.sphere_lamp[2],
+                                                     a.sphere_lamp[3], a.sphere_lamp[4])
+                            : pth_scene_shirley(a.width, a.height, a.no_simd ? 1 : 0, 42); // Random.init 42
   else if (a.scene == "cornell")
     hs = a.have_lamp ? pth_scene_cornell_lamp(a.width, a.height, a.ceiling_emit, a.lamp_half_side, a.lamp_y, a.lamp_emit)
                      : pth_scene_cornell(a.width, a.height, a.ceiling_emit);
@@ -304,6 +327,10 @@ int main(int argc, char** argv) {
   ptx_scene* scene = ptx_scene_create(d, a.device);
   if (!scene) {
     std::fprintf(stderr, "ptx_scene_create: %s\n", ptx_last_error());
+    return 1;
+  }
+  if (a.light_spheres && ptx_scene_set_sphere_light_sampling(scene, 1) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_sphere_light_sampling: %s\n", ptx_last_error());
     return 1;
   }
   // (with --envmap-sample the mode is set behind the environment and its sampling, which it may need)

@@ -275,7 +275,9 @@ void pth_camera_create(const double eye[3], const double target[3], const double
 
 // shirley_spheres/bin/main.ml: Shirley_spheres.spheres () under Random.init seed, camera (width // height),
 // every sphere moved to camera space; no_simd picks Array_leaf (cutoff 4) over Simd_leaf (cutoff 16).
-pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed) {
+// lamp (pth_scene_shirley_lamp): null, or {x, y, z, r, emit} of a white Lambertian lamp sphere in world coordinates, appended AFTER the
+// random spheres -- no RNG draw moves, and the scene without it is byte-identical
+static pth_scene* shirley_build(int32_t width, int32_t height, int32_t no_simd, int64_t seed, const double* lamp) {
   pth_scene* s = new pth_scene();
   BaseRandom rng(seed);
   const Camera cam = camera_create(v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, 20.0);
@@ -311,6 +313,11 @@ pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int
       s->sphere(center, radius, material);
     }
   }
+  if (lamp) {
+    const int m = s->material(PTX_MAT_LAMBERTIAN, s->solid(1.0, 1.0, 1.0));
+    s->mats[(size_t)m].emit[0] = s->mats[(size_t)m].emit[1] = s->mats[(size_t)m].emit[2] = lamp[4];
+    s->sphere(v3(lamp[0], lamp[1], lamp[2]), lamp[3], m);
+  }
   for (size_t i = 0; i < s->sx.size(); ++i) { // Sphere.transform ~f:(Camera.transform camera)
     const V3 c = camera_transform(cam, v3(s->sx[i], s->sy[i], s->sz[i]));
     s->sx[i] = c.x; s->sy[i] = c.y; s->sz[i] = c.z;
@@ -322,6 +329,14 @@ pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int
   s->d.num_bins = 32;
   s->sync();
   return s;
+}
+pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed) {
+  return shirley_build(width, height, no_simd, seed, nullptr);
+}
+pth_scene* pth_scene_shirley_lamp(int32_t width, int32_t height, int32_t no_simd, int64_t seed, double x, double y, double z, double r,
+                                  double emit) {
+  const double lamp[5] = {x, y, z, r, emit};
+  return shirley_build(width, height, no_simd, seed, lamp);
 }
 
 // cornell-box/bin/main.ml geometry for the path integrator; ceiling_emit is the documented emitter

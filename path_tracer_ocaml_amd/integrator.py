@@ -61,16 +61,18 @@ class Integrator:
     Scene.set_texture_image.  None leaves the scene's as they are.  ``environment_sampling``: True / False for
     Scene.set_environment_sampling -- with "sampled" lighting the light density then includes (or, on a scene without emissive
     triangles, is) the environment's; True is applied after the environment and before the lighting mode, which may need it.
-    ``lens``: (radius, focus_distance) for Scene.set_lens, the thin-lens camera; None leaves the scene's as it is."""
+    ``lens``: (radius, focus_distance) for Scene.set_lens, the thin-lens camera; None leaves the scene's as it is.
+    ``sphere_light_sampling``: True / False for Scene.set_sphere_light_sampling -- with "sampled" lighting the light half then holds
+    the scene's emissive spheres beside its emissive triangles; like ``environment_sampling`` True is applied before the lighting mode."""
 
     def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-                 environment=None, images=None, environment_sampling=None, lens=None):
+                 environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
         self.samples_per_pixel, self.max_bounces = samples_per_pixel, max_bounces
         self._scene = scene if isinstance(scene, Scene) else Scene(scene.ptr, device, keepalive=scene)
-        if lighting is not None and not environment_sampling:
+        if lighting is not None and not environment_sampling and not sphere_light_sampling:
             self._scene.set_lighting(lighting)
         if film is not None:
             self._scene.set_film(*film)
@@ -80,7 +82,9 @@ class Integrator:
             self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
         if environment_sampling is not None:
             self._scene.set_environment_sampling(bool(environment_sampling))
-        if lighting is not None and environment_sampling:
+        if sphere_light_sampling is not None:
+            self._scene.set_sphere_light_sampling(bool(sphere_light_sampling))
+        if lighting is not None and (environment_sampling or sphere_light_sampling):
             self._scene.set_lighting(lighting)
         for index, img in (images or {}).items():
             self._scene.set_texture_image(index, *(img if isinstance(img, tuple) else (img,)))
@@ -91,9 +95,9 @@ class Integrator:
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
-               environment=None, images=None, environment_sampling=None, lens=None):
+               environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None):
         return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images,
-                   environment_sampling, lens)
+                   environment_sampling, lens, sphere_light_sampling)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
