@@ -269,6 +269,54 @@ external lens : scene -> float * float = "ptx_ml_lens_stub"
 let set_lens scene ~radius ~focus_distance =
   set_lens_raw scene (Bigarray.Array1.of_array Bigarray.float64 Bigarray.c_layout [| radius; focus_distance |])
 
+(* The camera pose (ptx_scene_set_camera_pose; the rule is in include/ptx.h): the camera stands at [origin] of the scene's space,
+   turned by [rotation] (9 floats, row-major, posed camera space -> scene space) and, with [view] = (lower_left_x, lower_left_y,
+   view_x, view_y), looks through a frustum of its own: a viewport or a turntable moves the camera of one handle instead of building
+   the scene again.  Sticky: every later render of the scene reads it.  [pose] and [view] are each optional, but one must be given;
+   [view] alone keeps origin 0 and the identity.  Any pose, the identity included, switches the posed route on;
+   [clear_camera_pose] switches it off, which is a scene's first state: its own camera and its own launches, bit for bit.  Failure
+   for a non-finite origin, a matrix that is not a rotation (max |R R^T - I| > 1e-9 or det R <= 0), a non-finite view, or while a
+   render runs on the scene.  [camera_pose]: None while off, else (origin, rotation, view in effect). *)
+external set_camera_pose_raw
+  :  scene
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> unit
+  = "ptx_ml_set_camera_pose_stub"
+
+external clear_camera_pose : scene -> unit = "ptx_ml_clear_camera_pose_stub"
+
+external camera_pose_raw
+  :  scene
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> int
+  = "ptx_ml_camera_pose_stub"
+
+let set_camera_pose ?pose ?view scene =
+  let doubles a = Bigarray.Array1.of_array Bigarray.float64 Bigarray.c_layout a in
+  let pose =
+    match pose with
+    | None -> [||]
+    | Some (origin, rotation) ->
+      if Array.length origin <> 3 || Array.length rotation <> 9
+      then invalid_arg "Ptx.set_camera_pose: origin holds 3 floats and rotation 9";
+      Array.append origin rotation
+  in
+  let view =
+    match view with
+    | None -> [||]
+    | Some (llx, lly, vx, vy) -> [| llx; lly; vx; vy |]
+  in
+  set_camera_pose_raw scene (doubles pose) (doubles view)
+
+let camera_pose scene =
+  let out = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 16 in
+  if camera_pose_raw scene out = 0
+  then None
+  else (
+    let get i = Bigarray.Array1.get out i in
+    Some (Array.init 3 get, Array.init 9 (fun i -> get (3 + i)), (get 12, get 13, get 14, get 15)))
+
 external render_flat
   :  scene
   -> int (* width *)

@@ -269,6 +269,28 @@ static __attribute__((unused)) int32_t ptx_ml_lens(const ptx_scene* s, double* r
   return ptx_scene_lens(s, radius, focus_distance);
 }
 
+/* Ptx.set_camera_pose / Ptx.clear_camera_pose / Ptx.camera_pose: where every later render of the scene is taken from
+ * (ptx_scene_set_camera_pose).  pose: the 12 doubles origin (3) then rotation (9, row-major), or n_pose = 0 for none; view: the 4
+ * doubles lower_left_x, lower_left_y, view_x, view_y, or n_view = 0 for the scene's own.  -4 for any other length, or when both are
+ * empty (clearing is a call of its own: nothing is switched off by accident). */
+static __attribute__((unused)) int32_t ptx_ml_set_camera_pose(ptx_scene* s, const double* pose, int64_t n_pose, const double* view, int64_t n_view) {
+  if ((n_pose != 0 && n_pose != 12) || (n_view != 0 && n_view != 4) || (n_pose == 0 && n_view == 0)) return -4;
+  ptx_camera v;
+  if (n_view) { v.lower_left_x = view[0]; v.lower_left_y = view[1]; v.view_x = view[2]; v.view_y = view[3]; }
+  return ptx_scene_set_camera_pose(s, n_pose ? pose : NULL, n_pose ? pose + 3 : NULL, n_view ? &v : NULL);
+}
+static __attribute__((unused)) int32_t ptx_ml_clear_camera_pose(ptx_scene* s) { return ptx_scene_set_camera_pose(s, NULL, NULL, NULL); }
+/* out: 16 doubles -- origin, rotation, the view in effect; returns 1 = on, 0 = off, or the library's (negative) code; -4 when out is
+ * not 16 long (nothing is written) */
+static __attribute__((unused)) int32_t ptx_ml_camera_pose(const ptx_scene* s, double* out, int64_t n_out) {
+  if (n_out != 16) return -4;
+  ptx_camera v = {0.0, 0.0, 0.0, 0.0};
+  const int32_t rc = ptx_scene_camera_pose(s, out, out + 3, &v);
+  if (rc < 0) return rc;
+  out[12] = v.lower_left_x; out[13] = v.lower_left_y; out[14] = v.view_x; out[15] = v.view_y;
+  return rc;
+}
+
 /* Ptx.film_weights: the 2 * pixel_radius + 1 weights into out (n_out doubles); -4 when out is too short for an accepted film (the
  * library's own refusals keep their codes, and nothing is written) */
 static __attribute__((unused)) int32_t ptx_ml_film_weights(int32_t order, int32_t pixel_radius, double* out, int64_t n_out) {

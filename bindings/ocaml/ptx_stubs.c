@@ -426,6 +426,52 @@ CAMLprim value ptx_ml_lens_stub(value handle) {
   CAMLreturn(tuple);
 }
 
+/* external set_camera_pose_raw : scene -> doubles -> doubles -> unit = "ptx_ml_set_camera_pose_stub" (ptx_scene_set_camera_pose: a
+ * Bigarray of the 12 doubles origin, rotation -- or an empty one -- and one of the 4 doubles of the view -- or an empty one).  What a
+ * running render's camera rays are made of: like set_lens it takes the scene exclusively and raises Failure while a render runs on
+ * another thread or domain, and Failure with the library's message for a refused pose. */
+CAMLprim value ptx_ml_set_camera_pose_stub(value handle, value pose, value view) {
+  CAMLparam3(handle, pose, view);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_camera_pose: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_camera_pose: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s)
+    rc = ptx_ml_set_camera_pose(s, (const double*)Caml_ba_data_val(pose), (int64_t)Caml_ba_array_val(pose)->dim[0],
+                                (const double*)Caml_ba_data_val(view), (int64_t)Caml_ba_array_val(view)->dim[0]);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_camera_pose: scene already destroyed");
+  if (rc == -4) caml_invalid_argument("Ptx.set_camera_pose: the pose must hold 12 doubles or none, the view 4 or none, and one of them be given");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external clear_camera_pose : scene -> unit = "ptx_ml_clear_camera_pose_stub" (ptx_scene_set_camera_pose(scene, NULL, NULL, NULL)) */
+CAMLprim value ptx_ml_clear_camera_pose_stub(value handle) {
+  CAMLparam1(handle);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.clear_camera_pose: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.clear_camera_pose: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_clear_camera_pose(s);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.clear_camera_pose: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external camera_pose_raw : scene -> doubles -> int = "ptx_ml_camera_pose_stub" (ptx_scene_camera_pose into a Bigarray of 16 doubles:
+ * origin, rotation, the view in effect; 1 = on, 0 = off) */
+CAMLprim value ptx_ml_camera_pose_stub(value handle, value out) {
+  CAMLparam2(handle, out);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.camera_pose: scene already destroyed");
+  const int32_t rc = ptx_ml_camera_pose(s, (double*)Caml_ba_data_val(out), (int64_t)Caml_ba_array_val(out)->dim[0]);
+  if (rc == -4) caml_invalid_argument("Ptx.camera_pose: the output must hold 16 doubles");
+  if (rc < 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_int(rc));
+}
+
 /* external film_int : scene -> int * int * int = "ptx_ml_film_stub" (ptx_scene_film: order, pixel_radius, flags) */
 CAMLprim value ptx_ml_film_stub(value handle) {
   CAMLparam1(handle);

@@ -823,6 +823,72 @@ int32_t ptx_light_pdf(ptx_scene* scene, int64_t n, const double* points, const d
 int32_t ptx_scene_set_lens(ptx_scene* scene, double radius, double focus_distance);
 int32_t ptx_scene_lens(const ptx_scene* scene, double* radius_out, double* focus_distance_out);
 
+/* ---- camera pose: a movable camera, no rebuild ----
+ * The camera is the four fields Camera.ray reads, frozen into the descriptor, and the geometry is handed over in that camera's space.
+ * ptx_scene_set_camera_pose places the camera anywhere in that space -- the scene's space: the camera space of the descriptor -- and
+ * may give it another frustum, so a viewport or a turntable moves the camera of ONE handle instead of transforming every vertex,
+ * rebuilding the tree and uploading the scene again.  Only entry points are added: no struct or call changes, the ABI version stays 6.
+ *
+ * ptx_scene_set_camera_pose(scene, origin, rotation, view): sticky state of the handle, like the lens, the film and the lighting
+ * mode.  origin: where the camera stands; rotation: 3 x 3, row-major, from the posed camera's space (looking down -z, y up) to scene
+ * space; view: the posed camera's own (lower_left_x, lower_left_y, view_x, view_y), NULL = the scene's.
+ *   - all three NULL switches the pose OFF, the state of every scene that never called the setter: an off scene launches exactly
+ *     what it launched before this entry point existed, bit for bit;
+ *   - origin and rotation are given together or not at all; with `view` alone the pose is origin 0 and the identity rotation;
+ *   - any non-NULL call switches the pose ON, the identity at origin 0 included: an on scene always takes the route below.
+ * PTX_ERR_ARG with a message that starts "camera pose: " and names the rule: origin and rotation together; the origin finite; the
+ * rotation finite, max |R R^T - I| <= 1e-9 (the environment rotation's bar) and det R > 0; the view finite (ptx_scene_create reads
+ * the descriptor's camera as it is and applies no check of its own to it).  A refused call changes nothing.  PTX_ERR_STATE while a
+ * render runs on the scene.  A host-only scene accepts it; the replicas a scene owns follow it and ptx_scene_replicate copies it.
+ * ptx_scene_camera_pose returns 1 while the pose is on and 0 while it is off (a negative code for a NULL scene) and writes the
+ * origin, the rotation and the view in effect -- the pose's, else the scene's own; off: origin 0, the identity; any out pointer may
+ * be NULL.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction), for a sample with film coordinates (cx, cy) -- computed
+ * exactly as for the pinhole -- the view (llx, lly, vx, vy), the pose's if it has one, else the scene's, origin o and rotation
+ * R = (r00 r01 r02 / r10 r11 r12 / r20 r21 r22):
+ *   q  = (llx + (vx * cx), lly + (vy * cy), -1.0)
+ *   no lens:  e = q;  l = none
+ *   lens:     P = (F * q.x, F * q.y, F * q.z);  L as in the lens rule above;  e = (P.x - L.x, P.y - L.y, P.z - L.z);  l = L
+ *   Rv(a) = ((r00 * a.x + r01 * a.y) + r02 * a.z, (r10 * a.x + r11 * a.y) + r12 * a.z, (r20 * a.x + r21 * a.y) + r22 * a.z)
+ *   direction = V3.normalize (Rv(e))                         normalised AFTER it is rotated
+ *   origin    = no lens: o exactly;  lens: (o.x + Rv(l).x, o.y + Rv(l).y, o.z + Rv(l).z)
+ *   the ray is Ray.create origin direction
+ * Because the vector is rotated before it is normalised, the identity pose at origin 0 gives EXACTLY the pinhole's ray: 1 * x +
+ * 0 * y + 0 * z is x, and 0 + x is x; with a lens on, the same pose gives exactly the lens's ray.  The one caveat is the sign of a
+ * zero: a component that is -0 there can be +0 here (0 * y is -0 for a negative y, and x + -0 keeps x but -0 + +0 is +0).  No
+ * walk or shade result depends on it.  The film coordinates and the sampler are the pinhole's, or the lens's where a lens is on:
+ * THE POSE ADDS NO SAMPLER DIMENSION, so every alpha table is the one the same render without a pose reads.  The background, the
+ * environment map, normals and texture coordinates stay in scene space: the world does not tilt with the camera.
+ * "Off" and "posed back home" are different states: a pose computed for the scene's own eye and target
+ * (pth_camera_pose_look_at) is the identity within rounding only, and even the exact identity takes the route below.
+ *
+ * Entry points.  The pose is read by ptx_render, ptx_render_multi (every scene passed must carry the same pose: PTX_ERR_ARG
+ * otherwise), ptx_render_raw_device (bands and PTX_RENDER_ASYNC included), _passes_device, _pixels_device, _progressive, _adaptive,
+ * _denoised, ptx_render_features_device (the first hit of the posed ray; depth is t along that ray) and ptx_trace_samples.
+ * ptx_ppm_render and ptx_debug_first_scatter return PTX_ERR_STATE while a pose is on ("... ptx_scene_set_camera_pose(scene, NULL,
+ * NULL, NULL) first"), before any device is touched; ptx_intersect_rays and ptx_walk_rays take explicit rays and are unaffected.
+ * A posed render takes the lens's route: its camera rays are written into a path queue (k_generate_pose, one launch per batch,
+ * counted under PTX_KERNEL_GENERATE; the same 8 x 8-tile order, ids and holes) and bounced from there in the walk-first order.  It
+ * gives up the fused camera launch, the shade-first order, the per-octant LDS image, the camera tile lists (none is built) and the
+ * solo run.  Recorded on the MI355X (tools/camera_pose_cost.py, profiles/pr_camera_pose_cost.json, medians of 5): the 1080p spp 64
+ * depth 8 Shirley frame takes 16.4 ms as it is, 23.3 ms under the identity pose and 22.1 ms under an oblique one; eight turntable
+ * frames over a 148 k-triangle mesh take 29 ms each against 656 ms (host BVH builder) or 848 ms (GPU builder) for destroy / create /
+ * render.
+ *
+ * ptx_camera_rays (diagnostic): the camera rays the scene's renders launch for explicit (x, y, pass) triples under `params`
+ * (width, height, samples_per_pixel and max_bounces, which with a lens sets the sampler's dimension) -- the pose's, a lens's or the
+ * pinhole's, whatever the handle's state selects.  Host in, host out: origins_out and directions_out take 3 n doubles each.
+ *
+ * Out of scope: shutter motion blur (a time dimension would push the sampler past its 256-entry tables at depth 126 with a lens);
+ * a pose in the photon mapper; moving the geometry instead of the camera; the fused camera launch for poses that happen to have
+ * origin 0. */
+int32_t ptx_scene_set_camera_pose(ptx_scene* scene, const double origin[3], const double rotation[9] /* row-major */,
+                                  const ptx_camera* view /* NULL = the scene's own llx, lly, vx, vy */);
+int32_t ptx_scene_camera_pose(const ptx_scene* scene, double origin_out[3], double rotation_out[9], ptx_camera* view_out); /* 1 = on, 0 = off */
+int32_t ptx_camera_rays(ptx_scene* scene, const ptx_render_params* params, int64_t n, const int32_t* xs, const int32_t* ys, const int32_t* passes,
+                        double* origins_out /* 3n */, double* directions_out /* 3n */);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

@@ -45,6 +45,7 @@ EXPORTS = (
     "ptx_scene_set_environment_sampling", "ptx_scene_environment_sampling", "ptx_environment_distribution",
     "ptx_environment_sample", "ptx_environment_pdf",
     "ptx_scene_set_lens", "ptx_scene_lens",
+    "ptx_scene_set_camera_pose", "ptx_scene_camera_pose", "ptx_camera_rays",
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
 )
 
@@ -164,6 +165,10 @@ def lib():
     if hasattr(L, "ptx_scene_set_lens"):  # (likewise)
         L.ptx_scene_set_lens.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.ptx_scene_lens.argtypes = [C.c_void_p, dp, dp]
+    if hasattr(L, "ptx_scene_set_camera_pose"):  # (likewise)
+        L.ptx_scene_set_camera_pose.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.Camera)]
+        L.ptx_scene_camera_pose.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.Camera)]
+        L.ptx_camera_rays.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int64, ip, ip, ip, dp, dp]
     _LIB = L
     return L
 
@@ -275,6 +280,41 @@ class Scene:
         r, f = C.c_double(), C.c_double()
         _check(lib().ptx_scene_lens(self._h, C.byref(r), C.byref(f)))
         return r.value, f.value
+
+    def set_camera_pose(self, origin=None, rotation=None, view=None):
+        """ptx_scene_set_camera_pose: the camera stands at `origin` (3 doubles) of the scene's space, turned by `rotation` (3 x 3,
+        row-major, posed camera space -> scene space) and, with `view` = (lower_left_x, lower_left_y, view_x, view_y), looks through
+        a frustum of its own; every later render of this scene is taken from there, with no rebuild.  Sticky.  origin and rotation
+        go together; view alone keeps origin 0 and the identity.  All three None switch the pose off (the scene's own camera and
+        its own launches, bit for bit); anything else, the identity included, switches it on."""
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        r = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        v = None if view is None else abi.Camera(*(float(c) for c in view))
+        _check(lib().ptx_scene_set_camera_pose(self._h, None if o is None else _dp(o), None if r is None else _dp(r),
+                                               None if v is None else C.byref(v)))
+
+    @property
+    def camera_pose(self):
+        """ptx_scene_camera_pose: None while the pose is off, else (origin (3,), rotation (3, 3), view) with view the four fields in
+        effect (the pose's own, else the scene's)"""
+        o, r, v = np.zeros(3), np.zeros(9), abi.Camera()
+        rc = lib().ptx_scene_camera_pose(self._h, _dp(o), _dp(r), C.byref(v))
+        if rc < 0:
+            _check(rc)
+        if rc == 0:
+            return None
+        return o, r.reshape(3, 3), (v.lower_left_x, v.lower_left_y, v.view_x, v.view_y)
+
+    def camera_rays(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes):
+        """ptx_camera_rays (diagnostic): (origins (n, 3), directions (n, 3)) of the camera rays this scene's renders launch for the
+        (x, y, pass) triples -- under its pose, its lens, or neither"""
+        xs = np.ascontiguousarray(xs, dtype=np.int32)
+        ys = np.ascontiguousarray(ys, dtype=np.int32)
+        passes = np.ascontiguousarray(passes, dtype=np.int32)
+        p = render_params(width, height, samples_per_pixel, max_bounces)
+        o, d = np.zeros((len(xs), 3)), np.zeros((len(xs), 3))
+        _check(lib().ptx_camera_rays(self._h, C.byref(p), len(xs), _ip(xs), _ip(ys), _ip(passes), _dp(o), _dp(d)))
+        return o, d
 
     def set_texture_image(self, index, image, bilinear=False, repeat=(False, False)):
         """ptx_scene_set_texture_image: from now on every material that points at entry `index` of the scene's texture table
@@ -709,6 +749,13 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg):
+    """host.camera_pose_look_at: (origin, rotation, view) for Scene.set_camera_pose -- the camera (eye, target, up, aspect, fov_deg)
+    over a scene built for the camera whose Mat4.look_at rows are scene_look_at"""
+    from . import host
+    return host.camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg)
 
 
 def _image_arg(a, width, height, name):

@@ -4345,5 +4345,6 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "ppm.inc"
 #include "denoise.inc"
 #include "lens.inc"
+#include "camera_pose.inc"
 #include "ptx_api.inc"
 #endif

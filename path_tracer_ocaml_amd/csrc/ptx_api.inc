@@ -263,6 +263,7 @@ struct Schedule {
   bool lit = false;            /* emitters under lighting mode 1 or 2: the LIT instantiations */
   bool img = false;            /* an image texture or an environment: the IMG instantiations */
   bool lens = false;           /* a thin lens (ptx_scene_set_lens): camera rays are generated into a queue, never a PRIMARY launch; the walk-first order */
+  bool pose = false;           /* a camera pose (ptx_scene_set_camera_pose): like a lens, camera rays are generated into a queue (k_generate_pose) and bounced walk-first */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
@@ -311,6 +312,12 @@ struct ptx_scene {
   int lighting = 0;
   ptx_film_params film = kFilmDefault;      /* ptx_scene_set_film: what every entry point that films through this handle applies */
   double lens_radius = 0.0, lens_focus = 1.0; /* ptx_scene_set_lens: radius 0 = off, the pinhole */
+  /* ptx_scene_set_camera_pose: off = the state of a scene that never called it.  While on: where the camera stands, its rotation
+   * (row-major) and, with pose_has_view, its own four view fields */
+  bool pose_on = false, pose_has_view = false;
+  double pose_origin[3] = {0.0, 0.0, 0.0}, pose_rotation[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  ptx_camera pose_view = {0.0, 0.0, 0.0, 0.0};
+  ptx_camera own_view = {0.0, 0.0, 0.0, 0.0}; /* the descriptor's camera (a host-only scene keeps no PtSceneDev scalars) */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
   /* Sphere light sampling (ptx_scene_set_sphere_light_sampling): the flag; the sphere light table made when it is first set
@@ -580,6 +587,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * (k_generate_lens) and bounced like a list's.  The shade-first order starts at a camera launch: a lens scene keeps the walk-first
    * order, and with it has no per-octant LDS image and no tile lists. */
   c.lens = s->lens_radius > 0.0;
+  /* A posed camera (ptx_scene_set_camera_pose), the identity pose included: its rays start at the pose's origin, so they take the
+   * lens's route -- a queue (k_generate_pose) and the walk-first order; no per-octant LDS image, no tile lists (both are made for
+   * rays from the origin of the scene's own space), no solo run. */
+  c.pose = s->pose_on;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
   c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
@@ -601,7 +612,7 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * scenes, where two paths in five leave per bounce and end where their walk ends (Shirley: frame -8 %) -- and the others keep the
    * walk-first order: a closed box has no misses to save, loses its octant key and carries its emission through the walk (cornell:
    * +4.8 %; DESIGN.md Appendix A).  1 = wherever possible, 0 = nowhere (the A/B, the tests) */
-  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && !c.img && !c.lens && s->fused >= 2 && s->solo_entries <= 0 &&
+  c.carry_ok = (s->bounce_order == 1 || (s->bounce_order >= 2 && s->dev.sort_by_elevation)) && !c.lit && !c.img && !c.lens && !c.pose && s->fused >= 2 && s->solo_entries <= 0 &&
                in_lds && !c.from_hbm && c.carry.fits;
   /* how the camera rays of an LDS-resident scene walk the tree in k_bounce / k_bounce_carry.  By default (PTX_PRIMARY_WALK=2) the
    * Simd_leaf scenes walk one ray per lane -- not counting, that is the assembly node loop of the queued rays -- and the Array_leaf
@@ -845,6 +856,15 @@ struct Workspace {
 int sampler_dimension(const ptx_scene* s, int max_bounces) { return 2 + 2 * std::max(max_bounces, 0) + (s->lens_radius > 0.0 ? 2 : 0); }
 /* the lens of a launch (Schedule::lens) */
 PtLens scene_lens(const ptx_scene* s, int max_bounces) { return PtLens{s->lens_radius, s->lens_focus, sampler_dimension(s, max_bounces)}; }
+/* the pose of a launch (Schedule::pose): the view is the pose's own or the scene's */
+PtCameraPose scene_pose(const ptx_scene* s) {
+  PtCameraPose cp;
+  std::memcpy(cp.o, s->pose_origin, sizeof cp.o);
+  std::memcpy(cp.r, s->pose_rotation, sizeof cp.r);
+  const ptx_camera& view = s->pose_has_view ? s->pose_view : s->own_view;
+  cp.llx = view.lower_left_x; cp.lly = view.lower_left_y; cp.vx = view.view_x; cp.vy = view.view_y;
+  return cp;
+}
 
 /* The sampler's alpha table of this dimension becomes the scene's current one (ptx_scene.alpha): looked up, or made and
  * uploaded the first time the dimension is asked for */
@@ -952,7 +972,7 @@ void run_bounces(ptx_scene* s, hipStream_t st, Workspace& w, size_t n_upper, int
        * later ones return at once (the flag: a word of the batch's counts, zeroed with them).  A partial run (run_only) and a
        * hit-distance array without its second half never run solo. */
       PtSolo solo;
-      solo.flag = (run_only < 0 && s->solo_entries > 0 && !sc.lit && !sc.img && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
+      solo.flag = (run_only < 0 && s->solo_entries > 0 && !sc.lit && !sc.img && !sc.pose && (s->dev.has_triangles || w.hits.t_parity_stride > 0)) ? w.counts + kSoloFlagWord : nullptr;
       solo.max_entries = (uint32_t)std::max(0, s->solo_entries);
       solo.max_bounces = max_bounces;
       solo.cap_entries = (uint32_t)std::min<size_t>(w.cap_entries, 0xffffffffu);
@@ -1165,7 +1185,10 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     q0.count = w.counts;
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-      if (s->sched.lens)
+      if (s->sched.pose)
+        hipLaunchKernelGGL(s->sched.lens ? k_generate_pixels_pose<true> : k_generate_pixels_pose<false>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+      else if (s->sched.lens)
         hipLaunchKernelGGL(k_generate_pixels_lens, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
                            p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
       else
@@ -1182,13 +1205,16 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     g.tiles_x = (p->width + 7) / 8; g.tiles_y = (b.rows + 7) / 8;
     g.first_pass = first; g.n_pass = n_pass;
     pl.n = (uint32_t)((size_t)n_pass * (size_t)g.tiles_x * (size_t)g.tiles_y * 64u);
-    if (s->sched.lens) {
+    if (s->sched.lens || s->sched.pose) {
       /* the fused camera launch's virtual queue made real: pl.n entries in its order (b.cap is sized for them), then queued bounces */
       PtQueue q0 = w.q[0];
       q0.count = w.counts;
       {
         LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-        hipLaunchKernelGGL(k_generate_lens<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+        if (s->sched.pose)
+          hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, true> : k_generate_pose<false, true>), dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+        else
+          hipLaunchKernelGGL(k_generate_lens<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
       }
       run_bounces(s, ls, w, (size_t)pl.n, p->max_bounces, count, timed, PrimaryLaunch());
     } else {
@@ -1776,6 +1802,7 @@ static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
   if (!built) tree = bvh_build(boxes, num_bins, d->length_cutoff, simd);
   s->built_on_gpu = built;
   s->n_prims = n;
+  s->own_view = d->camera;
   s->tree_depth = tree.depth;
   s->tree_leaves = tree.leaves;
   auto ha = std::make_shared<PtHostArrays>();
@@ -2105,6 +2132,75 @@ int32_t ptx_scene_lens(const ptx_scene* s, double* radius_out, double* focus_dis
   if (radius_out) *radius_out = s->lens_radius;
   if (focus_distance_out) *focus_distance_out = s->lens_focus;
   return 0;
+}
+
+/* ---- camera pose ---- */
+namespace {
+const double kPoseIdentity[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+/* the setter's conditions on (origin, rotation, view); each refusal names its rule */
+int check_camera_pose(const double* origin, const double* R, const ptx_camera* view) {
+  if ((origin == nullptr) != (R == nullptr))
+    return fail(PTX_ERR_ARG, "camera pose: origin and rotation are given together or not at all (%s is NULL)", origin ? "rotation" : "origin");
+  if (origin) {
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(origin[i])) return fail(PTX_ERR_ARG, "camera pose: origin must be finite (component %d is %g)", i, origin[i]);
+    for (int i = 0; i < 9; ++i)
+      if (!std::isfinite(R[i])) return fail(PTX_ERR_ARG, "camera pose: rotation must be finite (entry %d is %g)", i, R[i]);
+    double worst = 0.0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        const double g = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
+        worst = std::max(worst, std::fabs(g - (i == j ? 1.0 : 0.0)));
+      }
+    if (!(worst <= 1e-9)) return fail(PTX_ERR_ARG, "camera pose: rotation must be orthonormal: max |R R^T - I| = %g exceeds 1e-9", worst);
+    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    if (!(det > 0.0)) return fail(PTX_ERR_ARG, "camera pose: rotation must have det R > 0 (got %g): a reflection is not a rotation", det);
+  }
+  /* ptx_scene_create reads the descriptor's camera as it is; a view given here must at least be finite */
+  if (view && !(std::isfinite(view->lower_left_x) && std::isfinite(view->lower_left_y) && std::isfinite(view->view_x) && std::isfinite(view->view_y)))
+    return fail(PTX_ERR_ARG, "camera pose: view must be finite (got lower_left %g, %g, view %g, %g)", view->lower_left_x, view->lower_left_y, view->view_x, view->view_y);
+  return 0;
+}
+bool same_camera_pose(const ptx_scene* a, const ptx_scene* b) {
+  if (a->pose_on != b->pose_on) return false;
+  if (!a->pose_on) return true;
+  if (std::memcmp(a->pose_origin, b->pose_origin, sizeof a->pose_origin) || std::memcmp(a->pose_rotation, b->pose_rotation, sizeof a->pose_rotation)) return false;
+  if (a->pose_has_view != b->pose_has_view) return false;
+  return !a->pose_has_view || std::memcmp(&a->pose_view, &b->pose_view, sizeof a->pose_view) == 0;
+}
+void copy_camera_pose(ptx_scene* dst, const ptx_scene* src) {
+  dst->pose_on = src->pose_on;
+  dst->pose_has_view = src->pose_has_view;
+  std::memcpy(dst->pose_origin, src->pose_origin, sizeof dst->pose_origin);
+  std::memcpy(dst->pose_rotation, src->pose_rotation, sizeof dst->pose_rotation);
+  dst->pose_view = src->pose_view;
+}
+}  // namespace
+
+int32_t ptx_scene_set_camera_pose(ptx_scene* s, const double origin[3], const double rotation[9], const ptx_camera* view) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  const int rc = check_camera_pose(origin, rotation, view);
+  if (rc) return rc;
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the camera pose cannot change while a render runs on the scene");
+  s->pose_on = origin || view;
+  s->pose_has_view = view != nullptr;
+  for (int i = 0; i < 3; ++i) s->pose_origin[i] = origin ? origin[i] : 0.0;
+  std::memcpy(s->pose_rotation, rotation ? rotation : kPoseIdentity, sizeof s->pose_rotation);
+  s->pose_view = view ? *view : ptx_camera{0.0, 0.0, 0.0, 0.0};
+  if (s->device >= 0) reschedule(s, s->sets_in_flight); /* (Schedule::pose, and what follows from it) */
+  for (ptx_scene* r : s->replicas) {
+    const int rr = ptx_scene_set_camera_pose(r, origin, rotation, view);
+    if (rr) return rr;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_camera_pose(const ptx_scene* s, double origin_out[3], double rotation_out[9], ptx_camera* view_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (origin_out) std::memcpy(origin_out, s->pose_origin, sizeof s->pose_origin);
+  if (rotation_out) std::memcpy(rotation_out, s->pose_rotation, sizeof s->pose_rotation);
+  if (view_out) *view_out = s->pose_has_view ? s->pose_view : s->own_view;
+  return s->pose_on ? 1 : 0;
 }
 
 /* ---- image textures and the environment ---- */
@@ -2568,6 +2664,8 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->film = src->film;
   s->lens_radius = src->lens_radius; /* (scene_upload schedules, like every setter) */
   s->lens_focus = src->lens_focus;
+  s->own_view = src->own_view;
+  copy_camera_pose(s, src);
   if (scene_upload(s) != 0) {
     ptx_scene_destroy(s);
     return nullptr;
@@ -2710,6 +2808,8 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
       return fail(PTX_ERR_ARG, "scene %d is not a replica of scene 0", k);
     if (scenes[k]->lens_radius != scenes[0]->lens_radius || (scenes[0]->lens_radius > 0.0 && scenes[k]->lens_focus != scenes[0]->lens_focus))
       return fail(PTX_ERR_ARG, "scene %d does not carry the lens of scene 0 (ptx_scene_set_lens): the bands would not be one image", k);
+    if (!same_camera_pose(scenes[k], scenes[0]))
+      return fail(PTX_ERR_ARG, "scene %d does not carry the camera pose of scene 0 (ptx_scene_set_camera_pose): the bands would not be one image", k);
   }
   int rc = check_params(p_in);
   if (rc) return rc;
@@ -3344,7 +3444,7 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
   const size_t cap = (size_t)ppb * (size_t)padded;
   HIP_TRY(s->feat_slot.ensure(cap));
   if (!s->dev.has_triangles) HIP_TRY(s->feat_t.ensure(cap));
-  const bool lens = s->sched.lens;
+  const bool lens = s->sched.lens || s->sched.pose; /* (rays with an origin: generated into a queue of their own) */
   if (lens) HIP_TRY(s->feat_ray.ensure(cap));
   HIP_TRY(s->feat_work.ensure(16)); /* [0..7] k_trace's hand-out words, [8] the entry count of a lens's ray queue */
   HIP_TRY(s->feat_susp.ensure((size_t)s->n_cu * 4 * 16 * PT_WAVE * 3)); /* as a workspace set's (ensure_workspace) */
@@ -3370,7 +3470,10 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
       /* the same entries as rays in a queue of their own (48 bytes per entry more), walked as ptx_intersect_rays' are */
       const PtLens ln = scene_lens(s, p->max_bounces);
       PtQueue q{s->feat_ray.p, nullptr, s->feat_work.p + 8};
-      hipLaunchKernelGGL(k_generate_lens<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, ln, alpha, q);
+      if (s->sched.pose)
+        hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, false> : k_generate_pose<false, false>), dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, scene_pose(s), ln, alpha, q);
+      else
+        hipLaunchKernelGGL(k_generate_lens<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, ln, alpha, q);
       launch_trace(s, st, q, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, kNoBounce);
       hipLaunchKernelGGL(s->sched.img ? k_features_lens<true> : k_features_lens<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, q, h, d_feat);
       HIP_TRY(hipGetLastError());
@@ -3575,6 +3678,22 @@ int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const p
   return render_updates(s, p, pol, true, rgb_out, err_out, stats);
 }
 
+namespace {
+/* the camera rays of explicit (x, y, pass) triples appended to q0, by the generator the scene's state selects */
+void launch_generate_list(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* dx, const int32_t* dy, const int32_t* dp, const PtQueue& q0) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (s->sched.pose)
+    hipLaunchKernelGGL(s->sched.lens ? k_generate_list_pose<true> : k_generate_list_pose<false>, grid, block, 0, nullptr, s->dev, p->width, p->height,
+                       p->samples_per_pixel, (long long)n, dx, dy, dp, scene_pose(s), scene_lens(s, p->max_bounces), s->alpha.p, q0);
+  else if (s->sched.lens)
+    hipLaunchKernelGGL(k_generate_list_lens, grid, block, 0, nullptr, s->dev, p->width, p->height,
+                       p->samples_per_pixel, (long long)n, dx, dy, dp, scene_lens(s, p->max_bounces), s->alpha.p, q0);
+  else
+    hipLaunchKernelGGL(k_generate_list, grid, block, 0, nullptr, s->dev, p->width, p->height,
+                       p->samples_per_pixel, (long long)n, dx, dy, dp, s->alpha.p, q0);
+}
+}  // namespace
+
 int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
                           const int32_t* passes, double* rgb_out, ptx_stats* stats) {
   if (!s || !xs || !ys || !passes || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
@@ -3607,12 +3726,7 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
   if (p->max_bounces > 0) {
     PtQueue q0 = w.q[0];
     q0.count = w.counts;
-    if (s->sched.lens)
-      hipLaunchKernelGGL(k_generate_list_lens, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
-                         p->samples_per_pixel, (long long)n, dx.p, dy.p, dp.p, scene_lens(s, p->max_bounces), s->alpha.p, q0);
-    else
-      hipLaunchKernelGGL(k_generate_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
-                         p->samples_per_pixel, (long long)n, dx.p, dy.p, dp.p, s->alpha.p, q0);
+    launch_generate_list(s, p, n, dx.p, dy.p, dp.p, q0);
     run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, count, false, PrimaryLaunch());
   }
   HIP_TRY(hipGetLastError());
@@ -3630,6 +3744,49 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
       rc = collect_counters(s, stats);
       if (rc) return rc;
     }
+  }
+  return 0;
+}
+
+int32_t ptx_camera_rays(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys, const int32_t* passes,
+                        double* origins_out, double* directions_out) {
+  if (!s || !xs || !ys || !passes || !origins_out || !directions_out) return fail(PTX_ERR_ARG, "NULL argument");
+  int rc = check_render_args(s, p, nullptr);
+  if (rc) return rc;
+  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad sample count");
+  if (n == 0) return 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (xs[i] < 0 || xs[i] >= p->width || ys[i] < 0 || ys[i] >= p->height || passes[i] < 0 || passes[i] >= p->samples_per_pixel)
+      return fail(PTX_ERR_ARG, "sample %lld out of range", (long long)i);
+  HIP_TRY(hipSetDevice(s->device));
+  RenderBusy busy(s);
+  Workspace w;
+  reschedule(s, 1);
+  rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
+  if (rc) return rc;
+  LocalBuf<int32_t> dx, dy, dp;
+  HIP_TRY(dx.ensure((size_t)n)); HIP_TRY(dy.ensure((size_t)n)); HIP_TRY(dp.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(dx.p, xs, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dy.p, ys, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dp.p, passes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
+  PtQueue q0 = w.q[0];
+  q0.count = w.counts;
+  launch_generate_list(s, p, n, dx.p, dy.p, dp.p, q0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  /* the generator appends wave by wave: entry e is the ray of sample path[e].id */
+  const size_t path_stride = s->dev.has_emit ? 2 : 1;
+  std::vector<PtRayRec> rays((size_t)n);
+  std::vector<PtPathRec> path((size_t)n * path_stride);
+  HIP_TRY(hipMemcpy(rays.data(), q0.ray, sizeof(PtRayRec) * rays.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(path.data(), q0.path, sizeof(PtPathRec) * path.size(), hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < (size_t)n; ++e) {
+    const size_t i = path[e * path_stride].id;
+    if (i >= (size_t)n) return fail(PTX_ERR_HIP, "BUG: camera ray %zu carries sample id %zu of %lld", e, i, (long long)n);
+    const PtRayRec& r = rays[e];
+    origins_out[3 * i] = r.ox; origins_out[3 * i + 1] = r.oy; origins_out[3 * i + 2] = r.oz;
+    directions_out[3 * i] = r.dx; directions_out[3 * i + 1] = r.dy; directions_out[3 * i + 2] = r.dz;
   }
   return 0;
 }
@@ -3798,6 +3955,8 @@ int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, 
 int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
                                 const int32_t* passes, double* ray_out, double* attn_out, int32_t* alive_out) {
   if (!s || !xs || !ys || !passes || !ray_out || !attn_out || !alive_out) return fail(PTX_ERR_ARG, "NULL argument");
+  /* (before any device is touched: a host-only scene gets this answer too) */
+  if (s->pose_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
   int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
@@ -3852,6 +4011,8 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
 int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* lights, int32_t n_lights, double* img_sum_out,
                        ptx_ppm_stats* stats, ptx_ppm_iteration_fn cb, void* user) {
   if (!s || !p || !lights || !img_sum_out) return fail(PTX_ERR_ARG, "NULL argument");
+  /* (before any device is touched: a host-only scene gets this answer too) */
+  if (s->pose_on) return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
   if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
   if (p->width <= 0 || p->height <= 0 || p->iterations <= 0 || p->max_bounces <= 0 || p->max_bounces > 60 || p->photon_count <= 0 || n_lights <= 0)
     return fail(PTX_ERR_ARG, "bad photon-mapping parameters");

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
-EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_camera_create", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
+EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_scene_camera", "pth_camera_create", "pth_camera_pose_look_at", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
            "pth_scene_ganesha_like", "pth_write_png", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
@@ -29,6 +29,9 @@ def lib():
         L.pth_scene_focus_distance.argtypes = [C.c_void_p]
         L.pth_camera_create.argtypes = [abi.c_double_p, abi.c_double_p, abi.c_double_p, C.c_double, C.c_double,
                                         C.POINTER(abi.Camera), abi.c_double_p]
+        L.pth_scene_camera.argtypes = [C.c_void_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
+        L.pth_camera_pose_look_at.argtypes = [abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, C.c_double, C.c_double,
+                                              abi.c_double_p, abi.c_double_p, C.POINTER(abi.Camera)]
         L.pth_scene_shirley.restype = C.c_void_p
         L.pth_scene_shirley.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
         L.pth_scene_cornell.restype = C.c_void_p
@@ -80,6 +83,17 @@ class HostScene:
         """the distance from the eye to the look-at target of the scene's camera: a thin lens's default focus (Scene.set_lens)"""
         return lib().pth_scene_focus_distance(self._h)
 
+    @property
+    def camera(self):
+        """the camera the scene was built for: {"eye", "target", "up" (3,), "fov_deg", "look_at" (4, 4: Mat4.look_at rows)} -- what
+        camera_pose_look_at poses another camera against"""
+        eye, target, up, fov, m = np.zeros(3), np.zeros(3), np.zeros(3), C.c_double(), np.zeros(16)
+        dp = abi.c_double_p
+        if lib().pth_scene_camera(self._h, eye.ctypes.data_as(dp), target.ctypes.data_as(dp), up.ctypes.data_as(dp), C.byref(fov),
+                                  m.ctypes.data_as(dp)) != 0:
+            raise RuntimeError("the scene records no camera")
+        return {"eye": eye, "target": target, "up": up, "fov_deg": fov.value, "look_at": m.reshape(4, 4)}
+
     def arrays(self):
         d = self.d
 
@@ -126,6 +140,29 @@ class HostScene:
             self.close()
         except Exception:
             pass
+
+
+def camera_create(eye, target, up, aspect, fov_deg):
+    """pth_camera_create (Camera.create): (view = (lower_left_x, lower_left_y, view_x, view_y), look_at (4, 4))"""
+    dp = abi.c_double_p
+    e, t, u = (np.ascontiguousarray(a, dtype=np.float64).reshape(3) for a in (eye, target, up))
+    view, m = abi.Camera(), np.zeros(16)
+    lib().pth_camera_create(e.ctypes.data_as(dp), t.ctypes.data_as(dp), u.ctypes.data_as(dp), float(aspect), float(fov_deg), C.byref(view),
+                            m.ctypes.data_as(dp))
+    return (view.lower_left_x, view.lower_left_y, view.view_x, view.view_y), m.reshape(4, 4)
+
+
+def camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg):
+    """pth_camera_pose_look_at: the pose (origin (3,), rotation (3, 3), view) of the camera (eye, target, up, aspect, fov_deg) over a
+    scene built for the camera whose Mat4.look_at rows are scene_look_at (HostScene.camera["look_at"]); Scene.set_camera_pose(*pose)
+    renders from there.  The scene's own eye and target give the identity within rounding only: not the same state as no pose."""
+    dp = abi.c_double_p
+    m = np.ascontiguousarray(scene_look_at, dtype=np.float64).reshape(16)
+    e, t, u = (np.ascontiguousarray(a, dtype=np.float64).reshape(3) for a in (eye, target, up))
+    o, r, view = np.zeros(3), np.zeros(9), abi.Camera()
+    lib().pth_camera_pose_look_at(m.ctypes.data_as(dp), e.ctypes.data_as(dp), t.ctypes.data_as(dp), u.ctypes.data_as(dp), float(aspect),
+                                  float(fov_deg), o.ctypes.data_as(dp), r.ctypes.data_as(dp), C.byref(view))
+    return o, r.reshape(3, 3), (view.lower_left_x, view.lower_left_y, view.view_x, view.view_y)
 
 
 def shirley_spheres(width, height, no_simd=False, seed=42):

@@ -17,11 +17,22 @@ const ptx_scene_desc* pth_scene_desc(pth_scene* s);
 void pth_scene_free(pth_scene* s);
 /* the distance from the eye to the look-at target of the scene's camera: the default focus distance of a thin lens (ptx_scene_set_lens) */
 double pth_scene_focus_distance(const pth_scene* s);
+/* the camera the scene was built for -- its geometry is in that camera's space: eye, target, up, the vertical field of view in degrees
+ * and the Mat4.look_at rows (what pth_camera_pose_look_at takes as scene_look_at).  Any out pointer may be NULL; -1 for a scene that
+ * records none. */
+int32_t pth_scene_camera(const pth_scene* s, double eye_out[3], double target_out[3], double up_out[3], double* fov_deg_out, double look_at_out[16]);
 
 /* Camera.create (path_tracer/src/camera.ml:58-83): view = the four fields Camera.ray reads;
  * look_at (optional) = Mat4.look_at rows, row-major 4x4 */
 void pth_camera_create(const double eye[3], const double target[3], const double up[3], double aspect, double fov_deg,
                        ptx_camera* view_out, double look_at_out[16]);
+/* A camera pose for ptx_scene_set_camera_pose: the camera (eye, target, up, aspect, fov_deg) seen from a scene that was built for
+ * another camera, whose Mat4.look_at rows (pth_camera_create's look_at_out) are scene_look_at.  origin = Mat4.transform scene_look_at
+ * eye; rotation = R_scene * R_new^T on the 3 x 3 row blocks, every sum left-associated; view = pth_camera_create's for the new
+ * camera.  Any out pointer may be NULL.  The scene's own eye and target give the identity and the origin 0 within rounding only
+ * (1e-15 and 1e-12 of the scene's units): "posed back home" is not "off". */
+void pth_camera_pose_look_at(const double scene_look_at[16], const double eye[3], const double target[3], const double up[3], double aspect,
+                             double fov_deg, double origin_out[3], double rotation_out[9], ptx_camera* view_out);
 
 /* shirley_spheres/bin/main.ml (Random.init seed; the reference uses 42) */
 pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed);

@@ -19,6 +19,10 @@
 // rotation is about the camera-space y axis); --ground-texture=FILE.pfm [--texture-nearest]: an image, repeated on both axes, on
 // the ground (shirley) or floor (ganesha) material (ptx_scene_set_texture_image); image_flags.h.
 // --lens-radius=R [--focus-distance=F]: a thin lens (ptx_scene_set_lens); without F it focuses on the camera's look-at target.
+// --camera-eye=X,Y,Z --camera-target=X,Y,Z [--camera-fov=DEG]: renders from another camera (world coordinates, the scene's own up
+// vector) over the scene built with its default one (ptx_scene_set_camera_pose: no vertex is transformed again, no tree rebuilt).
+// --turntable=N: N frames on a circle about the vertical axis through the target, through ONE scene handle; frame k goes to the -o name
+// with -kkk in front of its extension.
 // --envmap-sample (with --envmap and --lighting=sampled): the environment is importance-sampled (ptx_scene_set_environment_sampling),
 // and sampled lighting then needs no emissive triangle.
 // --sphere-lamp=X,Y,Z,R,EMIT (with --scene=shirley): a white Lambertian lamp sphere at that world point (pth_scene_shirley_lamp);
@@ -69,6 +73,10 @@ struct Args {
   double sphere_lamp[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   double lens_radius = 0.0;              // --lens-radius=R (0: the pinhole)
   double focus_distance = 0.0;           // --focus-distance=F (0: not given -- the distance from the eye to the look-at target)
+  bool have_eye = false, have_target = false; // --camera-eye, --camera-target (given together)
+  double camera_eye[3] = {0, 0, 0}, camera_target[3] = {0, 0, 0};
+  double camera_fov = 0.0;               // --camera-fov=DEG (0: the scene camera's)
+  int turntable = 0;                     // --turntable=N (0: one frame)
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -82,7 +90,8 @@ struct Args {
                "          [--denoise[=LEVELS]] [--aov=PREFIX] [--filter=ORDER,RADIUS] [--filter-renormalise]\n"
                "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n"
                "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n"
-               "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n",
+               "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n"
+               "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -191,6 +200,28 @@ Args parse(int argc, char** argv) {
       a.focus_distance = std::strtod(v.c_str(), &end);
       if (end == v.c_str() || *end || !(a.focus_distance > 0.0) || !std::isfinite(a.focus_distance)) usage(argv[0], "invalid value for --focus-distance, must be > 0");
     }
+    else if (take_value(argc, argv, i, "camera-eye", nullptr, &v)) {
+      char tail = 0;
+      double* c = a.camera_eye;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &c[0], &c[1], &c[2], &tail) != 3 || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+        usage(argv[0], "invalid value for --camera-eye, expected X,Y,Z");
+      a.have_eye = true;
+    } else if (take_value(argc, argv, i, "camera-target", nullptr, &v)) {
+      char tail = 0;
+      double* c = a.camera_target;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &c[0], &c[1], &c[2], &tail) != 3 || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+        usage(argv[0], "invalid value for --camera-target, expected X,Y,Z");
+      a.have_target = true;
+    } else if (take_value(argc, argv, i, "camera-fov", nullptr, &v)) {
+      char* end = nullptr;
+      a.camera_fov = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.camera_fov > 0.0) || !(a.camera_fov < 180.0)) usage(argv[0], "invalid value for --camera-fov, must be in (0, 180)");
+    } else if (take_value(argc, argv, i, "turntable", nullptr, &v)) {
+      char* end = nullptr;
+      const long n = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end || n < 1 || n > 999) usage(argv[0], "invalid value for --turntable, must be in 1..999");
+      a.turntable = (int)n;
+    }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
     else if (!std::strcmp(argv[i], "--no-simd")) a.no_simd = true;
@@ -221,6 +252,10 @@ Args parse(int argc, char** argv) {
     if (!bad.empty()) usage(argv[0], bad.c_str());
   }
   if (a.focus_distance > 0.0 && !(a.lens_radius > 0.0)) usage(argv[0], "--focus-distance requires --lens-radius > 0");
+  if (a.have_eye != a.have_target) usage(argv[0], "--camera-eye and --camera-target are given together");
+  if (a.have_eye && a.camera_eye[0] == a.camera_target[0] && a.camera_eye[1] == a.camera_target[1] && a.camera_eye[2] == a.camera_target[2])
+    usage(argv[0], "--camera-eye and --camera-target must differ");
+  if (a.camera_fov > 0.0 && !a.have_eye && a.turntable == 0) usage(argv[0], "--camera-fov requires --camera-eye and --camera-target, or --turntable");
   if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
   if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
   if (a.have_sphere_lamp && a.scene != "shirley") usage(argv[0], "--sphere-lamp requires --scene=shirley");
@@ -299,6 +334,47 @@ int write_aovs(const std::string& prefix, int width, int height, const std::vect
   for (size_t p = 0; p < npix; ++p)
     for (int c = 0; c < 3; ++c) img[3 * p + c] = zmax > 0.0 ? feat[8 * p + 6] / zmax : 0.0;
   return pth_write_png((prefix + "-depth.png").c_str(), width, height, img.data()) != 0 ? -1 : 0;
+}
+
+// the camera of frame `frame` posed over the scene (ptx_scene_set_camera_pose): --camera-eye / --camera-target / --camera-fov where given,
+// else the scene's own; a turntable turns the eye about the axis through the target along the scene camera's up vector (Rodrigues)
+int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
+  double eye[3], target[3], up[3], fov = 0.0, look_at[16];
+  if (pth_scene_camera(hs, eye, target, up, &fov, look_at) != 0) {
+    std::fprintf(stderr, "the scene records no camera to pose against\n");
+    return -1;
+  }
+  if (a.have_eye) {
+    std::memcpy(eye, a.camera_eye, sizeof eye);
+    std::memcpy(target, a.camera_target, sizeof target);
+  }
+  if (a.camera_fov > 0.0) fov = a.camera_fov;
+  if (a.turntable > 0) {
+    const double len = std::sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+    const double k[3] = {up[0] / len, up[1] / len, up[2] / len};
+    const double th = 2.0 * 3.14159265358979323846 * (double)frame / (double)a.turntable, c = std::cos(th), s = std::sin(th);
+    const double v[3] = {eye[0] - target[0], eye[1] - target[1], eye[2] - target[2]};
+    const double kxv[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+    const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+    for (int i = 0; i < 3; ++i) eye[i] = target[i] + (v[i] * c + kxv[i] * s + k[i] * kv * (1.0 - c));
+  }
+  double origin[3], rotation[9];
+  ptx_camera view;
+  pth_camera_pose_look_at(look_at, eye, target, up, (double)a.width / (double)a.height, fov, origin, rotation, &view);
+  if (ptx_scene_set_camera_pose(scene, origin, rotation, &view) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_camera_pose: %s\n", ptx_last_error());
+    return -1;
+  }
+  return 0;
+}
+
+// out.png -> out-007.png
+std::string frame_name(const std::string& output, int frame) {
+  char tag[16];
+  std::snprintf(tag, sizeof tag, "-%03d", frame);
+  const size_t dot = output.rfind('.'), slash = output.rfind('/');
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return output + tag;
+  return output.substr(0, dot) + tag + output.substr(dot);
 }
 
 }  // namespace
@@ -383,6 +459,10 @@ int main(int argc, char** argv) {
     std::printf(")\n");
     std::fflush(stdout);
   }
+  const bool posed = a.have_eye || a.turntable > 0;
+  for (int frame = 0; frame < (a.turntable > 0 ? a.turntable : 1); ++frame) {
+  const std::string output = a.turntable > 0 ? frame_name(a.output, frame) : a.output;
+  if (posed && pose_camera(scene, hs, a, frame) != 0) return 1;
   ptx_render_params p;
   std::memset(&p, 0, sizeof p);
   p.width = a.width; p.height = a.height; p.samples_per_pixel = a.samples_per_pixel; p.max_bounces = a.max_bounces;
@@ -395,7 +475,7 @@ int main(int argc, char** argv) {
   /* the image lives until the PNG is written, like the reference's Bimage (render_command.ml:64-70): pin it, so the frame comes
    * back with one DMA (optional: a failure only means the staged copy) */
   (void)ptx_image_pin(scene, rgb.data(), (int64_t)rgb.size());
-  Updates upd{a.output.c_str(), a.width, a.height};
+  Updates upd{output.c_str(), a.width, a.height};
   int rc;
   const bool adaptive = a.adaptive >= 0.0;
   if (adaptive) {
@@ -441,12 +521,14 @@ int main(int argc, char** argv) {
                  ptx_last_error());
     return 1;
   }
-  if (upd.write_failed || pth_write_png(a.output.c_str(), a.width, a.height, rgb.data()) != 0) {
-    std::fprintf(stderr, "cannot write %s\n", a.output.c_str());
+  if (upd.write_failed || pth_write_png(output.c_str(), a.width, a.height, rgb.data()) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", output.c_str());
     return 1;
   }
+  if (a.turntable > 0) std::printf("frame %d -> %s\n", frame, output.c_str());
   std::printf("rendered in: %.3f ms\n", elapsed);
   std::printf("throughput: %.3f Msamples/s\n", (double)st.samples / elapsed * 1e-3);
+  } // (frames)
   ptx_scene_destroy(scene);
   pth_scene_free(hs);
   return 0;

@@ -166,6 +166,15 @@ struct pth_scene {
   std::vector<ptx_material> mats;
   std::vector<ptx_texture> texs;
   double focus = 1.0; // |target - eye| of the scene's camera: what a thin lens focuses on by default (pth_scene_focus_distance)
+  // the camera the scene was built for (pth_scene_camera): what a camera pose is computed against (pth_camera_pose_look_at)
+  double cam_eye[3] = {0, 0, 0}, cam_target[3] = {0, 0, -1}, cam_up[3] = {0, 1, 0}, cam_fov = 0.0, cam_look_at[16] = {};
+  void built_for(const Camera& c, V3 eye, V3 target, V3 up, double fov_deg) {
+    const double e[3] = {eye.x, eye.y, eye.z}, t[3] = {target.x, target.y, target.z}, u[3] = {up.x, up.y, up.z};
+    std::memcpy(cam_eye, e, sizeof e); std::memcpy(cam_target, t, sizeof t); std::memcpy(cam_up, u, sizeof u);
+    cam_fov = fov_deg;
+    std::memcpy(cam_look_at, c.m, sizeof c.m);
+    look(eye, target);
+  }
   void look(V3 eye, V3 target) { focus = std::sqrt((target.x - eye.x) * (target.x - eye.x) + (target.y - eye.y) * (target.y - eye.y) + (target.z - eye.z) * (target.z - eye.z)); }
 
   int solid(double r, double g, double b) {
@@ -265,12 +274,36 @@ const ptx_scene_desc* pth_scene_desc(pth_scene* s) {
 }
 void pth_scene_free(pth_scene* s) { delete s; }
 double pth_scene_focus_distance(const pth_scene* s) { return s ? s->focus : 0.0; }
+int32_t pth_scene_camera(const pth_scene* s, double eye_out[3], double target_out[3], double up_out[3], double* fov_deg_out, double look_at_out[16]) {
+  if (!s || !(s->cam_fov > 0.0)) return -1;
+  if (eye_out) std::memcpy(eye_out, s->cam_eye, sizeof s->cam_eye);
+  if (target_out) std::memcpy(target_out, s->cam_target, sizeof s->cam_target);
+  if (up_out) std::memcpy(up_out, s->cam_up, sizeof s->cam_up);
+  if (fov_deg_out) *fov_deg_out = s->cam_fov;
+  if (look_at_out) std::memcpy(look_at_out, s->cam_look_at, sizeof s->cam_look_at);
+  return 0;
+}
 
 void pth_camera_create(const double eye[3], const double target[3], const double up[3], double aspect, double fov_deg,
                        ptx_camera* view_out, double look_at_out[16]) {
   const Camera c = camera_create(v3(eye[0], eye[1], eye[2]), v3(target[0], target[1], target[2]), v3(up[0], up[1], up[2]), aspect, fov_deg);
   if (view_out) *view_out = c.view;
   if (look_at_out) std::memcpy(look_at_out, c.m, sizeof c.m);
+}
+
+void pth_camera_pose_look_at(const double scene_look_at[16], const double eye[3], const double target[3], const double up[3], double aspect,
+                             double fov_deg, double origin_out[3], double rotation_out[9], ptx_camera* view_out) {
+  const Camera c = camera_create(v3(eye[0], eye[1], eye[2]), v3(target[0], target[1], target[2]), v3(up[0], up[1], up[2]), aspect, fov_deg);
+  Camera scene;
+  std::memcpy(scene.m, scene_look_at, sizeof scene.m);
+  if (origin_out) { // Mat4.transform scene_look_at eye: where the new camera stands in the scene's space
+    const V3 o = camera_transform(scene, v3(eye[0], eye[1], eye[2]));
+    origin_out[0] = o.x; origin_out[1] = o.y; origin_out[2] = o.z;
+  }
+  if (rotation_out) // R_scene * R_new^T on the 3 x 3 row blocks: new camera space -> world -> the scene's space
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) rotation_out[3 * i + j] = (scene.m[i][0] * c.m[j][0] + scene.m[i][1] * c.m[j][1]) + scene.m[i][2] * c.m[j][2];
+  if (view_out) *view_out = c.view;
 }
 
 // shirley_spheres/bin/main.ml: Shirley_spheres.spheres () under Random.init seed, camera (width // height),
@@ -281,7 +314,7 @@ static pth_scene* shirley_build(int32_t width, int32_t height, int32_t no_simd, 
   pth_scene* s = new pth_scene();
   BaseRandom rng(seed);
   const Camera cam = camera_create(v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, 20.0);
-  s->look(v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0));
+  s->built_for(cam, v3(13.0, 2.0, 4.5), v3(0.0, 0.0, 0.0), v3(0.0, 1.0, 0.0), 20.0);
   const double ga[3] = {0.2, 0.3, 0.1}, gb[3] = {0.9, 0.9, 0.9};
   s->sphere(v3(0.0, -1000.0, 0.0), 1000.0, s->material(PTX_MAT_LAMBERTIAN, s->checker(1000, 2000, ga, gb))); // ground
   const int glass = s->material(PTX_MAT_DIELECTRIC, 0, 1.5); // Material.glass
@@ -346,7 +379,7 @@ static pth_scene* cornell_build(int32_t width, int32_t height, double ceiling_em
   pth_scene* s = new pth_scene();
   const double fov = (2.0 * std::atan(0.5)) * 180.0 / kPi;
   const Camera cam = camera_create(v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0), v3(0.0, 1.0, 0.0), (double)width / (double)height, fov);
-  s->look(v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0));
+  s->built_for(cam, v3(0.5, 0.5, -1.0), v3(0.5, 0.5, 0.0), v3(0.0, 1.0, 0.0), fov);
   const V3 ux = v3(1.0, 0.0, 0.0), uy = v3(0.0, 1.0, 0.0), uz = v3(0.0, 0.0, 1.0), org = v3(0.0, 0.0, 0.0);
   auto emit = [&](const std::vector<Tri>& tris) {
     for (const Tri& t : tris) {
@@ -470,7 +503,7 @@ pth_scene* pth_scene_ganesha_from_mesh(int32_t width, int32_t height, const std:
                                        const std::vector<double>& Z, const std::vector<int32_t>& tri, bool sky_bg) {
   pth_scene* s = new pth_scene();
   const Camera cam = camera_create(v3(328.0, 70.282, 345.0), v3(328.0, 10.0, 0.0), v3(-0.00212272, 0.998201, -0.0599264), (double)width / (double)height, 30.0);
-  s->look(v3(328.0, 70.282, 345.0), v3(328.0, 10.0, 0.0));
+  s->built_for(cam, v3(328.0, 70.282, 345.0), v3(328.0, 10.0, 0.0), v3(-0.00212272, 0.998201, -0.0599264), 30.0);
   const int mat = s->material(PTX_MAT_LAMBERTIAN, s->solid(0.1, 0.7, 0.2));
   for (size_t i = 0; i < X.size(); ++i) s->vertex(camera_transform(cam, v3(X[i], Y[i], Z[i])));
   double uv[6];
