@@ -371,6 +371,22 @@ external render_denoised_flat
   -> int
   = "ptx_ml_render_denoised_stub_bytecode" "ptx_ml_render_denoised_stub"
 
+external render_temporal_flat
+  :  scene
+  -> floatarray
+     (* width, height, samples_per_pixel, max_bounces, pass_first, pass_count, max_history_passes, normal_threshold,
+        depth_tolerance, min_weight, denoise, levels, normal_power_log2, feature_passes, flags, sigma_luminance, sigma_depth,
+        sigma_albedo *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* image, W*H*3 *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* accumulated per-pixel error, W*H*3, or empty *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* motion (dx, dy, weight), W*H*3, or empty *)
+  -> int
+  = "ptx_ml_render_temporal_stub"
+
+(* Drops the frame history the scene keeps (ptx_temporal_reset): call it after a change of lighting, textures or environment, which
+   the library does not do for you.  Failure while a render runs on the scene. *)
+external temporal_reset : scene -> unit = "ptx_ml_temporal_reset_stub"
+
 module FA = Stdlib.Float.Array
 
 (* the tables are interned structurally: a 150 k-triangle mesh with one material gets one row, not 150 k *)
@@ -611,6 +627,66 @@ let render_denoised
   in
   render_denoised_flat scene params image err features (fun passes_done rel_err last ->
     on_update ~passes_done ~rel_err ~last)
+;;
+
+(* One frame of a sequence with temporal accumulation (ptx_render_temporal; the rule is in include/ptx.h): passes [pass_first,
+   pass_first + pass_count) of the SEQUENCE's [samples_per_pixel], accumulated onto the history the scene keeps from the frames
+   before by reprojecting every pixel's first hit through the last frame's camera and this one's ([set_camera_pose]); history is
+   dropped where the surface changed.  Advance [pass_first] from frame to frame (and wrap around [samples_per_pixel]): the same
+   slice under a still camera adds the same samples again and gains nothing.  [pass_count] is at least 2.  [denoise] runs the
+   variance-guided a-trous filter on the accumulated frame, with [render_denoised]'s settings.  [err] (if given) receives the
+   accumulated per-pixel standard error and [motion] (if given, W*H*3) each pixel's (dx, dy, weight) into the frame before.
+   The result is the number of pixels that took history: 0 for the first frame of a sequence.  History is dropped by
+   [temporal_reset] and by a frame of another size, never otherwise.  Failure on a scene whose lens is on. *)
+let render_temporal
+  ?(max_history_passes = 64.)
+  ?(normal_threshold = 0.9)
+  ?(depth_tolerance = 0.02)
+  ?(min_weight = 0x1p-10)
+  ?(denoise = false)
+  ?(levels = 5)
+  ?(normal_power_log2 = 5)
+  ?(demodulate = true)
+  ?(sigma_luminance = 4.)
+  ?(sigma_depth = 0.05)
+  ?(sigma_albedo = 0.2)
+  ?err
+  ?motion
+  scene
+  ~width
+  ~height
+  ~samples_per_pixel
+  ~max_bounces
+  ~pass_first
+  ~pass_count
+  ~image
+  =
+  let empty () = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0 in
+  let err = Option.value err ~default:(empty ()) in
+  let motion = Option.value motion ~default:(empty ()) in
+  let params =
+    FA.of_list
+      [ Float.of_int width
+      ; Float.of_int height
+      ; Float.of_int samples_per_pixel
+      ; Float.of_int max_bounces
+      ; Float.of_int pass_first
+      ; Float.of_int pass_count
+      ; max_history_passes
+      ; normal_threshold
+      ; depth_tolerance
+      ; min_weight
+      ; (if denoise then 1. else 0.)
+      ; Float.of_int levels
+      ; Float.of_int normal_power_log2
+      ; 0.
+      ; (if demodulate then 1. else 0.)
+      ; sigma_luminance
+      ; sigma_depth
+      ; sigma_albedo
+      ]
+  in
+  render_temporal_flat scene params image err motion
 ;;
 
 (* [render] with per-pixel pass counts: round 1 gives every pixel [min_passes] passes, every later round gives the pixels whose

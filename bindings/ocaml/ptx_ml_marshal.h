@@ -250,6 +250,41 @@ static __attribute__((unused)) int32_t ptx_ml_render_denoised(ptx_scene* s, cons
   return ptx_render_denoised(s, &p, &pp, &dn, image, err, feat, passes_done, NULL, on_update, user);
 }
 
+/* One frame of a sequence with temporal accumulation (ptx_render_temporal): params18 = width, height, samples_per_pixel (the
+ * SEQUENCE's N), max_bounces, pass_first, pass_count, then the temporal settings max_history_passes, normal_threshold,
+ * depth_tolerance, min_weight, then denoise (0 = no spatial filter) and the denoiser's levels, normal_power_log2, feature_passes,
+ * flags, sigma_luminance, sigma_depth, sigma_albedo (read only when denoise is not 0).  image (W*H*3) holds the frame, err (nullable)
+ * the accumulated per-pixel standard error, motion (nullable, W*H*3) each pixel's (dx, dy, weight) into the frame before,
+ * *history_pixels (nullable) how many pixels took history. */
+static __attribute__((unused)) int32_t ptx_ml_render_temporal(ptx_scene* s, const double* params18, double* image, double* err, double* motion,
+                                                              int64_t* history_pixels) {
+  if (!params18) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params18[0];
+  p.height = (int32_t)params18[1];
+  p.samples_per_pixel = (int32_t)params18[2];
+  p.max_bounces = (int32_t)params18[3];
+  ptx_temporal_params tp;
+  tp.max_history_passes = params18[6];
+  tp.normal_threshold = params18[7];
+  tp.depth_tolerance = params18[8];
+  tp.min_weight = params18[9];
+  ptx_denoise_params dn;
+  memset(&dn, 0, sizeof dn);
+  dn.levels = (int32_t)params18[11];
+  dn.normal_power_log2 = (int32_t)params18[12];
+  dn.feature_passes = (int32_t)params18[13];
+  dn.flags = (int32_t)params18[14];
+  dn.sigma_luminance = params18[15];
+  dn.sigma_depth = params18[16];
+  dn.sigma_albedo = params18[17];
+  return ptx_render_temporal(s, &p, &tp, params18[10] != 0.0 ? &dn : NULL, (int32_t)params18[4], (int32_t)params18[5], image, err, motion,
+                             history_pixels, NULL);
+}
+/* Ptx.temporal_reset: drops the frame history the scene keeps (ptx_temporal_reset) */
+static __attribute__((unused)) int32_t ptx_ml_temporal_reset(ptx_scene* s) { return ptx_temporal_reset(s); }
+
 /* Ptx.set_film: the film every later render of the scene applies (ptx_scene_set_film) */
 static __attribute__((unused)) int32_t ptx_ml_set_film(ptx_scene* s, int32_t order, int32_t pixel_radius, int32_t flags) {
   ptx_film_params f;

@@ -808,3 +808,49 @@ CAMLprim value ptx_ml_render_denoised_stub_bytecode(value* argv, int argn) {
   (void)argn;
   return ptx_ml_render_denoised_stub(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5]);
 }
+
+/* external render_temporal_flat : scene -> floatarray -> image -> err -> motion -> int = "ptx_ml_render_temporal_stub"
+ * (scene, the 18 floats of ptx_ml_render_temporal, image (W*H*3), err (W*H*3 or empty), motion (W*H*3 or empty)) -> the pixels that
+ * took history.  One frame of a sequence: no callback runs, so nothing can raise while the lock is released. */
+CAMLprim value ptx_ml_render_temporal_stub(value handle, value params, value image, value err, value motion) {
+  CAMLparam5(handle, params, image, err, motion);
+  if (floatarray_length(params) != 18) caml_invalid_argument("Ptx.render_temporal: params needs 18 floats");
+  double p18[18];
+  memcpy(p18, floatarray_data(params), sizeof p18);
+  const intnat w = (intnat)p18[0], h = (intnat)p18[1];
+  if (w <= 0 || h <= 0 || Caml_ba_array_val(image)->dim[0] != w * h * 3)
+    caml_invalid_argument("Ptx.render_temporal: image must hold width * height * 3 floats");
+  const intnat n_err = Caml_ba_array_val(err)->dim[0];
+  if (n_err != 0 && n_err != w * h * 3) caml_invalid_argument("Ptx.render_temporal: err must be empty or hold width * height * 3 floats");
+  const intnat n_motion = Caml_ba_array_val(motion)->dim[0];
+  if (n_motion != 0 && n_motion != w * h * 3) caml_invalid_argument("Ptx.render_temporal: motion must be empty or hold width * height * 3 floats");
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_temporal: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_temporal: scene already destroyed");
+  double* out = (double*)Caml_ba_data_val(image); /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  double* err_out = n_err ? (double*)Caml_ba_data_val(err) : NULL;
+  double* motion_out = n_motion ? (double*)Caml_ba_data_val(motion) : NULL;
+  int64_t history_pixels = 0;
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_temporal(s, p18, out, err_out, motion_out, &history_pixels);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_long((intnat)history_pixels));
+}
+
+/* external temporal_reset : scene -> unit = "ptx_ml_temporal_reset_stub" (ptx_temporal_reset).  Like set_camera_pose it takes the scene
+ * exclusively: Failure while a render runs on another thread or domain. */
+CAMLprim value ptx_ml_temporal_reset_stub(value handle) {
+  CAMLparam1(handle);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.temporal_reset: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.temporal_reset: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_temporal_reset(s);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.temporal_reset: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}

@@ -889,6 +889,128 @@ int32_t ptx_scene_camera_pose(const ptx_scene* scene, double origin_out[3], doub
 int32_t ptx_camera_rays(ptx_scene* scene, const ptx_render_params* params, int64_t n, const int32_t* xs, const int32_t* ys, const int32_t* passes,
                         double* origins_out /* 3n */, double* directions_out /* 3n */);
 
+/* ---- temporal accumulation: the frame history reprojected across camera poses ----
+ * The temporal half of the variance-guided filter: the per-pixel moments of the frames before are carried into the new frame by
+ * reprojecting every pixel's first hit through the two cameras, and dropped where the surface changed.  Only entry points and two
+ * structs are added: no existing struct or kernel changes, the ABI version stays 6, and a scene that never calls these launches
+ * exactly what it launched before.  Everything here runs on ONE GPU over the whole image.
+ *
+ * The history record of a pixel: PTX_HISTORY_DOUBLES doubles at index (y * W + x) * 12 of a 16-byte aligned buffer (the records
+ * move as 16-byte accesses; any hipMalloc'ed buffer is aligned):
+ *   [0..2]  M1  the running mean radiance
+ *   [3..5]  M2  the running mean of the squared samples
+ *   [6]     N   the effective passes behind them, as a double; 0 = no history, so a zeroed buffer is the empty history
+ *   [7]     hf  h / kfd: the share of the feature passes that hit
+ *   [8..10] n   the mean normal
+ *   [11]    zc  the mean hit distance from the camera of the frame that wrote the record (0 where nothing was hit)
+ *
+ * A camera (ptx_temporal_camera, 128 bytes) is an origin, a row-major rotation and the four view fields, as
+ * ptx_scene_set_camera_pose takes them; it is checked like a pose (finite, max |R R^T - I| <= 1e-9, det R > 0) and view_x and
+ * view_y must be non-zero (the rule divides by them).  The settings (ptx_temporal_params, 32 bytes) are accepted when all four are
+ * finite, max_history_passes >= 0, normal_threshold in [-1, 1], depth_tolerance >= 0 and 0 <= min_weight < 1.
+ * ptx_temporal_defaults gives 64, 0.9, 0.02 and 2^-10; they may be retuned only with the CPU quality table of
+ * tests/test_temporal_reference.py recorded beside them (README.md).
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction), for pixel (x, y) of a W x H frame with k = passes_done >= 2
+ * passes, kf = feature_passes_done >= 1 feature passes, the raw sums S1 and square sums S2 of THIS frame's passes (as
+ * ptx_render_passes_device leaves them), the feature sums A, Nrm, Z, h (ptx_render_features_device), the current camera
+ * (o, R, llx, lly, vx, vy), the camera of the frame that wrote the previous history (primed: o', R' = (r00' r01' r02' / r10' ... ),
+ * llx', lly', vx', vy') and cap = max_history_passes:
+ *   current     kd = (double)k;  kfd = (double)kf
+ *               mu_c = S1_c / kd;  nu_c = S2_c / kd
+ *               hf = h / kfd;  n = Nrm / kfd;  z = h > 0 ? Z / h : 0.0
+ *               cx = ((double)x + 0.5) * (1.0 / W);  cy = 1.0 - ((double)y + 0.5) * (1.0 / H)
+ *               d = the camera-pose rule's direction for (cx, cy), no lens, under the CURRENT camera
+ *   reproject   (a NULL previous history: every pixel takes "no history")
+ *               h > 0:   P = (o.x + z * d.x, o.y + z * d.y, o.z + z * d.z);  v = (P.x - o'.x, P.y - o'.y, P.z - o'.z)
+ *               h == 0:  v = d                                               (a miss is a point at infinity)
+ *               c = ((r00' * v.x + r10' * v.y) + r20' * v.z, (r01' * v.x + r11' * v.y) + r21' * v.z,
+ *                    (r02' * v.x + r12' * v.y) + r22' * v.z)                 (R'^T v)
+ *               if !(c.z < 0): no history
+ *               iz = -c.z;  qx = c.x / iz;  qy = c.y / iz
+ *               fx = ((qx - llx') / vx') * (double)W - 0.5;  fy = (1.0 - (qy - lly') / vy') * (double)H - 0.5
+ *               if !(fx > -1 && fx < W && fy > -1 && fy < H): no history     (NaN fails)
+ *               x0 = floor(fx), y0 = floor(fy);  tx = fx - x0;  ty = fy - y0
+ *               dist = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z)
+ *               sw = a1_c = a2_c = aN = 0;  taps j = 0, 1 (outer), i = 0, 1 (inner), q = (x0 + i, y0 + j):
+ *                 skip q outside the image;  rec = the previous history at q;  skip unless rec.N > 0
+ *                 h == 0:  skip unless rec.hf == 0
+ *                 h > 0:   skip unless rec.hf > 0 and (n.x * rec.n.x + n.y * rec.n.y) + n.z * rec.n.z >= normal_threshold
+ *                                                 and fabs(dist - rec.zc) <= depth_tolerance * dist
+ *                 w = (i ? tx : 1.0 - tx) * (j ? ty : 1.0 - ty)
+ *                 sw = sw + w;  a1_c = a1_c + w * rec.M1_c;  a2_c = a2_c + w * rec.M2_c;  aN = aN + w * rec.N
+ *               history iff sw > min_weight
+ *   blend       history:     H1_c = a1_c / sw;  H2_c = a2_c / sw;  NH = aN / sw;  if NH > cap: NH = cap
+ *                            al = kd / (NH + kd);  M1_c = H1_c * (1.0 - al) + mu_c * al;  M2_c = H2_c * (1.0 - al) + nu_c * al
+ *                            N = NH + kd
+ *               no history:  M1 = mu;  M2 = nu;  N = kd
+ *   outputs     the new record {M1, M2, N, hf, n, z}
+ *               raw_out_c = M1_c * kd: SUMS as of k passes, so ptx_denoise_device with passes_done = k and the film with spp = k
+ *                 apply unchanged
+ *               var_c = M2_c - M1_c * M1_c, set to 0 unless var_c > 0;  err_out_c = sqrt(var_c / (N - 1.0))
+ *               motion_out (nullable, W * H * 3): (fx - x, fy - y, sw) with history, (0, 0, 0) without
+ * With cap = 0 the blend has al = 1 and returns mu bit for bit while the pixel still counts as having history.  A miss matches
+ * misses only (a sky pixel's history follows the rotation, not the translation).
+ *
+ * ptx_temporal_accumulate_device: all buffers are DEVICE memory -- d_raw, d_sq, d_raw_out, d_err_out W*H*3, d_feat W*H*8,
+ * d_hist_prev (nullable) and d_hist_out W*H*12, d_motion_out (nullable) W*H*3 -- and must not alias one another (d_hist_out ==
+ * d_hist_prev included: a pixel's taps read records other pixels write).  *history_pixels_out (HOST, nullable): the pixels that
+ * took history.  prev_camera may be NULL only with a NULL history (it is then not read).  One thread owns a pixel, no float
+ * atomics: the same inputs give the same bits on every run.  Waits for `stream`.  PTX_ERR_ARG for NULL or aliased buffers,
+ * passes_done < 2, feature_passes_done < 1, refused settings or cameras; PTX_ERR_STATE for device < 0 (no CPU fallback). */
+#define PTX_HISTORY_DOUBLES 12
+typedef struct ptx_temporal_camera { /* 128 bytes */
+  double origin[3];
+  double rotation[9]; /* row-major */
+  ptx_camera view;
+} ptx_temporal_camera;
+typedef struct ptx_temporal_params { /* 32 bytes */
+  double max_history_passes; /* cap >= 0: a history counts for at most this many passes against the frame's k */
+  double normal_threshold;   /* in [-1, 1]: a tap is kept when n . n_tap >= this */
+  double depth_tolerance;    /* >= 0: ... and |dist - zc_tap| <= this * dist */
+  double min_weight;         /* in [0, 1): history needs more than this much bilinear weight left */
+} ptx_temporal_params;
+/* 64, 0.9, 0.02, 2^-10 */
+int32_t ptx_temporal_defaults(ptx_temporal_params* out);
+int32_t ptx_temporal_accumulate_device(int32_t device, int32_t width, int32_t height, const ptx_temporal_params* temporal,
+                                       int32_t passes_done /* k >= 2 */, int32_t feature_passes_done /* kf >= 1 */,
+                                       const ptx_temporal_camera* cur_camera, const ptx_temporal_camera* prev_camera,
+                                       const double* d_raw, const double* d_sq, const double* d_feat,
+                                       const double* d_hist_prev /* nullable */, double* d_hist_out, double* d_raw_out,
+                                       double* d_err_out, double* d_motion_out /* nullable */,
+                                       int64_t* history_pixels_out /* HOST, nullable */, void* stream);
+
+/* One frame of a sequence on a scene handle.  params->samples_per_pixel is the SEQUENCE's N, which fixes the sampler; the frame
+ * renders passes [pass_first, pass_first + pass_count) of it.  ADVANCE pass_first FROM FRAME TO FRAME (and wrap around N): under a
+ * still camera the same slice draws the same samples again, the history and the frame are then the same numbers, and accumulating
+ * them gains nothing -- different slices are different points of the low-discrepancy sequence, and their mean converges.
+ * The call is this chain and equals it bit for bit:
+ *   1. zero the raw sums, the square sums and the feature sums
+ *   2. ptx_render_passes_device over the range, with square sums
+ *   3. ptx_render_features_device over the same range
+ *   4. ptx_temporal_accumulate_device with k = kf = pass_count; the current camera is the scene's pose (ptx_scene_camera_pose), or
+ *      origin 0, the identity and the scene's own view while the pose is off; the previous camera and history are what the handle
+ *      kept from the frame before (none: a NULL history)
+ *   5. with `denoise` (nullable: no spatial filter): ptx_denoise_device(passes_done = pass_count, kf = pass_count) on the
+ *      accumulated sums and error (denoise->feature_passes is not read)
+ *   6. the scene's film (ptx_scene_set_film) with spp = pass_count
+ *   7. the copy to rgb_out (HOST, W*H*3); err_out (HOST, nullable, W*H*3): the accumulated err; motion_out (HOST, nullable, W*H*3);
+ *      *history_pixels_out (nullable)
+ * The handle then keeps the new history and the camera (it owns two history buffers and swaps them).  The history is dropped by
+ * ptx_temporal_reset and by a frame of another width or height, AND NEVER OTHERWISE: a caller who changes the lighting mode, a
+ * texture image, the environment or anything else the radiance depends on calls ptx_temporal_reset themself.  Moving geometry or
+ * lights, and what is seen through a reflection or refraction at the first hit, are not reprojected (the first hit's motion is).
+ * PTX_ERR_STATE on a scene whose lens is on (a lens ray's first hit is not a pinhole projection), on a host-only scene and from a
+ * callback of a running render; PTX_ERR_ARG for n_gpus > 1, band_step > 1, pass_count < 2, a range outside [0, N) and refused
+ * settings.  A failed call leaves the history as it was, a failed frame of another size included: that frame reads no history, and
+ * the handle's is replaced only once the frame stands.  stats->samples = W * H * pass_count. */
+int32_t ptx_render_temporal(ptx_scene* scene, const ptx_render_params* params, const ptx_temporal_params* temporal,
+                            const ptx_denoise_params* denoise /* nullable */, int32_t pass_first, int32_t pass_count, double* rgb_out,
+                            double* err_out /* nullable */, double* motion_out /* nullable */, int64_t* history_pixels_out /* nullable */,
+                            ptx_stats* stats);
+/* drops the history the handle keeps (its buffers stay); a host-only scene accepts it; PTX_ERR_STATE while a render runs */
+int32_t ptx_temporal_reset(ptx_scene* scene);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

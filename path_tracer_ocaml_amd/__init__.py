@@ -46,6 +46,7 @@ EXPORTS = (
     "ptx_environment_sample", "ptx_environment_pdf",
     "ptx_scene_set_lens", "ptx_scene_lens",
     "ptx_scene_set_camera_pose", "ptx_scene_camera_pose", "ptx_camera_rays",
+    "ptx_temporal_defaults", "ptx_temporal_accumulate_device", "ptx_render_temporal", "ptx_temporal_reset",
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
 )
 
@@ -169,6 +170,14 @@ def lib():
         L.ptx_scene_set_camera_pose.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.Camera)]
         L.ptx_scene_camera_pose.argtypes = [C.c_void_p, dp, dp, C.POINTER(abi.Camera)]
         L.ptx_camera_rays.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int64, ip, ip, ip, dp, dp]
+    if hasattr(L, "ptx_render_temporal"):  # (likewise)
+        tpp, tcp = C.POINTER(abi.TemporalParams), C.POINTER(abi.TemporalCamera)
+        L.ptx_temporal_defaults.argtypes = [tpp]
+        L.ptx_temporal_accumulate_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, tpp, C.c_int32, C.c_int32, tcp, tcp] + \
+            [C.c_void_p] * 8 + [C.POINTER(C.c_int64), C.c_void_p]
+        L.ptx_render_temporal.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), tpp, C.POINTER(abi.DenoiseParams), C.c_int32,
+                                          C.c_int32, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(abi.Stats)]
+        L.ptx_temporal_reset.argtypes = [C.c_void_p]
     _LIB = L
     return L
 
@@ -681,6 +690,35 @@ class Scene:
         _check(rc)
         return out, err_out, feat_out, done.value, stats_dict(st)
 
+    def render_temporal(self, width, height, samples_per_pixel, max_bounces, pass_first, pass_count, temporal=None, denoise=None,
+                        want_err=False, want_motion=False, out=None, **kw):
+        """ptx_render_temporal: one frame of a sequence -- passes [pass_first, pass_first + pass_count) of the sequence's
+        `samples_per_pixel`, accumulated onto the history this handle keeps by reprojecting every first hit through the last
+        frame's camera and this one's (the scene's pose).  Advance pass_first from frame to frame: the same slice under a still
+        camera adds the same samples again.  `temporal`: an abi.TemporalParams, a dict over the defaults, or None;
+        `denoise`: None for no spatial filter, else as render_denoised takes it (True: the defaults).
+        Returns (rgb, err or None, motion or None, history_pixels, stats)."""
+        if int(pass_count) < 2:
+            raise ValueError("pass_count must be >= 2")
+        if kw.get("n_gpus", 0) > 1 or kw.get("band_step", 0) > 1:
+            raise ValueError("temporal rendering runs on one GPU over the whole image")
+        tp = temporal_params(temporal)
+        dn = None if denoise is None or denoise is False else denoise_params(None if denoise is True else denoise)
+        out = _image_arg(out, width, height, "out")
+        err = np.zeros((height, width, 3)) if want_err else None
+        motion = np.zeros((height, width, 3)) if want_motion else None
+        p = render_params(width, height, samples_per_pixel, max_bounces, **kw)
+        took = C.c_int64(0)
+        st = abi.Stats()
+        _check(lib().ptx_render_temporal(self._h, C.byref(p), C.byref(tp), C.byref(dn) if dn is not None else None, int(pass_first),
+                                         int(pass_count), _dp(out), _dp(err) if want_err else None,
+                                         _dp(motion) if want_motion else None, C.byref(took), C.byref(st)))
+        return out, err, motion, took.value, stats_dict(st)
+
+    def temporal_reset(self):
+        """ptx_temporal_reset: drops the frame history this handle keeps (after a change of lighting, textures or environment)"""
+        _check(lib().ptx_temporal_reset(self._h))
+
     def trace_samples(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes, count_work=False):
         xs = np.ascontiguousarray(xs, dtype=np.int32)
         ys = np.ascontiguousarray(ys, dtype=np.int32)
@@ -829,6 +867,55 @@ def denoise_device(device, width, height, denoise, passes_done, feature_passes_d
                                     C.c_void_p(d_passes_ptr) if d_passes_ptr else None, int(feature_passes_done),
                                     C.c_void_p(d_raw_ptr), C.c_void_p(d_err_ptr), C.c_void_p(d_feat_ptr), C.c_void_p(d_out_ptr),
                                     C.c_void_p(stream) if stream else None))
+
+
+def temporal_defaults():
+    """ptx_temporal_defaults: max_history_passes 64, normal_threshold 0.9, depth_tolerance 0.02, min_weight 2^-10"""
+    t = abi.TemporalParams()
+    _check(lib().ptx_temporal_defaults(C.byref(t)))
+    return t
+
+
+def temporal_params(temporal=None):
+    """An abi.TemporalParams from None (the defaults), a dict of fields over the defaults, or a TemporalParams; checked as the
+    library checks it (ValueError)."""
+    if isinstance(temporal, abi.TemporalParams):
+        t = temporal
+    else:
+        t = temporal_defaults()
+        fields = {f for f, _ in abi.TemporalParams._fields_}
+        for k, v in (temporal or {}).items():
+            if k not in fields:
+                raise ValueError(f"unknown temporal setting {k!r}")
+            setattr(t, k, float(v))
+    inf = float("inf")
+    if not 0.0 <= t.max_history_passes < inf:
+        raise ValueError("max_history_passes must be >= 0 and finite")
+    if not -1.0 <= t.normal_threshold <= 1.0:
+        raise ValueError("normal_threshold must be in [-1, 1]")
+    if not 0.0 <= t.depth_tolerance < inf:
+        raise ValueError("depth_tolerance must be >= 0 and finite")
+    if not 0.0 <= t.min_weight < 1.0:
+        raise ValueError("min_weight must be in [0, 1)")
+    return t
+
+
+def temporal_accumulate_device(device, width, height, temporal, passes_done, feature_passes_done, cur_camera, prev_camera, d_raw_ptr,
+                               d_sq_ptr, d_feat_ptr, d_hist_prev_ptr, d_hist_out_ptr, d_raw_out_ptr, d_err_out_ptr,
+                               d_motion_out_ptr=None, stream=None):
+    """ptx_temporal_accumulate_device: this frame's DEVICE sums (raw, squares: W*H*3), feature sums (W*H*8) and the previous
+    history (W*H*12, or None) reprojected from prev_camera into cur_camera (abi.TemporalCamera; prev_camera None only with no
+    history) -> the new history, the accumulated sums as of passes_done passes, their standard error and, if asked for, the
+    motion (W*H*3).  Returns the number of pixels that took history."""
+    tp = temporal_params(temporal)
+    took = C.c_int64(0)
+    vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+    _check(lib().ptx_temporal_accumulate_device(int(device), int(width), int(height), C.byref(tp), int(passes_done),
+                                                int(feature_passes_done), C.byref(cur_camera),
+                                                C.byref(prev_camera) if prev_camera is not None else None, vp(d_raw_ptr), vp(d_sq_ptr),
+                                                vp(d_feat_ptr), vp(d_hist_prev_ptr), vp(d_hist_out_ptr), vp(d_raw_out_ptr),
+                                                vp(d_err_out_ptr), vp(d_motion_out_ptr), C.byref(took), vp(stream)))
+    return took.value
 
 
 def film_defaults():

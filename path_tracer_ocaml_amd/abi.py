@@ -107,6 +107,27 @@ class DenoiseParams(C.Structure):
                 ("sigma_luminance", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
+PTX_HISTORY_DOUBLES = 12  # M1 r g b, M2 r g b, N, hf, normal x y z, zc
+
+
+class TemporalCamera(C.Structure):  # ptx_temporal_camera, 128 bytes
+    _fields_ = [("origin", C.c_double * 3), ("rotation", C.c_double * 9), ("view", Camera)]
+
+
+class TemporalParams(C.Structure):  # ptx_temporal_params, 32 bytes
+    _fields_ = [("max_history_passes", C.c_double), ("normal_threshold", C.c_double), ("depth_tolerance", C.c_double),
+                ("min_weight", C.c_double)]
+
+
+def temporal_camera(origin, rotation, view):
+    """An abi.TemporalCamera from an origin (3), a rotation (3 x 3, row-major) and a view: a Camera or its four fields."""
+    import numpy as np
+    o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+    r = np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+    v = view if isinstance(view, Camera) else Camera(*[float(a) for a in view])
+    return TemporalCamera((C.c_double * 3)(*o), (C.c_double * 9)(*r), Camera(v.lower_left_x, v.lower_left_y, v.view_x, v.view_y))
+
+
 PTX_FILM_MAX_ORDER, PTX_FILM_MAX_RADIUS = 16, 7
 PTX_FILM_RENORMALISE = 1
 

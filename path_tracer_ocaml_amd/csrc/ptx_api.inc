@@ -405,6 +405,13 @@ struct ptx_scene {
   DevBuf<uint32_t> feat_work;
   DevBuf<uint4> feat_susp;
   DevBuf<double> feat, feat_mean, den_raw, den_guide, den_cv[2];
+  /* ptx_render_temporal: the two history buffers (hist[hist_cur] holds the last frame's records while hist_valid), the size and
+   * camera of the frame that wrote them, the accumulated sums, the motion and the history count */
+  DevBuf<double> hist[2], temporal_raw, temporal_motion;
+  DevBuf<unsigned long long> temporal_count;
+  int hist_cur = 0, hist_w = 0, hist_h = 0;
+  bool hist_valid = false;
+  ptx_temporal_camera hist_camera{};
   DevBuf<PtCounters> counters;
   std::vector<TimedLaunch> timed;
   std::vector<hipEvent_t> event_pool;
@@ -3676,6 +3683,215 @@ int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const p
   HIP_TRY(hipSetDevice(s->device));
   DenoisePolicy pol{s, p, *pp, *dp, rgb_out, err_out, feat_out, passes_done_out, on_update, user};
   return render_updates(s, p, pol, true, rgb_out, err_out, stats);
+}
+
+/* ---- temporal accumulation (temporal.inc; the rule: include/ptx.h) ---- */
+namespace {
+int check_temporal_params(const ptx_temporal_params* t) {
+  const double v[4] = {t->max_history_passes, t->normal_threshold, t->depth_tolerance, t->min_weight};
+  for (double a : v)
+    if (!std::isfinite(a)) return fail(PTX_ERR_ARG, "temporal: max_history_passes, normal_threshold, depth_tolerance and min_weight must be finite (got %g)", a);
+  if (!(t->max_history_passes >= 0.0)) return fail(PTX_ERR_ARG, "temporal: max_history_passes must be >= 0 (got %g)", t->max_history_passes);
+  if (!(t->normal_threshold >= -1.0 && t->normal_threshold <= 1.0)) return fail(PTX_ERR_ARG, "temporal: normal_threshold must be in [-1, 1] (got %g)", t->normal_threshold);
+  if (!(t->depth_tolerance >= 0.0)) return fail(PTX_ERR_ARG, "temporal: depth_tolerance must be >= 0 (got %g)", t->depth_tolerance);
+  if (!(t->min_weight >= 0.0 && t->min_weight < 1.0)) return fail(PTX_ERR_ARG, "temporal: min_weight must be in [0, 1) (got %g)", t->min_weight);
+  return 0;
+}
+/* a camera of the temporal rule: a pose's conditions, and a view the reprojection can divide by */
+int check_temporal_camera(const ptx_temporal_camera* c, const char* which) {
+  const int rc = check_camera_pose(c->origin, c->rotation, &c->view);
+  if (rc) return rc;
+  if (c->view.view_x == 0.0 || c->view.view_y == 0.0)
+    return fail(PTX_ERR_ARG, "temporal: view_x and view_y of the %s camera must be non-zero (got %g, %g)", which, c->view.view_x, c->view.view_y);
+  return 0;
+}
+PtCameraPose temporal_pose(const ptx_temporal_camera& c) {
+  PtCameraPose cp;
+  std::memcpy(cp.o, c.origin, sizeof cp.o);
+  std::memcpy(cp.r, c.rotation, sizeof cp.r);
+  cp.llx = c.view.lower_left_x; cp.lly = c.view.lower_left_y; cp.vx = c.view.view_x; cp.vy = c.view.view_y;
+  return cp;
+}
+/* the camera a scene's renders launch their rays from: the pose, or origin 0, the identity and the scene's own view */
+ptx_temporal_camera scene_temporal_camera(const ptx_scene* s) {
+  ptx_temporal_camera c;
+  std::memcpy(c.origin, s->pose_origin, sizeof c.origin);
+  std::memcpy(c.rotation, s->pose_rotation, sizeof c.rotation);
+  c.view = s->pose_has_view ? s->pose_view : s->own_view;
+  return c;
+}
+/* k_temporal_accumulate queued on st behind the zeroing of d_count; checked arguments (prev == nullptr exactly when d_hist_prev is) */
+int temporal_queue(int width, int height, const ptx_temporal_params& t, int k, int kf, const ptx_temporal_camera& cur,
+                   const ptx_temporal_camera* prev, const double* d_raw, const double* d_sq, const double* d_feat, const double* d_hist_prev,
+                   double* d_hist_out, double* d_raw_out, double* d_err_out, double* d_motion_out, unsigned long long* d_count, hipStream_t st) {
+  PtTemporal tp{};
+  tp.width = width; tp.height = height; tp.has_prev = d_hist_prev ? 1 : 0;
+  tp.kd = (double)k; tp.kfd = (double)kf;
+  tp.cap = t.max_history_passes; tp.normal_threshold = t.normal_threshold; tp.depth_tolerance = t.depth_tolerance; tp.min_weight = t.min_weight;
+  tp.cur = temporal_pose(cur);
+  tp.prev = temporal_pose(prev ? *prev : cur);
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+  const dim3 grid((unsigned)((width + PT_TEMPORAL_TX - 1) / PT_TEMPORAL_TX), (unsigned)((height + PT_TEMPORAL_TY - 1) / PT_TEMPORAL_TY));
+  hipLaunchKernelGGL(k_temporal_accumulate, grid, dim3(PT_TEMPORAL_TX * PT_TEMPORAL_TY), 0, st, tp, d_raw, d_sq, d_feat, d_hist_prev, d_hist_out,
+                     d_raw_out, d_err_out, d_motion_out, d_count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int32_t ptx_temporal_defaults(ptx_temporal_params* out) {
+  if (!out) return fail(PTX_ERR_ARG, "NULL argument");
+  out->max_history_passes = 64.0;
+  out->normal_threshold = 0.9;
+  out->depth_tolerance = 0.02;
+  out->min_weight = 0x1p-10;
+  return 0;
+}
+
+int32_t ptx_temporal_accumulate_device(int32_t device, int32_t width, int32_t height, const ptx_temporal_params* t, int32_t passes_done,
+                                       int32_t feature_passes_done, const ptx_temporal_camera* cur, const ptx_temporal_camera* prev,
+                                       const double* d_raw, const double* d_sq, const double* d_feat, const double* d_hist_prev,
+                                       double* d_hist_out, double* d_raw_out, double* d_err_out, double* d_motion_out,
+                                       int64_t* history_pixels_out, void* stream) {
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: temporal accumulation runs on a HIP device only, no CPU fallback exists", device);
+  if (!t || !cur || !d_raw || !d_sq || !d_feat || !d_hist_out || !d_raw_out || !d_err_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (width <= 0 || height <= 0) return fail(PTX_ERR_ARG, "bad dimensions (%d x %d)", width, height);
+  if (d_hist_prev && !prev) return fail(PTX_ERR_ARG, "prev_camera may be NULL only with a NULL history");
+  const size_t npix = (size_t)width * (size_t)height;
+  /* no two buffers may overlap: a pixel's taps read records of the previous history that other pixels' threads would be writing */
+  struct Span { const char* name; const double* p; size_t n; };
+  const Span spans[8] = {{"d_raw", d_raw, npix * 3},           {"d_sq", d_sq, npix * 3},           {"d_feat", d_feat, npix * 8},
+                         {"d_hist_prev", d_hist_prev, npix * 12}, {"d_hist_out", d_hist_out, npix * 12}, {"d_raw_out", d_raw_out, npix * 3},
+                         {"d_err_out", d_err_out, npix * 3},   {"d_motion_out", d_motion_out, npix * 3}};
+  for (int a = 0; a < 8; ++a)
+    for (int b = a + 1; b < 8; ++b) {
+      if (!spans[a].p || !spans[b].p) continue;
+      const uintptr_t a0 = (uintptr_t)spans[a].p, a1 = a0 + spans[a].n * sizeof(double), b0 = (uintptr_t)spans[b].p, b1 = b0 + spans[b].n * sizeof(double);
+      if (a0 < b1 && b0 < a1) return fail(PTX_ERR_ARG, "%s and %s must not alias", spans[a].name, spans[b].name);
+    }
+  if (((uintptr_t)d_feat | (uintptr_t)d_hist_prev | (uintptr_t)d_hist_out) & 15u) return fail(PTX_ERR_ARG, "d_feat, d_hist_prev and d_hist_out must be 16-byte aligned");
+  if (passes_done < 2) return fail(PTX_ERR_ARG, "passes_done must be >= 2 (got %d): the error of fewer passes is infinite", passes_done);
+  if (feature_passes_done < 1) return fail(PTX_ERR_ARG, "feature_passes_done must be >= 1 (got %d)", feature_passes_done);
+  int rc = check_temporal_params(t);
+  if (rc) return rc;
+  rc = check_temporal_camera(cur, "current");
+  if (rc) return rc;
+  if (prev) {
+    rc = check_temporal_camera(prev, "previous");
+    if (rc) return rc;
+  }
+  rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  LocalBuf<unsigned long long> count;
+  HIP_TRY(count.ensure(1));
+  hipStream_t st = (hipStream_t)stream;
+  rc = temporal_queue(width, height, *t, passes_done, feature_passes_done, *cur, d_hist_prev ? prev : nullptr, d_raw, d_sq, d_feat, d_hist_prev,
+                      d_hist_out, d_raw_out, d_err_out, d_motion_out, count.p, st);
+  unsigned long long took = 0;
+  hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&took, count.p, sizeof took, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st); /* (also on an error: the count buffer goes with this call) */
+  if (rc) return rc;
+  HIP_TRY(e);
+  HIP_TRY(e2);
+  if (history_pixels_out) *history_pixels_out = (int64_t)took;
+  return 0;
+}
+
+int32_t ptx_temporal_reset(ptx_scene* s) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the history cannot be dropped while a render runs on the scene");
+  s->hist_valid = false;
+  return 0;
+}
+
+int32_t ptx_render_temporal(ptx_scene* s, const ptx_render_params* p_in, const ptx_temporal_params* tp, const ptx_denoise_params* dp,
+                            int32_t pass_first, int32_t pass_count, double* rgb_out, double* err_out, double* motion_out,
+                            int64_t* history_pixels_out, ptx_stats* stats) {
+  int rc = check_render_args(s, p_in, (tp && rgb_out) ? nullptr : "NULL argument");
+  if (rc) return rc;
+  rc = check_one_gpu(p_in, "temporal rendering");
+  if (rc) return rc;
+  if (pass_count < 2) return fail(PTX_ERR_ARG, "pass_count must be >= 2 (got %d): the error of fewer passes is infinite", pass_count);
+  rc = check_pass_range(p_in, pass_first, pass_count);
+  if (rc) return rc;
+  rc = check_temporal_params(tp);
+  if (rc) return rc;
+  if (dp) {
+    rc = check_denoise_params(dp);
+    if (rc) return rc;
+  }
+  if (s->lens_radius > 0.0)
+    return fail(PTX_ERR_STATE, "temporal rendering needs a pinhole: a lens ray's first hit is not a pinhole projection (ptx_scene_set_lens(scene, 0, ...) first)");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "temporal rendering cannot start while a render runs on the scene");
+  const ptx_temporal_camera cur = scene_temporal_camera(s);
+  rc = check_temporal_camera(&cur, "current");
+  if (rc) return rc;
+  ptx_render_params p = *p_in;
+  p.band_step = 0; /* whole image on this GPU */
+  p.n_gpus = 0;
+  p.flags = 0;
+  HIP_TRY(hipSetDevice(s->device));
+  RenderBusy busy(s);
+  const double t0 = wall_ms();
+  const size_t npix = (size_t)p.width * (size_t)p.height, n = npix * 3;
+  /* a frame of another size starts without history; the handle's own history goes only once that frame stands */
+  const bool have_hist = s->hist_valid && s->hist_w == p.width && s->hist_h == p.height;
+  HIP_TRY(s->raw.ensure(n));
+  HIP_TRY(s->sq.ensure(n));
+  HIP_TRY(s->rgb.ensure(n));
+  HIP_TRY(s->err.ensure(n));
+  HIP_TRY(s->feat.ensure(npix * 8));
+  HIP_TRY(s->temporal_raw.ensure(n));
+  HIP_TRY(s->temporal_count.ensure(1));
+  if (motion_out) HIP_TRY(s->temporal_motion.ensure(n));
+  const int out = s->hist_valid ? 1 - s->hist_cur : s->hist_cur; /* (growing a buffer frees it: never the one that holds the history) */
+  HIP_TRY(s->hist[out].ensure(npix * PTX_HISTORY_DOUBLES));
+  if (dp) {
+    HIP_TRY(s->den_raw.ensure(n));
+    HIP_TRY(s->den_guide.ensure(npix * 8));
+    HIP_TRY(s->den_cv[0].ensure(npix * 4));
+    HIP_TRY(s->den_cv[1].ensure(npix * 4));
+  }
+  DrainOnExit drain;
+  HIP_TRY(hipMemsetAsync(s->feat.p, 0, sizeof(double) * npix * 8, nullptr));
+  rc = render_raw(s, &p, s->raw.p, nullptr, stats, nullptr, nullptr, nullptr, PassRange(pass_first, pass_count, true, s->sq.p));
+  if (rc) return rc;
+  rc = features_queue(s, &p, pass_first, pass_count, s->feat.p, nullptr);
+  if (rc) return rc;
+  const double* prev_hist = have_hist ? s->hist[s->hist_cur].p : nullptr;
+  rc = temporal_queue(p.width, p.height, *tp, pass_count, pass_count, cur, prev_hist ? &s->hist_camera : nullptr, s->raw.p, s->sq.p, s->feat.p,
+                      prev_hist, s->hist[out].p, s->temporal_raw.p, s->err.p, motion_out ? s->temporal_motion.p : nullptr, s->temporal_count.p, nullptr);
+  if (rc) return rc;
+  const double* filmed = s->temporal_raw.p;
+  if (dp) {
+    rc = denoise_queue(p.width, p.height, *dp, pass_count, nullptr, pass_count, s->temporal_raw.p, s->err.p, s->feat.p, s->den_guide.p,
+                       s->den_cv[0].p, s->den_cv[1].p, s->den_raw.p, nullptr);
+    if (rc) return rc;
+    filmed = s->den_raw.p;
+  }
+  rc = film_resolve(p.width, p.height, pass_count, filmed, s->rgb.p, nullptr, PtBandMap{1, 1, 0}, 0, -1, s->film);
+  if (rc) return rc;
+  rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n);
+  if (!rc && err_out) rc = framebuffer_to_host(s, s->err.p, err_out, n);
+  if (!rc && motion_out) rc = framebuffer_to_host(s, s->temporal_motion.p, motion_out, n);
+  if (rc) return rc;
+  unsigned long long took = 0;
+  HIP_TRY(hipMemcpy(&took, s->temporal_count.p, sizeof took, hipMemcpyDeviceToHost));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  drain.armed = false;
+  /* the frame stands: the handle keeps its history and its camera */
+  s->hist_cur = out;
+  s->hist_valid = true;
+  s->hist_w = p.width;
+  s->hist_h = p.height;
+  s->hist_camera = cur;
+  if (history_pixels_out) *history_pixels_out = (int64_t)took;
+  if (stats) {
+    stats->samples = (int64_t)p.width * p.height * pass_count;
+    stats->render_ms = wall_ms() - t0;
+  }
+  return 0;
 }
 
 namespace {

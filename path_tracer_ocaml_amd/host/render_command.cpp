@@ -22,7 +22,13 @@
 // --camera-eye=X,Y,Z --camera-target=X,Y,Z [--camera-fov=DEG]: renders from another camera (world coordinates, the scene's own up
 // vector) over the scene built with its default one (ptx_scene_set_camera_pose: no vertex is transformed again, no tree rebuilt).
 // --turntable=N: N frames on a circle about the vertical axis through the target, through ONE scene handle; frame k goes to the -o name
-// with -kkk in front of its extension.
+// with -kkk in front of its extension.  --turntable-arc=DEG (default 360): the N frames cover that arc, so a short sequence takes
+// small steps.
+// --temporal[=CAP] (with --turntable=T): every frame accumulates onto the history of the frames before, reprojected through the two
+// cameras (ptx_render_temporal; CAP = max_history_passes, default 64).  --samples-per-pixel=S is then ONE FRAME's passes: the
+// sequence's N is S * min(T, 16) and frame f renders slice f mod min(T, 16) of it, so consecutive frames draw different points of
+// the low-discrepancy sequence.  With --denoise[=LEVELS] the accumulated frame is filtered.  Each frame prints
+// "frame f -> FILE, history = P pixels".
 // --envmap-sample (with --envmap and --lighting=sampled): the environment is importance-sampled (ptx_scene_set_environment_sampling),
 // and sampled lighting then needs no emissive triangle.
 // --sphere-lamp=X,Y,Z,R,EMIT (with --scene=shirley): a white Lambertian lamp sphere at that world point (pth_scene_shirley_lamp);
@@ -77,6 +83,9 @@ struct Args {
   double camera_eye[3] = {0, 0, 0}, camera_target[3] = {0, 0, 0};
   double camera_fov = 0.0;               // --camera-fov=DEG (0: the scene camera's)
   int turntable = 0;                     // --turntable=N (0: one frame)
+  double turntable_arc = 360.0;          // --turntable-arc=DEG
+  bool have_arc = false;
+  double temporal = -1.0;                // --temporal[=CAP]: max_history_passes (< 0: no temporal accumulation)
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -91,7 +100,8 @@ struct Args {
                "          " PTH_IMAGE_FLAGS_USAGE " [--envmap-sample]\n"
                "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n"
                "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n"
-               "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n",
+               "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n"
+               "          [--turntable-arc=DEG] [--temporal[=CAP]]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -221,6 +231,17 @@ Args parse(int argc, char** argv) {
       const long n = std::strtol(v.c_str(), &end, 10);
       if (end == v.c_str() || *end || n < 1 || n > 999) usage(argv[0], "invalid value for --turntable, must be in 1..999");
       a.turntable = (int)n;
+    } else if (take_value(argc, argv, i, "turntable-arc", nullptr, &v)) {
+      char* end = nullptr;
+      a.turntable_arc = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.turntable_arc > 0.0) || !(a.turntable_arc <= 360.0)) usage(argv[0], "invalid value for --turntable-arc, must be in (0, 360]");
+      a.have_arc = true;
+    } else if (!std::strcmp(argv[i], "--temporal")) {
+      a.temporal = 64.0; // ptx_temporal_defaults' max_history_passes
+    } else if (!std::strncmp(argv[i], "--temporal=", 11)) {
+      char* end = nullptr;
+      a.temporal = std::strtod(argv[i] + 11, &end);
+      if (end == argv[i] + 11 || *end || !(a.temporal >= 0.0) || !std::isfinite(a.temporal)) usage(argv[0], "invalid value for --temporal, CAP must be >= 0");
     }
     else if (!std::strcmp(argv[i], "-ganesha-ply") && i + 1 < argc) a.ganesha_ply = argv[++i]; // Stdlib.Arg spelling
     else if (!std::strcmp(argv[i], "--no-progress")) a.no_progress = true;
@@ -256,6 +277,15 @@ Args parse(int argc, char** argv) {
   if (a.have_eye && a.camera_eye[0] == a.camera_target[0] && a.camera_eye[1] == a.camera_target[1] && a.camera_eye[2] == a.camera_target[2])
     usage(argv[0], "--camera-eye and --camera-target must differ");
   if (a.camera_fov > 0.0 && !a.have_eye && a.turntable == 0) usage(argv[0], "--camera-fov requires --camera-eye and --camera-target, or --turntable");
+  if (a.have_arc && a.turntable == 0) usage(argv[0], "--turntable-arc requires --turntable");
+  if (a.temporal >= 0.0) {
+    if (a.turntable == 0) usage(argv[0], "--temporal requires --turntable");
+    if (a.samples_per_pixel < 2) usage(argv[0], "--temporal requires --samples-per-pixel >= 2 (one frame's passes)");
+    if (adaptive || a.progressive) usage(argv[0], "--temporal cannot be combined with --adaptive or --progressive");
+    if (a.gpus > 1) usage(argv[0], "--temporal renders on one GPU (--gpus=1)");
+    if (a.lens_radius > 0.0) usage(argv[0], "--temporal needs a pinhole: it cannot be combined with --lens-radius");
+    if (!a.aov.empty()) usage(argv[0], "--aov cannot be combined with --temporal");
+  }
   if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
   if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
   if (a.have_sphere_lamp && a.scene != "shirley") usage(argv[0], "--sphere-lamp requires --scene=shirley");
@@ -352,7 +382,9 @@ int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
   if (a.turntable > 0) {
     const double len = std::sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
     const double k[3] = {up[0] / len, up[1] / len, up[2] / len};
-    const double th = 2.0 * 3.14159265358979323846 * (double)frame / (double)a.turntable, c = std::cos(th), s = std::sin(th);
+    // (the full circle keeps its own expression: the default arc gives the angles it always gave)
+    const double arc = a.turntable_arc == 360.0 ? 2.0 * 3.14159265358979323846 : a.turntable_arc * (3.14159265358979323846 / 180.0);
+    const double th = arc * (double)frame / (double)a.turntable, c = std::cos(th), s = std::sin(th);
     const double v[3] = {eye[0] - target[0], eye[1] - target[1], eye[2] - target[2]};
     const double kxv[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
     const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
@@ -478,7 +510,22 @@ int main(int argc, char** argv) {
   Updates upd{output.c_str(), a.width, a.height};
   int rc;
   const bool adaptive = a.adaptive >= 0.0;
-  if (adaptive) {
+  long long history_pixels = 0;
+  if (a.temporal >= 0.0) {
+    // one frame's passes are a slice of the sequence's N = S * min(T, 16): frame f renders slice f mod min(T, 16)
+    const int slices = a.turntable < 16 ? a.turntable : 16, slice = frame % slices;
+    p.samples_per_pixel = a.samples_per_pixel * slices;
+    ptx_temporal_params tp;
+    ptx_temporal_defaults(&tp);
+    tp.max_history_passes = a.temporal;
+    ptx_denoise_params dn;
+    ptx_denoise_defaults(&dn);
+    if (a.denoise >= 0) dn.levels = a.denoise;
+    int64_t took = 0;
+    rc = ptx_render_temporal(scene, &p, &tp, a.denoise >= 0 ? &dn : nullptr, slice * a.samples_per_pixel, a.samples_per_pixel, rgb.data(), nullptr,
+                             nullptr, &took, &st);
+    history_pixels = (long long)took;
+  } else if (adaptive) {
     ptx_adaptive_params ap;
     std::memset(&ap, 0, sizeof ap);
     ap.min_passes = a.min_passes ? a.min_passes : 8;
@@ -517,7 +564,7 @@ int main(int argc, char** argv) {
   (void)ptx_image_unpin(scene);
   const double elapsed = now_ms() - t0;
   if (rc != 0) {
-    std::fprintf(stderr, "%s: %s\n", adaptive ? "ptx_render_adaptive" : a.denoise >= 0 ? "ptx_render_denoised" : a.progressive ? "ptx_render_progressive" : "ptx_render",
+    std::fprintf(stderr, "%s: %s\n", a.temporal >= 0.0 ? "ptx_render_temporal" : adaptive ? "ptx_render_adaptive" : a.denoise >= 0 ? "ptx_render_denoised" : a.progressive ? "ptx_render_progressive" : "ptx_render",
                  ptx_last_error());
     return 1;
   }
@@ -525,7 +572,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "cannot write %s\n", output.c_str());
     return 1;
   }
-  if (a.turntable > 0) std::printf("frame %d -> %s\n", frame, output.c_str());
+  if (a.temporal >= 0.0) std::printf("frame %d -> %s, history = %lld pixels\n", frame, output.c_str(), history_pixels);
+  else if (a.turntable > 0) std::printf("frame %d -> %s\n", frame, output.c_str());
   std::printf("rendered in: %.3f ms\n", elapsed);
   std::printf("throughput: %.3f Msamples/s\n", (double)st.samples / elapsed * 1e-3);
   } // (frames)

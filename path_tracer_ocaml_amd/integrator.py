@@ -97,6 +97,7 @@ class Integrator:
         self.error = self.passes_done = None  # render_progressive
         self.passes = None  # render_adaptive
         self.features = None  # render_denoised
+        self.motion = self.history_pixels = None  # render_temporal
 
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
@@ -150,6 +151,21 @@ class Integrator:
         if out is None:
             self.image[...] = rgb
         self.error, self.passes_done, self.features, self.stats = err, done, feat, st
+        return self.image
+
+    def render_temporal(self, pass_first, pass_count, temporal=None, denoise=None, want_error=False, want_motion=False):
+        """One frame of a sequence (Scene.render_temporal): passes [pass_first, pass_first + pass_count) of ``samples_per_pixel``,
+        accumulated onto the history the scene keeps from the frames before, under the scene's camera pose.  ``image`` holds the
+        frame, ``error`` the accumulated per-pixel standard error (with want_error), ``motion`` each pixel's (dx, dy, weight) into
+        the previous frame (with want_motion) and ``history_pixels`` how many pixels took history.  Advance pass_first from frame
+        to frame; Scene.temporal_reset drops the history."""
+        out = self.image if self.image.flags["C_CONTIGUOUS"] else None
+        rgb, err, motion, took, st = self._scene.render_temporal(self.width, self.height, self.samples_per_pixel, self.max_bounces,
+                                                                 pass_first, pass_count, temporal=temporal, denoise=denoise,
+                                                                 want_err=want_error, want_motion=want_motion, out=out)
+        if out is None:
+            self.image[...] = rgb
+        self.error, self.motion, self.history_pixels, self.passes_done, self.stats = err, motion, took, pass_count, st
         return self.image
 
 
