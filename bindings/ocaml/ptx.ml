@@ -317,6 +317,59 @@ let camera_pose scene =
     let get i = Bigarray.Array1.get out i in
     Some (Array.init 3 get, Array.init 9 (fun i -> get (3 + i)), (get 12, get 13, get 14, get 15)))
 
+(* The camera projection (ptx_scene_set_camera_projection; the rule is in include/ptx.h): [Perspective] is the pinhole, a scene's first
+   state; [Latlong] is a 360-degree panorama in the environment map's (u, v) convention, taken from the pose's origin (the scene's own
+   while the pose is off): written as a PFM it lights another scene.  Sticky.  Failure for [Latlong] while a lens is on, or while a
+   render runs on the scene. *)
+type projection =
+  | Perspective
+  | Latlong
+
+external set_camera_projection_int : scene -> int -> unit = "ptx_ml_set_camera_projection_stub"
+external camera_projection_int : scene -> int = "ptx_ml_camera_projection_stub"
+
+let set_camera_projection scene projection =
+  set_camera_projection_int
+    scene
+    (match projection with
+     | Perspective -> 0
+     | Latlong -> 1)
+
+let camera_projection scene = if camera_projection_int scene = 1 then Latlong else Perspective
+
+(* Radiance along rays the caller owns (ptx_render_rays; the rule is in include/ptx.h): [origins] and [directions] hold 3 floats a ray
+   (unit directions, or any length with [normalize]), [offsets] the sampler offset of every ray (default: its index).  Returns
+   (sums, squares): 3 floats per bin of [rays_per_bin] consecutive rays, folded in ray order from zero; [squares] is empty without
+   [want_sq].  One ray per bin is the per-ray radiance.  Failure for a ray that is not finite, a zero direction or an offset outside
+   [0, 2^31 - 2] (the message names the lowest bad index), and for a host-only scene. *)
+external render_rays_flat
+  :  scene
+  -> floatarray (* max_bounces, rays_per_bin, normalize *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* origins, 3 n *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* directions, 3 n *)
+  -> (int32, Bigarray.int32_elt, Bigarray.c_layout) Bigarray.Array1.t (* offsets, n, or empty *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* sums, 3 n / m *)
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* squares, 3 n / m, or empty *)
+  -> unit
+  = "ptx_ml_render_rays_stub_bytecode" "ptx_ml_render_rays_stub"
+
+let render_rays ?offsets ?(max_bounces = 8) ?(rays_per_bin = 1) ?(normalize = false) ?(want_sq = false) scene ~origins ~directions =
+  let n3 = Bigarray.Array1.dim origins in
+  if rays_per_bin < 1 || n3 mod (3 * rays_per_bin) <> 0
+  then invalid_arg "Ptx.render_rays: origins hold 3 floats a ray and the rays a whole number of bins";
+  let bins3 = n3 / rays_per_bin in
+  let zeros k =
+    let a = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout k in
+    Bigarray.Array1.fill a 0.;
+    a
+  in
+  let offsets = Option.value offsets ~default:(Bigarray.Array1.create Bigarray.int32 Bigarray.c_layout 0) in
+  let sums = zeros bins3 in
+  let sq = zeros (if want_sq then bins3 else 0) in
+  let params = Stdlib.Float.Array.of_list [ Float.of_int max_bounces; Float.of_int rays_per_bin; (if normalize then 1. else 0.) ] in
+  render_rays_flat scene params origins directions offsets sums sq;
+  sums, sq
+
 external render_flat
   :  scene
   -> int (* width *)

@@ -326,6 +326,33 @@ static __attribute__((unused)) int32_t ptx_ml_camera_pose(const ptx_scene* s, do
   return rc;
 }
 
+/* Ptx.set_camera_projection / Ptx.camera_projection: 0 = the pinhole, 1 = the lat-long panorama (ptx_scene_set_camera_projection) */
+static __attribute__((unused)) int32_t ptx_ml_set_camera_projection(ptx_scene* s, int32_t projection) {
+  return ptx_scene_set_camera_projection(s, projection);
+}
+static __attribute__((unused)) int32_t ptx_ml_camera_projection(const ptx_scene* s) { return ptx_scene_camera_projection(s); }
+
+/* Ptx.render_rays (ptx_render_rays): params3 = max_bounces, rays_per_bin, normalize (0 / 1); origins and directions 3 n doubles each,
+ * offsets n int32 or n_offsets = 0 for offset i = i, sums 3 (n / rays_per_bin) doubles, sq as many or n_sq = 0 for none.  -4 for
+ * lengths that do not fit together (nothing is read or written); the library's own refusals keep their codes. */
+static __attribute__((unused)) int32_t ptx_ml_render_rays(ptx_scene* s, const double* params3, const double* origins, int64_t n_origins,
+                                                          const double* directions, int64_t n_directions, const int32_t* offsets,
+                                                          int64_t n_offsets, double* sums, int64_t n_sums, double* sq, int64_t n_sq) {
+  ptx_rays_params p;
+  memset(&p, 0, sizeof p);
+  p.max_bounces = (int32_t)params3[0];
+  p.rays_per_bin = (int32_t)params3[1];
+  p.flags = params3[2] != 0.0 ? PTX_RAYS_NORMALIZE : 0;
+  if (n_origins % 3 != 0 || n_directions != n_origins) return -4;
+  const int64_t n = n_origins / 3;
+  if (n_offsets != 0 && n_offsets != n) return -4;
+  if (p.rays_per_bin >= 1 && n % p.rays_per_bin == 0) { /* (otherwise the library refuses the call before it touches the sums) */
+    const int64_t want = 3 * (n / p.rays_per_bin);
+    if (n_sums != want || (n_sq != 0 && n_sq != want)) return -4;
+  }
+  return ptx_render_rays(s, &p, n, origins, directions, n_offsets ? offsets : NULL, sums, n_sq ? sq : NULL, NULL);
+}
+
 /* Ptx.film_weights: the 2 * pixel_radius + 1 weights into out (n_out doubles); -4 when out is too short for an accepted film (the
  * library's own refusals keep their codes, and nothing is written) */
 static __attribute__((unused)) int32_t ptx_ml_film_weights(int32_t order, int32_t pixel_radius, double* out, int64_t n_out) {

@@ -472,6 +472,71 @@ CAMLprim value ptx_ml_camera_pose_stub(value handle, value out) {
   CAMLreturn(Val_int(rc));
 }
 
+/* external set_camera_projection_int : scene -> int -> unit = "ptx_ml_set_camera_projection_stub" (ptx_scene_set_camera_projection).  What
+ * a running render's camera rays are made of: like set_lens it takes the scene exclusively and raises Failure while a render runs on
+ * another thread or domain, and Failure with the library's message for a refused projection (an unknown kind, LATLONG under a lens). */
+CAMLprim value ptx_ml_set_camera_projection_stub(value handle, value projection) {
+  CAMLparam2(handle, projection);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_camera_projection: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_camera_projection: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_set_camera_projection(s, (int32_t)Int_val(projection));
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_camera_projection: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external camera_projection_int : scene -> int = "ptx_ml_camera_projection_stub" (ptx_scene_camera_projection: 0 or 1) */
+CAMLprim value ptx_ml_camera_projection_stub(value handle) {
+  CAMLparam1(handle);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.camera_projection: scene already destroyed");
+  const int32_t rc = ptx_ml_camera_projection(s);
+  if (rc < 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_int(rc));
+}
+
+/* external render_rays_flat : scene -> floatarray -> doubles -> doubles -> int32s -> doubles -> doubles -> unit
+ * = "ptx_ml_render_rays_stub_bytecode" "ptx_ml_render_rays_stub" (scene, the 3 floats of ptx_ml_render_rays, origins (3 n), directions
+ * (3 n), offsets (n or empty), sums (3 n / m), squares (as many or empty)).  No callback runs, so nothing can raise while the lock is
+ * released. */
+CAMLprim value ptx_ml_render_rays_stub(value handle, value params, value origins, value directions, value offsets, value sums, value sq) {
+  CAMLparam5(handle, params, origins, directions, offsets);
+  CAMLxparam2(sums, sq);
+  if (floatarray_length(params) != 3) caml_invalid_argument("Ptx.render_rays: params needs 3 floats");
+  double p3[3];
+  memcpy(p3, floatarray_data(params), sizeof p3);
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_rays: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_rays: scene already destroyed");
+  /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  const double* o = (const double*)Caml_ba_data_val(origins);
+  const double* d = (const double*)Caml_ba_data_val(directions);
+  const int32_t* off = (const int32_t*)Caml_ba_data_val(offsets);
+  double* sum_out = (double*)Caml_ba_data_val(sums);
+  double* sq_out = (double*)Caml_ba_data_val(sq);
+  const int64_t n_o = (int64_t)Caml_ba_array_val(origins)->dim[0], n_d = (int64_t)Caml_ba_array_val(directions)->dim[0];
+  const int64_t n_off = (int64_t)Caml_ba_array_val(offsets)->dim[0], n_sum = (int64_t)Caml_ba_array_val(sums)->dim[0];
+  const int64_t n_sq = (int64_t)Caml_ba_array_val(sq)->dim[0];
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_rays(s, p3, o, n_o, d, n_d, off, n_off, sum_out, n_sum, sq_out, n_sq);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (rc == -4)
+    caml_invalid_argument("Ptx.render_rays: origins and directions hold 3 floats a ray, offsets one a ray or none, sums and squares 3 a bin");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* bytecode entry of the 7-argument external */
+CAMLprim value ptx_ml_render_rays_stub_bytecode(value* argv, int argn) {
+  (void)argn;
+  return ptx_ml_render_rays_stub(argv[0], argv[1], argv[2], argv[3], argv[4], argv[5], argv[6]);
+}
+
 /* external film_int : scene -> int * int * int = "ptx_ml_film_stub" (ptx_scene_film: order, pixel_radius, flags) */
 CAMLprim value ptx_ml_film_stub(value handle) {
   CAMLparam1(handle);

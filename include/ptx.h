@@ -889,6 +889,47 @@ int32_t ptx_scene_camera_pose(const ptx_scene* scene, double origin_out[3], doub
 int32_t ptx_camera_rays(ptx_scene* scene, const ptx_render_params* params, int64_t n, const int32_t* xs, const int32_t* ys, const int32_t* passes,
                         double* origins_out /* 3n */, double* directions_out /* 3n */);
 
+/* ---- camera projection: a lat-long panorama ----
+ * The library can be lit by a lat-long image (ptx_scene_set_environment); with PTX_PROJECTION_LATLONG it can produce one.  The
+ * panorama uses the environment's own (u, v) convention, so a probe rendered at a point can light another scene.  Only entry points
+ * and two defines are added: no struct or call changes, the ABI version stays 6.
+ *
+ * ptx_scene_set_camera_projection(scene, projection): sticky state of the handle, like the pose.  PTX_PROJECTION_PERSPECTIVE is
+ * the state of every scene that never called the setter, and renders as before, bit for bit.  PTX_ERR_ARG for another value;
+ * PTX_ERR_STATE while a render runs on the scene, and for LATLONG while a lens is on ("... ptx_scene_set_lens(scene, 0, 1) first";
+ * ptx_scene_set_lens with a radius > 0 is refused likewise while LATLONG is on).  A refused call changes nothing.  A host-only scene
+ * accepts it; the replicas a scene owns follow it and ptx_scene_replicate copies it.  ptx_scene_camera_projection returns the kind,
+ * or a negative code for a NULL scene.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction; sincos is pt_math.h's), for a sample with film coordinates
+ * (cx, cy) -- computed exactly as for the pinhole -- with pi = Float.pi:
+ *   u = cx;  v = 1.0 - cy;  al = u * (2.0 * pi) - pi;  th = v * pi
+ *   (sa, ca) = sincos(al);  (st, ct) = sincos(th)
+ *   e = (st * ca, -ct, -(st * sa))
+ *   direction = V3.normalize (Rv(e));  origin = o        the pose rule's Rv and o; origin 0 and the identity while the pose is off
+ *   the ray is Ray.create origin direction
+ * e is the environment-sampling rule's m from (u, v), so the rule is the inverse of the environment lookup: the lookup of the
+ * direction of film point (cx, cy), under an environment rotation that is the pose's transpose, lands on (u, v) = (cx, 1 - cy).  Image
+ * row 0 is v = 0, which the environment map puts at -y (straight down in the pose's space; the last row looks straight up), the
+ * centre column looks down +x of the pose's space and the left and right edges meet at -x: the environment map's convention, row
+ * for row -- viewed as a picture with row 0 on top, a panorama shows the ground above the sky, exactly as an environment image does.  So a panorama rendered at a point and loaded as an environment with the
+ * identity R shows a second scene what the first one looked like from that point.  The view fields (the scene's and the pose's) are
+ * not read.  THE PROJECTION ADDS NO SAMPLER DIMENSION.
+ *
+ * Route.  A LATLONG scene takes the posed route whether a pose is on or not: its camera rays are written into a path queue
+ * (k_generate_pano, counted under PTX_KERNEL_GENERATE; the same 8 x 8-tile order, ids and holes) and bounced walk-first, through
+ * every driver the pose serves: ptx_render, ptx_render_multi (every scene passed must carry the same projection: PTX_ERR_ARG
+ * otherwise), ptx_render_raw_device, _passes_device, _pixels_device, _progressive, _adaptive, _denoised,
+ * ptx_render_features_device, ptx_trace_samples and ptx_camera_rays.  ptx_render_temporal (its reprojection is a pinhole's),
+ * ptx_ppm_render and ptx_debug_first_scatter return PTX_ERR_STATE while LATLONG is on ("... ptx_scene_set_camera_projection(scene,
+ * PTX_PROJECTION_PERSPECTIVE) first"), before anything is launched.
+ *
+ * Out of scope: fisheye and orthographic projections; a lens or temporal accumulation under LATLONG. */
+#define PTX_PROJECTION_PERSPECTIVE 0
+#define PTX_PROJECTION_LATLONG 1
+int32_t ptx_scene_set_camera_projection(ptx_scene* scene, int32_t projection);
+int32_t ptx_scene_camera_projection(const ptx_scene* scene); /* the kind, or a negative code */
+
 /* ---- temporal accumulation: the frame history reprojected across camera poses ----
  * The temporal half of the variance-guided filter: the per-pixel moments of the frames before are carried into the new frame by
  * reprojecting every pixel's first hit through the two cameras, and dropped where the surface changed.  Only entry points and two
@@ -1010,6 +1051,62 @@ int32_t ptx_render_temporal(ptx_scene* scene, const ptx_render_params* params, c
                             ptx_stats* stats);
 /* drops the history the handle keeps (its buffers stay); a host-only scene accepts it; PTX_ERR_STATE while a render runs */
 int32_t ptx_temporal_reset(ptx_scene* scene);
+
+/* ---- radiance along rays the caller owns ----
+ * Every other radiance entry point starts at a pixel of the scene's camera.  ptx_render_rays_device runs the same paths from rays
+ * the caller hands over -- light probes, irradiance at surface points, a sensor that is no pinhole, a batch a device program built --
+ * by the route a lens or a posed render takes: the rays are written into a path queue and bounced from there in the walk-first
+ * order.  Only entry points, one struct and one define are added: no existing struct, kernel or call changes, the ABI version
+ * stays 6, and a scene that never calls these launches exactly what it launched before.
+ *
+ * The path.  Ray i is Ray.create o_i d_i with (o_i, d_i) the i-th triples of `origins` and `directions`; with PTX_RAYS_NORMALIZE,
+ * Ray.create o_i (V3.normalize d_i).  Its radiance is path_tracer's (integrator.ml:16-69) from that ray at depth max_bounces, under
+ * the handle's shading state: the lighting mode, image textures, the environment, environment sampling and sphere-light sampling.
+ * The lens, the pose and the scene's camera are not read.  The caller hands UNIT directions, as every camera of the library does.
+ * Without the flag a direction is used as it is given and no length is checked: a non-unit one is walked correctly (hit distances
+ * are then in units of its length, and the closest hit is the same), but the shade step's formulas that take the incoming direction
+ * for a unit vector (the mirror and refraction directions, Schlick's cosine) get it as it is, as the reference would for a ray
+ * created that way -- the value is well defined and reproducible, and it is not the radiance along the normalised ray.
+ *
+ * The sampler.  The path of ray i reads the low-discrepancy sequence at offset offsets[i] (offsets == NULL: offset i = i), with the
+ * dimension the scene's own renders of that depth use: 2 + 2 max_bounces, and two more while the scene has a lens.  Bounce k reads
+ * dimensions 2 + 2 k and 3 + 2 k, exactly as for a camera ray.  Dimensions 0 and 1 (and the lens pair, the last two) are not read
+ * here: they belong to the caller, who may have drawn the ray from them -- ptx_lds_sample gives them.  So the rays ptx_camera_rays
+ * returns for samples (x, y, pass), with the offsets y W + x + pass N those samples have, give what ptx_trace_samples gives for
+ * them, bit for bit.  Offsets lie in [0, 2^31 - 2] (Low_discrepancy_sequence.get forms 1 + offset in 32 bits).
+ *
+ * The sums.  With m = rays_per_bin, bin b is rays [b m, (b + 1) m) and n must be a multiple of m.  For every ray of the bin, in ray
+ * order, with c its radiance: sum[b]_c = sum[b]_c + c and, if d_sq_inout is given, sq[b]_c = sq[b]_c + (c * c) -- a left fold onto
+ * what the buffers held (binary64, the product rounded before the add).  NOTHING IS ZEROED by the device call; m = 1 onto zeros is
+ * the per-ray radiance.  No floating-point atomics: the same inputs give the same bits on every run and for every batch size.
+ *
+ * Batching.  n may exceed any workspace: the call runs the rays in batches (16 M rays; PTX_RAYS_BATCH, a test hook, sets another
+ * size), each one generate launch (k_generate_rays: entry = id = the ray's index in the batch), the bounces, and one fold
+ * (k_accum_rays: a thread per bin).  A bin may straddle batches: the later batch's fold continues from the buffer.
+ *
+ * Checks.  Before a device is touched, in this order: PTX_ERR_ARG for NULL scene, params, origins, directions or sums, max_bounces
+ * outside [0, 126], rays_per_bin < 1, unknown bits in flags, n < 0, n >= 2^31 - 1, n no multiple of rays_per_bin; PTX_ERR_STATE for a
+ * host-only scene and for a call made while a render runs on the scene (from one of its callbacks).  n == 0 returns 0.  Then, on the
+ * device and before anything is queued (k_rays_check), every ray: a component of the origin or the direction that is not finite, a
+ * direction whose three components are all zero, or an offset outside [0, 2^31 - 2] is PTX_ERR_ARG, the message starts
+ * "ray <lowest refused index> " and the sums are left untouched.
+ *
+ * Stream and stats.  All pointers of ptx_render_rays_device are DEVICE pointers on the scene's device; the work is queued on
+ * `stream` (NULL: the null stream) and the call waits for it.  stats (nullable): samples = n; with count_work, segments and the
+ * work counters as ptx_trace_samples reports them.  ptx_render_rays is the same with HOST pointers: it zeroes the sums (n / m bins
+ * of 3 doubles; sq_out nullable), runs the device call and copies them back. */
+#define PTX_RAYS_NORMALIZE 1
+typedef struct ptx_rays_params { /* 16 bytes */
+  int32_t max_bounces;  /* as ptx_render_params */
+  int32_t rays_per_bin; /* m >= 1; n must be a multiple of m */
+  int32_t flags;        /* PTX_RAYS_NORMALIZE; unknown bits are PTX_ERR_ARG */
+  int32_t count_work;   /* as ptx_render_params */
+} ptx_rays_params;
+int32_t ptx_render_rays_device(ptx_scene* scene, const ptx_rays_params* params, int64_t n, const double* d_origins /* n x 3 */,
+                               const double* d_directions /* n x 3 */, const int32_t* d_offsets /* n, nullable: offset i = i */,
+                               double* d_sum_inout /* (n / m) x 3 */, double* d_sq_inout /* nullable */, void* stream, ptx_stats* stats);
+int32_t ptx_render_rays(ptx_scene* scene, const ptx_rays_params* params, int64_t n, const double* origins, const double* directions,
+                        const int32_t* offsets, double* sum_out, double* sq_out, ptx_stats* stats);
 
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.

@@ -48,6 +48,7 @@ EXPORTS = (
     "ptx_scene_set_camera_pose", "ptx_scene_camera_pose", "ptx_camera_rays",
     "ptx_temporal_defaults", "ptx_temporal_accumulate_device", "ptx_render_temporal", "ptx_temporal_reset",
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
+    "ptx_render_rays_device", "ptx_render_rays", "ptx_scene_set_camera_projection", "ptx_scene_camera_projection",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -178,6 +179,14 @@ def lib():
         L.ptx_render_temporal.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), tpp, C.POINTER(abi.DenoiseParams), C.c_int32,
                                           C.c_int32, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(abi.Stats)]
         L.ptx_temporal_reset.argtypes = [C.c_void_p]
+    if hasattr(L, "ptx_render_rays_device"):  # (likewise)
+        rpp = C.POINTER(abi.RaysParams)
+        L.ptx_render_rays_device.argtypes = [C.c_void_p, rpp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(abi.Stats)]
+        L.ptx_render_rays.argtypes = [C.c_void_p, rpp, C.c_int64, dp, dp, ip, dp, dp, C.POINTER(abi.Stats)]
+    if hasattr(L, "ptx_scene_set_camera_projection"):  # (likewise)
+        L.ptx_scene_set_camera_projection.argtypes = [C.c_void_p, C.c_int32]
+        L.ptx_scene_camera_projection.argtypes = [C.c_void_p]
     _LIB = L
     return L
 
@@ -313,6 +322,20 @@ class Scene:
         if rc == 0:
             return None
         return o, r.reshape(3, 3), (v.lower_left_x, v.lower_left_y, v.view_x, v.view_y)
+
+    def set_camera_projection(self, projection):
+        """ptx_scene_set_camera_projection: "perspective" (the pinhole, the state of every scene that never called this) or
+        "latlong" -- a 360-degree panorama in the environment map's (u, v) convention, taken from the pose's origin (the scene's
+        own while the pose is off) -- or the abi.PTX_PROJECTION_* value.  Sticky.  Refused while a lens is on."""
+        _check(lib().ptx_scene_set_camera_projection(self._h, abi.projection_kind(projection)))
+
+    @property
+    def camera_projection(self):
+        """ptx_scene_camera_projection: "perspective" or "latlong" """
+        rc = lib().ptx_scene_camera_projection(self._h)
+        if rc < 0:
+            _check(rc)
+        return abi.PTX_PROJECTION_NAMES[rc]
 
     def camera_rays(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes):
         """ptx_camera_rays (diagnostic): (origins (n, 3), directions (n, 3)) of the camera rays this scene's renders launch for the
@@ -728,6 +751,47 @@ class Scene:
         st = abi.Stats()
         _check(lib().ptx_trace_samples(self._h, C.byref(p), len(xs), _ip(xs), _ip(ys), _ip(passes), _dp(out), C.byref(st)))
         return out, stats_dict(st)
+
+    def render_rays(self, origins, directions, offsets=None, max_bounces=8, rays_per_bin=1, normalize=False, want_sq=False,
+                    count_work=False):
+        """ptx_render_rays: the radiance along the caller's rays -- origins and directions (n, 3), unit directions unless
+        `normalize` -- under this scene's shading state, ray i's path reading the sampler at offsets[i] (None: i).  Returns
+        (sums (n / rays_per_bin, 3), squares or None, stats): bin b is the left fold of rays [b m, (b + 1) m) in ray order onto
+        zeros, so rays_per_bin = 1 gives the per-ray radiance."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"origins {o.shape} and directions {d.shape} differ in shape")
+        n = o.shape[0]
+        off = None
+        if offsets is not None:
+            off64 = np.asarray(offsets, dtype=np.int64).reshape(-1)
+            if off64.shape[0] != n:
+                raise ValueError(f"{off64.shape[0]} offsets for {n} rays")
+            if n and (off64.min() < -2**31 or off64.max() >= 2**31):
+                raise ValueError("a sampler offset does not fit 32 bits")
+            off = np.ascontiguousarray(off64, dtype=np.int32)
+        p = abi.rays_params(max_bounces, rays_per_bin, normalize, count_work)
+        bins = n // p.rays_per_bin if p.rays_per_bin >= 1 else 0
+        out = np.zeros((bins, 3))
+        sq = np.zeros((bins, 3)) if want_sq else None
+        st = abi.Stats()
+        _check(lib().ptx_render_rays(self._h, C.byref(p), n, _dp(o), _dp(d), None if off is None else _ip(off), _dp(out),
+                                     None if sq is None else _dp(sq), C.byref(st)))
+        return out, sq, stats_dict(st)
+
+    def render_rays_device(self, n, d_origins_ptr, d_directions_ptr, d_sum_ptr, d_offsets_ptr=None, d_sq_ptr=None, max_bounces=8,
+                           rays_per_bin=1, normalize=False, count_work=False, stream=None):
+        """ptx_render_rays_device: the same on DEVICE pointers of this scene's device (origins and directions n x 3 doubles,
+        offsets n int32 or None), ADDED to the (n / rays_per_bin) x 3 sums at d_sum_ptr (never zeroed), the squares to d_sq_ptr if
+        given; queued on `stream` and waited for."""
+        p = abi.rays_params(max_bounces, rays_per_bin, normalize, count_work)
+        st = abi.Stats()
+        _check(lib().ptx_render_rays_device(self._h, C.byref(p), int(n), C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
+                                            C.c_void_p(d_offsets_ptr) if d_offsets_ptr else None, C.c_void_p(d_sum_ptr),
+                                            C.c_void_p(d_sq_ptr) if d_sq_ptr else None, C.c_void_p(stream) if stream else None,
+                                            C.byref(st)))
+        return stats_dict(st)
 
     def intersect_rays(self, origins, directions):
         o = np.ascontiguousarray(origins, dtype=np.float64)

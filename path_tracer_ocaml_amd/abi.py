@@ -128,6 +128,31 @@ def temporal_camera(origin, rotation, view):
     return TemporalCamera((C.c_double * 3)(*o), (C.c_double * 9)(*r), Camera(v.lower_left_x, v.lower_left_y, v.view_x, v.view_y))
 
 
+PTX_PROJECTION_PERSPECTIVE, PTX_PROJECTION_LATLONG = 0, 1
+PTX_PROJECTION_NAMES = ("perspective", "latlong")
+
+
+def projection_kind(projection):
+    """A PTX_PROJECTION_* value from the value itself or from its name in PTX_PROJECTION_NAMES."""
+    if isinstance(projection, str):
+        if projection not in PTX_PROJECTION_NAMES:
+            raise ValueError(f"projection must be one of {', '.join(PTX_PROJECTION_NAMES)} (got {projection!r})")
+        return PTX_PROJECTION_NAMES.index(projection)
+    return int(projection)
+
+
+PTX_RAYS_NORMALIZE = 1
+
+
+class RaysParams(C.Structure):  # ptx_rays_params, 16 bytes
+    _fields_ = [("max_bounces", C.c_int32), ("rays_per_bin", C.c_int32), ("flags", C.c_int32), ("count_work", C.c_int32)]
+
+
+def rays_params(max_bounces=8, rays_per_bin=1, normalize=False, count_work=False):
+    """An abi.RaysParams for ptx_render_rays / ptx_render_rays_device."""
+    return RaysParams(int(max_bounces), int(rays_per_bin), PTX_RAYS_NORMALIZE if normalize else 0, int(bool(count_work)))
+
+
 PTX_FILM_MAX_ORDER, PTX_FILM_MAX_RADIUS = 16, 7
 PTX_FILM_RENORMALISE = 1
 

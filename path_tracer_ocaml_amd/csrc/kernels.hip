@@ -4346,6 +4346,8 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "denoise.inc"
 #include "lens.inc"
 #include "camera_pose.inc"
+#include "panorama.inc"
 #include "temporal.inc"
+#include "rays.inc"
 #include "ptx_api.inc"
 #endif

@@ -264,6 +264,7 @@ struct Schedule {
   bool img = false;            /* an image texture or an environment: the IMG instantiations */
   bool lens = false;           /* a thin lens (ptx_scene_set_lens): camera rays are generated into a queue, never a PRIMARY launch; the walk-first order */
   bool pose = false;           /* a camera pose (ptx_scene_set_camera_pose): like a lens, camera rays are generated into a queue (k_generate_pose) and bounced walk-first */
+  bool latlong = false;        /* the lat-long projection (ptx_scene_set_camera_projection): the posed route (pose is set with it), its generators k_generate_pano* */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
@@ -317,6 +318,8 @@ struct ptx_scene {
   bool pose_on = false, pose_has_view = false;
   double pose_origin[3] = {0.0, 0.0, 0.0}, pose_rotation[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
   ptx_camera pose_view = {0.0, 0.0, 0.0, 0.0};
+  /* ptx_scene_set_camera_projection: PTX_PROJECTION_PERSPECTIVE = the state of a scene that never called it */
+  int32_t projection = PTX_PROJECTION_PERSPECTIVE;
   ptx_camera own_view = {0.0, 0.0, 0.0, 0.0}; /* the descriptor's camera (a host-only scene keeps no PtSceneDev scalars) */
   std::vector<double> light_table;
   DevBuf<double> d_lights;
@@ -396,6 +399,7 @@ struct ptx_scene {
   DevBuf<uint8_t> sel_keep;
   DevBuf<uint32_t> sel_blocks, sel_offsets;
   hipEvent_t ev_select = nullptr;
+  DevBuf<uint32_t> rays_lowest; /* ptx_render_rays_device: k_rays_check's lowest refused index */
   /* ptx_render_features_device: the hit records of one batch of camera rays (slot; t on scenes without triangles), k_trace's
    * hand-out words and parked walks -- its own, because a queued slice of a render may be running on the workspace sets meanwhile;
    * ptx_render_denoised: the feature sums, their means for the host, the filter's guide and {c, V} pair, the denoised sums */
@@ -597,7 +601,10 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
   /* A posed camera (ptx_scene_set_camera_pose), the identity pose included: its rays start at the pose's origin, so they take the
    * lens's route -- a queue (k_generate_pose) and the walk-first order; no per-octant LDS image, no tile lists (both are made for
    * rays from the origin of the scene's own space), no solo run. */
-  c.pose = s->pose_on;
+  /* The lat-long projection: rays in every direction from the pose's origin (origin 0 and the identity while the pose is off) -- the
+   * posed route with generators of its own (panorama.inc), and everything a posed scene gives up. */
+  c.latlong = s->projection == PTX_PROJECTION_LATLONG;
+  c.pose = s->pose_on || c.latlong;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
   c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
@@ -1192,7 +1199,10 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     q0.count = w.counts;
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-      if (s->sched.pose)
+      if (s->sched.latlong)
+        hipLaunchKernelGGL(k_generate_pixels_pano, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
+                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_pose(s), (const double*)s->alpha.p, q0);
+      else if (s->sched.pose)
         hipLaunchKernelGGL(s->sched.lens ? k_generate_pixels_pose<true> : k_generate_pixels_pose<false>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
                            p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
       else if (s->sched.lens)
@@ -1218,7 +1228,9 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
       q0.count = w.counts;
       {
         LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-        if (s->sched.pose)
+        if (s->sched.latlong)
+          hipLaunchKernelGGL(k_generate_pano<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_pose(s), (const double*)s->alpha.p, q0);
+        else if (s->sched.pose)
           hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, true> : k_generate_pose<false, true>), dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
         else
           hipLaunchKernelGGL(k_generate_lens<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
@@ -2123,6 +2135,8 @@ int32_t ptx_scene_set_lens(ptx_scene* s, double radius, double focus_distance) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");
   if (!std::isfinite(radius) || !(radius >= 0.0)) return fail(PTX_ERR_ARG, "lens: radius must be finite and >= 0 (got %g); 0 switches the lens off", radius);
   if (!std::isfinite(focus_distance) || !(focus_distance > 0.0)) return fail(PTX_ERR_ARG, "lens: focus_distance must be finite and > 0 (got %g)", focus_distance);
+  if (radius > 0.0 && s->projection == PTX_PROJECTION_LATLONG)
+    return fail(PTX_ERR_STATE, "lens: the lat-long projection has no lens: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
   if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the lens cannot change while a render runs on the scene");
   s->lens_radius = radius;
   s->lens_focus = focus_distance;
@@ -2139,6 +2153,28 @@ int32_t ptx_scene_lens(const ptx_scene* s, double* radius_out, double* focus_dis
   if (radius_out) *radius_out = s->lens_radius;
   if (focus_distance_out) *focus_distance_out = s->lens_focus;
   return 0;
+}
+
+/* ---- camera projection ---- */
+int32_t ptx_scene_set_camera_projection(ptx_scene* s, int32_t projection) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (projection != PTX_PROJECTION_PERSPECTIVE && projection != PTX_PROJECTION_LATLONG)
+    return fail(PTX_ERR_ARG, "camera projection: %d is neither PTX_PROJECTION_PERSPECTIVE (0) nor PTX_PROJECTION_LATLONG (1)", projection);
+  if (projection == PTX_PROJECTION_LATLONG && s->lens_radius > 0.0)
+    return fail(PTX_ERR_STATE, "camera projection: the lat-long projection has no lens: switch the lens off with ptx_scene_set_lens(scene, 0, 1) first");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the camera projection cannot change while a render runs on the scene");
+  s->projection = projection;
+  if (s->device >= 0) reschedule(s, s->sets_in_flight); /* (Schedule::latlong and ::pose, and what follows from them) */
+  for (ptx_scene* r : s->replicas) {
+    const int rr = ptx_scene_set_camera_projection(r, projection);
+    if (rr) return rr;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_camera_projection(const ptx_scene* s) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  return s->projection;
 }
 
 /* ---- camera pose ---- */
@@ -2673,6 +2709,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->lens_focus = src->lens_focus;
   s->own_view = src->own_view;
   copy_camera_pose(s, src);
+  s->projection = src->projection;
   if (scene_upload(s) != 0) {
     ptx_scene_destroy(s);
     return nullptr;
@@ -2815,6 +2852,8 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
       return fail(PTX_ERR_ARG, "scene %d is not a replica of scene 0", k);
     if (scenes[k]->lens_radius != scenes[0]->lens_radius || (scenes[0]->lens_radius > 0.0 && scenes[k]->lens_focus != scenes[0]->lens_focus))
       return fail(PTX_ERR_ARG, "scene %d does not carry the lens of scene 0 (ptx_scene_set_lens): the bands would not be one image", k);
+    if (scenes[k]->projection != scenes[0]->projection)
+      return fail(PTX_ERR_ARG, "scene %d does not carry the camera projection of scene 0 (ptx_scene_set_camera_projection): the bands would not be one image", k);
     if (!same_camera_pose(scenes[k], scenes[0]))
       return fail(PTX_ERR_ARG, "scene %d does not carry the camera pose of scene 0 (ptx_scene_set_camera_pose): the bands would not be one image", k);
   }
@@ -3477,7 +3516,9 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
       /* the same entries as rays in a queue of their own (48 bytes per entry more), walked as ptx_intersect_rays' are */
       const PtLens ln = scene_lens(s, p->max_bounces);
       PtQueue q{s->feat_ray.p, nullptr, s->feat_work.p + 8};
-      if (s->sched.pose)
+      if (s->sched.latlong)
+        hipLaunchKernelGGL(k_generate_pano<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, scene_pose(s), alpha, q);
+      else if (s->sched.pose)
         hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, false> : k_generate_pose<false, false>), dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, scene_pose(s), ln, alpha, q);
       else
         hipLaunchKernelGGL(k_generate_lens<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, ln, alpha, q);
@@ -3808,6 +3849,9 @@ int32_t ptx_temporal_reset(ptx_scene* s) {
 int32_t ptx_render_temporal(ptx_scene* s, const ptx_render_params* p_in, const ptx_temporal_params* tp, const ptx_denoise_params* dp,
                             int32_t pass_first, int32_t pass_count, double* rgb_out, double* err_out, double* motion_out,
                             int64_t* history_pixels_out, ptx_stats* stats) {
+  /* (before any device is touched: a host-only scene gets this answer too) */
+  if (s && s->projection != PTX_PROJECTION_PERSPECTIVE)
+    return fail(PTX_ERR_STATE, "temporal rendering needs a pinhole: its reprojection is a perspective camera's (ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first)");
   int rc = check_render_args(s, p_in, (tp && rgb_out) ? nullptr : "NULL argument");
   if (rc) return rc;
   rc = check_one_gpu(p_in, "temporal rendering");
@@ -3898,7 +3942,10 @@ namespace {
 /* the camera rays of explicit (x, y, pass) triples appended to q0, by the generator the scene's state selects */
 void launch_generate_list(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* dx, const int32_t* dy, const int32_t* dp, const PtQueue& q0) {
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (s->sched.pose)
+  if (s->sched.latlong)
+    hipLaunchKernelGGL(k_generate_list_pano, grid, block, 0, nullptr, s->dev, p->width, p->height, p->samples_per_pixel, (long long)n, dx, dy, dp,
+                       scene_pose(s), s->alpha.p, q0);
+  else if (s->sched.pose)
     hipLaunchKernelGGL(s->sched.lens ? k_generate_list_pose<true> : k_generate_list_pose<false>, grid, block, 0, nullptr, s->dev, p->width, p->height,
                        p->samples_per_pixel, (long long)n, dx, dy, dp, scene_pose(s), scene_lens(s, p->max_bounces), s->alpha.p, q0);
   else if (s->sched.lens)
@@ -4004,6 +4051,138 @@ int32_t ptx_camera_rays(ptx_scene* s, const ptx_render_params* p, int64_t n, con
     origins_out[3 * i] = r.ox; origins_out[3 * i + 1] = r.oy; origins_out[3 * i + 2] = r.oz;
     directions_out[3 * i] = r.dx; directions_out[3 * i + 1] = r.dy; directions_out[3 * i + 2] = r.dz;
   }
+  return 0;
+}
+
+namespace {
+/* rays per batch of ptx_render_rays_device: PTX_RAYS_BATCH (a test hook: any batch size gives the same sums), else 16 M, and never
+ * more than a path queue can number */
+size_t rays_batch(const ptx_scene* s, int64_t n) {
+  long long batch = 16ll << 20;
+  if (const char* e = getenv("PTX_RAYS_BATCH")) batch = std::max(1ll, atoll(e));
+  const size_t most = kPoolMaxEntries - shade_pool_slack(s) - 1;
+  return std::min<size_t>(std::min<size_t>((size_t)batch, most), (size_t)n);
+}
+
+/* the caller's DEVICE arrays, checked on the device before anything else is queued (waits for st); the message names the lowest
+ * refused ray and what is wrong with it (that one ray is read back) */
+int check_rays_device(ptx_scene* s, int64_t n, const double* d_o, const double* d_d, const int32_t* d_off, hipStream_t st) {
+  HIP_TRY(s->rays_lowest.ensure(1));
+  HIP_TRY(hipMemsetAsync(s->rays_lowest.p, 0xff, sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_rays_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, d_o, d_d, d_off, s->rays_lowest.p);
+  HIP_TRY(hipGetLastError());
+  uint32_t lowest = 0xffffffffu;
+  HIP_TRY(hipMemcpyAsync(&lowest, s->rays_lowest.p, sizeof lowest, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (lowest == 0xffffffffu) return 0;
+  if ((int64_t)lowest >= n) return fail(PTX_ERR_HIP, "BUG: the ray check names ray %u of %lld", lowest, (long long)n);
+  double o[3], d[3];
+  int32_t off = 0;
+  HIP_TRY(hipMemcpy(o, d_o + 3 * (size_t)lowest, sizeof o, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(d, d_d + 3 * (size_t)lowest, sizeof d, hipMemcpyDeviceToHost));
+  if (d_off) HIP_TRY(hipMemcpy(&off, d_off + lowest, sizeof off, hipMemcpyDeviceToHost));
+  const bool finite = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]) && std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]);
+  if (!finite) return fail(PTX_ERR_ARG, "ray %u has a component that is not finite (origin %g %g %g, direction %g %g %g)", lowest, o[0], o[1], o[2], d[0], d[1], d[2]);
+  if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) return fail(PTX_ERR_ARG, "ray %u has the direction (0, 0, 0)", lowest);
+  return fail(PTX_ERR_ARG, "ray %u has the sampler offset %d, outside [0, 2^31 - 2]", lowest, off);
+}
+
+/* what ptx_render_rays_device and ptx_render_rays check before a device is touched: the caller's arguments first (a host-only scene
+ * gets the same PTX_ERR_ARG for them), then the scene's state */
+int check_rays_args(const ptx_scene* s, const ptx_rays_params* rp, int64_t n, const void* origins, const void* directions, const void* sum) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (!rp) return fail(PTX_ERR_ARG, "NULL params");
+  if (rp->max_bounces < 0 || rp->max_bounces > 126) return fail(PTX_ERR_ARG, "max_bounces must be in [0, 126] (got %d)", rp->max_bounces);
+  if (rp->rays_per_bin < 1) return fail(PTX_ERR_ARG, "rays_per_bin must be >= 1 (got %d)", rp->rays_per_bin);
+  if (rp->flags & ~PTX_RAYS_NORMALIZE) return fail(PTX_ERR_ARG, "unknown bits in flags (%d): only PTX_RAYS_NORMALIZE is defined", rp->flags);
+  if (!origins || !directions || !sum) return fail(PTX_ERR_ARG, "NULL argument");
+  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad ray count %lld: n must be in [0, 2^31 - 1)", (long long)n);
+  if (n % rp->rays_per_bin != 0) return fail(PTX_ERR_ARG, "n = %lld is not a multiple of rays_per_bin = %d", (long long)n, rp->rays_per_bin);
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "ptx_render_rays cannot start while a render runs on the scene (called from one of its callbacks?)");
+  return 0;
+}
+}  // namespace
+
+int32_t ptx_render_rays_device(ptx_scene* s, const ptx_rays_params* rp, int64_t n, const double* d_origins, const double* d_directions,
+                               const int32_t* d_offsets, double* d_sum_inout, double* d_sq_inout, void* stream, ptx_stats* stats) {
+  int rc = check_rays_args(s, rp, n, d_origins, d_directions, d_sum_inout);
+  if (rc) return rc;
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    fill_tree_stats(s, stats);
+  }
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(s->device));
+  const double t0 = wall_ms();
+  hipStream_t st = (hipStream_t)stream;
+  rc = check_rays_device(s, n, d_origins, d_directions, d_offsets, st);
+  if (rc) return rc;
+  RenderBusy busy(s);
+  reschedule(s, 1);
+  const size_t batch = rays_batch(s, n);
+  Workspace w;
+  rc = ensure_workspace(s, batch, rp->max_bounces, &w);
+  if (rc) return rc;
+  const bool count = rp->count_work != 0, normalize = (rp->flags & PTX_RAYS_NORMALIZE) != 0;
+  const long long m = rp->rays_per_bin;
+  if (count) HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(PtCounters), st));
+  DrainOnExit drain; /* (an error half-way: nothing this call queued still reads the caller's arrays when it returns) */
+  for (int64_t first = 0; first < n; first += (int64_t)batch) {
+    const uint32_t nb = (uint32_t)std::min<int64_t>((int64_t)batch, n - first);
+    HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * kCountsWords, st));
+    /* a path that ends without a contribution leaves its entry as it is: zero (and max_bounces = 0 is zero for every ray) */
+    HIP_TRY(hipMemsetAsync(w.contrib_all, 0, sizeof(double) * 4 * (size_t)nb, st));
+    if (rp->max_bounces > 0) {
+      PtQueue q0 = w.q[0];
+      q0.count = w.counts;
+      hipLaunchKernelGGL(normalize ? k_generate_rays<true> : k_generate_rays<false>, dim3((nb + 255u) / 256u), dim3(256), 0, st, s->dev, (long long)first, nb,
+                         d_origins, d_directions, d_offsets, q0);
+      run_bounces(s, st, w, (size_t)nb, rp->max_bounces, count, false, PrimaryLaunch());
+    }
+    const long long bins = (first + nb - 1) / m - first / m + 1;
+    hipLaunchKernelGGL(d_sq_inout ? k_accum_rays<true> : k_accum_rays<false>, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, st, w.contrib, (long long)first,
+                       (long long)nb, m, d_sum_inout, d_sq_inout);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  drain.armed = false;
+  if (stats) {
+    stats->samples = n;
+    stats->render_ms = wall_ms() - t0;
+    if (count) {
+      rc = collect_counters(s, stats);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
+int32_t ptx_render_rays(ptx_scene* s, const ptx_rays_params* rp, int64_t n, const double* origins, const double* directions, const int32_t* offsets,
+                        double* sum_out, double* sq_out, ptx_stats* stats) {
+  int rc = check_rays_args(s, rp, n, origins, directions, sum_out);
+  if (rc) return rc;
+  if (n == 0) return ptx_render_rays_device(s, rp, 0, origins, directions, offsets, sum_out, sq_out, nullptr, stats);
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t n3 = (size_t)n * 3, bins3 = (size_t)(n / rp->rays_per_bin) * 3;
+  LocalBuf<double> d_o, d_d, d_sum, d_sq;
+  LocalBuf<int32_t> d_off;
+  HIP_TRY(d_o.ensure(n3)); HIP_TRY(d_d.ensure(n3)); HIP_TRY(d_sum.ensure(bins3));
+  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * n3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * n3, hipMemcpyHostToDevice));
+  if (offsets) {
+    HIP_TRY(d_off.ensure((size_t)n));
+    HIP_TRY(hipMemcpy(d_off.p, offsets, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemset(d_sum.p, 0, sizeof(double) * bins3));
+  if (sq_out) {
+    HIP_TRY(d_sq.ensure(bins3));
+    HIP_TRY(hipMemset(d_sq.p, 0, sizeof(double) * bins3));
+  }
+  rc = ptx_render_rays_device(s, rp, n, d_o.p, d_d.p, offsets ? d_off.p : nullptr, d_sum.p, sq_out ? d_sq.p : nullptr, nullptr, stats);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(sum_out, d_sum.p, sizeof(double) * bins3, hipMemcpyDeviceToHost));
+  if (sq_out) HIP_TRY(hipMemcpy(sq_out, d_sq.p, sizeof(double) * bins3, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -4172,6 +4351,8 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
                                 const int32_t* passes, double* ray_out, double* attn_out, int32_t* alive_out) {
   if (!s || !xs || !ys || !passes || !ray_out || !attn_out || !alive_out) return fail(PTX_ERR_ARG, "NULL argument");
   /* (before any device is touched: a host-only scene gets this answer too) */
+  if (s->projection != PTX_PROJECTION_PERSPECTIVE)
+    return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own pinhole: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
   if (s->pose_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
   int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
@@ -4228,6 +4409,8 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
                        ptx_ppm_stats* stats, ptx_ppm_iteration_fn cb, void* user) {
   if (!s || !p || !lights || !img_sum_out) return fail(PTX_ERR_ARG, "NULL argument");
   /* (before any device is touched: a host-only scene gets this answer too) */
+  if (s->projection != PTX_PROJECTION_PERSPECTIVE)
+    return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own pinhole: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
   if (s->pose_on) return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
   if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
   if (p->width <= 0 || p->height <= 0 || p->iterations <= 0 || p->max_bounces <= 0 || p->max_bounces > 60 || p->photon_count <= 0 || n_lights <= 0)

@@ -61,6 +61,15 @@ def lib():
         L.pth_lights_cornell.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.Light)]
         L.pth_lights_ganesha.argtypes = [C.c_void_p, C.POINTER(abi.Light)]
         L.pth_ppm_gamma.argtypes = [abi.c_double_p, C.c_int64, C.c_int32, abi.c_double_p]
+        L.pth_pfm_write.argtypes = [C.c_char_p, C.c_int32, C.c_int32, abi.c_double_p]
+        L.pth_pfm_load.restype = C.c_void_p
+        L.pth_pfm_load.argtypes = [C.c_char_p]
+        L.pth_image_free.argtypes = [C.c_void_p]
+        L.pth_image_width.argtypes = [C.c_void_p]
+        L.pth_image_height.argtypes = [C.c_void_p]
+        L.pth_image_rgb.restype = abi.c_double_p
+        L.pth_image_rgb.argtypes = [C.c_void_p]
+        L.pth_image_error.restype = C.c_char_p
         _LIB = L
     return _LIB
 
@@ -255,6 +264,28 @@ def ganesha_ply(path, width, height):
     if not h:
         raise PlyError(lib().pth_last_error().decode())
     return HostScene(h)
+
+
+def load_pfm(path):
+    """pth_pfm_load: the (H, W, 3) binary64 image of a PFM file, rows as they come (row 0 = v = 0)"""
+    L = lib()
+    h = L.pth_pfm_load(path.encode())
+    if not h:
+        raise IOError(L.pth_image_error().decode())
+    try:
+        w, hh = L.pth_image_width(h), L.pth_image_height(h)
+        return np.ctypeslib.as_array(L.pth_image_rgb(h), shape=(hh, w, 3)).copy()
+    finally:
+        L.pth_image_free(h)
+
+
+def write_pfm(path, rgb):
+    """pth_pfm_write: the (H, W, 3) image as a little-endian PFM, every value rounded to binary32, rows in the order given (row 0 =
+    v = 0: what load_pfm and --envmap read back)"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    h, w, _ = rgb.shape
+    if lib().pth_pfm_write(path.encode(), w, h, rgb.ctypes.data_as(abi.c_double_p)) != 0:
+        raise IOError(lib().pth_image_error().decode())
 
 
 def write_ganesha_like_ply(path, n_target=150000, seed=7):

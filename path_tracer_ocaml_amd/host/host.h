@@ -80,6 +80,10 @@ typedef struct pth_image pth_image;
 const char* pth_image_error(void);
 pth_image* pth_pfm_load(const char* path);
 pth_image* pth_pfm_parse(const unsigned char* bytes, size_t n);
+/* the mirror of pth_pfm_load: a little-endian "PF" file of width * height * 3 values rounded to binary32, rows in the order given
+ * (row 0 = v = 0), so a file written and loaded back is the binary32 rounding of `rgb`, row for row.  0, or -1 + pth_image_error()
+ * (NULL argument, a size outside [1, PTX_IMAGE_MAX_SIZE], a value that is not finite in binary32, a file that cannot be written) */
+int32_t pth_pfm_write(const char* path, int32_t width, int32_t height, const double* rgb);
 void pth_image_free(pth_image* img);
 int32_t pth_image_width(const pth_image* img);
 int32_t pth_image_height(const pth_image* img);

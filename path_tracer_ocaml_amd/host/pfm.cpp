@@ -1,4 +1,5 @@
-// pfm.cpp -- a reader for Portable Float Map images, the one image format the hosts decode (--envmap, --ground-texture).
+// pfm.cpp -- a reader for Portable Float Map images, the one image format the hosts decode (--envmap, --ground-texture), and the
+// writer that mirrors it (--hdr-out).
 //
 //   "PF" (three channels) or "Pf" (one, read as grey: r = g = b), white space, WIDTH, white space, HEIGHT, white space, SCALE, exactly
 //   one white-space byte, then WIDTH * HEIGHT * channels binary32 values, rows BOTTOM TO TOP.  SCALE < 0: little-endian, > 0:
@@ -119,6 +120,43 @@ pth_image* pth_pfm_load(const char* path) {
   }
   std::fclose(f);
   return pth_pfm_parse(bytes.data(), bytes.size());
+}
+
+// The mirror of pth_pfm_load: "PF", WIDTH HEIGHT, the scale -1.0 (little-endian), one newline each, then width * height * 3 binary32
+// values -- each the binary64 value rounded to nearest -- rows in the order they are given (the reader keeps them as they come, so
+// a file written and read back is the binary32 rounding of what was written, row for row).  A value that is not finite, or that
+// rounds to a binary32 that is not, is refused: the reader would refuse the file.  0 on success, -1 + pth_image_error().
+int32_t pth_pfm_write(const char* path, int32_t width, int32_t height, const double* rgb) {
+  if (!path || !rgb) return fail("pth_pfm_write: NULL argument"), -1;
+  if (width < 1 || width > PTX_IMAGE_MAX_SIZE || height < 1 || height > PTX_IMAGE_MAX_SIZE)
+    return fail("size " + std::to_string(width) + " x " + std::to_string(height) + ": width and height must be in [1, " + std::to_string(PTX_IMAGE_MAX_SIZE) + "]"), -1;
+  try {
+    const size_t count = (size_t)width * (size_t)height * 3;
+    const std::string header = "PF\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    std::vector<unsigned char> bytes(header.size() + count * 4);
+    std::memcpy(bytes.data(), header.data(), header.size());
+    unsigned char* px = bytes.data() + header.size();
+    for (size_t i = 0; i < count; ++i) {
+      const float f = (float)rgb[i];
+      if (!std::isfinite(f)) {
+        const size_t pixel = i / 3;
+        return fail("pixel (" + std::to_string(pixel % (size_t)width) + ", " + std::to_string(pixel / (size_t)width) + ") is not finite in binary32"), -1;
+      }
+      uint32_t u;
+      std::memcpy(&u, &f, 4);
+      px[4 * i] = (unsigned char)(u & 0xffu);
+      px[4 * i + 1] = (unsigned char)((u >> 8) & 0xffu);
+      px[4 * i + 2] = (unsigned char)((u >> 16) & 0xffu);
+      px[4 * i + 3] = (unsigned char)((u >> 24) & 0xffu);
+    }
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(std::string("cannot write ") + path), -1;
+    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (std::fclose(f) != 0 || !ok) return fail(std::string("writing ") + path + " failed"), -1;
+    return 0;
+  } catch (const std::exception& e) {
+    return fail(std::string("write failed: ") + e.what()), -1;
+  }
 }
 
 void pth_image_free(pth_image* img) { delete img; }

@@ -34,6 +34,11 @@
 // --sphere-lamp=X,Y,Z,R,EMIT (with --scene=shirley): a white Lambertian lamp sphere at that world point (pth_scene_shirley_lamp);
 // --light-spheres (with --lighting=sampled): the emissive spheres are cone-sampled (ptx_scene_set_sphere_light_sampling), and sampled
 // lighting then needs no emissive triangle.
+// --panorama: a 360-degree lat-long panorama in the environment map's (u, v) convention (ptx_scene_set_camera_projection), for every
+// --scene=; taken from the scene's own eye, or from --camera-eye / --turntable's; refused with --lens-radius and --temporal.
+// --hdr-out=FILE.pfm (any render): also writes the square of every value of the final image -- the filmed linear radiance -- as a PFM
+// (pth_pfm_write), which --envmap reads back: a panorama written here lights another scene.  With --turntable, frame k goes to the name
+// with -kkk in front of its extension.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -86,6 +91,8 @@ struct Args {
   double turntable_arc = 360.0;          // --turntable-arc=DEG
   bool have_arc = false;
   double temporal = -1.0;                // --temporal[=CAP]: max_history_passes (< 0: no temporal accumulation)
+  bool panorama = false;                 // --panorama
+  std::string hdr_out;                   // --hdr-out=FILE.pfm
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -101,7 +108,7 @@ struct Args {
                "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n"
                "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n"
                "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n"
-               "          [--turntable-arc=DEG] [--temporal[=CAP]]\n",
+               "          [--turntable-arc=DEG] [--temporal[=CAP]] [--panorama] [--hdr-out=FILE.pfm]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -132,6 +139,11 @@ Args parse(int argc, char** argv) {
     std::string v, bad;
     if (!std::strcmp(argv[i], "--envmap-sample")) a.envmap_sample = true;
     else if (!std::strcmp(argv[i], "--light-spheres")) a.light_spheres = true;
+    else if (!std::strcmp(argv[i], "--panorama")) a.panorama = true;
+    else if (take_value(argc, argv, i, "hdr-out", nullptr, &v)) {
+      if (v.empty()) usage(argv[0], "invalid value for --hdr-out, expected a file name");
+      a.hdr_out = v;
+    }
     else if (take_value(argc, argv, i, "sphere-lamp", nullptr, &v)) {
       char tail = 0;
       double* l = a.sphere_lamp;
@@ -286,6 +298,8 @@ Args parse(int argc, char** argv) {
     if (a.lens_radius > 0.0) usage(argv[0], "--temporal needs a pinhole: it cannot be combined with --lens-radius");
     if (!a.aov.empty()) usage(argv[0], "--aov cannot be combined with --temporal");
   }
+  if (a.panorama && a.lens_radius > 0.0) usage(argv[0], "--panorama has no lens: it cannot be combined with --lens-radius");
+  if (a.panorama && a.temporal >= 0.0) usage(argv[0], "--temporal needs a pinhole: it cannot be combined with --panorama");
   if (a.envmap_sample && a.images.envmap.empty()) usage(argv[0], "--envmap-sample requires --envmap");
   if (a.envmap_sample && a.lighting != PTX_LIGHTING_SAMPLED) usage(argv[0], "--envmap-sample requires --lighting=sampled");
   if (a.have_sphere_lamp && a.scene != "shirley") usage(argv[0], "--sphere-lamp requires --scene=shirley");
@@ -451,6 +465,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ptx_scene_set_lens: %s\n", ptx_last_error());
     return 1;
   }
+  if (a.panorama && ptx_scene_set_camera_projection(scene, PTX_PROJECTION_LATLONG) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_camera_projection: %s\n", ptx_last_error());
+    return 1;
+  }
   if (a.have_filter && ptx_scene_set_film(scene, &a.film) != 0) {
     std::fprintf(stderr, "ptx_scene_set_film: %s\n", ptx_last_error());
     return 1;
@@ -571,6 +589,15 @@ int main(int argc, char** argv) {
   if (upd.write_failed || pth_write_png(output.c_str(), a.width, a.height, rgb.data()) != 0) {
     std::fprintf(stderr, "cannot write %s\n", output.c_str());
     return 1;
+  }
+  if (!a.hdr_out.empty()) { // the image is sqrt(filmed radiance): its square, rounded to binary32 by the writer
+    std::vector<double> linear(rgb.size());
+    for (size_t k = 0; k < rgb.size(); ++k) linear[k] = rgb[k] * rgb[k];
+    const std::string hdr = a.turntable > 0 ? frame_name(a.hdr_out, frame) : a.hdr_out;
+    if (pth_pfm_write(hdr.c_str(), a.width, a.height, linear.data()) != 0) {
+      std::fprintf(stderr, "cannot write %s: %s\n", hdr.c_str(), pth_image_error());
+      return 1;
+    }
   }
   if (a.temporal >= 0.0) std::printf("frame %d -> %s, history = %lld pixels\n", frame, output.c_str(), history_pixels);
   else if (a.turntable > 0) std::printf("frame %d -> %s\n", frame, output.c_str());

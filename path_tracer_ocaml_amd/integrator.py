@@ -65,11 +65,12 @@ class Integrator:
     ``sphere_light_sampling``: True / False for Scene.set_sphere_light_sampling -- with "sampled" lighting the light half then holds
     the scene's emissive spheres beside its emissive triangles; like ``environment_sampling`` True is applied before the lighting mode.
     ``camera_pose``: (origin, rotation) or (origin, rotation, view) for Scene.set_camera_pose -- what camera_pose_look_at returns;
-    None leaves the scene's as it is."""
+    None leaves the scene's as it is.  ``projection``: "perspective" or "latlong" (or the PTX_PROJECTION_* value) for
+    Scene.set_camera_projection, applied after the lens; None leaves the scene's as it is."""
 
     def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
                  environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None,
-                 camera_pose=None):
+                 camera_pose=None, projection=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
@@ -83,6 +84,8 @@ class Integrator:
             self._scene.set_lens(*lens)
         if camera_pose is not None:
             self._scene.set_camera_pose(*camera_pose)
+        if projection is not None:
+            self._scene.set_camera_projection(projection)
         if environment is not None:
             self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
         if environment_sampling is not None:
@@ -102,9 +105,9 @@ class Integrator:
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
                environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None,
-               camera_pose=None):
+               camera_pose=None, projection=None):
         return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images,
-                   environment_sampling, lens, sphere_light_sampling, camera_pose)
+                   environment_sampling, lens, sphere_light_sampling, camera_pose, projection)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
