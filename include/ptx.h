@@ -1149,6 +1149,20 @@ int32_t ptx_intersect_rays(ptx_scene* scene, int64_t n, const double* origins,
 int32_t ptx_walk_rays(ptx_scene* scene, int32_t walk, int64_t n, const double* origins, const double* directions,
                       double* t_out, int32_t* prim_out);
 
+/* Diagnostic, for the test suite's coverage record: the instantiations of the four hot kernel families (k_trace, k_shade_pool,
+ * k_bounce_carry, k_bounce) the library is built with, and which of them a handle has launched.
+ * ptx_kernel_table: every family's selector walked over the whole cube of its arguments in a fixed order; an instantiation is entered
+ * the first time it is returned, under a name made of the arguments that returned it ("k_bounce/array/count/lit/queued/hbm/plain/img").
+ * Returns the number of instantiations; names_out (NULL: the count alone) receives the names in table order, each followed by '\n',
+ * then a NUL -- PTX_ERR_ARG when `capacity` bytes do not hold them.  Needs no device.
+ * ptx_scene_launched_kernels: the table indices, ascending, of the instantiations launched on this handle since it was created or
+ * since ptx_scene_clear_launched_kernels -- the pointers handed to the launches themselves, not a schedule read again.  Returns their
+ * number; PTX_ERR_ARG for a NULL scene, a NULL buffer and a `capacity` (in entries) that does not hold them (nothing is written).
+ * A host-only scene has launched nothing.  Clearing while a render runs on the scene is PTX_ERR_STATE. */
+int32_t ptx_kernel_table(char* names_out, int64_t capacity);
+int32_t ptx_scene_launched_kernels(const ptx_scene* scene, int32_t* indices_out, int32_t capacity);
+int32_t ptx_scene_clear_launched_kernels(ptx_scene* scene);
+
 /* Replaces Progressive_photon_map.Make(Scene).go (:420-451) up to, but not including, the per-iteration
  * gamma + PNG write: img_sum_out (HOST, width*height*3, row 0 = top as Bimage stores it) receives the
  * reference's img_sum after `iterations` iterations, i.e. the sum over iterations of estimate / photon_count.

@@ -49,6 +49,7 @@ EXPORTS = (
     "ptx_temporal_defaults", "ptx_temporal_accumulate_device", "ptx_render_temporal", "ptx_temporal_reset",
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
     "ptx_render_rays_device", "ptx_render_rays", "ptx_scene_set_camera_projection", "ptx_scene_camera_projection",
+    "ptx_kernel_table", "ptx_scene_launched_kernels", "ptx_scene_clear_launched_kernels",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -164,6 +165,10 @@ def lib():
         L.ptx_light_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp]
     if hasattr(L, "ptx_walk_rays"):  # (likewise)
         L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
+    if hasattr(L, "ptx_kernel_table"):  # (likewise)
+        L.ptx_kernel_table.argtypes = [C.c_char_p, C.c_int64]
+        L.ptx_scene_launched_kernels.argtypes = [C.c_void_p, ip, C.c_int32]
+        L.ptx_scene_clear_launched_kernels.argtypes = [C.c_void_p]
     if hasattr(L, "ptx_scene_set_lens"):  # (likewise)
         L.ptx_scene_set_lens.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.ptx_scene_lens.argtypes = [C.c_void_p, dp, dp]
@@ -206,6 +211,21 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(ip)
+
+
+def kernel_table():
+    """ptx_kernel_table: the names of the instantiations of k_trace, k_shade_pool, k_bounce_carry and k_bounce the library is built
+    with, in table order (the indices ptx_scene_launched_kernels reports).  Needs no device."""
+    n = lib().ptx_kernel_table(None, 0)
+    if n < 0:
+        _check(n)
+    buf = C.create_string_buffer(128 * n + 1)
+    got = lib().ptx_kernel_table(buf, len(buf))
+    if got < 0:
+        _check(got)
+    names = buf.value.decode().split("\n")[:-1]
+    assert len(names) == got == n
+    return names
 
 
 def render_params(width, height, samples_per_pixel=1, max_bounces=8, band_rows=32, band_first=0, band_step=0,
@@ -813,6 +833,19 @@ class Scene:
         prim = np.zeros(n, dtype=np.int32)
         _check(lib().ptx_walk_rays(self._h, int(walk), n, _dp(o), _dp(d), _dp(t), _ip(prim)))
         return t, prim
+
+    def launched_kernels(self):
+        """ptx_scene_launched_kernels: the names (kernel_table()'s) of the hot kernels' instantiations launched on this handle since
+        it was created or since clear_launched_kernels(), in table order"""
+        names = kernel_table()
+        idx = np.zeros(len(names), dtype=np.int32)
+        n = lib().ptx_scene_launched_kernels(self._h, _ip(idx), len(idx))
+        if n < 0:
+            _check(n)
+        return [names[i] for i in idx[:n]]
+
+    def clear_launched_kernels(self):
+        _check(lib().ptx_scene_clear_launched_kernels(self._h))
 
     def ppm_render(self, params, lights, callback=None):
         """ptx_ppm_render: Progressive_photon_map.Make(Scene).go without the gamma / PNG step -> img_sum (H, W, 3).

@@ -192,6 +192,9 @@ PTX_IMAGE_MAX_SIZE = 16384
 (PTX_WALK_SHARED_ASM, PTX_WALK_OCT_ASM, PTX_WALK_SHARED_DIV, PTX_WALK_PACKET, PTX_WALK_SHARED_ASM_ZERO, PTX_WALK_OCT_ASM_ZERO,
  PTX_WALK_SHARED_DIV_ZERO, PTX_WALK_SHARED_ASM_TAIL, PTX_WALK_OCT_ASM_TAIL, PTX_WALK_SHARED_DIV_TAIL) = range(10)
 
+# ptx_kernel_table: the kernel families its names begin with, in table order (include/ptx.h)
+PTX_KERNEL_FAMILIES = ("k_trace", "k_shade_pool", "k_bounce_carry", "k_bounce")
+
 
 class Image(C.Structure):  # ptx_image
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("rgb", c_double_p)]

@@ -691,7 +691,8 @@ ShadePoolKernel shade_pool_kernel(Shading shading, bool primary, bool img) {
 
 /* k_bounce_carry: 24 = MODE 2 x COUNT 2 x EMIT 2 x (PRIMARY, LANE_WALK) in {00, 10, 11}: only camera rays walk one per lane (a
  * lane walk asked of a queued launch is the plain kernel), and a lit scene never takes this kernel (Schedule::carry_ok);
- * + 4 on the per-octant LDS image (LOCT; Simd_leaf, not counting): EMIT 2 x {queued, camera with lane walk} */
+ * + 6 on the per-octant LDS image (LOCT; Simd_leaf, not counting): EMIT 2 x {queued, camera with lane walk, camera with lane walk
+ * over tile lists} */
 CarryKernel carry_kernel_oct(bool emit, bool primary, bool tile) {
   if (primary && tile) return emit ? k_bounce_carry<PT_MODE_SIMD, false, true, true, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, false, true, true, true, true>;
   if (emit) return primary ? k_bounce_carry<PT_MODE_SIMD, false, true, true, true, true> : k_bounce_carry<PT_MODE_SIMD, false, true, false, false, true>;
@@ -761,6 +762,73 @@ BounceKernel bounce_kernel(int mode, bool count, Shading shading, bool primary, 
 }
 Shading scene_shading(const ptx_scene* s) { return s->sched.lit ? Shading::lit : (s->dev.has_emit ? Shading::emit : Shading::none); }
 
+/* ---- the kernel table (ptx_kernel_table): every selector above walked over the whole cube of its arguments, in the fixed order below;
+ * a pointer is entered the first time a selector returns it, under the name of the arguments that did.  Host code only: the selectors
+ * are pure and the pointers are the host stubs that hipLaunchKernelGGL takes, which is what ptx_scene::attr_done holds. ---- */
+struct KernelEntry {
+  const void* kern;
+  std::string name;
+};
+const std::vector<KernelEntry>& kernel_table() {
+  static const std::vector<KernelEntry> table = [] {
+    std::vector<KernelEntry> t;
+    std::set<const void*> seen;
+    const auto add = [&](const void* k, std::string name) {
+      if (seen.insert(k).second) t.push_back(KernelEntry{k, std::move(name)});
+    };
+    const int modes[2] = {PT_MODE_SIMD, PT_MODE_ARRAY};
+    const char* const mode_n[2] = {"simd", "array"};
+    const char* const count_n[2] = {"nocount", "count"};
+    const char* const shading_n[3] = {"none", "emit", "lit"};
+    const char* const primary_n[2] = {"queued", "camera"};
+    const char* const lds_n[2] = {"hbm", "lds"};
+    const char* const variant_n[3] = {"plain", "solo", "lanewalk"};
+    const char* const img_n[2] = {"noimg", "img"};
+    const auto join = [](std::initializer_list<const char*> parts) {
+      std::string s;
+      for (const char* p : parts) {
+        if (!s.empty()) s += '/';
+        s += p;
+      }
+      return s;
+    };
+    for (int m = 0; m < 2; ++m)
+      for (int c = 0; c < 2; ++c)
+        for (int p = 0; p < 2; ++p)
+          for (int l = 0; l < 2; ++l)
+            for (int k = 0; k < 2; ++k)
+              add((const void*)trace_kernel(modes[m], c != 0, p != 0, l != 0, k != 0),
+                  join({"k_trace", mode_n[m], count_n[c], primary_n[p], lds_n[l], k ? "packet" : "nopacket"}));
+    for (int sh = 0; sh < 3; ++sh)
+      for (int p = 0; p < 2; ++p)
+        for (int i = 0; i < 2; ++i)
+          add((const void*)shade_pool_kernel((Shading)sh, p != 0, i != 0), join({"k_shade_pool", shading_n[sh], primary_n[p], img_n[i]}));
+    for (int m = 0; m < 2; ++m)
+      for (int c = 0; c < 2; ++c)
+        for (int e = 0; e < 2; ++e)
+          for (int p = 0; p < 2; ++p)
+            for (int w = 0; w < 2; ++w)
+              add((const void*)carry_kernel(modes[m], c != 0, e != 0, p != 0, w != 0),
+                  join({"k_bounce_carry", mode_n[m], count_n[c], shading_n[e], primary_n[p], w ? "lanewalk" : "plain"}));
+    for (int e = 0; e < 2; ++e)
+      for (int p = 0; p < 2; ++p)
+        for (int tl = 0; tl < 2; ++tl)
+          add((const void*)carry_kernel_oct(e != 0, p != 0, tl != 0),
+              join({"k_bounce_carry", "simd", "nocount", shading_n[e], primary_n[p], p ? "lanewalk" : "plain", tl ? "oct-tiles" : "oct"}));
+    for (int i = 0; i < 2; ++i)
+      for (int m = 0; m < 2; ++m)
+        for (int c = 0; c < 2; ++c)
+          for (int sh = 0; sh < 3; ++sh)
+            for (int p = 0; p < 2; ++p)
+              for (int l = 0; l < 2; ++l)
+                for (int v = 0; v < 3; ++v)
+                  add((const void*)bounce_kernel(modes[m], c != 0, (Shading)sh, p != 0, l != 0, (Variant)v, i != 0),
+                      join({"k_bounce", mode_n[m], count_n[c], shading_n[sh], primary_n[p], lds_n[l], variant_n[v], img_n[i]}));
+    return t;
+  }();
+  return table;
+}
+
 /* ---- one launch function per family: the kernel by its selector, prepared once, then grid, block and LDS from the schedule ---- */
 constexpr int kNoBounce = -1; /* launch_trace: the rays are not a numbered bounce of a render (ptx_intersect_rays) */
 /* work: 8 zeroed hand-out counters of this launch (PtChunkFeed); susp: the parked-walk buffer of the launching workspace set; bounce:
@@ -806,7 +874,9 @@ void launch_shade_pool(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtH
   const int per_cu = s->shade_wgs_per_cu > 0 ? std::min(s->shade_wgs_per_cu, most) : (sc.share_cus ? std::max(1, most / 2) : most);
   const int grid = strided_grid(s, n_upper, threads, per_cu);
   const size_t lds = pt_lds_shade_pool_bytes(threads / 64);
-  hipLaunchKernelGGL(shade_pool_kernel(scene_shading(s), pl.on, sc.img), dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
+  const ShadePoolKernel kern = shade_pool_kernel(scene_shading(s), pl.on, sc.img);
+  s->attr_done.insert((const void*)kern); /* the launch record (ptx_scene_launched_kernels); its dynamic LDS needs no raised limit */
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, s->dev, q, h, out, c, s->alpha.p, bounce, last, pl.g, pl.n, work);
 }
 
 void launch_bounce_carry(ptx_scene* s, hipStream_t st, const PtQueue& q, const PtHits& h, const PtQueue& out, const PtHits& hout,
@@ -4315,6 +4385,41 @@ int32_t ptx_walk_rays(ptx_scene* s, int32_t walk, int64_t n, const double* origi
       prim_out[i] = s->host->slot_prim[(size_t)sl];
     }
   }
+  return 0;
+}
+
+int32_t ptx_kernel_table(char* names_out, int64_t capacity) {
+  const std::vector<KernelEntry>& table = kernel_table();
+  if (!names_out) return (int32_t)table.size();
+  size_t need = 1;
+  for (const KernelEntry& e : table) need += e.name.size() + 1;
+  if (capacity < 0 || (size_t)capacity < need) return fail(PTX_ERR_ARG, "buffer too small: the %zu names take %zu bytes (capacity %lld)", table.size(), need, (long long)capacity);
+  char* p = names_out;
+  for (const KernelEntry& e : table) {
+    std::memcpy(p, e.name.data(), e.name.size());
+    p += e.name.size();
+    *p++ = '\n';
+  }
+  *p = '\0';
+  return (int32_t)table.size();
+}
+
+int32_t ptx_scene_launched_kernels(const ptx_scene* s, int32_t* indices_out, int32_t capacity) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (!indices_out) return fail(PTX_ERR_ARG, "NULL argument");
+  const std::vector<KernelEntry>& table = kernel_table();
+  std::vector<int32_t> found; /* (attr_done also holds what other launch functions prepared: only the table's kernels are reported) */
+  for (size_t i = 0; i < table.size(); ++i)
+    if (s->attr_done.count(table[i].kern)) found.push_back((int32_t)i);
+  if (capacity < 0 || (size_t)capacity < found.size()) return fail(PTX_ERR_ARG, "buffer too small: %zu kernels were launched (capacity %d)", found.size(), capacity);
+  std::copy(found.begin(), found.end(), indices_out);
+  return (int32_t)found.size();
+}
+
+int32_t ptx_scene_clear_launched_kernels(ptx_scene* s) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the launch record cannot be cleared while a render runs on the scene");
+  s->attr_done.clear(); /* (a kernel's next launch prepares it again: the same limit, the same check) */
   return 0;
 }
 
