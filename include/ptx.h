@@ -868,7 +868,7 @@ int32_t ptx_scene_lens(const ptx_scene* scene, double* radius_out, double* focus
  * _denoised, ptx_render_features_device (the first hit of the posed ray; depth is t along that ray) and ptx_trace_samples.
  * ptx_ppm_render and ptx_debug_first_scatter return PTX_ERR_STATE while a pose is on ("... ptx_scene_set_camera_pose(scene, NULL,
  * NULL, NULL) first"), before any device is touched; ptx_intersect_rays and ptx_walk_rays take explicit rays and are unaffected.
- * A posed render takes the lens's route: its camera rays are written into a path queue (k_generate_pose, one launch per batch,
+ * A posed render takes the lens's route: its camera rays are written into a path queue (k_generate_tiles, one launch per batch,
  * counted under PTX_KERNEL_GENERATE; the same 8 x 8-tile order, ids and holes) and bounced from there in the walk-first order.  It
  * gives up the fused camera launch, the shade-first order, the per-octant LDS image, the camera tile lists (none is built) and the
  * solo run.  Recorded on the MI355X (tools/camera_pose_cost.py, profiles/pr_camera_pose_cost.json, medians of 5): the 1080p spp 64
@@ -917,7 +917,7 @@ int32_t ptx_camera_rays(ptx_scene* scene, const ptx_render_params* params, int64
  * not read.  THE PROJECTION ADDS NO SAMPLER DIMENSION.
  *
  * Route.  A LATLONG scene takes the posed route whether a pose is on or not: its camera rays are written into a path queue
- * (k_generate_pano, counted under PTX_KERNEL_GENERATE; the same 8 x 8-tile order, ids and holes) and bounced walk-first, through
+ * (k_generate_tiles, counted under PTX_KERNEL_GENERATE; the same 8 x 8-tile order, ids and holes) and bounced walk-first, through
  * every driver the pose serves: ptx_render, ptx_render_multi (every scene passed must carry the same projection: PTX_ERR_ARG
  * otherwise), ptx_render_raw_device, _passes_device, _pixels_device, _progressive, _adaptive, _denoised,
  * ptx_render_features_device, ptx_trace_samples and ptx_camera_rays.  ptx_render_temporal (its reprojection is a pinhole's),

@@ -5,18 +5,16 @@
  * -ffp-contract=off). */
 
 /* ------------------------------------------------------------------ first-hit features */
-/* The feature record of primary sample i of a PRIMARY k_trace launch (the virtual queue of pt_primary_decode): the camera ray is
- * computed again from the sample's index by the launch's own functions, the hit is the one the walk stored, and the surface comes
- * from the functions of the render's shade step (pt_shade_entry): the same operands through the same code, the same bits. */
+/* The feature record of entry i of a k_trace launch whose ray was (o, d): the hit is the one the walk stored, and the surface comes
+ * from the functions of the render's shade step (pt_shade_entry): the same operands through the same code, the same bits.  depth is t
+ * along the ray. */
 struct PtFeature {
   V3 albedo, normal;
   double depth, hit;
 };
 template <bool IMG>
-__device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, const PtGenParams& g, const PtPrimarySample& ps,
-                                                       const PtHits& hits, const double* __restrict__ alpha, uint32_t i) {
+__device__ __forceinline__ PtFeature pt_feature_ray(const PtSceneDev& sc, V3 o, V3 d, const PtHits& hits, uint32_t i) {
   PtFeature f;
-  const V3 o = v3(0.0, 0.0, 0.0), d = pt_primary_dir(sc, g, ps, alpha);
   const int slot = hits.slot[i];
   if (slot < 0) {
     f.albedo = pt_background<IMG>(sc, d);
@@ -56,9 +54,40 @@ __device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, con
   return f;
 }
 
+/* ... of primary sample i of a PRIMARY launch (the virtual queue of pt_primary_decode): the pinhole's ray is computed again from the
+ * sample's index by the launch's own functions */
+template <bool IMG>
+__device__ __forceinline__ PtFeature pt_feature_sample(const PtSceneDev& sc, const PtGenParams& g, const PtPrimarySample& ps,
+                                                       const PtHits& hits, const double* __restrict__ alpha, uint32_t i) {
+  const V3 o = v3(0.0, 0.0, 0.0), d = pt_primary_dir(sc, g, ps, alpha);
+  return pt_feature_ray<IMG>(sc, o, d, hits, i);
+}
+
+/* a pixel's 64-byte record of sums, in and out as four 16-byte accesses */
+struct PtFeatureSums {
+  double2 r0, r1, r2, r3;
+};
+__device__ __forceinline__ PtFeatureSums pt_feature_sums_load(const double2* rec) { return PtFeatureSums{rec[0], rec[1], rec[2], rec[3]}; }
+__device__ __forceinline__ void pt_feature_sums_add(PtFeatureSums& s, const PtFeature& f) {
+  s.r0.x = s.r0.x + f.albedo.x;
+  s.r0.y = s.r0.y + f.albedo.y;
+  s.r1.x = s.r1.x + f.albedo.z;
+  s.r1.y = s.r1.y + f.normal.x;
+  s.r2.x = s.r2.x + f.normal.y;
+  s.r2.y = s.r2.y + f.normal.z;
+  s.r3.x = s.r3.x + f.depth;
+  s.r3.y = s.r3.y + f.hit;
+}
+__device__ __forceinline__ void pt_feature_sums_store(double2* rec, const PtFeatureSums& s) {
+  rec[0] = s.r0;
+  rec[1] = s.r1;
+  rec[2] = s.r2;
+  rec[3] = s.r3;
+}
+
 /* feat[pixel] += the records of the batch's n_pass passes, in pass order.  One thread per entry j of ONE pass of the virtual primary
  * queue (8x8 tiles, ragged edges padded: neighbouring lanes read neighbouring hit records); it owns its pixel, so the sums need no
- * atomics and a pixel's additions run in pass order.  The 64-byte record goes in and out as four 16-byte accesses. */
+ * atomics and a pixel's additions run in pass order. */
 template <bool IMG = false> /* IMG: scenes with an image texture or an environment (pt_shade_entry) */
 __global__ __launch_bounds__(256) void k_features(PtSceneDev sc, PtGenParams g, PtHits hits, const double* __restrict__ alpha,
                                                   double* __restrict__ feat) {
@@ -68,24 +97,33 @@ __global__ __launch_bounds__(256) void k_features(PtSceneDev sc, PtGenParams g, 
   const PtPrimarySample p0 = pt_primary_decode(g, j);
   if (!p0.valid) return; /* (n_pass >= 1: pass 0 of the batch decides for every pass) */
   double2* rec = (double2*)(feat + ((long long)p0.gy * g.width + p0.x) * 8);
-  double2 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+  PtFeatureSums sums = pt_feature_sums_load(rec);
   for (int k = 0; k < g.n_pass; ++k) {
     const uint32_t i = (uint32_t)k * per_pass + j;
     const PtPrimarySample ps = pt_primary_decode(g, i);
-    const PtFeature f = pt_feature_sample<IMG>(sc, g, ps, hits, alpha, i);
-    r0.x = r0.x + f.albedo.x;
-    r0.y = r0.y + f.albedo.y;
-    r1.x = r1.x + f.albedo.z;
-    r1.y = r1.y + f.normal.x;
-    r2.x = r2.x + f.normal.y;
-    r2.y = r2.y + f.normal.z;
-    r3.x = r3.x + f.depth;
-    r3.y = r3.y + f.hit;
+    pt_feature_sums_add(sums, pt_feature_sample<IMG>(sc, g, ps, hits, alpha, i));
   }
-  rec[0] = r0;
-  rec[1] = r1;
-  rec[2] = r2;
-  rec[3] = r3;
+  pt_feature_sums_store(rec, sums);
+}
+
+/* k_features for the cameras whose rays are generated (k_generate_tiles<CAM, false>): the same thread-per-pixel sums in pass order over
+ * the queue the generator wrote and k_trace walked; the ray of an entry is read back from that queue */
+template <bool IMG>
+__global__ __launch_bounds__(256) void k_features_queue(PtSceneDev sc, PtGenParams g, PtQueue q, PtHits hits, double* __restrict__ feat) {
+  const uint32_t per_pass = (uint32_t)(g.tiles_x * g.tiles_y) * 64u;
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= per_pass) return;
+  const PtPrimarySample p0 = pt_primary_decode(g, j);
+  if (!p0.valid) return;
+  double2* rec = (double2*)(feat + ((long long)p0.gy * g.width + p0.x) * 8);
+  PtFeatureSums sums = pt_feature_sums_load(rec);
+  for (int k = 0; k < g.n_pass; ++k) {
+    const uint32_t i = (uint32_t)k * per_pass + j;
+    V3 o, d;
+    pt_q_load_ray(q, i, o, d);
+    pt_feature_sums_add(sums, pt_feature_ray<IMG>(sc, o, d, hits, i));
+  }
+  pt_feature_sums_store(rec, sums);
 }
 
 /* the feature means of ptx_render_denoised's feat_out: sums / kf, the hits included */

@@ -186,26 +186,6 @@ __device__ __forceinline__ V3 pt_camera_dir(const PtSceneDev& sc, double cx, dou
   return v3_normalize(v3(sc.cam_llx + (sc.cam_vx * cx), sc.cam_lly + (sc.cam_vy * cy), -1.0));
 }
 
-/* explicit (x, y, pass) triples: ptx_trace_samples */
-__global__ __launch_bounds__(256) void k_generate_list(PtSceneDev sc, int width, int height, int spp, long long n,
-                                                       const int32_t* __restrict__ xs, const int32_t* __restrict__ ys,
-                                                       const int32_t* __restrict__ passes,
-                                                       const double* __restrict__ alpha, PtQueue q) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = i < n;
-  const uint32_t dst = pt_wave_append(q.count, valid);
-  if (!valid) return;
-  const int x = xs[i], gy = ys[i], pass = passes[i];
-  const int offset = (gy * width) + x + (pass * spp);
-  const double widthf = 1.0 / (double)width, heightf = 1.0 / (double)height;
-  const double dxs = pt_lds_get(alpha, offset, 0), dys = pt_lds_get(alpha, offset, 1);
-  const double cx = ((double)x + dxs) * widthf;
-  const double cy = 1.0 - (((double)gy + dys) * heightf);
-  const V3 dir = pt_camera_dir(sc, cx, cy);
-  if (sc.has_emit) pt_q_store<true>(q, dst, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
-  else pt_q_store<false>(q, dst, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
-}
-
 /* ------------------------------------------------------------------ trace */
 /* Bbox.is_hit (bbox.ml:40-56) with Base's NaN-propagating min/max */
 __device__ __forceinline__ bool pt_slab_hit(const PtNode& n, V3 o, V3 inv, double t_min, double t_max) {
@@ -289,13 +269,15 @@ __device__ __forceinline__ PtPrimarySample pt_primary_decode(const PtGenParams& 
   s.id = (uint32_t)((long long)pass_in_batch * g.width * g.local_rows + (long long)s.y * g.width + s.x);
   return s;
 }
+
+/* camera rays written into a queue: the film coordinates, the camera kinds and the three generators */
+#include "camera_rays.inc"
+
 /* render_tile (integrator.ml:98-105) + Camera.ray (camera.ml:93-102) */
 __device__ __forceinline__ V3 pt_primary_dir(const PtSceneDev& sc, const PtGenParams& g, const PtPrimarySample& s,
                                              const double* __restrict__ alpha) {
-  const double widthf = 1.0 / (double)g.width, heightf = 1.0 / (double)g.height;
-  const double dxs = pt_lds_get(alpha, s.offset, 0), dys = pt_lds_get(alpha, s.offset, 1);
-  const double cx = ((double)s.x + dxs) * widthf;
-  const double cy = 1.0 - (((double)s.gy + dys) * heightf);
+  double cx, cy;
+  pt_film_coords(alpha, s.x, s.gy, g.width, g.height, s.offset, &cx, &cy);
   return pt_camera_dir(sc, cx, cy);
 }
 
@@ -3831,29 +3813,6 @@ __global__ __launch_bounds__(256) void k_list_check(const int32_t* __restrict__ 
   if (p < 0 || (long long)p >= npix) *bad = 1;
 }
 
-/* Camera rays of passes [first_pass, first_pass + n_pass) for the listed pixels (pix[j] = y * width + x, whole image), pass-major
- * then list order: entry i = pass_in_batch * n_list + j, and its contribution id is i.  k_generate_list's arithmetic, but every entry
- * owns its slot (no append), so the queue is dense and keeps the list's order; *q.count is set to the entry count. */
-__global__ __launch_bounds__(256) void k_generate_pixels(PtSceneDev sc, int width, int height, int spp, int first_pass, int n_pass,
-                                                         const int32_t* __restrict__ pix, long long n_list,
-                                                         const double* __restrict__ alpha, PtQueue q) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long n = (long long)n_pass * n_list;
-  if (i == 0) *q.count = (uint32_t)n;
-  if (i >= n) return;
-  const long long pass_in_batch = i / n_list, j = i - pass_in_batch * n_list;
-  const int p = pix[j];
-  const int gy = p / width, x = p - gy * width;
-  const int offset = (gy * width) + x + ((first_pass + (int)pass_in_batch) * spp);
-  const double widthf = 1.0 / (double)width, heightf = 1.0 / (double)height;
-  const double dxs = pt_lds_get(alpha, offset, 0), dys = pt_lds_get(alpha, offset, 1);
-  const double cx = ((double)x + dxs) * widthf;
-  const double cy = 1.0 - (((double)gy + dys) * heightf);
-  const V3 dir = pt_camera_dir(sc, cx, cy);
-  if (sc.has_emit) pt_q_store<true>(q, (uint32_t)i, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
-  else pt_q_store<false>(q, (uint32_t)i, v3(0.0, 0.0, 0.0), dir, v3(1.0, 1.0, 1.0), v3(0.0, 0.0, 0.0), (uint32_t)i, offset);
-}
-
 /* k_accum / k_accum_sq over a pixel list: raw[pix[j]] += contributions pass_in_batch * n_list + j in pass order, sq (nullable) the
  * squares, as those kernels add them; passes (nullable: the count map) [pix[j]] = pass_end */
 __global__ __launch_bounds__(256) void k_accum_list(PtContrib contrib, long long n_list, int n_pass, const int32_t* __restrict__ pix,
@@ -4344,9 +4303,6 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "bvh_build_gpu.inc"
 #include "ppm.inc"
 #include "denoise.inc"
-#include "lens.inc"
-#include "camera_pose.inc"
-#include "panorama.inc"
 #include "temporal.inc"
 #include "rays.inc"
 #include "ptx_api.inc"

@@ -263,8 +263,8 @@ struct Schedule {
   bool lit = false;            /* emitters under lighting mode 1 or 2: the LIT instantiations */
   bool img = false;            /* an image texture or an environment: the IMG instantiations */
   bool lens = false;           /* a thin lens (ptx_scene_set_lens): camera rays are generated into a queue, never a PRIMARY launch; the walk-first order */
-  bool pose = false;           /* a camera pose (ptx_scene_set_camera_pose): like a lens, camera rays are generated into a queue (k_generate_pose) and bounced walk-first */
-  bool latlong = false;        /* the lat-long projection (ptx_scene_set_camera_projection): the posed route (pose is set with it), its generators k_generate_pano* */
+  bool pose = false;           /* a camera pose (ptx_scene_set_camera_pose): like a lens, camera rays are generated into a queue (k_generate_tiles) and bounced walk-first */
+  bool latlong = false;        /* the lat-long projection (ptx_scene_set_camera_projection): the posed route (pose is set with it), the PT_CAM_LATLONG kind of the generators */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
   bool lane_walk = false;      /* camera launches of k_bounce / k_bounce_carry walk one ray per lane */
@@ -404,7 +404,7 @@ struct ptx_scene {
    * hand-out words and parked walks -- its own, because a queued slice of a render may be running on the workspace sets meanwhile;
    * ptx_render_denoised: the feature sums, their means for the host, the filter's guide and {c, V} pair, the denoised sums */
   DevBuf<int32_t> feat_slot;
-  DevBuf<PtRayRec> feat_ray; /* a lens's feature slices: the camera rays k_trace walks (k_generate_lens<false>) */
+  DevBuf<PtRayRec> feat_ray; /* a lens's feature slices: the camera rays k_trace walks (k_generate_tiles<CAM, false>) */
   DevBuf<double> feat_t;
   DevBuf<uint32_t> feat_work;
   DevBuf<uint4> feat_susp;
@@ -595,14 +595,14 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
    * it never takes the shade-first order -- hence no per-octant LDS image and no tile lists either -- and never runs solo. */
   c.img = s->dev.n_images != 0 || s->dev.env != nullptr;
   /* A scene with a lens: its camera rays have an origin, which no fused camera launch can take, so they are written into a queue
-   * (k_generate_lens) and bounced like a list's.  The shade-first order starts at a camera launch: a lens scene keeps the walk-first
+   * (k_generate_tiles) and bounced like a list's.  The shade-first order starts at a camera launch: a lens scene keeps the walk-first
    * order, and with it has no per-octant LDS image and no tile lists. */
   c.lens = s->lens_radius > 0.0;
   /* A posed camera (ptx_scene_set_camera_pose), the identity pose included: its rays start at the pose's origin, so they take the
-   * lens's route -- a queue (k_generate_pose) and the walk-first order; no per-octant LDS image, no tile lists (both are made for
+   * lens's route -- a queue (k_generate_tiles) and the walk-first order; no per-octant LDS image, no tile lists (both are made for
    * rays from the origin of the scene's own space), no solo run. */
   /* The lat-long projection: rays in every direction from the pose's origin (origin 0 and the identity while the pose is off) -- the
-   * posed route with generators of its own (panorama.inc), and everything a posed scene gives up. */
+   * posed route with a camera kind of its own (camera_rays.inc), and everything a posed scene gives up. */
   c.latlong = s->projection == PTX_PROJECTION_LATLONG;
   c.pose = s->pose_on || c.latlong;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
@@ -950,6 +950,48 @@ PtCameraPose scene_pose(const ptx_scene* s) {
   return cp;
 }
 
+/* ---- the camera of a launch: which generator instantiation writes a scene's camera rays (camera_rays.inc) ---- */
+/* the one place that maps a scene's state to a camera kind */
+PtCameraKind camera_kind(const Schedule& c) {
+  if (c.latlong) return PT_CAM_LATLONG;
+  if (c.pose) return c.lens ? PT_CAM_POSE_LENS : PT_CAM_POSE;
+  return c.lens ? PT_CAM_LENS : PT_CAM_PINHOLE;
+}
+/* what the kinds read, for renders of this depth (a kind reads its own fields and no other) */
+PtCameraArg scene_camera(const ptx_scene* s, int max_bounces) { return PtCameraArg{scene_pose(s), scene_lens(s, max_bounces)}; }
+/* the one switch over kinds: f(std::integral_constant<int, kind>) with the run-time kind made a compile-time constant */
+template <class F>
+void with_camera_kind(PtCameraKind kind, F&& f) {
+  switch (kind) {
+    case PT_CAM_PINHOLE: return f(std::integral_constant<int, PT_CAM_PINHOLE>());
+    case PT_CAM_LENS: return f(std::integral_constant<int, PT_CAM_LENS>());
+    case PT_CAM_POSE: return f(std::integral_constant<int, PT_CAM_POSE>());
+    case PT_CAM_POSE_LENS: return f(std::integral_constant<int, PT_CAM_POSE_LENS>());
+    case PT_CAM_LATLONG: return f(std::integral_constant<int, PT_CAM_LATLONG>());
+  }
+}
+/* The camera rays of a whole batch in the fused camera launch's order, written to q (pl.n entries, holes included).  path = false: the
+ * rays alone (the feature slices).  Not for the pinhole, whose whole batch IS the fused camera launch: callers ask sched.lens || pose. */
+void launch_generate_tiles(const ptx_scene* s, const ptx_render_params* p, const PrimaryLaunch& pl, bool path, const PtQueue& q, hipStream_t st) {
+  const PtCameraArg cam = scene_camera(s, p->max_bounces);
+  with_camera_kind(camera_kind(s->sched), [&](auto kind) {
+    constexpr int CAM = decltype(kind)::value;
+    if constexpr (CAM != PT_CAM_PINHOLE)
+      hipLaunchKernelGGL((path ? k_generate_tiles<CAM, true> : k_generate_tiles<CAM, false>), dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, pl.g,
+                         cam, (const double*)s->alpha.p, q);
+  });
+}
+/* the camera rays of n_pass passes of a pixel list, dense and pass-major in q */
+void launch_generate_pixels(const ptx_scene* s, const ptx_render_params* p, int first, int n_pass, const int32_t* d_list, long long n_list,
+                            const PtQueue& q, hipStream_t st) {
+  const PtCameraArg cam = scene_camera(s, p->max_bounces);
+  const size_t n_paths = (size_t)n_pass * (size_t)n_list;
+  with_camera_kind(camera_kind(s->sched), [&](auto kind) {
+    hipLaunchKernelGGL(k_generate_pixels<decltype(kind)::value>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, st, s->dev, p->width,
+                       p->height, p->samples_per_pixel, first, n_pass, d_list, n_list, cam, (const double*)s->alpha.p, q);
+  });
+}
+
 /* The sampler's alpha table of this dimension becomes the scene's current one (ptx_scene.alpha): looked up, or made and
  * uploaded the first time the dimension is asked for */
 int use_alpha_table(ptx_scene* s, int dim) {
@@ -1269,18 +1311,7 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
     q0.count = w.counts;
     {
       LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-      if (s->sched.latlong)
-        hipLaunchKernelGGL(k_generate_pixels_pano, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_pose(s), (const double*)s->alpha.p, q0);
-      else if (s->sched.pose)
-        hipLaunchKernelGGL(s->sched.lens ? k_generate_pixels_pose<true> : k_generate_pixels_pose<false>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
-      else if (s->sched.lens)
-        hipLaunchKernelGGL(k_generate_pixels_lens, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
-      else
-        hipLaunchKernelGGL(k_generate_pixels, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, ls, s->dev, p->width, p->height,
-                           p->samples_per_pixel, first, n_pass, range.d_list, range.n_list, (const double*)s->alpha.p, q0);
+      launch_generate_pixels(s, p, first, n_pass, range.d_list, range.n_list, q0, ls);
     }
     run_bounces(s, ls, w, n_paths, p->max_bounces, count, timed, PrimaryLaunch());
   } else {
@@ -1298,12 +1329,7 @@ int queue_batch_paths(ptx_scene* s, const ptx_render_params* p, const BatchPlan&
       q0.count = w.counts;
       {
         LaunchTimer t(s, ls, timed, PTX_KERNEL_GENERATE);
-        if (s->sched.latlong)
-          hipLaunchKernelGGL(k_generate_pano<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_pose(s), (const double*)s->alpha.p, q0);
-        else if (s->sched.pose)
-          hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, true> : k_generate_pose<false, true>), dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_pose(s), scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
-        else
-          hipLaunchKernelGGL(k_generate_lens<true>, dim3((pl.n + 255) / 256), dim3(256), 0, ls, s->dev, g, scene_lens(s, p->max_bounces), (const double*)s->alpha.p, q0);
+        launch_generate_tiles(s, p, pl, true, q0, ls);
       }
       run_bounces(s, ls, w, (size_t)pl.n, p->max_bounces, count, timed, PrimaryLaunch());
     } else {
@@ -3584,16 +3610,10 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
     HIP_TRY(hipMemsetAsync(s->feat_work.p, 0, sizeof(uint32_t) * 8, st));
     if (lens) {
       /* the same entries as rays in a queue of their own (48 bytes per entry more), walked as ptx_intersect_rays' are */
-      const PtLens ln = scene_lens(s, p->max_bounces);
       PtQueue q{s->feat_ray.p, nullptr, s->feat_work.p + 8};
-      if (s->sched.latlong)
-        hipLaunchKernelGGL(k_generate_pano<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, scene_pose(s), alpha, q);
-      else if (s->sched.pose)
-        hipLaunchKernelGGL((s->sched.lens ? k_generate_pose<true, false> : k_generate_pose<false, false>), dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, scene_pose(s), ln, alpha, q);
-      else
-        hipLaunchKernelGGL(k_generate_lens<false>, dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, g, ln, alpha, q);
+      launch_generate_tiles(s, p, pl, false, q, st);
       launch_trace(s, st, q, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, kNoBounce);
-      hipLaunchKernelGGL(s->sched.img ? k_features_lens<true> : k_features_lens<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, q, h, d_feat);
+      hipLaunchKernelGGL(s->sched.img ? k_features_queue<true> : k_features_queue<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, q, h, d_feat);
       HIP_TRY(hipGetLastError());
       continue;
     }
@@ -4009,21 +4029,15 @@ int32_t ptx_render_temporal(ptx_scene* s, const ptx_render_params* p_in, const p
 }
 
 namespace {
-/* the camera rays of explicit (x, y, pass) triples appended to q0, by the generator the scene's state selects */
-void launch_generate_list(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* dx, const int32_t* dy, const int32_t* dp, const PtQueue& q0) {
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (s->sched.latlong)
-    hipLaunchKernelGGL(k_generate_list_pano, grid, block, 0, nullptr, s->dev, p->width, p->height, p->samples_per_pixel, (long long)n, dx, dy, dp,
-                       scene_pose(s), s->alpha.p, q0);
-  else if (s->sched.pose)
-    hipLaunchKernelGGL(s->sched.lens ? k_generate_list_pose<true> : k_generate_list_pose<false>, grid, block, 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx, dy, dp, scene_pose(s), scene_lens(s, p->max_bounces), s->alpha.p, q0);
-  else if (s->sched.lens)
-    hipLaunchKernelGGL(k_generate_list_lens, grid, block, 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx, dy, dp, scene_lens(s, p->max_bounces), s->alpha.p, q0);
-  else
-    hipLaunchKernelGGL(k_generate_list, grid, block, 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx, dy, dp, s->alpha.p, q0);
+/* the camera rays of explicit (x, y, pass) triples appended to q0 on the null stream, by the generator of this camera kind
+ * (launch_generate_tiles and launch_generate_pixels are its siblings) */
+void launch_generate_list(ptx_scene* s, const ptx_render_params* p, PtCameraKind kind, int64_t n, const int32_t* dx, const int32_t* dy,
+                          const int32_t* dp, const PtQueue& q0) {
+  const PtCameraArg cam = scene_camera(s, p->max_bounces);
+  with_camera_kind(kind, [&](auto k) {
+    hipLaunchKernelGGL(k_generate_list<decltype(k)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
+                       p->samples_per_pixel, (long long)n, dx, dy, dp, cam, (const double*)s->alpha.p, q0);
+  });
 }
 }  // namespace
 
@@ -4059,7 +4073,7 @@ int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, c
   if (p->max_bounces > 0) {
     PtQueue q0 = w.q[0];
     q0.count = w.counts;
-    launch_generate_list(s, p, n, dx.p, dy.p, dp.p, q0);
+    launch_generate_list(s, p, camera_kind(s->sched), n, dx.p, dy.p, dp.p, q0);
     run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, count, false, PrimaryLaunch());
   }
   HIP_TRY(hipGetLastError());
@@ -4105,7 +4119,7 @@ int32_t ptx_camera_rays(ptx_scene* s, const ptx_render_params* p, int64_t n, con
   HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
   PtQueue q0 = w.q[0];
   q0.count = w.counts;
-  launch_generate_list(s, p, n, dx.p, dy.p, dp.p, q0);
+  launch_generate_list(s, p, camera_kind(s->sched), n, dx.p, dy.p, dp.p, q0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   /* the generator appends wave by wave: entry e is the ray of sample path[e].id */
@@ -4478,8 +4492,7 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
   {
     PtQueue q0 = w.q[0];
     q0.count = w.counts;
-    hipLaunchKernelGGL(k_generate_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx.p, dy.p, dpp.p, s->alpha.p, q0);
+    launch_generate_list(s, p, PT_CAM_PINHOLE, n, dx.p, dy.p, dpp.p, q0); /* (every other kind was refused above) */
   }
   run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, false, false, PrimaryLaunch(), 1);
   HIP_TRY(hipGetLastError());

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void k_rays_check(long long n, const double* _
 
 /* One batch: rays [first, first + n) of the caller's arrays become entries [0, n) of the queue, entry = id = the ray's index in the
  * batch (every thread owns its slot: no append, the queue's order is the caller's).  Consecutive lanes read consecutive 24-byte
- * triples of both arrays (a wave: two contiguous 1.5 KiB stretches) and write consecutive records through pt_lens_store, so a lit
+ * triples of both arrays (a wave: two contiguous 1.5 KiB stretches) and write consecutive records through pt_q_store_fresh, so a lit
  * scene gets its emission record.  NORMALIZE: V3.normalize of the direction first; otherwise the direction as it was given. */
 template <bool NORMALIZE>
 __global__ __launch_bounds__(256) void k_generate_rays(PtSceneDev sc, long long first, uint32_t n, const double* __restrict__ o3,
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_generate_rays(PtSceneDev sc, long long 
   V3 d = v3(d3[3 * r], d3[3 * r + 1], d3[3 * r + 2]);
   if (NORMALIZE) d = v3_normalize(d);
   const int offset = offsets ? offsets[r] : (int)r;
-  pt_lens_store(sc, q, i, o, d, i, offset);
+  pt_q_store_fresh(sc, q, i, o, d, i, offset);
 }
 
 /* The batch's contributions folded into the caller's bins: bin b is rays [b m, (b + 1) m), one thread per bin that the batch

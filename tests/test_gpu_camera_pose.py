@@ -105,8 +105,8 @@ def test_samples_under_a_pose_and_a_lens(P, oracle):
 @pytest.mark.parametrize("name, w, h, spp, depth", [("shirley", 13, 7, 4, 4), ("shirley", 64, 40, 4, 4), ("cornell", 16, 16, 4, 8)])
 @pytest.mark.parametrize("lens", [False, True])
 def test_the_identity_pose_renders_the_pinholes_sums(P, oracle, torch, name, w, h, spp, depth, lens):
-    """order, ids, holes and offsets of the generator against the fused camera launch's (or k_generate_lens's), and the counters of
-    a posed render; with the pose off again the scene reports what it reported before"""
+    """order, ids, holes and offsets of the generator against the fused camera launch's (or the lens kind of k_generate_tiles), and
+    the counters of a posed render; with the pose off again the scene reports what it reported before"""
     c = S.case(name, oracle, w, h)
     g = S.gpu_scene(P, c, None, lens=lens)
     params, counting = P.render_params(w, h, spp, depth), P.render_params(w, h, spp, depth, count_work=True)
@@ -293,6 +293,51 @@ def test_features_are_the_first_hit_of_the_posed_ray(P, oracle, torch, name, pos
     sums = np.zeros((H * W, 8))
     for k in range(SPP):
         sums = sums + want[:, k]
+    got = feat.cpu().numpy().reshape(-1, 8)
+    assert np.array_equal(got[:, 7], sums[:, 7]) and 0 < sums[:, 7].sum()
+    assert np.array_equal(bits(got[:, 6]), bits(sums[:, 6])), "depth"
+    assert np.array_equal(bits(got[:, :3]), bits(sums[:, :3])), "albedo"
+    assert np.array_equal(bits(got[:, 3:6]), bits(sums[:, 3:6])), "normal"
+    g.close()
+
+
+def test_a_pixel_list_and_the_features_under_a_pose_and_a_lens(P, oracle, torch):
+    """pose + lens away from the explicit-sample list: the pixel-list generator and the rays-only tile generator that feeds the
+    features, at a frame of two ragged tile columns and two ragged tile rows"""
+    c = S.case("shirley", oracle)
+    pose = c["poses"]["inside_glass"]
+    g = S.gpu_scene(P, c, pose, lens=True)
+    depth = 4
+    params = P.render_params(W, H, SPP, depth)
+    # the pixel list: those pixels of the raw sums, which are the restated samples in pass order
+    want, _ = S.restated(c, pose, depth, lens=True)
+    whole, _ = _raw(torch, g, params)
+    assert np.array_equal(bits(whole), bits(S.pass_order_sums(want, W, H, SPP))) and float(want.max()) > 0.0
+    assert not np.array_equal(bits(want), bits(S.restated(c, pose, depth)[0]))  # the lens is not ignored
+    pix = np.random.default_rng(9).choice(W * H, 37, replace=False).astype(np.int32)  # ragged: no multiple of a wave, unordered
+    d_pix = torch.tensor(pix, device="cuda:0")
+    raw = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
+    st = g.render_pixels_device(params, 0, SPP, d_pix.data_ptr(), len(pix), raw.data_ptr())
+    raw = raw.cpu().numpy().reshape(-1, 3)
+    assert st["samples"] == len(pix) * SPP
+    assert np.array_equal(bits(raw[pix]), bits(whole.reshape(-1, 3)[pix])) and float(raw[pix].max()) > 0.0
+    rest = np.setdiff1d(np.arange(W * H), pix)
+    assert (raw[rest] == 0.0).all()
+    # the features, in two slices
+    feat = torch.zeros((H, W, 8), dtype=torch.float64, device="cuda:0")
+    sliced = P.render_params(W, H, SPP, depth, passes_per_batch=2)
+    g.render_features_device(sliced, 0, 2, feat.data_ptr())
+    g.render_features_device(sliced, 2, 1, feat.data_ptr())
+    xs, ys, ps = S.all_samples()
+
+    def sums_of(lens):
+        hits = c["ref"].first_hits(pose, W, H, SPP, depth, xs, ys, ps, c["images"], c["env"], lens=lens).reshape(H * W, SPP, 8)
+        sums = np.zeros((H * W, 8))
+        for k in range(SPP):
+            sums = sums + hits[:, k]
+        return sums
+    sums = sums_of(c["lens"])
+    assert not np.array_equal(bits(sums), bits(sums_of(None)))  # the lens is not ignored
     got = feat.cpu().numpy().reshape(-1, 8)
     assert np.array_equal(got[:, 7], sums[:, 7]) and 0 < sums[:, 7].sum()
     assert np.array_equal(bits(got[:, 6]), bits(sums[:, 6])), "depth"

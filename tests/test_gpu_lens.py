@@ -87,7 +87,7 @@ def test_raw_sums_are_the_samples_in_pass_order(P, oracle, torch, name):
 @pytest.mark.parametrize("name, knobs, two_kernels", [("shirley", {"PTX_FUSED": "0"}, True), ("shirley", {"PTX_FUSED": "1"}, False),
                                                       ("cornell", {"PTX_FUSED": "0"}, True), ("mesh", {"PTX_FUSED_GLOBAL": "0"}, True)])
 def test_the_two_kernel_bounces_take_generated_rays_too(P, oracle, torch, monkeypatch, name, knobs, two_kernels):
-    """k_trace + k_shade_pool behind k_generate_lens (the knobs are read when the handle is created), and a frame queued with
+    """k_trace + k_shade_pool behind k_generate_tiles (the knobs are read when the handle is created), and a frame queued with
     PTX_RENDER_ASYNC.  PTX_FUSED=1 keeps only the camera LAUNCH on the two kernels: a lens render has none, its bounce 0 is a queued
     bounce like the others and stays one k_bounce launch."""
     for k, v in knobs.items():
