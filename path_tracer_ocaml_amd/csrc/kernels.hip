@@ -1633,6 +1633,101 @@ struct PtChunkFeed {
   }
 };
 
+/* ------------------------------------------------------------------ steps the walking kernels share
+ * (k_trace, k_bounce, k_bounce_carry, k_walk_eval: each step is written here once; DESIGN.md section 4, "Shared protocols") */
+/* two doubles <-> one 16-byte word {lo a, hi a, lo b, hi b} */
+__device__ __forceinline__ uint4 pt_pack2(double a, double b) {
+  return make_uint4((uint32_t)__double2loint(a), (uint32_t)__double2hiint(a), (uint32_t)__double2loint(b), (uint32_t)__double2hiint(b));
+}
+__device__ __forceinline__ double pt_unpack_lo(uint4 w) { return __hiloint2double((int)w.y, (int)w.x); }
+__device__ __forceinline__ double pt_unpack_hi(uint4 w) { return __hiloint2double((int)w.w, (int)w.z); }
+/* {x, y, t} and {t, x, y}: one double and two plain words */
+__device__ __forceinline__ uint4 pt_pack_xy_t(uint32_t x, uint32_t y, double t) { return make_uint4(x, y, (uint32_t)__double2loint(t), (uint32_t)__double2hiint(t)); }
+__device__ __forceinline__ uint4 pt_pack_t_xy(double t, uint32_t x, uint32_t y) { return make_uint4((uint32_t)__double2loint(t), (uint32_t)__double2hiint(t), x, y); }
+
+/* A parked walk (PtTailCtl, and the closest hit so far) as 16-byte words:
+ *   head {queue index, node | slot << 16, t}   an LDS image has < 65536 nodes and slots; slot 0xffff = none yet
+ *   uv   {u, v}                                Array_leaf scenes: the triangle hit's barycentrics
+ *   w    {node, slot, -, -}                    the walk from HBM / L2 (WIDE): both as 32-bit words, head's packed word then unused
+ * k_bounce_carry's record has the same packed word in front of its own fields (its ray is nowhere in memory). */
+__device__ __forceinline__ uint32_t pt_tail_node_slot(uint32_t node, int slot) { return node | ((uint32_t)(slot < 0 ? 0xffff : slot) << 16); }
+__device__ __forceinline__ uint32_t pt_tail_node_of(uint32_t w) { return w & 0xffffu; }
+__device__ __forceinline__ int pt_tail_slot_of(uint32_t w) { return (int)(w >> 16) == 0xffff ? -1 : (int)(w >> 16); }
+__device__ __forceinline__ uint4 pt_tail_head(uint32_t i, uint32_t node, int slot, double t) { return pt_pack_xy_t(i, pt_tail_node_slot(node, slot), t); }
+__device__ __forceinline__ uint4 pt_tail_wide(uint32_t node, int slot) { return make_uint4(node, (uint32_t)slot, 0u, 0u); }
+/* (the way back is spelled field by field at its three users, tc.node = WIDE ? w.x : pt_tail_node_of(head.y) ...: one function that
+ * fills a PtTailCtl compiles the non-counting k_trace and k_walk_eval to other code than the same statements in place) */
+
+/* The lane's ray for entry i of a chunk: declares o and d, the camera sample's ray (PRIMARY) or the queue's, and clears `valid` where
+ * the lane has none; such a lane holds P3.origin and -z.  A hole of the queue (pt_is_hole) is no ray: ON_HOLE is what the kernel
+ * does about it besides (k_trace notes PT_SLOT_HOLE for the shade launch to drop; k_bounce nothing).
+ * A macro like PT_STAGE_FLOOR below, for the same reason as PT_SHARE_*: as an inlined function (reference outputs, or a struct
+ * returned) the non-counting k_trace instantiations come out with other code and up to 8 more bytes of scratch. */
+#define PT_CHUNK_RAY(PRIMARY, sc, g, alpha, q, i, valid, o, d, ON_HOLE) \
+  V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0); /* P3.origin */ \
+  if (valid) { \
+    if (PRIMARY) { \
+      const PtPrimarySample ps = pt_primary_decode(g, i); \
+      valid = ps.valid; \
+      if (valid) d = pt_primary_dir(sc, g, ps, alpha); \
+    } else { \
+      pt_q_load_ray(q, i, o, d); \
+      if (pt_is_hole(d.x)) { /* never parked, so never seen on resume */ \
+        valid = false; \
+        ON_HOLE; \
+        o = v3(0.0, 0.0, 0.0); \
+        d = v3(0.0, 0.0, -1.0); \
+      } \
+    } \
+  }
+
+/* Scenes walked from HBM / L2: the pre-tested floor triangles (PtSceneView.floor_lds) into the workgroup's `lds_floor`, then the
+ * barrier pt_scene_view leaves out when it copies nothing. */
+#define PT_STAGE_FLOOR(MODE, sc, sv, lds_floor) do { \
+    if (MODE == PT_MODE_ARRAY && sc.n_floor > 0) { \
+      sv.n_floor_lds = sc.n_floor < PT_FLOOR_LDS ? sc.n_floor : PT_FLOOR_LDS; \
+      sv.floor_lds = (const __attribute__((address_space(3))) double*)lds_floor; \
+      for (int k = threadIdx.x; k < sv.n_floor_lds * 10; k += blockDim.x) lds_floor[k] = sc.tri[(size_t)sc.n_slots * 10 + k]; \
+    } \
+    __syncthreads(); \
+  } while (0)
+
+/* A wave's work counters (count_work) into the launch's: one sum over the wave and one atomic per counter. */
+__device__ __forceinline__ void pt_counters_flush(PtCounters* counters, unsigned long long c_nodes, unsigned long long c_prims, unsigned long long c_floor,
+                                                  unsigned long long c_seg, const unsigned long long* c_filter) {
+  c_nodes = pt_wave_sum(c_nodes);
+  c_prims = pt_wave_sum(c_prims);
+  c_floor = pt_wave_sum(c_floor);
+  c_seg = pt_wave_sum(c_seg);
+  const unsigned long long f0 = pt_wave_sum(c_filter[0]), f1 = pt_wave_sum(c_filter[1]);
+  if (pt_lane() == 0) {
+    atomicAdd(&counters->nodes, c_nodes);
+    atomicAdd(&counters->prims, c_prims);
+    atomicAdd(&counters->floor, c_floor);
+    atomicAdd(&counters->segments, c_seg);
+    atomicAdd(&counters->undecided, f0);
+    atomicAdd(&counters->fallback_steps, f1);
+  }
+}
+
+/* Where a wave's life goes (diagnostic builds, tools/diag_phases.py): tick(var) adds the time since the last tick to var, in ticks
+ * of the 100 MHz clock.  ON = false (every default build): nothing. */
+template <bool ON>
+struct PtPhaseClock {
+  unsigned long long last, begin;
+  __device__ __forceinline__ void start() { last = begin = ON ? __builtin_readcyclecounter() : 0ull; }
+  __device__ __forceinline__ void tick(unsigned long long& var) {
+    if (ON) {
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long now = __builtin_readcyclecounter();
+      var += now - last;
+      last = now;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  __device__ __forceinline__ unsigned long long life() const { return last - begin; }
+};
+
 /* The traverse + intersect stage.  PRIMARY: bounce 0, rays come from the sampler + camera, not from a queue.
  * LDS_SCENE: the whole tree and every leaf packet are first copied into LDS (small scenes: Shirley is
  * 22 KB of nodes + 22 KB of packets), so node / packet reads are ds_read_b128 instead of L1 traffic.
@@ -1675,12 +1770,7 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
   PtSceneView sv = pt_scene_view<MODE, LDS_SCENE>(sc, lds_raw, stack_depth, top_in_lds != 0);
   if (!LDS_SCENE) {
     __shared__ double lds_floor[PT_FLOOR_LDS * 10];
-    if (MODE == PT_MODE_ARRAY && sc.n_floor > 0) { /* the pre-tested floor triangles: see PtSceneView.floor_lds */
-      sv.n_floor_lds = sc.n_floor < PT_FLOOR_LDS ? sc.n_floor : PT_FLOOR_LDS;
-      sv.floor_lds = (const __attribute__((address_space(3))) double*)lds_floor;
-      for (int k = threadIdx.x; k < sv.n_floor_lds * 10; k += blockDim.x) lds_floor[k] = sc.tri[(size_t)sc.n_slots * 10 + k];
-    }
-    __syncthreads(); /* pt_scene_view ends with a barrier only when it copies the whole scene */
+    PT_STAGE_FLOOR(MODE, sc, sv, lds_floor);
   }
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   PtChunkFeed feed;
@@ -1694,22 +1784,7 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
     while (feed.take(chunk)) {
       const uint32_t i = chunk * PT_WAVE + lane;
       bool valid = i < n;
-      V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0);
-      if (valid) {
-        if (PRIMARY) {
-          const PtPrimarySample ps = pt_primary_decode(g, i);
-          valid = ps.valid;
-          if (valid) d = pt_primary_dir(sc, g, ps, alpha);
-        } else {
-          pt_q_load_ray(q, i, o, d);
-          if (pt_is_hole(d.x)) {
-            valid = false;
-            hits.slot[i] = PT_SLOT_HOLE;
-            o = v3(0.0, 0.0, 0.0);
-            d = v3(0.0, 0.0, -1.0);
-          }
-        }
-      }
+      PT_CHUNK_RAY(PRIMARY, sc, g, alpha, q, i, valid, o, d, hits.slot[i] = PT_SLOT_HOLE);
       if (COUNT && valid) c_seg++;
       const PtTraceResult r = pt_trace_packet<MODE, COUNT, PRIMARY, LDS_SCENE>(sc, sv, wstack, valid, o, d, c_nodes, c_prims, c_floor, c_filter);
       if (valid) {
@@ -1750,32 +1825,17 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
           valid = i < n;
         }
       }
-      V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0); /* P3.origin */
-      if (valid) {
-        if (PRIMARY) {
-          const PtPrimarySample ps = pt_primary_decode(g, i);
-          valid = ps.valid;
-          if (valid) d = pt_primary_dir(sc, g, ps, alpha);
-        } else {
-          pt_q_load_ray(q, i, o, d);
-          if (pt_is_hole(d.x)) { /* never parked, so never seen on resume */
-            valid = false;
-            hits.slot[i] = PT_SLOT_HOLE;
-            o = v3(0.0, 0.0, 0.0);
-            d = v3(0.0, 0.0, -1.0);
-          }
-        }
-      }
+      PT_CHUNK_RAY(PRIMARY, sc, g, alpha, q, i, valid, o, d, hits.slot[i] = PT_SLOT_HOLE);
       if (COUNT && valid && !resume) c_seg++;
       const unsigned long long diag_n0 = c_nodes;
       PtTailCtl tc;
       tc.min_active = (TAIL && more) ? CUT : 0; /* the last chunks of a wave run to completion */
       tc.resume = resume && valid;
-      tc.node = TAIL_W ? parked_w.x : (parked.y & 0xffffu);
-      tc.slot = TAIL_W ? (int)parked_w.y : ((int)(parked.y >> 16) == 0xffff ? -1 : (int)(parked.y >> 16));
-      tc.t = __hiloint2double((int)parked.w, (int)parked.z);
-      tc.u = __hiloint2double((int)parked_uv.y, (int)parked_uv.x);
-      tc.v = __hiloint2double((int)parked_uv.w, (int)parked_uv.z);
+      tc.node = TAIL_W ? parked_w.x : pt_tail_node_of(parked.y);
+      tc.slot = TAIL_W ? (int)parked_w.y : pt_tail_slot_of(parked.y);
+      tc.t = pt_unpack_hi(parked);
+      tc.u = pt_unpack_lo(parked_uv);
+      tc.v = pt_unpack_hi(parked_uv);
       tc.unfinished = false;
       /* every lane goes in (wave-level ballots inside); lanes without a ray commit nothing */
       /* (the node loop as one divergent loop where the kernel runs at 4 waves per SIMD: the walk from HBM / L2 -- ganesha-like
@@ -1799,11 +1859,9 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
         if (pm != 0) {
           if (park) {
             const uint32_t k = n_susp + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
-            my_susp[k] = make_uint4(i, tc.node | ((uint32_t)(r.slot < 0 ? 0xffff : r.slot) << 16),
-                                    (uint32_t)__double2loint(r.t), (uint32_t)__double2hiint(r.t));
-            if (TAIL_W) my_susp[2 * PT_WAVE + k] = make_uint4(tc.node, (uint32_t)r.slot, 0u, 0u);
-            if (TAIL_UV)
-              my_susp[PT_WAVE + k] = make_uint4((uint32_t)__double2loint(r.u), (uint32_t)__double2hiint(r.u), (uint32_t)__double2loint(r.v), (uint32_t)__double2hiint(r.v));
+            my_susp[k] = pt_tail_head(i, tc.node, r.slot, r.t);
+            if (TAIL_W) my_susp[2 * PT_WAVE + k] = pt_tail_wide(tc.node, r.slot);
+            if (TAIL_UV) my_susp[PT_WAVE + k] = pt_pack2(r.u, r.v);
           }
           n_susp += (uint32_t)__popcll(pm);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1811,22 +1869,7 @@ __global__ __launch_bounds__(PT_TRACE_BLOCK_OF(MODE, LDS_SCENE), (LDS_SCENE && M
       }
     }
   }
-  if (COUNT) {
-    c_nodes = pt_wave_sum(c_nodes);
-    c_prims = pt_wave_sum(c_prims);
-    c_floor = pt_wave_sum(c_floor);
-    c_seg = pt_wave_sum(c_seg);
-    c_filter[0] = pt_wave_sum(c_filter[0]);
-    c_filter[1] = pt_wave_sum(c_filter[1]);
-    if (lane == 0) {
-      atomicAdd(&counters->nodes, c_nodes);
-      atomicAdd(&counters->prims, c_prims);
-      atomicAdd(&counters->floor, c_floor);
-      atomicAdd(&counters->segments, c_seg);
-      atomicAdd(&counters->undecided, c_filter[0]);
-      atomicAdd(&counters->fallback_steps, c_filter[1]);
-    }
-  }
+  if (COUNT) pt_counters_flush(counters, c_nodes, c_prims, c_floor, c_seg, c_filter);
 }
 
 /* ------------------------------------------------------------------ shade */
@@ -2352,14 +2395,11 @@ __device__ __forceinline__ double pt_env_pd(const PtSceneDev& sc, V3 w) {
   return st > 0.0 ? ((wt / total) * ((double)W * (double)H)) / ((2.0 * (pi * pi)) * st) : 0.0;
 }
 
-/* PT_CAMERA_CARRY (default 1): the camera launches of k_bounce_carry hand shade 0 the decoded sample, the camera direction and the hit
- * distance the same lane held a few instructions earlier (PtCameraCarry), instead of storing hits.t[i] behind a pair of fences and
- * having every category step decode the index, derive the direction and load the distance again.  The same values, so the same
- * arithmetic on them.  With it the TILE launches request their chunk's tile record before the camera direction is derived instead of
- * where it is used.  0: the camera branch without either (tools/build_variant.sh builds the A/B partner with -DPT_CAMERA_CARRY=0). */
-#ifndef PT_CAMERA_CARRY
-#define PT_CAMERA_CARRY 1
-#endif
+/* The camera launches of k_bounce_carry hand shade 0 the decoded sample, the camera direction and the hit distance the same lane held
+ * a few instructions earlier (PtCameraCarry), instead of storing hits.t[i] behind a pair of fences and having every category step
+ * decode the index, derive the direction and load the distance again.  The same values, so the same arithmetic on them.  The TILE
+ * launches request their chunk's tile record before the camera direction is derived instead of where it is used.  (The camera branch
+ * without either was this one's A/B partner: profiles/pr_ab_camera_carry.txt, profiles/pr_camera_carry_isa.txt.) */
 /* of ps only id, offset and valid are read after the walk: the caller leaves the rest zero and the registers go */
 struct PtCameraCarry {
   PtPrimarySample ps;
@@ -2669,6 +2709,43 @@ __device__ __forceinline__ void pt_pool_push(const PtSceneDev& sc, const PtQueue
   if (so.keep) pt_q_store<EMIT>(out, dst, so.n_o, so.n_d, so.n_attn, so.n_emit, so.id, so.offset);
 }
 
+/* The workgroup's share of a launch's chunks (k_shade_pool, k_bounce, k_bounce_carry).  PT_SHARE_WGS declares n_wg, how many
+ * workgroups take part -- fewer than the grid when a wave would get less than min_chunks (workgroup-uniform; the others return at
+ * once).  Those deal the chunks among themselves in runs of PT_POOL_RUN, round-robin; a workgroup's waves take the chunks of its runs
+ * one by one from a counter in LDS: PT_SHARE_NEXT declares k, the wave's next count (wave-uniform), PT_SHARE_CHUNK is that count's
+ * chunk of the launch (>= total_chunks: the share is exhausted).
+ * Macros, not functions: as inlined functions the same statements compile every instantiation of k_shade_pool to other code (+-300
+ * of ~10000 instructions, other SGPR spill counts), and that kernel is held to the parent's instructions. */
+#define PT_SHARE_WGS(n_wg, total_chunks, min_chunks, nw) \
+  uint32_t n_wg = (total_chunks) / (uint32_t)((min_chunks) * (nw)); \
+  n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg)
+#define PT_SHARE_NEXT(k, lds_ctr, lane) \
+  uint32_t k = 0u; \
+  if ((lane) == 0) k = __hip_atomic_fetch_add(&(lds_ctr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
+  k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k)
+#define PT_SHARE_CHUNK(k, n_wg) (((k) / PT_POOL_RUN) * ((n_wg) * PT_POOL_RUN) + blockIdx.x * PT_POOL_RUN + ((k) % PT_POOL_RUN))
+
+/* HOLES (above): the last of the workgroup's nw waves to arrive marks what is left of the workgroup's part-filled output blocks;
+ * mark(e) makes entry e of the output queue a hole, the way the kernel's reader looks for one. */
+template <typename Mark>
+__device__ __forceinline__ void pt_blocks_close(uint32_t* lds_done, const uint32_t* lds_out, int nw, Mark mark) {
+  const int lane = pt_lane();
+  uint32_t done = 0u;
+  if (lane == 0) done = __hip_atomic_fetch_add(lds_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+  done = (uint32_t)__builtin_amdgcn_readfirstlane((int)done);
+  if (done != (uint32_t)(nw - 1)) return;
+  for (int b = 0; b < PT_POOL_BINS; ++b) {
+    const uint32_t st = __hip_atomic_load(lds_out + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint32_t blk = st >> 12, pos = st & 0xfffu;
+    if (blk == PT_POOL_NO_BLOCK) continue;
+    for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE) mark((size_t)blk * PT_POOL_BLOCK + e);
+  }
+}
+/* a queue whose reader looks at the rays (k_trace, k_bounce): direction x = the hole NaN */
+__device__ __forceinline__ void pt_blocks_close_rays(uint32_t* lds_done, const uint32_t* lds_out, int nw, const PtQueue& out) {
+  pt_blocks_close(lds_done, lds_out, nw, [&](size_t e) { out.ray[e].dx = __hiloint2double((int)PT_HOLE_HI, 0); });
+}
+
 template <bool EMIT, bool PRIMARY, bool LIT = false, bool IMG = false>
 __global__ __launch_bounds__(IMG ? PT_POOL_THREADS_IMG : PT_POOL_THREADS, IMG ? PT_IMG_WAVES : PT_SHADE_WAVES) void k_shade_pool(PtSceneDev sc, PtQueue q, PtHits hits, PtQueue out, PtContrib contrib,
                                                 const double* __restrict__ alpha, int bounce, int last_bounce,
@@ -2679,8 +2756,7 @@ __global__ __launch_bounds__(IMG ? PT_POOL_THREADS_IMG : PT_POOL_THREADS, IMG ? 
   const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
-  uint32_t n_wg = total_chunks / (uint32_t)(PT_POOL_MIN_CHUNKS * nw);
-  n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg);
+  PT_SHARE_WGS(n_wg, total_chunks, PT_POOL_MIN_CHUNKS, nw);
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
   if (threadIdx.x == 0) { lds_chunk_ctr = 0u; lds_done = 0u; }
   if (threadIdx.x < PT_POOL_BINS) lds_out[threadIdx.x] = (PT_POOL_NO_BLOCK << 12) | (uint32_t)PT_POOL_BLOCK; /* "full": the first push brings a block */
@@ -2695,10 +2771,8 @@ __global__ __launch_bounds__(IMG ? PT_POOL_THREADS_IMG : PT_POOL_THREADS, IMG ? 
   int slotB = PT_SLOT_HOLE, slotC = PT_SLOT_HOLE, catC = PT_CAT_NONE;
   bool haveB = false, haveC = false; /* wave-uniform */
 #define PT_POOL_TAKE_B() do { \
-    uint32_t unit_ = 0u; \
-    if (lane == 0) unit_ = __hip_atomic_fetch_add(&lds_chunk_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-    unit_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit_); \
-    unit_ = (unit_ / PT_POOL_RUN) * (n_wg * PT_POOL_RUN) + blockIdx.x * PT_POOL_RUN + (unit_ % PT_POOL_RUN); \
+    PT_SHARE_NEXT(unit_, lds_chunk_ctr, lane); \
+    unit_ = PT_SHARE_CHUNK(unit_, n_wg); \
     haveB = unit_ < total_chunks; \
     iB = unit_ * PT_WAVE + (uint32_t)lane; \
     slotB = PT_SLOT_HOLE; \
@@ -2799,18 +2873,7 @@ __global__ __launch_bounds__(IMG ? PT_POOL_THREADS_IMG : PT_POOL_THREADS, IMG ? 
 #undef PT_POOL_TAKE_B
 #undef PT_POOL_ADVANCE
   if (last_bounce) return;
-  /* the workgroup's last wave marks what is left of its blocks as holes */
-  uint32_t done = 0u;
-  if (lane == 0) done = __hip_atomic_fetch_add(&lds_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-  done = (uint32_t)__builtin_amdgcn_readfirstlane((int)done);
-  if (done != (uint32_t)(nw - 1)) return;
-  for (int b = 0; b < PT_POOL_BINS; ++b) {
-    const uint32_t st = __hip_atomic_load(lds_out + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint32_t blk = st >> 12, pos = st & 0xfffu;
-    if (blk == PT_POOL_NO_BLOCK) continue;
-    for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE)
-      out.ray[(size_t)blk * PT_POOL_BLOCK + e].dx = __hiloint2double((int)PT_HOLE_HI, 0);
-  }
+  pt_blocks_close_rays(&lds_done, lds_out, nw, out);
 }
 
 /* ------------------------------------------------------------------ one kernel per bounce
@@ -2877,6 +2940,48 @@ __device__ __forceinline__ void pt_lds_unlock(uint32_t* l) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   if (pt_lane() == 0) __hip_atomic_store(l, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+/* The workgroup's parked walks (PtTailCtl): a stack of records in LDS under a count and a lock.  A wave that parks walks, or takes up to
+ * 64 up again, brackets its own record stores / loads with a begin, which takes the lock and says where they go, and an end, which
+ * leaves the new count and the lock.  Every lane of the wave calls both; what they return is wave-uniform. */
+struct PtParkSpan {
+  uint32_t base, take; /* records base .. base + take - 1 */
+};
+/* the most recently parked 64, or what is left once this wave's share of the input is exhausted (!more); take == 0: another wave was faster */
+__device__ __forceinline__ PtParkSpan pt_park_take_begin(uint32_t* park_n, uint32_t* park_lock, bool more) {
+  pt_lds_lock(park_lock);
+  const uint32_t np = __hip_atomic_load(park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  PtParkSpan s;
+  s.take = (np >= (uint32_t)PT_WAVE || !more) ? (np < (uint32_t)PT_WAVE ? np : (uint32_t)PT_WAVE) : 0u;
+  s.base = np - s.take;
+  return s;
+}
+__device__ __forceinline__ void pt_park_take_end(uint32_t* park_n, uint32_t* park_lock, PtParkSpan s) {
+  if (pt_lane() == 0 && s.take) __hip_atomic_store(park_n, s.base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  pt_lds_unlock(park_lock);
+}
+/* the lanes of mask pm (not empty) park: the lane's record is base + its rank among them */
+__device__ __forceinline__ uint32_t pt_park_put_begin(uint32_t* park_n, uint32_t* park_lock) {
+  pt_lds_lock(park_lock);
+  return __hip_atomic_load(park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void pt_park_put_end(uint32_t* park_n, uint32_t* park_lock, uint32_t base, unsigned long long pm) {
+  if (pt_lane() == 0) __hip_atomic_store(park_n, base + (uint32_t)__popcll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  pt_lds_unlock(park_lock);
+}
+/* A wave's own stores (hit records, parked states, pool entries) before its own later loads of them: program order is enough for
+ * that (one wave's vector memory instructions reach the L1 / L2 in order), the compiler must not move them -- wavefront scope.
+ * wg (PT_BOUNCE_FENCE_WG, or PTX_BOUNCE_FENCE_WG=1 at run time; wave-uniform): workgroup-scope fences instead -- every store of the
+ * turn is waited for (s_waitcnt vmcnt(0)) before the wave goes on.  The safety net should the in-order assumption ever fail on some
+ * part; the parity tests run both (tests/test_gpu_parity.py). */
+__device__ __forceinline__ void pt_own_fence(bool wg) {
+  if (wg) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
 struct PtSolo {
   uint32_t* flag;       /* per batch, zero at its start; null = never run solo */
   uint32_t max_entries; /* run solo when the input queue holds at most this many entries (0 = never) */
@@ -2906,8 +3011,7 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
   StackT* stack = (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(LDS_SCENE, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
-  uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
-  n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg);
+  PT_SHARE_WGS(n_wg, total_chunks, PT_BOUNCE_MIN_CHUNKS, nw);
   bool solo_on = false; /* launch-uniform */
   if (SOLO && solo.flag != nullptr) {
     const uint32_t f = __hip_atomic_load(solo.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2936,12 +3040,7 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
   PtSceneView sv = pt_scene_view<MODE, LDS_SCENE>(sc, lds_raw, stack_depth); /* LDS_SCENE: ends with the workgroup's only barrier (SOLO: per bounce, two more) */
   if (!LDS_SCENE) {
     __shared__ double lds_floor[PT_FLOOR_LDS * 10];
-    if (MODE == PT_MODE_ARRAY && sc.n_floor > 0) { /* the pre-tested floor triangles: see PtSceneView.floor_lds */
-      sv.n_floor_lds = sc.n_floor < PT_FLOOR_LDS ? sc.n_floor : PT_FLOOR_LDS;
-      sv.floor_lds = (const __attribute__((address_space(3))) double*)lds_floor;
-      for (int k = threadIdx.x; k < sv.n_floor_lds * 10; k += blockDim.x) lds_floor[k] = sc.tri[(size_t)sc.n_slots * 10 + k];
-    }
-    __syncthreads(); /* the workgroup's only barrier */
+    PT_STAGE_FLOOR(MODE, sc, sv, lds_floor); /* ends with the workgroup's only barrier */
   }
 #if PT_DIAG_FLOOR == 1
   if (gridDim.x > 0) return; /* diagnostic build: launch + the scene image in LDS, nothing else */
@@ -2971,13 +3070,15 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
   for (int k = 0; k < PT_N_SHADE_CAT; ++k) cnt[k] = 0u;
   /* Parked walks (PtTailCtl) are pooled per WORKGROUP in LDS, behind the shade pools: whichever wave next looks for work and finds
    * 64 of them walks them as a dense chunk.  (Round 4 kept them per wave, in global memory: a wave had to collect 48 of its own
-   * stragglers -- three or four cut chunks -- before it could resume any, which is what held the cut at 16 rays.)  16-byte entries
-   * {queue index, node | slot << 16, t}; + {u, v} for triangle hits; + {node, slot} as 32-bit words on the walk from HBM / L2. */
+   * stragglers -- three or four cut chunks -- before it could resume any, which is what held the cut at 16 rays.)  An entry's
+   * 16-byte words: pt_tail_head; the pool's lock and count: pt_park_take_begin. */
   const uint32_t park_cap = (uint32_t)PT_PARK_CAP(nw, CUT);
   uint4 *park0, *park_uv, *park_w, *park_end;
 #define PT_PARK_AT(region, off_) region = (uint4*)(lds_raw + off_)
 #define PT_PARK_AFTER(region, prev, words_) region = prev + (words_)
   PT_LDS_BOUNCE_PARK(PT_PARK_AT, PT_PARK_AFTER, pool_off, nw, LDS_SCENE, TAIL_UV, park_cap);
+#undef PT_PARK_AT
+#undef PT_PARK_AFTER
   (void)park_end;
   bool more = true;    /* wave-uniform: the workgroup's share of the queue is not exhausted */
   unsigned long long c_nodes = 0, c_prims = 0, c_floor = 0, c_seg = 0, c_filter[2] = {0, 0}; /* COUNT: as in k_trace */
@@ -2992,12 +3093,11 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
    * else in the loop (chunk hand-out, ray loads, filing, parking), segments = the whole loop; undecided / fallback_steps = the
    * number of shade steps / walks */
   constexpr bool DIAG_T = COUNT && (((PT_DIAG == 5 || PT_DIAG == 6 || PT_DIAG == 7) && !PRIMARY) || (PT_DIAG == 8 && PRIMARY)); /* 8: as 5, the camera rays' launches */ /* 6: prims = the walks' leaf phases instead of the shade steps; 7: prims = the pushes alone */
-  unsigned long long tm_last = DIAG_T ? __builtin_readcyclecounter() : 0ull;
-  const unsigned long long tm_begin = tm_last;
-#define PT_TM5(var) do { if (DIAG_T) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); (var) += now_ - tm_last; tm_last = now_; __builtin_amdgcn_sched_barrier(0); } } while (0)
+  PtPhaseClock<DIAG_T> clk;
+  clk.start();
  for (;;) { /* (one turn per bounce; a launch that does not run solo leaves after the first) */
   for (;;) {
-    PT_TM5(c_floor);
+    clk.tick(c_floor);
     const uint32_t park_hint = TAIL ? __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u; /* (wave-uniform: one LDS word) */
     const bool input_left = more || park_hint > 0;
     /* the fullest pool that holds a whole step; once nothing is left to walk, the fullest pool */
@@ -3033,14 +3133,14 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
         default: break;
       }
 #undef PT_POOL_STEP
-      if (PT_DIAG == 7) PT_TM5(c_floor);
+      if (PT_DIAG == 7) clk.tick(c_floor);
       if (c != PT_CAT_MISS && !last_bounce) {
         if (SOLO && solo_on) pt_pool_push<EMIT>(sc, out, so, lds_out, lds_blk[SOLO ? (cur_list ^ 1u) : 0u], &lds_nblk[cur_list ^ 1u],
                                                 own_blocks && own_chunks <= (uint32_t)(PT_SOLO_ONE_BIN_CHUNKS * nw));
         else pt_pool_push<EMIT>(sc, out, so, lds_out);
       }
-      if (PT_DIAG == 6) PT_TM5(c_floor);
-      else PT_TM5(c_prims);
+      if (PT_DIAG == 6) clk.tick(c_floor);
+      else clk.tick(c_prims);
       if (DIAG_T) c_filter[0] += (lane == 0);
       continue;
     }
@@ -3051,29 +3151,23 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
     uint4 parked = make_uint4(0, 0, 0, 0), parked_uv = make_uint4(0, 0, 0, 0), parked_w = make_uint4(0, 0, 0, 0);
     if (TAIL && (park_hint >= (uint32_t)PT_WAVE || (!more && park_hint > 0))) {
       /* 64 parked walks (the most recently parked: a stack), or what is left once this wave's share of the input is exhausted */
-      pt_lds_lock(&lds_park_lock);
-      const uint32_t np = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const uint32_t take = (np >= (uint32_t)PT_WAVE || !more) ? (np < (uint32_t)PT_WAVE ? np : (uint32_t)PT_WAVE) : 0u;
-      const uint32_t base = np - take;
-      if ((uint32_t)lane < take) {
-        parked = park0[base + lane];
-        if (TAIL_UV) parked_uv = park_uv[base + lane];
-        if (TAIL_W) parked_w = park_w[base + lane];
+      const PtParkSpan s = pt_park_take_begin(&lds_park_n, &lds_park_lock, more);
+      if ((uint32_t)lane < s.take) {
+        parked = park0[s.base + lane];
+        if (TAIL_UV) parked_uv = park_uv[s.base + lane];
+        if (TAIL_W) parked_w = park_w[s.base + lane];
       }
-      if (lane == 0 && take) __hip_atomic_store(&lds_park_n, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      pt_lds_unlock(&lds_park_lock);
-      if (take == 0u) continue; /* (another wave was faster) */
+      pt_park_take_end(&lds_park_n, &lds_park_lock, s);
+      if (s.take == 0u) continue; /* (another wave was faster) */
       resume = true;
-      valid = (uint32_t)lane < take;
+      valid = (uint32_t)lane < s.take;
       i = parked.x;
     } else {
       if (!more) continue; /* (only here when the hint and the pool disagreed a moment ago) */
-      /* the next chunk of the workgroup's share (runs of PT_POOL_RUN consecutive chunks, dealt round-robin, as in k_shade_pool;
+      /* the next chunk of the workgroup's share (PT_SHARE_NEXT;
        * taking a chunk one turn ahead and touching its ray records cost 2 % in round 3 and 3.5 % (cornell 5 %) in round 4: a line
        * touched ~10 us early is evicted from the L2 again before the wave comes back for it, and is then fetched twice) */
-      uint32_t unit = 0u;
-      if (lane == 0) unit = __hip_atomic_fetch_add(&lds_chunk_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
+      PT_SHARE_NEXT(unit, lds_chunk_ctr, lane);
       if (SOLO && own_blocks) { /* the workgroup's own blocks of the bounce before (block | entries written << 20), PT_POOL_BLOCK / 64 chunks each */
         more = unit < own_chunks;
         if (more) {
@@ -3084,45 +3178,31 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
           valid = off + (uint32_t)lane < fill;
         }
       } else {
-      unit = (unit / PT_POOL_RUN) * (n_wg * PT_POOL_RUN) + blockIdx.x * PT_POOL_RUN + (unit % PT_POOL_RUN);
-      more = unit < total_chunks;
-      if (more) {
-        i = unit * PT_WAVE + (uint32_t)lane;
-        valid = i < n;
-      }
-      }
-    }
-    V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0); /* P3.origin */
-    if (valid) {
-      if (PRIMARY) {
-        const PtPrimarySample ps = pt_primary_decode(g, i);
-        valid = ps.valid;
-        if (valid) d = pt_primary_dir(sc, g, ps, alpha);
-      } else {
-        pt_q_load_ray(q, i, o, d);
-        if (pt_is_hole(d.x)) { /* never parked, so never seen on resume */
-          valid = false;
-          o = v3(0.0, 0.0, 0.0);
-          d = v3(0.0, 0.0, -1.0);
+        unit = PT_SHARE_CHUNK(unit, n_wg);
+        more = unit < total_chunks;
+        if (more) {
+          i = unit * PT_WAVE + (uint32_t)lane;
+          valid = i < n;
         }
       }
     }
+    PT_CHUNK_RAY(PRIMARY, sc, g, alpha, q, i, valid, o, d, (void)0);
     if (COUNT && !DIAG_T && valid && !resume) c_seg++;
     PtTailCtl tc;
     tc.min_active = (TAIL && more) ? CUT : 0; /* the last chunks of a wave run to completion */
     tc.resume = resume && valid;
-    tc.node = TAIL_W ? parked_w.x : (parked.y & 0xffffu);
-    tc.slot = TAIL_W ? (int)parked_w.y : ((int)(parked.y >> 16) == 0xffff ? -1 : (int)(parked.y >> 16));
-    tc.t = __hiloint2double((int)parked.w, (int)parked.z);
-    tc.u = __hiloint2double((int)parked_uv.y, (int)parked_uv.x);
-    tc.v = __hiloint2double((int)parked_uv.w, (int)parked_uv.z);
+    tc.node = TAIL_W ? parked_w.x : pt_tail_node_of(parked.y);
+    tc.slot = TAIL_W ? (int)parked_w.y : pt_tail_slot_of(parked.y);
+    tc.t = pt_unpack_hi(parked);
+    tc.u = pt_unpack_lo(parked_uv);
+    tc.v = pt_unpack_hi(parked_uv);
     tc.unfinished = false;
     PtTraceResult r;
-    PT_TM5(c_floor);
+    clk.tick(c_floor);
     unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the walk's own counters go nowhere) */
     if constexpr (PRIMARY && LDS_SCENE && !LANE_WALK) r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, valid, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
     else r = pt_trace_ray<MODE, COUNT, PRIMARY, StackT, LDS_SCENE, true, LDS_SCENE && !COUNT && MODE == PT_MODE_SIMD /* (Array_leaf kernels have no registers to pin: cornell +0.5 %; the walk from HBM / L2 in assembly: +1.9 %, profiles/r05_ab_oct_asm.txt) */>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
-    PT_TM5(c_nodes);
+    clk.tick(c_nodes);
     if (DIAG_T) c_filter[1] += (lane == 0);
     const bool park = TAIL && tc.unfinished;
     const bool done = valid && !park;
@@ -3146,32 +3226,17 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
     if (TAIL) {
       const unsigned long long pm = __ballot(park);
       if (pm != 0) {
-        pt_lds_lock(&lds_park_lock);
-        const uint32_t base = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t base = pt_park_put_begin(&lds_park_n, &lds_park_lock);
         if (park) {
           const uint32_t k = base + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
-          park0[k] = make_uint4(i, tc.node | ((uint32_t)(r.slot < 0 ? 0xffff : r.slot) << 16),
-                                (uint32_t)__double2loint(r.t), (uint32_t)__double2hiint(r.t));
-          if (TAIL_W) park_w[k] = make_uint4(tc.node, (uint32_t)r.slot, 0u, 0u);
-          if (TAIL_UV)
-            park_uv[k] = make_uint4((uint32_t)__double2loint(r.u), (uint32_t)__double2hiint(r.u), (uint32_t)__double2loint(r.v), (uint32_t)__double2hiint(r.v));
+          park0[k] = pt_tail_head(i, tc.node, r.slot, r.t);
+          if (TAIL_W) park_w[k] = pt_tail_wide(tc.node, r.slot);
+          if (TAIL_UV) park_uv[k] = pt_pack2(r.u, r.v);
         }
-        if (lane == 0) __hip_atomic_store(&lds_park_n, base + (uint32_t)__popcll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pt_lds_unlock(&lds_park_lock);
+        pt_park_put_end(&lds_park_n, &lds_park_lock, base, pm);
       }
     }
-    /* this wave's own stores (hit records, parked states, pool entries) before its own later loads of them: program order
-     * is enough for that (one wave's vector memory instructions reach the L1 / L2 in order), the compiler must not move them */
-    /* fence_wg (PTX_BOUNCE_FENCE_WG=1, wave-uniform): workgroup-scope fences instead -- every store of the turn is waited for
-     * (s_waitcnt vmcnt(0)) before the wave goes on.  The safety net should the in-order assumption ever fail on some part; the
-     * parity tests run both (tests/test_gpu_parity.py). */
-    if (PT_BOUNCE_FENCE_WG || fence_wg) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    pt_own_fence(PT_BOUNCE_FENCE_WG || fence_wg); /* this turn's hit records, parked states and pool entries */
   }
   if (!(SOLO && solo_on) || last_bounce) break;
   /* SOLO: this workgroup's next bounce.  Every wave has filed, shaded and pushed its last ray of this one when the barrier
@@ -3215,40 +3280,14 @@ __global__ __launch_bounds__(IMG ? PT_BOUNCE_THREADS_IMG : PT_BOUNCE_THREADS, IM
   hits.t += (bounce & 1) ? (ptrdiff_t)hits.t_parity_stride : -(ptrdiff_t)hits.t_parity_stride;
  }
   if (DIAG_T) {
-    PT_TM5(c_floor);
-    c_seg = (lane == 0) ? tm_last - tm_begin : 0ull;
+    clk.tick(c_floor);
+    c_seg = (lane == 0) ? clk.life() : 0ull;
     if (lane != 0) c_nodes = c_prims = c_floor = 0ull; /* wave-uniform quantities: one lane's copy */
   }
-#undef PT_TM5
-  if (COUNT && !(PT_DIAG != 0 && (PRIMARY != (PT_DIAG == 8)))) { /* (diagnostic builds measure the queued rays' launches only; 8: the camera rays') */
-    c_nodes = pt_wave_sum(c_nodes);
-    c_prims = pt_wave_sum(c_prims);
-    c_floor = pt_wave_sum(c_floor);
-    c_seg = pt_wave_sum(c_seg);
-    c_filter[0] = pt_wave_sum(c_filter[0]);
-    c_filter[1] = pt_wave_sum(c_filter[1]);
-    if (lane == 0) {
-      atomicAdd(&counters->nodes, c_nodes);
-      atomicAdd(&counters->prims, c_prims);
-      atomicAdd(&counters->floor, c_floor);
-      atomicAdd(&counters->segments, c_seg);
-      atomicAdd(&counters->undecided, c_filter[0]);
-      atomicAdd(&counters->fallback_steps, c_filter[1]);
-    }
-  }
+  if (COUNT && !(PT_DIAG != 0 && (PRIMARY != (PT_DIAG == 8)))) /* (diagnostic builds measure the queued rays' launches only; 8: the camera rays') */
+    pt_counters_flush(counters, c_nodes, c_prims, c_floor, c_seg, c_filter);
   if (last_bounce || (SOLO && solo_on)) return; /* (a solo launch leaves no queue behind: its paths have all ended) */
-  /* the workgroup's last wave marks what is left of its blocks as holes */
-  uint32_t fin = 0u;
-  if (lane == 0) fin = __hip_atomic_fetch_add(&lds_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-  fin = (uint32_t)__builtin_amdgcn_readfirstlane((int)fin);
-  if (fin != (uint32_t)(nw - 1)) return;
-  for (int b = 0; b < PT_POOL_BINS; ++b) {
-    const uint32_t st = __hip_atomic_load(lds_out + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint32_t blk = st >> 12, pos = st & 0xfffu;
-    if (blk == PT_POOL_NO_BLOCK) continue;
-    for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE)
-      out.ray[(size_t)blk * PT_POOL_BLOCK + e].dx = __hiloint2double((int)PT_HOLE_HI, 0);
-  }
+  pt_blocks_close_rays(&lds_done, lds_out, nw, out);
 }
 
 /* ------------------------------------------------------------------ a bounce launch that shades first and walks second
@@ -3298,8 +3337,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   StackT* stack = LOCT ? nullptr : (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
   const uint32_t n = PRIMARY ? n_primary : *q.count;
   const uint32_t total_chunks = (uint32_t)(((unsigned long long)n + PT_WAVE - 1) / PT_WAVE);
-  uint32_t n_wg = total_chunks / (uint32_t)(PT_BOUNCE_MIN_CHUNKS * nw);
-  n_wg = n_wg < 1u ? 1u : (n_wg > gridDim.x ? gridDim.x : n_wg);
+  PT_SHARE_WGS(n_wg, total_chunks, PT_BOUNCE_MIN_CHUNKS, nw);
   if (COUNT && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->carry, 1ull);
   if (COUNT && PRIMARY && LANE_WALK && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters->lane_walks, 1ull);
   if (blockIdx.x >= n_wg) return; /* workgroup-uniform */
@@ -3316,6 +3354,8 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   /* the workgroup's parked walks behind the scene image (there are no pools): one array of 16-byte words per field (PT_CARRY_PARK_WORDS) */
   const uint32_t park_cap = (uint32_t)PT_PARK_CAP(nw, CUT);
   uint4 *park0, *park_emit, *park_uv, *park_end;
+#define PT_PARK_AT(region, off_) region = (uint4*)(lds_raw + off_)
+#define PT_PARK_AFTER(region, prev, words_) region = prev + (words_)
   PT_LDS_CARRY_REGIONS(PT_PARK_AT, PT_PARK_AFTER, pool_off, EMIT, TAIL_UV, park_cap);
 #undef PT_PARK_AT
 #undef PT_PARK_AFTER
@@ -3327,12 +3367,11 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
    * walk (resumed walks included), undecided = pushes + parking, segments = the whole loop; fallback_steps = the number of tile turns.
    * The queued rays' launches add nothing */
   constexpr bool DIAG_T = COUNT && PT_DIAG == 8 && PRIMARY;
-  unsigned long long tm_last = DIAG_T ? __builtin_readcyclecounter() : 0ull;
-  const unsigned long long tm_begin = tm_last;
+  PtPhaseClock<DIAG_T> clk;
+  clk.start();
   unsigned long long dg_n = 0, dg_p = 0, dg_f = 0; /* (diagnostic builds: the walks' own counters go nowhere) */
-#define PT_TM8(var) do { if (DIAG_T) { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); (var) += now_ - tm_last; tm_last = now_; __builtin_amdgcn_sched_barrier(0); } } while (0)
   for (;;) {
-    PT_TM8(c_filter[0]);
+    clk.tick(c_filter[0]);
     const uint32_t park_hint = TAIL ? __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u; /* (wave-uniform: one LDS word) */
     /* what this turn walks: the lane's ray, and the rest of the entry it will push */
     bool resume = false, valid = false;
@@ -3345,36 +3384,33 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
     tc.t = tc.u = tc.v = 0.0;
     if (TAIL && (park_hint >= (uint32_t)PT_WAVE || (!more && park_hint > 0))) {
       /* 64 parked walks (the most recently parked: a stack), or what is left once this wave's share of the input is exhausted */
-      pt_lds_lock(&lds_park_lock);
-      const uint32_t np = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const uint32_t take = (np >= (uint32_t)PT_WAVE || !more) ? (np < (uint32_t)PT_WAVE ? np : (uint32_t)PT_WAVE) : 0u;
-      const uint32_t base = np - take;
-      if ((uint32_t)lane < take) {
+      const PtParkSpan s = pt_park_take_begin(&lds_park_n, &lds_park_lock, more);
+      if ((uint32_t)lane < s.take) {
+        const uint32_t base = s.base;
         const uint4* p = park0 + base + lane;
         const uint4 h = p[0], r0 = p[park_cap], r1 = p[2u * park_cap], r2 = p[3u * park_cap], a0 = p[4u * park_cap], a1 = p[5u * park_cap];
-        tc.node = h.x & 0xffffu;
-        tc.slot = (int)(h.x >> 16) == 0xffff ? -1 : (int)(h.x >> 16);
+        tc.node = pt_tail_node_of(h.x);
+        tc.slot = pt_tail_slot_of(h.x);
         offset = (int)h.y;
-        tc.t = __hiloint2double((int)h.w, (int)h.z);
-        o = v3(__hiloint2double((int)r0.y, (int)r0.x), __hiloint2double((int)r0.w, (int)r0.z), __hiloint2double((int)r1.y, (int)r1.x));
-        d = v3(__hiloint2double((int)r1.w, (int)r1.z), __hiloint2double((int)r2.y, (int)r2.x), __hiloint2double((int)r2.w, (int)r2.z));
-        attn = v3(__hiloint2double((int)a0.y, (int)a0.x), __hiloint2double((int)a0.w, (int)a0.z), __hiloint2double((int)a1.y, (int)a1.x));
+        tc.t = pt_unpack_hi(h);
+        o = v3(pt_unpack_lo(r0), pt_unpack_hi(r0), pt_unpack_lo(r1));
+        d = v3(pt_unpack_hi(r1), pt_unpack_lo(r2), pt_unpack_hi(r2));
+        attn = v3(pt_unpack_lo(a0), pt_unpack_hi(a0), pt_unpack_lo(a1));
         id = a1.z;
         if (EMIT) {
           const uint4 e0 = park_emit[base + lane], e1 = park_emit[park_cap + base + lane];
-          emit = v3(__hiloint2double((int)e0.y, (int)e0.x), __hiloint2double((int)e0.w, (int)e0.z), __hiloint2double((int)e1.y, (int)e1.x));
+          emit = v3(pt_unpack_lo(e0), pt_unpack_hi(e0), pt_unpack_lo(e1));
         }
         if (TAIL_UV) {
           const uint4 w = park_uv[base + lane];
-          tc.u = __hiloint2double((int)w.y, (int)w.x);
-          tc.v = __hiloint2double((int)w.w, (int)w.z);
+          tc.u = pt_unpack_lo(w);
+          tc.v = pt_unpack_hi(w);
         }
       }
-      if (lane == 0 && take) __hip_atomic_store(&lds_park_n, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      pt_lds_unlock(&lds_park_lock);
-      if (take == 0u) continue; /* (another wave was faster) */
+      pt_park_take_end(&lds_park_n, &lds_park_lock, s);
+      if (s.take == 0u) continue; /* (another wave was faster) */
       resume = true;
-      valid = (uint32_t)lane < take;
+      valid = (uint32_t)lane < s.take;
     } else {
       /* a shade step on the next chunk of the share: 64 entries of one category by construction (launch 0: 64 camera samples) */
       int c = -1;
@@ -3386,11 +3422,8 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         if (park_hint > 0) continue;
         break;
       }
-      /* the next chunk of the workgroup's share (runs of PT_POOL_RUN consecutive chunks, dealt round-robin, as in k_bounce) */
-      uint32_t unit = 0u;
-      if (lane == 0) unit = __hip_atomic_fetch_add(&lds_chunk_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)unit);
-      unit = (unit / PT_POOL_RUN) * (n_wg * PT_POOL_RUN) + blockIdx.x * PT_POOL_RUN + (unit % PT_POOL_RUN);
+      PT_SHARE_NEXT(unit, lds_chunk_ctr, lane); /* the next chunk of the workgroup's share */
+      unit = PT_SHARE_CHUNK(unit, n_wg);
       more = unit < total_chunks;
       if (!more) continue;
       i = unit * PT_WAVE + (uint32_t)lane;
@@ -3400,7 +3433,6 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
          * in turn, its lanes live */
         live = i < n;
         int tile_x = 0, tile_gy = 0; /* TILE: the lane's pixel column and GLOBAL row (lane 0: the tile's first) */
-#if PT_CAMERA_CARRY
         PtPrimarySample ps;
         ps.x = ps.y = ps.gy = ps.pass_in_batch = ps.offset = 0;
         ps.id = 0u;
@@ -3431,30 +3463,11 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
           id = ps.id; /* (what a survivor of shade 0 is pushed with: the step leaves them alone) */
           offset = ps.offset;
         }
-#else
-        if (live) {
-          const PtPrimarySample ps = pt_primary_decode(g, i);
-          live = ps.valid;
-          if (live) d = pt_primary_dir(sc, g, ps, alpha);
-          tile_x = ps.x;
-          tile_gy = ps.gy;
-        }
-#endif
         if (COUNT && !DIAG_T && live) c_seg++;
         PtTraceResult r;
         bool scanned = false; /* wave-uniform */
         if constexpr (TILE) {
-#if PT_CAMERA_CARRY
           if (rec_ok) {
-#else
-          /* lane 0 holds the tile's first pixel, inside the image whenever any lane is live; the record's index is checked against the grid */
-          const uint32_t gtx = (uint32_t)(g.width + 7) >> 3, gty = (uint32_t)(g.height + 7) >> 3;
-          const uint32_t tx = (uint32_t)__builtin_amdgcn_readfirstlane(tile_x) >> 3, ty = (uint32_t)__builtin_amdgcn_readfirstlane(tile_gy) >> 3;
-          if (__ballot(live) != 0ull && tx < gtx && ty < gty) {
-            /* the 32-byte record: lane k < 16 reads halfword k, the header and the slot numbers come out of it by readlane and stay scalar */
-            const uint16_t* rec = (const uint16_t*)sc.tile_lists + ((size_t)ty * gtx + tx) * 16u;
-            const int recv = (int)rec[lane & 15];
-#endif
             const uint32_t head = (uint32_t)__builtin_amdgcn_readlane(recv, 0);
             const uint32_t n_list = head & 0xffu, oct = head >> 8;
             const uint32_t dirs = (d.x >= 0.0 ? 1u : 0u) | (d.y >= 0.0 ? 2u : 0u) | (d.z >= 0.0 ? 4u : 0u); /* PtTraverser::begin */
@@ -3477,7 +3490,6 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         } else if constexpr (LANE_WALK) /* no tail cut: the tile runs to completion */
           r = pt_trace_ray<MODE, COUNT, true, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, live, nullptr, DIAG_T ? nullptr : c_filter);
         else r = pt_trace_packet<MODE, COUNT, true, true>(sc, sv, (uint32_t*)stack, live, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, DIAG_T ? nullptr : c_filter);
-#if PT_CAMERA_CARRY
         /* shade 0 runs in this lane on what it holds: the sample, the direction and the hit distance stay in registers; nothing is
          * stored to hits.t and there is nothing to fence (fence_wg: the queued launches never used it either).  They stay in the
          * registers of what the turn walks next, which a lane does not need before its own category step has run: the path id and the
@@ -3488,24 +3500,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
         }
         o = v3(r.t, 0.0, 0.0);
         (void)fence_wg;
-#else
-        if (live) {
-          if (!(MODE == PT_MODE_ARRAY && sc.has_triangles)) hits.t[i] = r.t; /* (else the shade step recomputes it: PtHits) */
-          sl = r.slot;
-          my_cat = r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot];
-        }
-        /* this wave's own stores (hit distances) before its own loads of them (k_bounce) */
-        if (PT_BOUNCE_FENCE_WG || fence_wg) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        } else {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        o = v3(0.0, 0.0, 0.0);
-        d = v3(0.0, 0.0, -1.0);
-#endif
-        PT_TM8(c_nodes);
+        clk.tick(c_nodes);
         if (DIAG_T) c_filter[1] += (lane == 0);
       } else {
         sl = i < n ? hits.slot[i] : PT_SLOT_HOLE;
@@ -3521,31 +3516,30 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
   if (PRIMARY ? __ballot(my_cat == K) != 0ull : c == K) {                                                              \
     PtShadeOut so;                                                                                                     \
     const PtCameraCarry cam = pt_camera_carry(id, offset, live, d, o.x);                                               \
-    pt_shade_entry<EMIT, PRIMARY, K>(scl, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, SLOT, CAM_CARRY ? &cam : nullptr); \
+    pt_shade_entry<EMIT, PRIMARY, K>(scl, q, hits, contrib, alpha, bounce, last_bounce, g, i, live && my_cat == K, so, SLOT, PRIMARY ? &cam : nullptr); \
     if (so.keep) {                                                                                                     \
       valid = true;                                                                                                    \
       o = so.n_o;                                                                                                      \
       d = so.n_d;                                                                                                      \
       attn = so.n_attn;                                                                                                \
       emit = so.n_emit;                                                                                                \
-      if (!CAM_CARRY) {                                                                                                \
+      if (!PRIMARY) { /* (the camera launch holds them since the sample was decoded) */                               \
         id = so.id;                                                                                                    \
         offset = so.offset;                                                                                            \
       }                                                                                                                \
     }                                                                                                                  \
   }
-      constexpr bool CAM_CARRY = PRIMARY && PT_CAMERA_CARRY != 0;
       PT_CARRY_STEP(PT_CAT_MISS, PT_SLOT_HOLE)
       PT_CARRY_STEP(PT_CAT_LAMBERT_SOLID, sl)
       PT_CARRY_STEP(PT_CAT_LAMBERT_CHECKER, sl)
       PT_CARRY_STEP(PT_CAT_METAL, sl)
       PT_CARRY_STEP(PT_CAT_DIELECTRIC, sl)
 #undef PT_CARRY_STEP
-      if (CAM_CARRY && !valid) { /* no ray to walk: the lane's registers as every other turn leaves them */
+      if (PRIMARY && !valid) { /* no ray to walk: the lane's registers as every other turn leaves them */
         o = v3(0.0, 0.0, 0.0);
         d = v3(0.0, 0.0, -1.0);
       }
-      PT_TM8(c_prims);
+      clk.tick(c_prims);
       if (last_bounce || __ballot(valid) == 0ull) continue; /* nothing survives the step */
       if (COUNT && !DIAG_T && valid) c_seg++;
     }
@@ -3554,7 +3548,7 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
     tc.resume = resume && valid;
     tc.unfinished = false;
     const PtTraceResult r = pt_trace_ray<MODE, COUNT, false, StackT, true, true, !COUNT && MODE == PT_MODE_SIMD>(sc, sv, stack, o, d, DIAG_T ? dg_n : c_nodes, DIAG_T ? dg_p : c_prims, DIAG_T ? dg_f : c_floor, valid, TAIL ? &tc : nullptr, DIAG_T ? nullptr : c_filter);
-    PT_TM8(c_floor);
+    clk.tick(c_floor);
     const bool park = TAIL && tc.unfinished;
     const bool done = valid && !park;
     const int cat = !done ? PT_CAT_NONE : (r.slot < 0 ? PT_CAT_MISS : (int)sv.cat[r.slot]);
@@ -3576,63 +3570,34 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_bounce_c
     if (TAIL) {
       const unsigned long long pm = __ballot(park);
       if (pm != 0) {
-        pt_lds_lock(&lds_park_lock);
-        const uint32_t base = __hip_atomic_load(&lds_park_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t base = pt_park_put_begin(&lds_park_n, &lds_park_lock);
         if (park) {
           uint4* p = park0 + base + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull));
-          p[0] = make_uint4(tc.node | ((uint32_t)(r.slot < 0 ? 0xffff : r.slot) << 16), (uint32_t)offset,
-                            (uint32_t)__double2loint(r.t), (uint32_t)__double2hiint(r.t));
-          p[park_cap] = make_uint4((uint32_t)__double2loint(o.x), (uint32_t)__double2hiint(o.x), (uint32_t)__double2loint(o.y), (uint32_t)__double2hiint(o.y));
-          p[2u * park_cap] = make_uint4((uint32_t)__double2loint(o.z), (uint32_t)__double2hiint(o.z), (uint32_t)__double2loint(d.x), (uint32_t)__double2hiint(d.x));
-          p[3u * park_cap] = make_uint4((uint32_t)__double2loint(d.y), (uint32_t)__double2hiint(d.y), (uint32_t)__double2loint(d.z), (uint32_t)__double2hiint(d.z));
-          p[4u * park_cap] = make_uint4((uint32_t)__double2loint(attn.x), (uint32_t)__double2hiint(attn.x), (uint32_t)__double2loint(attn.y), (uint32_t)__double2hiint(attn.y));
-          p[5u * park_cap] = make_uint4((uint32_t)__double2loint(attn.z), (uint32_t)__double2hiint(attn.z), id, 0u);
+          p[0] = pt_pack_xy_t(pt_tail_node_slot(tc.node, r.slot), (uint32_t)offset, r.t);
+          p[park_cap] = pt_pack2(o.x, o.y);
+          p[2u * park_cap] = pt_pack2(o.z, d.x);
+          p[3u * park_cap] = pt_pack2(d.y, d.z);
+          p[4u * park_cap] = pt_pack2(attn.x, attn.y);
+          p[5u * park_cap] = pt_pack_t_xy(attn.z, id, 0u);
           if (EMIT) {
-            p[6u * park_cap] = make_uint4((uint32_t)__double2loint(emit.x), (uint32_t)__double2hiint(emit.x), (uint32_t)__double2loint(emit.y), (uint32_t)__double2hiint(emit.y));
-            p[7u * park_cap] = make_uint4((uint32_t)__double2loint(emit.z), (uint32_t)__double2hiint(emit.z), 0u, 0u);
+            p[6u * park_cap] = pt_pack2(emit.x, emit.y);
+            p[7u * park_cap] = pt_pack_t_xy(emit.z, 0u, 0u);
           }
-          if (TAIL_UV)
-            p[(EMIT ? 8u : 6u) * park_cap] = make_uint4((uint32_t)__double2loint(r.u), (uint32_t)__double2hiint(r.u), (uint32_t)__double2loint(r.v), (uint32_t)__double2hiint(r.v));
+          if (TAIL_UV) p[(EMIT ? 8u : 6u) * park_cap] = pt_pack2(r.u, r.v);
         }
-        if (lane == 0) __hip_atomic_store(&lds_park_n, base + (uint32_t)__popcll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pt_lds_unlock(&lds_park_lock);
+        pt_park_put_end(&lds_park_n, &lds_park_lock, base, pm);
       }
     }
   }
   if (DIAG_T) {
-    PT_TM8(c_filter[0]);
-    c_seg = (lane == 0) ? tm_last - tm_begin : 0ull;
+    clk.tick(c_filter[0]);
+    c_seg = (lane == 0) ? clk.life() : 0ull;
     if (lane != 0) c_nodes = c_prims = c_floor = c_filter[0] = 0ull; /* wave-uniform quantities: one lane's copy */
   }
-#undef PT_TM8
-  if (COUNT && !(PT_DIAG == 8 && !PRIMARY)) { /* (that diagnostic build measures the camera launch only) */
-    c_nodes = pt_wave_sum(c_nodes);
-    c_prims = pt_wave_sum(c_prims);
-    c_floor = pt_wave_sum(c_floor);
-    c_seg = pt_wave_sum(c_seg);
-    c_filter[0] = pt_wave_sum(c_filter[0]);
-    c_filter[1] = pt_wave_sum(c_filter[1]);
-    if (lane == 0) {
-      atomicAdd(&counters->nodes, c_nodes);
-      atomicAdd(&counters->prims, c_prims);
-      atomicAdd(&counters->floor, c_floor);
-      atomicAdd(&counters->segments, c_seg);
-      atomicAdd(&counters->undecided, c_filter[0]);
-      atomicAdd(&counters->fallback_steps, c_filter[1]);
-    }
-  }
+  if (COUNT && !(PT_DIAG == 8 && !PRIMARY)) /* (that diagnostic build measures the camera launch only) */
+    pt_counters_flush(counters, c_nodes, c_prims, c_floor, c_seg, c_filter);
   if (last_bounce) return;
-  /* the workgroup's last wave marks what is left of its blocks as holes */
-  uint32_t fin = 0u;
-  if (lane == 0) fin = __hip_atomic_fetch_add(&lds_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-  fin = (uint32_t)__builtin_amdgcn_readfirstlane((int)fin);
-  if (fin != (uint32_t)(nw - 1)) return;
-  for (int b = 0; b < PT_POOL_BINS; ++b) {
-    const uint32_t st = __hip_atomic_load(lds_out + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const uint32_t blk = st >> 12, pos = st & 0xfffu;
-    if (blk == PT_POOL_NO_BLOCK) continue;
-    for (uint32_t e = pos + (uint32_t)lane; e < (uint32_t)PT_POOL_BLOCK; e += PT_WAVE) hout.slot[(size_t)blk * PT_POOL_BLOCK + e] = PT_SLOT_HOLE;
-  }
+  pt_blocks_close(&lds_done, lds_out, nw, [&](size_t e) { hout.slot[e] = PT_SLOT_HOLE; }); /* (holes of a carried queue: in the slot array) */
 }
 
 /* ------------------------------------------------------------------ accumulate + film */
@@ -4192,8 +4157,8 @@ __global__ void k_load_rays(long long n, const double* __restrict__ o, const dou
  * TAIL: a chunk stops where k_bounce_carry's would (PtTailCtl, min_active = PT_TAIL_CUT) and the walks it cut short go in again, with
  * the finished lanes idle, until none is left.  In between a walk is what k_bounce_carry's parked record keeps of it (word 0 of the
  * entry, written after its walk and read back before it: the node in 16 bits, the slot in 16 with 0xffff for none; t, and u, v on
- * Array_leaf scenes, as they are) -- restated below, the kernel's own pool, lock and ray words are not needed for 64 lanes that
- * keep their rays in registers. */
+ * Array_leaf scenes, as they are) -- through the kernel's own pair (pt_tail_node_slot); its pool, lock and ray words are not needed
+ * for 64 lanes that keep their rays in registers. */
 template <int MODE, bool PACKET, bool LOCT, bool ZERO, bool TAIL>
 __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_walk_eval(PtSceneDev sc, long long n, const double* __restrict__ o3,
                                                                                     const double* __restrict__ d3, double* __restrict__ t_out,
@@ -4239,10 +4204,10 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_walk_eva
           r = rr;
           todo = false;
         }
-        if (todo) { /* k_bounce_carry: p[0] = {tc.node | slot << 16, .., t} when it parks, h.x & 0xffff / h.x >> 16 when it takes the walk up again */
-          const uint32_t w = tc.node | ((uint32_t)(rr.slot < 0 ? 0xffff : rr.slot) << 16);
-          tc.node = w & 0xffffu;
-          tc.slot = (int)(w >> 16) == 0xffff ? -1 : (int)(w >> 16);
+        if (todo) { /* through the parked record's packed word, as k_bounce_carry parks a walk and takes it up again */
+          const uint32_t w = pt_tail_node_slot(tc.node, rr.slot);
+          tc.node = pt_tail_node_of(w);
+          tc.slot = pt_tail_slot_of(w);
           tc.t = rr.t;
           tc.u = MODE == PT_MODE_ARRAY ? rr.u : 0.0; /* (park_uv: Array_leaf scenes only) */
           tc.v = MODE == PT_MODE_ARRAY ? rr.v : 0.0;

@@ -1,4 +1,4 @@
-"""The camera launch of k_bounce_carry hands shade 0 its sample, its ray and its hit in registers (PT_CAMERA_CARRY, csrc/kernels.hip;
+"""The camera launch of k_bounce_carry hands shade 0 its sample, its ray and its hit in registers (PtCameraCarry, csrc/kernels.hip;
 DESIGN.md section 4): the lane that generated and walked a camera ray shades it, category step by category step, on the decoded sample
 (path id, sampler offset), the direction and the hit distance it still holds, instead of storing the distance, fencing, and decoding,
 deriving and loading all three again in every step.  The values are the same, so raw per-pixel sums equal the CPU oracle's bit for bit on
