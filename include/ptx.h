@@ -647,7 +647,8 @@ typedef struct ptx_image { /* 24 bytes */
   const double* rgb; /* width * height * 3; NULL in what the getters return */
 } ptx_image;
 /* From now on every material that points at entry texture_index of the scene's texture table evaluates the image (an entry declared
- * solid included); NULL restores the descriptor's texture. */
+ * solid included); NULL restores the descriptor's texture.  A texture_index the scene's texture table does not have is PTX_ERR_ARG
+ * ("texture index ... out of range ..."), from the setter and from the getter alike, and changes nothing. */
 int32_t ptx_scene_set_texture_image(ptx_scene* scene, int32_t texture_index, const ptx_image* image);
 /* NULL image restores the descriptor's background; NULL R is the identity; of the flags only PTX_IMAGE_BILINEAR is accepted. */
 int32_t ptx_scene_set_environment(ptx_scene* scene, const ptx_image* image, const double R[9]);
@@ -674,8 +675,9 @@ int32_t ptx_environment_eval(ptx_scene* scene, int64_t n, const double* dirs, do
  * While it is on: ptx_scene_set_lighting(PTX_LIGHTING_SAMPLED) also accepts a scene without emissive tree triangles (the light half is
  * then the environment alone); ptx_scene_set_environment with a new image or R rebuilds the density, and refuses (the old state kept)
  * an image or R that fails the conditions above; clearing the environment (NULL) is PTX_ERR_STATE, "turn environment sampling off
- * first"; turning sampling off while the mode is PTX_LIGHTING_SAMPLED and the light list is empty is PTX_ERR_STATE likewise ("set another
- * lighting mode first").  In modes 0 and 1 the flag has no effect on a pixel.
+ * first"; turning sampling off while the mode is PTX_LIGHTING_SAMPLED and nothing else is left to sample -- the light list is empty and
+ * sphere light sampling (below) is off -- is PTX_ERR_STATE likewise ("set another lighting mode first"); with sphere light sampling on
+ * it is accepted, and the light half is then the sphere lights alone.  In modes 0 and 1 the flag has no effect on a pixel.
  *
  * The rule, operation for operation (binary64, no fma, no contraction; sin, cos, atan2, acos are pt_math.h's), W x H the image:
  *   The density (built on the host), texel (ix, iy) = (r, g, b):

@@ -132,8 +132,9 @@ CASES = _cases()
 
 
 # ------------------------------------------------------------------------------------------------ the scheduler, restated
-def expected(case):
-    """the names (ptx_kernel_table's) of the instantiations the case launches: make_schedule, run_bounces and the launch functions"""
+def expected(case, depth=DEPTH):
+    """the names (ptx_kernel_table's) of the instantiations the case launches at `depth` bounces: make_schedule, run_bounces and the
+    launch functions"""
     f, k = SCENES[case.scene], {key[4:]: v for key, v in case.knobs}
     simd, lds = f["mode"] == "simd", f["lds"]
     has_emit = f["emit"] or (case.light == 2 and case.sampling)  # apply_lighting: a sampled environment is an emitter
@@ -154,8 +155,8 @@ def expected(case):
     for count in case.counts:
         cnt = "count" if count else "nocount"
         for camera in ((False,) if queued_camera else (True, False)):  # render_raw_device, then trace_samples
-            carry = camera and carry_ok and fused
-            for b in range(DEPTH):
+            carry = camera and carry_ok and fused and depth >= 2  # run_bounces: the shade-first order needs a bounce to carry into
+            for b in range(depth):
                 primary = camera and b == 0
                 prim = "camera" if primary else "queued"
                 if carry:
