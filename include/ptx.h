@@ -120,7 +120,11 @@ typedef struct ptx_scene_desc {
   int32_t leaf_kind;
   int32_t length_cutoff; /* 16 for SIMD (lib.rs:13), 4 / 2 / 8 for the array leaves */
   int32_t num_bins;      /* 0 -> 32 */
-  int32_t reserved;      /* BVH builder: 0 auto (GPU for >= 4096 primitives, else host), 1 host, 2 GPU -- same tree */
+  int32_t reserved;      /* BVH builder: 0 auto (GPU for >= 4096 primitives, else host), 1 host, 2 GPU -- same tree.
+                          * The GPU builder takes at most 64 bins and no primitive boxes of which one bound (min x .. max z)
+                          * is +0.0 in one box and -0.0 in another: there the reference's result depends on the order of
+                          * the primitives.  0 builds such scenes on the host; 2 fails with PTX_ERR_ARG, as it does on a
+                          * host-only scene. */
 } ptx_scene_desc;
 
 /* ---- render parameters: Render_command.Args.t (render_command.ml:7-14) ---- */

@@ -5,8 +5,13 @@
  * Every pending node ("segment" = a slice order[lo, hi) plus its bbox) of the current level goes through
  *   1. Bshape.centroid_bbox: min/max of the centroids;
  *   2. Proposal.propose_split_one_axis for X, Y, Z: bins kept as order-preserving u64 images of the f64 bounds
- *      (integer atomic min/max -- exact and order-independent), then one thread per axis builds the prefix boxes
- *      and evaluates the candidate costs with the reference's arithmetic and tie rules (List.min_elt = first
+ *      (integer atomic min/max -- exact and order-independent, with ONE exception: the images order -0.0 below
+ *      +0.0, while the reference's Float.min / Float.max keep the second of two equal arguments, so among zeros of
+ *      both signs ITS result depends on the slice order and no order-independent reduction can follow it.  The
+ *      prefix and suffix unions below have the same limit: on a tie they keep `mine`, the reference the neighbour.
+ *      bvh_build_gpu (ptx_api.inc) therefore refuses boxes of which one bound column holds both zeros; the photon
+ *      map's device-resident boxes are not checked, see DESIGN F3), then one thread per axis builds the prefix
+ *      boxes and evaluates the candidate costs with the reference's arithmetic and tie rules (List.min_elt = first
  *      minimum of a consed list);
  *   3. the leaf test of Tree.create;
  *   4. Slice.partition_in_place, reproduced exactly: the Hoare scan swaps the q-th misplaced element from the
@@ -908,7 +913,9 @@ __global__ void k_fin_emit(const BvhTmpNode* __restrict__ nodes, const BvhFin* _
   out_nodes[f.index] = nd;
 }
 
-/* Tree root box (shape_tree.ml:257-260): union of all element boxes -- min/max are exact, any order */
+/* Tree root box (shape_tree.ml:257-260): union of all element boxes -- min/max are exact in any order, except that a
+ * bound that is +0.0 in one box and -0.0 in another comes out as -0.0 (minima) / +0.0 (maxima) here and as the LAST
+ * of them in the reference (see the head of this file).  Only the photon map comes this way. */
 __global__ __launch_bounds__(BVH_BLOCK) void k_bvh_root_box(const double* __restrict__ prim_box, int n,
                                                             unsigned long long* __restrict__ enc /* 6, initialised */) {
   unsigned long long mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0ull, 0ull, 0ull};

@@ -1684,18 +1684,31 @@ bool bvh_build_device(const double* d_boxes, int n, const Box* root, int num_bin
   return true;
 }
 
-/* host boxes in, host BvhResult out (scene creation) */
-bool bvh_build_gpu(const std::vector<Box>& boxes, int num_bins, int length_cutoff, bool pad4, BvhResult* out) {
+/* host boxes in, host BvhResult out (scene creation).
+ * The kernels reduce bounds as integers, where -0.0 < +0.0; the host builder's box_union keeps whichever of two equal
+ * bounds Float.min / Float.max meet second, so among zeros of both signs its result depends on the slice order.  One
+ * of the six bound columns holding both zeros is therefore refused before the device is touched (*mixed_zeros says so)
+ * and the caller builds on the host; with one kind of zero per column every order gives the same bits. */
+bool bvh_build_gpu(const std::vector<Box>& boxes, int num_bins, int length_cutoff, bool pad4, BvhResult* out, bool* mixed_zeros = nullptr) {
   const int n = (int)boxes.size();
+  if (mixed_zeros) *mixed_zeros = false;
   if (n == 0 || num_bins > BVH_MAX_BINS) return false;
   std::vector<double> flat((size_t)n * 6);
   Box root = boxes[0];
+  unsigned zeros[6] = {0, 0, 0, 0, 0, 0}; /* per bound column: bit 0 = holds a +0.0, bit 1 = holds a -0.0 */
   for (int i = 0; i < n; ++i) {
     const Box& b = boxes[(size_t)i];
     double* f = &flat[(size_t)i * 6];
     f[0] = b.mn.x; f[1] = b.mn.y; f[2] = b.mn.z; f[3] = b.mx.x; f[4] = b.mx.y; f[5] = b.mx.z;
+    for (int k = 0; k < 6; ++k)
+      if (f[k] == 0.0) zeros[k] |= std::signbit(f[k]) ? 2u : 1u;
     if (i) root = box_union(root, b); /* shape_tree.ml:257-260 */
   }
+  for (int k = 0; k < 6; ++k)
+    if (zeros[k] == 3u) {
+      if (mixed_zeros) *mixed_zeros = true;
+      return false;
+    }
   BvhGpuWorkspace& ws = bvh_gpu_workspace();
   if (ws.d_box.ensure(flat.size()) != hipSuccess) return false;
   if (hipMemcpy(ws.d_box.p, flat.data(), sizeof(double) * flat.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
@@ -1911,7 +1924,11 @@ static int scene_build(ptx_scene* s, const ptx_scene_desc* d) {
   const bool want_gpu = s->device >= 0 && (d->reserved == 2 || (d->reserved == 0 && n >= 4096)) && num_bins <= BVH_MAX_BINS;
   if (d->reserved == 2 && !want_gpu) return fail(PTX_ERR_ARG, "GPU BVH build requested but unavailable (host-only scene or num_bins > %d)", BVH_MAX_BINS);
   if (want_gpu) {
-    built = bvh_build_gpu(boxes, num_bins, d->length_cutoff, simd, &tree);
+    bool mixed_zeros = false;
+    built = bvh_build_gpu(boxes, num_bins, d->length_cutoff, simd, &tree, &mixed_zeros);
+    if (mixed_zeros && d->reserved == 2)
+      return fail(PTX_ERR_ARG, "GPU BVH build requested but unavailable (a bound of the primitives' boxes is +0.0 and -0.0 among them: "
+                               "the host builder's result depends on their order)");
     if (!built && d->reserved == 2) return fail(PTX_ERR_HIP, "GPU BVH build failed: %s", hipGetErrorString(hipGetLastError()));
   }
   if (!built) tree = bvh_build(boxes, num_bins, d->length_cutoff, simd);
