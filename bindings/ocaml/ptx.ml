@@ -813,3 +813,196 @@ let ppm_render scene ~width ~height ~iterations ~max_bounces ~photon_count ~alph
   ppm_render_flat scene params (FA.of_list rows) img_sum (fun iteration radius photon_map_length ->
     on_iteration ~iteration ~radius ~photon_map_length)
 ;;
+
+(* Display outputs (ptx_render_display / ptx_render_progressive_display; the rule is in include/ptx.h): the image as 8-bit or
+   binary32 pixels in the format, transfer, tone curve and exposure the caller names, converted on the device and copied as what it
+   is.  [Reference] is the conversion Render_command.run's PNG gets (it needs [No_tone] and exposure 1); [Linear] and [Srgb] take the
+   square of the image times [exposure] through the tone curve; the binary32 formats refuse [Srgb].  The library's refusals surface
+   as Failure with the rule in the message. *)
+type pixel_format =
+  | Rgb8
+  | Rgba8
+  | Rgb32f
+  | Rgba32f
+
+type transfer =
+  | Reference
+  | Linear
+  | Srgb
+
+type tone =
+  | No_tone
+  | Reinhard
+  | Aces
+
+type display =
+  { format : pixel_format
+  ; transfer : transfer
+  ; tone : tone
+  ; exposure : float
+  }
+
+(* the display image: width * height * 3 or 4 elements, row 0 on top *)
+type pixels =
+  | Bytes of (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Bigarray.Array1.t
+  | Floats of (float, Bigarray.float32_elt, Bigarray.c_layout) Bigarray.Array1.t
+
+external display_defaults_flat : unit -> int * int * int * float = "ptx_ml_display_defaults_stub"
+
+(* one C stub behind two element types: the wrappers below pick the external that fits the format *)
+external render_display_u8
+  :  scene
+  -> floatarray (* width, height, samples_per_pixel, max_bounces, gpus, format, transfer, tone, exposure *)
+  -> (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (int -> unit)
+  -> unit
+  = "ptx_ml_render_display_stub"
+
+external render_display_f32
+  :  scene
+  -> floatarray
+  -> (float, Bigarray.float32_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (int -> unit)
+  -> unit
+  = "ptx_ml_render_display_stub"
+
+external render_progressive_display_u8
+  :  scene
+  -> floatarray (* the 18 floats of ptx_ml_render_progressive_display *)
+  -> (int, Bigarray.int8_unsigned_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t (* per-pixel error, W*H*3, or empty *)
+  -> (int -> float -> bool -> bool)
+  -> int
+  = "ptx_ml_render_progressive_display_stub"
+
+external render_progressive_display_f32
+  :  scene
+  -> floatarray
+  -> (float, Bigarray.float32_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> (int -> float -> bool -> bool)
+  -> int
+  = "ptx_ml_render_progressive_display_stub"
+
+let pixel_format_code = function
+  | Rgb8 -> 0
+  | Rgba8 -> 1
+  | Rgb32f -> 2
+  | Rgba32f -> 3
+;;
+
+let transfer_code = function
+  | Reference -> 0
+  | Linear -> 1
+  | Srgb -> 2
+;;
+
+let tone_code = function
+  | No_tone -> 0
+  | Reinhard -> 1
+  | Aces -> 2
+;;
+
+let pixel_channels = function
+  | Rgb8 | Rgb32f -> 3
+  | Rgba8 | Rgba32f -> 4
+;;
+
+(* ptx_display_defaults: Rgb8, Reference, No_tone, exposure 1 *)
+let display_defaults () =
+  let format, transfer, tone, exposure = display_defaults_flat () in
+  { format = (match format with 1 -> Rgba8 | 2 -> Rgb32f | 3 -> Rgba32f | _ -> Rgb8)
+  ; transfer = (match transfer with 1 -> Linear | 2 -> Srgb | _ -> Reference)
+  ; tone = (match tone with 1 -> Reinhard | 2 -> Aces | _ -> No_tone)
+  ; exposure
+  }
+;;
+
+let display_floats d =
+  [ Float.of_int (pixel_format_code d.format)
+  ; Float.of_int (transfer_code d.transfer)
+  ; Float.of_int (tone_code d.tone)
+  ; d.exposure
+  ]
+;;
+
+(* a fresh display image for a width x height frame in [format] *)
+let create_pixels format ~width ~height =
+  let n = width * height * pixel_channels format in
+  match format with
+  | Rgb8 | Rgba8 -> Bytes (Bigarray.Array1.create Bigarray.int8_unsigned Bigarray.c_layout n)
+  | Rgb32f | Rgba32f -> Floats (Bigarray.Array1.create Bigarray.float32 Bigarray.c_layout n)
+;;
+
+(* [render] whose image comes back as display pixels: bit for bit the display of the image [render] gives *)
+let render_display ?(gpus = 1) ?display scene ~width ~height ~samples_per_pixel ~max_bounces ~update_progress =
+  let display = match display with Some d -> d | None -> display_defaults () in
+  let params =
+    FA.of_list
+      ([ Float.of_int width
+       ; Float.of_int height
+       ; Float.of_int samples_per_pixel
+       ; Float.of_int max_bounces
+       ; Float.of_int gpus
+       ]
+       @ display_floats display)
+  in
+  let pixels = create_pixels display.format ~width ~height in
+  (match pixels with
+   | Bytes b -> render_display_u8 scene params b update_progress
+   | Floats f -> render_display_f32 scene params f update_progress);
+  pixels
+;;
+
+(* [render_progressive] -- with [denoise], [render_denoised] with its settings -- whose updates are display pixels: [pixels]
+   (from [create_pixels], the display's format) holds the update's display image when [on_update] runs, [err] (if given) its f64
+   per-pixel standard error.  The result is the number of passes in [pixels]. *)
+let render_progressive_display
+  ?(target_rel_err = 0.)
+  ?(denoise = false)
+  ?(levels = 5)
+  ?(normal_power_log2 = 5)
+  ?(feature_passes = 8)
+  ?(demodulate = true)
+  ?(sigma_luminance = 4.)
+  ?(sigma_depth = 0.05)
+  ?(sigma_albedo = 0.2)
+  ?display
+  ?err
+  scene
+  ~width
+  ~height
+  ~samples_per_pixel
+  ~max_bounces
+  ~passes_per_update
+  ~pixels
+  ~on_update
+  =
+  let display = match display with Some d -> d | None -> display_defaults () in
+  let err = Option.value err ~default:(Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 0) in
+  let params =
+    FA.of_list
+      ([ Float.of_int width
+       ; Float.of_int height
+       ; Float.of_int samples_per_pixel
+       ; Float.of_int max_bounces
+       ; Float.of_int passes_per_update
+       ; target_rel_err
+       ]
+       @ display_floats display
+       @ [ (if denoise then 1. else 0.)
+         ; Float.of_int levels
+         ; Float.of_int normal_power_log2
+         ; Float.of_int feature_passes
+         ; (if demodulate then 1. else 0.)
+         ; sigma_luminance
+         ; sigma_depth
+         ; sigma_albedo
+         ])
+  in
+  let callback passes_done rel_err last = on_update ~passes_done ~rel_err ~last in
+  match pixels, display.format with
+  | Bytes b, (Rgb8 | Rgba8) -> render_progressive_display_u8 scene params b err callback
+  | Floats f, (Rgb32f | Rgba32f) -> render_progressive_display_f32 scene params f err callback
+  | Bytes _, _ | Floats _, _ -> invalid_arg "Ptx.render_progressive_display: pixels do not have the display's element type"
+;;

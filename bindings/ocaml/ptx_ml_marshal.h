@@ -403,4 +403,94 @@ static __attribute__((unused)) int32_t ptx_ml_set_environment(ptx_scene* s, int3
   return ptx_scene_set_environment(s, &img, n_rot == 9 ? rot : NULL);
 }
 
+/* ---- display outputs (include/ptx.h, "display outputs") ----
+ * A display as OCaml hands it over: display4 = format, transfer, tone (the PTX_* values as floats), exposure; flags and the reserved
+ * words are 0.  The library's checks are the ones that refuse. */
+static __attribute__((unused)) void ptx_ml_display(const double* display4, ptx_display_params* out) {
+  memset(out, 0, sizeof *out);
+  out->format = (int32_t)display4[0];
+  out->transfer = (int32_t)display4[1];
+  out->tone = (int32_t)display4[2];
+  out->exposure = display4[3];
+}
+
+/* ptx_display_defaults as the four floats above */
+static __attribute__((unused)) int32_t ptx_ml_display_defaults(double* display4) {
+  ptx_display_params d;
+  const int32_t rc = ptx_display_defaults(&d);
+  if (rc != 0) return rc;
+  display4[0] = (double)d.format;
+  display4[1] = (double)d.transfer;
+  display4[2] = (double)d.tone;
+  display4[3] = d.exposure;
+  return 0;
+}
+
+/* the elements of a display image of `format` per pixel (3 or 4: bytes for the 8-bit formats, binary32 values for the others), and
+ * whether they are binary32; 0 for an unknown format */
+static __attribute__((unused)) int32_t ptx_ml_display_channels(int32_t format, int32_t* is_float) {
+  if (is_float) *is_float = format == PTX_PIXEL_RGB32F || format == PTX_PIXEL_RGBA32F;
+  if (format == PTX_PIXEL_RGB8 || format == PTX_PIXEL_RGB32F) return 3;
+  if (format == PTX_PIXEL_RGBA8 || format == PTX_PIXEL_RGBA32F) return 4;
+  return 0;
+}
+
+/* Integrator.render whose image comes back as display pixels (ptx_render_display): params9 = width, height, samples_per_pixel,
+ * max_bounces, gpus, then display4.  pixels: width * height * channels elements of the format.  -4: the image is too small. */
+static __attribute__((unused)) int32_t ptx_ml_render_display(ptx_scene* s, const double* params9, void* pixels, int64_t n_elements,
+                                                             ptx_progress_fn progress, void* user) {
+  if (!params9) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params9[0];
+  p.height = (int32_t)params9[1];
+  p.samples_per_pixel = (int32_t)params9[2];
+  p.max_bounces = (int32_t)params9[3];
+  p.n_gpus = (int32_t)params9[4];
+  ptx_display_params d;
+  ptx_ml_display(params9 + 5, &d);
+  const int32_t ch = ptx_ml_display_channels(d.format, NULL);
+  if (ch && p.width > 0 && p.height > 0 && n_elements < (int64_t)p.width * p.height * ch) return -4;
+  return ptx_render_display(s, &p, &d, pixels, NULL, progress, user);
+}
+
+/* ptx_render_progressive_display: params18 = width, height, samples_per_pixel, max_bounces, passes_per_update, target_rel_err, then
+ * display4, then denoise (0 = the plain updates of ptx_render_progressive) and the denoiser's levels, normal_power_log2,
+ * feature_passes, flags, sigma_luminance, sigma_depth, sigma_albedo (read only when denoise is not 0).  pixels holds the display
+ * image of the last update, err (nullable, W*H*3 doubles) its f64 per-pixel standard error, *passes_done its passes.  -4: the
+ * image is too small. */
+static __attribute__((unused)) int32_t ptx_ml_render_progressive_display(ptx_scene* s, const double* params18, void* pixels, int64_t n_elements,
+                                                                         double* err, int32_t* passes_done,
+                                                                         ptx_update_display_fn on_update, void* user) {
+  if (!params18) return -1;
+  ptx_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = (int32_t)params18[0];
+  p.height = (int32_t)params18[1];
+  p.samples_per_pixel = (int32_t)params18[2];
+  p.max_bounces = (int32_t)params18[3];
+  ptx_progressive_params pp;
+  memset(&pp, 0, sizeof pp);
+  pp.passes_per_update = (int32_t)params18[4];
+  pp.want_error = 1;
+  pp.target_rel_err = params18[5];
+  ptx_display_params d;
+  ptx_ml_display(params18 + 6, &d);
+  const int32_t ch = ptx_ml_display_channels(d.format, NULL);
+  if (ch && p.width > 0 && p.height > 0 && n_elements < (int64_t)p.width * p.height * ch) return -4;
+  ptx_denoise_params dn;
+  memset(&dn, 0, sizeof dn);
+  const int filter = params18[10] != 0.0;
+  if (filter) {
+    dn.levels = (int32_t)params18[11];
+    dn.normal_power_log2 = (int32_t)params18[12];
+    dn.feature_passes = (int32_t)params18[13];
+    dn.flags = (int32_t)params18[14];
+    dn.sigma_luminance = params18[15];
+    dn.sigma_depth = params18[16];
+    dn.sigma_albedo = params18[17];
+  }
+  return ptx_render_progressive_display(s, &p, &pp, filter ? &dn : NULL, &d, pixels, err, passes_done, NULL, on_update, user);
+}
+
 #endif /* PTX_ML_MARSHAL_H */

@@ -919,3 +919,95 @@ CAMLprim value ptx_ml_temporal_reset_stub(value handle) {
   if (rc != 0) caml_failwith(ptx_last_error());
   CAMLreturn(Val_unit);
 }
+
+/* ---- display outputs (include/ptx.h, "display outputs") ---- */
+
+/* external display_defaults_flat : unit -> int * int * int * float = "ptx_ml_display_defaults_stub" (ptx_display_defaults, host only):
+ * format, transfer, tone as the PTX_* values, exposure */
+CAMLprim value ptx_ml_display_defaults_stub(value unit) {
+  CAMLparam1(unit);
+  CAMLlocal2(tuple, boxed);
+  double d4[4];
+  if (ptx_ml_display_defaults(d4) != 0) caml_failwith(ptx_last_error());
+  boxed = caml_copy_double(d4[3]);
+  tuple = caml_alloc_tuple(4);
+  Store_field(tuple, 0, Val_long((intnat)d4[0]));
+  Store_field(tuple, 1, Val_long((intnat)d4[1]));
+  Store_field(tuple, 2, Val_long((intnat)d4[2]));
+  Store_field(tuple, 3, boxed);
+  CAMLreturn(tuple);
+}
+
+/* external render_display_u8 / render_display_f32 : scene -> floatarray -> pixels -> (int -> unit) -> unit = "ptx_ml_render_display_stub"
+ * (scene, [width; height; samples_per_pixel; max_bounces; gpus; format; transfer; tone; exposure], the display image as an
+ * int8_unsigned or float32 Bigarray of W*H*channels -- the OCaml side picks the external whose element type fits the format --
+ * update_progress) */
+CAMLprim value ptx_ml_render_display_stub(value handle, value params, value pixels, value update_progress) {
+  CAMLparam4(handle, params, pixels, update_progress);
+  CAMLlocal1(exn);
+  if (floatarray_length(params) != 9) caml_invalid_argument("Ptx.render_display: params needs 9 floats");
+  double p9[9];
+  memcpy(p9, floatarray_data(params), sizeof p9);
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_display: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_display: scene already destroyed");
+  void* out = Caml_ba_data_val(pixels); /* Bigarray data lives outside the OCaml heap: stable while the lock is released */
+  const int64_t n = (int64_t)Caml_ba_array_val(pixels)->dim[0];
+  exn = Val_unit;
+  ptx_ml_cb cb = {&update_progress, &exn, 0};
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_display(s, p9, out, n, ptx_ml_progress, &cb);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (cb.raised) caml_raise(exn);
+  if (rc == -4) caml_invalid_argument("Ptx.render_display: pixels must hold width * height * channels elements");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* ptx_ml_on_update for updates that arrive as display pixels: the library has already filled the caller's Bigarrays when it calls */
+static int32_t ptx_ml_on_update_display(void* user, int32_t passes_done, double rel_err, const void* pixels, const double* err) {
+  ptx_ml_update_cb* u = (ptx_ml_update_cb*)user;
+  (void)pixels;
+  (void)err;
+  if (u->cb.raised) return 1;
+  caml_acquire_runtime_system(); /* the render runs with the lock released */
+  ptx_ml_call_on_update(u, passes_done, rel_err);
+  caml_release_runtime_system();
+  return (u->cb.raised || u->stop) ? 1 : 0; /* a raise stops the render: no callbacks after it */
+}
+
+/* external render_progressive_display_u8 / _f32 : scene -> floatarray -> pixels -> err -> (int -> float -> bool -> bool) -> int
+ *   = "ptx_ml_render_progressive_display_stub"
+ * (scene, the 18 floats of ptx_ml_render_progressive_display, the display image, err (W*H*3 float64 or empty),
+ * on_update passes_done rel_err last -> stop) -> passes done */
+CAMLprim value ptx_ml_render_progressive_display_stub(value handle, value params, value pixels, value err, value on_update) {
+  CAMLparam5(handle, params, pixels, err, on_update);
+  CAMLlocal1(exn);
+  if (floatarray_length(params) != 18) caml_invalid_argument("Ptx.render_progressive_display: params needs 18 floats");
+  double p18[18];
+  memcpy(p18, floatarray_data(params), sizeof p18);
+  const intnat w = (intnat)p18[0], h = (intnat)p18[1];
+  const intnat n_err = Caml_ba_array_val(err)->dim[0];
+  if (n_err != 0 && (w <= 0 || h <= 0 || n_err != w * h * 3))
+    caml_invalid_argument("Ptx.render_progressive_display: err must be empty or hold width * height * 3 floats");
+  int busy = 0;
+  ptx_scene* s = ptx_ml_scene_acquire(handle, &busy);
+  if (!s && busy) caml_failwith("Ptx.render_progressive_display: the scene's image is being pinned or unpinned on another thread");
+  if (!s) caml_invalid_argument("Ptx.render_progressive_display: scene already destroyed");
+  void* out = Caml_ba_data_val(pixels);
+  const int64_t n = (int64_t)Caml_ba_array_val(pixels)->dim[0];
+  double* err_out = n_err ? (double*)Caml_ba_data_val(err) : NULL;
+  exn = Val_unit;
+  ptx_ml_update_cb cb = {{&on_update, &exn, 0}, (int32_t)p18[2], 0};
+  int32_t passes_done = 0;
+  caml_release_runtime_system();
+  const int32_t rc = ptx_ml_render_progressive_display(s, p18, out, n, err_out, &passes_done, ptx_ml_on_update_display, &cb);
+  caml_acquire_runtime_system();
+  ptx_ml_scene_release(handle);
+  if (cb.cb.raised) caml_raise(exn);
+  if (rc == -4) caml_invalid_argument("Ptx.render_progressive_display: pixels must hold width * height * channels elements");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_long(passes_done));
+}

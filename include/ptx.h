@@ -1114,6 +1114,101 @@ int32_t ptx_render_rays_device(ptx_scene* scene, const ptx_rays_params* params, 
 int32_t ptx_render_rays(ptx_scene* scene, const ptx_rays_params* params, int64_t n, const double* origins, const double* directions,
                         const int32_t* offsets, double* sum_out, double* sq_out, ptx_stats* stats);
 
+/* ---- display outputs: 8-bit and binary32 framebuffers, exposure, tone curves ----
+ * Every image above is binary64, sqrt-encoded and unclamped: 24 bytes a pixel, of which a PNG, a display or an encoder wants 3, 4,
+ * 12 or 16.  The display is a function of THE IMAGE ptx_render RETURNS: per channel it takes the binary64 value v of the filmed,
+ * sqrt-encoded image, so "the display of the f64 image" (ptx_display_apply on the host, ptx_display_image_device on a device) and
+ * "the display entry point" (ptx_render_display, ptx_render_progressive_display) are the same bits for every setting.  Only entry
+ * points, one struct and one callback type are added: no existing struct, kernel or call changes, the ABI version stays 6.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction), for one channel value v:
+ *   Stage A, the value t
+ *     REFERENCE:         t = v                               (needs tone == NONE and exposure == 1.0)
+ *     LINEAR and SRGB:   L = (v * v) * exposure;  L = (L > 0x1p40) ? 0x1p40 : L      (a NaN stays a NaN; the cap keeps inf / inf
+ *                                                                                     out of the curves)
+ *       NONE:            t = L
+ *       REINHARD:        t = L / (1.0 + L)
+ *       ACES:            t = (L * ((2.51 * L) + 0.03)) / ((L * ((2.43 * L) + 0.59)) + 0.14)      (the Narkowicz fit)
+ *   Stage B, the stored channel
+ *     8 bits, REFERENCE or LINEAR:   y = t * 255.0;  if (!(y > 0.0)) y = 0.0;  if (y > 255.0) y = 255.0;  code = (uint8_t)(int)y
+ *                                    -- the PNG writer's conversion, a truncation; NaN gives 0
+ *     8 bits, SRGB:                  code = the number of k in 1 .. 255 with T[k] <= t; NaN gives 0.  T[k] is the binary64 threshold
+ *                                    between codes k - 1 and k under round-to-nearest of the sRGB encoding:
+ *                                      e = (k - 0.5) / 255.0;  T[k] = e <= 0.04045 ? e / 12.92 : pow((e + 0.055) / 1.055, 2.4)
+ *                                    computed ONCE on the host with libm's pow, held by the library, copied to each device and handed
+ *                                    out by ptx_display_thresholds: host, device and any restatement search the same 255 doubles
+ *     binary32, REFERENCE or LINEAR: (float)t, round to nearest even, subnormal results included; no clamp, infinities and NaN pass
+ *     binary32 with SRGB:            refused: the binary32 formats carry linear or reference values
+ *   Alpha is 255 or 1.0f.  Every channel of a pixel goes through the same path.
+ *
+ * Refusals (ptx_display_check is what every entry point below applies, before anything is queued): PTX_ERR_ARG with a message that
+ * starts "display: " and names the rule for an unknown format, transfer or tone; non-zero flags or reserved words; an exposure that
+ * is not finite or is negative; REFERENCE with a tone other than NONE or an exposure other than 1.0; a binary32 format with SRGB.
+ *
+ * Out of scope: dithering, 16-bit PNG and half floats, a display transform inside the photon mappers, chromatic adaptation or
+ * colour spaces other than the scene's own RGB, a film kernel fused with the display. */
+#define PTX_PIXEL_RGB8 0    /* 3 bytes a pixel */
+#define PTX_PIXEL_RGBA8 1   /* 4 */
+#define PTX_PIXEL_RGB32F 2  /* 12 */
+#define PTX_PIXEL_RGBA32F 3 /* 16 */
+#define PTX_TRANSFER_REFERENCE 0
+#define PTX_TRANSFER_LINEAR 1
+#define PTX_TRANSFER_SRGB 2
+#define PTX_TONE_NONE 0
+#define PTX_TONE_REINHARD 1
+#define PTX_TONE_ACES 2
+typedef struct ptx_display_params { /* 40 bytes */
+  int32_t format;    /* PTX_PIXEL_* */
+  int32_t transfer;  /* PTX_TRANSFER_* */
+  int32_t tone;      /* PTX_TONE_* */
+  int32_t flags;     /* 0 */
+  double exposure;   /* multiplies linear radiance; finite, >= 0 */
+  int32_t reserved[4]; /* 0 */
+} ptx_display_params;
+/* RGB8, REFERENCE, NONE, exposure 1.0: the bytes the PNG writer makes of ptx_render's image */
+int32_t ptx_display_defaults(ptx_display_params* out);
+/* 0, or PTX_ERR_ARG with the rule in ptx_last_error().  Needs no device. */
+int32_t ptx_display_check(const ptx_display_params* display);
+/* bytes of one pixel of `format`, or PTX_ERR_ARG */
+int32_t ptx_display_pixel_bytes(int32_t format);
+/* out[k - 1] = T[k], k = 1 .. 255.  Needs no device. */
+int32_t ptx_display_thresholds(double out[255]);
+/* The rule on the host: n_pixels pixels of 3 doubles at rgb to n_pixels * ptx_display_pixel_bytes(format) bytes at out.  Needs no
+ * device.  n_pixels == 0 returns 0. */
+int32_t ptx_display_apply(const ptx_display_params* display, int64_t n_pixels, const double* rgb, void* out);
+/* The rule on a device, for any filmed f64 image there: the film's output, ptx_denoise_device's after the film, a frame of
+ * ptx_render_temporal.  d_rgb and d_out are DEVICE memory, both 16-byte aligned (any hipMalloc'ed buffer is) and not overlapping.
+ * Queued on `stream`; waits for it, like ptx_film_resolve_device.  PTX_ERR_STATE for device < 0 (the host has ptx_display_apply). */
+int32_t ptx_display_image_device(int32_t device, const ptx_display_params* display, int64_t n_pixels, const double* d_rgb,
+                                 void* d_out, void* stream);
+/* The same over pixels [pixel_first, pixel_first + n_pixels) of the two images, whose bases d_rgb and d_out stay the images' first
+ * pixels (aligned as above): the form ptx_render_display's row slabs take, a range that starts at row0 * width pixels.  Bytes of
+ * d_out outside the range are not written, whatever the range's alignment to the kernel's four-pixel quads -- two adjacent ranges
+ * never write the same byte.  ptx_display_image_device is the range [0, n_pixels). */
+int32_t ptx_display_range_device(int32_t device, const ptx_display_params* display, int64_t pixel_first, int64_t n_pixels,
+                                 const double* d_rgb, void* d_out, void* stream);
+/* The byte-typed twin of ptx_image_pin, for a display image: same contract, and still ONE pinned image per handle of either kind
+ * (pinning another releases the first); ptx_image_unpin releases either. */
+int32_t ptx_image_pin_bytes(ptx_scene* scene, void* image, int64_t n_bytes);
+/* ptx_render with `out` (HOST, width * height * ptx_display_pixel_bytes(format) bytes) in the named format: the film runs into the
+ * handle's f64 image as in ptx_render, the display kernel runs over it, and the display bytes are what is copied.  Into a pinned
+ * image (ptx_image_pin_bytes) the frame's tail is ptx_render's row-slab pipeline: per slab the film, the display kernel over the
+ * slab's rows, the copy of the slab's display bytes.  n_gpus > 1 renders as ptx_render_multi does and displays the image filmed on
+ * the first device.  out == display_apply(ptx_render's image), bit for bit.  A refused call leaves `out` untouched. */
+int32_t ptx_render_display(ptx_scene* scene, const ptx_render_params* params, const ptx_display_params* display, void* out,
+                           ptx_stats* stats, ptx_progress_fn progress, void* user);
+/* ptx_update_fn with the update's image as display pixels */
+typedef int32_t (*ptx_update_display_fn)(void* user, int32_t passes_done, double rel_err, const void* pixels, const double* err);
+/* ptx_render_progressive -- with `denoise` (nullable) ptx_render_denoised -- whose updates are display images: after every update's
+ * film the display kernel runs over the image, and the display bytes are what is copied into `out` and handed to the callback.  The
+ * error image (err_out, nullable, with denoise the un-denoised se) stays f64.  Everything else -- the checks, the slices, the early
+ * stop, the drain on every exit -- is the f64 entry point's.  Run to N passes with REFERENCE / RGB8, `out` is the display of
+ * ptx_render's image bit for bit. */
+int32_t ptx_render_progressive_display(ptx_scene* scene, const ptx_render_params* params, const ptx_progressive_params* progressive,
+                                       const ptx_denoise_params* denoise /* nullable */, const ptx_display_params* display, void* out,
+                                       double* err_out /* nullable */, int32_t* passes_done_out, ptx_stats* stats,
+                                       ptx_update_display_fn on_update, void* user);
+
 /* Per-sample radiance for explicit (x, y, pass) triples -- the value Integrator's
  * trace_path returns (integrator.ml:106).  Host in / host out, n*3 doubles.
  * Used by the parity tests (bit-exact against the oracle). */

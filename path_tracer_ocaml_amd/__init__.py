@@ -50,6 +50,8 @@ EXPORTS = (
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
     "ptx_render_rays_device", "ptx_render_rays", "ptx_scene_set_camera_projection", "ptx_scene_camera_projection",
     "ptx_kernel_table", "ptx_scene_launched_kernels", "ptx_scene_clear_launched_kernels",
+    "ptx_display_defaults", "ptx_display_check", "ptx_display_pixel_bytes", "ptx_display_thresholds", "ptx_display_apply",
+    "ptx_display_image_device", "ptx_display_range_device", "ptx_image_pin_bytes", "ptx_render_display", "ptx_render_progressive_display",
 )
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64)
@@ -192,6 +194,21 @@ def lib():
     if hasattr(L, "ptx_scene_set_camera_projection"):  # (likewise)
         L.ptx_scene_set_camera_projection.argtypes = [C.c_void_p, C.c_int32]
         L.ptx_scene_camera_projection.argtypes = [C.c_void_p]
+    if hasattr(L, "ptx_render_display"):  # (likewise)
+        dpp = C.POINTER(abi.DisplayParams)
+        L.ptx_display_defaults.argtypes = [dpp]
+        L.ptx_display_check.argtypes = [dpp]
+        L.ptx_display_pixel_bytes.argtypes = [C.c_int32]
+        L.ptx_display_thresholds.argtypes = [dp]
+        L.ptx_display_apply.argtypes = [dpp, C.c_int64, dp, C.c_void_p]
+        L.ptx_display_image_device.argtypes = [C.c_int32, dpp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptx_display_range_device.argtypes = [C.c_int32, dpp, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptx_image_pin_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.ptx_render_display.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), dpp, C.c_void_p, C.POINTER(abi.Stats), C.c_void_p,
+                                         C.c_void_p]
+        L.ptx_render_progressive_display.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.POINTER(abi.ProgressiveParams),
+                                                     C.POINTER(abi.DenoiseParams), dpp, C.c_void_p, dp, ip, C.POINTER(abi.Stats),
+                                                     C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 
@@ -555,6 +572,66 @@ class Scene:
         _check(lib().ptx_image_unpin(self._h))
         self._pinned_image = None
 
+    def image_pin_bytes(self, image):
+        """ptx_image_pin_bytes: pin_image for a display image (any C-contiguous uint8 or float32 array).  One pinned image per
+        scene, of either kind; unpin_image() releases it."""
+        if image.dtype not in (np.uint8, np.float32) or not image.flags["C_CONTIGUOUS"]:
+            raise ValueError("image must be a C-contiguous uint8 or float32 array")
+        _check(lib().ptx_image_pin_bytes(self._h, C.c_void_p(image.ctypes.data), image.nbytes))
+        self._pinned_image = image  # keeps it mapped while the registration exists
+
+    def render_display(self, width, height, samples_per_pixel, max_bounces, format="rgb8", transfer="reference", tone="none",
+                       exposure=1.0, progress=None, out=None, **kw):
+        """ptx_render_display: render() whose image comes back as display pixels -- a uint8 or float32 array of shape (H, W, 3 or
+        4), bit for bit display_apply(render()'s image) -- converted on the device and copied as what it is.  `out`: the caller's
+        array of that shape and dtype to fill.  Returns (pixels, stats)."""
+        d = abi.display_params(None, format, transfer, tone, exposure)
+        out = _display_arg(out, width, height, d.format, "out")
+        p = render_params(width, height, samples_per_pixel, max_bounces, **kw)
+        st = abi.Stats()
+        cb = PROGRESS_FN(lambda user, n: progress(n)) if progress else None
+        _check(lib().ptx_render_display(self._h, C.byref(p), C.byref(d), C.c_void_p(out.ctypes.data), C.byref(st),
+                                        C.cast(cb, C.c_void_p) if cb else None, None))
+        return out, stats_dict(st)
+
+    def render_progressive_display(self, width, height, samples_per_pixel, max_bounces, passes_per_update, denoise=None,
+                                   format="rgb8", transfer="reference", tone="none", exposure=1.0, on_update=None,
+                                   target_rel_err=0.0, want_error=True, out=None, err_out=None, **kw):
+        """ptx_render_progressive_display: render_progressive -- with `denoise` (True for the defaults, a dict or an
+        abi.DenoiseParams) render_denoised -- whose updates are display pixels.  on_update(passes_done, rel_err, pixels, err) sees
+        the (H, W, 3 or 4) display image of the update and the f64 per-pixel error (None without want_error).  Returns
+        (pixels, err, passes_done, stats)."""
+        d = abi.display_params(None, format, transfer, tone, exposure)
+        dn = None if denoise is None or denoise is False else denoise_params(None if denoise is True else denoise)
+        want_error = bool(want_error) or dn is not None
+        out = _display_arg(out, width, height, d.format, "out")
+        err_out = _image_arg(err_out, width, height, "err_out") if want_error else None
+        p = render_params(width, height, samples_per_pixel, max_bounces, **kw)
+        pp = abi.ProgressiveParams()
+        pp.passes_per_update, pp.want_error, pp.target_rel_err = int(passes_per_update), int(want_error), float(target_rel_err)
+        raised = []
+
+        def trampoline(user, passes_done, rel_err, pixels, err):
+            if raised:
+                return 1
+            try:
+                return 1 if on_update(passes_done, rel_err, out, err_out) else 0
+            except BaseException as e:  # noqa: BLE001 -- carried across the C frames, raised again below
+                raised.append(e)
+                return 1
+
+        cb = abi.UPDATE_DISPLAY_FN(trampoline) if on_update is not None else None
+        done = C.c_int32(0)
+        st = abi.Stats()
+        rc = lib().ptx_render_progressive_display(self._h, C.byref(p), C.byref(pp), C.byref(dn) if dn is not None else None,
+                                                  C.byref(d), C.c_void_p(out.ctypes.data),
+                                                  _dp(err_out) if err_out is not None else None, C.byref(done), C.byref(st),
+                                                  C.cast(cb, C.c_void_p) if cb else None, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return out, err_out, done.value, stats_dict(st)
+
     def render_raw_device(self, params, d_raw_ptr, stream=None):
         """ptx_render_raw_device: raw per-pixel sums for this rank's rows into DEVICE memory."""
         st = abi.Stats()
@@ -899,6 +976,64 @@ def _image_arg(a, width, height, name):
     if a.shape != (height, width, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
         raise ValueError(f"{name} must be a C-contiguous float64 array of shape (height, width, 3)")
     return a
+
+
+def _display_arg(a, width, height, fmt, name):
+    dtype, channels = abi.PTX_PIXEL_LAYOUT[fmt] if 0 <= fmt < len(abi.PTX_PIXEL_LAYOUT) else ("uint8", 3)  # (the library refuses it)
+    if a is None:
+        return np.zeros((height, width, channels), dtype=dtype)
+    if a.shape != (height, width, channels) or a.dtype != np.dtype(dtype) or not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{name} must be a C-contiguous {dtype} array of shape (height, width, {channels})")
+    return a
+
+
+def display_defaults():
+    """ptx_display_defaults: RGB8, the reference's transfer, no tone curve, exposure 1.0"""
+    d = abi.DisplayParams()
+    _check(lib().ptx_display_defaults(C.byref(d)))
+    return d
+
+
+def display_pixel_bytes(fmt):
+    """ptx_display_pixel_bytes: 3, 4, 12 or 16"""
+    n = lib().ptx_display_pixel_bytes(abi._named(fmt, abi.PTX_PIXEL_NAMES, "format"))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def display_thresholds():
+    """ptx_display_thresholds: the 255 sRGB thresholds the library searches, [k - 1] = T[k].  Needs no device."""
+    t = np.zeros(255)
+    _check(lib().ptx_display_thresholds(_dp(t)))
+    return t
+
+
+def display_apply(image, display=None, **fields):
+    """ptx_display_apply: the display rule on the host over a float64 array of shape (..., 3); returns the uint8 or float32 array
+    of shape (..., 3 or 4).  `display`: an abi.DisplayParams or None; fields: format=, transfer=, tone=, exposure= over it."""
+    d = abi.display_params(display, **fields)
+    a = np.ascontiguousarray(image, dtype=np.float64)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("image must have shape (..., 3)")
+    _check(lib().ptx_display_check(C.byref(d)))
+    dtype, channels = abi.PTX_PIXEL_LAYOUT[d.format]
+    out = np.zeros(a.shape[:-1] + (channels,), dtype=dtype)
+    _check(lib().ptx_display_apply(C.byref(d), a.size // 3, _dp(a), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def display_image_device(device, n_pixels, d_rgb_ptr, d_out_ptr, display=None, stream=None, pixel_first=0, **fields):
+    """ptx_display_image_device: the display rule over n_pixels pixels of a DEVICE f64 image (16-byte aligned) into DEVICE display
+    pixels (16-byte aligned); waits for `stream`.  With pixel_first, ptx_display_range_device: pixels [pixel_first, pixel_first +
+    n_pixels) of the two images, nothing outside them written."""
+    d = abi.display_params(display, **fields)
+    if pixel_first:
+        _check(lib().ptx_display_range_device(int(device), C.byref(d), int(pixel_first), int(n_pixels), C.c_void_p(d_rgb_ptr),
+                                              C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None))
+        return
+    _check(lib().ptx_display_image_device(int(device), C.byref(d), int(n_pixels), C.c_void_p(d_rgb_ptr), C.c_void_p(d_out_ptr),
+                                          C.c_void_p(stream) if stream else None))
 
 
 def pixel_error_device(device, width, rows, passes_done, d_raw_ptr, d_sq_ptr, d_err_ptr=None, stream=None):

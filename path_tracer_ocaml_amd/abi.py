@@ -185,6 +185,50 @@ def film_params(film=None, renormalise=None):
     return f
 
 
+# display outputs (include/ptx.h): the pixel formats with their numpy dtype and channels, the transfers, the tone curves
+PTX_PIXEL_RGB8, PTX_PIXEL_RGBA8, PTX_PIXEL_RGB32F, PTX_PIXEL_RGBA32F = range(4)
+PTX_PIXEL_NAMES = ("rgb8", "rgba8", "rgb32f", "rgba32f")
+PTX_PIXEL_LAYOUT = (("uint8", 3), ("uint8", 4), ("float32", 3), ("float32", 4))
+PTX_TRANSFER_REFERENCE, PTX_TRANSFER_LINEAR, PTX_TRANSFER_SRGB = range(3)
+PTX_TRANSFER_NAMES = ("reference", "linear", "srgb")
+PTX_TONE_NONE, PTX_TONE_REINHARD, PTX_TONE_ACES = range(3)
+PTX_TONE_NAMES = ("none", "reinhard", "aces")
+
+
+class DisplayParams(C.Structure):  # ptx_display_params, 40 bytes
+    _fields_ = [("format", C.c_int32), ("transfer", C.c_int32), ("tone", C.c_int32), ("flags", C.c_int32), ("exposure", C.c_double),
+                ("reserved", C.c_int32 * 4)]
+
+
+def _named(value, names, what):
+    if isinstance(value, str):
+        if value not in names:
+            raise ValueError(f"{what} must be one of {', '.join(names)} (got {value!r})")
+        return names.index(value)
+    return int(value)
+
+
+def display_params(display=None, format=None, transfer=None, tone=None, exposure=None):
+    """An abi.DisplayParams from None (RGB8, reference, no tone curve, exposure 1) or a DisplayParams, with the named fields set: each
+    a PTX_* value or its name in PTX_PIXEL_NAMES / PTX_TRANSFER_NAMES / PTX_TONE_NAMES.  Not checked here: the library's refusals
+    (PtxError, the rule in the message) are the ones to see."""
+    d = DisplayParams(PTX_PIXEL_RGB8, PTX_TRANSFER_REFERENCE, PTX_TONE_NONE, 0, 1.0)
+    if display is not None:
+        C.memmove(C.byref(d), C.byref(display), C.sizeof(d))
+    if format is not None:
+        d.format = _named(format, PTX_PIXEL_NAMES, "format")
+    if transfer is not None:
+        d.transfer = _named(transfer, PTX_TRANSFER_NAMES, "transfer")
+    if tone is not None:
+        d.tone = _named(tone, PTX_TONE_NAMES, "tone")
+    if exposure is not None:
+        d.exposure = float(exposure)
+    return d
+
+
+# ptx_update_display_fn: (user, passes_done, rel_err, pixels, err) -> non-zero stops the render
+UPDATE_DISPLAY_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p)
+
 PTX_IMAGE_BILINEAR, PTX_IMAGE_REPEAT_U, PTX_IMAGE_REPEAT_V = 1, 2, 4
 PTX_IMAGE_MAX_SIZE = 16384
 

@@ -4270,5 +4270,6 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "denoise.inc"
 #include "temporal.inc"
 #include "rays.inc"
+#include "display.inc"
 #include "ptx_api.inc"
 #endif

@@ -305,8 +305,12 @@ struct ptx_scene {
   size_t pinned_n = 0;
   hipStream_t copy_stream = nullptr;        /* ptx_render into a pinned image: film + copy of the row slabs */
   hipEvent_t ev_slab[8] = {};
-  double* reg_ptr = nullptr;                /* the caller's framebuffer while it is pinned (ptx_image_pin) */
-  size_t reg_n = 0;
+  char* reg_ptr = nullptr;                  /* the caller's framebuffer while it is pinned (ptx_image_pin, ptx_image_pin_bytes) */
+  size_t reg_bytes = 0;
+  bool holds_pinned(const void* ptr, size_t bytes) const {
+    return reg_ptr && (const char*)ptr >= reg_ptr && (const char*)ptr + bytes <= reg_ptr + reg_bytes;
+  }
+  DevBuf<uint8_t> disp;                     /* the display image of ptx_render_display / ptx_render_progressive_display (display.inc) */
   /* Lighting (ptx_scene_set_lighting): the mode asked for; the light table made of host->emissive_tris when mode 2 is first set
    * (PT_LIGHT_DOUBLES per record) and its device copy, which lives as long as the handle (queued frames keep reading it);
    * the number of calls that are rendering with this handle right now */
@@ -2001,20 +2005,25 @@ int32_t ptx_image_unpin(ptx_scene* s) {
     (void)hipHostUnregister(s->reg_ptr);
     (void)hipGetLastError();
     s->reg_ptr = nullptr;
-    s->reg_n = 0;
+    s->reg_bytes = 0;
   }
   return 0;
 }
 
-int32_t ptx_image_pin(ptx_scene* s, double* image, int64_t n_doubles) {
-  if (!s || !image || n_doubles <= 0) return fail(PTX_ERR_ARG, "NULL argument or empty image");
+int32_t ptx_image_pin_bytes(ptx_scene* s, void* image, int64_t n_bytes) {
+  if (!s || !image || n_bytes <= 0) return fail(PTX_ERR_ARG, "NULL argument or empty image");
   if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1)");
   (void)ptx_image_unpin(s);
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipHostRegister(image, sizeof(double) * (size_t)n_doubles, hipHostRegisterDefault));
-  s->reg_ptr = image;
-  s->reg_n = (size_t)n_doubles;
+  HIP_TRY(hipHostRegister(image, (size_t)n_bytes, hipHostRegisterDefault));
+  s->reg_ptr = (char*)image;
+  s->reg_bytes = (size_t)n_bytes;
   return 0;
+}
+
+int32_t ptx_image_pin(ptx_scene* s, double* image, int64_t n_doubles) {
+  if (n_doubles > (int64_t)(INT64_MAX / sizeof(double))) return fail(PTX_ERR_ARG, "n_doubles %lld is out of range", (long long)n_doubles);
+  return ptx_image_pin_bytes(s, image, n_doubles > 0 ? n_doubles * (int64_t)sizeof(double) : 0);
 }
 
 void ptx_scene_destroy(ptx_scene* s) {
@@ -2885,41 +2894,44 @@ int timed_film(const ptx_render_params& p, const double* d_raw, double* d_rgb, P
  * buffer with asynchronous DMA while a few host threads move finished chunks on to the caller's buffer: ~2 ms. */
 /* cs: the stream the copies are ordered on (NULL: the null stream, and the call waits for the whole device at the end);
  * ptx_render_progressive copies update j on its copy stream while the next slice is already queued on the others */
-int copy_to_host_on(hipStream_t cs, const double* d_src, double* dst, size_t n_doubles) {
+int copy_to_host_on(hipStream_t cs, const char* d_src, char* dst, size_t n_bytes) {
   if (!cs) {
-    HIP_TRY(hipMemcpy(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dst, d_src, n_bytes, hipMemcpyDeviceToHost));
     return 0;
   }
-  HIP_TRY(hipMemcpyAsync(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost, cs));
+  HIP_TRY(hipMemcpyAsync(dst, d_src, n_bytes, hipMemcpyDeviceToHost, cs));
   HIP_TRY(hipStreamSynchronize(cs));
   return 0;
 }
-int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n_doubles, hipStream_t cs = nullptr) {
-  if (env_int("PTX_PLAIN_D2H", 0) || n_doubles < (1u << 20)) return copy_to_host_on(cs, d_src, dst, n_doubles);
+/* (in bytes: an f64 image through framebuffer_to_host below, a display image as it is) */
+int image_bytes_to_host(ptx_scene* s, const char* d_src, char* dst, size_t n_bytes, hipStream_t cs = nullptr) {
+  if (env_int("PTX_PLAIN_D2H", 0) || n_bytes < ((size_t)8 << 20)) return copy_to_host_on(cs, d_src, dst, n_bytes);
   /* an image the caller has pinned (ptx_image_pin): one DMA straight into it */
-  if (s->reg_ptr && dst >= s->reg_ptr && dst + n_doubles <= s->reg_ptr + s->reg_n) {
-    HIP_TRY(hipMemcpyAsync(dst, d_src, sizeof(double) * n_doubles, hipMemcpyDeviceToHost, cs));
+  if (s->holds_pinned(dst, n_bytes)) {
+    HIP_TRY(hipMemcpyAsync(dst, d_src, n_bytes, hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipStreamSynchronize(cs));
     return 0;
   }
+  const size_t n_doubles = (n_bytes + sizeof(double) - 1) / sizeof(double); /* the staging buffer is counted in doubles */
   if (s->pinned_n < n_doubles) {
     if (s->pinned) (void)hipHostFree(s->pinned);
     s->pinned = nullptr;
     s->pinned_n = 0;
     if (hipHostMalloc((void**)&s->pinned, sizeof(double) * n_doubles, hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
-      return copy_to_host_on(cs, d_src, dst, n_doubles); /* no pinned memory to be had */
+      return copy_to_host_on(cs, d_src, dst, n_bytes); /* no pinned memory to be had */
     }
     s->pinned_n = n_doubles;
   }
-  const size_t chunk = (size_t)512 * 1024; /* doubles: 4 MB */
-  const size_t n_chunks = (n_doubles + chunk - 1) / chunk;
+  char* const stage = (char*)s->pinned;
+  const size_t chunk = (size_t)4 << 20; /* 4 MB */
+  const size_t n_chunks = (n_bytes + chunk - 1) / chunk;
   std::vector<hipEvent_t> done(n_chunks, nullptr);
   int rc = 0;
   for (size_t k = 0; k < n_chunks && rc == 0; ++k) {
-    const size_t off = k * chunk, len = std::min(chunk, n_doubles - off);
+    const size_t off = k * chunk, len = std::min(chunk, n_bytes - off);
     if (hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess ||
-        hipMemcpyAsync(s->pinned + off, d_src + off, sizeof(double) * len, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipMemcpyAsync(stage + off, d_src + off, len, hipMemcpyDeviceToHost, cs) != hipSuccess ||
         hipEventRecord(done[k], cs) != hipSuccess)
       rc = fail(PTX_ERR_HIP, "framebuffer copy failed: %s", hipGetErrorString(hipGetLastError()));
   }
@@ -2931,8 +2943,8 @@ int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n
       (void)hipSetDevice(dev);
       for (size_t k = (size_t)tid; k < n_chunks; k += (size_t)n_threads) {
         if (hipEventSynchronize(done[k]) != hipSuccess) { bad = 1; return; }
-        const size_t off = k * chunk, len = std::min(chunk, n_doubles - off);
-        std::memcpy(dst + off, s->pinned + off, sizeof(double) * len);
+        const size_t off = k * chunk, len = std::min(chunk, n_bytes - off);
+        std::memcpy(dst + off, stage + off, len);
       }
     };
     std::vector<std::thread> th;
@@ -2947,14 +2959,79 @@ int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n
     if (e) (void)hipEventDestroy(e);
   return rc;
 }
+int framebuffer_to_host(ptx_scene* s, const double* d_src, double* dst, size_t n_doubles, hipStream_t cs = nullptr) {
+  return image_bytes_to_host(s, (const char*)d_src, (char*)dst, sizeof(double) * n_doubles, cs);
+}
+
+/* ---- display outputs (display.inc; the rule: include/ptx.h) ---- */
+/* one display call as the render entry points carry it: the checked settings, the caller's image and its size */
+struct DisplayJob {
+  ptx_display_params d;
+  void* out;
+  size_t pixel_bytes;
+};
+
+int check_display(const ptx_display_params* d) {
+  if (!d) return fail(PTX_ERR_ARG, "display: NULL ptx_display_params");
+  std::string msg;
+  const int rc = display_check(d, &msg);
+  return rc ? fail(rc, "%s", msg.c_str()) : 0;
+}
+
+/* the sRGB thresholds on the current device: copied into the module's table the first time the device displays.  The flag is the
+ * process's, like the dynamic-LDS limits the handles remember: an embedding application that calls hipDeviceReset re-zeroes the
+ * module's table behind it (every sRGB code would then read 255) and has to restart the process, as it has to for every handle it
+ * made before the reset. */
+constexpr int kMaxDisplayDevices = 64;
+int display_thresholds_device() {
+  static std::mutex mu;
+  static bool done[kMaxDisplayDevices] = {};
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxDisplayDevices) return fail(PTX_ERR_ARG, "display: device %d is beyond the %d the threshold table is kept for", dev, kMaxDisplayDevices);
+  std::lock_guard<std::mutex> lock(mu);
+  if (done[dev]) return 0;
+  HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_display_thresholds), display_thresholds(), sizeof(double) * PT_DISPLAY_THRESHOLDS));
+  done[dev] = true;
+  return 0;
+}
+
+/* k_display_image over pixels [p0, p1) of the image at d_rgb into the display image at d_out, queued on st (the device is current
+ * and has its thresholds -- display_thresholds_device, a blocking copy, is called by every entry point before it queues anything --
+ * d has passed check_display, both images are 16-byte aligned) */
+int display_queue(const ptx_display_params& d, long long p0, long long p1, const double* d_rgb, void* d_out, hipStream_t st) {
+  if (p1 <= p0) return 0;
+  const long long quads = (p1 + 3) / 4 - p0 / 4;
+  const dim3 grid((unsigned)((quads + 255) / 256)), block(256);
+  const PtDisplay pd{d.transfer, d.tone, d.exposure};
+  switch (d.format) {
+    case PTX_PIXEL_RGB8: hipLaunchKernelGGL(k_display_image<PTX_PIXEL_RGB8>, grid, block, 0, st, d_rgb, p0, p1, pd, d_out); break;
+    case PTX_PIXEL_RGBA8: hipLaunchKernelGGL(k_display_image<PTX_PIXEL_RGBA8>, grid, block, 0, st, d_rgb, p0, p1, pd, d_out); break;
+    case PTX_PIXEL_RGB32F: hipLaunchKernelGGL(k_display_image<PTX_PIXEL_RGB32F>, grid, block, 0, st, d_rgb, p0, p1, pd, d_out); break;
+    default: hipLaunchKernelGGL(k_display_image<PTX_PIXEL_RGBA32F>, grid, block, 0, st, d_rgb, p0, p1, pd, d_out); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+constexpr long long kMaxDisplayPixels = 1ll << 40; /* the grid: a quad a thread, 256 a workgroup, fewer than 2^31 workgroups */
+
+/* the display image of the handle's filmed image s->rgb, whole, queued on st */
+int display_scene_image(ptx_scene* s, const DisplayJob& job, long long npix, hipStream_t st) {
+  return display_queue(job.d, 0, npix, s->rgb.p, s->disp.p, st);
+}
 
 /* progress sink of the worker threads: pixel counts are only ADDED here; the calling thread hands them on */
 void progress_to_counter(void* user, int64_t pixels) { ((std::atomic<long long>*)user)->fetch_add(pixels); }
 }  // namespace
 
-int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_params* p_in, double* rgb_out, ptx_stats* stats,
-                         ptx_progress_fn progress, void* user) {
-  if (!scenes || !rgb_out || n < 1) return fail(PTX_ERR_ARG, "NULL argument or no scenes");
+/* ptx_render and ptx_render_multi with the image they hand back chosen by `job`: NULL = the f64 image into rgb_out; otherwise the
+ * display image into job->out (ptx_render_display), and rgb_out is not read */
+static int32_t render_one(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out, const DisplayJob* job, ptx_stats* stats,
+                          ptx_progress_fn progress, void* user);
+
+static int32_t render_many(ptx_scene* const* scenes, int32_t n, const ptx_render_params* p_in, double* rgb_out, const DisplayJob* job,
+                           ptx_stats* stats, ptx_progress_fn progress, void* user) {
+  if (!scenes || !(job ? job->out : (void*)rgb_out) || n < 1) return fail(PTX_ERR_ARG, "NULL argument or no scenes");
   if (n > 64) return fail(PTX_ERR_ARG, "at most 64 scenes");
   for (int k = 0; k < n; ++k) {
     if (!scenes[k]) return fail(PTX_ERR_ARG, "scene %d is NULL", k);
@@ -2975,7 +3052,7 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
   if (n == 1) {
     ptx_render_params p1 = *p_in;
     p1.n_gpus = 0;
-    return ptx_render(scenes[0], &p1, rgb_out, stats, progress, user);
+    return render_one(scenes[0], &p1, rgb_out, job, stats, progress, user);
   }
   ptx_render_params p = *p_in;
   p.n_gpus = 0;
@@ -2993,6 +3070,11 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
   const size_t slice = (size_t)pad_rows * p.width * 3;
   HIP_TRY(root->gather.ensure(slice * (size_t)n));
   HIP_TRY(root->rgb.ensure((size_t)p.width * p.height * 3));
+  if (job) {
+    HIP_TRY(root->disp.ensure((size_t)p.width * p.height * job->pixel_bytes));
+    rc = display_thresholds_device();
+    if (rc) return rc;
+  }
 
   /* Peer access root <-> replica, once per pair (kept with the replica's handle): with it hipMemcpyPeer moves the bands
    * device to device over xGMI; without it the runtime stages them through host memory.  Either way the bytes are the same. */
@@ -3084,10 +3166,20 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
       if (scenes[k]->device != root->device) (scenes[k]->peer_ok ? stats->peer_copies : stats->staged_copies) += 1;
   rc = timed_film(p, root->gather.p, root->rgb.p, PtBandMap{n, p.band_rows, pad_rows}, stats, root->film); /* the film runs on scenes[0]: its film governs */
   if (rc) return rc;
-  rc = framebuffer_to_host(root, root->rgb.p, rgb_out, (size_t)p.width * p.height * 3);
+  if (job) { /* the display kernel runs over the filmed image: it needs no band map of its own */
+    rc = display_scene_image(root, *job, (long long)p.width * p.height, nullptr);
+    if (!rc) rc = image_bytes_to_host(root, (const char*)root->disp.p, (char*)job->out, (size_t)p.width * p.height * job->pixel_bytes);
+  } else {
+    rc = framebuffer_to_host(root, root->rgb.p, rgb_out, (size_t)p.width * p.height * 3);
+  }
   if (rc) return rc;
   if (stats) stats->render_ms = wall_ms() - t0;
   return 0;
+}
+
+int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_params* p_in, double* rgb_out, ptx_stats* stats,
+                         ptx_progress_fn progress, void* user) {
+  return render_many(scenes, n, p_in, rgb_out, nullptr, stats, progress, user);
 }
 
 /* ptx_render's tail into an image the caller has pinned, as a pipeline: the last batch's accumulate runs in row slabs, and on a
@@ -3098,7 +3190,7 @@ int32_t ptx_render_multi(ptx_scene* const* scenes, int32_t n, const ptx_render_p
  * *copied = false: the frame had no last batch to cut into slabs (one pass per batch); the raw sums are complete in s->raw and
  * the caller films and copies them the plain way. */
 namespace {
-int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, double* rgb_out, ptx_stats* stats, bool* copied) {
+int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, double* rgb_out, const DisplayJob* job, ptx_stats* stats, bool* copied) {
   FinalSlabs fs;
   fs.n = std::min(n_slabs, kMaxFinalSlabs);
   for (int k = 0; k <= fs.n; ++k) fs.row[k] = (int)((long long)p.height * k / fs.n);
@@ -3125,7 +3217,17 @@ int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, do
     rc = film_resolve(p.width, p.height, p.samples_per_pixel, s->raw.p, s->rgb.p, s->copy_stream, PtBandMap{1, 1, 0}, fs.row[k], fs.row[k + 1], s->film);
     if (rc) return rc;
     const size_t off = (size_t)fs.row[k] * p.width * 3, len = (size_t)(fs.row[k + 1] - fs.row[k]) * p.width * 3;
-    if (len) HIP_TRY(hipMemcpyAsync(rgb_out + off, s->rgb.p + off, sizeof(double) * len, hipMemcpyDeviceToHost, s->copy_stream));
+    if (job) { /* the display kernel over the slab's rows, then the slab's display bytes */
+      const long long p0 = (long long)fs.row[k] * p.width, p1 = (long long)fs.row[k + 1] * p.width;
+      rc = display_queue(job->d, p0, p1, s->rgb.p, s->disp.p, s->copy_stream);
+      if (rc) return rc;
+#ifdef PT_DISPLAY_MUTANT_SLAB
+      const size_t boff = (size_t)p0 * 3, blen = (size_t)(p1 - p0) * job->pixel_bytes; /* the offset counted in doubles */
+#else
+      const size_t boff = (size_t)p0 * job->pixel_bytes, blen = (size_t)(p1 - p0) * job->pixel_bytes;
+#endif
+      if (blen) HIP_TRY(hipMemcpyAsync((char*)job->out + boff, (const char*)s->disp.p + boff, blen, hipMemcpyDeviceToHost, s->copy_stream));
+    } else if (len) HIP_TRY(hipMemcpyAsync(rgb_out + off, s->rgb.p + off, sizeof(double) * len, hipMemcpyDeviceToHost, s->copy_stream));
   }
   if (fs.used) HIP_TRY(hipStreamSynchronize(s->copy_stream));
   HIP_TRY(hipStreamSynchronize(nullptr));
@@ -3135,8 +3237,9 @@ int render_into_pinned(ptx_scene* s, const ptx_render_params& p, int n_slabs, do
 }
 }  // namespace
 
-int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out, ptx_stats* stats, ptx_progress_fn progress, void* user) {
-  if (!s || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
+static int32_t render_one(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out, const DisplayJob* job, ptx_stats* stats,
+                          ptx_progress_fn progress, void* user) {
+  if (!s || !(job ? job->out : (void*)rgb_out)) return fail(PTX_ERR_ARG, "NULL argument");
   int rc = check_render_args(s, p_in, nullptr);
   if (rc) return rc;
   if (p_in->n_gpus > 1) {
@@ -3153,7 +3256,7 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
     std::vector<ptx_scene*> all;
     all.push_back(s);
     for (int k = 0; k + 1 < p_in->n_gpus; ++k) all.push_back(s->replicas[(size_t)k]);
-    return ptx_render_multi(all.data(), (int32_t)all.size(), p_in, rgb_out, stats, progress, user);
+    return render_many(all.data(), (int32_t)all.size(), p_in, rgb_out, job, stats, progress, user);
   }
   ptx_render_params p = *p_in;
   p.band_step = 0; /* whole image on this GPU */
@@ -3163,11 +3266,17 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
   const size_t n = (size_t)p.width * p.height * 3;
   HIP_TRY(s->raw.ensure(n));
   HIP_TRY(s->rgb.ensure(n));
+  const size_t out_bytes = job ? (size_t)p.width * p.height * job->pixel_bytes : sizeof(double) * n;
+  if (job) {
+    HIP_TRY(s->disp.ensure(out_bytes));
+    rc = display_thresholds_device();
+    if (rc) return rc;
+  }
   /* an image the caller has pinned takes the frame's tail as a pipeline (render_into_pinned) */
-  const bool pinned = s->reg_ptr && rgb_out >= s->reg_ptr && rgb_out + n <= s->reg_ptr + s->reg_n;
+  const bool pinned = s->holds_pinned(job ? job->out : (void*)rgb_out, out_bytes);
   const int n_slabs = (pinned && !p.count_work && !p.time_kernels && !progress && p.height >= kMinSlabImageRows && p.max_bounces > 0) ? env_int("PTX_FINAL_SLABS", 4) : 1;
   bool copied = false;
-  if (n_slabs > 1) rc = render_into_pinned(s, p, n_slabs, rgb_out, stats, &copied);
+  if (n_slabs > 1) rc = render_into_pinned(s, p, n_slabs, rgb_out, job, stats, &copied);
   else rc = render_raw(s, &p, s->raw.p, nullptr, stats, progress, user);
   if (rc) return rc;
   if (copied) {
@@ -3176,10 +3285,27 @@ int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out,
   }
   rc = timed_film(p, s->raw.p, s->rgb.p, PtBandMap{1, 1, 0}, stats, s->film);
   if (rc) return rc;
-  rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n);
+  if (job) {
+    rc = display_scene_image(s, *job, (long long)p.width * p.height, nullptr);
+    if (!rc) rc = image_bytes_to_host(s, (const char*)s->disp.p, (char*)job->out, out_bytes);
+  } else {
+    rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n);
+  }
   if (rc) return rc;
   if (stats) stats->render_ms = wall_ms() - t0;
   return 0;
+}
+
+int32_t ptx_render(ptx_scene* s, const ptx_render_params* p_in, double* rgb_out, ptx_stats* stats, ptx_progress_fn progress, void* user) {
+  return render_one(s, p_in, rgb_out, nullptr, stats, progress, user);
+}
+
+int32_t ptx_render_display(ptx_scene* s, const ptx_render_params* p_in, const ptx_display_params* display, void* out, ptx_stats* stats,
+                           ptx_progress_fn progress, void* user) {
+  const int rc = check_display(display);
+  if (rc) return rc;
+  const DisplayJob job{*display, out, (size_t)display_pixel_bytes(display->format)};
+  return render_one(s, p_in, nullptr, &job, stats, progress, user);
 }
 
 /* ---- progressive rendering: a frame rendered as consecutive pass slices into the same raw sums ---- */
@@ -3223,13 +3349,19 @@ void add_slice_stats(ptx_stats* acc, const ptx_stats& o) {
  * the frame is complete (it may wait for what queue_update queued, and for nothing else); copy_extras(cs) queues further copies of
  * the update to the host on cs; call_back(update, cur, next, samples, rel) is the caller's callback and the stopping rule. */
 extern "C++" template <class Policy>
-int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool want_err, double* rgb_out, double* err_out, ptx_stats* stats) {
+int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool want_err, double* rgb_out, double* err_out, ptx_stats* stats,
+                   const DisplayJob* job = nullptr) {
   RenderBusy busy(s);
   const double t0 = wall_ms();
   const long long npix = (long long)p.width * p.height;
   const size_t n = (size_t)npix * 3;
   HIP_TRY(s->raw.ensure(n));
   HIP_TRY(s->rgb.ensure(n));
+  if (job) { /* the updates' images leave as display pixels (ptx_render_progressive_display): rgb_out is not read */
+    HIP_TRY(s->disp.ensure((size_t)npix * job->pixel_bytes));
+    const int rd = display_thresholds_device();
+    if (rd) return rd;
+  }
   if (want_err) {
     HIP_TRY(s->sq.ensure(n));
     HIP_TRY(s->err_partials.ensure(pixel_error_partials(npix)));
@@ -3262,6 +3394,7 @@ int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool w
   double rel = std::nan("");
   for (int update = 1;; ++update) {
     rc = pol.queue_update(cur);
+    if (!rc && job) rc = display_scene_image(s, *job, npix, nullptr);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(s->ev_update, nullptr));
     rc = pol.next_slice(cur, &next);
@@ -3272,7 +3405,8 @@ int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool w
       if (rc) return rc;
     }
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_update, 0));
-    rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n, s->copy_stream);
+    if (job) rc = image_bytes_to_host(s, (const char*)s->disp.p, (char*)job->out, (size_t)npix * job->pixel_bytes, s->copy_stream);
+    else rc = framebuffer_to_host(s, s->rgb.p, rgb_out, n, s->copy_stream);
     if (rc) return rc;
     if (err_out) {
       rc = framebuffer_to_host(s, s->err.p, err_out, n, s->copy_stream);
@@ -3398,9 +3532,25 @@ struct ProgressivePolicy {
 };
 }  // namespace
 
-int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
-                               double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update, void* user) {
-  int rc = check_render_args(s, p_in, (pp && rgb_out) ? nullptr : "NULL argument");
+namespace {
+/* The callback of a display render behind the f64 policies' ptx_update_fn: the policies hand it their rgb_out (NULL under a display
+ * job); the caller's function gets the display image instead. */
+struct DisplayUpdate {
+  ptx_update_display_fn fn;
+  void* user;
+  const void* pixels;
+  static int32_t call(void* self, int32_t passes_done, double rel_err, const double*, const double* err) {
+    const DisplayUpdate* u = (const DisplayUpdate*)self;
+    return u->fn(u->user, passes_done, rel_err, u->pixels, err);
+  }
+};
+}  // namespace
+
+/* ptx_render_progressive, and with `job` ptx_render_progressive_display without denoise (rgb_out is then not read) */
+static int32_t render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
+                                  const DisplayJob* job, double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update,
+                                  void* user) {
+  int rc = check_render_args(s, p_in, (pp && (job ? job->out : (void*)rgb_out)) ? nullptr : "NULL argument");
   if (rc) return rc;
   if (p_in->n_gpus > 1) return fail(PTX_ERR_ARG, "progressive rendering runs on one GPU (n_gpus %d)", p_in->n_gpus);
   if (pp->passes_per_update < 1) return fail(PTX_ERR_ARG, "passes_per_update must be >= 1 (got %d)", pp->passes_per_update);
@@ -3413,7 +3563,12 @@ int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, cons
   p.n_gpus = 0;
   HIP_TRY(hipSetDevice(s->device));
   ProgressivePolicy pol{s, p, *pp, rgb_out, err_out, passes_done_out, on_update, user};
-  return render_updates(s, p, pol, pol.want_err(), rgb_out, err_out, stats);
+  return render_updates(s, p, pol, pol.want_err(), rgb_out, err_out, stats, job);
+}
+
+int32_t ptx_render_progressive(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, double* rgb_out,
+                               double* err_out, int32_t* passes_done_out, ptx_stats* stats, ptx_update_fn on_update, void* user) {
+  return render_progressive(s, p_in, pp, rgb_out, nullptr, err_out, passes_done_out, stats, on_update, user);
 }
 
 /* ---- adaptive sampling: rounds of passes for the pixels that have not converged yet ---- */
@@ -3812,10 +3967,11 @@ struct DenoisePolicy {
 };
 }  // namespace
 
-int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, const ptx_denoise_params* dp,
-                            double* rgb_out, double* err_out, double* feat_out, int32_t* passes_done_out, ptx_stats* stats,
-                            ptx_update_fn on_update, void* user) {
-  int rc = check_render_args(s, p_in, (pp && dp && rgb_out) ? nullptr : "NULL argument");
+/* ptx_render_denoised, and with `job` ptx_render_progressive_display with denoise (rgb_out is then not read) */
+static int32_t render_denoised(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, const ptx_denoise_params* dp,
+                               double* rgb_out, const DisplayJob* job, double* err_out, double* feat_out, int32_t* passes_done_out,
+                               ptx_stats* stats, ptx_update_fn on_update, void* user) {
+  int rc = check_render_args(s, p_in, (pp && dp && (job ? job->out : (void*)rgb_out)) ? nullptr : "NULL argument");
   if (rc) return rc;
   rc = check_one_gpu(p_in, "denoised rendering");
   if (rc) return rc;
@@ -3830,7 +3986,85 @@ int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const p
   p.n_gpus = 0;
   HIP_TRY(hipSetDevice(s->device));
   DenoisePolicy pol{s, p, *pp, *dp, rgb_out, err_out, feat_out, passes_done_out, on_update, user};
-  return render_updates(s, p, pol, true, rgb_out, err_out, stats);
+  return render_updates(s, p, pol, true, rgb_out, err_out, stats, job);
+}
+
+int32_t ptx_render_denoised(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp, const ptx_denoise_params* dp,
+                            double* rgb_out, double* err_out, double* feat_out, int32_t* passes_done_out, ptx_stats* stats,
+                            ptx_update_fn on_update, void* user) {
+  return render_denoised(s, p_in, pp, dp, rgb_out, nullptr, err_out, feat_out, passes_done_out, stats, on_update, user);
+}
+
+int32_t ptx_render_progressive_display(ptx_scene* s, const ptx_render_params* p_in, const ptx_progressive_params* pp,
+                                       const ptx_denoise_params* dp, const ptx_display_params* display, void* out, double* err_out,
+                                       int32_t* passes_done_out, ptx_stats* stats, ptx_update_display_fn on_update, void* user) {
+  const int rc = check_display(display);
+  if (rc) return rc;
+  const DisplayJob job{*display, out, (size_t)display_pixel_bytes(display->format)};
+  DisplayUpdate du{on_update, user, out};
+  const ptx_update_fn fn = on_update ? DisplayUpdate::call : nullptr;
+  if (dp) return render_denoised(s, p_in, pp, dp, nullptr, &job, err_out, nullptr, passes_done_out, stats, fn, &du);
+  return render_progressive(s, p_in, pp, nullptr, &job, err_out, passes_done_out, stats, fn, &du);
+}
+
+/* ---- display outputs without a scene: the defaults, the table, the rule on the host and on a device ---- */
+int32_t ptx_display_defaults(ptx_display_params* out) {
+  if (!out) return fail(PTX_ERR_ARG, "NULL argument");
+  std::memset(out, 0, sizeof *out);
+  out->format = PTX_PIXEL_RGB8;
+  out->transfer = PTX_TRANSFER_REFERENCE;
+  out->tone = PTX_TONE_NONE;
+  out->exposure = 1.0;
+  return 0;
+}
+
+int32_t ptx_display_check(const ptx_display_params* display) { return check_display(display); }
+
+int32_t ptx_display_pixel_bytes(int32_t format) {
+  const int b = display_pixel_bytes(format);
+  return b ? b : fail(PTX_ERR_ARG, "display: unknown format %d (PTX_PIXEL_RGB8 0, RGBA8 1, RGB32F 2, RGBA32F 3)", format);
+}
+
+int32_t ptx_display_thresholds(double out[255]) {
+  if (!out) return fail(PTX_ERR_ARG, "NULL argument");
+  std::memcpy(out, display_thresholds(), sizeof(double) * PT_DISPLAY_THRESHOLDS);
+  return 0;
+}
+
+int32_t ptx_display_apply(const ptx_display_params* display, int64_t n_pixels, const double* rgb, void* out) {
+  const int rc = check_display(display);
+  if (rc) return rc;
+  if (n_pixels < 0) return fail(PTX_ERR_ARG, "display: n_pixels must be >= 0 (got %lld)", (long long)n_pixels);
+  if (n_pixels == 0) return 0;
+  if (!rgb || !out) return fail(PTX_ERR_ARG, "NULL argument");
+  display_apply_host(*display, n_pixels, rgb, out);
+  return 0;
+}
+
+int32_t ptx_display_image_device(int32_t device, const ptx_display_params* display, int64_t n_pixels, const double* d_rgb, void* d_out,
+                                 void* stream) {
+  return ptx_display_range_device(device, display, 0, n_pixels, d_rgb, d_out, stream);
+}
+
+int32_t ptx_display_range_device(int32_t device, const ptx_display_params* display, int64_t pixel_first, int64_t n_pixels,
+                                 const double* d_rgb, void* d_out, void* stream) {
+  int rc = check_display(display);
+  if (rc) return rc;
+  if (device < 0) return fail(PTX_ERR_STATE, "device %d: the display kernel runs on a HIP device only (the host has ptx_display_apply)", device);
+  if (n_pixels < 0 || n_pixels > kMaxDisplayPixels) return fail(PTX_ERR_ARG, "display: n_pixels %lld is outside [0, 2^40]", (long long)n_pixels);
+  if (pixel_first < 0 || pixel_first > kMaxDisplayPixels) return fail(PTX_ERR_ARG, "display: pixel_first %lld is outside [0, 2^40]", (long long)pixel_first);
+  if (n_pixels == 0) return 0;
+  if (!d_rgb || !d_out) return fail(PTX_ERR_ARG, "NULL argument");
+  if (((uintptr_t)d_rgb | (uintptr_t)d_out) & 15) return fail(PTX_ERR_ARG, "display: d_rgb and d_out must be 16-byte aligned (the kernel moves 16-byte pieces)");
+  rc = check_device(device);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  rc = display_thresholds_device();
+  if (rc) return rc;
+  rc = display_queue(*display, pixel_first, pixel_first + n_pixels, d_rgb, d_out, (hipStream_t)stream);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return 0;
 }
 
 /* ---- temporal accumulation (temporal.inc; the rule: include/ptx.h) ---- */

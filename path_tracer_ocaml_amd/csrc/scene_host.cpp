@@ -3,6 +3,7 @@
  * the light table must carry the bits the shade step itself would compute. */
 #include "scene_host.h"
 
+#include "pt_display.h"
 #include "pt_lds_layout.h"
 
 #include <algorithm>
@@ -817,4 +818,72 @@ PtTileGrid scene_tile_lists(const PtHostArrays& h, int width, int height) {
     }
   }
   return g;
+}
+
+/* ---- display outputs (include/ptx.h): checks, the sRGB thresholds, the rule of pt_display.h over an image ---- */
+int display_pixel_bytes(int32_t format) {
+  switch (format) {
+    case PTX_PIXEL_RGB8: return 3;
+    case PTX_PIXEL_RGBA8: return 4;
+    case PTX_PIXEL_RGB32F: return 12;
+    case PTX_PIXEL_RGBA32F: return 16;
+    default: return 0;
+  }
+}
+
+int display_check(const ptx_display_params* d, std::string* msg) {
+  if (display_pixel_bytes(d->format) == 0)
+    return reject(msg, "display: unknown format %d (PTX_PIXEL_RGB8 0, RGBA8 1, RGB32F 2, RGBA32F 3)", d->format);
+  if (d->transfer < PTX_TRANSFER_REFERENCE || d->transfer > PTX_TRANSFER_SRGB)
+    return reject(msg, "display: unknown transfer %d (PTX_TRANSFER_REFERENCE 0, LINEAR 1, SRGB 2)", d->transfer);
+  if (d->tone < PTX_TONE_NONE || d->tone > PTX_TONE_ACES)
+    return reject(msg, "display: unknown tone %d (PTX_TONE_NONE 0, REINHARD 1, ACES 2)", d->tone);
+  if (d->flags != 0) return reject(msg, "display: flags must be 0 (got %d)", d->flags);
+  for (int i = 0; i < 4; ++i)
+    if (d->reserved[i] != 0) return reject(msg, "display: reserved[%d] must be 0 (got %d)", i, d->reserved[i]);
+  if (!std::isfinite(d->exposure) || d->exposure < 0.0) return reject(msg, "display: exposure must be finite and >= 0 (got %g)", d->exposure);
+  if (d->transfer == PTX_TRANSFER_REFERENCE && (d->tone != PTX_TONE_NONE || d->exposure != 1.0))
+    return reject(msg, "display: PTX_TRANSFER_REFERENCE needs tone PTX_TONE_NONE and exposure 1.0 (got tone %d, exposure %g): the reference's "
+                       "conversion has neither; use PTX_TRANSFER_LINEAR or PTX_TRANSFER_SRGB", d->tone, d->exposure);
+  if (d->transfer == PTX_TRANSFER_SRGB && (d->format == PTX_PIXEL_RGB32F || d->format == PTX_PIXEL_RGBA32F))
+    return reject(msg, "display: the binary32 formats carry linear or reference values, not PTX_TRANSFER_SRGB (format %d)", d->format);
+  return 0;
+}
+
+const double* display_thresholds() {
+  struct Table {
+    double t[PT_DISPLAY_THRESHOLDS];
+    Table() {
+      for (int k = 1; k <= PT_DISPLAY_THRESHOLDS; ++k) {
+        const double e = ((double)k - 0.5) / 255.0;
+        t[k - 1] = e <= 0.04045 ? e / 12.92 : std::pow((e + 0.055) / 1.055, 2.4);
+      }
+    }
+  };
+  static const Table table; /* initialised once, by whichever thread asks first */
+  return table.t;
+}
+
+namespace {
+template <class T, int C>
+void display_apply_as(const ptx_display_params& d, int64_t n_pixels, const double* rgb, T* out, const double* th) {
+  for (int64_t p = 0; p < n_pixels; ++p) {
+    for (int c = 0; c < 3; ++c) {
+      const double v = rgb[3 * p + c];
+      if constexpr (sizeof(T) == 1) out[C * p + c] = pt_display_code(v, d.transfer, d.tone, d.exposure, th);
+      else out[C * p + c] = pt_display_f32(v, d.transfer, d.tone, d.exposure);
+    }
+    if constexpr (C == 4) out[4 * p + 3] = sizeof(T) == 1 ? (T)255 : (T)1;
+  }
+}
+}  // namespace
+
+void display_apply_host(const ptx_display_params& d, int64_t n_pixels, const double* rgb, void* out) {
+  const double* th = display_thresholds();
+  switch (d.format) {
+    case PTX_PIXEL_RGB8: display_apply_as<uint8_t, 3>(d, n_pixels, rgb, (uint8_t*)out, th); break;
+    case PTX_PIXEL_RGBA8: display_apply_as<uint8_t, 4>(d, n_pixels, rgb, (uint8_t*)out, th); break;
+    case PTX_PIXEL_RGB32F: display_apply_as<float, 3>(d, n_pixels, rgb, (float*)out, th); break;
+    default: display_apply_as<float, 4>(d, n_pixels, rgb, (float*)out, th); break;
+  }
 }

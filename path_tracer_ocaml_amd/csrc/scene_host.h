@@ -139,4 +139,14 @@ struct PtTileGrid {
 bool scene_tile_lists_possible(const PtHostArrays& h);
 PtTileGrid scene_tile_lists(const PtHostArrays& h, int width, int height);
 
+/* ---- display outputs (include/ptx.h): the host half of the rule of pt_display.h ----
+ * Every check of a caller's ptx_display_params.  0, or PTX_ERR_ARG with *msg naming the rule that refused. */
+int display_check(const ptx_display_params* d, std::string* msg);
+/* bytes of a pixel of `format`, 0 for an unknown one */
+int display_pixel_bytes(int32_t format);
+/* the 255 sRGB thresholds, [k - 1] = T[k]: computed with libm the first time they are asked for and kept for the process */
+const double* display_thresholds();
+/* the rule over n_pixels pixels (3 doubles each) into n_pixels * display_pixel_bytes(d.format) bytes; d has passed display_check */
+void display_apply_host(const ptx_display_params& d, int64_t n_pixels, const double* rgb, void* out);
+
 #endif /* SCENE_HOST_H */

@@ -12,7 +12,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
 EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_scene_camera", "pth_camera_create", "pth_camera_pose_look_at", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
-           "pth_scene_ganesha_like", "pth_write_png", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
+           "pth_scene_ganesha_like", "pth_write_png", "pth_write_png8", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
 
@@ -43,6 +43,7 @@ def lib():
         L.pth_scene_ganesha_like.restype = C.c_void_p
         L.pth_scene_ganesha_like.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint64]
         L.pth_write_png.argtypes = [C.c_char_p, C.c_int32, C.c_int32, abi.c_double_p]
+        L.pth_write_png8.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
         L.pth_last_error.restype = C.c_char_p
         L.pth_ply_load.restype = C.c_void_p
         L.pth_ply_load.argtypes = [C.c_char_p]
@@ -207,6 +208,17 @@ def write_png(path, rgb):
     rc = lib().pth_write_png(path.encode(), w, h, rgb.ctypes.data_as(abi.c_double_p))
     if rc != 0:
         raise IOError(f"pth_write_png({path}) failed: {rc}")
+
+
+def write_png8(path, rgb8):
+    """pth_write_png8: the PNG of an (H, W, 3) uint8 image, the RGB8 display pixels of Scene.render_display"""
+    rgb8 = np.ascontiguousarray(rgb8)
+    if rgb8.dtype != np.uint8 or rgb8.ndim != 3 or rgb8.shape[2] != 3:
+        raise ValueError("rgb8 must be a uint8 array of shape (height, width, 3)")
+    h, w, _ = rgb8.shape
+    rc = lib().pth_write_png8(path.encode(), w, h, C.c_void_p(rgb8.ctypes.data))
+    if rc != 0:
+        raise IOError(f"pth_write_png8({path}) failed: {rc}")
 
 
 class PlyError(RuntimeError):

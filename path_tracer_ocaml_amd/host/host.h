@@ -98,6 +98,9 @@ int32_t pth_ground_texture(const ptx_scene_desc* d);
 /* Bimage_unix.Stb.write of the f64 image (render_command.ml:66-70): 8-bit RGB PNG, v -> int(v*255) clamped.
  * returns 0 on success */
 int32_t pth_write_png(const char* path, int32_t width, int32_t height, const double* rgb);
+/* the same file from 8-bit codes, width * height * 3 of them (PTX_PIXEL_RGB8: what ptx_render_display hands back); pth_write_png is
+ * its own conversion in front of this */
+int32_t pth_write_png8(const char* path, int32_t width, int32_t height, const uint8_t* rgb8);
 
 #ifdef __cplusplus
 }

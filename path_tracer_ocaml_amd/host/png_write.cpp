@@ -37,16 +37,23 @@ void chunk(std::vector<uint8_t>& out, const char type[4], const std::vector<uint
 
 extern "C" int32_t pth_write_png(const char* path, int32_t width, int32_t height, const double* rgb) {
   if (!path || !rgb || width <= 0 || height <= 0) return -1;
+  std::vector<uint8_t> codes((size_t)height * (size_t)width * 3);
+  for (size_t k = 0; k < codes.size(); ++k) {
+    double v = rgb[k] * 255.0;
+    if (!(v > 0.0)) v = 0.0;
+    if (v > 255.0) v = 255.0;
+    codes[k] = (uint8_t)(int)v;
+  }
+  return pth_write_png8(path, width, height, codes.data());
+}
+
+extern "C" int32_t pth_write_png8(const char* path, int32_t width, int32_t height, const uint8_t* rgb8) {
+  if (!path || !rgb8 || width <= 0 || height <= 0) return -1;
   std::vector<uint8_t> raw;
   raw.reserve((size_t)height * ((size_t)width * 3 + 1));
   for (int y = 0; y < height; ++y) {
     raw.push_back(0);  // filter: none
-    for (int x = 0; x < width * 3; ++x) {
-      double v = rgb[(size_t)y * width * 3 + x] * 255.0;
-      if (!(v > 0.0)) v = 0.0;
-      if (v > 255.0) v = 255.0;
-      raw.push_back((uint8_t)(int)v);
-    }
+    raw.insert(raw.end(), rgb8 + (size_t)y * width * 3, rgb8 + ((size_t)y + 1) * width * 3);
   }
   std::vector<uint8_t> z = {0x78, 0x01};
   uint32_t a = 1, b = 0;  // adler32

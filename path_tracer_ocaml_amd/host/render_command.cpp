@@ -39,6 +39,11 @@
 // --hdr-out=FILE.pfm (any render): also writes the square of every value of the final image -- the filmed linear radiance -- as a PFM
 // (pth_pfm_write), which --envmap reads back: a panorama written here lights another scene.  With --turntable, frame k goes to the name
 // with -kkk in front of its extension.
+// --exposure=E, --tone=none|reinhard|aces, --transfer=reference|linear|srgb (any render): the display of the image (include/ptx.h,
+// "display outputs"); -o is written from its RGB8 bytes (pth_write_png8).  The plain render, --progressive and --denoise get those bytes
+// from the device (ptx_render_display, ptx_render_progressive_display); --adaptive, --turntable, --temporal, --aov and --hdr-out keep the
+// f64 image and convert it with ptx_display_apply, the same rule.  With no such flag the display is the reference's own conversion and
+// every file is what it always was.  --hdr-out is the RGB32F / linear / no-tone display at exposure 1 whatever the flags say.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -93,6 +98,7 @@ struct Args {
   double temporal = -1.0;                // --temporal[=CAP]: max_history_passes (< 0: no temporal accumulation)
   bool panorama = false;                 // --panorama
   std::string hdr_out;                   // --hdr-out=FILE.pfm
+  ptx_display_params display{PTX_PIXEL_RGB8, PTX_TRANSFER_REFERENCE, PTX_TONE_NONE, 0, 1.0, {0, 0, 0, 0}}; // --transfer, --tone, --exposure
 };
 
 [[noreturn]] void usage(const char* prog, const char* msg) {
@@ -108,7 +114,8 @@ struct Args {
                "          [--lens-radius=FLOAT] [--focus-distance=FLOAT]\n"
                "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n"
                "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n"
-               "          [--turntable-arc=DEG] [--temporal[=CAP]] [--panorama] [--hdr-out=FILE.pfm]\n",
+               "          [--turntable-arc=DEG] [--temporal[=CAP]] [--panorama] [--hdr-out=FILE.pfm]\n"
+               "          [--exposure=FLOAT] [--tone=none|reinhard|aces] [--transfer=reference|linear|srgb]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
 }
@@ -143,6 +150,22 @@ Args parse(int argc, char** argv) {
     else if (take_value(argc, argv, i, "hdr-out", nullptr, &v)) {
       if (v.empty()) usage(argv[0], "invalid value for --hdr-out, expected a file name");
       a.hdr_out = v;
+    }
+    else if (take_value(argc, argv, i, "exposure", nullptr, &v)) {
+      char* end = nullptr;
+      a.display.exposure = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.display.exposure >= 0.0) || !std::isfinite(a.display.exposure))
+        usage(argv[0], "invalid value for --exposure, must be finite and >= 0");
+    } else if (take_value(argc, argv, i, "tone", nullptr, &v)) {
+      if (v == "none") a.display.tone = PTX_TONE_NONE;
+      else if (v == "reinhard") a.display.tone = PTX_TONE_REINHARD;
+      else if (v == "aces") a.display.tone = PTX_TONE_ACES;
+      else usage(argv[0], "invalid value for --tone, expected none, reinhard or aces");
+    } else if (take_value(argc, argv, i, "transfer", nullptr, &v)) {
+      if (v == "reference") a.display.transfer = PTX_TRANSFER_REFERENCE;
+      else if (v == "linear") a.display.transfer = PTX_TRANSFER_LINEAR;
+      else if (v == "srgb") a.display.transfer = PTX_TRANSFER_SRGB;
+      else usage(argv[0], "invalid value for --transfer, expected reference, linear or srgb");
     }
     else if (take_value(argc, argv, i, "sphere-lamp", nullptr, &v)) {
       char tail = 0;
@@ -333,16 +356,35 @@ void on_progress(void* user, int64_t pixels) { // the ASCII bar of render_comman
   if (p->done >= p->total) std::fputc('\n', stderr);
 }
 
+// the PNG of an f64 image under the display: its RGB8 bytes by the library's rule on the host (ptx_display_apply)
+int write_display_png(const char* path, int width, int height, const double* rgb, const ptx_display_params& display) {
+  std::vector<uint8_t> codes((size_t)width * height * 3);
+  if (ptx_display_apply(&display, (int64_t)width * height, rgb, codes.data()) != 0) return -1;
+  return pth_write_png8(path, width, height, codes.data());
+}
+
 struct Updates { // --progressive: the PNG rewritten after every update, one line per update on stdout
   const char* output;
   int width, height;
+  const ptx_display_params* display;
   bool write_failed = false;
 };
 int32_t on_update(void* user, int32_t passes_done, double rel_err, const double* rgb, const double*) {
   Updates* u = (Updates*)user;
   std::printf("#passes = %d, error = %.6g\n", passes_done, rel_err);
   std::fflush(stdout);
-  if (pth_write_png(u->output, u->width, u->height, rgb) != 0) {
+  if (write_display_png(u->output, u->width, u->height, rgb, *u->display) != 0) {
+    u->write_failed = true;
+    return 1;
+  }
+  return 0;
+}
+// the same for updates that arrive as RGB8 display pixels (ptx_render_progressive_display)
+int32_t on_update_display(void* user, int32_t passes_done, double rel_err, const void* pixels, const double*) {
+  Updates* u = (Updates*)user;
+  std::printf("#passes = %d, error = %.6g\n", passes_done, rel_err);
+  std::fflush(stdout);
+  if (pth_write_png8(u->output, u->width, u->height, (const uint8_t*)pixels) != 0) {
     u->write_failed = true;
     return 1;
   }
@@ -356,7 +398,7 @@ int32_t on_round(void* user, int32_t round, int32_t passes_done, int64_t active_
   std::printf("#round = %d, passes = %d, active = %lld, samples = %lld, error = %.6g\n", round, passes_done, (long long)active_next,
               (long long)samples, rel_err);
   std::fflush(stdout);
-  if (pth_write_png(u->output, u->width, u->height, rgb) != 0) {
+  if (write_display_png(u->output, u->width, u->height, rgb, *u->display) != 0) {
     u->write_failed = true;
     return 1;
   }
@@ -427,6 +469,7 @@ std::string frame_name(const std::string& output, int frame) {
 
 int main(int argc, char** argv) {
   const Args a = parse(argc, argv);
+  if (ptx_display_check(&a.display) != 0) usage(argv[0], ptx_last_error()); // e.g. --tone without --transfer=linear|srgb
   pth_scene* hs = nullptr;
   if (a.scene == "shirley")
     hs = a.have_sphere_lamp ? pth_scene_shirley_lamp(a.width, a.height, a.no_simd ? 1 : 0, 42, a.sphere_lamp[0], a.sphere_lamp[1], a.sphere_lamp[2],
@@ -517,15 +560,20 @@ int main(int argc, char** argv) {
   std::memset(&p, 0, sizeof p);
   p.width = a.width; p.height = a.height; p.samples_per_pixel = a.samples_per_pixel; p.max_bounces = a.max_bounces;
   p.n_gpus = a.gpus;
-  std::vector<double> rgb((size_t)a.width * a.height * 3);
+  /* the display route: the RGB8 bytes come from the device.  The drivers below that keep their f64 image (and --aov's feature image,
+   * --hdr-out's binary32 one, which need it) convert it on the host by the same rule. */
+  const bool on_device = a.temporal < 0.0 && a.adaptive < 0.0 && a.turntable == 0 && a.aov.empty() && a.hdr_out.empty();
+  std::vector<double> rgb(on_device ? 0 : (size_t)a.width * a.height * 3);
+  std::vector<uint8_t> rgb8(on_device ? (size_t)a.width * a.height * 3 : 0);
   Progress prog;
   prog.total = (long long)a.width * a.height;
   prog.t0 = prog.last = now_ms();
   const double t0 = now_ms();
   /* the image lives until the PNG is written, like the reference's Bimage (render_command.ml:64-70): pin it, so the frame comes
    * back with one DMA (optional: a failure only means the staged copy) */
-  (void)ptx_image_pin(scene, rgb.data(), (int64_t)rgb.size());
-  Updates upd{output.c_str(), a.width, a.height};
+  if (on_device) (void)ptx_image_pin_bytes(scene, rgb8.data(), (int64_t)rgb8.size());
+  else (void)ptx_image_pin(scene, rgb.data(), (int64_t)rgb.size());
+  Updates upd{output.c_str(), a.width, a.height, &a.display};
   int rc;
   const bool adaptive = a.adaptive >= 0.0;
   long long history_pixels = 0;
@@ -562,7 +610,8 @@ int main(int argc, char** argv) {
     dn.levels = a.denoise;
     std::vector<double> feat(a.aov.empty() ? 0 : (size_t)a.width * a.height * PTX_FEATURE_DOUBLES);
     int32_t passes_done = 0;
-    rc = ptx_render_denoised(scene, &p, &pp, &dn, rgb.data(), nullptr, feat.empty() ? nullptr : feat.data(), &passes_done, &st, on_update,
+    if (on_device) rc = ptx_render_progressive_display(scene, &p, &pp, &dn, &a.display, rgb8.data(), nullptr, &passes_done, &st, on_update_display, &upd);
+    else rc = ptx_render_denoised(scene, &p, &pp, &dn, rgb.data(), nullptr, feat.empty() ? nullptr : feat.data(), &passes_done, &st, on_update,
                              &upd);
     if (rc == 0 && !feat.empty() && write_aovs(a.aov, a.width, a.height, feat) != 0) {
       std::fprintf(stderr, "cannot write %s-*.png\n", a.aov.c_str());
@@ -575,9 +624,11 @@ int main(int argc, char** argv) {
     pp.want_error = 1;
     pp.target_rel_err = a.target_error;
     int32_t passes_done = 0;
-    rc = ptx_render_progressive(scene, &p, &pp, rgb.data(), nullptr, &passes_done, &st, on_update, &upd);
+    if (on_device) rc = ptx_render_progressive_display(scene, &p, &pp, nullptr, &a.display, rgb8.data(), nullptr, &passes_done, &st, on_update_display, &upd);
+    else rc = ptx_render_progressive(scene, &p, &pp, rgb.data(), nullptr, &passes_done, &st, on_update, &upd);
   } else {
-    rc = ptx_render(scene, &p, rgb.data(), &st, a.no_progress ? nullptr : on_progress, &prog);
+    if (on_device) rc = ptx_render_display(scene, &p, &a.display, rgb8.data(), &st, a.no_progress ? nullptr : on_progress, &prog);
+    else rc = ptx_render(scene, &p, rgb.data(), &st, a.no_progress ? nullptr : on_progress, &prog);
   }
   (void)ptx_image_unpin(scene);
   const double elapsed = now_ms() - t0;
@@ -586,13 +637,19 @@ int main(int argc, char** argv) {
                  ptx_last_error());
     return 1;
   }
-  if (upd.write_failed || pth_write_png(output.c_str(), a.width, a.height, rgb.data()) != 0) {
+  if (upd.write_failed || (on_device ? pth_write_png8(output.c_str(), a.width, a.height, rgb8.data())
+                                     : write_display_png(output.c_str(), a.width, a.height, rgb.data(), a.display)) != 0) {
     std::fprintf(stderr, "cannot write %s\n", output.c_str());
     return 1;
   }
-  if (!a.hdr_out.empty()) { // the image is sqrt(filmed radiance): its square, rounded to binary32 by the writer
-    std::vector<double> linear(rgb.size());
-    for (size_t k = 0; k < rgb.size(); ++k) linear[k] = rgb[k] * rgb[k];
+  if (!a.hdr_out.empty()) { // the image is sqrt(filmed radiance): its RGB32F / linear display at exposure 1 -- the square, in binary32
+    const ptx_display_params hdr_display{PTX_PIXEL_RGB32F, PTX_TRANSFER_LINEAR, PTX_TONE_NONE, 0, 1.0, {0, 0, 0, 0}};
+    std::vector<float> linear32(rgb.size());
+    if (ptx_display_apply(&hdr_display, (int64_t)a.width * a.height, rgb.data(), linear32.data()) != 0) {
+      std::fprintf(stderr, "ptx_display_apply: %s\n", ptx_last_error());
+      return 1;
+    }
+    const std::vector<double> linear(linear32.begin(), linear32.end()); // (exact: the writer's rounding to binary32 gives them back)
     const std::string hdr = a.turntable > 0 ? frame_name(a.hdr_out, frame) : a.hdr_out;
     if (pth_pfm_write(hdr.c_str(), a.width, a.height, linear.data()) != 0) {
       std::fprintf(stderr, "cannot write %s: %s\n", hdr.c_str(), pth_image_error());

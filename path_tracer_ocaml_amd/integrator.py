@@ -117,6 +117,25 @@ class Integrator:
         self.stats = st
         return self.image
 
+    def render_display(self, format="rgb8", transfer="reference", tone="none", exposure=1.0, update_progress=None, out=None):
+        """``render`` whose result is display pixels (Scene.render_display): a uint8 or float32 array of shape (H, W, 3 or 4),
+        converted on the device.  ``image``, the f64 Bimage, is not written."""
+        pixels, st = self._scene.render_display(self.width, self.height, self.samples_per_pixel, self.max_bounces, format=format,
+                                                transfer=transfer, tone=tone, exposure=exposure, progress=update_progress, out=out)
+        self.stats = st
+        return pixels
+
+    def render_progressive_display(self, passes_per_update, denoise=None, format="rgb8", transfer="reference", tone="none",
+                                   exposure=1.0, on_update=None, target_rel_err=0.0, want_error=True, out=None):
+        """``render_progressive`` -- with ``denoise``, ``render_denoised`` -- whose updates are display pixels
+        (Scene.render_progressive_display).  Returns the last update's pixels; ``error`` and ``passes_done`` as there."""
+        pixels, err, done, st = self._scene.render_progressive_display(
+            self.width, self.height, self.samples_per_pixel, self.max_bounces, passes_per_update, denoise=denoise, format=format,
+            transfer=transfer, tone=tone, exposure=exposure, on_update=on_update, target_rel_err=target_rel_err,
+            want_error=want_error, out=out)
+        self.error, self.passes_done, self.stats = err, done, st
+        return pixels
+
     def render_progressive(self, passes_per_update, on_update=None, target_rel_err=0.0, want_error=True):
         """``render`` as a sequence of updates (Scene.render_progressive): ``image`` holds the image of the last update,
         ``error`` its per-pixel standard error (None without want_error), ``passes_done`` how many passes it holds."""
