@@ -1250,6 +1250,18 @@ int32_t ptx_intersect_rays(ptx_scene* scene, int64_t n, const double* origins,
 int32_t ptx_walk_rays(ptx_scene* scene, int32_t walk, int64_t n, const double* origins, const double* directions,
                       double* t_out, int32_t* prim_out);
 
+/* Diagnostic, beside ptx_walk_rays: the BOX DECISIONS of the walks that have a node loop of their own (SHARED_ASM, OCT_ASM,
+ * SHARED_DIV and their _ZERO forms; PACKET and the _TAIL walks are PTX_ERR_ARG), one leaf at a time.  Per triple i: the ray
+ * (origins, directions: 3 doubles each), nodes[i] = a node in the numbering of ptx_scene_tree and t_max[i] = the closest hit so far.
+ * leaf_out[i] = the first slot of the next leaf whose box test the walk passes, starting with the visit of nodes[i] (the order of a
+ * walk resumed there: near child first on a hit, on past the subtree on a miss), or -1 when the walk runs off the tree first.  No
+ * leaf is entered, so t_max stays what the caller gave and the result depends on box decisions alone: the binary32 filter's, the
+ * nested-interval rule's and the binary64 test's, made by the production node loops.
+ * Errors as ptx_walk_rays'; also PTX_ERR_ARG for a node outside 0 .. n_nodes - 1 and for a t_max that is NaN or negative.  Nothing is
+ * launched when an error is returned; n == 0 returns 0. */
+int32_t ptx_walk_next_leaf(ptx_scene* scene, int32_t walk, int64_t n, const double* origins, const double* directions,
+                           const int32_t* nodes, const double* t_max, int32_t* leaf_out);
+
 /* Diagnostic, for the test suite's coverage record: the instantiations of the four hot kernel families (k_trace, k_shade_pool,
  * k_bounce_carry, k_bounce) the library is built with, and which of them a handle has launched.
  * ptx_kernel_table: every family's selector walked over the whole cube of its arguments in a fixed order; an instantiation is entered

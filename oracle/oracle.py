@@ -71,6 +71,8 @@ def lib():
     L.orc_tile_split.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.c_int]
     L.orc_film_tile_kat.argtypes = [C.c_int] * 7 + [dp, ip]
     L.orc_bbox_is_hit.argtypes = [dp, dp, dp, C.c_double, C.c_double]
+    L.orc_bbox_is_hit_vec.restype = None
+    L.orc_bbox_is_hit_vec.argtypes = [C.c_int64, dp, dp, dp, dp, dp, ip]
     L.orc_bbox_mem.argtypes = [dp, dp]
     L.orc_sphere_intersect.argtypes = [dp, C.c_double, dp, dp, C.c_double, C.c_double, dp]
     L.orc_spheres_intersect_packet.argtypes = [dp, dp, dp, dp, C.c_int, dp, dp, C.c_double, C.c_double, dp]
@@ -332,6 +334,16 @@ def lights_cornell(width, height):
     out = (abi.Light * 1)()
     n = lib().orc_lights_cornell(width, height, out)
     return [out[i] for i in range(n)]
+
+
+def bbox_is_hit_vec(boxes, origins, directions, t_min, t_max):
+    """orc_bbox_is_hit_vec: Bbox.is_hit per (box (n, 6), ray, t_min, t_max) -> (n,) bool; a loop over orc_bbox_is_hit"""
+    b, o, d, lo, hi = f64(boxes), f64(origins), f64(directions), f64(t_min), f64(t_max)
+    n = b.shape[0]
+    assert b.shape == (n, 6) and o.shape == (n, 3) and d.shape == (n, 3) and lo.shape == (n,) and hi.shape == (n,)
+    out = np.zeros(n, dtype=np.int32)
+    lib().orc_bbox_is_hit_vec(n, _dp(b), _dp(o), _dp(d), _dp(lo), _dp(hi), _ip(out))
+    return out != 0
 
 
 def set_math(mode):

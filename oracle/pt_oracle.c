@@ -342,6 +342,11 @@ ORC_API int orc_bbox_is_hit(const double* bb /*6*/, const double* o, const doubl
   ray_t r = ray_create(v3_make(o[0], o[1], o[2]), v3_make(d[0], d[1], d[2]));
   return bbox_is_hit(&b, &r, t_min, t_max);
 }
+/* orc_bbox_is_hit over n (box, ray, t_min, t_max) tuples: a loop over the function above, out[i] = its result */
+ORC_API void orc_bbox_is_hit_vec(int64_t n, const double* bb /*6n*/, const double* o /*3n*/, const double* d /*3n*/, const double* t_min,
+                                 const double* t_max, int32_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = orc_bbox_is_hit(bb + 6 * i, o + 3 * i, d + 3 * i, t_min[i], t_max[i]);
+}
 ORC_API int orc_bbox_mem(const double* bb, const double* p) {
   bbox_t b = {v3_make(bb[0], bb[1], bb[2]), v3_make(bb[3], bb[4], bb[5])};
   return bbox_mem(&b, v3_make(p[0], p[1], p[2]));

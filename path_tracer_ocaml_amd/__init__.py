@@ -41,7 +41,7 @@ EXPORTS = (
     "ptx_film_defaults", "ptx_film_weights", "ptx_scene_set_film", "ptx_scene_film", "ptx_film_resolve_ex_device",
     "ptx_film_resolve_banded_ex_device", "ptx_film_resolve_counts_ex_device", "ptx_tile_list_stats",
     "ptx_scene_set_texture_image", "ptx_scene_set_environment", "ptx_scene_texture_image", "ptx_scene_environment",
-    "ptx_texture_eval", "ptx_environment_eval", "ptx_walk_rays",
+    "ptx_texture_eval", "ptx_environment_eval", "ptx_walk_rays", "ptx_walk_next_leaf",
     "ptx_scene_set_environment_sampling", "ptx_scene_environment_sampling", "ptx_environment_distribution",
     "ptx_environment_sample", "ptx_environment_pdf",
     "ptx_scene_set_lens", "ptx_scene_lens",
@@ -167,6 +167,8 @@ def lib():
         L.ptx_light_pdf.argtypes = [C.c_void_p, C.c_int64, dp, dp, dp]
     if hasattr(L, "ptx_walk_rays"):  # (likewise)
         L.ptx_walk_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, ip]
+    if hasattr(L, "ptx_walk_next_leaf"):  # (likewise)
+        L.ptx_walk_next_leaf.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dp, dp, ip, dp, ip]
     if hasattr(L, "ptx_kernel_table"):  # (likewise)
         L.ptx_kernel_table.argtypes = [C.c_char_p, C.c_int64]
         L.ptx_scene_launched_kernels.argtypes = [C.c_void_p, ip, C.c_int32]
@@ -910,6 +912,20 @@ class Scene:
         prim = np.zeros(n, dtype=np.int32)
         _check(lib().ptx_walk_rays(self._h, int(walk), n, _dp(o), _dp(d), _dp(t), _ip(prim)))
         return t, prim
+
+    def walk_next_leaf(self, walk, origins, directions, nodes, t_max):
+        """ptx_walk_next_leaf: per (ray, node of tree()'s numbering, closest hit so far) the first slot of the next leaf whose box
+        test the walk (abi.PTX_NEXT_LEAF_WALKS) passes, starting with the visit of the node; -1 when the walk runs off the tree."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        k = np.ascontiguousarray(nodes, dtype=np.int32)
+        tm = np.ascontiguousarray(t_max, dtype=np.float64)
+        n = o.shape[0]
+        if d.shape[0] != n or k.shape[0] != n or tm.shape[0] != n:
+            raise ValueError("origins, directions, nodes and t_max must have one entry per triple")
+        leaf = np.zeros(n, dtype=np.int32)
+        _check(lib().ptx_walk_next_leaf(self._h, int(walk), n, _dp(o), _dp(d), _ip(k), _dp(tm), _ip(leaf)))
+        return leaf
 
     def launched_kernels(self):
         """ptx_scene_launched_kernels: the names (kernel_table()'s) of the hot kernels' instantiations launched on this handle since

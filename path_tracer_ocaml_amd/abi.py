@@ -235,6 +235,9 @@ PTX_IMAGE_MAX_SIZE = 16384
 # ptx_walk_rays: which of the bounce kernels' walks to run (include/ptx.h)
 (PTX_WALK_SHARED_ASM, PTX_WALK_OCT_ASM, PTX_WALK_SHARED_DIV, PTX_WALK_PACKET, PTX_WALK_SHARED_ASM_ZERO, PTX_WALK_OCT_ASM_ZERO,
  PTX_WALK_SHARED_DIV_ZERO, PTX_WALK_SHARED_ASM_TAIL, PTX_WALK_OCT_ASM_TAIL, PTX_WALK_SHARED_DIV_TAIL) = range(10)
+# ptx_walk_next_leaf: the walks with a node loop of their own (no PACKET, no _TAIL)
+PTX_NEXT_LEAF_WALKS = (PTX_WALK_SHARED_ASM, PTX_WALK_OCT_ASM, PTX_WALK_SHARED_DIV, PTX_WALK_SHARED_ASM_ZERO, PTX_WALK_OCT_ASM_ZERO,
+                       PTX_WALK_SHARED_DIV_ZERO)
 
 # ptx_kernel_table: the kernel families its names begin with, in table order (include/ptx.h)
 PTX_KERNEL_FAMILIES = ("k_trace", "k_shade_pool", "k_bounce_carry", "k_bounce")

@@ -1094,6 +1094,16 @@ struct PtTraverser {
       node = hit ? oct_link : oct_skip;
     }
   }
+  /* the first slot of the leaf this lane holds (holds_leaf(), the LDS images), read where packet() reads it and nothing of the walk
+   * touched: k_next_leaf_eval, which reports the leaf and never enters it */
+  __device__ __forceinline__ int held_leaf_first(const PtSceneView& sv) const {
+    static_assert(TAGGED || LOCT, "the LDS images' walks");
+    if (LOCT) {
+      const uint32_t rec = node & (PT_LOCT_LEAF_TAG - 1u);
+      return (int)(*(const __attribute__((address_space(3))) uint32_t*)PT_LDS_AT(sv.oct_leaf + ((rec - skip_off) << 2)) & 0xffffu);
+    }
+    return (int)(lkx & 0xffffu);
+  }
   /* Leaf.intersect on the held leaf (caller checks leaf_n > 0) */
   __device__ __forceinline__ void packet(const PtSceneView& sv, unsigned long long& c_nodes, unsigned long long& c_floor) {
     const double t_min = 0.0;
@@ -4220,6 +4230,76 @@ __global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_walk_eva
       t_out[i] = r.t;
       slot_out[i] = r.slot;
     }
+  }
+}
+
+/* ptx_walk_next_leaf: the BOX DECISIONS of the same walks, one at a time.  Per (ray, node, closest hit so far) the first slot of the
+ * next leaf whose box test the walk passes, starting with the visit of `node`; -1 when the walk runs off the tree first.  k_walk_eval's
+ * shape (launch bounds, image, 64 triples per wave).  A lane is put where a resumed parked walk is put (pt_trace_ray, the
+ * `tc->resume` block): begin(), then the node as the image's own link, r.t and update_t32().  Then the production node phase and
+ * nothing else -- packet() is never called, so the closest hit stays the caller's and what comes out depends on box decisions alone.
+ * Nothing of a visit is restated: the filter, nested_hit and slab64 are PtTraverser's.
+ * The dispatch below is pt_trace_ray's node phase (its three `if constexpr` branches), spelled again: taking it out of pt_trace_ray
+ * into a function of its own would hand the compiler other code for every kernel that inlines it.  Keep the two alike. */
+template <int MODE, bool LOCT, bool ZERO>
+__global__ __launch_bounds__(PT_BOUNCE_THREADS, PT_BOUNCE_WAVES) void k_next_leaf_eval(PtSceneDev sc, long long n, const double* __restrict__ o3,
+                                                                                         const double* __restrict__ d3, const int32_t* __restrict__ node_in,
+                                                                                         const double* __restrict__ t_max, int32_t* __restrict__ leaf_out,
+                                                                                         int stack_depth) {
+  extern __shared__ __attribute__((aligned(64))) unsigned char lds_raw[];
+  static_assert(!LOCT || MODE == PT_MODE_SIMD, "the per-octant LDS image: Simd_leaf");
+  typedef typename std::conditional<LOCT, PtLdsOctTag, uint16_t>::type StackT;
+  typedef PtTraverser<MODE, false, ZERO, StackT, true> Walk;
+  constexpr int WALK_MIN = PT_WALK_MIN;
+  const int lane = pt_lane(), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+  StackT* stack = LOCT ? nullptr : (StackT*)(lds_raw + (size_t)wave * PT_WAVE_STACK_BYTES(true, stack_depth));
+  PtSceneView sv = pt_scene_view<MODE, true, LOCT>(sc, lds_raw, stack_depth); /* ends with the workgroup's only barrier */
+  const long long chunks = (n + PT_WAVE - 1) / PT_WAVE;
+  unsigned long long c_nodes = 0, c_prims = 0, no_count = 0; /* (not counting: the walk leaves them alone) */
+  for (long long c = (long long)blockIdx.x * nw + wave; c < chunks; c += (long long)gridDim.x * nw) { /* wave-uniform */
+    const long long i = c * PT_WAVE + lane;
+    const bool valid = i < n;
+    V3 o = v3(0.0, 0.0, 0.0), d = v3(0.0, 0.0, -1.0);
+    uint32_t k = 0u;
+    double tm = 0.0;
+    if (valid) {
+      if (!ZERO) o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]);
+      d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+      k = (uint32_t)node_in[i]; /* 0 .. n_nodes - 1: the host has checked */
+      tm = t_max[i];
+    }
+    Walk tr;
+    tr.begin(sc, sv, o, d, no_count);
+    /* a lane without a triple has ended; the others stand on node k of ptx_scene_tree's numbering: its record of the ray's octant
+     * (LOCT: begin() left the octant's first record in skip_off), or its absolute LDS address in the shared image */
+    if (LOCT) tr.node = valid ? tr.skip_off + k : (uint32_t)PT_LOCT_END;
+    else tr.node = valid ? sv.swz_root + k * (uint32_t)PT_SWZ_NODE_BYTES : (uint32_t)PT_SWZ_END;
+    tr.r.t = tm;
+    tr.update_t32();
+    while (tr.wants_node_mask() != 0ull) { /* wave-uniform: the node phase again until every lane holds a leaf or has ended */
+      if constexpr ((PT_WALK_ASM != 0) && (PT_DIAG == 0) && MODE == PT_MODE_SIMD && LOCT) {
+#if PT_WALK_ASM
+        while (tr.walk_asm_oct(sv.oct_base, WALK_MIN) != 0ull)
+          if (tr.wants_node()) tr.node_step(sv, stack, c_nodes, c_prims);
+#endif
+      } else if constexpr ((PT_WALK_ASM != 0) && (PT_DIAG == 0) && MODE == PT_MODE_SIMD) {
+#if PT_WALK_ASM
+        while (tr.walk_asm(WALK_MIN) != 0ull)
+          if (tr.wants_node()) tr.node_step(sv, stack, c_nodes, c_prims);
+#endif
+      } else {
+        if (tr.wants_node()) { /* pt_trace_ray's DIV_LOOP on a tagged image */
+          const unsigned long long entered = __builtin_amdgcn_ballot_w64(true);
+          for (;;) {
+            tr.node_step(sv, stack, c_nodes, c_prims);
+            if (!tr.wants_node()) break;
+            const unsigned long long now = __builtin_amdgcn_ballot_w64(true);
+            if (now != entered && pt_popc_mask(now) < WALK_MIN) break;
+          }
+        }
+      }
+    }
+    if (valid) leaf_out[i] = tr.holds_leaf() ? tr.held_leaf_first(sv) : -1;
   }
 }
 

@@ -4653,6 +4653,74 @@ int32_t ptx_walk_rays(ptx_scene* s, int32_t walk, int64_t n, const double* origi
   return 0;
 }
 
+namespace {
+/* k_next_leaf_eval: 6 = the walks with a node loop of their own x {plain, origin zero}.  Template arguments: <MODE, LOCT, ZERO>. */
+using NextLeafKernel = decltype(&k_next_leaf_eval<PT_MODE_SIMD, false, false>);
+NextLeafKernel next_leaf_kernel(int walk) {
+  switch (walk) {
+    case PTX_WALK_SHARED_ASM: return k_next_leaf_eval<PT_MODE_SIMD, false, false>;
+    case PTX_WALK_SHARED_ASM_ZERO: return k_next_leaf_eval<PT_MODE_SIMD, false, true>;
+    case PTX_WALK_OCT_ASM: return k_next_leaf_eval<PT_MODE_SIMD, true, false>;
+    case PTX_WALK_OCT_ASM_ZERO: return k_next_leaf_eval<PT_MODE_SIMD, true, true>;
+    case PTX_WALK_SHARED_DIV: return k_next_leaf_eval<PT_MODE_ARRAY, false, false>;
+    case PTX_WALK_SHARED_DIV_ZERO: return k_next_leaf_eval<PT_MODE_ARRAY, false, true>;
+    default: return nullptr;
+  }
+}
+}  // namespace
+
+int32_t ptx_walk_next_leaf(ptx_scene* s, int32_t walk, int64_t n, const double* origins, const double* directions, const int32_t* nodes,
+                           const double* t_max, int32_t* leaf_out) {
+  if (!s || !origins || !directions || !nodes || !t_max || !leaf_out) return fail(PTX_ERR_ARG, "NULL argument");
+  const NextLeafKernel kern = next_leaf_kernel(walk);
+  if (!kern) return fail(PTX_ERR_ARG, "unknown walk %d (the walks with a node loop of their own: no PACKET, no _TAIL)", walk);
+  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
+  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad triple count");
+  HIP_TRY(hipSetDevice(s->device));
+  reschedule(s, 1);
+  const Schedule& sc = s->sched;
+  /* what the scene can take: ptx_walk_rays' conditions */
+  const bool simd = s->dev.mode == PT_MODE_SIMD;
+  const bool oct = walk == PTX_WALK_OCT_ASM || walk == PTX_WALK_OCT_ASM_ZERO;
+  const bool div = walk == PTX_WALK_SHARED_DIV || walk == PTX_WALK_SHARED_DIV_ZERO;
+  const bool zero = walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_SHARED_DIV_ZERO;
+  if (!sc.in_lds() || sc.from_hbm) return fail(PTX_ERR_STATE, "walk %d: the scene is walked from HBM / L2, these walks run on LDS-resident scenes", walk);
+  if (!div && !simd) return fail(PTX_ERR_STATE, "walk %d is a Simd_leaf walk and the scene is Array_leaf", walk);
+  if (div && simd) return fail(PTX_ERR_STATE, "walk %d is the Array_leaf walk and the scene is Simd_leaf", walk);
+  if (oct && (s->dev.lds_oct == nullptr || !sc.carry_oct.fits)) return fail(PTX_ERR_STATE, "walk %d: the scene has no per-octant LDS image, or a launch does not fit with it", walk);
+  if (!oct && !sc.carry.fits) return fail(PTX_ERR_STATE, "walk %d: a launch of the bounce kernel does not fit LDS with the scene's image", walk);
+  if (sc.bounce_threads > PT_BOUNCE_THREADS) return fail(PTX_ERR_STATE, "walk %d: workgroups of %d threads", walk, sc.bounce_threads);
+  if (zero) {
+    const double pz = 0.0;
+    for (int64_t k = 0; k < 3 * n; ++k)
+      if (std::memcmp(&origins[k], &pz, sizeof pz) != 0)
+        return fail(PTX_ERR_ARG, "walk %d takes the origin as (+0, +0, +0): component %lld of the origins is %a", walk, (long long)k, origins[k]);
+  }
+  const int64_t n_nodes = (int64_t)s->host->nodes.size();
+  for (int64_t k = 0; k < n; ++k) {
+    if (nodes[k] < 0 || (int64_t)nodes[k] >= n_nodes) return fail(PTX_ERR_ARG, "triple %lld: node %d is not one of the tree's %lld", (long long)k, nodes[k], (long long)n_nodes);
+    if (!(t_max[k] >= 0.0)) return fail(PTX_ERR_ARG, "triple %lld: t_max %a is NaN or negative", (long long)k, t_max[k]);
+  }
+  if (n == 0) return 0;
+  LocalBuf<double> d_o, d_d, d_t;
+  LocalBuf<int32_t> d_k, d_l;
+  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3)); HIP_TRY(d_t.ensure((size_t)n)); HIP_TRY(d_k.ensure((size_t)n)); HIP_TRY(d_l.ensure((size_t)n));
+  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_t.p, t_max, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_k.p, nodes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  /* ptx_walk_rays' launch: k_bounce_carry's workgroup, its dynamic LDS for this image, one workgroup (one scene image) per CU */
+  prepare_kernel(s, (const void*)kern, "k_next_leaf_eval", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
+  const int threads = sc.bounce_threads;
+  const int grid = strided_grid(s, (size_t)n, threads, 1);
+  const int stack_depth = std::max(1, s->tree_depth + 1);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, nullptr, s->dev, (long long)n, d_o.p, d_d.p, d_k.p, d_t.p, d_l.p, stack_depth);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(leaf_out, d_l.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int32_t ptx_kernel_table(char* names_out, int64_t capacity) {
   const std::vector<KernelEntry>& table = kernel_table();
   if (!names_out) return (int32_t)table.size();
