@@ -317,6 +317,41 @@ let camera_pose scene =
     let get i = Bigarray.Array1.get out i in
     Some (Array.init 3 get, Array.init 9 (fun i -> get (3 + i)), (get 12, get 13, get 14, get 15)))
 
+(* The camera shutter (ptx_scene_set_camera_shutter; the rule is in include/ptx.h): while a frame is exposed the camera moves from the
+   pose's origin by [translation] (3 floats, scene space) and turns by [angle] radians about the unit vector [axis] (3 floats, scene
+   space), at constant velocity, so every later render of the scene is blurred by that motion.  Sticky.  Any shutter, a zero motion
+   included, switches the shutter's route on; [clear_camera_shutter] switches it off, which is a scene's first state: its own launches,
+   bit for bit.  Failure for a non-finite value, |angle| > pi, an axis that is not a unit vector while angle <> 0, or while a render runs
+   on the scene.  [camera_shutter]: None while off, else (translation, axis, angle). *)
+external set_camera_shutter_raw
+  :  scene
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> unit
+  = "ptx_ml_set_camera_shutter_stub"
+
+external clear_camera_shutter : scene -> unit = "ptx_ml_clear_camera_shutter_stub"
+
+external camera_shutter_raw
+  :  scene
+  -> (float, Bigarray.float64_elt, Bigarray.c_layout) Bigarray.Array1.t
+  -> int
+  = "ptx_ml_camera_shutter_stub"
+
+let set_camera_shutter scene ~translation ~axis ~angle =
+  if Array.length translation <> 3 || Array.length axis <> 3
+  then invalid_arg "Ptx.set_camera_shutter: translation and axis hold 3 floats each";
+  set_camera_shutter_raw
+    scene
+    (Bigarray.Array1.of_array Bigarray.float64 Bigarray.c_layout (Array.concat [ translation; axis; [| angle |] ]))
+
+let camera_shutter scene =
+  let out = Bigarray.Array1.create Bigarray.float64 Bigarray.c_layout 7 in
+  if camera_shutter_raw scene out = 0
+  then None
+  else (
+    let get i = Bigarray.Array1.get out i in
+    Some (Array.init 3 get, Array.init 3 (fun i -> get (3 + i)), get 6))
+
 (* The camera projection (ptx_scene_set_camera_projection; the rule is in include/ptx.h): [Perspective] is the pinhole, a scene's first
    state; [Latlong] is a 360-degree panorama in the environment map's (u, v) convention, taken from the pose's origin (the scene's own
    while the pose is off): written as a PFM it lights another scene.  Sticky.  Failure for [Latlong] while a lens is on, or while a

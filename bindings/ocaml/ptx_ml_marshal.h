@@ -332,6 +332,21 @@ static __attribute__((unused)) int32_t ptx_ml_set_camera_projection(ptx_scene* s
 }
 static __attribute__((unused)) int32_t ptx_ml_camera_projection(const ptx_scene* s) { return ptx_scene_camera_projection(s); }
 
+/* Ptx.set_camera_shutter / Ptx.clear_camera_shutter / Ptx.camera_shutter: how the camera moves while a frame is exposed
+ * (ptx_scene_set_camera_shutter).  motion: the 7 doubles translation (3), axis (3), angle; -4 for any other length (clearing is a call of
+ * its own: nothing is switched off by accident). */
+static __attribute__((unused)) int32_t ptx_ml_set_camera_shutter(ptx_scene* s, const double* motion, int64_t n_motion) {
+  if (n_motion != 7) return -4;
+  return ptx_scene_set_camera_shutter(s, motion, motion + 3, motion[6]);
+}
+static __attribute__((unused)) int32_t ptx_ml_clear_camera_shutter(ptx_scene* s) { return ptx_scene_set_camera_shutter(s, NULL, NULL, 0.0); }
+/* out: 7 doubles -- translation, axis, angle; returns 1 = on, 0 = off, or the library's (negative) code; -4 when out is not 7 long
+ * (nothing is written) */
+static __attribute__((unused)) int32_t ptx_ml_camera_shutter(const ptx_scene* s, double* out, int64_t n_out) {
+  if (n_out != 7) return -4;
+  return ptx_scene_camera_shutter(s, out, out + 3, out + 6);
+}
+
 /* Ptx.render_rays (ptx_render_rays): params3 = max_bounces, rays_per_bin, normalize (0 / 1); origins and directions 3 n doubles each,
  * offsets n int32 or n_offsets = 0 for offset i = i, sums 3 (n / rays_per_bin) doubles, sq as many or n_sq = 0 for none.  -4 for
  * lengths that do not fit together (nothing is read or written); the library's own refusals keep their codes. */

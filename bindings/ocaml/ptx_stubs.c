@@ -472,6 +472,50 @@ CAMLprim value ptx_ml_camera_pose_stub(value handle, value out) {
   CAMLreturn(Val_int(rc));
 }
 
+/* external set_camera_shutter_raw : scene -> doubles -> unit = "ptx_ml_set_camera_shutter_stub" (ptx_scene_set_camera_shutter: a Bigarray
+ * of the 7 doubles translation, axis, angle).  What a running render's camera rays are made of: like set_camera_pose it takes the scene
+ * exclusively and raises Failure while a render runs on another thread or domain, and Failure with the library's message for a refused
+ * shutter. */
+CAMLprim value ptx_ml_set_camera_shutter_stub(value handle, value motion) {
+  CAMLparam2(handle, motion);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.set_camera_shutter: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.set_camera_shutter: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_set_camera_shutter(s, (const double*)Caml_ba_data_val(motion), (int64_t)Caml_ba_array_val(motion)->dim[0]);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.set_camera_shutter: scene already destroyed");
+  if (rc == -4) caml_invalid_argument("Ptx.set_camera_shutter: the motion must hold 7 doubles");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external clear_camera_shutter : scene -> unit = "ptx_ml_clear_camera_shutter_stub" (ptx_scene_set_camera_shutter(scene, NULL, NULL, 0)) */
+CAMLprim value ptx_ml_clear_camera_shutter_stub(value handle) {
+  CAMLparam1(handle);
+  if (!Scene_val(handle)) caml_invalid_argument("Ptx.clear_camera_shutter: scene already destroyed");
+  if (!ptx_ml_scene_acquire_exclusive(handle)) caml_failwith("Ptx.clear_camera_shutter: a render is running on this scene");
+  ptx_scene* s = __atomic_load_n(&Handle_val(handle)->scene, __ATOMIC_ACQUIRE);
+  int32_t rc = 0;
+  if (s) rc = ptx_ml_clear_camera_shutter(s);
+  ptx_ml_scene_release_exclusive(handle);
+  if (!s) caml_invalid_argument("Ptx.clear_camera_shutter: scene already destroyed");
+  if (rc != 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_unit);
+}
+
+/* external camera_shutter_raw : scene -> doubles -> int = "ptx_ml_camera_shutter_stub" (ptx_scene_camera_shutter into a Bigarray of 7
+ * doubles: translation, axis, angle; 1 = on, 0 = off) */
+CAMLprim value ptx_ml_camera_shutter_stub(value handle, value out) {
+  CAMLparam2(handle, out);
+  ptx_scene* s = Scene_val(handle);
+  if (!s) caml_invalid_argument("Ptx.camera_shutter: scene already destroyed");
+  const int32_t rc = ptx_ml_camera_shutter(s, (double*)Caml_ba_data_val(out), (int64_t)Caml_ba_array_val(out)->dim[0]);
+  if (rc == -4) caml_invalid_argument("Ptx.camera_shutter: the output must hold 7 doubles");
+  if (rc < 0) caml_failwith(ptx_last_error());
+  CAMLreturn(Val_int(rc));
+}
+
 /* external set_camera_projection_int : scene -> int -> unit = "ptx_ml_set_camera_projection_stub" (ptx_scene_set_camera_projection).  What
  * a running render's camera rays are made of: like set_lens it takes the scene exclusively and raises Failure while a render runs on
  * another thread or domain, and Failure with the library's message for a refused projection (an unknown kind, LATLONG under a lens). */

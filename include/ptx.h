@@ -825,7 +825,8 @@ int32_t ptx_light_pdf(ptx_scene* scene, int64_t n, const double* points, const d
  * from there in the walk-first order: no fused camera launch, no shade-first order, no per-octant LDS image,
  * no camera tile lists, no solo run.  The queue keeps the fused launch's order -- 64 consecutive entries are one 8 x 8 pixel tile
  * of one pass; the lanes of a ragged tile that fall off the image are holes, marked as the queues mark theirs.
- * Out of scope: polygonal or anamorphic apertures, focus by picking a pixel, motion blur, a lens in the photon mapper. */
+ * Out of scope: polygonal or anamorphic apertures, focus by picking a pixel, a lens in the photon mapper.  (Motion blur of a moving
+ * camera: the camera shutter below; with it the lens pair is the two dimensions BEFORE the last.) */
 int32_t ptx_scene_set_lens(ptx_scene* scene, double radius, double focus_distance);
 int32_t ptx_scene_lens(const ptx_scene* scene, double* radius_out, double* focus_distance_out);
 
@@ -886,8 +887,9 @@ int32_t ptx_scene_lens(const ptx_scene* scene, double* radius_out, double* focus
  * (width, height, samples_per_pixel and max_bounces, which with a lens sets the sampler's dimension) -- the pose's, a lens's or the
  * pinhole's, whatever the handle's state selects.  Host in, host out: origins_out and directions_out take 3 n doubles each.
  *
- * Out of scope: shutter motion blur (a time dimension would push the sampler past its 256-entry tables at depth 126 with a lens);
- * a pose in the photon mapper; moving the geometry instead of the camera; the fused camera launch for poses that happen to have
+ * A camera that moves while a frame is exposed: the camera shutter below (its time dimension keeps the sampler inside its 256-entry
+ * tables by capping a lens + shutter render at 125 bounces).
+ * Out of scope: a pose in the photon mapper; moving the geometry instead of the camera; the fused camera launch for poses that happen to have
  * origin 0. */
 int32_t ptx_scene_set_camera_pose(ptx_scene* scene, const double origin[3], const double rotation[9] /* row-major */,
                                   const ptx_camera* view /* NULL = the scene's own llx, lly, vx, vy */);
@@ -935,6 +937,61 @@ int32_t ptx_camera_rays(ptx_scene* scene, const ptx_render_params* params, int64
 #define PTX_PROJECTION_LATLONG 1
 int32_t ptx_scene_set_camera_projection(ptx_scene* scene, int32_t projection);
 int32_t ptx_scene_camera_projection(const ptx_scene* scene); /* the kind, or a negative code */
+
+/* ---- camera shutter: motion blur between two poses ----
+ * Every frame of a posed sequence is exposed for an instant, so a moving camera strobes.  ptx_scene_set_camera_shutter lets the camera
+ * move while the frame is exposed: each sample draws a time t in [0, 1) and sees the scene from the camera of that time.  Only entry
+ * points are added: no struct or call changes, the ABI version stays 6.
+ *
+ * ptx_scene_set_camera_shutter(scene, translation, axis, angle): sticky state of the handle, like the pose.  While the shutter is open
+ * the camera moves from the pose's origin o to o + translation and turns from the pose's rotation R to Rot(axis, angle) * R, at
+ * constant velocity and constant angular velocity.  translation and axis are in scene space, axis is a unit vector, angle in radians.
+ *   - NULL, NULL, 0.0 switches the shutter OFF, the state of every scene that never called the setter: an off scene launches exactly
+ *     what it launched before this entry point existed, bit for bit, with the same alpha tables;
+ *   - any other accepted call switches it ON, a zero translation with angle 0 included (the axis may then be zero): an on scene always
+ *     takes the route below;
+ *   - while the shutter is on and the pose is off, the pose is origin 0 and the identity (as under PTX_PROJECTION_LATLONG).
+ * PTX_ERR_ARG with a message that starts "camera shutter: " and names the rule: translation and axis are given together or not at all
+ * (and not NULL with an angle != 0); every value finite; |angle| <= pi; and, while angle != 0, | |axis| - 1 | <= 1e-9 (the rotation's
+ * bar).  PTX_ERR_STATE while a render runs on the scene.  A refused call changes nothing.  A host-only scene accepts it; the replicas a
+ * scene owns follow it and ptx_scene_replicate copies it.  ptx_scene_camera_shutter returns 1 while the shutter is on and 0 while it
+ * is off (a negative code for a NULL scene) and writes what was set (off: zeros); any out pointer may be NULL.
+ *
+ * The rule, operation for operation (binary64, no fma, no contraction; sincos is pt_math.h's), for a sample with film coordinates
+ * (cx, cy), its time t, translation T, axis k and angle A:
+ *   a = t * A;  (sn, cs) = sincos(a);  oc = 1.0 - cs
+ *   S(w):  kw = (k.x * w.x + k.y * w.y) + k.z * w.z
+ *          c  = ((k.y * w.z) - (k.z * w.y), (k.z * w.x) - (k.x * w.z), (k.x * w.y) - (k.y * w.x))
+ *          S(w).i = ((w.i * cs) + (c.i * sn)) + (k.i * (kw * oc))                                  i = x, y, z
+ *   ot = (o.x + (t * T.x), o.y + (t * T.y), o.z + (t * T.z))
+ *   pose, no lens:  direction = V3.normalize (S(Rv(q)));      origin = ot
+ *   pose, lens:     direction = V3.normalize (S(Rv(P - L)));  origin = (ot.x + S(Rv(L)).x, ot.y + S(Rv(L)).y, ot.z + S(Rv(L)).z)
+ *   lat-long:       direction = V3.normalize (S(Rv(e)));      origin = ot
+ *   the ray is Ray.create origin direction
+ * q, P, L, e and Rv are exactly the pose, lens and projection rules' own (kw and c are written out: V3.dot and V3.cross are fused).
+ * The vector is turned AFTER Rv and BEFORE it is normalised.  With T = 0 and A = 0, sn = 0, cs = 1 and oc = 0, so S(w) = w and
+ * ot = o: the rule gives the posed ray of the same (cx, cy, u, v), up to the sign of a zero (w * 1 + c * 0 + k * 0 turns a -0 into
+ * +0).  S is Rodrigues' rotation by t A about k, so the ray at time t is, within rounding, the posed ray of the pose
+ * (o + t T, Rot(k, t A) * R), and with a lens every sample's ray passes through that camera's focus point.
+ *
+ * Sampler dimensions.  A shutter render's sampler has ONE MORE dimension: d = 2 + 2 * max_bounces (+ 2 with a lens) + 1.  t is the
+ * LAST dimension, d - 1, at the sample's own offset; the lens pair moves to d - 3 and d - 2; the jitter and the bounces stay where
+ * they are.  alpha_i depends on d, so EVERY alpha of a shutter render differs from the same render without a shutter, as with the
+ * lens.  d stays <= 256: lens + shutter at max_bounces = 126 is PTX_ERR_ARG ("camera shutter: ... at most 125 bounces with a lens");
+ * without a lens 126 stays legal (d = 255).
+ *
+ * Entry points.  The shutter is read by ptx_render, ptx_render_multi (every scene passed must carry the same shutter: PTX_ERR_ARG
+ * otherwise), ptx_render_raw_device (bands and PTX_RENDER_ASYNC included), _passes_device, _pixels_device, _progressive, _adaptive,
+ * _denoised and the display forms, ptx_render_features_device (the first hit of the shutter ray), ptx_trace_samples and
+ * ptx_camera_rays.  A shutter scene takes the posed route whether a pose is on or not (k_generate_*, three camera kinds of their own).
+ * ptx_render_temporal (its reprojection takes one pose per frame), ptx_ppm_render and ptx_debug_first_scatter return PTX_ERR_STATE
+ * while the shutter is on ("... ptx_scene_set_camera_shutter(scene, NULL, NULL, 0) first"), before anything is queued.
+ * ptx_render_rays*, ptx_intersect_rays and ptx_walk_* take explicit rays and are unaffected.
+ *
+ * Out of scope: moving geometry or lights; a shutter curve other than uniform; a rolling shutter; motion vectors for
+ * ptx_render_temporal under a shutter; a shutter in the photon mapper. */
+int32_t ptx_scene_set_camera_shutter(ptx_scene* scene, const double translation[3], const double axis[3], double angle);
+int32_t ptx_scene_camera_shutter(const ptx_scene* scene, double translation_out[3], double axis_out[3], double* angle_out); /* 1 = on, 0 = off */
 
 /* ---- temporal accumulation: the frame history reprojected across camera poses ----
  * The temporal half of the variance-guided filter: the per-pixel moments of the frames before are carried into the new frame by

@@ -49,6 +49,7 @@ EXPORTS = (
     "ptx_temporal_defaults", "ptx_temporal_accumulate_device", "ptx_render_temporal", "ptx_temporal_reset",
     "ptx_scene_set_sphere_light_sampling", "ptx_scene_sphere_lights", "ptx_light_table", "ptx_light_sample", "ptx_light_pdf",
     "ptx_render_rays_device", "ptx_render_rays", "ptx_scene_set_camera_projection", "ptx_scene_camera_projection",
+    "ptx_scene_set_camera_shutter", "ptx_scene_camera_shutter",
     "ptx_kernel_table", "ptx_scene_launched_kernels", "ptx_scene_clear_launched_kernels",
     "ptx_display_defaults", "ptx_display_check", "ptx_display_pixel_bytes", "ptx_display_thresholds", "ptx_display_apply",
     "ptx_display_image_device", "ptx_display_range_device", "ptx_image_pin_bytes", "ptx_render_display", "ptx_render_progressive_display",
@@ -196,6 +197,9 @@ def lib():
     if hasattr(L, "ptx_scene_set_camera_projection"):  # (likewise)
         L.ptx_scene_set_camera_projection.argtypes = [C.c_void_p, C.c_int32]
         L.ptx_scene_camera_projection.argtypes = [C.c_void_p]
+    if hasattr(L, "ptx_scene_set_camera_shutter"):  # (likewise)
+        L.ptx_scene_set_camera_shutter.argtypes = [C.c_void_p, dp, dp, C.c_double]
+        L.ptx_scene_camera_shutter.argtypes = [C.c_void_p, dp, dp, dp]
     if hasattr(L, "ptx_render_display"):  # (likewise)
         dpp = C.POINTER(abi.DisplayParams)
         L.ptx_display_defaults.argtypes = [dpp]
@@ -375,6 +379,30 @@ class Scene:
         if rc < 0:
             _check(rc)
         return abi.PTX_PROJECTION_NAMES[rc]
+
+    def set_camera_shutter(self, translation=None, axis=None, angle=0.0):
+        """ptx_scene_set_camera_shutter: while a frame is exposed the camera moves from the pose's origin by `translation` (3 doubles,
+        scene space) and turns by `angle` radians about the unit vector `axis` (scene space), at constant velocity: every later
+        render of this scene is blurred by that motion (camera_shutter_between gives the three from two poses).  Sticky.
+        translation and axis go together; None (or no argument) switches the shutter off -- the scene's own launches, bit for bit;
+        anything else, a zero motion included, switches it on."""
+        if translation is None and axis is None:
+            _check(lib().ptx_scene_set_camera_shutter(self._h, None, None, float(angle)))
+            return
+        t = None if translation is None else np.ascontiguousarray(translation, dtype=np.float64).reshape(3)
+        k = None if axis is None else np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
+        _check(lib().ptx_scene_set_camera_shutter(self._h, None if t is None else _dp(t), None if k is None else _dp(k), float(angle)))
+
+    @property
+    def camera_shutter(self):
+        """ptx_scene_camera_shutter: None while the shutter is off, else (translation (3,), axis (3,), angle)"""
+        t, k, a = np.zeros(3), np.zeros(3), C.c_double()
+        rc = lib().ptx_scene_camera_shutter(self._h, _dp(t), _dp(k), C.cast(C.byref(a), dp))
+        if rc < 0:
+            _check(rc)
+        if rc == 0:
+            return None
+        return t, k, a.value
 
     def camera_rays(self, width, height, samples_per_pixel, max_bounces, xs, ys, passes):
         """ptx_camera_rays (diagnostic): (origins (n, 3), directions (n, 3)) of the camera rays this scene's renders launch for the
@@ -984,6 +1012,12 @@ def camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg):
     over a scene built for the camera whose Mat4.look_at rows are scene_look_at"""
     from . import host
     return host.camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg)
+
+
+def camera_shutter_between(origin0, rotation0, origin1, rotation1):
+    """host.camera_shutter_between: (translation, axis, angle) for Scene.set_camera_shutter -- the motion that takes the camera from
+    pose 0 to pose 1 (two results of camera_pose_look_at) while the shutter is open; the turn is R1 R0^T."""
+    return host.camera_shutter_between(origin0, rotation0, origin1, rotation1)
 
 
 def _image_arg(a, width, height, name):

@@ -1,5 +1,5 @@
 /* camera_rays.inc -- camera rays written into a path queue (included from kernels.hip; the rules: include/ptx.h and pt_lens.h,
- * pt_camera_pose.h, pt_projection.h).
+ * pt_camera_pose.h, pt_projection.h, pt_shutter.h).
  * The fused camera launches take a pinhole at the origin for granted.  Every other camera, and every render of a list of pixels or
  * samples, WRITES its camera rays into a queue and bounces them from there like any queued rays.  A camera is one arm of
  * pt_camera_sample_ray and an enumeration of samples is one kernel templated on the camera, so nothing here is written per camera.
@@ -8,6 +8,7 @@
 #include "pt_lens.h"
 #include "pt_camera_pose.h"
 #include "pt_projection.h"
+#include "pt_shutter.h"
 
 /* The camera of a launch.  A new kind is four edits and nothing else: a value here, an arm in pt_camera_sample_ray, an arm in the
  * host's camera_kind and a line in the host's with_camera_kind (ptx_api.inc). */
@@ -17,11 +18,15 @@ enum PtCameraKind {
   PT_CAM_POSE,      /* a posed camera (pt_camera_pose.h) */
   PT_CAM_POSE_LENS, /* ... through a thin lens */
   PT_CAM_LATLONG,   /* the lat-long panorama from the pose's origin (pt_projection.h) */
+  PT_CAM_POSE_SHUTTER,      /* the posed camera, moving while its shutter is open (pt_shutter.h) */
+  PT_CAM_POSE_LENS_SHUTTER, /* ... through a thin lens */
+  PT_CAM_LATLONG_SHUTTER,   /* the panorama from a moving pose */
 };
 /* what the kinds read besides the scene: a kind reads the fields of its rule and no other (a pinhole's alpha table has no lens pair) */
 struct PtCameraArg {
   PtCameraPose pose;
   PtLens lens;
+  PtShutter shutter;
 };
 
 /* render_tile's film coordinates of sample (x, gy) with sampler offset `offset` (integrator.ml:98-105) */
@@ -34,12 +39,13 @@ __device__ __forceinline__ void pt_film_coords(const double* __restrict__ alpha,
 }
 
 /* The camera ray of sample (x, gy) with sampler offset `offset`.  A lens pair comes from the sampler's last two dimensions at the same
- * offset; pose and projection add no dimension.  Each kind calls its own rule with its own operands: the kinds agree with one another
+ * offset, or the two before the last where a shutter's time is the last; pose and projection add no dimension.  Each kind calls its own rule with its own operands: the kinds agree with one another
  * only up to the sign of a zero (pt_camera_pose.h), and the tests compare bits. */
 template <int CAM>
 __device__ __forceinline__ void pt_camera_sample_ray(const PtSceneDev& sc, const PtCameraArg& cam, const double* __restrict__ alpha, int x,
                                                      int gy, int width, int height, int offset, V3* o, V3* d) {
-  constexpr bool LENS = CAM == PT_CAM_LENS || CAM == PT_CAM_POSE_LENS;
+  constexpr bool LENS = CAM == PT_CAM_LENS || CAM == PT_CAM_POSE_LENS || CAM == PT_CAM_POSE_LENS_SHUTTER;
+  constexpr bool SHUTTER = CAM == PT_CAM_POSE_SHUTTER || CAM == PT_CAM_POSE_LENS_SHUTTER || CAM == PT_CAM_LATLONG_SHUTTER;
   const PtLens& ln = cam.lens;
   double cx, cy, u = 0.0, v = 0.0;
   pt_film_coords(alpha, x, gy, width, height, offset, &cx, &cy);
@@ -47,6 +53,7 @@ __device__ __forceinline__ void pt_camera_sample_ray(const PtSceneDev& sc, const
     u = pt_lds_get(alpha, offset, ln.dim - 2);
     v = pt_lds_get(alpha, offset, ln.dim - 1);
   }
+  const double t = SHUTTER ? pt_lds_get(alpha, offset, cam.shutter.dim - 1) : 0.0;
   switch (CAM) {
     case PT_CAM_PINHOLE:
       *o = v3(0.0, 0.0, 0.0);
@@ -61,6 +68,13 @@ __device__ __forceinline__ void pt_camera_sample_ray(const PtSceneDev& sc, const
       break;
     case PT_CAM_LATLONG:
       pt_latlong_ray(cam.pose, cx, cy, o, d);
+      break;
+    case PT_CAM_POSE_SHUTTER:
+    case PT_CAM_POSE_LENS_SHUTTER:
+      pt_shutter_pose_ray<LENS>(cam.pose, cam.shutter, cx, cy, ln.radius, ln.focus, u, v, t, o, d);
+      break;
+    case PT_CAM_LATLONG_SHUTTER:
+      pt_shutter_latlong_ray(cam.pose, cam.shutter, cx, cy, t, o, d);
       break;
   }
 }

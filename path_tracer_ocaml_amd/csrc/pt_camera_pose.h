@@ -26,14 +26,14 @@ PT_HD V3 pt_pose_rotate(const PtCameraPose& cp, V3 a) {
 }
 
 /* (cx, cy): the sample's film coordinates.  LENS: a lens of this radius and focus distance, (u, v) its lens pair (the steps up to
- * e and l are pt_lens.h's, which normalises where this rule has yet to rotate); otherwise the four are not read. */
+ * e and l are pt_lens.h's, which normalises where this rule has yet to rotate); otherwise the four are not read.
+ * The rule's vectors before they are rotated: e (q without a lens, P - L with one) and, with a lens, l = L (pt_shutter.h turns them
+ * once more before they are normalised). */
 template <bool LENS>
-PT_HD void pt_camera_pose_ray(const PtCameraPose& cp, double cx, double cy, double radius, double focus, double u, double v, V3* origin,
-                              V3* direction) {
+PT_HD void pt_camera_pose_vectors(const PtCameraPose& cp, double cx, double cy, double radius, double focus, double u, double v, V3* e, V3* l) {
   const V3 q = v3(cp.llx + (cp.vx * cx), cp.lly + (cp.vy * cy), -1.0);
   if (!LENS) {
-    *origin = v3(cp.o[0], cp.o[1], cp.o[2]);
-    *direction = v3_normalize(pt_pose_rotate(cp, q));
+    *e = q;
     return;
   }
   const double pi = 3.14159265358979323846; /* Float.pi */
@@ -42,10 +42,22 @@ PT_HD void pt_camera_pose_ray(const PtCameraPose& cp, double cx, double cy, doub
   const double th = (v * 2.0) * pi;
   double sn, cs;
   pt_sincos(th, &sn, &cs);
-  const V3 l = v3(radius * (r * cs), radius * (r * sn), 0.0);
-  const V3 rl = pt_pose_rotate(cp, l);
-  *origin = v3(cp.o[0] + rl.x, cp.o[1] + rl.y, cp.o[2] + rl.z);
-  *direction = v3_normalize(pt_pose_rotate(cp, v3_sub(p, l)));
+  *l = v3(radius * (r * cs), radius * (r * sn), 0.0);
+  *e = v3_sub(p, *l);
+}
+
+template <bool LENS>
+PT_HD void pt_camera_pose_ray(const PtCameraPose& cp, double cx, double cy, double radius, double focus, double u, double v, V3* origin,
+                              V3* direction) {
+  V3 e, l;
+  pt_camera_pose_vectors<LENS>(cp, cx, cy, radius, focus, u, v, &e, &l);
+  if (!LENS) {
+    *origin = v3(cp.o[0], cp.o[1], cp.o[2]);
+  } else {
+    const V3 rl = pt_pose_rotate(cp, l);
+    *origin = v3(cp.o[0] + rl.x, cp.o[1] + rl.y, cp.o[2] + rl.z);
+  }
+  *direction = v3_normalize(pt_pose_rotate(cp, e));
 }
 
 #endif /* PT_CAMERA_POSE_H */

@@ -12,9 +12,8 @@
 
 #include "pt_camera_pose.h"
 
-/* (cx, cy): the sample's film coordinates, exactly the pinhole's.  Of the pose, the origin and the rotation are read (origin 0 and the
- * identity while the pose is off); the view fields are not. */
-PT_HD void pt_latlong_ray(const PtCameraPose& cp, double cx, double cy, V3* origin, V3* direction) {
+/* e: the environment-sampling rule's direction of film point (cx, cy), before it is rotated */
+PT_HD V3 pt_latlong_vector(double cx, double cy) {
   const double pi = 3.14159265358979323846; /* Float.pi */
   const double u = cx;
   const double v = 1.0 - cy;
@@ -23,9 +22,14 @@ PT_HD void pt_latlong_ray(const PtCameraPose& cp, double cx, double cy, V3* orig
   double sa, ca, st, ct;
   pt_sincos(al, &sa, &ca);
   pt_sincos(th, &st, &ct);
-  const V3 e = v3(st * ca, -ct, -(st * sa));
+  return v3(st * ca, -ct, -(st * sa));
+}
+
+/* (cx, cy): the sample's film coordinates, exactly the pinhole's.  Of the pose, the origin and the rotation are read (origin 0 and the
+ * identity while the pose is off); the view fields are not. */
+PT_HD void pt_latlong_ray(const PtCameraPose& cp, double cx, double cy, V3* origin, V3* direction) {
   *origin = v3(cp.o[0], cp.o[1], cp.o[2]);
-  *direction = v3_normalize(pt_pose_rotate(cp, e));
+  *direction = v3_normalize(pt_pose_rotate(cp, pt_latlong_vector(cx, cy)));
 }
 
 #endif /* PT_PROJECTION_H */

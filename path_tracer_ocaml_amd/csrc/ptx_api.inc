@@ -264,6 +264,7 @@ struct Schedule {
   bool img = false;            /* an image texture or an environment: the IMG instantiations */
   bool lens = false;           /* a thin lens (ptx_scene_set_lens): camera rays are generated into a queue, never a PRIMARY launch; the walk-first order */
   bool pose = false;           /* a camera pose (ptx_scene_set_camera_pose): like a lens, camera rays are generated into a queue (k_generate_tiles) and bounced walk-first */
+  bool shutter = false;        /* a camera shutter (ptx_scene_set_camera_shutter): the posed route (pose is set with it), the _SHUTTER kinds of the generators */
   bool latlong = false;        /* the lat-long projection (ptx_scene_set_camera_projection): the posed route (pose is set with it), the PT_CAM_LATLONG kind of the generators */
   bool fused_possible = false; /* a bounce can be one k_bounce launch (PTX_FUSED, the placement, the layout fits) ... */
   bool carry_ok = false;       /* the shade-first order (k_bounce_carry) can be taken */
@@ -322,6 +323,10 @@ struct ptx_scene {
   bool pose_on = false, pose_has_view = false;
   double pose_origin[3] = {0.0, 0.0, 0.0}, pose_rotation[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
   ptx_camera pose_view = {0.0, 0.0, 0.0, 0.0};
+  /* ptx_scene_set_camera_shutter: off = the state of a scene that never called it.  While on: how far the camera moves and about
+   * which unit axis, by what angle, it turns while the shutter is open */
+  bool shutter_on = false;
+  double shutter_translation[3] = {0.0, 0.0, 0.0}, shutter_axis[3] = {0.0, 0.0, 0.0}, shutter_angle = 0.0;
   /* ptx_scene_set_camera_projection: PTX_PROJECTION_PERSPECTIVE = the state of a scene that never called it */
   int32_t projection = PTX_PROJECTION_PERSPECTIVE;
   ptx_camera own_view = {0.0, 0.0, 0.0, 0.0}; /* the descriptor's camera (a host-only scene keeps no PtSceneDev scalars) */
@@ -608,7 +613,9 @@ Schedule make_schedule(const ptx_scene* s, int sets) {
   /* The lat-long projection: rays in every direction from the pose's origin (origin 0 and the identity while the pose is off) -- the
    * posed route with a camera kind of its own (camera_rays.inc), and everything a posed scene gives up. */
   c.latlong = s->projection == PTX_PROJECTION_LATLONG;
-  c.pose = s->pose_on || c.latlong;
+  /* A camera shutter: the posed route too (origin 0 and the identity while the pose is off), with camera kinds of its own. */
+  c.shutter = s->shutter_on;
+  c.pose = s->pose_on || c.latlong || c.shutter;
   /* scenes walked from HBM / L2: the top of the tree goes to LDS (PtSceneDev.top_nodes), PTX_TRACE_TOP=0 switches it off */
   c.top_in_lds = (!in_lds && s->dev.n_top > 0 && s->trace_top) ? 1 : 0;
   c.trace_threads = in_lds ? trace_block_lds : kTraceBlockGlobal;
@@ -939,11 +946,25 @@ struct Workspace {
   size_t contrib_n = 0;
 };
 
-/* The sampler's dimension for renders of this depth: 2 + 2 max_bounces, and two more -- the last two, the lens pair -- while the
- * scene has a lens (include/ptx.h: every alpha of the table then differs from the pinhole's) */
-int sampler_dimension(const ptx_scene* s, int max_bounces) { return 2 + 2 * std::max(max_bounces, 0) + (s->lens_radius > 0.0 ? 2 : 0); }
-/* the lens of a launch (Schedule::lens) */
-PtLens scene_lens(const ptx_scene* s, int max_bounces) { return PtLens{s->lens_radius, s->lens_focus, sampler_dimension(s, max_bounces)}; }
+/* The sampler's dimension for renders of this depth: 2 + 2 max_bounces, two more -- the lens pair -- while the scene has a lens and
+ * one more -- the last, the sample's time -- while it has a shutter (include/ptx.h: every alpha of the table then differs from the
+ * pinhole's) */
+int sampler_dimension(const ptx_scene* s, int max_bounces) {
+  return 2 + 2 * std::max(max_bounces, 0) + (s->lens_radius > 0.0 ? 2 : 0) + (s->shutter_on ? 1 : 0);
+}
+/* the lens of a launch (Schedule::lens): its pair is the sampler's last two dimensions, or the two before a shutter's time */
+PtLens scene_lens(const ptx_scene* s, int max_bounces) {
+  return PtLens{s->lens_radius, s->lens_focus, sampler_dimension(s, max_bounces) - (s->shutter_on ? 1 : 0)};
+}
+/* the shutter of a launch (Schedule::shutter) */
+PtShutter scene_shutter(const ptx_scene* s, int max_bounces) {
+  PtShutter sh;
+  std::memcpy(sh.tr, s->shutter_translation, sizeof sh.tr);
+  std::memcpy(sh.k, s->shutter_axis, sizeof sh.k);
+  sh.angle = s->shutter_angle;
+  sh.dim = sampler_dimension(s, max_bounces);
+  return sh;
+}
 /* the pose of a launch (Schedule::pose): the view is the pose's own or the scene's */
 PtCameraPose scene_pose(const ptx_scene* s) {
   PtCameraPose cp;
@@ -957,12 +978,15 @@ PtCameraPose scene_pose(const ptx_scene* s) {
 /* ---- the camera of a launch: which generator instantiation writes a scene's camera rays (camera_rays.inc) ---- */
 /* the one place that maps a scene's state to a camera kind */
 PtCameraKind camera_kind(const Schedule& c) {
+  if (c.shutter) return c.latlong ? PT_CAM_LATLONG_SHUTTER : c.lens ? PT_CAM_POSE_LENS_SHUTTER : PT_CAM_POSE_SHUTTER;
   if (c.latlong) return PT_CAM_LATLONG;
   if (c.pose) return c.lens ? PT_CAM_POSE_LENS : PT_CAM_POSE;
   return c.lens ? PT_CAM_LENS : PT_CAM_PINHOLE;
 }
 /* what the kinds read, for renders of this depth (a kind reads its own fields and no other) */
-PtCameraArg scene_camera(const ptx_scene* s, int max_bounces) { return PtCameraArg{scene_pose(s), scene_lens(s, max_bounces)}; }
+PtCameraArg scene_camera(const ptx_scene* s, int max_bounces) {
+  return PtCameraArg{scene_pose(s), scene_lens(s, max_bounces), scene_shutter(s, max_bounces)};
+}
 /* the one switch over kinds: f(std::integral_constant<int, kind>) with the run-time kind made a compile-time constant */
 template <class F>
 void with_camera_kind(PtCameraKind kind, F&& f) {
@@ -972,6 +996,9 @@ void with_camera_kind(PtCameraKind kind, F&& f) {
     case PT_CAM_POSE: return f(std::integral_constant<int, PT_CAM_POSE>());
     case PT_CAM_POSE_LENS: return f(std::integral_constant<int, PT_CAM_POSE_LENS>());
     case PT_CAM_LATLONG: return f(std::integral_constant<int, PT_CAM_LATLONG>());
+    case PT_CAM_POSE_SHUTTER: return f(std::integral_constant<int, PT_CAM_POSE_SHUTTER>());
+    case PT_CAM_POSE_LENS_SHUTTER: return f(std::integral_constant<int, PT_CAM_POSE_LENS_SHUTTER>());
+    case PT_CAM_LATLONG_SHUTTER: return f(std::integral_constant<int, PT_CAM_LATLONG_SHUTTER>());
   }
 }
 /* The camera rays of a whole batch in the fused camera launch's order, written to q (pl.n entries, holes included).  path = false: the
@@ -1803,10 +1830,20 @@ int film_counts_queue(int width, int height, const double* d_raw, const int32_t*
   return 0;
 }
 
-/* What the render entry points check first, in this order: the scene handle, a device behind it, the caller's other pointers
- * (missing: the message when one of them is NULL, else nullptr), the params */
+/* the sampler's tables hold 256 dimensions: a lens and a shutter together leave room for 125 bounces (2 + 2 * 125 + 2 + 1 = 255);
+ * a depth past 126 is check_params' to refuse */
+int check_shutter_depth(const ptx_scene* s, const ptx_render_params* p) {
+  if (p && s->shutter_on && s->lens_radius > 0.0 && p->max_bounces == 126)
+    return fail(PTX_ERR_ARG, "camera shutter: the sampler has 256 dimensions, which is at most 125 bounces with a lens (got max_bounces %d)", p->max_bounces);
+  return 0;
+}
+
+/* What the render entry points check first, in this order: the scene handle, the depth a lens and a shutter leave (a host-only scene
+ * gets this answer too), a device behind it, the caller's other pointers (missing: the message when one of them is NULL, else
+ * nullptr), the params */
 int check_render_args(const ptx_scene* s, const ptx_render_params* p, const char* missing) {
   if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (const int rc = check_shutter_depth(s, p)) return rc;
   if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
   if (missing) return fail(PTX_ERR_ARG, "%s", missing);
   return check_params(p);
@@ -2368,6 +2405,63 @@ int32_t ptx_scene_camera_pose(const ptx_scene* s, double origin_out[3], double r
   return s->pose_on ? 1 : 0;
 }
 
+/* ---- camera shutter ---- */
+namespace {
+bool same_camera_shutter(const ptx_scene* a, const ptx_scene* b) {
+  if (a->shutter_on != b->shutter_on) return false;
+  return !a->shutter_on || (std::memcmp(a->shutter_translation, b->shutter_translation, sizeof a->shutter_translation) == 0 &&
+                            std::memcmp(a->shutter_axis, b->shutter_axis, sizeof a->shutter_axis) == 0 &&
+                            std::memcmp(&a->shutter_angle, &b->shutter_angle, sizeof a->shutter_angle) == 0);
+}
+void copy_camera_shutter(ptx_scene* dst, const ptx_scene* src) {
+  dst->shutter_on = src->shutter_on;
+  std::memcpy(dst->shutter_translation, src->shutter_translation, sizeof dst->shutter_translation);
+  std::memcpy(dst->shutter_axis, src->shutter_axis, sizeof dst->shutter_axis);
+  dst->shutter_angle = src->shutter_angle;
+}
+}  // namespace
+
+int32_t ptx_scene_set_camera_shutter(ptx_scene* s, const double translation[3], const double axis[3], double angle) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if ((translation == nullptr) != (axis == nullptr))
+    return fail(PTX_ERR_ARG, "camera shutter: translation and axis are given together or not at all (%s is NULL)", translation ? "axis" : "translation");
+  if (!std::isfinite(angle)) return fail(PTX_ERR_ARG, "camera shutter: angle must be finite (got %g)", angle);
+  if (!translation && angle != 0.0)
+    return fail(PTX_ERR_ARG, "camera shutter: translation and axis are given together with an angle (both are NULL, angle is %g); NULL, NULL, 0 switches the shutter off", angle);
+  if (translation) {
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(translation[i])) return fail(PTX_ERR_ARG, "camera shutter: translation must be finite (component %d is %g)", i, translation[i]);
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(axis[i])) return fail(PTX_ERR_ARG, "camera shutter: axis must be finite (component %d is %g)", i, axis[i]);
+    const double pi = 3.14159265358979323846;
+    if (!(std::fabs(angle) <= pi)) return fail(PTX_ERR_ARG, "camera shutter: |angle| must be at most pi (got %g)", angle);
+    const double len = std::sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
+    if (angle != 0.0 && !(std::fabs(len - 1.0) <= 1e-9))
+      return fail(PTX_ERR_ARG, "camera shutter: axis must be a unit vector while angle != 0: | |axis| - 1 | = %g exceeds 1e-9", std::fabs(len - 1.0));
+  }
+  if (s->busy.load() != 0) return fail(PTX_ERR_STATE, "the camera shutter cannot change while a render runs on the scene");
+  s->shutter_on = translation != nullptr;
+  for (int i = 0; i < 3; ++i) {
+    s->shutter_translation[i] = translation ? translation[i] : 0.0;
+    s->shutter_axis[i] = axis ? axis[i] : 0.0;
+  }
+  s->shutter_angle = translation ? angle : 0.0;
+  if (s->device >= 0) reschedule(s, s->sets_in_flight); /* (Schedule::shutter and ::pose, and what follows from them) */
+  for (ptx_scene* r : s->replicas) {
+    const int rr = ptx_scene_set_camera_shutter(r, translation, axis, angle);
+    if (rr) return rr;
+  }
+  return 0;
+}
+
+int32_t ptx_scene_camera_shutter(const ptx_scene* s, double translation_out[3], double axis_out[3], double* angle_out) {
+  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
+  if (translation_out) std::memcpy(translation_out, s->shutter_translation, sizeof s->shutter_translation);
+  if (axis_out) std::memcpy(axis_out, s->shutter_axis, sizeof s->shutter_axis);
+  if (angle_out) *angle_out = s->shutter_angle;
+  return s->shutter_on ? 1 : 0;
+}
+
 /* ---- image textures and the environment ---- */
 /* A setter changes a scene and its replicas together or not at all: everything that can fail -- the uploads of the texels and of
  * the slot categories and shading records made of them -- goes into fresh buffers first, for every scene (stage); only when all of
@@ -2831,6 +2925,7 @@ ptx_scene* ptx_scene_replicate(const ptx_scene* src, int32_t device) {
   s->lens_focus = src->lens_focus;
   s->own_view = src->own_view;
   copy_camera_pose(s, src);
+  copy_camera_shutter(s, src);
   s->projection = src->projection;
   if (scene_upload(s) != 0) {
     ptx_scene_destroy(s);
@@ -3046,8 +3141,12 @@ static int32_t render_many(ptx_scene* const* scenes, int32_t n, const ptx_render
       return fail(PTX_ERR_ARG, "scene %d does not carry the camera projection of scene 0 (ptx_scene_set_camera_projection): the bands would not be one image", k);
     if (!same_camera_pose(scenes[k], scenes[0]))
       return fail(PTX_ERR_ARG, "scene %d does not carry the camera pose of scene 0 (ptx_scene_set_camera_pose): the bands would not be one image", k);
+    if (!same_camera_shutter(scenes[k], scenes[0]))
+      return fail(PTX_ERR_ARG, "scene %d does not carry the camera shutter of scene 0 (ptx_scene_set_camera_shutter): the bands would not be one image", k);
   }
   int rc = check_params(p_in);
+  if (rc) return rc;
+  rc = check_shutter_depth(scenes[0], p_in);
   if (rc) return rc;
   if (n == 1) {
     ptx_render_params p1 = *p_in;
@@ -4193,6 +4292,8 @@ int32_t ptx_render_temporal(ptx_scene* s, const ptx_render_params* p_in, const p
   /* (before any device is touched: a host-only scene gets this answer too) */
   if (s && s->projection != PTX_PROJECTION_PERSPECTIVE)
     return fail(PTX_ERR_STATE, "temporal rendering needs a pinhole: its reprojection is a perspective camera's (ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first)");
+  if (s && s->shutter_on)
+    return fail(PTX_ERR_STATE, "temporal rendering takes one pose per frame: its reprojection has no shutter (ptx_scene_set_camera_shutter(scene, NULL, NULL, 0) first)");
   int rc = check_render_args(s, p_in, (tp && rgb_out) ? nullptr : "NULL argument");
   if (rc) return rc;
   rc = check_one_gpu(p_in, "temporal rendering");
@@ -4792,6 +4893,7 @@ int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_
   if (s->projection != PTX_PROJECTION_PERSPECTIVE)
     return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own pinhole: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
   if (s->pose_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
+  if (s->shutter_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera shutter off with ptx_scene_set_camera_shutter(scene, NULL, NULL, 0) first");
   int rc = check_render_args(s, p, nullptr);
   if (rc) return rc;
   if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
@@ -4849,6 +4951,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   if (s->projection != PTX_PROJECTION_PERSPECTIVE)
     return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own pinhole: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
   if (s->pose_on) return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
+  if (s->shutter_on) return fail(PTX_ERR_STATE, "the photon mapper's eye pass looks through the scene's own camera: switch the camera shutter off with ptx_scene_set_camera_shutter(scene, NULL, NULL, 0) first");
   if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
   if (p->width <= 0 || p->height <= 0 || p->iterations <= 0 || p->max_bounces <= 0 || p->max_bounces > 60 || p->photon_count <= 0 || n_lights <= 0)
     return fail(PTX_ERR_ARG, "bad photon-mapping parameters");

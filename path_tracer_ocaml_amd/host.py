@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(_HERE, "libpt_host.so")
 _LIB = None
 
-EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_scene_camera", "pth_camera_create", "pth_camera_pose_look_at", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
+EXPORTS = ("pth_scene_desc", "pth_scene_free", "pth_scene_focus_distance", "pth_scene_camera", "pth_camera_create", "pth_camera_pose_look_at", "pth_camera_shutter_between", "pth_scene_shirley", "pth_scene_shirley_lamp", "pth_scene_cornell", "pth_scene_cornell_lamp",
            "pth_scene_ganesha_like", "pth_write_png", "pth_write_png8", "pth_last_error", "pth_ply_load", "pth_ply_free", "pth_ply_count",
            "pth_ply_floats", "pth_ply_ints", "pth_ply_rows", "pth_scene_ganesha_ply", "pth_write_ganesha_like_ply", "pth_lights_cornell", "pth_lights_ganesha", "pth_ppm_gamma")
 
@@ -32,6 +32,7 @@ def lib():
         L.pth_scene_camera.argtypes = [C.c_void_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
         L.pth_camera_pose_look_at.argtypes = [abi.c_double_p, abi.c_double_p, abi.c_double_p, abi.c_double_p, C.c_double, C.c_double,
                                               abi.c_double_p, abi.c_double_p, C.POINTER(abi.Camera)]
+        L.pth_camera_shutter_between.argtypes = [abi.c_double_p] * 7
         L.pth_scene_shirley.restype = C.c_void_p
         L.pth_scene_shirley.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
         L.pth_scene_cornell.restype = C.c_void_p
@@ -173,6 +174,19 @@ def camera_pose_look_at(scene_look_at, eye, target, up, aspect, fov_deg):
     lib().pth_camera_pose_look_at(m.ctypes.data_as(dp), e.ctypes.data_as(dp), t.ctypes.data_as(dp), u.ctypes.data_as(dp), float(aspect),
                                   float(fov_deg), o.ctypes.data_as(dp), r.ctypes.data_as(dp), C.byref(view))
     return o, r.reshape(3, 3), (view.lower_left_x, view.lower_left_y, view.view_x, view.view_y)
+
+
+def camera_shutter_between(origin0, rotation0, origin1, rotation1):
+    """pth_camera_shutter_between: (translation (3,), axis (3,), angle) of the motion from pose 0 to pose 1 -- the turn is
+    R1 R0^T about a unit axis of the scene's space; Scene.set_camera_shutter(*shutter) on a scene posed at pose 0 exposes the frame
+    while the camera moves to pose 1."""
+    dp = abi.c_double_p
+    o0, o1 = (np.ascontiguousarray(a, dtype=np.float64).reshape(3) for a in (origin0, origin1))
+    r0, r1 = (np.ascontiguousarray(a, dtype=np.float64).reshape(9) for a in (rotation0, rotation1))
+    t, k, angle = np.zeros(3), np.zeros(3), C.c_double()
+    lib().pth_camera_shutter_between(o0.ctypes.data_as(dp), r0.ctypes.data_as(dp), o1.ctypes.data_as(dp), r1.ctypes.data_as(dp),
+                                     t.ctypes.data_as(dp), k.ctypes.data_as(dp), C.cast(C.byref(angle), dp))
+    return t, k, angle.value
 
 
 def shirley_spheres(width, height, no_simd=False, seed=42):

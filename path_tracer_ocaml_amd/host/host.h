@@ -34,6 +34,13 @@ void pth_camera_create(const double eye[3], const double target[3], const double
 void pth_camera_pose_look_at(const double scene_look_at[16], const double eye[3], const double target[3], const double up[3], double aspect,
                              double fov_deg, double origin_out[3], double rotation_out[9], ptx_camera* view_out);
 
+/* A camera shutter for ptx_scene_set_camera_shutter: the motion that takes pose 0 (origin0, rotation0 -- what
+ * ptx_scene_set_camera_pose takes) to pose 1 while the shutter is open.  translation = origin1 - origin0; (axis, angle) = the turn
+ * R1 * R0^T about a unit axis of the scene's space, angle in [0, pi]; no turn within rounding gives angle 0 and a zero axis.  Any out
+ * pointer may be NULL. */
+void pth_camera_shutter_between(const double origin0[3], const double rotation0[9], const double origin1[3], const double rotation1[9],
+                                double translation_out[3], double axis_out[3], double* angle_out);
+
 /* shirley_spheres/bin/main.ml (Random.init seed; the reference uses 42) */
 pth_scene* pth_scene_shirley(int32_t width, int32_t height, int32_t no_simd, int64_t seed);
 /* the same scene with a white Lambertian lamp sphere of radius r that emits (emit, emit, emit) at the WORLD point (x, y, z), moved to

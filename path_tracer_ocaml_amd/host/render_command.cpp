@@ -39,6 +39,11 @@
 // --hdr-out=FILE.pfm (any render): also writes the square of every value of the final image -- the filmed linear radiance -- as a PFM
 // (pth_pfm_write), which --envmap reads back: a panorama written here lights another scene.  With --turntable, frame k goes to the name
 // with -kkk in front of its extension.
+// --shutter=F (with --turntable=N; 0 < F <= 1): motion blur (ptx_scene_set_camera_shutter) -- frame f is exposed while the camera moves
+// from its pose to fraction F of the way to frame f + 1's (pth_camera_shutter_between; 0.5 is a 180-degree shutter).
+// --shutter-eye=X,Y,Z [--shutter-target=X,Y,Z] (with --camera-eye, no turntable): one frame exposed while the camera moves from
+// --camera-eye / --camera-target to that eye (and target; default: --camera-target).  The library refuses --temporal under a shutter:
+// its message, exit code 124.
 // --exposure=E, --tone=none|reinhard|aces, --transfer=reference|linear|srgb (any render): the display of the image (include/ptx.h,
 // "display outputs"); -o is written from its RGB8 bytes (pth_write_png8).  The plain render, --progressive and --denoise get those bytes
 // from the device (ptx_render_display, ptx_render_progressive_display); --adaptive, --turntable, --temporal, --aov and --hdr-out keep the
@@ -96,6 +101,9 @@ struct Args {
   double turntable_arc = 360.0;          // --turntable-arc=DEG
   bool have_arc = false;
   double temporal = -1.0;                // --temporal[=CAP]: max_history_passes (< 0: no temporal accumulation)
+  double shutter = 0.0;                  // --shutter=F (0: none)
+  bool have_shutter_eye = false, have_shutter_target = false; // --shutter-eye, --shutter-target
+  double shutter_eye[3] = {0, 0, 0}, shutter_target[3] = {0, 0, 0};
   bool panorama = false;                 // --panorama
   std::string hdr_out;                   // --hdr-out=FILE.pfm
   ptx_display_params display{PTX_PIXEL_RGB8, PTX_TRANSFER_REFERENCE, PTX_TONE_NONE, 0, 1.0, {0, 0, 0, 0}}; // --transfer, --tone, --exposure
@@ -115,6 +123,7 @@ struct Args {
                "          [--light-spheres] [--sphere-lamp=X,Y,Z,R,EMIT]\n"
                "          [--camera-eye=X,Y,Z --camera-target=X,Y,Z] [--camera-fov=DEG] [--turntable=N]\n"
                "          [--turntable-arc=DEG] [--temporal[=CAP]] [--panorama] [--hdr-out=FILE.pfm]\n"
+               "          [--shutter=FRACTION] [--shutter-eye=X,Y,Z [--shutter-target=X,Y,Z]]\n"
                "          [--exposure=FLOAT] [--tone=none|reinhard|aces] [--transfer=reference|linear|srgb]\n",
                prog);
   std::exit(msg ? 124 : 0); // Cmdliner exits 124 on a CLI error
@@ -271,6 +280,22 @@ Args parse(int argc, char** argv) {
       a.turntable_arc = std::strtod(v.c_str(), &end);
       if (end == v.c_str() || *end || !(a.turntable_arc > 0.0) || !(a.turntable_arc <= 360.0)) usage(argv[0], "invalid value for --turntable-arc, must be in (0, 360]");
       a.have_arc = true;
+    } else if (take_value(argc, argv, i, "shutter", nullptr, &v)) {
+      char* end = nullptr;
+      a.shutter = std::strtod(v.c_str(), &end);
+      if (end == v.c_str() || *end || !(a.shutter > 0.0) || !(a.shutter <= 1.0)) usage(argv[0], "invalid value for --shutter, must be in (0, 1]");
+    } else if (take_value(argc, argv, i, "shutter-eye", nullptr, &v)) {
+      char tail = 0;
+      double* c = a.shutter_eye;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &c[0], &c[1], &c[2], &tail) != 3 || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+        usage(argv[0], "invalid value for --shutter-eye, expected X,Y,Z");
+      a.have_shutter_eye = true;
+    } else if (take_value(argc, argv, i, "shutter-target", nullptr, &v)) {
+      char tail = 0;
+      double* c = a.shutter_target;
+      if (std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &c[0], &c[1], &c[2], &tail) != 3 || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]))
+        usage(argv[0], "invalid value for --shutter-target, expected X,Y,Z");
+      a.have_shutter_target = true;
     } else if (!std::strcmp(argv[i], "--temporal")) {
       a.temporal = 64.0; // ptx_temporal_defaults' max_history_passes
     } else if (!std::strncmp(argv[i], "--temporal=", 11)) {
@@ -313,6 +338,13 @@ Args parse(int argc, char** argv) {
     usage(argv[0], "--camera-eye and --camera-target must differ");
   if (a.camera_fov > 0.0 && !a.have_eye && a.turntable == 0) usage(argv[0], "--camera-fov requires --camera-eye and --camera-target, or --turntable");
   if (a.have_arc && a.turntable == 0) usage(argv[0], "--turntable-arc requires --turntable");
+  if (a.shutter > 0.0 && a.turntable == 0) usage(argv[0], "--shutter requires --turntable (a single frame takes --shutter-eye)");
+  if (a.have_shutter_eye && (!a.have_eye || a.turntable > 0)) usage(argv[0], "--shutter-eye requires --camera-eye and --camera-target, without --turntable");
+  if (a.have_shutter_target && !a.have_shutter_eye) usage(argv[0], "--shutter-target requires --shutter-eye");
+  if (a.have_shutter_eye) {
+    const double* t = a.have_shutter_target ? a.shutter_target : a.camera_target;
+    if (a.shutter_eye[0] == t[0] && a.shutter_eye[1] == t[1] && a.shutter_eye[2] == t[2]) usage(argv[0], "--shutter-eye and its target must differ");
+  }
   if (a.temporal >= 0.0) {
     if (a.turntable == 0) usage(argv[0], "--temporal requires --turntable");
     if (a.samples_per_pixel < 2) usage(argv[0], "--temporal requires --samples-per-pixel >= 2 (one frame's passes)");
@@ -422,9 +454,14 @@ int write_aovs(const std::string& prefix, int width, int height, const std::vect
   return pth_write_png((prefix + "-depth.png").c_str(), width, height, img.data()) != 0 ? -1 : 0;
 }
 
-// the camera of frame `frame` posed over the scene (ptx_scene_set_camera_pose): --camera-eye / --camera-target / --camera-fov where given,
-// else the scene's own; a turntable turns the eye about the axis through the target along the scene camera's up vector (Rodrigues)
-int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
+// The camera of frame `frame`: --camera-eye / --camera-target / --camera-fov where given, else the scene's own; a turntable turns the
+// eye about the axis through the target along the scene camera's up vector (Rodrigues).  closing: the pose a single frame's shutter
+// closes at (--shutter-eye / --shutter-target) instead.
+struct CameraPose {
+  double origin[3], rotation[9];
+  ptx_camera view;
+};
+int camera_of_frame(pth_scene* hs, const Args& a, int frame, bool closing, CameraPose* out) {
   double eye[3], target[3], up[3], fov = 0.0, look_at[16];
   if (pth_scene_camera(hs, eye, target, up, &fov, look_at) != 0) {
     std::fprintf(stderr, "the scene records no camera to pose against\n");
@@ -433,6 +470,10 @@ int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
   if (a.have_eye) {
     std::memcpy(eye, a.camera_eye, sizeof eye);
     std::memcpy(target, a.camera_target, sizeof target);
+  }
+  if (closing) {
+    std::memcpy(eye, a.shutter_eye, sizeof eye);
+    if (a.have_shutter_target) std::memcpy(target, a.shutter_target, sizeof target);
   }
   if (a.camera_fov > 0.0) fov = a.camera_fov;
   if (a.turntable > 0) {
@@ -446,11 +487,30 @@ int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
     const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
     for (int i = 0; i < 3; ++i) eye[i] = target[i] + (v[i] * c + kxv[i] * s + k[i] * kv * (1.0 - c));
   }
-  double origin[3], rotation[9];
-  ptx_camera view;
-  pth_camera_pose_look_at(look_at, eye, target, up, (double)a.width / (double)a.height, fov, origin, rotation, &view);
-  if (ptx_scene_set_camera_pose(scene, origin, rotation, &view) != 0) {
+  pth_camera_pose_look_at(look_at, eye, target, up, (double)a.width / (double)a.height, fov, out->origin, out->rotation, &out->view);
+  return 0;
+}
+
+// poses the scene for frame `frame` (ptx_scene_set_camera_pose) and, with --shutter or --shutter-eye, opens its shutter
+// (ptx_scene_set_camera_shutter): towards frame + 1's pose by the fraction --shutter, or all the way to --shutter-eye's
+int pose_camera(ptx_scene* scene, pth_scene* hs, const Args& a, int frame) {
+  CameraPose cp;
+  if (camera_of_frame(hs, a, frame, false, &cp) != 0) return -1;
+  if (ptx_scene_set_camera_pose(scene, cp.origin, cp.rotation, &cp.view) != 0) {
     std::fprintf(stderr, "ptx_scene_set_camera_pose: %s\n", ptx_last_error());
+    return -1;
+  }
+  if (!(a.shutter > 0.0) && !a.have_shutter_eye) return 0;
+  CameraPose next;
+  if (camera_of_frame(hs, a, frame + 1, a.have_shutter_eye, &next) != 0) return -1;
+  double translation[3], axis[3], angle = 0.0;
+  pth_camera_shutter_between(cp.origin, cp.rotation, next.origin, next.rotation, translation, axis, &angle);
+  if (a.shutter > 0.0) {
+    for (int i = 0; i < 3; ++i) translation[i] = translation[i] * a.shutter;
+    angle = angle * a.shutter;
+  }
+  if (ptx_scene_set_camera_shutter(scene, translation, axis, angle) != 0) {
+    std::fprintf(stderr, "ptx_scene_set_camera_shutter: %s\n", ptx_last_error());
     return -1;
   }
   return 0;
@@ -635,7 +695,7 @@ int main(int argc, char** argv) {
   if (rc != 0) {
     std::fprintf(stderr, "%s: %s\n", a.temporal >= 0.0 ? "ptx_render_temporal" : adaptive ? "ptx_render_adaptive" : a.denoise >= 0 ? "ptx_render_denoised" : a.progressive ? "ptx_render_progressive" : "ptx_render",
                  ptx_last_error());
-    return 1;
+    return (rc == -3 /* PTX_ERR_STATE */ && a.temporal >= 0.0 && a.shutter > 0.0) ? 124 : 1; // (a shutter under --temporal: the library's refusal)
   }
   if (upd.write_failed || (on_device ? pth_write_png8(output.c_str(), a.width, a.height, rgb8.data())
                                      : write_display_png(output.c_str(), a.width, a.height, rgb.data(), a.display)) != 0) {

@@ -306,6 +306,39 @@ void pth_camera_pose_look_at(const double scene_look_at[16], const double eye[3]
   if (view_out) *view_out = c.view;
 }
 
+void pth_camera_shutter_between(const double origin0[3], const double rotation0[9], const double origin1[3], const double rotation1[9],
+                                double translation_out[3], double axis_out[3], double* angle_out) {
+  if (translation_out)
+    for (int i = 0; i < 3; ++i) translation_out[i] = origin1[i] - origin0[i];
+  // M = R1 * R0^T: the turn from pose 0 to pose 1 in the scene's space; M - M^T = 2 sin(A) [k]x and trace M = 1 + 2 cos(A)
+  double m[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      m[i][j] = (rotation1[3 * i] * rotation0[3 * j] + rotation1[3 * i + 1] * rotation0[3 * j + 1]) + rotation1[3 * i + 2] * rotation0[3 * j + 2];
+  double k[3] = {m[2][1] - m[1][2], m[0][2] - m[2][0], m[1][0] - m[0][1]};
+  const double two_sin = std::sqrt((k[0] * k[0] + k[1] * k[1]) + k[2] * k[2]);
+  const double two_cos = ((m[0][0] + m[1][1]) + m[2][2]) - 1.0;
+  double angle = std::atan2(two_sin, two_cos); // in [0, pi]
+  const double v[3] = {k[0], k[1], k[2]};
+  if (two_cos > 0.0 && !(two_sin > 1e-15)) { // no turn within rounding: exactly none
+    angle = 0.0;
+    k[0] = k[1] = k[2] = 0.0;
+  } else if (two_cos > 0.0 || two_sin > 1e-6) { // (the error of k is 1e-16 / sin A, and it moves a ray by sin A times as much)
+    for (int i = 0; i < 3; ++i) k[i] /= two_sin;
+  } else { // a half turn within 1e-6: M = 2 k k^T - I within rounding, so k from the largest diagonal entry and its row, signed like v
+    int a = 0;
+    if (m[1][1] > m[a][a]) a = 1;
+    if (m[2][2] > m[a][a]) a = 2;
+    const double ka = std::sqrt(std::fmax((m[a][a] + 1.0) * 0.5, 0.0));
+    for (int i = 0; i < 3; ++i) k[i] = i == a ? ka : ((m[a][i] + m[i][a]) * 0.25) / ka;
+    const double len = std::sqrt((k[0] * k[0] + k[1] * k[1]) + k[2] * k[2]);
+    const double sign = ((k[0] * v[0] + k[1] * v[1]) + k[2] * v[2]) < 0.0 ? -1.0 : 1.0;
+    for (int i = 0; i < 3; ++i) k[i] = sign * (k[i] / len);
+  }
+  if (axis_out) std::memcpy(axis_out, k, sizeof k);
+  if (angle_out) *angle_out = angle;
+}
+
 // shirley_spheres/bin/main.ml: Shirley_spheres.spheres () under Random.init seed, camera (width // height),
 // every sphere moved to camera space; no_simd picks Array_leaf (cutoff 4) over Simd_leaf (cutoff 16).
 // lamp (pth_scene_shirley_lamp): null, or {x, y, z, r, emit} of a white Lambertian lamp sphere in world coordinates, appended AFTER the

@@ -66,11 +66,12 @@ class Integrator:
     the scene's emissive spheres beside its emissive triangles; like ``environment_sampling`` True is applied before the lighting mode.
     ``camera_pose``: (origin, rotation) or (origin, rotation, view) for Scene.set_camera_pose -- what camera_pose_look_at returns;
     None leaves the scene's as it is.  ``projection``: "perspective" or "latlong" (or the PTX_PROJECTION_* value) for
-    Scene.set_camera_projection, applied after the lens; None leaves the scene's as it is."""
+    Scene.set_camera_projection, applied after the lens; None leaves the scene's as it is.  ``camera_shutter``: (translation, axis,
+    angle) for Scene.set_camera_shutter -- what camera_shutter_between returns; None leaves the scene's as it is."""
 
     def __init__(self, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
                  environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None,
-                 camera_pose=None, projection=None):
+                 camera_pose=None, projection=None, camera_shutter=None):
         if image.shape != (height, width, 3) or image.dtype != np.float64:
             raise ValueError("image must be a float64 array of shape (height, width, 3)")
         self.width, self.height, self.image = width, height, image
@@ -86,6 +87,8 @@ class Integrator:
             self._scene.set_camera_pose(*camera_pose)
         if projection is not None:
             self._scene.set_camera_projection(projection)
+        if camera_shutter is not None:
+            self._scene.set_camera_shutter(*camera_shutter)
         if environment is not None:
             self._scene.set_environment(*(environment if isinstance(environment, tuple) else (environment,)))
         if environment_sampling is not None:
@@ -105,9 +108,9 @@ class Integrator:
     @classmethod
     def create(cls, *, width, height, image, samples_per_pixel, max_bounces, scene, device=0, lighting=None, film=None,
                environment=None, images=None, environment_sampling=None, lens=None, sphere_light_sampling=None,
-               camera_pose=None, projection=None):
+               camera_pose=None, projection=None, camera_shutter=None):
         return cls(width, height, image, samples_per_pixel, max_bounces, scene, device, lighting, film, environment, images,
-                   environment_sampling, lens, sphere_light_sampling, camera_pose, projection)
+                   environment_sampling, lens, sphere_light_sampling, camera_pose, projection, camera_shutter)
 
     def render(self, update_progress=None):
         """``Integrator.render ~update_progress``: update_progress receives pixel counts summing to W*H."""
