@@ -4352,4 +4352,5 @@ __global__ __launch_bounds__(256) void k_filter_error(PtSceneDev sc, long long n
 #include "rays.inc"
 #include "display.inc"
 #include "ptx_api.inc"
+#include "probes.inc"
 #endif

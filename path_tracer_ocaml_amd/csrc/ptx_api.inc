@@ -1,5 +1,6 @@
 /* ptx_api.inc -- host side of libptx_hip.so: the C ABI declared in include/ptx.h.
- * Included at the end of kernels.hip (one translation unit, so the launches see the templates). */
+ * Included at the end of kernels.hip (one translation unit, so the launches see the templates), in front of probes.inc, which holds
+ * the point-probe entry points (ptx_camera_rays, ptx_walk_rays, ptx_trace_samples, ptx_math_eval and their kin). */
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -197,9 +198,21 @@ struct ThreadLifeBuf : DevBuf<T> {
   ~ThreadLifeBuf() { this->p = nullptr; this->n = 0; }
 };
 
-/* (the name function-local buffers were declared under before DevBuf freed itself) */
+/* Staging for the calls that take host arrays: `count` items into a buffer made large enough, `count` items back out.  Each fails
+ * as HIP_TRY does and adds no synchronisation of its own. */
 template <class T>
-using LocalBuf = DevBuf<T>;
+int upload(DevBuf<T>& d, const T* host, size_t count) {
+  HIP_TRY(d.ensure(count));
+  HIP_TRY(hipMemcpy(d.p, host, sizeof(T) * count, hipMemcpyHostToDevice));
+  return 0;
+}
+template <class T>
+int download(T* host, const DevBuf<T>& d, size_t count) {
+  HIP_TRY(hipMemcpy(host, d.p, sizeof(T) * count, hipMemcpyDeviceToHost));
+  return 0;
+}
+/* the grid of a launch with one thread per item on 256-thread blocks */
+inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 struct QueueMem {
   DevBuf<PtRayRec> ray;
@@ -1008,7 +1021,7 @@ void launch_generate_tiles(const ptx_scene* s, const ptx_render_params* p, const
   with_camera_kind(camera_kind(s->sched), [&](auto kind) {
     constexpr int CAM = decltype(kind)::value;
     if constexpr (CAM != PT_CAM_PINHOLE)
-      hipLaunchKernelGGL((path ? k_generate_tiles<CAM, true> : k_generate_tiles<CAM, false>), dim3((pl.n + 255) / 256), dim3(256), 0, st, s->dev, pl.g,
+      hipLaunchKernelGGL((path ? k_generate_tiles<CAM, true> : k_generate_tiles<CAM, false>), grid256(pl.n), dim3(256), 0, st, s->dev, pl.g,
                          cam, (const double*)s->alpha.p, q);
   });
 }
@@ -1018,7 +1031,7 @@ void launch_generate_pixels(const ptx_scene* s, const ptx_render_params* p, int 
   const PtCameraArg cam = scene_camera(s, p->max_bounces);
   const size_t n_paths = (size_t)n_pass * (size_t)n_list;
   with_camera_kind(camera_kind(s->sched), [&](auto kind) {
-    hipLaunchKernelGGL(k_generate_pixels<decltype(kind)::value>, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, st, s->dev, p->width,
+    hipLaunchKernelGGL(k_generate_pixels<decltype(kind)::value>, grid256(n_paths), dim3(256), 0, st, s->dev, p->width,
                        p->height, p->samples_per_pixel, first, n_pass, d_list, n_list, cam, (const double*)s->alpha.p, q);
   });
 }
@@ -1376,7 +1389,7 @@ int queue_batch_accumulate(ptx_scene* s, const ptx_render_params* p, const Batch
                            const Workspace& w, hipStream_t ls, double* d_raw, int first, int n_pass) {
   const bool timed = p->time_kernels != 0, last_batch = first + b.ppb >= b.pass_end;
   LaunchTimer t(s, ls, timed, PTX_KERNEL_ACCUM);
-  const dim3 grid((unsigned)((b.per_pass + 255) / 256)), block(256);
+  const dim3 grid(grid256(b.per_pass)), block(256);
   if (b.list) {
     hipLaunchKernelGGL(k_accum_list, grid, block, 0, ls, w.contrib, range.n_list, n_pass, range.d_list, d_raw, range.d_sq, range.d_passes,
                        first + n_pass);
@@ -1386,7 +1399,7 @@ int queue_batch_accumulate(ptx_scene* s, const ptx_render_params* p, const Batch
     /* the frame's last accumulate in row slabs, an event behind each: the caller films and copies slab k while k + 1 is summed */
     for (int k = 0; k < slabs->n; ++k) {
       const long long q0 = (long long)slabs->row[k] * p->width, q1 = (long long)slabs->row[k + 1] * p->width;
-      if (q1 > q0) hipLaunchKernelGGL(k_accum, dim3((unsigned)((q1 - q0 + 255) / 256)), block, 0, ls, w.contrib, b.npix, n_pass, d_raw, q0, q1);
+      if (q1 > q0) hipLaunchKernelGGL(k_accum, grid256(q1 - q0), block, 0, ls, w.contrib, b.npix, n_pass, d_raw, q0, q1);
       HIP_TRY(hipEventRecord(slabs->done[k], ls));
     }
     slabs->used = true;
@@ -1603,7 +1616,7 @@ bool bvh_build_device(const double* d_boxes, int n, const Box* root, int num_bin
     for (int k = 0; k < 3; ++k)
       if (!chk(ws.d_seg[c][k].ensure(cap[k]))) return false;
   const int root_cls = n <= BVH_SMALL_MAX ? 0 : (n >= BVH_BIG_MIN ? 2 : 1);
-  hipLaunchKernelGGL(k_bvh_iota, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, ws.d_order.p, n);
+  hipLaunchKernelGGL(k_bvh_iota, grid256(n), dim3(256), 0, nullptr, ws.d_order.p, n);
   if (root) {
     BvhSeg rs;
     rs.lo = 0; rs.hi = n; rs.node = 0; rs.pad = 0;
@@ -1694,13 +1707,13 @@ bool bvh_build_device(const double* d_boxes, int n, const Box* root, int num_bin
   auto level_count = [&](int l) { return (l + 1 < (int)level_start.size() ? level_start[(size_t)l + 1] : n_tmp) - level_start[(size_t)l]; };
   for (int l = n_levels - 1; l >= 0; --l) {
     const int c = level_count(l);
-    if (c > 0) hipLaunchKernelGGL(k_fin_sizes, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, level_start[(size_t)l], c, pad4 ? 1 : 0);
+    if (c > 0) hipLaunchKernelGGL(k_fin_sizes, grid256(c), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, level_start[(size_t)l], c, pad4 ? 1 : 0);
   }
   for (int l = 0; l < n_levels; ++l) {
     const int c = level_count(l);
-    if (c > 0) hipLaunchKernelGGL(k_fin_index, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, level_start[(size_t)l], c);
+    if (c > 0) hipLaunchKernelGGL(k_fin_index, grid256(c), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, level_start[(size_t)l], c);
   }
-  hipLaunchKernelGGL(k_fin_emit, dim3((unsigned)((n_tmp + 255) / 256)), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, n_tmp, ws.d_order.p, ws.d_nodes.p, ws.d_slot.p);
+  hipLaunchKernelGGL(k_fin_emit, grid256(n_tmp), dim3(256), 0, nullptr, ws.d_tmp.p, ws.d_fin.p, n_tmp, ws.d_order.p, ws.d_nodes.p, ws.d_slot.p);
   if (!chk(hipGetLastError())) return false;
   BvhFin rootfin;
   if (!chk(hipMemcpy(&rootfin, ws.d_fin.p, sizeof rootfin, hipMemcpyDeviceToHost))) return false;
@@ -1788,7 +1801,7 @@ int film_resolve(int width, int height, int spp, const double* d_raw, double* d_
   binomial_3x3(k.w);
   const long long n = (long long)width * (row1 - row0);
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_film, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, width, height, spp_inv, k, map, d_out, row0, row1);
+  hipLaunchKernelGGL(k_film, grid256(n), dim3(256), 0, st, d_raw, width, height, spp_inv, k, map, d_out, row0, row1);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1825,7 +1838,7 @@ int film_counts_queue(int width, int height, const double* d_raw, const int32_t*
   PtFilm3 k;
   binomial_3x3(k.w);
   const long long n = (long long)width * height;
-  hipLaunchKernelGGL(k_film_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_raw, d_passes, width, height, k, d_out);
+  hipLaunchKernelGGL(k_film_counts, grid256(n), dim3(256), 0, st, d_raw, d_passes, width, height, k, d_out);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2200,45 +2213,6 @@ int32_t ptx_light_table(const ptx_scene* s, double* triangles_out, double* spher
   if (triangles_out && !s->light_table.empty()) std::memcpy(triangles_out, s->light_table.data(), sizeof(double) * s->light_table.size());
   if (spheres_out && s->sphere_sampling && !s->sphere_table.empty())
     std::memcpy(spheres_out, s->sphere_table.data(), sizeof(double) * s->sphere_table.size());
-  return 0;
-}
-
-static int light_half_ready(const ptx_scene* s) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (s->dev.lighting != PTX_LIGHTING_SAMPLED || s->dev.n_lights + s->dev.n_sphere_lights < 1)
-    return fail(PTX_ERR_STATE, "the light half needs PTX_LIGHTING_SAMPLED and a light triangle or a sphere light to sample");
-  return 0;
-}
-int32_t ptx_light_sample(ptx_scene* s, int64_t n, const double* points, const double* uv, double* dir_out, int32_t* index_out) {
-  if (const int rc = light_half_ready(s)) return rc;
-  if (n < 0 || !points || !uv || !dir_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_p, d_uv, d_out;
-  LocalBuf<int32_t> d_index;
-  HIP_TRY(d_p.ensure((size_t)n * 3)); HIP_TRY(d_uv.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
-  if (index_out) HIP_TRY(d_index.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_p.p, points, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_uv.p, uv, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_light_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_p.p, d_uv.p, d_out.p, index_out ? d_index.p : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(dir_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
-  if (index_out) HIP_TRY(hipMemcpy(index_out, d_index.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  return 0;
-}
-int32_t ptx_light_pdf(ptx_scene* s, int64_t n, const double* points, const double* dirs, double* pd_out) {
-  if (const int rc = light_half_ready(s)) return rc;
-  if (n < 0 || !points || !dirs || !pd_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_p, d_dirs, d_out;
-  HIP_TRY(d_p.ensure((size_t)n * 3)); HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_p.p, points, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_light_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_p.p, d_dirs.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(pd_out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2704,89 +2678,6 @@ int32_t ptx_scene_environment(const ptx_scene* s, ptx_image* out, double* R_out)
   return 0;
 }
 
-int32_t ptx_texture_eval(ptx_scene* s, int32_t index, int64_t n, const double* uv, double* rgb_out) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  int rc = check_texture_index(s, index);
-  if (rc) return rc;
-  if (n < 0 || !uv || !rgb_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  /* the record a slot whose material points at this entry holds: the descriptor's texture, or the image in its place */
-  PtShadeRec rec{};
-  const PtTexture& t = s->host->texs[(size_t)index];
-  rec.kind = PTX_MAT_LAMBERTIAN;
-  rec.tex_kind = t.kind; rec.tex_w = t.width; rec.tex_h = t.height;
-  std::memcpy(rec.even, t.even, sizeof rec.even);
-  std::memcpy(rec.odd, t.odd, sizeof rec.odd);
-  if (!s->images.empty() && s->images[(size_t)index]->host) {
-    const ptx_scene::ImageSlot& e = *s->images[(size_t)index];
-    const uint64_t texels = (uint64_t)(uintptr_t)e.dev.p, flags = (uint64_t)(uint32_t)e.host->flags;
-    rec.tex_kind = PT_TEX_IMAGE; rec.tex_w = e.host->width; rec.tex_h = e.host->height;
-    std::memset(rec.even, 0, sizeof rec.even);
-    std::memcpy(&rec.even[0], &texels, sizeof texels);
-    std::memcpy(&rec.even[1], &flags, sizeof flags);
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_uv, d_out;
-  HIP_TRY(d_uv.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
-  HIP_TRY(hipMemcpy(d_uv.p, uv, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_texture_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, rec, (long long)n, d_uv.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(rgb_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int32_t ptx_environment_eval(ptx_scene* s, int64_t n, const double* dirs, double* rgb_out) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (n < 0 || !dirs || !rgb_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_dirs, d_out;
-  HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n * 3));
-  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_environment_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_dirs.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(rgb_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-static int env_sampling_ready(const ptx_scene* s) {
-  if (!s) return fail(PTX_ERR_ARG, "NULL scene");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (!s->env_sampling || !s->dev.env_sample) return fail(PTX_ERR_STATE, "environment sampling is off (ptx_scene_set_environment_sampling)");
-  return 0;
-}
-int32_t ptx_environment_sample(ptx_scene* s, int64_t n, const double* ab, double* dirs_out, int32_t* texel_out) {
-  if (const int rc = env_sampling_ready(s)) return rc;
-  if (n < 0 || !ab || !dirs_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_ab, d_out;
-  LocalBuf<int32_t> d_texel;
-  HIP_TRY(d_ab.ensure((size_t)n * 2)); HIP_TRY(d_out.ensure((size_t)n * 3));
-  if (texel_out) HIP_TRY(d_texel.ensure((size_t)n * 2));
-  HIP_TRY(hipMemcpy(d_ab.p, ab, sizeof(double) * (size_t)n * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_environment_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_ab.p, d_out.p, texel_out ? d_texel.p : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(dirs_out, d_out.p, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToHost));
-  if (texel_out) HIP_TRY(hipMemcpy(texel_out, d_texel.p, sizeof(int32_t) * (size_t)n * 2, hipMemcpyDeviceToHost));
-  return 0;
-}
-int32_t ptx_environment_pdf(ptx_scene* s, int64_t n, const double* dirs, double* pd_out) {
-  if (const int rc = env_sampling_ready(s)) return rc;
-  if (n < 0 || !dirs || !pd_out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_dirs, d_out;
-  HIP_TRY(d_dirs.ensure((size_t)n * 3)); HIP_TRY(d_out.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_dirs.p, dirs, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_environment_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_dirs.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(pd_out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
 int32_t ptx_scene_stats(const ptx_scene* s, ptx_stats* out) {
   if (!s || !out) return fail(PTX_ERR_ARG, "NULL argument");
   std::memset(out, 0, sizeof *out);
@@ -3097,7 +2988,7 @@ int display_thresholds_device() {
 int display_queue(const ptx_display_params& d, long long p0, long long p1, const double* d_rgb, void* d_out, hipStream_t st) {
   if (p1 <= p0) return 0;
   const long long quads = (p1 + 3) / 4 - p0 / 4;
-  const dim3 grid((unsigned)((quads + 255) / 256)), block(256);
+  const dim3 grid(grid256(quads)), block(256);
   const PtDisplay pd{d.transfer, d.tone, d.exposure};
   switch (d.format) {
     case PTX_PIXEL_RGB8: hipLaunchKernelGGL(k_display_image<PTX_PIXEL_RGB8>, grid, block, 0, st, d_rgb, p0, p1, pd, d_out); break;
@@ -3540,7 +3431,7 @@ int render_updates(ptx_scene* s, const ptx_render_params& p, Policy& pol, bool w
 int check_list_device(ptx_scene* s, const int32_t* d_list, long long n, long long npix, hipStream_t st) {
   HIP_TRY(s->sel_n.ensure(2)); /* [1]: the flag */
   HIP_TRY(hipMemsetAsync(s->sel_n.p + 1, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(k_list_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_list, n, npix, s->sel_n.p + 1);
+  hipLaunchKernelGGL(k_list_check, grid256(n), dim3(256), 0, st, d_list, n, npix, s->sel_n.p + 1);
   HIP_TRY(hipGetLastError());
   int32_t bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, s->sel_n.p + 1, sizeof bad, hipMemcpyDeviceToHost, st));
@@ -3557,7 +3448,7 @@ int pixel_error_device(int32_t device, int32_t width, int32_t rows, int32_t pass
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   const long long npix = (long long)width * rows;
-  LocalBuf<double> part;
+  DevBuf<double> part;
   HIP_TRY(part.ensure(pixel_error_partials(npix)));
   rc = pixel_error_queue(npix, passes_done, d_passes, d_raw, d_sq, d_err_out, part.p, st);
   if (rc) {
@@ -3884,12 +3775,12 @@ int features_queue(ptx_scene* s, const ptx_render_params* p, int pass_first, int
       PtQueue q{s->feat_ray.p, nullptr, s->feat_work.p + 8};
       launch_generate_tiles(s, p, pl, false, q, st);
       launch_trace(s, st, q, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, kNoBounce);
-      hipLaunchKernelGGL(s->sched.img ? k_features_queue<true> : k_features_queue<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, q, h, d_feat);
+      hipLaunchKernelGGL(s->sched.img ? k_features_queue<true> : k_features_queue<false>, grid256(padded), dim3(256), 0, st, s->dev, g, q, h, d_feat);
       HIP_TRY(hipGetLastError());
       continue;
     }
     launch_trace(s, st, PtQueue{}, h, (size_t)pl.n, false, s->feat_work.p, s->feat_susp.p, 0, pl);
-    hipLaunchKernelGGL(s->sched.img ? k_features<true> : k_features<false>, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
+    hipLaunchKernelGGL(s->sched.img ? k_features<true> : k_features<false>, grid256(padded), dim3(256), 0, st, s->dev, g, h, alpha, d_feat);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -3918,7 +3809,7 @@ int denoise_queue(int width, int height, const ptx_denoise_params& d, int k, con
   PtDenoise dn;
   dn.width = width; dn.height = height; dn.m = d.normal_power_log2; dn.demodulate = (d.flags & PTX_DENOISE_DEMODULATE) ? 1 : 0;
   dn.sl2 = d.sigma_luminance * d.sigma_luminance; dn.sz = d.sigma_depth; dn.sa2 = d.sigma_albedo * d.sigma_albedo;
-  const dim3 lin((unsigned)((npix + 255) / 256)), tiles((unsigned)((width + PT_ATROUS_TX - 1) / PT_ATROUS_TX), (unsigned)((height + PT_ATROUS_TY - 1) / PT_ATROUS_TY));
+  const dim3 lin(grid256(npix)), tiles((unsigned)((width + PT_ATROUS_TX - 1) / PT_ATROUS_TX), (unsigned)((height + PT_ATROUS_TY - 1) / PT_ATROUS_TY));
   double4* cv[2] = {(double4*)cv0, (double4*)cv1};
   hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, st, dn, k, d_passes, (double)kf, d_raw, d_err, d_feat, (PtGuide*)guide, cv[0]);
   /* how a level fetches its taps: the tile and its halo through LDS at steps <= PTX_ATROUS_LDS (0 .. PT_ATROUS_LDS_STEP), gathers
@@ -3991,7 +3882,7 @@ int32_t ptx_denoise_device(int32_t device, int32_t width, int32_t height, const 
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   const size_t npix = (size_t)width * (size_t)height;
-  LocalBuf<double> guide, cv0, cv1;
+  DevBuf<double> guide, cv0, cv1;
   if (d->levels > 0) {
     HIP_TRY(guide.ensure(npix * 8));
     HIP_TRY(cv0.ensure(npix * 4));
@@ -4045,7 +3936,7 @@ struct DenoisePolicy {
     if (!rc) rc = film_resolve(p.width, p.height, k, s->den_raw.p, s->rgb.p, nullptr, PtBandMap{1, 1, 0}, 0, -1, s->film);
     if (rc || !feat_out) return rc;
     const long long n = npix() * 8;
-    hipLaunchKernelGGL(k_feature_means, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const double*)s->feat.p, n, (double)kf, s->feat_mean.p);
+    hipLaunchKernelGGL(k_feature_means, grid256(n), dim3(256), 0, nullptr, (const double*)s->feat.p, n, (double)kf, s->feat_mean.p);
     HIP_TRY(hipGetLastError());
     return 0;
   }
@@ -4264,7 +4155,7 @@ int32_t ptx_temporal_accumulate_device(int32_t device, int32_t width, int32_t he
   rc = check_device(device);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
-  LocalBuf<unsigned long long> count;
+  DevBuf<unsigned long long> count;
   HIP_TRY(count.ensure(1));
   hipStream_t st = (hipStream_t)stream;
   rc = temporal_queue(width, height, *t, passes_done, feature_passes_done, *cur, d_hist_prev ? prev : nullptr, d_raw, d_sq, d_feat, d_hist_prev,
@@ -4381,116 +4272,6 @@ int32_t ptx_render_temporal(ptx_scene* s, const ptx_render_params* p_in, const p
 }
 
 namespace {
-/* the camera rays of explicit (x, y, pass) triples appended to q0 on the null stream, by the generator of this camera kind
- * (launch_generate_tiles and launch_generate_pixels are its siblings) */
-void launch_generate_list(ptx_scene* s, const ptx_render_params* p, PtCameraKind kind, int64_t n, const int32_t* dx, const int32_t* dy,
-                          const int32_t* dp, const PtQueue& q0) {
-  const PtCameraArg cam = scene_camera(s, p->max_bounces);
-  with_camera_kind(kind, [&](auto k) {
-    hipLaunchKernelGGL(k_generate_list<decltype(k)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, p->width, p->height,
-                       p->samples_per_pixel, (long long)n, dx, dy, dp, cam, (const double*)s->alpha.p, q0);
-  });
-}
-}  // namespace
-
-int32_t ptx_trace_samples(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
-                          const int32_t* passes, double* rgb_out, ptx_stats* stats) {
-  if (!s || !xs || !ys || !passes || !rgb_out) return fail(PTX_ERR_ARG, "NULL argument");
-  int rc = check_render_args(s, p, nullptr);
-  if (rc) return rc;
-  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad sample count");
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    fill_tree_stats(s, stats);
-  }
-  if (n == 0) return 0;
-  for (int64_t i = 0; i < n; ++i)
-    if (xs[i] < 0 || xs[i] >= p->width || ys[i] < 0 || ys[i] >= p->height || passes[i] < 0 || passes[i] >= p->samples_per_pixel)
-      return fail(PTX_ERR_ARG, "sample %lld out of range", (long long)i);
-  HIP_TRY(hipSetDevice(s->device));
-  RenderBusy busy(s);
-  Workspace w;
-  reschedule(s, 1);
-  rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
-  if (rc) return rc;
-  LocalBuf<int32_t> dx, dy, dp;
-  HIP_TRY(dx.ensure((size_t)n)); HIP_TRY(dy.ensure((size_t)n)); HIP_TRY(dp.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(dx.p, xs, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dy.p, ys, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.p, passes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  const bool count = p->count_work != 0;
-  HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
-  HIP_TRY(hipMemset(w.contrib_all, 0, sizeof(double) * w.contrib_n));
-  if (count) HIP_TRY(hipMemset(s->counters.p, 0, sizeof(PtCounters)));
-  if (p->max_bounces > 0) {
-    PtQueue q0 = w.q[0];
-    q0.count = w.counts;
-    launch_generate_list(s, p, camera_kind(s->sched), n, dx.p, dy.p, dp.p, q0);
-    run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, count, false, PrimaryLaunch());
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<double> rgbx((size_t)n * 4);
-  HIP_TRY(hipMemcpy(rgbx.data(), w.contrib.rgbx, sizeof(double) * rgbx.size(), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) {
-    rgb_out[3 * i] = rgbx[(size_t)i * 4];
-    rgb_out[3 * i + 1] = rgbx[(size_t)i * 4 + 1];
-    rgb_out[3 * i + 2] = rgbx[(size_t)i * 4 + 2];
-  }
-  if (stats) {
-    stats->samples = n;
-    if (count) {
-      rc = collect_counters(s, stats);
-      if (rc) return rc;
-    }
-  }
-  return 0;
-}
-
-int32_t ptx_camera_rays(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys, const int32_t* passes,
-                        double* origins_out, double* directions_out) {
-  if (!s || !xs || !ys || !passes || !origins_out || !directions_out) return fail(PTX_ERR_ARG, "NULL argument");
-  int rc = check_render_args(s, p, nullptr);
-  if (rc) return rc;
-  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad sample count");
-  if (n == 0) return 0;
-  for (int64_t i = 0; i < n; ++i)
-    if (xs[i] < 0 || xs[i] >= p->width || ys[i] < 0 || ys[i] >= p->height || passes[i] < 0 || passes[i] >= p->samples_per_pixel)
-      return fail(PTX_ERR_ARG, "sample %lld out of range", (long long)i);
-  HIP_TRY(hipSetDevice(s->device));
-  RenderBusy busy(s);
-  Workspace w;
-  reschedule(s, 1);
-  rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
-  if (rc) return rc;
-  LocalBuf<int32_t> dx, dy, dp;
-  HIP_TRY(dx.ensure((size_t)n)); HIP_TRY(dy.ensure((size_t)n)); HIP_TRY(dp.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(dx.p, xs, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dy.p, ys, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp.p, passes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
-  PtQueue q0 = w.q[0];
-  q0.count = w.counts;
-  launch_generate_list(s, p, camera_kind(s->sched), n, dx.p, dy.p, dp.p, q0);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  /* the generator appends wave by wave: entry e is the ray of sample path[e].id */
-  const size_t path_stride = s->dev.has_emit ? 2 : 1;
-  std::vector<PtRayRec> rays((size_t)n);
-  std::vector<PtPathRec> path((size_t)n * path_stride);
-  HIP_TRY(hipMemcpy(rays.data(), q0.ray, sizeof(PtRayRec) * rays.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(path.data(), q0.path, sizeof(PtPathRec) * path.size(), hipMemcpyDeviceToHost));
-  for (size_t e = 0; e < (size_t)n; ++e) {
-    const size_t i = path[e * path_stride].id;
-    if (i >= (size_t)n) return fail(PTX_ERR_HIP, "BUG: camera ray %zu carries sample id %zu of %lld", e, i, (long long)n);
-    const PtRayRec& r = rays[e];
-    origins_out[3 * i] = r.ox; origins_out[3 * i + 1] = r.oy; origins_out[3 * i + 2] = r.oz;
-    directions_out[3 * i] = r.dx; directions_out[3 * i + 1] = r.dy; directions_out[3 * i + 2] = r.dz;
-  }
-  return 0;
-}
-
-namespace {
 /* rays per batch of ptx_render_rays_device: PTX_RAYS_BATCH (a test hook: any batch size gives the same sums), else 16 M, and never
  * more than a path queue can number */
 size_t rays_batch(const ptx_scene* s, int64_t n) {
@@ -4505,7 +4286,7 @@ size_t rays_batch(const ptx_scene* s, int64_t n) {
 int check_rays_device(ptx_scene* s, int64_t n, const double* d_o, const double* d_d, const int32_t* d_off, hipStream_t st) {
   HIP_TRY(s->rays_lowest.ensure(1));
   HIP_TRY(hipMemsetAsync(s->rays_lowest.p, 0xff, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_rays_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, d_o, d_d, d_off, s->rays_lowest.p);
+  hipLaunchKernelGGL(k_rays_check, grid256(n), dim3(256), 0, st, (long long)n, d_o, d_d, d_off, s->rays_lowest.p);
   HIP_TRY(hipGetLastError());
   uint32_t lowest = 0xffffffffu;
   HIP_TRY(hipMemcpyAsync(&lowest, s->rays_lowest.p, sizeof lowest, hipMemcpyDeviceToHost, st));
@@ -4577,7 +4358,7 @@ int32_t ptx_render_rays_device(ptx_scene* s, const ptx_rays_params* rp, int64_t 
       run_bounces(s, st, w, (size_t)nb, rp->max_bounces, count, false, PrimaryLaunch());
     }
     const long long bins = (first + nb - 1) / m - first / m + 1;
-    hipLaunchKernelGGL(d_sq_inout ? k_accum_rays<true> : k_accum_rays<false>, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, st, w.contrib, (long long)first,
+    hipLaunchKernelGGL(d_sq_inout ? k_accum_rays<true> : k_accum_rays<false>, grid256(bins), dim3(256), 0, st, w.contrib, (long long)first,
                        (long long)nb, m, d_sum_inout, d_sq_inout);
     HIP_TRY(hipGetLastError());
   }
@@ -4601,15 +4382,11 @@ int32_t ptx_render_rays(ptx_scene* s, const ptx_rays_params* rp, int64_t n, cons
   if (n == 0) return ptx_render_rays_device(s, rp, 0, origins, directions, offsets, sum_out, sq_out, nullptr, stats);
   HIP_TRY(hipSetDevice(s->device));
   const size_t n3 = (size_t)n * 3, bins3 = (size_t)(n / rp->rays_per_bin) * 3;
-  LocalBuf<double> d_o, d_d, d_sum, d_sq;
-  LocalBuf<int32_t> d_off;
-  HIP_TRY(d_o.ensure(n3)); HIP_TRY(d_d.ensure(n3)); HIP_TRY(d_sum.ensure(bins3));
-  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * n3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * n3, hipMemcpyHostToDevice));
-  if (offsets) {
-    HIP_TRY(d_off.ensure((size_t)n));
-    HIP_TRY(hipMemcpy(d_off.p, offsets, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  }
+  DevBuf<double> d_o, d_d, d_sum, d_sq;
+  DevBuf<int32_t> d_off;
+  if ((rc = upload(d_o, origins, n3)) != 0 || (rc = upload(d_d, directions, n3)) != 0) return rc;
+  if (offsets && (rc = upload(d_off, offsets, (size_t)n)) != 0) return rc;
+  HIP_TRY(d_sum.ensure(bins3));
   HIP_TRY(hipMemset(d_sum.p, 0, sizeof(double) * bins3));
   if (sq_out) {
     HIP_TRY(d_sq.ensure(bins3));
@@ -4617,209 +4394,8 @@ int32_t ptx_render_rays(ptx_scene* s, const ptx_rays_params* rp, int64_t n, cons
   }
   rc = ptx_render_rays_device(s, rp, n, d_o.p, d_d.p, offsets ? d_off.p : nullptr, d_sum.p, sq_out ? d_sq.p : nullptr, nullptr, stats);
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(sum_out, d_sum.p, sizeof(double) * bins3, hipMemcpyDeviceToHost));
-  if (sq_out) HIP_TRY(hipMemcpy(sq_out, d_sq.p, sizeof(double) * bins3, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int32_t ptx_intersect_rays(ptx_scene* s, int64_t n, const double* origins, const double* directions, double* t_out,
-                           int32_t* prim_out, ptx_stats* stats) {
-  if (!s || !origins || !directions || !t_out || !prim_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad ray count");
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    fill_tree_stats(s, stats);
-  }
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  Workspace w;
-  reschedule(s, 1);
-  int rc = ensure_workspace(s, (size_t)n, 1, &w, 0, true); /* this entry point hands the hit distances back: keep the records */
-  if (rc) return rc;
-  LocalBuf<double> d_o, d_d;
-  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3));
-  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  const uint32_t cnt = (uint32_t)n;
-  HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
-  HIP_TRY(hipMemcpy(w.counts, &cnt, sizeof cnt, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(s->counters.p, 0, sizeof(PtCounters)));
-  PtQueue q0 = w.q[0];
-  q0.count = w.counts;
-  hipLaunchKernelGGL(k_load_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, d_o.p, d_d.p, q0);
-  launch_trace(s, nullptr, q0, w.hits, (size_t)n, true, w.counts + kWorkBase, w.susp, kNoBounce);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int32_t> slot((size_t)n);
-  if (w.hits.tuv) { /* scenes with triangles keep {t, u, v, -} records (PtHits) */
-    std::vector<double> tuv((size_t)n * 4);
-    HIP_TRY(hipMemcpy(tuv.data(), w.hits.tuv, sizeof(double) * tuv.size(), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) t_out[i] = tuv[(size_t)i * 4];
-  } else {
-    HIP_TRY(hipMemcpy(t_out, w.hits.t, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  HIP_TRY(hipMemcpy(slot.data(), w.hits.slot, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) {
-    const int sl = slot[(size_t)i];
-    if (sl < 0) {
-      prim_out[i] = -1;
-      t_out[i] = 0.0;
-    } else {
-      prim_out[i] = s->host->slot_prim[(size_t)sl];
-    }
-  }
-  if (stats) {
-    rc = collect_counters(s, stats);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-namespace {
-/* k_walk_eval: 11 = on the shared image {assembly loop, divergent loop} x {plain, origin zero, tail cut}, on the per-octant image the
- * assembly loop x the same three, and the packet walk per leaf kind.  Template arguments: <MODE, PACKET, LOCT, ZERO, TAIL>. */
-using WalkKernel = decltype(&k_walk_eval<PT_MODE_SIMD, false, false, false, false>);
-WalkKernel walk_kernel(int walk, int mode) {
-  switch (walk) {
-    case PTX_WALK_SHARED_ASM: return k_walk_eval<PT_MODE_SIMD, false, false, false, false>;
-    case PTX_WALK_SHARED_ASM_ZERO: return k_walk_eval<PT_MODE_SIMD, false, false, true, false>;
-    case PTX_WALK_SHARED_ASM_TAIL: return k_walk_eval<PT_MODE_SIMD, false, false, false, true>;
-    case PTX_WALK_OCT_ASM: return k_walk_eval<PT_MODE_SIMD, false, true, false, false>;
-    case PTX_WALK_OCT_ASM_ZERO: return k_walk_eval<PT_MODE_SIMD, false, true, true, false>;
-    case PTX_WALK_OCT_ASM_TAIL: return k_walk_eval<PT_MODE_SIMD, false, true, false, true>;
-    case PTX_WALK_SHARED_DIV: return k_walk_eval<PT_MODE_ARRAY, false, false, false, false>;
-    case PTX_WALK_SHARED_DIV_ZERO: return k_walk_eval<PT_MODE_ARRAY, false, false, true, false>;
-    case PTX_WALK_SHARED_DIV_TAIL: return k_walk_eval<PT_MODE_ARRAY, false, false, false, true>;
-    case PTX_WALK_PACKET: return mode == PT_MODE_SIMD ? k_walk_eval<PT_MODE_SIMD, true, false, true, false> : k_walk_eval<PT_MODE_ARRAY, true, false, true, false>;
-    default: return nullptr;
-  }
-}
-}  // namespace
-
-int32_t ptx_walk_rays(ptx_scene* s, int32_t walk, int64_t n, const double* origins, const double* directions, double* t_out,
-                      int32_t* prim_out) {
-  if (!s || !origins || !directions || !t_out || !prim_out) return fail(PTX_ERR_ARG, "NULL argument");
-  if (walk < 0 || walk > PTX_WALK_SHARED_DIV_TAIL) return fail(PTX_ERR_ARG, "unknown walk %d", walk);
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad ray count");
-  HIP_TRY(hipSetDevice(s->device));
-  reschedule(s, 1);
-  const Schedule& sc = s->sched;
-  /* what the scene can take: the bounce kernels' own conditions (make_schedule), less the knobs that choose between possible walks */
-  const bool simd = s->dev.mode == PT_MODE_SIMD;
-  const bool oct = walk == PTX_WALK_OCT_ASM || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_OCT_ASM_TAIL;
-  const bool asm_shared = walk == PTX_WALK_SHARED_ASM || walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_SHARED_ASM_TAIL;
-  const bool div = walk == PTX_WALK_SHARED_DIV || walk == PTX_WALK_SHARED_DIV_ZERO || walk == PTX_WALK_SHARED_DIV_TAIL;
-  const bool zero = walk == PTX_WALK_PACKET || walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_SHARED_DIV_ZERO;
-  if (!sc.in_lds() || sc.from_hbm) return fail(PTX_ERR_STATE, "walk %d: the scene is walked from HBM / L2, these walks run on LDS-resident scenes", walk);
-  if ((oct || asm_shared) && !simd) return fail(PTX_ERR_STATE, "walk %d is a Simd_leaf walk and the scene is Array_leaf", walk);
-  if (div && simd) return fail(PTX_ERR_STATE, "walk %d is the Array_leaf walk and the scene is Simd_leaf", walk);
-  if (oct && (s->dev.lds_oct == nullptr || !sc.carry_oct.fits)) return fail(PTX_ERR_STATE, "walk %d: the scene has no per-octant LDS image, or a launch does not fit with it", walk);
-  if (!oct && !sc.carry.fits) return fail(PTX_ERR_STATE, "walk %d: a launch of the bounce kernel does not fit LDS with the scene's image", walk);
-  if (sc.bounce_threads > PT_BOUNCE_THREADS) return fail(PTX_ERR_STATE, "walk %d: workgroups of %d threads", walk, sc.bounce_threads);
-  if (zero) {
-    const double pz = 0.0;
-    for (int64_t k = 0; k < 3 * n; ++k)
-      if (std::memcmp(&origins[k], &pz, sizeof pz) != 0)
-        return fail(PTX_ERR_ARG, "walk %d takes the origin as (+0, +0, +0): component %lld of the origins is %a", walk, (long long)k, origins[k]);
-  }
-  if (n == 0) return 0;
-  LocalBuf<double> d_o, d_d, d_t;
-  LocalBuf<int32_t> d_s;
-  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3)); HIP_TRY(d_t.ensure((size_t)n)); HIP_TRY(d_s.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  const WalkKernel kern = walk_kernel(walk, s->dev.mode);
-  /* k_bounce_carry's launch: its workgroup, its dynamic LDS for this image, one workgroup (one scene image) per CU */
-  prepare_kernel(s, (const void*)kern, "k_walk_eval", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
-  const int threads = sc.bounce_threads;
-  const int grid = strided_grid(s, (size_t)n, threads, 1);
-  const int stack_depth = std::max(1, s->tree_depth + 1);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, nullptr, s->dev, (long long)n, d_o.p, d_d.p, d_t.p, d_s.p, stack_depth);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int32_t> slot((size_t)n);
-  HIP_TRY(hipMemcpy(t_out, d_t.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(slot.data(), d_s.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) {
-    const int sl = slot[(size_t)i];
-    if (sl < 0) {
-      prim_out[i] = -1;
-      t_out[i] = 0.0;
-    } else {
-      prim_out[i] = s->host->slot_prim[(size_t)sl];
-    }
-  }
-  return 0;
-}
-
-namespace {
-/* k_next_leaf_eval: 6 = the walks with a node loop of their own x {plain, origin zero}.  Template arguments: <MODE, LOCT, ZERO>. */
-using NextLeafKernel = decltype(&k_next_leaf_eval<PT_MODE_SIMD, false, false>);
-NextLeafKernel next_leaf_kernel(int walk) {
-  switch (walk) {
-    case PTX_WALK_SHARED_ASM: return k_next_leaf_eval<PT_MODE_SIMD, false, false>;
-    case PTX_WALK_SHARED_ASM_ZERO: return k_next_leaf_eval<PT_MODE_SIMD, false, true>;
-    case PTX_WALK_OCT_ASM: return k_next_leaf_eval<PT_MODE_SIMD, true, false>;
-    case PTX_WALK_OCT_ASM_ZERO: return k_next_leaf_eval<PT_MODE_SIMD, true, true>;
-    case PTX_WALK_SHARED_DIV: return k_next_leaf_eval<PT_MODE_ARRAY, false, false>;
-    case PTX_WALK_SHARED_DIV_ZERO: return k_next_leaf_eval<PT_MODE_ARRAY, false, true>;
-    default: return nullptr;
-  }
-}
-}  // namespace
-
-int32_t ptx_walk_next_leaf(ptx_scene* s, int32_t walk, int64_t n, const double* origins, const double* directions, const int32_t* nodes,
-                           const double* t_max, int32_t* leaf_out) {
-  if (!s || !origins || !directions || !nodes || !t_max || !leaf_out) return fail(PTX_ERR_ARG, "NULL argument");
-  const NextLeafKernel kern = next_leaf_kernel(walk);
-  if (!kern) return fail(PTX_ERR_ARG, "unknown walk %d (the walks with a node loop of their own: no PACKET, no _TAIL)", walk);
-  if (s->device < 0) return fail(PTX_ERR_STATE, "scene was created host-only (device -1): no CPU fallback exists");
-  if (n < 0 || n >= 0x7fffffffll) return fail(PTX_ERR_ARG, "bad triple count");
-  HIP_TRY(hipSetDevice(s->device));
-  reschedule(s, 1);
-  const Schedule& sc = s->sched;
-  /* what the scene can take: ptx_walk_rays' conditions */
-  const bool simd = s->dev.mode == PT_MODE_SIMD;
-  const bool oct = walk == PTX_WALK_OCT_ASM || walk == PTX_WALK_OCT_ASM_ZERO;
-  const bool div = walk == PTX_WALK_SHARED_DIV || walk == PTX_WALK_SHARED_DIV_ZERO;
-  const bool zero = walk == PTX_WALK_SHARED_ASM_ZERO || walk == PTX_WALK_OCT_ASM_ZERO || walk == PTX_WALK_SHARED_DIV_ZERO;
-  if (!sc.in_lds() || sc.from_hbm) return fail(PTX_ERR_STATE, "walk %d: the scene is walked from HBM / L2, these walks run on LDS-resident scenes", walk);
-  if (!div && !simd) return fail(PTX_ERR_STATE, "walk %d is a Simd_leaf walk and the scene is Array_leaf", walk);
-  if (div && simd) return fail(PTX_ERR_STATE, "walk %d is the Array_leaf walk and the scene is Simd_leaf", walk);
-  if (oct && (s->dev.lds_oct == nullptr || !sc.carry_oct.fits)) return fail(PTX_ERR_STATE, "walk %d: the scene has no per-octant LDS image, or a launch does not fit with it", walk);
-  if (!oct && !sc.carry.fits) return fail(PTX_ERR_STATE, "walk %d: a launch of the bounce kernel does not fit LDS with the scene's image", walk);
-  if (sc.bounce_threads > PT_BOUNCE_THREADS) return fail(PTX_ERR_STATE, "walk %d: workgroups of %d threads", walk, sc.bounce_threads);
-  if (zero) {
-    const double pz = 0.0;
-    for (int64_t k = 0; k < 3 * n; ++k)
-      if (std::memcmp(&origins[k], &pz, sizeof pz) != 0)
-        return fail(PTX_ERR_ARG, "walk %d takes the origin as (+0, +0, +0): component %lld of the origins is %a", walk, (long long)k, origins[k]);
-  }
-  const int64_t n_nodes = (int64_t)s->host->nodes.size();
-  for (int64_t k = 0; k < n; ++k) {
-    if (nodes[k] < 0 || (int64_t)nodes[k] >= n_nodes) return fail(PTX_ERR_ARG, "triple %lld: node %d is not one of the tree's %lld", (long long)k, nodes[k], (long long)n_nodes);
-    if (!(t_max[k] >= 0.0)) return fail(PTX_ERR_ARG, "triple %lld: t_max %a is NaN or negative", (long long)k, t_max[k]);
-  }
-  if (n == 0) return 0;
-  LocalBuf<double> d_o, d_d, d_t;
-  LocalBuf<int32_t> d_k, d_l;
-  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3)); HIP_TRY(d_t.ensure((size_t)n)); HIP_TRY(d_k.ensure((size_t)n)); HIP_TRY(d_l.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_o.p, origins, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_d.p, directions, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_t.p, t_max, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_k.p, nodes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  /* ptx_walk_rays' launch: k_bounce_carry's workgroup, its dynamic LDS for this image, one workgroup (one scene image) per CU */
-  prepare_kernel(s, (const void*)kern, "k_next_leaf_eval", !oct /* (record numbers, not 16-bit addresses) */, 160 * 1024 - 256, PT_LDS_CU_BYTES - PT_LDS_BOUNCE_LIMIT);
-  const int threads = sc.bounce_threads;
-  const int grid = strided_grid(s, (size_t)n, threads, 1);
-  const int stack_depth = std::max(1, s->tree_depth + 1);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), oct ? sc.carry_oct.total : sc.carry.total, nullptr, s->dev, (long long)n, d_o.p, d_d.p, d_k.p, d_t.p, d_l.p, stack_depth);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(leaf_out, d_l.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-  return 0;
+  if ((rc = download(sum_out, d_sum, bins3)) != 0) return rc;
+  return sq_out ? download(sq_out, d_sq, bins3) : 0;
 }
 
 int32_t ptx_kernel_table(char* names_out, int64_t capacity) {
@@ -4881,66 +4457,6 @@ int32_t ptx_scene_tree(const ptx_scene* s, double* bbox_out, int32_t* info_out, 
   if (prim_order_out)
     for (int i = 0; i < s->dev.n_slots && i < slot_capacity; ++i) prim_order_out[i] = s->host->slot_prim[(size_t)i];
   return n;
-}
-
-/* Debug / parity aid: the state of every path after ONE segment (generate + trace + shade of bounce 0):
- * alive_out[i] = 1 and ray_out[6i..] = (origin, direction), attn_out[3i..] when sample i scattered,
- * alive_out[i] = 0 when it terminated.  Not part of the rendering path. */
-int32_t ptx_debug_first_scatter(ptx_scene* s, const ptx_render_params* p, int64_t n, const int32_t* xs, const int32_t* ys,
-                                const int32_t* passes, double* ray_out, double* attn_out, int32_t* alive_out) {
-  if (!s || !xs || !ys || !passes || !ray_out || !attn_out || !alive_out) return fail(PTX_ERR_ARG, "NULL argument");
-  /* (before any device is touched: a host-only scene gets this answer too) */
-  if (s->projection != PTX_PROJECTION_PERSPECTIVE)
-    return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own pinhole: ptx_scene_set_camera_projection(scene, PTX_PROJECTION_PERSPECTIVE) first");
-  if (s->pose_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera pose off with ptx_scene_set_camera_pose(scene, NULL, NULL, NULL) first");
-  if (s->shutter_on) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the rays of the scene's own camera: switch the camera shutter off with ptx_scene_set_camera_shutter(scene, NULL, NULL, 0) first");
-  int rc = check_render_args(s, p, nullptr);
-  if (rc) return rc;
-  if (n <= 0 || p->max_bounces < 2) return fail(PTX_ERR_ARG, "need n > 0 and max_bounces >= 2");
-  if (s->lens_radius > 0.0) return fail(PTX_ERR_STATE, "ptx_debug_first_scatter traces the pinhole's rays: switch the lens off with ptx_scene_set_lens(scene, 0, f) first");
-  HIP_TRY(hipSetDevice(s->device));
-  RenderBusy busy(s);
-  Workspace w;
-  reschedule(s, 1);
-  rc = ensure_workspace(s, (size_t)n, p->max_bounces, &w);
-  if (rc) return rc;
-  LocalBuf<int32_t> dx, dy, dpp;
-  HIP_TRY(dx.ensure((size_t)n)); HIP_TRY(dy.ensure((size_t)n)); HIP_TRY(dpp.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(dx.p, xs, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dy.p, ys, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dpp.p, passes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(w.counts, 0, sizeof(uint32_t) * kCountsWords));
-  {
-    PtQueue q0 = w.q[0];
-    q0.count = w.counts;
-    launch_generate_list(s, p, PT_CAM_PINHOLE, n, dx.p, dy.p, dpp.p, q0); /* (every other kind was refused above) */
-  }
-  run_bounces(s, nullptr, w, (size_t)n, p->max_bounces, false, false, PrimaryLaunch(), 1);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  uint32_t cnt = 0;
-  HIP_TRY(hipMemcpy(&cnt, w.counts + 1, sizeof cnt, hipMemcpyDeviceToHost));
-  std::vector<PtRayRec> rays((size_t)cnt);
-  const size_t pstride = s->dev.has_emit ? 2 : 1; /* emissive scenes: {path, emission} pairs (PtQueue) */
-  std::vector<PtPathRec> paths((size_t)cnt * pstride);
-  HIP_TRY(hipMemcpy(rays.data(), w.q[1].ray, sizeof(PtRayRec) * cnt, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(paths.data(), w.q[1].path, sizeof(PtPathRec) * cnt * pstride, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) alive_out[i] = 0;
-  for (uint32_t j = 0; j < cnt; ++j) {
-    const PtRayRec& r = rays[j];
-    uint64_t dx_bits;
-    memcpy(&dx_bits, &r.dx, sizeof dx_bits);
-    if ((uint32_t)(dx_bits >> 32) == (uint32_t)PT_HOLE_HI) continue; /* an unused entry of a part-filled block (k_shade_pool) */
-    const PtPathRec& pr = paths[(size_t)j * pstride];
-    const uint32_t i = pr.id;
-    alive_out[i] = 1;
-    const double ray6[6] = {r.ox, r.oy, r.oz, r.dx, r.dy, r.dz};
-    for (int k = 0; k < 6; ++k) ray_out[6 * (size_t)i + k] = ray6[k];
-    attn_out[3 * (size_t)i] = pr.ar;
-    attn_out[3 * (size_t)i + 1] = pr.ag;
-    attn_out[3 * (size_t)i + 2] = pr.ab;
-  }
-  return 0;
 }
 
 /* ---------------------------------------------------------------- progressive photon mapping */
@@ -5016,13 +4532,13 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   const double inv_photon_count = 1.0 / (double)p->photon_count;
 
   const size_t cap = (size_t)total * (size_t)mb;
-  LocalBuf<double> d_out, d_pm, d_palpha, d_ealpha, d_img;
-  LocalBuf<uint8_t> d_ndep;
-  LocalBuf<PtLightDev> d_lights;
-  LocalBuf<int> d_first;
-  LocalBuf<unsigned long long> d_cnt;
-  LocalBuf<PtNode> d_nodes;
-  LocalBuf<int> d_tile, d_src;
+  DevBuf<double> d_out, d_pm, d_palpha, d_ealpha, d_img;
+  DevBuf<uint8_t> d_ndep;
+  DevBuf<PtLightDev> d_lights;
+  DevBuf<int> d_first;
+  DevBuf<unsigned long long> d_cnt;
+  DevBuf<PtNode> d_nodes;
+  DevBuf<int> d_tile, d_src;
   const bool host_list = getenv("PTX_PPM_HOST_LIST") != nullptr && atoi(getenv("PTX_PPM_HOST_LIST")) != 0;
   auto release = [] {}; /* the buffers free themselves on every exit path */
 #define PPM_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return fail(PTX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
@@ -5064,7 +4580,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
     {
       const int depth = std::max(1, s->tree_depth + 1);
       const size_t lds = (size_t)4 * depth * PT_WAVE * sizeof(uint32_t);
-      const dim3 gd((unsigned)((total + 255) / 256)), bd(256);
+      const dim3 gd(grid256(total)), bd(256);
       /* (a scene with an image texture: the IMG instantiations, as in a render) */
       const auto kern = s->dev.n_images != 0 ? (array_mode ? k_ppm_photons<PT_MODE_ARRAY, true> : k_ppm_photons<PT_MODE_SIMD, true>)
                                              : (array_mode ? k_ppm_photons<PT_MODE_ARRAY> : k_ppm_photons<PT_MODE_SIMD>);
@@ -5099,7 +4615,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
         if (bvh_build_device(bws.d_box.p, n_list, nullptr, 8, 8, false, &dt)) {
           n_slots = (size_t)dt.n_slots;
           PPM_TRY(d_pm.ensure(n_slots * 9));
-          hipLaunchKernelGGL(k_ppm_slots, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, nullptr, dt.slot_prim, d_src.p, (int)n_slots, d_out.p, cap, d_pm.p);
+          hipLaunchKernelGGL(k_ppm_slots, grid256(n_slots), dim3(256), 0, nullptr, dt.slot_prim, d_src.p, (int)n_slots, d_out.p, cap, d_pm.p);
           PPM_TRY(hipGetLastError());
           tree_depth = dt.depth;
           tree_nodes = dt.n_nodes;
@@ -5161,7 +4677,7 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
       const int depth = std::max(std::max(1, s->tree_depth + 1), tree_depth + 1);
       const size_t lds = (size_t)4 * depth * PT_WAVE * sizeof(uint32_t);
       if (lds > 160 * 1024) { release(); return fail(PTX_ERR_STATE, "photon tree too deep for the LDS stack"); }
-      const dim3 gd((unsigned)(((size_t)W * H + 255) / 256)), bd(256);
+      const dim3 gd(grid256((int64_t)W * H)), bd(256);
       const auto kern = s->dev.n_images != 0 ? (array_mode ? k_ppm_gather<PT_MODE_ARRAY, true> : k_ppm_gather<PT_MODE_SIMD, true>)
                                              : (array_mode ? k_ppm_gather<PT_MODE_ARRAY> : k_ppm_gather<PT_MODE_SIMD>);
       if (lds > 64 * 1024) raise_dynamic_lds_limit((const void*)kern, (int)(160 * 1024 - 1024)); /* the kernels also hold static words (chunk counters, the floor triangles) */
@@ -5186,63 +4702,6 @@ int32_t ptx_ppm_render(ptx_scene* s, const ptx_ppm_params* p, const ptx_light* l
   if (stats) *stats = st;
   release();
 #undef PPM_TRY
-  return 0;
-}
-
-int32_t ptx_lds_sample(int32_t device, int32_t dimension, int64_t n, const int32_t* offsets, const int32_t* dims, double* out) {
-  if (dimension < 1 || n < 0 || !offsets || !dims || !out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  for (int64_t i = 0; i < n; ++i)
-    if (dims[i] < 0 || dims[i] >= dimension) return fail(PTX_ERR_ARG, "dimension index out of range");
-  HIP_TRY(hipSetDevice(device));
-  const std::vector<double> alpha = lds_alpha(dimension);
-  LocalBuf<double> d_alpha, d_out;
-  LocalBuf<int32_t> d_off, d_dim;
-  HIP_TRY(d_alpha.ensure((size_t)dimension)); HIP_TRY(d_out.ensure((size_t)n));
-  HIP_TRY(d_off.ensure((size_t)n)); HIP_TRY(d_dim.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_alpha.p, alpha.data(), sizeof(double) * (size_t)dimension, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off.p, offsets, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_dim.p, dims, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_lds_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_alpha.p, (long long)n, d_off.p, d_dim.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-#if PT_FILTER_DEBUG
-/* diagnostic builds only (kernels.hip, k_filter_error; tools/filter_error_study.py) -- not declared in include/ptx.h, not in the product */
-int32_t ptx_debug_filter_error(ptx_scene* s, int64_t n, const double* o3, const double* d3, const int32_t* nodes, const double* tmax, double* out6) {
-  if (!s || n < 0 || !o3 || !d3 || !nodes || !tmax || !out6) return fail(PTX_ERR_ARG, "bad argument");
-  if (s->device < 0 || !s->dev.nodes32o) return fail(PTX_ERR_ARG, "needs a scene on a device with the per-octant node image");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(s->device));
-  LocalBuf<double> d_o, d_d, d_t, d_out;
-  LocalBuf<int32_t> d_n;
-  HIP_TRY(d_o.ensure((size_t)n * 3)); HIP_TRY(d_d.ensure((size_t)n * 3)); HIP_TRY(d_t.ensure((size_t)n)); HIP_TRY(d_out.ensure((size_t)n * 6)); HIP_TRY(d_n.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_o.p, o3, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_d.p, d3, sizeof(double) * (size_t)n * 3, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_t.p, tmax, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_n.p, nodes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_filter_error, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev, (long long)n, d_o.p, d_d.p, d_n.p, d_t.p, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out6, d_out.p, sizeof(double) * (size_t)n * 6, hipMemcpyDeviceToHost));
-  return 0;
-}
-#endif
-int32_t ptx_math_eval(int32_t device, int32_t fn, int64_t n, const double* a, const double* b, double* out) {
-  if (fn < 0 || fn > 14 || n < 0 || !a || !out) return fail(PTX_ERR_ARG, "bad argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(device));
-  LocalBuf<double> d_a, d_b, d_out;
-  HIP_TRY(d_a.ensure((size_t)n)); HIP_TRY(d_out.ensure((size_t)n));
-  HIP_TRY(hipMemcpy(d_a.p, a, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  if (b) {
-    HIP_TRY(d_b.ensure((size_t)n));
-    HIP_TRY(hipMemcpy(d_b.p, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  }
-  hipLaunchKernelGGL(k_math_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, fn, (long long)n, d_a.p, b ? d_b.p : nullptr, d_out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
